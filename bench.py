@@ -2,6 +2,12 @@
 """Benchmark of the pairwise-LD hot path on MI355X: SNP-pairs/s producing r^2 + D'.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--snps S] [--haps H] [--fmt k16|ld32] [--path fp4|mfma|popcount]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps once and prints the result line (and, with --dump-outputs, writes what
+the last timed step computed).  Everything else moves behind --full: the from-idle figure, the seven timed regions, the
+cell-for-cell check of the timed output, the other kernel paths and workloads, the one-GPU leg at N > 1 and the CPU
+baseline.
 
 One "step" = one full pass of the hot path over one synthetic panel that is already resident in HBM as packed slab
 shards: (N > 1: all-gather of the shards over RCCL) -> ld_triangle kernel over this rank's share of the pass list ->
@@ -18,16 +24,21 @@ itself, as a CHILD process and before this process has touched the GPU, relays r
 if the child fails or overruns --deadline; under torch.distributed.run (RANK / WORLD_SIZE set) it runs as a rank.
 
 Timing: W warm-up steps, then --settle-steps more untimed steps (the shader clock needs tens of ms of load to settle;
-reported as config.settle_steps, and the from-idle figure is reported beside it as cold_ms_per_step), then EXACTLY K
-steps between barrier + synchronize on both sides, max over ranks.  At N = 1 the K steps are replayed as one HIP graph
-(eager with --no-graph; a failed capture falls back to eager): a 0.13 ms kernel is launch-bound otherwise.  At N > 1 a
+reported as config.settle_steps; with --full the from-idle figure is reported beside it as cold_ms_per_step), then
+EXACTLY K steps between barrier + synchronize on both sides, max over ranks (with --full: --repeats such regions).
+At N = 1 the K steps are replayed as one HIP graph (eager with --no-graph; a failed capture falls back to eager): a
+0.13 ms kernel is launch-bound otherwise.  At N > 1 a
 step is milliseconds and the launches are eager unless --graph-dist asks for a captured RCCL exchange; a failed child
 run is repeated once in the plainest mode (eager, exchange not overlapped).  The output is poisoned before the timed
-region and compared bit for bit with a separately computed result after it.
+region; with --full it is compared bit for bit with a separately computed result after it.
 
 Prints ONE JSON line on rank 0: whole-job pairs/s, ms per step, the roofline object of the dominant kernel (HIP events
-on the launch stream, live), at N = 1 the other two kernel paths on the same workload (int8 MFMA, AND+popcount) and the
-CPU baseline (the pure-Python restatement of the reference's list/zip/count algorithm, 1 core, bounded sample).
+on the launch stream, live); with --full, at N = 1 the other two kernel paths on the same workload (int8 MFMA,
+AND+popcount) and the CPU baseline (the pure-Python restatement of the reference's list/zip/count algorithm, 1 core,
+bounded sample).
+
+--dump-outputs DIR writes, after the timed steps, the r2 and D' values the timed path returned in its last step for a
+fixed, seeded sample of pairs (dump_outputs below); the panel is the same on every run with the same arguments.
 """
 from __future__ import annotations
 
@@ -55,16 +66,23 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=7,
-                    help="timed regions of --steps steps each; the line reports the median region (and all of them)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the from-idle figure, --repeats timed "
+                         "regions, the cell-for-cell check of the timed output, the other kernel paths and workloads "
+                         "(N = 1), the one-GPU leg (N > 1) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; the line reports the median region (and all of them) "
+                         "(default: 1, with --full 7)")
     ap.add_argument("--snps", type=int, default=0, help="panel size (default: 10 000 at N = 1, 100 000 at N > 1)")
     ap.add_argument("--haps", type=int, default=5008)
     ap.add_argument("--fmt", default="k16", choices=("k16", "ld32"),
                     help="result cells: k16 = 4 bytes per pair (two uint16 k = value * 10^4, lossless), ld32 = 8 bytes (two float32)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="N = 1: skip the int8 / popcount / other-format legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extra-legs", action="store_true", help="--full, N = 1: skip the int8 / popcount / other-format legs")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="N = 1: skip BASELINE configs[4] (50 000 x 1008 triangle), configs[2] (100 000-SNP ld_area) and the "
+                    help="--full, N = 1: skip BASELINE configs[4] (50 000 x 1008 triangle), configs[2] (100 000-SNP ld_area) and the "
                          "pack / host-to-device timings that follow the headline")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--force-dist", action="store_true", help="run the sharded path (process group + all-gather) even at world 1")
@@ -95,8 +113,13 @@ def parse(argv=None):
                     help="test hook: one cell of the configs[4] leg of other_workloads is flipped before its check (the run "
                          "must end with exit code 97 and no throughput line: tests/test_gpu_dist.py)")
     ap.add_argument("--no-single-gpu-leg", action="store_true",
-                    help="N > 1: skip timing the whole workload on rank 0 alone (the strong-scaling reference)")
-    return ap.parse_args(argv)
+                    help="--full, N > 1: skip timing the whole workload on rank 0 alone (the strong-scaling reference)")
+    args = ap.parse_args(argv)
+    if (args.debug_corrupt_result or args.debug_corrupt_other) and not args.full:
+        ap.error("the --debug-corrupt-* hooks test checks that only --full runs")
+    if args.repeats is None:
+        args.repeats = 7 if args.full else 1
+    return args
 
 
 # ------------------------------------------------------------------------------------------ launcher (no GPU use)
@@ -189,6 +212,48 @@ def launch_ranks(args, argv) -> int:
         pass
     print(line, flush=True)
     return rc
+
+
+# ------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_PAIRS = 1 << 20        # pairs sampled at most: 40 MB of .npy files
+DUMP_SEED = 20250611
+
+
+def dump_outputs(res, n_snps, out_dir):
+    """Write what a caller of ld_triangle receives from the timed path's last step, decoded as TriangleResult.k_and_int0
+    decodes it, for a fixed sample of pairs (every pair when there are at most DUMP_PAIRS; otherwise DUMP_PAIRS draws of a
+    numpy Generator seeded with DUMP_SEED, duplicates dropped, in pair order).  At N > 1 the sample is this rank's share.
+
+      pairs.npy     float64 [m, 2]  (row, col), row > col: var_1, var_2 of the pair
+      r_square.npy  float64 [m]     round(r2, 4) as the cell holds it; NaN for an escape cell
+      d_prime.npy   float64 [m]     round(D', 4) likewise
+      int0.npy      float32 [m, 2]  1 where the value is the reference's int 0 (r2, D')
+    """
+    import numpy as np
+
+    n_pairs = n_snps * (n_snps - 1) // 2
+    if n_pairs <= DUMP_PAIRS:
+        p = np.arange(n_pairs, dtype=np.int64)
+    else:
+        p = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n_pairs, size=DUMP_PAIRS, dtype=np.int64))
+    # pair index p = row * (row - 1) / 2 + col, col < row (the order of `for row: for col < row`)
+    rows = np.floor((1.0 + np.sqrt(1.0 + 8.0 * p.astype(np.float64))) / 2.0).astype(np.int64)
+    rows -= rows * (rows - 1) // 2 > p
+    rows += (rows + 1) * rows // 2 <= p
+    cols = p - rows * (rows - 1) // 2
+    assert np.all((cols >= 0) & (cols < rows))
+    idx = res.cell_index(rows, cols) if p.size else np.zeros(0, np.int64)
+    mine = (idx >= 0) & (idx < res.cells.shape[0])
+    rows, cols, idx = rows[mine], cols[mine], idx[mine]
+    k, int0, esc = res.k_and_int0(idx)
+    vals = np.where(esc, np.nan, k / 1e4)
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "pairs.npy", np.stack([rows, cols], axis=1).astype(np.float64))
+    np.save(d / "r_square.npy", vals[:, 0].astype(np.float64))
+    np.save(d / "d_prime.npy", vals[:, 1].astype(np.float64))
+    np.save(d / "int0.npy", int0.astype(np.float32))
+    return int(rows.size)
 
 
 # ------------------------------------------------------------------------------------------ CPU baseline
@@ -600,10 +665,22 @@ def run_rank(args):
         fence()
         return time.perf_counter() - t0, a.elapsed_time(c)
 
-    run_steps(args.warmup)
-    fence()
-    # from-idle figure: the K steps right after the warm-up, before any clock settling (what a short job sees)
-    cold_dt, _ = timed_region(lambda: run_steps(args.steps))
+    cold_dt = None
+    if args.full:
+        run_steps(args.warmup)
+        fence()
+        # from-idle figure: the K steps right after the warm-up, before any clock settling (what a short job sees)
+        cold_dt, _ = timed_region(lambda: run_steps(args.steps))
+        step_s = cold_dt / args.steps
+    else:
+        # A plain run times nothing but its K steps: the warm-up's own pace sizes the settling load below.  Its first step
+        # (code-object load, output allocation; run even at --warmup 0, capture needs the output) is left out of that.
+        run_steps(1)
+        fence()
+        t0 = time.perf_counter()
+        run_steps(args.warmup - 1)
+        fence()
+        step_s = (time.perf_counter() - t0) / (args.warmup - 1) if args.warmup > 1 else None
     # The K steps are K back-to-back launches of a ~0.15 ms kernel (plus, for N > 1, the exchange's all-gather and a
     # handful of small copies): a launch-bound inner loop, captured once into a HIP graph and replayed inside the
     # timed region; any failure to capture falls back to eager launches.
@@ -626,7 +703,12 @@ def run_rank(args):
     # the shader clock takes to settle under load.  A step COUNT, so every rank issues the same collectives.
     settle = args.settle_steps
     if settle < 0:
-        settle = max(args.steps, int(0.15 / max(cold_dt / args.steps, 1e-6)))
+        if step_s is None:
+            settle = args.steps
+        else:
+            settle = int(0.15 / max(step_s, 1e-6))
+            if args.full:
+                settle = max(args.steps, settle)
         settle = min(settle, 2000)
         if use_dist:                        # every rank must run the same number of collectives
             t = torch.tensor([settle], dtype=torch.int64, device=dev)
@@ -635,16 +717,19 @@ def run_rank(args):
     settle_done = 0
     if settle > 0:
         if graph is not None:
-            for _ in range((settle + args.steps - 1) // args.steps):
+            # a plain run counts the graph's untimed replay above (K steps of load) towards the settling load
+            todo = settle - (0 if args.full else args.steps)
+            for _ in range(max(0, todo + args.steps - 1) // args.steps):
                 graph.replay()
                 settle_done += args.steps
         else:
             run_steps(settle)
             settle_done = settle
     if out is not None:
-        out.cells.fill_(-1)                # the timed steps must produce every result again (checked below)
+        out.cells.fill_(-1)                # the timed steps must produce every result again (--full checks it below)
     # "3 warm-ups, 10 timed, report median and min".  The timed region -- EXACTLY K steps between barrier +
-    # synchronize on both sides -- is repeated R = 7 times (the same graph; the output was poisoned once, before the first);
+    # synchronize on both sides -- runs once in a plain run; with --full it is repeated R = 7 times (the same graph; the
+    # output was poisoned once, before the first);
     # `ms_per_step`, `value` and `roofline.frac` come from the MEDIAN region, all R are printed (ms_per_step_runs) with their
     # minimum beside them: one 2.5-ms region on a pool whose boxes differ by 8 % is not a measurement.
     repeats = max(1, args.repeats)
@@ -672,21 +757,26 @@ def run_rank(args):
     dt = per_region[mid]
     dt_min = per_region[order[0]]
     kern_ms = runs[mid][1]
-    cold_dt, _ = allmax(cold_dt)
+    if cold_dt is not None:
+        cold_dt, _ = allmax(cold_dt)
     kern_ms_max, kern_ms_min = allmax(kern_ms)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, n_snps, args.dump_outputs)
 
     # the output of the timed region against a separately computed result -- by the INDEPENDENT kernel (AND + popcount counts,
     # fp64 epilogue; the FP4 kernel when popcount itself is timed): nothing was skipped, left stale, or computed wrongly
     check_path = "popcount" if path != "popcount" else "fp4"
-    check = ld_triangle(panel, unit_range=(u0, u1), fmt=fmt, path=check_path)
-    torch.cuda.synchronize()
-    if args.debug_corrupt_result and rank == 0:
-        out.cells.view(torch.int32).view(-1)[12345] ^= 1
-    if not torch.equal(check.cells.view(torch.int32), out.cells.view(torch.int32)):
-        print("bench.py: the timed steps did not reproduce the triangle (stale or skipped work)", file=sys.stderr, flush=True)
-        print(f"{VERIFY_MARK} rank {rank}", flush=True)
-        os._exit(RC_VERIFY)     # a distinct code the launcher propagates and never retries
-    del check
+    if args.full:
+        check = ld_triangle(panel, unit_range=(u0, u1), fmt=fmt, path=check_path)
+        torch.cuda.synchronize()
+        if args.debug_corrupt_result and rank == 0:
+            out.cells.view(torch.int32).view(-1)[12345] ^= 1
+        if not torch.equal(check.cells.view(torch.int32), out.cells.view(torch.int32)):
+            print("bench.py: the timed steps did not reproduce the triangle (stale or skipped work)", file=sys.stderr,
+                  flush=True)
+            print(f"{VERIFY_MARK} rank {rank}", flush=True)
+            os._exit(RC_VERIFY)     # a distinct code the launcher propagates and never retries
+        del check
 
     value = n_pairs * args.steps / dt
     # which devices did the ranks really run on?  (uuid where the runtime has one, else the PCI address)
@@ -761,7 +851,6 @@ def run_rank(args):
         "ms_per_step_runs": [x / args.steps * 1e3 for x in per_region],   # every timed region of K steps, in run order
         "timing": f"{repeats} timed regions of {args.steps} steps each (barrier + synchronize on both sides, max over ranks "
                   "per region); ms_per_step / value / roofline.frac from the median region",
-        "cold_ms_per_step": cold_dt / args.steps * 1e3,     # the same K steps from idle clocks, eager launches
         "higher_is_better": True,
         "scaling": "strong",
         "vs_baseline": None,
@@ -775,7 +864,8 @@ def run_rank(args):
                                    "mfma": "int8 MFMA counts + fp64 epilogue",
                                    "popcount": "AND+popcount counts + fp64 epilogue"}[path],
                    "launch": (("HIP graph of the K steps" if graph is not None else "eager launches") +
-                              f"; every cell of the timed region's output verified against the {check_path} kernel"),
+                              (f"; every cell of the timed region's output verified against the {check_path} kernel"
+                               if args.full else "; output not verified in this run (bench.py --full checks every cell)")),
                    "settle_steps": settle_done,   # untimed, beyond --warmup: the timed region starts at sustained clocks
                    "sharding": "none" if world == 1 else f"row-block shards, all-gather, pass list / {world}",
                    # ranks that met over RCCL (null when the group is not an RCCL group: gloo rehearsals, no group at N = 1)
@@ -790,6 +880,8 @@ def run_rank(args):
         "roofline": roofline,
         "roofline_hbm": hbm,      # the metric's "% HBM roofline": result bytes + one read of the packed plane
     }
+    if cold_dt is not None:     # --full: the same K steps from idle clocks, eager launches
+        line["cold_ms_per_step"] = cold_dt / args.steps * 1e3
     if path == "popcount":   # the popcount path is bound by the integer VALU, not by HBM
         line["roofline_valu"] = {"bound": "valu-int", "achieved": lane_ops / kern_s / 1e12, "peak": VALU_PEAK_TLANEOPS,
                                  "unit": "T lane-ops/s", "frac": lane_ops / kern_s / 1e12 / VALU_PEAK_TLANEOPS,
@@ -837,7 +929,7 @@ def run_rank(args):
             o["frac_of_pipe_peak"] = alg_ops / (ms * 1e-3) / 1e12 / (MFMA_FP4_PEAK_TOPS if leg_path == "fp4" else MFMA_I8_PEAK_TOPS)
         return o
 
-    if world == 1 and not use_dist and not args.no_extra_legs:
+    if args.full and world == 1 and not use_dist and not args.no_extra_legs:
         # north_star: "MFMA only if ... proves faster than the popcount path" -- all three on the driver-run record
         reps = max(10, min(args.steps, 100))
         other = "ld32" if fmt == "k16" else "k16"
@@ -916,7 +1008,7 @@ def run_rank(args):
             del outs
         except Exception as exc:   # noqa: BLE001  (an extra)
             line["other_paths"]["two_streams"] = {"error": f"{type(exc).__name__}: {exc}"}
-    if world == 1 and not use_dist and not args.no_other_workloads:
+    if args.full and world == 1 and not use_dist and not args.no_other_workloads:
         line["other_workloads"] = other_workloads(torch, dev, fmt, codes_local, args.other_scale, args.debug_corrupt_other)
     # every extra leg that compares two results is held to the headline's rule: a mismatch is a wrong RESULT -- no
     # throughput line, exit code RC_VERIFY
@@ -926,7 +1018,7 @@ def run_rank(args):
         print(f"bench.py: {bad} did not reproduce the independently computed result", file=sys.stderr, flush=True)
         print(f"{VERIFY_MARK} rank {rank} {bad}", flush=True)
         os._exit(RC_VERIFY)
-    if world > 1 and not args.no_single_gpu_leg:
+    if args.full and world > 1 and not args.no_single_gpu_leg:
         # strong-scaling reference: the WHOLE workload on rank 0's GPU alone, a few steps (the other ranks wait)
         single = None
         if rank == 0:
@@ -949,7 +1041,7 @@ def run_rank(args):
             line["config"]["single_gpu_same_workload"] = single
             if single and "pairs_per_s" in single:
                 line["config"]["speedup_over_one_gpu"] = value / single["pairs_per_s"]
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         need = max(args.cpu_sample_snps, 1536)
         host = codes_local[:need].cpu().numpy()
         line["cpu_baseline"] = cpu_baseline(host, args.cpu_sample_snps)

@@ -142,3 +142,58 @@ def test_bench_launcher_ends_the_whole_process_group_at_the_deadline():
     for pid in pids:
         alive = psutil.pid_exists(pid) and psutil.Process(pid).status() != psutil.STATUS_ZOMBIE
         assert not alive, f"rank process {pid} survived the launcher"
+
+
+def test_bench_plain_run_options():
+    """A plain run times ONE region of --steps steps; --full restores the seven regions and the checks, and the hooks that
+    test those checks refuse to run without it."""
+    import pytest
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    plain, full = bench.parse(["--steps", "9"]), bench.parse(["--steps", "9", "--full"])
+    assert (plain.full, plain.repeats, plain.dump_outputs) == (False, 1, None)
+    assert (full.full, full.repeats) == (True, 7)
+    assert bench.parse(["--repeats", "3"]).repeats == 3 and bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+    for hook in ("--debug-corrupt-result", "--debug-corrupt-other"):
+        with pytest.raises(SystemExit):
+            bench.parse([hook])
+        assert getattr(bench.parse([hook, "--full"]), hook[2:].replace("-", "_"))
+
+
+def test_bench_dump_outputs_decodes_a_fixed_sample(tmp_path):
+    """bench.dump_outputs on a k16 result held on the host: every pair of a small triangle, a fixed seeded sample of a
+    large one (the same on every call), each pair's cell decoded as TriangleResult.k_and_int0 decodes it."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+    from ld_tools_amd._lib import K16_INT0, UNIT_PAIRS, lib
+    from ld_tools_amd.ops import TriangleResult
+
+    for n, want in ((300, 300 * 299 // 2), (2000, None)):
+        units = lib.ldx_triangle_units(n)
+        k = np.random.default_rng(n).integers(0, 10001, size=(units * UNIT_PAIRS, 2)).astype(np.uint16)
+        k[::97, 1] = K16_INT0
+        res = TriangleResult(n, 0, units, k16=torch.from_numpy(k.view(np.int16)))
+        m = bench.dump_outputs(res, n, tmp_path / "a")
+        assert bench.dump_outputs(res, n, tmp_path / "b") == m
+        got = {f: np.load(tmp_path / "a" / f) for f in ("pairs.npy", "r_square.npy", "d_prime.npy", "int0.npy")}
+        for f, a in got.items():
+            assert np.array_equal(a, np.load(tmp_path / "b" / f)) and a.dtype in (np.float32, np.float64)
+        pairs = got["pairs.npy"].astype(np.int64)
+        if want is not None:
+            assert m == want
+        else:
+            assert 0.75 * bench.DUMP_PAIRS < m <= bench.DUMP_PAIRS     # draws with replacement, duplicates dropped
+        assert pairs.shape == (m, 2) and np.all(pairs[:, 0] > pairs[:, 1]) and np.all(pairs[:, 0] < n)
+        p = pairs[:, 0] * (pairs[:, 0] - 1) // 2 + pairs[:, 1]
+        assert np.all(np.diff(p) > 0)
+        idx = res.cell_index(pairs[:, 0], pairs[:, 1])
+        assert np.array_equal(got["int0.npy"][:, 1], (k[idx, 1] == K16_INT0).astype(np.float32))
+        assert np.array_equal(got["r_square.npy"], k[idx, 0] / 1e4)
+        assert np.array_equal(got["d_prime.npy"], np.where(k[idx, 1] == K16_INT0, 0, k[idx, 1]) / 1e4)
+        total = sum((tmp_path / "a" / f).stat().st_size for f in got)
+        assert total <= 64 << 20

@@ -36,7 +36,7 @@ def test_bench_launches_its_own_ranks():
     env.pop("RANK", None)
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--snps", "3000",
-                        "--backend", "gloo", "--settle-steps", "0", "--deadline", "400"], capture_output=True, text=True,
+                        "--backend", "gloo", "--settle-steps", "0", "--deadline", "400", "--full"], capture_output=True, text=True,
                        timeout=500, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -68,7 +68,7 @@ def test_bench_never_retries_a_wrong_result():
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--snps", "2000",
                         "--backend", "gloo", "--settle-steps", "0", "--deadline", "400", "--no-single-gpu-leg",
-                        "--debug-corrupt-result"], capture_output=True, text=True, timeout=500, env=env, cwd=str(ROOT))
+                        "--debug-corrupt-result", "--full"], capture_output=True, text=True, timeout=500, env=env, cwd=str(ROOT))
     assert r.returncode == 97, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
     assert not any(ln.startswith("{") and '"metric"' in ln for ln in r.stdout.splitlines())
     assert "NOT retried" in r.stderr and "once more in the plainest mode" not in r.stderr
@@ -79,7 +79,7 @@ def _bench_n1(extra):
     env.pop("RANK", None)
     env.pop("WORLD_SIZE", None)
     return subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--snps", "2000",
-                           "--settle-steps", "0", "--no-cpu-baseline", "--other-scale", "small"] + extra,
+                           "--settle-steps", "0", "--no-cpu-baseline", "--other-scale", "small", "--full"] + extra,
                           capture_output=True, text=True, timeout=500, env=env, cwd=str(ROOT))
 
 
@@ -132,7 +132,7 @@ def test_bench_four_ranks_one_card_configs3():
     env.pop("RANK", None)
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--backend", "gloo",
-                        "--settle-steps", "2", "--deadline", "800"], capture_output=True, text=True, timeout=900, env=env,
+                        "--settle-steps", "2", "--deadline", "800", "--full"], capture_output=True, text=True, timeout=900, env=env,
                        cwd=str(ROOT))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -166,7 +166,7 @@ def test_bench_one_rank_rccl_group():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--force-dist", "--steps", "3", "--warmup", "1", "--snps", "6000",
-                        "--settle-steps", "2", "--no-cpu-baseline", "--no-other-workloads", "--no-extra-legs"],
+                        "--settle-steps", "2", "--no-cpu-baseline", "--no-other-workloads", "--no-extra-legs", "--full"],
                        capture_output=True, text=True, timeout=500, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -175,3 +175,36 @@ def test_bench_one_rank_rccl_group():
     assert cfg["workload"] == "ld_triangle 6000x5008" and "popcount kernel" in cfg["launch"]
     assert len(rec["ms_per_step_runs"]) == 7 and rec["ms_per_step_min"] <= rec["ms_per_step"]
     assert len(rec["per_rank"]) == 1 and rec["per_rank"][0]["pairs"] == 6000 * 5999 // 2 and rec["per_rank"][0]["kernel_ms"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times its K steps once and prints the headline only; --dump-outputs writes what the last
+    timed step returned.  The same arguments give the same panel, so the FP4 kernel's dump and the popcount kernel's are
+    equal value for value -- every pair of the 1 200-SNP triangle (fewer than bench.DUMP_PAIRS)."""
+    import json
+
+    import numpy as np
+
+    env = dict(os.environ, OMP_NUM_THREADS="1")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    for path in ("fp4", "popcount"):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "5", "--warmup", "2", "--snps", "1200",
+                            "--path", path, "--dump-outputs", str(tmp_path / path)],
+                           capture_output=True, text=True, timeout=300, env=env, cwd=str(ROOT))
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert rec["steps"] == 5 and len(rec["ms_per_step_runs"]) == 1 and rec["ms_per_step"] == rec["ms_per_step_runs"][0] > 0
+        assert rec["value"] > 0 and rec["higher_is_better"] is True and rec["config"]["workload"] == "ld_triangle 1200x5008"
+        for key in ("cold_ms_per_step", "other_paths", "other_workloads", "cpu_baseline"):
+            assert key not in rec, key
+    names = sorted(f.name for f in (tmp_path / "fp4").iterdir())
+    assert names == ["d_prime.npy", "int0.npy", "pairs.npy", "r_square.npy"]
+    for name in names:
+        a, b = np.load(tmp_path / "fp4" / name), np.load(tmp_path / "popcount" / name)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b, equal_nan=True), name
+    pairs = np.load(tmp_path / "fp4" / "pairs.npy")
+    assert pairs.shape == (1200 * 1199 // 2, 2) and np.all(pairs[:, 0] > pairs[:, 1])
+    r2 = np.load(tmp_path / "fp4" / "r_square.npy")
+    assert np.all((r2 >= 0) & (r2 <= 1)) and np.count_nonzero(r2) > 0

@@ -211,38 +211,44 @@ def test_oracles_area_driver(drivers, panel_codes):
 
 
 # ------------------------------------------------------------------ the pin's own recipe
-REFERENCE_CALC_LD = "/root/reference/backend/calc_ld.py"
 GOLDEN_FILES = ("kat_counts.json", "small_n.npz", "panels.npz", "drivers.json", "driver_text.json")
 
 
-@pytest.mark.skipif(not __import__("os").path.isfile(REFERENCE_CALC_LD),
-                    reason="the reference exists in the build container only")
-def test_golden_generators_load_the_reference_and_reproduce_the_fixtures(tmp_path):
-    """Regenerate every fixture from the REAL reference into a temp dir and byte-compare with tests/golden/.
-
-    Guards against (i) the generators resolving ``backend.calc_ld`` to this repo's own top-level ``backend/``
-    package (the GPU drop-in) instead of /root/reference/backend/calc_ld.py:3-99 -- which would make the golden
-    vectors circular -- and (ii) committed fixtures that are not what the committed scripts produce.
-    """
-    import subprocess
+def test_golden_generators_load_calc_ld_by_path(tmp_path, monkeypatch):
+    """The generators (tests/golden/make_golden*.py, run by hand where the reference's source tree is) must take calc_ld
+    from the reference BY FILE PATH: with this repo's own top-level ``backend/`` package (the GPU drop-in) on sys.path, an
+    ``import backend.calc_ld`` would resolve to the product and make the golden vectors circular.  Checked here without the
+    reference: both scripts go through ``_reference.load_reference_calc_ld()`` and import no ``backend``; the loader
+    accepts a calc_ld defined under its root and refuses the product's drop-in; the fixtures it writes are byte-stable."""
     import sys
     from pathlib import Path
 
     golden = Path(__file__).resolve().parent / "golden"
+    for name in GOLDEN_FILES:
+        assert (golden / name).stat().st_size > 0, name
+    for script in ("make_golden.py", "make_golden_drivers.py"):
+        text = (golden / script).read_text()
+        assert "load_reference_calc_ld()" in text, script
+        assert "from backend" not in text and "import backend" not in text, script
     sys.path.insert(0, str(golden))
     try:
         import _reference
     finally:
         sys.path.remove(str(golden))
+    stand_in = tmp_path / "ref"
+    (stand_in / "backend").mkdir(parents=True)
+    (stand_in / "backend" / "calc_ld.py").write_text("def calc_ld(a, b):\n    return {'r_square': 0, 'd_prime': 0}\n")
+    monkeypatch.setattr(_reference, "REFERENCE_ROOT", stand_in)
+    monkeypatch.setattr(_reference, "REFERENCE_CALC_LD", stand_in / "backend" / "calc_ld.py")
     fn = _reference.load_reference_calc_ld()
-    assert fn.__code__.co_filename == REFERENCE_CALC_LD
-    for script in ("make_golden.py", "make_golden_drivers.py"):
-        text = (golden / script).read_text()
-        assert "load_reference_calc_ld()" in text and "from backend" not in text, script
-        subprocess.run([sys.executable, str(golden / script), "--out", str(tmp_path)], check=True,
-                       stdout=subprocess.DEVNULL, timeout=600)
-    for name in GOLDEN_FILES:
-        assert (tmp_path / name).read_bytes() == (golden / name).read_bytes(), f"{name}: regen differs"
+    assert fn.__code__.co_filename == str(stand_in / "backend" / "calc_ld.py")
+    monkeypatch.setattr(_reference, "REFERENCE_CALC_LD", golden.parent.parent / "backend" / "calc_ld.py")
+    with pytest.raises(AssertionError, match="not from the reference"):
+        _reference.load_reference_calc_ld()
+    arrays = {"b": np.arange(7, dtype=np.int64), "a": np.linspace(0, 1, 5)}
+    _reference.save_npz(tmp_path / "x.npz", **arrays)
+    _reference.save_npz(tmp_path / "y.npz", **arrays)
+    assert (tmp_path / "x.npz").read_bytes() == (tmp_path / "y.npz").read_bytes()
 
 
 def test_degenerate_snps_give_int_zero_against_any_snp():

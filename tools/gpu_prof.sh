@@ -12,7 +12,7 @@
 #         is busy.  A counter the device refuses fails its pass; the log says which (bench_pmc_<pass>.log).
 set -u
 TAG=${1:-r02}; shift || true
-ARGS=${*:---steps 20 --warmup 3 --no-cpu-baseline}
+ARGS=${*:---steps 20 --warmup 3 --full --no-cpu-baseline}
 CMD=${PROG:-bench.py $ARGS}
 PASSES=${PASSES:-trace fetch write sq sq2 sq3 sq4}
 export TMPDIR=/tmp
