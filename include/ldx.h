@@ -49,7 +49,7 @@ extern "C" {
  * each).  Inside a row the order follows what ONE lane of the matrix kernel holds -- a 32 x 32 MFMA tile puts column l
  * of each of the four column tiles into lane l, i.e. the four columns {c0, c0 + 32, c0 + 64, c0 + 96} -- so that the lane
  * writes them with 16-byte stores and a wave's store instruction covers whole contiguous runs:
- *   4-byte cells (ldx_k16):  the lane's four cells are adjacent: element 4 * (c % 32) + c / 32  (one store per row);
+ *   4-byte cells (ldx_k16, ldx_r32):  the lane's four cells are adjacent: element 4 * (c % 32) + c / 32  (one store per row);
  *   8-byte cells (ldx_ld32): the lane's cells of column tiles (0, 1) and (2, 3) are adjacent pairs:
  *                            element 64 * (c / 64) + 2 * (c % 32) + (c / 32) % 2              (two stores per row).
  * Why: the kernel's result stream was bound by the number of store INSTRUCTIONS a CU can issue, not by bytes (round 4:
@@ -104,6 +104,19 @@ typedef struct { double r_square; double d_prime; } ldx_ld64;   /* unrounded, fo
 typedef struct { uint16_t value; } ldx_k16one;
 #define LDX_OUT_K16_RSQ 2
 #define LDX_OUT_K16_DPRIME 3
+/* Signed r, unrounded: ONE float32 per pair, the correlation of the two SNPs' ALT-allele indicators -- what fine-mapping,
+ * colocalisation and summary-statistics imputation consume.  Same element order as ldx_k16 (LDX_CELL_OFFSET4).  With n = n_hap,
+ * a / r = ALT / REF counts (missing codes count in n only) and n11 the exact alt/alt count:
+ *     num = n * n11 - a_i * a_j                         (an exact integer, |num| < 2^31)
+ *     cell = -0.0f                                      if a_i r_i == 0 or a_j r_j == 0 (the reference's degenerate SNPs:
+ *                                                       its r^2 is the int 0 there, as in ldx_ld32)
+ *     cell = float32 of num / sqrt(a_i r_i a_j r_j)     otherwise, within 4 float32 ulps of the exact value; +0.0f iff num == 0
+ * r > 0 when ALT alleles co-occur more often than independence predicts (D > 0); r^2 is the reference's unrounded r^2
+ * (calc_ld.py:50,86-90), so with missing codes |r| may exceed 1.  Without missing codes r is the Pearson correlation of the
+ * two 0/1 haplotype vectors.  Every kernel computes it with the same arithmetic: the cells are bit-identical across
+ * paths.  No side outputs (out_raw, out_n11) with this format; ldx_triangle_r_block_dev turns the strips into a square. */
+typedef struct { float r; } ldx_r32;
+#define LDX_OUT_R32 4
 
 /* one ld_area hit (ld_area.py:261-271): query/opposing SNP row indices and rounded values */
 typedef struct {
@@ -200,9 +213,10 @@ int ldx_triangle_dev(const void *alt, const double *fa, const double *fr, const 
 #define LDX_PATH_FP4 3
 int ldx_set_triangle_path(int path);
 int ldx_get_triangle_path(void);
-/* ldx_triangle_dev with the kernel path and the cell format per call.  out: ldx_ld32, ldx_k16 or ldx_k16one cells
- * (out_format = LDX_OUT_LD32 / LDX_OUT_K16 / LDX_OUT_K16_RSQ / LDX_OUT_K16_DPRIME), indexed as in ldx_triangle_dev.  out_raw
- * needs LDX_OUT_LD32; the one-measure formats take neither side output and run on the FP4 or the popcount kernel.
+/* ldx_triangle_dev with the kernel path and the cell format per call.  out: ldx_ld32, ldx_k16, ldx_k16one or ldx_r32 cells
+ * (out_format = LDX_OUT_LD32 / LDX_OUT_K16 / LDX_OUT_K16_RSQ / LDX_OUT_K16_DPRIME / LDX_OUT_R32), indexed as in
+ * ldx_triangle_dev.  out_raw needs LDX_OUT_LD32; the one-measure formats take neither side output and run on the FP4 or the
+ * popcount kernel; LDX_OUT_R32 takes neither side output and runs on all three kernels.
  * workspace (ABI 102): ldx_triangle_workspace_bytes() bytes of device memory, 256-byte aligned, that hold the matrix
  * kernel's pass scheduler (two ticket counters).  Contract:
  *   - ZERO it once before the first launch that uses it (hipMemsetAsync, torch.zeros, or ldx_triangle_workspace_init_dev);
@@ -236,6 +250,13 @@ int ldx_triangle_dense_dev(const ldx_ld32 *strips, uint32_t n_snps, int measure,
 int ldx_triangle_dense_ex_dev(const void *strips, int strips_format, uint32_t n_snps, int measure, int has_thres,
                               double thres, uint32_t row_begin, uint32_t row_end, float *dense,
                               size_t ld, void *stream);
+/* Full (unsharded) LDX_OUT_R32 strips -> block [row_begin, row_end) x [col_begin, col_end) of the SYMMETRIC square r matrix,
+ * row-major float32 with leading dimension ld_out: (i, j) = strip cell (i, j) for i > j, (j, i) for i < j; the diagonal is the
+ * same formula at i = j, (n - a_i) / r_i (exactly 1.0f for a polymorphic SNP without missing codes, -0.0f for a degenerate
+ * one), from acnt / rcnt (ldx_pack_codes_dev) and n_hap.  Reads and writes are coalesced (tiles staged through LDS). */
+int ldx_triangle_r_block_dev(const ldx_r32 *strips, uint32_t n_snps, const uint32_t *acnt, const uint32_t *rcnt,
+                             uint32_t n_hap, uint32_t row_begin, uint32_t row_end, uint32_t col_begin, uint32_t col_end,
+                             float *out, size_t ld_out, void *stream);
 
 /* ---- ld_area: windowed scan around query SNPs (ld_area.py:152-276) --------------------- */
 /* positions: int64 [n_snps] ascending 1-based coordinates (VCF order).  queries: uint32 row

@@ -23,8 +23,8 @@ UNIT_PAIRS = SLAB_ROWS * GROUP_ROWS
 def cell_offset(r8, c, fmt="k16"):
     """LDX_CELL_OFFSET of include/ldx.h: element of cell (row % 8, column % 128) inside its unit, in the order of the cell
     format: rows one after the other; inside a row the columns {c0, c0 + 32, c0 + 64, c0 + 96} one lane of the matrix kernel
-    holds are adjacent (k16: all four; ld32: in two pairs).  Works on ints and numpy arrays."""
-    if fmt in ("k16", "k16r", "k16d"):
+    holds are adjacent (k16, r32: all four; ld32: in two pairs).  Works on ints and numpy arrays."""
+    if fmt in ("k16", "k16r", "k16d", "r32"):
         return r8 * SLAB_ROWS + ((c & 31) << 2) + (c >> 5)
     if fmt != "ld32":
         raise ValueError(f"unknown cell format {fmt!r}")
@@ -35,7 +35,8 @@ MAX_HAPS = 10240
 FLAG_DPRIME_INT0 = 1
 FLAG_RSQ_INT0 = 2
 MEASURES = {"r_square": 0, "d_prime": 1}
-FORMATS = {"ld32": 0, "k16": 1, "k16r": 2, "k16d": 3}   # LDX_OUT_LD32 / LDX_OUT_K16 / LDX_OUT_K16_RSQ / LDX_OUT_K16_DPRIME
+FORMATS = {"ld32": 0, "k16": 1, "k16r": 2, "k16d": 3,   # LDX_OUT_LD32 / LDX_OUT_K16 / LDX_OUT_K16_RSQ / LDX_OUT_K16_DPRIME
+           "r32": 4}                                  # LDX_OUT_R32: signed r, unrounded float32 (no rounded measure)
 ONE_MEASURE = {"k16r": "r_square", "k16d": "d_prime"}    # the one-measure formats (2-byte cells) and what they hold
 ONE_MEASURE_FMT = {v: k for k, v in ONE_MEASURE.items()}
 LD32_BIG_BITS = 0x7FC00B16               # ldx_ld32 escape (value >= 1024): a quiet NaN
@@ -113,6 +114,7 @@ SIGNATURES = {
     "ldx_triangle_workspace_bytes": (_sz, []),
     "ldx_triangle_workspace_init_dev": (_int, [_vp, _sz, _vp]),
     "ldx_triangle_dense_ex_dev": (_int, [_vp, _int, _u32, _int, _int, _dbl, _u32, _u32, _vp, _sz, _vp]),
+    "ldx_triangle_r_block_dev": (_int, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp]),
     "ldx_ld_from_counts_ex_dev": (_int, [_u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ldx_ld_pairs_dev": (_int, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "ldx_debug_force_short_passes": (_int, [_int]),

@@ -212,6 +212,38 @@ __device__ __forceinline__ ldx_k16r zero_cell<ldx_k16r>() { return ldx_k16r{0}; 
 template <>
 __device__ __forceinline__ ldx_k16d zero_cell<ldx_k16d>() { return ldx_k16d{0}; }
 
+template <>
+__device__ __forceinline__ ldx_r32 zero_cell<ldx_r32>() { return ldx_r32{0.0f}; }
+
+// ---- signed r cells (LDX_OUT_R32, include/ldx.h): ONE arithmetic for every producer, so that the kernels agree bit for bit.
+// Per SNP: its ALT count a and rs = 1 / sqrt(a r) in fp64 (0 for a degenerate SNP, a r == 0); per pair
+//     num = n n11 - a1 a2      exact in fp64 (every product < 2^27 for n <= LDX_MAX_HAPS), so +0.0 exactly when it is 0
+//     cell = (float)(num * (rs1 * rs2))
+// sqrt and the division round once each, the two products once each: the fp64 value is within ~4 2^-53 of the exact
+// quotient, and the float32 conversion adds half an ulp -- well inside the contract's 4 ulps.  A degenerate SNP makes the
+// product 0 (a non-degenerate one is >= 1 / LDX_MAX_HAPS: no underflow), which selects -0.0f.  -ffp-contract=off keeps
+// every operation as written.
+struct R32Snp {
+    double a, rs;
+};
+__host__ __device__ inline R32Snp r32_snp(double fa, double fr, double n)
+{
+    const double a = __builtin_rint(fa * n), r = __builtin_rint(fr * n);   // the counts back from a/n, r/n: exact
+    const double ar = a * r;
+    return R32Snp{a, ar > 0.0 ? 1.0 / __builtin_sqrt(ar) : 0.0};
+}
+__device__ __forceinline__ ldx_r32 r32_cell(double n11, double n, double a1, double rs1, double a2, double rs2)
+{
+    const double num = __builtin_fma(n11, n, -(a1 * a2));
+    const double s = rs1 * rs2;
+    return ldx_r32{s == 0.0 ? -0.0f : (float)(num * s)};
+}
+// the diagonal, the same formula at i = j: a (n - a) / (a r) = (n - a) / r -- one division, so exactly 1.0f when n - a == r
+__device__ __forceinline__ float r32_diag(double a, double r, double n)
+{
+    return a * r == 0.0 ? -0.0f : (float)((n - a) / r);
+}
+
 template <typename Cell>
 __device__ __forceinline__ Cell encode_cell(const LdK &k)
 {

@@ -393,7 +393,8 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
     uint32_t *tickets = reinterpret_cast<uint32_t *>(cstat + kSlab * kStat + kMfmaWaves * ((kArea ? kRows64 : kStatRows) * kStat));   // [2]
     uint32_t *cols_odd = tickets + 2;   // [2]: per wave of the column stagers, != 0 if one of its columns is not "ordinary"
     // fp32 tier (ldx_common.h, ld_multi_f32): its per-SNP tables and each wave's queue of lane-steps for the fp64 tier
-    constexpr bool kF32Tier = kFp4 && !kRaw && !kN11 && !kArea;
+    constexpr bool kR32 = std::is_same<Cell, ldx_r32>::value;   // signed r cells: epilogue_r32, none of the rounding tiers
+    constexpr bool kF32Tier = kFp4 && !kRaw && !kN11 && !kArea && !kR32;
     constexpr bool kBandF32 = kFp4 && kArea;   // the band screens its steps in float32 first (area_epilogue)
     float *ctab32 = reinterpret_cast<float *>(tickets + 8);                 // [128][4]: F32Col
     float *rtab32 = ctab32 + kSlab * 4u + wave * (kRows64 * 4u);            // [64][4]: F32Row, private to the wave
@@ -652,7 +653,17 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 bquarter(bexp + kBBuf, br[1], 0);
             }
             bool rows_ordinary = false;
-            if (!kRaw) {   // epilogue operands -> LDS (every wave is past its previous epilogue: barrier above)
+            typedef double d2s __attribute__((ext_vector_type(2)));
+            if constexpr (kR32) {   // signed r: {a, 1 / sqrt(a r)} per SNP (ldx_common.h, r32_snp) in the first two slots
+                if (new_tile && tid < kSlab) {
+                    const uint32_t j = t * kSlab + tid;
+                    const R32Snp c = r32_snp(fa[j], fr[j], n);
+                    *reinterpret_cast<d2s *>(cstat + tid * kStat) = d2s{c.a, c.rs};
+                }
+                const uint32_t i = row0 + (MM == 1 ? l32 : lane);   // (a half-height unit's lanes 32-63 repeat rows 0-31)
+                const R32Snp r = r32_snp(fa[i], fr[i], n);
+                if (lane < kStatRows) *reinterpret_cast<d2s *>(rstat + lane * kStat) = d2s{r.a, r.rs};
+            } else if (!kRaw) {   // epilogue operands -> LDS (every wave is past its previous epilogue: barrier above)
                 if (new_tile && tid < kSlab) {
                     const uint32_t j = t * kSlab + tid;
                     const FastCol c = fast_col(fa[j], fr[j], n);
@@ -1272,6 +1283,60 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 return false;
               }
             };
+            // ---- signed r cells (LDX_OUT_R32) ----
+            // r32_cell per pair (ldx_common.h) from the count and the two SNPs' {a, 1 / sqrt(a r)} staged above: nothing is
+            // rounded, so there is no margin, no parking and no mirror -- every unit, inside the triangle or on its edge, takes
+            // this loop.  A lane's four cells of a row are adjacent (LDX_CELL_OFFSET4): one 16-byte store per row and step,
+            // through the same scalar-base store as the fp32 tier's k16 cells.
+            auto epilogue_r32 = [&]() {
+              if constexpr (kR32) {
+                const uint64_t ub = vv * 8u - u_begin;   // this unit's first cell unit, relative to the output (wraps if before it)
+                const uint64_t ubs = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(ub >> 32)) << 32) |
+                                     __builtin_amdgcn_readfirstlane((uint32_t)ub);
+                uint32_t ln = lane;   // (lane-derived values recomputed from an opaque copy of the lane id: see epilogue_f32)
+                asm volatile("" : "+v"(ln));
+                const uint32_t l32e = ln & 31u, halfe = ln >> 5;
+                const uint32_t lane_off_b = (halfe * 4u * kSlab + 4u * l32e) * (uint32_t)sizeof(Cell);
+                const uint32_t grp0 = roff / kGroup;
+                double ca[4], cs[4];   // this lane's four columns
+#pragma unroll
+                for (int tt = 0; tt < 4; ++tt) {
+                    const d2s c = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32e) * kStat);
+                    ca[tt] = c.x;
+                    cs[tt] = c.y;
+                }
+                const uint32_t j0 = t * kSlab + l32e;   // column of tile tt: j0 + 32 tt
+                // wave-uniform: every row of the wave lies below the j-tile and inside the panel -- no per-cell test
+                const bool all_valid = row0 >= (t + 1u) * kSlab && row0 + 32u * MM <= n_snps;
+#pragma unroll 1
+                for (int e = 0; e < 16; ++e) {
+#pragma unroll
+                    for (int m = 0; m < MM; ++m) {
+                        const uint32_t g = 4u * m + grp0 + (uint32_t)(e >> 2);   // 8-row group inside the unit (scalar)
+                        const uint64_t us = vv * 8u + g;
+                        if (us < u_begin || us >= u_end) continue;   // wave-uniform
+                        accel_t c4[4];   // ONE register-indexed read per accumulator, pinned (see area_epilogue)
+#pragma unroll
+                        for (int tt = 0; tt < 4; ++tt) {
+                            c4[tt] = acc[m][tt][e];
+                            asm volatile("" : "+v"(c4[tt]));
+                        }
+                        const uint32_t ri = 32u * m + (uint32_t)(e & 3) + 8u * (uint32_t)(e >> 2) + 4u * halfe;
+                        const d2s rw = *reinterpret_cast<const d2s *>(rstat + ri * kStat);   // two addresses per wave: broadcast
+                        const uint32_t i = row0 + ri;
+                        Cell o4[4];
+#pragma unroll
+                        for (int tt = 0; tt < 4; ++tt) {
+                            const double cnt = kFp4 ? (double)c4[tt] : (double)((uint32_t)c4[tt] >> 3);   // int8: 8 n11
+                            o4[tt] = r32_cell(cnt, n, rw.x, rw.y, ca[tt], cs[tt]);
+                            if (!all_valid && !(i > j0 + 32u * tt && i < n_snps)) o4[tt] = zero_cell<Cell>();
+                        }
+                        Cell *const row = out + ((ubs + g) * LDX_UNIT_PAIRS + (uint32_t)(e & 3) * kSlab);   // scalar
+                        store_cells4_saddr(row, lane_off_b, o4[0], o4[1], o4[2], o4[3]);
+                    }
+                }
+              }
+            };
             // ---- ld_area: thresholded hits instead of a dense result ----
             // Pair (i, j), i > j, pos_i >= pos_j, serves two ordered pairs of the reference's loop:
             //   A: query i, opposing j -- j lies in i's window iff max(0, pos_i - flank) < pos_j     (ld_area.py:174-177)
@@ -1515,7 +1580,9 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                                 vv * 8u >= u_begin && vv * 8u + 8u <= u_end;
             const bool all_ordinary = rows_ordinary && (cols_odd[0] | cols_odd[1]) == 0u;
             const bool clean = inside && all_ordinary;
-            if constexpr (kF32Tier) {
+            if constexpr (kR32) {
+                epilogue_r32();
+            } else if constexpr (kF32Tier) {
                 // The fp32 tier takes every `inside` unit: rows / columns of SNPs that are not ordinary park their lane-steps
                 // (ldx_common.h, f32_row) and the drain runs the general fp64 variant for such a unit.  A unit that parks more
                 // than the queue holds (four or more such SNPs) goes through the fp64 epilogue whole.
@@ -1567,7 +1634,7 @@ static int launch_mfma(const void *alt, const double *fa, const double *fr, cons
         set_error("ld_triangle on the matrix pipe: a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", n_snps, n_hap);
         return kNoMatrixPath;   // LDX_PATH_AUTO: the popcount kernel; an explicit matrix-pipe path: LDX_E_UNSUPPORTED
     }
-    const size_t lds = mfma_lds_bytes(kStatRows, kFp4 && !kRaw && !kN11);
+    const size_t lds = mfma_lds_bytes(kStatRows, kFp4 && !kRaw && !kN11 && !std::is_same<Cell, ldx_r32>::value);
     if (lds > 64u * 1024u) {   // above 64 KiB the dynamic LDS size needs the opt-in attribute: once per device
         static std::atomic<uint64_t> opted{0};   // one bit per device ordinal, per instantiation
         int dev = 0;
@@ -1668,6 +1735,7 @@ int triangle_mfma(const void *alt, const double *fa, const double *fr, const dou
         return launch_mfma<false, false, true, ldx_k16d>(alt, fa, fr, q, n_snps, n_hap, unit_begin, unit_end, (ldx_k16d *)out,
                                                         nullptr, nullptr, sched, s);
     }
+    if (out_format == LDX_OUT_R32) LDX_GO(false, false, ldx_r32);   // signed r: no side output (ldx_triangle_ex_dev checks)
     if (out_format == LDX_OUT_K16) {   // no unrounded output beside the 4-byte cells (ldx_triangle_ex_dev checks)
         if (out_n11) LDX_GO(false, true, ldx_k16);
         LDX_GO(false, false, ldx_k16);

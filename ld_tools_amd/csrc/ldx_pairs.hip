@@ -61,6 +61,8 @@ triangle_kernel(const uint4 *__restrict__ alt, const double *__restrict__ fa, co
         const uint32_t j0 = t * kSlab + lane, j1 = j0 + 64u;
         const double fa2[2] = {fa[j0], fa[j1]};
         const double fr2[2] = {fr[j0], fr[j1]};
+        constexpr bool kR32 = std::is_same<Cell, ldx_r32>::value;   // signed r: its own per-pair arithmetic (ldx_common.h)
+        const R32Snp rc2[2] = {r32_snp(fa2[0], fr2[0], n), r32_snp(fa2[1], fr2[1], n)};
         block_sync();
 
         for (uint32_t k = wave; k < seg_len; k += kWaves) {
@@ -83,7 +85,10 @@ triangle_kernel(const uint4 *__restrict__ alt, const double *__restrict__ fa, co
                     const size_t o = obase + cell_offset<Cell>((uint32_t)r, jj * 64u + lane);
                     Cell res = zero_cell<Cell>();
                     ldx_ld64 rw = {0.0, 0.0};
-                    if (valid) {
+                    if constexpr (kR32) {
+                        const R32Snp r1 = r32_snp(fa1, fr1, n);
+                        if (valid) res = r32_cell((double)acc.v[r][jj], n, r1.a, r1.rs, rc2[jj].a, rc2[jj].rs);
+                    } else if (valid) {
                         const double f11 = div_by_n((double)acc.v[r][jj], n, rn);   // calc_ld.py:33
                         LdK lk;
                         if (kRaw) {   // parity / debugging output: the op-for-op mirror, unrounded values kept
@@ -346,6 +351,63 @@ __global__ void triangle_dense_kernel(const Cell *__restrict__ strips, uint32_t 
     dense[(size_t)(i - row_begin) * ld + j] = v;
 }
 
+// ---- r32 strips -> a block of the symmetric square r matrix (ldx_triangle_r_block_dev) ----
+// One workgroup per PAIR of 128 x 128 output tiles {(x, y), (y, x)}, tile indices absolute so that the strips behind them --
+// rows of tile max(x, y) against columns of tile min(x, y) -- are 16 whole consecutive units, 64 KiB in one piece.  The
+// workgroup stages that block in LDS with 16-byte loads, then writes the tile below the diagonal straight from it and the tile
+// above from its transpose, 512 contiguous bytes per output row segment: both the reads and the writes are coalesced, and
+// every strip cell is read once for its two places.  LDS rows are XOR-swizzled (column c of block row p at p * 128 +
+// (c ^ p)), so that the row-wise reads of the lower tile and the column-wise reads of the upper one are both free of bank
+// conflicts.  Tile (x, y) of the grid with x < y is left to the workgroup of (y, x) when that one exists.
+constexpr uint32_t kRbThreads = 256;
+__global__ void __launch_bounds__(kRbThreads)
+r_block_kernel(const float4 *__restrict__ strips, uint32_t n_slabs, const uint32_t *__restrict__ acnt,
+               const uint32_t *__restrict__ rcnt, double n, uint32_t r0, uint32_t r1, uint32_t c0, uint32_t c1,
+               uint32_t tr0, uint32_t tr1, uint32_t tc0, uint32_t tc1, float *__restrict__ out, size_t ld)
+{
+    __shared__ float blk[kSlab * kSlab];
+    const uint32_t x = tr0 + blockIdx.y, y = tc0 + blockIdx.x;   // output row tile, column tile
+    const bool mirror_in_grid = x >= tc0 && x < tc1 && y >= tr0 && y < tr1;   // tile (y, x) is part of the block too
+    if (x < y && mirror_in_grid) return;                                      // (the workgroup of (y, x) writes this one)
+    const uint32_t hi = x > y ? x : y, lo = x > y ? y : x;
+    const uint64_t G = (uint64_t)n_slabs * kGroupsPerSlab;
+    const uint64_t u0 = tile_base(lo, G) + (uint64_t)(hi - lo) * kGroupsPerSlab;   // units of row groups 16 hi .. 16 hi + 15
+    const float4 *src = strips + u0 * (LDX_UNIT_PAIRS / 4u);
+    const uint32_t tid = threadIdx.x;
+#pragma unroll 4
+    for (uint32_t it = 0; it < kSlab * kSlab / 4u / kRbThreads; ++it) {
+        const uint32_t v4 = tid + it * kRbThreads;   // float4 index inside the block
+        const float4 v = src[v4];
+        const uint32_t e = 4u * v4;
+        const uint32_t p = (e / LDX_UNIT_PAIRS) * kGroup + (e % LDX_UNIT_PAIRS) / kSlab;   // block row (unit, row inside it)
+        const uint32_t c = (e % kSlab) / 4u;   // the four cells are columns c, c + 32, c + 64, c + 96 (LDX_CELL_OFFSET4)
+        float *row = blk + p * kSlab;
+        row[c ^ p] = v.x;
+        row[(c + 32u) ^ p] = v.y;
+        row[(c + 64u) ^ p] = v.z;
+        row[(c + 96u) ^ p] = v.w;
+    }
+    block_sync();
+    auto write_tile = [&](uint32_t tx, uint32_t ty) {
+        const uint32_t jj = tid % kSlab, j = ty * kSlab + jj;
+        if (j < c0 || j >= c1) return;
+        for (uint32_t ii = tid / kSlab; ii < kSlab; ii += kRbThreads / kSlab) {
+            const uint32_t i = tx * kSlab + ii;
+            if (i < r0 || i >= r1) continue;
+            float v;
+            if (i == j) {
+                v = r32_diag((double)acnt[i], (double)rcnt[i], n);
+            } else {
+                const uint32_t p = (i > j ? i : j) - hi * kSlab, q = (i > j ? j : i) - lo * kSlab;   // strip cell (max, min)
+                v = blk[p * kSlab + (q ^ p)];
+            }
+            __builtin_nontemporal_store(v, out + (size_t)(i - r0) * ld + (j - c0));
+        }
+    };
+    write_tile(x, y);
+    if (x > y && mirror_in_grid) write_tile(y, x);
+}
+
 // ---- peak-rate probe for the inner loop's instruction pair ----
 // 16 accumulators x 4 words per round = 64 v_and_b32 (SGPR x VGPR) + 64 accumulating v_bcnt_u32_b32 per
 // lane and round, no memory traffic: what the VALU sustains for exactly the inner loop's two opcodes.
@@ -459,9 +521,11 @@ extern "C" int ldx_triangle_ex_dev(const void *alt, const double *fa, const doub
     LDX_REQUIRE(alt && fa && fr && q && out, "null pointer");
     LDX_REQUIRE(known_path(path), "unknown path");
     const bool one_measure = out_format == LDX_OUT_K16_RSQ || out_format == LDX_OUT_K16_DPRIME;
-    LDX_REQUIRE(out_format == LDX_OUT_LD32 || out_format == LDX_OUT_K16 || one_measure, "unknown output format");
+    LDX_REQUIRE(out_format == LDX_OUT_LD32 || out_format == LDX_OUT_K16 || one_measure || out_format == LDX_OUT_R32,
+                "unknown output format");
     LDX_REQUIRE(out_format == LDX_OUT_LD32 || !out_raw, "out_raw needs LDX_OUT_LD32");
     LDX_REQUIRE(!one_measure || !out_n11, "the one-measure formats take no side output");
+    LDX_REQUIRE(out_format != LDX_OUT_R32 || !out_n11, "LDX_OUT_R32 takes no side output");
     LDX_REQUIRE(n_snps >= 1 && n_hap >= 1, "bad shape");
     if (n_hap > LDX_MAX_HAPS) {
         set_error("ldx_triangle_dev: n_hap %u > LDX_MAX_HAPS %u", n_hap, LDX_MAX_HAPS);
@@ -482,6 +546,8 @@ extern "C" int ldx_triangle_ex_dev(const void *alt, const double *fa, const doub
         if (path != LDX_PATH_AUTO) return LDX_E_UNSUPPORTED;   // an explicit matrix-pipe path: say so (message set)
         // AUTO and a bit plane of 4 GiB or more: the popcount kernel gives the very same cells
     }
+    if (out_format == LDX_OUT_R32)
+        return launch_triangle<false, false>(alt, fa, fr, q, n_snps, n_hap, unit_begin, unit_end, (ldx_r32 *)out, out_raw, out_n11, s);
     if (out_format == LDX_OUT_K16_RSQ)
         return launch_triangle<false, false>(alt, fa, fr, q, n_snps, n_hap, unit_begin, unit_end, (ldx_k16r *)out, out_raw, out_n11, s);
     if (out_format == LDX_OUT_K16_DPRIME)
@@ -587,6 +653,25 @@ extern "C" int ldx_triangle_dense_ex_dev(const void *strips, int strips_format, 
     else
         triangle_dense_kernel<<<grid, 256, 0, (hipStream_t)stream>>>((const ldx_ld32 *)strips, n_snps, ldx::n_slabs(n_snps),
                                                                     measure, has_thres, kt, row_begin, row_end, dense, ld);
+    LDX_HIP(hipGetLastError());
+    return LDX_OK;
+}
+
+extern "C" int ldx_triangle_r_block_dev(const ldx_r32 *strips, uint32_t n_snps, const uint32_t *acnt, const uint32_t *rcnt,
+                                        uint32_t n_hap, uint32_t row_begin, uint32_t row_end, uint32_t col_begin,
+                                        uint32_t col_end, float *out, size_t ld_out, void *stream)
+{
+    LDX_REQUIRE(strips && acnt && rcnt && out, "null pointer");
+    LDX_REQUIRE(n_snps >= 1 && n_hap >= 1, "bad shape");
+    LDX_REQUIRE(row_begin <= row_end && row_end <= n_snps && col_begin <= col_end && col_end <= n_snps,
+                "block outside the matrix");
+    LDX_REQUIRE(ld_out >= col_end - col_begin, "ld_out smaller than the block's width");
+    if (row_begin == row_end || col_begin == col_end) return LDX_OK;
+    const uint32_t tr0 = row_begin / kSlab, tr1 = (row_end + kSlab - 1u) / kSlab;
+    const uint32_t tc0 = col_begin / kSlab, tc1 = (col_end + kSlab - 1u) / kSlab;
+    r_block_kernel<<<dim3(tc1 - tc0, tr1 - tr0), kRbThreads, 0, (hipStream_t)stream>>>(
+        (const float4 *)strips, ldx::n_slabs(n_snps), acnt, rcnt, (double)n_hap, row_begin, row_end, col_begin, col_end, tr0,
+        tr1, tc0, tc1, out, ld_out);
     LDX_HIP(hipGetLastError());
     return LDX_OK;
 }

@@ -27,22 +27,44 @@ class TriangleMatrix:
     alt_freqs: List[float]            # round(a / n, 4) per variant     (calc_ld.py:96-97)
 
 
+@dataclass
+class ChromVariants:
+    """The position-sorted variants of one chromosome, each fetched ONCE: what the pair loops of ld_triangle.py:158-186
+    re-fetch for every pair.  Entries of a variant without a matching record: rec None, empty genotype list, '' text."""
+
+    poss: List[int]
+    rs_ids: List[str]
+    recs: list
+    genotypes: List[list]
+    alleles: List[str]                # ref + '/' + alts[0]   (ld_triangle.py:165,179)
+    types: List[str]                  # info['VT'][0]          (ld_triangle.py:166,180)
+
+
+def fetch_variants(vcf, chrom, chrom_rows: Sequence[Sequence], sample_names: Sequence[str]) -> ChromVariants:
+    """[pos, rsID] rows of one chromosome -> their records and genotype lists, sorted by position (ld_triangle.py:88,
+    stable)."""
+    rows = sorted(chrom_rows, key=lambda r: r[0])                     # ld_triangle.py:88 (stable, by position)
+    poss = [int(r[0]) for r in rows]
+    rs_ids = [r[1] for r in rows]
+    recs, genotypes, alleles, types = [], [], [], []
+    for pos, rs_id in zip(poss, rs_ids):
+        rec = find_record(vcf, chrom, pos, rs_id)
+        recs.append(rec)
+        # no matching record: the reference's genotype list stays empty and calc_ld divides by zero (calc_ld.py:33)
+        genotypes.append(sample_genotypes(rec, sample_names) if rec is not None else [])
+        alleles.append(rec.ref + "/" + rec.alts[0] if rec is not None else "")
+        types.append(rec.info["VT"][0] if rec is not None else "")
+    return ChromVariants(poss, rs_ids, recs, genotypes, alleles, types)
+
+
 def triangle_matrix(vcf, chrom, chrom_rows: Sequence[Sequence], sample_names: Sequence[str],
                     ld_measure: str = "r_square", ld_low_thres: Optional[float] = None) -> TriangleMatrix:
     """The pair loop of ld_triangle.py:133-230 for one chromosome: every row > col pair of the position-sorted
     variants, var_1 = row (larger position), var_2 = col; cells whose rounded measure is below ``ld_low_thres``
     keep the template's int 0 (ld_triangle.py:223-225).  Each variant is fetched and packed ONCE."""
-    rows = sorted(chrom_rows, key=lambda r: r[0])                     # ld_triangle.py:88 (stable, by position)
-    poss = [int(r[0]) for r in rows]
-    rs_ids = [r[1] for r in rows]
-    genotypes, alleles, types = [], [], []
-    for pos, rs_id in zip(poss, rs_ids):
-        rec = find_record(vcf, chrom, pos, rs_id)
-        # no matching record: the reference's genotype list stays empty and calc_ld divides by zero (calc_ld.py:33)
-        genotypes.append(sample_genotypes(rec, sample_names) if rec is not None else [])
-        alleles.append(rec.ref + "/" + rec.alts[0] if rec is not None else "")
-        types.append(rec.info["VT"][0] if rec is not None else "")
-    n = len(rows)
+    cv = fetch_variants(vcf, chrom, chrom_rows, sample_names)
+    poss, rs_ids, genotypes, alleles, types = cv.poss, cv.rs_ids, cv.genotypes, cv.alleles, cv.types
+    n = len(poss)
     try:
         codes = codes_matrix(genotypes)
     except RaggedGenotypesError:

@@ -55,6 +55,8 @@ class TriangleResult:
     only, 2 bytes per pair, what a table writer needs (ld_triangle.py:223-230,344-360 print ONE measure) -- ``k16r`` /
     ``k16d`` (the r_square / d_prime half of k16).  Values a format cannot hold (>= 1024 / >= 3.2767: only with missing
     codes) are escape cells; ``dense_values()`` resolves them through ldx_ld_pairs_dev, so nothing is ever returned inexact.
+    ``r32`` holds no rounded measure: the signed correlation r of the ALT-allele indicators, unrounded float32, 4 bytes per
+    pair (include/ldx.h, LDX_OUT_R32); ``r_matrix()`` turns it into blocks of the symmetric square matrix.
     """
 
     n_snps: int
@@ -67,18 +69,23 @@ class TriangleResult:
     panel: Optional[PackedPanel] = None      # the panel the result came from (resolves escape cells)
     k16one: Optional[torch.Tensor] = None    # int16   [(units)*1024]     one measure's uint16 cells (fmt k16r / k16d)
     one_fmt: Optional[str] = None            # "k16r" / "k16d" when k16one is set
+    r32: Optional[torch.Tensor] = None       # float32 [(units)*1024]     signed r (fmt r32)
     ws: Optional[torch.Tensor] = None        # the matrix kernel's pass-scheduler workspace (include/ldx.h, ldx_triangle_ex_dev):
                                              # zeroed once here, re-armed by every launch; one per result buffer, because two
                                              # launches that may overlap write different buffers
 
     @property
     def fmt(self) -> str:
+        if self.r32 is not None:
+            return "r32"
         if self.k16one is not None:
             return self.one_fmt
         return "ld32" if self.ld32 is not None else "k16"
 
     @property
     def cells(self) -> torch.Tensor:
+        if self.r32 is not None:
+            return self.r32
         if self.k16one is not None:
             return self.k16one
         return self.ld32 if self.ld32 is not None else self.k16
@@ -99,6 +106,7 @@ class TriangleResult:
     def k_and_int0(self, idx) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(k int64 [m, 2], int0 bool [m, 2], escape bool [m, 2]) of the cells at flat indices ``idx`` (host arrays);
         k of an escape cell is -1."""
+        self._rounded_only("k_and_int0")
         ix = torch.as_tensor(np.asarray(idx, dtype=np.int64), device=self.cells.device)
         if self.k16one is not None:          # one measure: arrays of shape [m, 1]
             u = self.k16one[ix].cpu().numpy().view(np.uint16).astype(np.int64).reshape(-1, 1)
@@ -123,7 +131,8 @@ class TriangleResult:
         ``thres``) hold -0.0; a computed int 0 (monomorphic variant) is -0.0 too, a float 0.0 is +0.0.
         Escape cells come out as NaN (``dense_values`` resolves them).  Needs the full triangle.
         """
-        if self.unit_begin != 0 or self.unit_end != lib.ldx_triangle_units(self.n_snps):
+        self._rounded_only("dense")
+        if not self.unsharded:
             raise _lib.LdxError("dense() needs an unsharded TriangleResult")
         if self.k16one is not None and _lib.ONE_MEASURE[self.one_fmt] != measure:
             raise _lib.LdxError(f"this result holds {_lib.ONE_MEASURE[self.one_fmt]} only (format {self.one_fmt})")
@@ -141,6 +150,7 @@ class TriangleResult:
         {(row, col): Python value}).  The dict holds, for every NaN cell of the array, what the reference's
         ld_two_dim holds there: round(x, 4) as a float, or the int 0 when it lies below ``thres``
         (ld_triangle.py:223-230)."""
+        self._rounded_only("dense_values")
         r0, _ = rows if rows is not None else (0, self.n_snps)
         d = self.dense(measure, thres, rows).cpu().numpy()
         rr, cc = np.nonzero(np.isnan(d))
@@ -155,6 +165,38 @@ class TriangleResult:
                 fixes[(a, b)] = 0 if (thres is not None and v < thres) else v
         return d, fixes
 
+    @property
+    def unsharded(self) -> bool:
+        return self.unit_begin == 0 and self.unit_end == lib.ldx_triangle_units(self.n_snps)
+
+    def _rounded_only(self, what: str) -> None:
+        if self.r32 is not None:
+            raise _lib.LdxError(f"{what}() reads a rounded measure; an r32 result holds signed r (use r_matrix())")
+
+    def r_matrix(self, rows: Optional[Tuple[int, int]] = None, cols: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+        """Block [rows[0], rows[1]) x [cols[0], cols[1]) (default: everything) of the symmetric square matrix of signed r, as a
+        float32 device tensor: (i, j) and (j, i) both hold the strip cell of max(i, j), min(i, j); the diagonal is
+        (n - a_i) / r_i -- 1.0 for a polymorphic SNP without missing codes, -0.0 for a degenerate one
+        (ldx_triangle_r_block_dev).  Needs an unsharded r32 result."""
+        if self.r32 is None:
+            raise _lib.LdxError(f"r_matrix() needs an r32 result (this one is {self.fmt})")
+        if not self.unsharded:
+            raise _lib.LdxError("r_matrix() needs an unsharded TriangleResult")
+        if self.panel is None:
+            raise _lib.LdxError("r_matrix() needs the panel (TriangleResult.panel) for the diagonal")
+        n = self.n_snps
+        r0, r1 = rows if rows is not None else (0, n)
+        c0, c1 = cols if cols is not None else (0, n)
+        if not (0 <= r0 <= r1 <= n and 0 <= c0 <= c1 <= n):
+            raise _lib.LdxError(f"r_matrix(): block {rows} x {cols} outside the {n} x {n} matrix")
+        out = torch.empty((r1 - r0, c1 - c0), dtype=torch.float32, device=self.r32.device)
+        if out.numel():
+            p = self.panel
+            check(lib.ldx_triangle_r_block_dev(self.r32.data_ptr(), n, p.acnt.data_ptr(), p.rcnt.data_ptr(), p.n_hap,
+                                               r0, r1, c0, c1, out.data_ptr(), c1 - c0, _stream_ptr()),
+                  "ldx_triangle_r_block_dev")
+        return out
+
 
 def ld_triangle(panel: PackedPanel, unit_range: Optional[Tuple[int, int]] = None, want_raw: bool = False,
                 want_n11: bool = False, out: Optional[TriangleResult] = None, fmt: str = "ld32",
@@ -164,7 +206,7 @@ def ld_triangle(panel: PackedPanel, unit_range: Optional[Tuple[int, int]] = None
     ``unit_range`` restricts the work to a contiguous slice of the unit list (multi-GPU sharding);
     ``out`` re-uses the buffers of a previous result of the same shape (benchmark loops); ``fmt`` picks the cell
     format ('ld32': 8 bytes per pair, 'k16': 4 bytes per pair, 'k16r' / 'k16d': ONE measure, 2 bytes per pair -- the kernel
-    then skips the other value's arithmetic); ``path`` overrides the process-wide kernel choice ('fp4', 'mfma', 'popcount')
+    then skips the other value's arithmetic; 'r32': signed r, unrounded float32, 4 bytes per pair); ``path`` overrides the process-wide kernel choice ('fp4', 'mfma', 'popcount')
     for this call.
     """
     total = panel.n_units
@@ -178,6 +220,8 @@ def ld_triangle(panel: PackedPanel, unit_range: Optional[Tuple[int, int]] = None
         raise _lib.LdxError("the unrounded output travels with the ld32 format only")
     if fmt in _lib.ONE_MEASURE and want_n11:
         raise _lib.LdxError("the one-measure formats take no side output")
+    if fmt == "r32" and want_n11:
+        raise _lib.LdxError("the r32 format takes no side output")
     if out is None:
         out = TriangleResult(panel.n_snps, u0, u1,
                              torch.empty((cells, 2), dtype=torch.float32, device=dev) if fmt == "ld32" else None,
@@ -185,7 +229,8 @@ def ld_triangle(panel: PackedPanel, unit_range: Optional[Tuple[int, int]] = None
                              torch.empty(cells, dtype=torch.int32, device=dev) if want_n11 else None,
                              torch.empty((cells, 2), dtype=torch.int16, device=dev) if fmt == "k16" else None,
                              k16one=torch.empty(cells, dtype=torch.int16, device=dev) if fmt in _lib.ONE_MEASURE else None,
-                             one_fmt=fmt if fmt in _lib.ONE_MEASURE else None)
+                             one_fmt=fmt if fmt in _lib.ONE_MEASURE else None,
+                             r32=torch.empty(cells, dtype=torch.float32, device=dev) if fmt == "r32" else None)
     elif (out.n_snps, out.unit_begin, out.unit_end, out.fmt) != (panel.n_snps, u0, u1, fmt):
         raise _lib.LdxError("ld_triangle: `out` has a different shape or format")
     out.panel = panel
