@@ -316,6 +316,35 @@ size_t ldx_area_band_passes_offset(uint32_t n_snps);
 int ldx_set_area_path(int path);
 int ldx_get_area_path(void);
 
+/* ---- LD scores: windowed sums of r^2 per SNP (LD score regression's l2 column) on the matrix-pipe band ---- */
+/* For every SNP i, with r_ij the signed r cell of ldx_triangle_ex_dev(LDX_OUT_R32) for the pair (bit for bit the same value),
+ * and the diagonal r_ii = (n - a_i) / r_i of ldx_triangle_r_block_dev (1 for a polymorphic SNP without missing codes, -0.0f
+ * for a degenerate one):
+ *     term(r) = rint(2^32 * (r *f32 r))        one IEEE float32 multiply, then exact scaling; a uint64.  Exact for every
+ *                                              r^2 >= 2^-9; the -0.0f of a degenerate SNP gives 0
+ *     sums[i][0]     = sum of term(r_ij) over j with |pos_i - pos_j| <= window      (j = i included: the window is
+ *                                                                                      symmetric and inclusive)
+ *     sums[i][1 + k] = the same sum over the j whose annot[j] has bit k set (j = i: if annot[i] has it), k < n_annot
+ * so sums / 2^32 is the LD score L(i, C) = sum of r^2.  Every SNP is a query.  The sums are 64-bit integer atomics, so the
+ * result does not depend on the order of the work: it is bit-reproducible run to run and equal to a host sum of the terms
+ * of the r32 triangle.  They wrap only if one SNP's sum of r^2 reaches 2^32 (without missing codes r^2 <= 1: never).
+ *   positions: int64 [n_snps], NON-DECREASING (duplicates allowed: both SNPs are then in each other's window);
+ *   window >= 0 in the units of positions (values above 2^52 act as 2^52);
+ *   annot: uint8 [n_snps] category bitmasks (bits >= n_annot are ignored), NULL iff n_annot == 0; n_annot <= 8;
+ *   sums: uint64 [n_snps][1 + n_annot], written by the call (no need to zero it);
+ *   acnt / rcnt from ldx_pack_codes_dev, fa / fr from ldx_snp_stats_dev;
+ *   path: LDX_PATH_AUTO / LDX_PATH_FP4 = the FP4 band, LDX_PATH_MFMA = the int8 band (identical sums), LDX_PATH_POPCOUNT =
+ *         LDX_E_UNSUPPORTED; n_hap > LDX_MAX_HAPS = LDX_E_UNSUPPORTED.
+ * workspace: ldx_ld_score_workspace_bytes() bytes, 256-byte aligned, no initialisation needed (the call's first kernels set
+ * what it reads): ONE workspace per launch that may be in flight, as for ldx_area_dev -- launches that may overlap (different
+ * streams, parallel graph branches) need different workspaces; consecutive launches of one stream may share one.
+ * The call only enqueues work on `stream`: it allocates nothing and does not synchronise. */
+size_t ldx_ld_score_workspace_bytes(uint32_t n_snps, uint32_t n_hap);
+int ldx_ld_score_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
+                     uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window,
+                     const uint8_t *annot, uint32_t n_annot, int path,
+                     uint64_t *sums, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- synthetic panels: deterministic, identical on host and device ------ */
 /* codes int8 [n_snps][ld_codes] receive global SNPs [snp_offset, snp_offset + n_snps) (a rank's
  * shard).  thresholds: per-SNP ALT probability * 2^64 (computed on the host, see

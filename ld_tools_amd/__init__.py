@@ -9,8 +9,8 @@ All arithmetic runs in libldx.so (HIP, C ABI in include/ldx.h); importing the pa
 that library fails -- there is no CPU fallback.
 """
 from ._lib import LdxError, version  # noqa: F401  (loads libldx.so or raises)
-from .ops import AreaHits, TriangleResult, ld_area, ld_from_counts, ld_triangle, pair_counts  # noqa: F401
+from .ops import AreaHits, LDScores, TriangleResult, ld_area, ld_from_counts, ld_score, ld_triangle, pair_counts  # noqa: F401
 from .panel import PackedPanel, encode_codes  # noqa: F401
 
 __all__ = ["PackedPanel", "encode_codes", "ld_triangle", "ld_area", "pair_counts", "ld_from_counts",
-           "TriangleResult", "AreaHits", "LdxError", "version"]
+           "TriangleResult", "AreaHits", "ld_score", "LDScores", "LdxError", "version"]

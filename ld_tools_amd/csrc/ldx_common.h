@@ -244,6 +244,19 @@ __device__ __forceinline__ float r32_diag(double a, double r, double n)
     return a * r == 0.0 ? -0.0f : (float)((n - a) / r);
 }
 
+// LD-score term of a signed r cell (ldx_ld_score_dev, include/ldx.h): rint(2^32 r^2), r^2 ONE float32 multiply.  Exact for
+// r^2 >= 2^-9 (a float32 of that size is a multiple of 2^-32); -0.0f (a degenerate SNP) gives 0.
+__device__ __forceinline__ uint64_t score_term(float r)
+{
+    const float r2 = r * r;
+    return (uint64_t)__builtin_rint((double)r2 * 0x1p32);
+}
+// the diagonal's term: r32_diag squared the same way
+__device__ __forceinline__ uint64_t score_self_term(uint32_t a, uint32_t r, uint32_t n)
+{
+    return score_term(r32_diag((double)a, (double)r, (double)n));
+}
+
 template <typename Cell>
 __device__ __forceinline__ Cell encode_cell(const LdK &k)
 {

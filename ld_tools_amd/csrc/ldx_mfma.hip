@@ -315,11 +315,37 @@ __device__ __forceinline__ void store_cells4_saddr(Cell *sbase, uint32_t voff_by
     }
 }
 
+// Sum of a 64-bit value over the 32 lanes of each wave half, left in lanes 31 and 63 (other lanes: partial sums).  DPP
+// row_shr 1, 2, 4, 8 sum each row of 16 lanes into its lane 15; row_bcast:15 (rows 1 and 3 only) adds row 0's total to
+// row 1 and row 2's to row 3.  Lanes a shift leaves without a source read 0.  Integer adds: the order does not matter.
+__device__ __forceinline__ uint64_t dpp_half_sum(uint64_t x)
+{
+    uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
+#define LDX_DPP_ADD(ctrl, rows)                                                                               \
+    {                                                                                                         \
+        const uint32_t ylo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lo, ctrl, rows, 0xF, true);        \
+        const uint32_t yhi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hi, ctrl, rows, 0xF, true);        \
+        const uint64_t s = (((uint64_t)hi << 32) | lo) + (((uint64_t)yhi << 32) | ylo);                       \
+        lo = (uint32_t)s;                                                                                     \
+        hi = (uint32_t)(s >> 32);                                                                             \
+    }
+    LDX_DPP_ADD(0x111, 0xF)   // row_shr:1
+    LDX_DPP_ADD(0x112, 0xF)   // row_shr:2
+    LDX_DPP_ADD(0x114, 0xF)   // row_shr:4
+    LDX_DPP_ADD(0x118, 0xF)   // row_shr:8
+    LDX_DPP_ADD(0x142, 0xA)   // row_bcast:15 into rows 1 and 3
+#undef LDX_DPP_ADD
+    return ((uint64_t)hi << 32) | lo;
+}
+
 // kFp4: the counting runs on v_mfma_f32_32x32x64_f8f6f4 with FP4 operands (expand32_a4 / expand32_b4) instead of
 // v_mfma_i32_32x32x32_i8: a K-block is then 256 haplotypes -- two 128-haplotype chunks, one per lane half -- in four
 // steps of 64, so the loop below keeps its shape (per step 8 MFMAs, 4 fragment reads, one quarter of the thread's share
 // of a later block's j-tile image) with `nblocks` = nchunks / 2 iterations and ~16 instead of ~28 VALU per step.
-template <bool kRaw, bool kN11, bool kArea = false, bool kFp4 = false, typename Cell = ldx_ld32>
+// kScoreW (with kArea): the LD-score band (ldx_ld_score_dev) -- the band's passes and K loop with score_epilogue instead of
+// the hit scan; kScoreW is the number of `sums` words one sweep of the accumulators reduces (1: column 0 only; 5: column 0
+// and the categories, in sweeps of three words -- four or five spill).
+template <bool kRaw, bool kN11, bool kArea = false, bool kFp4 = false, typename Cell = ldx_ld32, int kScoreW = 0>
 __global__ void __launch_bounds__(kMfmaThreads, kArea ? 2 : kWgPerCu)
 triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ fa, const double *__restrict__ fr,
                      const double *__restrict__ q, uint32_t n_snps, uint32_t n_slabs, uint32_t nchunks, double n,
@@ -395,7 +421,9 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
     // fp32 tier (ldx_common.h, ld_multi_f32): its per-SNP tables and each wave's queue of lane-steps for the fp64 tier
     constexpr bool kR32 = std::is_same<Cell, ldx_r32>::value;   // signed r cells: epilogue_r32, none of the rounding tiers
     constexpr bool kF32Tier = kFp4 && !kRaw && !kN11 && !kArea && !kR32;
-    constexpr bool kBandF32 = kFp4 && kArea;   // the band screens its steps in float32 first (area_epilogue)
+    constexpr bool kScore = kScoreW != 0;   // LD scores (score_epilogue): r32 operands, integer sums instead of hits
+    static_assert(!kScore || kArea, "the LD-score epilogue runs on the band");
+    constexpr bool kBandF32 = kFp4 && kArea && !kScore;   // the band screens its steps in float32 first (area_epilogue)
     float *ctab32 = reinterpret_cast<float *>(tickets + 8);                 // [128][4]: F32Col
     float *rtab32 = ctab32 + kSlab * 4u + wave * (kRows64 * 4u);            // [64][4]: F32Row, private to the wave
     uint32_t *qid = reinterpret_cast<uint32_t *>(ctab32 + kSlab * 4u + kMfmaWaves * kRows64 * 4u) + wave * kQueueCap;   // [kQueueCap]
@@ -654,7 +682,20 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             }
             bool rows_ordinary = false;
             typedef double d2s __attribute__((ext_vector_type(2)));
-            if constexpr (kR32) {   // signed r: {a, 1 / sqrt(a r)} per SNP (ldx_common.h, r32_snp) in the first two slots
+            if constexpr (kScore) {   // LD scores: {a, 1 / sqrt(a r)} (r32_snp) and {position, annotation mask} per SNP
+                if (new_tile && tid < kSlab) {
+                    const uint32_t j = t * kSlab + tid;
+                    const R32Snp c = r32_snp(fa[j], fr[j], n);
+                    d2s *dst = reinterpret_cast<d2s *>(cstat + tid * kStat);
+                    dst[0] = d2s{c.a, c.rs};
+                    dst[1] = j < n_snps ? d2s{(double)aa.pos[j], (double)(aa.is_query ? aa.is_query[j] : (uint8_t)0)} : d2s{0.0, 0.0};
+                }
+                const uint32_t i = row0 + lane;
+                const R32Snp r = r32_snp(fa[i], fr[i], n);
+                d2s *dst = reinterpret_cast<d2s *>(rstat + lane * kStat);
+                dst[0] = d2s{r.a, r.rs};
+                dst[1] = i < n_snps ? d2s{(double)aa.pos[i], (double)(aa.is_query ? aa.is_query[i] : (uint8_t)0)} : d2s{0.0, 0.0};
+            } else if constexpr (kR32) {   // signed r: {a, 1 / sqrt(a r)} per SNP (ldx_common.h, r32_snp) in the first two slots
                 if (new_tile && tid < kSlab) {
                     const uint32_t j = t * kSlab + tid;
                     const R32Snp c = r32_snp(fa[j], fr[j], n);
@@ -858,7 +899,12 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             // to spare) in instruction arbitration: +2 % at 40k SNPs.
             if (ablate & 32) __builtin_amdgcn_s_setprio(0);
             else if (!(ablate & 16)) __builtin_amdgcn_s_setprio(3);
-            if (!active) {   // wave-uniform; inactive waves only helped with B and the barriers
+            if constexpr (kScore) {
+                // LD scores: every wave is past its last read of the j-tile image -- the two image buffers hold the column
+                // sums of the waves until the next pass's prologue (after the barrier at the top of the loop) overwrites them.
+                // Inactive waves stay for the barriers and the column flush.
+                block_sync();
+            } else if (!active) {   // wave-uniform; inactive waves only helped with B and the barriers
                 if (tid == 0) tickets[parity] = next_ticket;
                 return;
             }
@@ -1345,8 +1391,109 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             // D' and the fast path's r^2 do not depend on the order; the reference's r^2 does in its last bits
             // ((fa1*fr1)*fa2)*fr2 associates in argument order), so a pair that needs the mirror
             // gets it once per order.
+            // ---- LD scores (ldx_ld_score_dev): a reduction where the scan appends ----
+            // Pair (i, j), i > j, |pos_i - pos_j| <= w (positions are non-decreasing, so pos_i >= pos_j): the r32 cell of the
+            // triangle (r32_cell, bit for bit), its term t = rint(2^32 r^2) (score_term) goes to row i's words and column j's.
+            // Word c of SNP x: c = 0 always, c = 1 + k if bit k of the OTHER SNP's mask is set.  Rows: a lane holds four columns
+            // of one row per (step, row tile) -- it sums them, and a DPP reduction over the 32 lanes of its half leaves the
+            // row's total for the pass's 128 columns in lane 31 / 63, which keeps it in the wave's LDS table.  Columns: a lane
+            // holds its four columns for 32 rows and sums them in registers; the two halves meet through one shuffle, the four
+            // waves through LDS (the image buffers, free after the barrier above).  Every word then goes to global memory
+            // once per pass and destination, as a 64-bit integer atomic (order-independent: bit-reproducible).  A sweep covers
+            // kScoreW words (registers: 4 x kScoreW column sums beside the 128 accumulators); categories beyond it take a
+            // second sweep over the same accumulators.
+            uint64_t *const score_cols = reinterpret_cast<uint64_t *>(bexp);   // [4 waves][128 columns][1 + K]
+            auto score_epilogue = [&](uint32_t st) {
+              if constexpr (kScore) {
+                const double win = aa.flank;   // the window w (integer-valued)
+                uint64_t *const rows_lds = reinterpret_cast<uint64_t *>(ctab32) + wave * (kRows64 * 9u);   // [64 rows][1 + K]
+                uint32_t ln = lane;   // (lane-derived values recomputed from an opaque copy of the lane id: see epilogue_f32)
+                asm volatile("" : "+v"(ln));
+                const uint32_t l32e = ln & 31u, halfe = ln >> 5;
+                double ca[4], cs[4], cpos[4];   // this lane's four columns
+                uint32_t cmask[4];              // (annotation << 1) | 1: bit c selects word c
+#pragma unroll
+                for (int tt = 0; tt < 4; ++tt) {
+                    const d2s c0 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32e) * kStat);
+                    const d2s c1 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32e) * kStat + 2u);
+                    ca[tt] = c0.x;
+                    cs[tt] = c0.y;
+                    cpos[tt] = c1.x;
+                    cmask[tt] = ((uint32_t)c1.y << 1) | 1u;
+                }
+                const uint32_t j0 = t * kSlab + l32e;   // column of tile tt: j0 + 32 tt
+                for (uint32_t w0 = 0; w0 < st; w0 += (uint32_t)kScoreW) {   // wave-uniform sweeps
+                    uint64_t csum[4][kScoreW];
+#pragma unroll
+                    for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+                        for (int c = 0; c < kScoreW; ++c) csum[tt][c] = 0;
+#pragma unroll 1
+                    for (int e = 0; e < 16; ++e) {
+#pragma unroll
+                        for (int m = 0; m < 2; ++m) {
+                            accel_t c4[4];   // ONE register-indexed read per accumulator, pinned (see area_epilogue)
+#pragma unroll
+                            for (int tt = 0; tt < 4; ++tt) {
+                                c4[tt] = acc[m][tt][e];
+                                asm volatile("" : "+v"(c4[tt]));
+                            }
+                            const uint32_t ri = 32u * m + (uint32_t)(e & 3) + 8u * (uint32_t)(e >> 2) + 4u * halfe;
+                            const d2s r0 = *reinterpret_cast<const d2s *>(rstat + ri * kStat);   // two addresses per wave: broadcast
+                            const d2s r1 = *reinterpret_cast<const d2s *>(rstat + ri * kStat + 2u);
+                            const uint32_t rmask = (((uint32_t)r1.y << 1) | 1u) >> w0;
+                            const uint32_t i = row0 + ri;
+                            uint64_t rsum[kScoreW];
+#pragma unroll
+                            for (int c = 0; c < kScoreW; ++c) rsum[c] = 0;
+#pragma unroll
+                            for (int tt = 0; tt < 4; ++tt) {
+                                const double cnt = kFp4 ? (double)c4[tt] : (double)((uint32_t)c4[tt] >> 3);   // int8: 8 n11
+                                uint64_t term = score_term(r32_cell(cnt, n, r0.x, r0.y, ca[tt], cs[tt]).r);
+                                const bool ok = i > j0 + 32u * tt && i < n_snps && r1.x - cpos[tt] <= win;
+                                term = ok ? term : 0u;
+                                const uint32_t cm = cmask[tt] >> w0;
+#pragma unroll
+                                for (int c = 0; c < kScoreW; ++c) {
+                                    rsum[c] += ((cm >> c) & 1u) ? term : 0u;
+                                    csum[tt][c] += ((rmask >> c) & 1u) ? term : 0u;
+                                }
+                            }
+#pragma unroll
+                            for (int c = 0; c < kScoreW; ++c) {
+                                if (w0 + (uint32_t)c >= st) break;   // wave-uniform
+                                const uint64_t v = dpp_half_sum(rsum[c]);
+                                if (l32e == 31u) rows_lds[ri * st + w0 + (uint32_t)c] = v;
+                            }
+                        }
+                    }
+                    // the halves' column sums meet: half 0 keeps column tiles 0, 1, half 1 tiles 2, 3 (one shuffle per pair)
+                    uint64_t *const my_cols = score_cols + (size_t)wave * (kSlab * 9u);
+#pragma unroll
+                    for (int c = 0; c < kScoreW; ++c) {
+                        if (w0 + (uint32_t)c >= st) break;   // wave-uniform
+#pragma unroll
+                        for (int p = 0; p < 2; ++p) {
+                            const uint64_t send = halfe ? csum[p][c] : csum[2 + p][c];
+                            const uint64_t mine = halfe ? csum[2 + p][c] : csum[p][c];
+                            const uint64_t got = __shfl_xor(send, 32);
+                            my_cols[(32u * (2u * halfe + (uint32_t)p) + l32e) * st + w0 + (uint32_t)c] = mine + got;
+                        }
+                    }
+                }
+                // this wave's row totals -> sums (its own table: a wave-level barrier suffices)
+                __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): the table writes have landed
+                __builtin_amdgcn_wave_barrier();
+                uint64_t *const sums = reinterpret_cast<uint64_t *>(aa.hits);
+                for (uint32_t f = lane; f < kRows64 * st; f += 64u) {
+                    const uint32_t i = row0 + f / st;
+                    const uint64_t v = rows_lds[f];
+                    if (v != 0u && i < n_snps) atomicAdd(reinterpret_cast<unsigned long long *>(sums) + (size_t)i * st + f % st, (unsigned long long)v);
+                }
+              }
+            };
             auto area_epilogue = [&]() {
-              if constexpr (kArea && MM == 2) {
+              if constexpr (kArea && MM == 2 && !kScore) {
                 uint64_t slot = hit_slot, slot_end = hit_slot_end;
                 const double kthr = aa.k_thres;
                 const bool prefilter = aa.k_thres > 2.0;
@@ -1559,6 +1706,23 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 hit_slot_end = slot_end;
               }
             };
+            if constexpr (kScore) {
+                const uint32_t st = 1u + (uint32_t)aa.measure;   // words per SNP: column 0 and K categories
+                if (active) score_epilogue(st);
+                block_sync();   // every wave's column sums are in LDS
+                uint64_t *const sums = reinterpret_cast<uint64_t *>(aa.hits);
+                for (uint32_t f = tid; f < kSlab * st; f += kMfmaThreads) {   // the four waves' sums, one atomic per word
+                    uint64_t v = 0;
+#pragma unroll
+                    for (uint32_t w = 0; w < (uint32_t)kMfmaWaves; ++w)
+                        if (pass + w >= seg_begin && pass + w < seg_end) v += score_cols[w * (kSlab * 9u) + f];   // active waves only
+                    const uint32_t j = t * kSlab + f / st;
+                    if (v != 0u && j < n_snps) atomicAdd(reinterpret_cast<unsigned long long *>(sums) + (size_t)j * st + f % st, (unsigned long long)v);
+                }
+                if (tid == 0) tickets[parity] = next_ticket;
+                if (!(ablate & 16)) __builtin_amdgcn_s_setprio(0);
+                return;
+            }
             if constexpr (kArea) {
                 area_epilogue();
                 if (tid == 0) tickets[parity] = next_ticket;
@@ -1991,7 +2155,133 @@ int area_mfma(const void *alt, const double *fa, const double *fr, const double 
     return LDX_OK;
 }
 
+// ---- LD scores on the band (ldx_ld_score_dev) ------------------------------------------------------------------------
+// Every SNP's own term (r32_diag squared as score_term) WRITES its words -- the call needs no memset of `sums` -- and the
+// two-row query list {0, n - 1} the plan kernel reads (every SNP a query: the plan then keeps every tile's whole band).
+__global__ void score_init_kernel(const uint32_t *__restrict__ acnt, const uint32_t *__restrict__ rcnt,
+                                  const uint8_t *__restrict__ annot, uint32_t st, uint32_t n_snps, uint32_t n_hap,
+                                  uint64_t *__restrict__ sums, uint32_t *__restrict__ qrows)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) {
+        qrows[0] = 0u;
+        qrows[1] = n_snps - 1u;
+    }
+    if (i >= n_snps) return;
+    const uint64_t t = score_self_term(acnt[i], rcnt[i], n_hap);
+    const uint32_t m = annot ? ((uint32_t)annot[i] << 1) | 1u : 1u;   // bit c selects word c
+    for (uint32_t c = 0; c < st; ++c) sums[(size_t)i * st + c] = ((m >> c) & 1u) ? t : 0u;
+}
+
+// the band's workspace (area_mfma's layout) + 256 bytes: the two query rows and the plan kernel's (unused) hit counter
+size_t score_mfma_workspace_bytes(uint32_t n_snps) { return area_mfma_workspace_bytes(n_snps) + 256u; }
+
+template <bool kFp4, int kW>
+static int launch_score(const void *alt, const double *fa, const double *fr, uint32_t n_snps, uint32_t n_hap, uint32_t T,
+                        uint32_t nch, uint64_t units, size_t lds, const AreaArgs &aa, uint32_t *sched, hipStream_t s)
+{
+    static std::atomic<uint64_t> opted{0};   // the dynamic LDS opt-in: once per device (72 KiB)
+    int dev = 0;
+    LDX_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !((opted.load(std::memory_order_relaxed) >> dev) & 1u)) {
+        LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, kW>,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (dev >= 0 && dev < 64) opted.fetch_or(1ull << dev, std::memory_order_relaxed);
+    }
+    triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, kW><<<(uint32_t)device_cus() * 2u, kMfmaThreads, lds, s>>>(
+        (const uint4 *)alt, fa, fr, nullptr, n_snps, T, nch, (double)n_hap, 1.0 / (double)n_hap, 0, units * 8u,
+        (ldx_ld32 *)nullptr, nullptr, nullptr, 0u, 0u, 0u, sched, 0, nullptr, aa);
+    LDX_HIP(hipGetLastError());
+    return LDX_OK;
+}
+
+int score_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
+               uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, const uint8_t *annot,
+               uint32_t n_annot, bool fp4, uint64_t *sums, void *workspace, hipStream_t s)
+{
+    const uint32_t T = n_slabs(n_snps), nch = n_chunks(n_hap);
+    if ((uint64_t)T * nch * kSlab * 16u >= (1ull << 32)) {   // the K loop addresses the plane with 32-bit lane offsets
+        set_error("ldx_ld_score_dev: a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", n_snps, n_hap);
+        return LDX_E_UNSUPPORTED;
+    }
+    // the band's buffers, carved as in area_mfma (its query mask stays unused)
+    char *w = (char *)workspace + ((size_t)n_snps + 255u) / 256u * 256u;
+    uint32_t *pass_base = (uint32_t *)w;
+    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
+    uint32_t *g_end = (uint32_t *)w;
+    w += ((size_t)T * 4u + 255u) / 256u * 256u;
+    uint32_t *g_begin = (uint32_t *)w;
+    w += ((size_t)T * 4u + 255u) / 256u * 256u;
+    uint32_t *first_base = (uint32_t *)w;
+    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
+    uint32_t *order = area_order_entries(n_snps) ? (uint32_t *)w : nullptr;
+    w += (area_order_entries(n_snps) * 4u + 255u) / 256u * 256u;
+    uint32_t *sched = (uint32_t *)w;
+    w += kAreaSchedWords * 4u;
+    uint32_t *qrows = (uint32_t *)w;                               // [2]
+    unsigned long long *n_hits = (unsigned long long *)(w + 8);   // the plan kernel zeroes it; nothing reads it
+    const uint32_t st = 1u + n_annot;
+    score_init_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(acnt, rcnt, n_annot ? annot : nullptr, st, n_snps, n_hap, sums, qrows);
+    LDX_HIP(hipGetLastError());
+    if (n_snps < 2) return LDX_OK;   // no pairs
+    // the plan keeps, per j-tile, the rows with pos <= pos(last column) + window: every pair with pos_i - pos_j <= window
+    // (|delta| = window included); score_epilogue applies the exact symmetric bound per pair
+    area_band_plan_kernel<<<1, 1024, 0, s>>>(positions, n_snps, T, window, qrows, 2u, g_begin, g_end, pass_base, n_hits,
+                                             order, first_base, sched);
+    LDX_HIP(hipGetLastError());
+    AreaArgs aa{};
+    aa.f32 = f32_const((double)n_hap);
+    aa.pos = positions;
+    aa.is_query = n_annot ? annot : nullptr;   // score: the annotation masks (null: none)
+    aa.pass_base = pass_base;
+    aa.g_begin = g_begin;
+    aa.g_end = g_end;
+    aa.order = order;
+    aa.hits = (ldx_hit *)sums;                 // score: the uint64 sums [n_snps][1 + n_annot]
+    aa.n_hits = n_hits;
+    aa.flank = (double)window;
+    aa.measure = (int)n_annot;                 // score: K
+    const uint64_t units = ldx_triangle_units(n_snps) / 8u;   // 64-row units of the full triangle
+    const size_t lds = mfma_lds_bytes(kRows64, false, false) + (size_t)kMfmaWaves * kRows64 * 9u * sizeof(uint64_t);   // + the row tables
+    if (fp4)
+        return n_annot ? launch_score<true, 3>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s)
+                       : launch_score<true, 1>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
+    return n_annot ? launch_score<false, 3>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s)
+                   : launch_score<false, 1>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
+}
+
 }  // namespace ldx
+
+extern "C" size_t ldx_ld_score_workspace_bytes(uint32_t n_snps, uint32_t n_hap)
+{
+    (void)n_hap;   // (the layout depends on the SNP count alone)
+    return ldx::score_mfma_workspace_bytes(n_snps ? n_snps : 1u);
+}
+
+extern "C" int ldx_ld_score_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
+                                uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, const uint8_t *annot,
+                                uint32_t n_annot, int path, uint64_t *sums, void *workspace, size_t workspace_bytes,
+                                void *stream)
+{
+    LDX_REQUIRE(alt && acnt && rcnt && fa && fr && positions && sums && workspace, "null pointer");
+    LDX_REQUIRE(n_annot <= 8u, "at most 8 annotation categories");
+    LDX_REQUIRE(annot || n_annot == 0u, "annot is null but n_annot > 0");
+    LDX_REQUIRE(n_snps >= 1 && n_hap >= 1 && window >= 0, "bad shape");
+    LDX_REQUIRE(((uintptr_t)workspace & 255u) == 0, "workspace must be 256-byte aligned");
+    LDX_REQUIRE(workspace_bytes >= ldx::score_mfma_workspace_bytes(n_snps), "workspace too small (see ldx_ld_score_workspace_bytes)");
+    LDX_REQUIRE(path == LDX_PATH_AUTO || path == LDX_PATH_POPCOUNT || path == LDX_PATH_MFMA || path == LDX_PATH_FP4, "unknown path");
+    if (n_hap > LDX_MAX_HAPS) {
+        ldx::set_error("ldx_ld_score_dev: n_hap %u > LDX_MAX_HAPS %u", n_hap, LDX_MAX_HAPS);
+        return LDX_E_UNSUPPORTED;
+    }
+    if (path == LDX_PATH_POPCOUNT) {
+        ldx::set_error("ldx_ld_score_dev: LD scores run on the matrix-pipe band (LDX_PATH_FP4 / LDX_PATH_MFMA), not on the popcount kernels");
+        return LDX_E_UNSUPPORTED;
+    }
+    const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles: keep pos + window exact
+    return ldx::score_mfma(alt, acnt, rcnt, fa, fr, n_snps, n_hap, positions, window < wmax ? window : wmax, annot, n_annot,
+                           path != LDX_PATH_MFMA, sums, workspace, (hipStream_t)stream);
+}
 
 // ---- peak-rate probe for the matrix pipe: back-to-back int8 MFMAs on 8 independent accumulators,
 // operands in registers, no memory traffic.  variant 0: 32x32x32 (32 K MACs), 1: 16x16x64 (16 K MACs).

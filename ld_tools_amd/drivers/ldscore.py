@@ -1,0 +1,106 @@
+"""LD scores of one chromosome in the LDSC file layout: for every variant the sum of r^2 over the variants within
+``window_bp`` of it (itself included), optionally per annotation category -- the ``l2`` files that LD score regression and
+stratified LDSC read.  Not a reference workflow: it takes the inputs of drivers/rmatrix.py and runs ops.ld_score on the
+matrix-pipe band (include/ldx.h, ldx_ld_score_dev).
+
+r is the haplotype-based correlation of the ALT-allele indicators with n = n_hap (include/ldx.h, LDX_OUT_R32), and the
+unbiased estimate (``adjust``) uses n_obs = n_hap.  ``ldsc.py --l2`` estimates r^2 from diploid dosages over the samples
+instead, so its values are close to these but not identical.
+"""
+from __future__ import annotations
+
+import gzip
+from dataclasses import dataclass
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from .._lib import LdxError
+from ..ops import LDScores, ld_score
+from ..panel import PackedPanel
+from .ingest import RaggedGenotypesError, codes_matrix
+from .triangle import fetch_variants
+
+
+@dataclass
+class LDScoreTable:
+    """Row k is variant k of these lists (position-sorted; variants without a matching record are left out)."""
+
+    chrom: str
+    rs_ids: List[str]
+    poss: List[int]
+    alt_freqs_exact: np.ndarray       # float64 a / n_hap per variant (the MAF filter of M_5_50)
+    annot: Optional[np.ndarray]       # bool [n, K] in row order, or None
+    annot_names: List[str]
+    scores: LDScores
+    adjust: bool
+
+    @property
+    def n(self) -> int:
+        return len(self.rs_ids)
+
+    def values(self) -> np.ndarray:
+        """float64 [n, K or 1]: the written columns (the per-category columns with an annotation, else column 0)."""
+        v = self.scores.adjusted() if self.adjust else self.scores.l2
+        return v[:, 1:] if self.annot is not None else v[:, :1]
+
+
+def ld_scores(vcf, chrom, chrom_rows: Sequence[Sequence], sample_names: Sequence[str], window_bp: int = 1_000_000,
+              annot=None, annot_names: Optional[Sequence[str]] = None, adjust: bool = True) -> LDScoreTable:
+    """LD scores of one chromosome's variants, from the inputs of ``r_matrix`` (VCF rows [pos, rsID]; each record fetched
+    once).  ``annot``: bool / 0-1 [len(chrom_rows), K], K <= 8, one row per input row; ``annot_names``: K column names
+    (default A0, A1, ...).  ``adjust``: write LDSC's unbiased r^2 (LDScores.adjusted) rather than r^2.  Mixed-ploidy panels
+    (genotype lists of different lengths) are out of scope: LdxError."""
+    order = sorted(range(len(chrom_rows)), key=lambda k: chrom_rows[k][0])   # fetch_variants' stable sort
+    cv = fetch_variants(vcf, chrom, chrom_rows, sample_names)
+    keep = [k for k, rec in enumerate(cv.recs) if rec is not None]
+    if not keep:
+        raise LdxError(f"ld_scores: no variant of chromosome {chrom} has a matching record")
+    ann = None
+    names: List[str] = []
+    if annot is not None:
+        a = np.asarray(annot)
+        if a.ndim == 1:
+            a = a[:, None]
+        if a.shape[0] != len(chrom_rows):
+            raise LdxError("ld_scores: annot needs one row per input row")
+        if a.dtype != bool and not np.isin(a, (0, 1)).all():
+            raise LdxError("ld_scores: annot must be boolean or 0/1")
+        ann = a.astype(bool)[np.asarray(order, dtype=np.int64)][np.asarray(keep, dtype=np.int64)]
+        names = list(annot_names) if annot_names is not None else [f"A{k}" for k in range(ann.shape[1])]
+        if len(names) != ann.shape[1]:
+            raise LdxError("ld_scores: one name per annotation column")
+    try:
+        codes = codes_matrix([cv.genotypes[k] for k in keep])
+    except ZeroDivisionError as exc:   # a record that carries none of the samples
+        raise LdxError(f"ld_scores: a variant of chromosome {chrom} has no genotype of the selected samples") from exc
+    except RaggedGenotypesError as exc:
+        raise LdxError(f"ld_scores: mixed ploidy on chromosome {chrom} ({exc}); LD scores need one haplotype count") from exc
+    panel = PackedPanel.from_codes(codes)
+    poss = [cv.poss[k] for k in keep]
+    res = ld_score(panel, np.asarray(poss, dtype=np.int64), window_bp=window_bp, annot=ann)
+    fa = panel.alt_counts().astype(np.float64) / panel.n_hap
+    return LDScoreTable(str(chrom), [cv.rs_ids[k] for k in keep], poss, fa, ann, names, res, adjust)
+
+
+def write_ldscore(base: str, table: LDScoreTable) -> List[str]:
+    """``{base}.l2.ldscore.gz``: tab-separated CHR, SNP, BP and one column per category ({name}L2; L2 without an
+    annotation), values as %.3f, degenerate variants (no ALT or no REF allele) left out; ``{base}.l2.M``: one line, per
+    column the number of written variants in the category; ``{base}.l2.M_5_50``: the same for MAF = min(fa, 1 - fa) > 0.05.
+    Returns the three paths."""
+    live = table.scores.live
+    vals = table.values()
+    cols = [f"{nm}L2" for nm in table.annot_names] if table.annot is not None else ["L2"]
+    inc = table.annot if table.annot is not None else np.ones((table.n, 1), dtype=bool)
+    fa = np.asarray(table.alt_freqs_exact, dtype=np.float64)
+    common = np.minimum(fa, 1.0 - fa) > 0.05
+    gz, mp, m550 = base + ".l2.ldscore.gz", base + ".l2.M", base + ".l2.M_5_50"
+    with gzip.open(gz, "wt") as out:
+        out.write("\t".join(["CHR", "SNP", "BP"] + cols) + "\n")
+        for k in np.flatnonzero(live):
+            out.write("\t".join([table.chrom, table.rs_ids[k], str(table.poss[k])] + ["%.3f" % x for x in vals[k]]) + "\n")
+    with open(mp, "w") as out:
+        out.write("\t".join(str(int((inc[:, c] & live).sum())) for c in range(inc.shape[1])) + "\n")
+    with open(m550, "w") as out:
+        out.write("\t".join(str(int((inc[:, c] & live & common).sum())) for c in range(inc.shape[1])) + "\n")
+    return [gz, mp, m550]

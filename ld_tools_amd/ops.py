@@ -2,6 +2,7 @@
 
     ld_triangle(panel)                      <- ld_triangle.py:133-230  (all row > col pairs)
     ld_area(panel, positions, queries, ...) <- ld_area.py:152-276      (windowed scan, thresholded hits)
+    ld_score(panel, positions, ...)         LD scores: windowed sums of r^2 per SNP (LDSC's l2), optionally per category
     pair_counts(panel_i, panel_j)           <- calc_ld.py:32           (bit-exact n11 block)
     ld_from_counts(n, n11, a1, r1, a2, r2)  <- calc_ld.py:33-97        (the epilogue alone)
 
@@ -18,7 +19,7 @@ import torch
 
 from . import _lib
 from ._lib import MEASURES, UNIT_PAIRS, check, lib
-from .panel import PackedPanel, _ptr, _stream_ptr
+from .panel import PackedPanel, _ptr, _stream_ptr, require_gpu
 
 
 PATHS = {"auto": 0, "popcount": 1, "mfma": 2, "fp4": 3}
@@ -537,6 +538,170 @@ def ld_area(panel: PackedPanel, positions, queries: Optional[Sequence[int]] = No
     if use_band:
         band = lambda: int(word.view(torch.int32).item())    # noqa: E731
     return AreaHits(qrow, orow, ld32, count_pairs, offsets, band)
+
+
+# --------------------------------------------------------------------------- LD scores
+SCORE_SCALE = float(1 << 32)    # sums are integers in units of 2^-32 r^2 (include/ldx.h, ldx_ld_score_dev)
+MAX_ANNOT = 8
+
+
+def score_terms(r) -> np.ndarray:
+    """Host mirror of the kernel's term (include/ldx.h, ldx_ld_score_dev): rint(2^32 * (r *f32 r)) as uint64, from float32 r
+    cells (ld_triangle(fmt="r32") / TriangleResult.r_matrix()).  One float32 multiply, then exact scaling and round-half-even."""
+    r = np.asarray(r, dtype=np.float32)
+    r2 = np.multiply(r, r, dtype=np.float32)
+    return np.rint(np.ldexp(r2.astype(np.float64), 32)).astype(np.uint64)
+
+
+def window_bounds(positions, window: int) -> Tuple[np.ndarray, np.ndarray]:
+    """[lo, hi) row range of every SNP's window |pos_i - pos_j| <= window over non-decreasing positions."""
+    pos = np.asarray(positions, dtype=np.int64)
+    lo = np.searchsorted(pos, pos - window, side="left")
+    hi = np.searchsorted(pos, pos + window, side="right")
+    return lo, hi
+
+
+def window_counts(positions, window: int, live, annot_bits=None, n_annot: int = 0) -> np.ndarray:
+    """m of LDSC: int64 [n, 1 + n_annot], the number of SNPs j with |pos_i - pos_j| <= window (i itself included) that are
+    `live` (not degenerate) and -- column 1 + k -- carry bit k of annot_bits[j]."""
+    lo, hi = window_bounds(positions, window)
+    live = np.asarray(live, dtype=bool)
+    cols = [live]
+    if n_annot:
+        bits = np.asarray(annot_bits, dtype=np.uint8)
+        cols += [live & (((bits >> k) & 1) != 0) for k in range(n_annot)]
+    ind = np.stack(cols, axis=1).astype(np.int64)
+    pre = np.concatenate([np.zeros((1, ind.shape[1]), dtype=np.int64), np.cumsum(ind, axis=0)])
+    return pre[hi] - pre[lo]
+
+
+def adjust_l2(l2, m, n_obs: int) -> np.ndarray:
+    """LDSC's unbiased r^2, r^2 - (1 - r^2) / (n_obs - 2), summed over a window: linear in r^2, so it applies to the sums
+    as (n_obs - 1) / (n_obs - 2) * L - m / (n_obs - 2) with m the number of terms (window_counts)."""
+    if n_obs <= 2:
+        raise _lib.LdxError("adjusted() needs n_obs > 2")
+    return (n_obs - 1) / (n_obs - 2) * np.asarray(l2, dtype=np.float64) - np.asarray(m, dtype=np.float64) / (n_obs - 2)
+
+
+def pack_annot(annot, n_snps: int) -> Tuple[np.ndarray, int]:
+    """bool / 0-1 array [n, K] (or [n] for K = 1), K <= 8 -> (uint8 bitmask per SNP, K)."""
+    a = np.asarray(annot)
+    if a.ndim == 1:
+        a = a[:, None]
+    if a.ndim != 2 or a.shape[0] != n_snps:
+        raise _lib.LdxError(f"annot must have shape [n_snps, K] (n_snps = {n_snps}), got {a.shape}")
+    k = a.shape[1]
+    if k > MAX_ANNOT:
+        raise _lib.LdxError(f"at most {MAX_ANNOT} annotation categories (got {k})")
+    if a.dtype != bool and not np.isin(a, (0, 1)).all():
+        raise _lib.LdxError("annot must be boolean or 0/1")
+    ab = a.astype(bool)
+    bits = np.zeros(n_snps, dtype=np.uint8)
+    for j in range(k):
+        bits |= (ab[:, j].astype(np.uint8) << j)
+    return bits, k
+
+
+@dataclass
+class LDScores:
+    """LD scores of one panel (ld_score).  ``sums`` is the device uint64 tensor [n, 1 + K] the kernel wrote (units of 2^-32
+    r^2); ``l2`` (float64 [n, 1 + K]) = sums / 2^32 and ``m`` (int64 [n, 1 + K]: non-degenerate SNPs in each window and
+    category, self included) are computed on the host when first asked for."""
+
+    sums: torch.Tensor
+    positions: np.ndarray
+    window: int
+    n_hap: int
+    annot_bits: Optional[np.ndarray]
+    n_annot: int
+    panel: Optional[PackedPanel] = None
+    _l2: Optional[np.ndarray] = None
+    _m: Optional[np.ndarray] = None
+    _live: Optional[np.ndarray] = None
+
+    @property
+    def live(self) -> np.ndarray:
+        """bool [n]: the SNP is not degenerate (a r > 0: it has ALT and REF codes)."""
+        if self._live is None:
+            self._live = (self.panel.alt_counts().astype(np.int64) * self.panel.ref_counts().astype(np.int64)) > 0
+        return self._live
+
+    @property
+    def l2(self) -> np.ndarray:
+        if self._l2 is None:
+            self._l2 = self.sums.cpu().numpy().astype(np.float64) / SCORE_SCALE
+        return self._l2
+
+    @property
+    def m(self) -> np.ndarray:
+        if self._m is None:
+            pos = self.positions.cpu().numpy() if isinstance(self.positions, torch.Tensor) else self.positions
+            self._m = window_counts(pos, self.window, self.live, self.annot_bits, self.n_annot)
+        return self._m
+
+    def adjusted(self, n_obs: Optional[int] = None) -> np.ndarray:
+        """LDSC's unbiased r^2 estimate summed over the windows (adjust_l2), n_obs defaulting to n_hap."""
+        return adjust_l2(self.l2, self.m, self.n_hap if n_obs is None else int(n_obs))
+
+
+def ld_score(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, window_snps: Optional[int] = None,
+             annot=None, path: Optional[str] = None, workspace: Optional[torch.Tensor] = None,
+             check_positions: bool = True) -> LDScores:
+    """LD scores on the matrix-pipe band: for every SNP i, the sum of r^2 over the SNPs j with |pos_i - pos_j| <= window
+    (i itself included), and with ``annot`` (bool / 0-1 [n, K], K <= 8) the same sum per category over the j that carry it
+    (include/ldx.h, ldx_ld_score_dev).  r is the signed r of ld_triangle(fmt="r32"), bit for bit; the sums are exact
+    integer sums of rint(2^32 r^2), so they are reproducible run to run.
+
+    ``window_snps`` counts the window in SNPs instead of base pairs (positions 0 .. n-1).  ``path``: 'fp4' (default) or
+    'mfma' (the int8 band: identical sums).  ``workspace``: a uint8 device tensor of ldx_ld_score_workspace_bytes() bytes to
+    reuse (one per launch that may be in flight); by default one is allocated per call.  The call is stream-ordered: the
+    host reads nothing until ``.l2`` / ``.m`` are asked for (a device tensor of positions is checked on the device unless
+    ``check_positions`` is False).
+    """
+    require_gpu()
+    n = panel.n_snps
+    if panel.n_hap > _lib.MAX_HAPS:
+        raise _lib.LdxError(f"n_hap {panel.n_hap} > LDX_MAX_HAPS {_lib.MAX_HAPS}")
+    if window_snps is not None:
+        window = int(window_snps)
+        pos_h = np.arange(n, dtype=np.int64)
+        pos = torch.arange(n, dtype=torch.int64, device=panel.device)
+    else:
+        window = int(window_bp)
+        if positions is None:
+            raise _lib.LdxError("ld_score needs positions (or window_snps)")
+        if isinstance(positions, torch.Tensor):
+            pos = positions.to(panel.device, dtype=torch.int64).contiguous()
+            if check_positions and pos.numel() > 1 and bool((pos[1:] < pos[:-1]).any().item()):
+                raise _lib.LdxError("positions must be non-decreasing (VCF order)")
+            pos_h = None
+        else:
+            pos_h = np.ascontiguousarray(np.asarray(positions, dtype=np.int64))
+            if pos_h.size > 1 and bool((pos_h[1:] < pos_h[:-1]).any()):
+                raise _lib.LdxError("positions must be non-decreasing (VCF order)")
+            pos = torch.as_tensor(pos_h).to(panel.device)
+        if pos.numel() != n:
+            raise _lib.LdxError("positions must have one entry per SNP")
+    if window < 0:
+        raise _lib.LdxError("the window must be >= 0")
+    bits, k = (None, 0) if annot is None else pack_annot(annot, n)
+    annot_d = torch.as_tensor(bits).to(panel.device) if k else None
+    pcode = PATHS["fp4"] if path is None else PATHS[path]
+    need = lib.ldx_ld_score_workspace_bytes(n, panel.n_hap)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=panel.device)
+    elif workspace.numel() * workspace.element_size() < need:
+        raise _lib.LdxError(f"workspace too small: {need} bytes needed")
+    sums = torch.empty((n, 1 + k), dtype=torch.uint64, device=panel.device)
+    check(lib.ldx_ld_score_dev(panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), panel.fa.data_ptr(),
+                               panel.fr.data_ptr(), n, panel.n_hap, pos.data_ptr(), window, _ptr(annot_d), k, pcode,
+                               sums.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                               _stream_ptr()), "ldx_ld_score_dev")
+    res = LDScores(sums, pos_h, window, panel.n_hap, bits, k, panel)
+    if pos_h is None:   # positions stayed on the device: fetched with m
+        res.positions = pos      # type: ignore[assignment]
+    res._keep = (pos, annot_d, workspace)   # alive until the launch is done (stream-ordered frees would allow reuse anyway)
+    return res
 
 
 # --------------------------------------------------------------------------- instrumentation
