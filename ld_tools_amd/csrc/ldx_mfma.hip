@@ -546,6 +546,11 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             const uint32_t g64 = (uint32_t)((vv < te ? vv : pass) - tb) + 2u * t;   // a row group inside the panel either way
             const uint32_t roff = MM == 1 ? 32u * hsel : 0u;                        // half-height: rows roff .. roff+31 of the unit
             const uint32_t row0 = g64 * kRows64 + roff;
+            // FP4 triangle: a unit whose rows are all padding (the last row group of a panel padded to whole tiles, at 10 000
+            // SNPs one unit per tile) holds no pair of the triangle.  It takes the idle K loop below -- its share of the j-tile
+            // image and the barriers, nothing else -- and stores zero cells instead of an epilogue (epilogue_f32).
+            const bool pad_only = kF32Tier && row0 >= n_snps;
+            const bool counting = active && !pad_only;   // wave-uniform
             // this lane's A rows: row0 + 32*m + l32 (both inside one slab: 64 | 128)
             // FP4: each lane half streams its own chunk of a K-block (half 0: chunk 2b, half 1: chunk 2b + 1)
             const uint4 *ai = alt + ((size_t)(row0 / kSlab) * nchunks) * kSlab + (row0 % kSlab) + l32 + (kFp4 ? half * kSlab : 0u);
@@ -825,7 +830,8 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 LDX_CSTAMP(5)                                                                                      \
             }
             // A wave whose unit lies outside the tile's segment (the last pass of a tile: 2 of 4 units every other tile of the
-            // triangle, ~1.5 of 20 in the band's five passes per tile at +-1000 rows) has nothing to count: it keeps up its
+            // triangle, ~1.5 of 20 in the band's five passes per tile at +-1000 rows), or whose rows are all padding
+            // (pad_only), has nothing to count: it keeps up its
             // share of the j-tile image -- the same loads and the same image writes on the same side of the per-block
             // barrier -- and issues no fragment reads and no MFMAs, which would only compete with the CU's other workgroup.
 #define LDX_CHUNK_IDLE(NXT, FAR, cc)                                                                               \
@@ -843,7 +849,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 asm volatile("" : "+v"(br[FAR]));                                                                  \
                 bquarter(bexp + (c_ & 1u) * kBBuf, br[FAR], 0);                                                    \
             }
-            if (__builtin_expect(!active, 0)) {   // wave-uniform
+            if (__builtin_expect(!counting, 0)) {   // wave-uniform
                 for (uint32_t c = 0; c < nch_run; c += 3) {
                     LDX_CHUNK_IDLE(1, 2, c)
                     if (c + 1 < nch_run) LDX_CHUNK_IDLE(2, 0, c + 1)
@@ -1062,7 +1068,10 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             // fp64 tier (ld_multi_fast2, and the op-for-op mirror behind it) has the registers it wants -- eight entries
             // at a time, one parked PAIR per lane: the rare path runs at full lane occupancy.  A unit that parks more steps
             // than the queue holds is redone as a whole by the fp64 epilogue (returns false).
-            auto epilogue_f32 = [&](bool all_ordinary) -> bool {
+            // `edge` (wave-uniform): the unit reaches the diagonal, pad rows or the last tile's pad columns.  Its cells that are
+            // not pairs of the triangle (row <= col, row or col >= n_snps) are forced to zero_cell per step under a scalar lane
+            // mask (the kDeg instantiation, after the int-0 forcing), and the drain re-applies the same test to what parked.
+            auto epilogue_f32 = [&](bool all_ordinary, bool edge) -> bool {
               if constexpr (kF32Tier) {
                 if (ablate & 1) return true;   // tuning: no epilogue at all
                 // this unit's cells: a wave-uniform base (scalar registers) + a per-lane constant + a per-step scalar offset
@@ -1082,6 +1091,12 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 const uint32_t lane_off_b = lane_off * (uint32_t)sizeof(Cell);
                 const float *const rt = rtab32 + halfe * 16u, *const ct = ctab32 + l32e * 4u;
                 const uint32_t grp0 = roff / kGroup;   // first 8-row group of this wave's rows inside the unit (scalar)
+                if (pad_only) {   // wave-uniform: zero cells for this wave's 4 MM small units (contiguous), 1 KiB per store
+#pragma unroll 1
+                    for (uint32_t k = 0; k < 4u * MM * (uint32_t)sizeof(Cell); ++k)
+                        store_cells4_saddr(reinterpret_cast<uint32_t *>(ubase + grp0 * LDX_UNIT_PAIRS) + k * 256u, ln * 16u, 0u, 0u, 0u, 0u);
+                    return true;
+                }
                 uint32_t qn = 0;   // parked steps (wave-uniform)
                 F32Col cols[4];    // this lane's four columns: held for the sixteen steps (16 registers; no spills at 256)
 #pragma unroll
@@ -1110,10 +1125,22 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                     for (int tt = 0; tt < 4; ++tt) f32_split_a(cols[tt].a, cols[tt].a, cal[tt]);
                 }
                 // the sixteen steps, in four instantiations: n <= 4096 needs no error term for the product a1 a2 (ldx_common.h);
-                // kDeg forces the cells of degenerate rows / columns to the int-0 code (one v_cndmask per cell)
+                // kDeg forces the cells of degenerate rows / columns to the int-0 code (one v_cndmask per cell), and in an edge
+                // unit the cells outside the triangle to zero_cell (one more, behind a scalar branch)
                 auto steps = [&](auto small_c, auto deg_c) -> bool {
                 constexpr bool kDeg = decltype(deg_c)::value;
                 [[maybe_unused]] const uint32_t forced = sizeof(Cell) == 4 ? ((uint32_t)LDX_K16_INT0 << 16 | LDX_K16_INT0) : 0x80000000u;   // int 0, int 0
+                // edge units: the lanes of column tile tt whose cells with this step's rows i0 (lanes 0-31) and i0 + 4 (lanes
+                // 32-63) are not pairs of the triangle.  Cell (i, j) is one iff j < i < n_snps, i.e. j < lim = (i < n_snps ? i : 0),
+                // i.e. l32 < lim - j0: the lanes from there up are invalid.  Scalar arithmetic on wave-uniform values.
+                [[maybe_unused]] auto outside = [&](uint32_t i0, int tt) -> uint64_t {
+                    const uint32_t j0 = t * kSlab + 32u * (uint32_t)tt;
+                    auto half32 = [&](uint32_t i) -> uint32_t {
+                        const uint32_t lim = i < n_snps ? i : 0u;
+                        return lim <= j0 ? 0xFFFFFFFFu : (lim - j0 >= 32u ? 0u : 0xFFFFFFFFu << (lim - j0));
+                    };
+                    return (uint64_t)half32(i0) | ((uint64_t)half32(i0 + 4u) << 32);
+                };
                 // LDX_STEP_UNROLL steps per trip of the loop (1, 2, 4, 8 or 16; the rows of a step are (e & 3) + 8 (e >> 2) + 32 m:
                 // unrolled by 4 the row inside its group of eight is static -- LDS and store offsets become immediates, the
                 // scalar address arithmetic happens once per four steps --, unrolled by 16 the accumulator index is static too)
@@ -1169,6 +1196,10 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                             if constexpr (kDeg) {
 #pragma unroll
                                 for (int tt = 0; tt < 4; ++tt) b4[tt] = select_lanes(b4[tt], (uint32_t)LDX_K16_INT0, rowmask | colmask[tt]);
+                                if (edge) {   // wave-uniform; after the int-0 forcing (pad rows / columns look degenerate)
+#pragma unroll
+                                    for (int tt = 0; tt < 4; ++tt) b4[tt] = select_lanes(b4[tt], 0u, outside(row0 + 32u * g + (e & 3) + 8u * (e >> 2), tt));
+                                }
                             }
                             // the cells are the low halves of 2^23 + k: two per byte permute
                             cellw[2 * g] = __builtin_amdgcn_perm(b4[1], b4[0], 0x05040100u);
@@ -1185,6 +1216,18 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                                     } else {
                                         const v2u w = __builtin_bit_cast(v2u, o4[tt]);
                                         o4[tt] = __builtin_bit_cast(Cell, v2u{select_lanes(w.x, forced, m), select_lanes(w.y, forced, m)});
+                                    }
+                                }
+                                if (edge) {   // wave-uniform; zero_cell is all-zero bits in every format
+#pragma unroll
+                                    for (int tt = 0; tt < 4; ++tt) {
+                                        const uint64_t m = outside(row0 + 32u * g + (e & 3) + 8u * (e >> 2), tt);
+                                        if constexpr (sizeof(Cell) == 4) {
+                                            o4[tt] = __builtin_bit_cast(Cell, select_lanes(__builtin_bit_cast(uint32_t, o4[tt]), 0u, m));
+                                        } else {
+                                            const v2u w = __builtin_bit_cast(v2u, o4[tt]);
+                                            o4[tt] = __builtin_bit_cast(Cell, v2u{select_lanes(w.x, 0u, m), select_lanes(w.y, 0u, m)});
+                                        }
                                     }
                                 }
                             }
@@ -1240,7 +1283,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                     return true;
                 };
                 const bool small_n = f32_small_n((double)fc32.n);
-                const bool done = any_deg ? (small_n ? steps(std::true_type{}, std::true_type{}) : steps(std::false_type{}, std::true_type{}))
+                const bool done = (any_deg || edge) ? (small_n ? steps(std::true_type{}, std::true_type{}) : steps(std::false_type{}, std::true_type{}))
                                           : (small_n ? steps(std::true_type{}, std::false_type{}) : steps(std::false_type{}, std::false_type{}));
                 if (!done) return false;
                 // ---- the parked steps: fp64 tier ----
@@ -1299,6 +1342,13 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                         const FastCol fcx[1] = {FastCol{c01.x, c01.y, c23.x, c23.y}};
                         if (all_ordinary) ld_multi_fast2<1, true, Cell>(a2, fk, frk, fcx, r2, s2);
                         else ld_multi_fast2<1, false, Cell>(a2, fk, frk, fcx, r2, s2);   // a monomorphic SNP / missing codes in the unit
+                        if (edge) {   // wave-uniform: a parked step of an edge unit may hold cells outside the triangle
+                            const uint32_t i = row0 + ri2, j = t * kSlab + cl;
+                            if (!(i > j && i < n_snps)) {
+                                r2[0] = zero_cell<Cell>();
+                                s2[0] = false;
+                            }
+                        }
                     }
                     const bool unsure = live && s2[0];
                     const unsigned long long um = __ballot(unsure);
@@ -1739,18 +1789,23 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 return;
             }
             // `inside`: the unit lies wholly below the diagonal, inside the panel and inside [u_begin, u_end) (no validity
-            // tests); `clean`: and all of its 64 rows and 128 columns are ordinary SNPs (no degenerate handling either)
-            const bool inside = !kRaw && row0 >= (t + 1u) * kSlab && row0 + 32u * MM <= n_snps && (t + 1u) * kSlab <= n_snps &&
-                                vv * 8u >= u_begin && vv * 8u + 8u <= u_end;
+            // tests); `clean`: and all of its 64 rows and 128 columns are ordinary SNPs (no degenerate handling either);
+            // `whole`: all of its small units are inside [u_begin, u_end)
+            const bool interior = row0 >= (t + 1u) * kSlab && row0 + 32u * MM <= n_snps && (t + 1u) * kSlab <= n_snps;
+            const bool whole = vv * 8u >= u_begin && vv * 8u + 8u <= u_end;
+            const bool inside = !kRaw && interior && whole;
             const bool all_ordinary = rows_ordinary && (cols_odd[0] | cols_odd[1]) == 0u;
             const bool clean = inside && all_ordinary;
             if constexpr (kR32) {
                 epilogue_r32();
             } else if constexpr (kF32Tier) {
-                // The fp32 tier takes every `inside` unit: rows / columns of SNPs that are not ordinary park their lane-steps
-                // (ldx_common.h, f32_row) and the drain runs the general fp64 variant for such a unit.  A unit that parks more
-                // than the queue holds (four or more such SNPs) goes through the fp64 epilogue whole.
-                if (inside && !(ablate & 512) && epilogue_f32(all_ordinary)) {
+                // The fp32 tier takes every unit whose small units are all inside the range (`whole`), on the diagonal and
+                // at the padded end of the panel too (`edge`: the cells outside the triangle are forced to zero_cell):
+                // rows / columns of SNPs that are not ordinary park their lane-steps (ldx_common.h, f32_row) and the drain runs
+                // the general fp64 variant for such a unit.  A unit that parks more than the queue holds (four or more such
+                // SNPs) goes through the fp64 epilogue whole, as do the at most two units a range boundary cuts (a pad_only one
+                // included: its accumulators are still zero, and every cell of it is outside the triangle).
+                if (whole && !(ablate & 512) && epilogue_f32(all_ordinary, !interior)) {
                 } else if (clean && !(ablate & 512)) {
                     epilogue(std::true_type{});
                 } else {
