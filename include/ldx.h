@@ -118,12 +118,13 @@ typedef struct { uint16_t value; } ldx_k16one;
 typedef struct { float r; } ldx_r32;
 #define LDX_OUT_R32 4
 
-/* one ld_area hit (ld_area.py:261-271): query/opposing SNP row indices and rounded values */
+/* one ld_area hit (ld_area.py:261-271): query/opposing SNP row indices and rounded values.  A record of
+ * ldx_ld_neighbors_dev uses the same layout with other values: r_square holds the signed r cell, d_prime s = r *f32 r. */
 typedef struct {
     uint32_t query;      /* row index of var_1 (the query) in the panel */
     uint32_t oppos;      /* row index of var_2 (the opposing variant) */
-    float r_square;      /* as ldx_ld32 */
-    float d_prime;
+    float r_square;      /* as ldx_ld32 (neighbour lists: the signed r) */
+    float d_prime;       /* (neighbour lists: s = r *f32 r) */
 } ldx_hit;
 
 /* ---- library / device ---------------------------------------------------------------- */
@@ -344,6 +345,56 @@ int ldx_ld_score_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt
                      uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window,
                      const uint8_t *annot, uint32_t n_annot, int path,
                      uint64_t *sums, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- LD neighbour lists on the matrix-pipe band (clumping and pruning, with ldx_ld_select_dev) ---- */
+/* Every ordered pair (i, j), i != j, with
+ *     |pos_i - pos_j| <= window          (the inclusive, symmetric window of ldx_ld_score_dev; duplicate positions allowed)
+ *     s_ij = c_ij *f32 c_ij >= r2_bound  (c_ij the signed r cell of ldx_triangle_ex_dev(LDX_OUT_R32), bit for bit; s ONE
+ *                                         IEEE float32 multiply, as in ldx_ld_score_dev's term)
+ * is stored as the record {query = i, oppos = j, r_square = c_ij, d_prime = s_ij} -- every pair in both orientations.
+ * r2_bound: a float32 > 0 (so the -0.0f cell of a degenerate SNP and a cell with num == 0 never pass).  A caller with a
+ * threshold t (a double) passes the smallest float32 not below t for `r^2 >= t`, and the smallest float32 above t for
+ * `r^2 > t`: s is a float32, so either test is then exactly s >= r2_bound.
+ *   positions: int64 [n_snps], NON-DECREASING; window >= 0 in their units (values above 2^52 act as 2^52);
+ *   acnt / rcnt from ldx_pack_codes_dev (as for ldx_ld_score_dev), fa / fr from ldx_snp_stats_dev;
+ *   path: LDX_PATH_AUTO / LDX_PATH_FP4 = the FP4 band, LDX_PATH_MFMA = the int8 band (identical records), LDX_PATH_POPCOUNT
+ *         = LDX_E_UNSUPPORTED; n_hap > LDX_MAX_HAPS = LDX_E_UNSUPPORTED.
+ * hits: capacity hit_cap (< 2^32), written in arbitrary order; *n_hits (device uint64) receives the number of slots
+ * RESERVED (batches of 256 per wave; unused slots carry query == UINT32_MAX), as for ldx_area_scan_dev: if it exceeds
+ * hit_cap only the first hit_cap slots were stored -- retry with a larger buffer.  row_counts: device uint32 [n_snps + 1]
+ * (zeroed here) or NULL; with row_counts = ldx_area_finish_counts(finish workspace), ldx_area_finish_ex_dev(counts_ready = 1)
+ * turns the slots into the per-SNP neighbour CSR: records sorted by (query, oppos), row i's at [offsets[i], offsets[i + 1]).
+ * workspace: ldx_ld_neighbors_workspace_bytes() bytes, 256-byte aligned, no initialisation needed: one per launch that may
+ * be in flight (as for ldx_ld_score_dev).  The call only enqueues work on `stream`. */
+size_t ldx_ld_neighbors_workspace_bytes(uint32_t n_snps, uint32_t n_hap);
+int ldx_ld_neighbors_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
+                         uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, float r2_bound, int path,
+                         ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits, uint32_t *row_counts,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
+/* Greedy selection over a neighbour CSR (records + offsets of ldx_area_finish_ex_dev after ldx_ld_neighbors_dev; only
+ * `oppos` is read).  rank: uint32 [n_snps], distinct among the candidates, UINT32_MAX for a SNP that is not one;
+ * member_ok: uint8 [n_snps], non-zero for every candidate.  The result is that of the sequential rule: take the candidates
+ * in increasing rank; one not yet assigned becomes an INDEX, and each of its neighbours that is not yet assigned and has
+ * member_ok set is assigned to it.  So the indices are the lexicographically-first maximal independent set of the
+ * candidates' subgraph, and a SNP's owner is its neighbour index of smallest rank.  Computed in ROUNDS, one kernel launch
+ * each: an undecided candidate becomes an index once every neighbour candidate of smaller rank has been removed, and is
+ * removed as soon as one of them is an index.  Decisions are final, so a round may read what other workgroups wrote in it;
+ * each round decides at least the undecided candidate of lowest rank: at most (number of candidates) rounds.
+ * The call enqueues rounds [first_round, first_round + n_rounds) (n_rounds >= 1; first_round = 0 initialises the
+ * workspace, later calls continue from where the previous one stopped: call them in order on one stream with one
+ * workspace), then writes the number of candidates still undecided to *undecided (device uint32).  A round enqueued after
+ * convergence returns at once.  When *undecided is 0 the call has also written
+ *     state[i] (uint8) = LDX_SEL_INDEX, LDX_SEL_ASSIGNED (a candidate that is not an index) or LDX_SEL_OUT (no candidate)
+ *     owner[i] (uint32) = i for an index; the index row SNP i was assigned to; UINT32_MAX for none.
+ * workspace: ldx_ld_select_workspace_bytes() bytes, 256-byte aligned. */
+#define LDX_SEL_INDEX 1
+#define LDX_SEL_ASSIGNED 2
+#define LDX_SEL_OUT 3
+size_t ldx_ld_select_workspace_bytes(uint32_t n_snps);
+int ldx_ld_select_dev(const ldx_hit *nbrs, const uint32_t *offsets, uint32_t n_snps, const uint32_t *rank,
+                      const uint8_t *member_ok, uint32_t first_round, uint32_t n_rounds, uint8_t *state, uint32_t *owner,
+                      uint32_t *undecided, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- synthetic panels: deterministic, identical on host and device ------ */
 /* codes int8 [n_snps][ld_codes] receive global SNPs [snp_offset, snp_offset + n_snps) (a rank's

@@ -135,6 +135,11 @@ SIGNATURES = {
     "ldx_area_band_passes_offset": (_sz, [_u32]),
     "ldx_ld_score_workspace_bytes": (_sz, [_u32, _u32]),
     "ldx_ld_score_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _i64, _vp, _u32, _int, _vp, _vp, _sz, _vp]),
+    "ldx_ld_neighbors_workspace_bytes": (_sz, [_u32, _u32]),
+    "ldx_ld_neighbors_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _i64, C.c_float, _int, _vp, _u64, _vp, _vp,
+                                    _vp, _sz, _vp]),
+    "ldx_ld_select_workspace_bytes": (_sz, [_u32]),
+    "ldx_ld_select_dev": (_int, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ldx_set_area_path": (_int, [_int]),
     "ldx_get_area_path": (_int, []),
     "ldx_synth_codes_dev": (_int, [_vp, _u32, _u32, _sz, _u64, _vp, _u64, _u32, _u64, _u32, _vp]),

@@ -674,3 +674,119 @@ extern "C" int ldx_area_scan_dev(const void *alt, const double *fa, const double
     LDX_HIP(hipGetLastError());
     return LDX_OK;
 }
+
+// ---- greedy selection over a neighbour CSR (ldx_ld_select_dev): clumping and pruning ----------------------------------
+// One launch is one ROUND; one thread per SNP.  Working states live in the workspace as uint32 words, written with
+// agent-scope atomic stores and read with agent-scope atomic loads: a decision another XCD made earlier in the same round
+// is then seen at once (a stale "undecided" would only delay a decision by a round: every state moves once, from undecided
+// to final).  Round r's count of candidates left undecided goes to ctr[r % 3]: the round reads its predecessor's word
+// ctr[(r + 2) % 3] (0: converged, return at once) and re-arms ctr[(r + 1) % 3], which the round before read and the
+// next round fills.  No thread waits for another workgroup, and there is no grid barrier.
+namespace ldx {
+
+constexpr uint32_t kSelUndecided = 0;
+
+__device__ __forceinline__ uint32_t load_agent(const uint32_t *p)
+{
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ void select_init_kernel(const uint32_t *__restrict__ rank, uint32_t n_snps, uint32_t *__restrict__ st,
+                                   uint32_t *__restrict__ ctr)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 3u) ctr[i] = i == 2u ? 1u : 0u;   // "round -1" left candidates undecided: round 0 runs
+    if (i < n_snps) st[i] = rank[i] == 0xFFFFFFFFu ? (uint32_t)LDX_SEL_OUT : kSelUndecided;
+}
+
+__global__ void __launch_bounds__(256) select_round_kernel(const ldx_hit *__restrict__ nbrs, const uint32_t *__restrict__ offsets,
+                                                           const uint32_t *__restrict__ rank, uint32_t n_snps, uint32_t round,
+                                                           uint32_t *st, uint32_t *ctr)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) store_agent(&ctr[(round + 1u) % 3u], 0u);
+    if (ctr[(round + 2u) % 3u] == 0u) return;   // converged (block-uniform)
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool left = false;   // this candidate is still undecided after the round
+    if (i < n_snps && load_agent(&st[i]) == kSelUndecided) {
+        const uint32_t ri = rank[i];
+        uint32_t verdict = LDX_SEL_INDEX;   // until a neighbour of smaller rank says otherwise
+        for (uint32_t k = offsets[i], e = offsets[i + 1u]; k < e; ++k) {
+            const uint32_t j = nbrs[k].oppos;
+            if (rank[j] >= ri) continue;   // a later candidate, or none (UINT32_MAX)
+            const uint32_t sj = load_agent(&st[j]);
+            if (sj == LDX_SEL_INDEX) {
+                verdict = LDX_SEL_ASSIGNED;
+                break;
+            }
+            if (sj == kSelUndecided) verdict = kSelUndecided;   // keep looking: an index further on still decides
+        }
+        if (verdict != kSelUndecided) store_agent(&st[i], verdict);
+        left = verdict == kSelUndecided;
+    }
+    const unsigned long long m = __ballot(left);
+    if (m && (threadIdx.x & 63u) == 0u) atomicAdd(&ctr[round % 3u], (uint32_t)__builtin_popcountll(m));
+}
+
+// the count of the last round -> *undecided; at convergence, state and owner (the neighbour index of smallest rank)
+__global__ void __launch_bounds__(256) select_owner_kernel(const ldx_hit *__restrict__ nbrs, const uint32_t *__restrict__ offsets,
+                                                           const uint32_t *__restrict__ rank, const uint8_t *__restrict__ member_ok,
+                                                           uint32_t n_snps, uint32_t last_round, const uint32_t *__restrict__ st,
+                                                           const uint32_t *__restrict__ ctr, uint8_t *__restrict__ state,
+                                                           uint32_t *__restrict__ owner, uint32_t *__restrict__ undecided)
+{
+    const uint32_t left = ctr[last_round % 3u];
+    if (blockIdx.x == 0 && threadIdx.x == 0) *undecided = left;
+    if (left) return;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_snps) return;
+    const uint32_t s = st[i];
+    uint32_t o = 0xFFFFFFFFu;
+    if (s == LDX_SEL_INDEX) {
+        o = i;
+    } else if (member_ok[i]) {
+        uint32_t best = 0xFFFFFFFFu;
+        for (uint32_t k = offsets[i], e = offsets[i + 1u]; k < e; ++k) {
+            const uint32_t j = nbrs[k].oppos;
+            if (st[j] == LDX_SEL_INDEX && rank[j] < best) {
+                best = rank[j];
+                o = j;
+            }
+        }
+    }
+    state[i] = (uint8_t)s;
+    owner[i] = o;
+}
+
+}  // namespace ldx
+
+extern "C" size_t ldx_ld_select_workspace_bytes(uint32_t n_snps)
+{
+    return ((size_t)n_snps * 4u + 255u) / 256u * 256u + 256u;   // the working states, the three round counters
+}
+
+extern "C" int ldx_ld_select_dev(const ldx_hit *nbrs, const uint32_t *offsets, uint32_t n_snps, const uint32_t *rank,
+                                 const uint8_t *member_ok, uint32_t first_round, uint32_t n_rounds, uint8_t *state,
+                                 uint32_t *owner, uint32_t *undecided, void *workspace, size_t workspace_bytes, void *stream)
+{
+    LDX_REQUIRE(offsets && rank && member_ok && state && owner && undecided && workspace, "null pointer");
+    LDX_REQUIRE(n_snps >= 1 && n_rounds >= 1, "bad shape");
+    LDX_REQUIRE((uint64_t)first_round + n_rounds <= 0xFFFFFFFFull, "round index overflow");
+    LDX_REQUIRE(((uintptr_t)workspace & 255u) == 0, "workspace must be 256-byte aligned");
+    LDX_REQUIRE(workspace_bytes >= ldx_ld_select_workspace_bytes(n_snps), "workspace too small (see ldx_ld_select_workspace_bytes)");
+    hipStream_t s = (hipStream_t)stream;
+    uint32_t *st = (uint32_t *)workspace;
+    uint32_t *ctr = (uint32_t *)((char *)workspace + ((size_t)n_snps * 4u + 255u) / 256u * 256u);
+    const uint32_t blocks = (n_snps + 255u) / 256u;
+    if (first_round == 0) {
+        ldx::select_init_kernel<<<blocks, 256, 0, s>>>(rank, n_snps, st, ctr);
+        LDX_HIP(hipGetLastError());
+    }
+    for (uint32_t r = first_round; r < first_round + n_rounds; ++r) {
+        ldx::select_round_kernel<<<blocks, 256, 0, s>>>(nbrs, offsets, rank, n_snps, r, st, ctr);
+        LDX_HIP(hipGetLastError());
+    }
+    ldx::select_owner_kernel<<<blocks, 256, 0, s>>>(nbrs, offsets, rank, member_ok, n_snps, first_round + n_rounds - 1u, st, ctr,
+                                                    state, owner, undecided);
+    LDX_HIP(hipGetLastError());
+    return LDX_OK;
+}

@@ -345,7 +345,10 @@ __device__ __forceinline__ uint64_t dpp_half_sum(uint64_t x)
 // kScoreW (with kArea): the LD-score band (ldx_ld_score_dev) -- the band's passes and K loop with score_epilogue instead of
 // the hit scan; kScoreW is the number of `sums` words one sweep of the accumulators reduces (1: column 0 only; 5: column 0
 // and the categories, in sweeps of three words -- four or five spill).
-template <bool kRaw, bool kN11, bool kArea = false, bool kFp4 = false, typename Cell = ldx_ld32, int kScoreW = 0>
+// kNbr (with kArea): the neighbour-list band (ldx_ld_neighbors_dev) -- the band's passes and K loop with nbr_epilogue, which
+// appends every pair with r *f32 r >= a float32 bound in both orientations, instead of the rounded hit scan.
+template <bool kRaw, bool kN11, bool kArea = false, bool kFp4 = false, typename Cell = ldx_ld32, int kScoreW = 0,
+          bool kNbr = false>
 __global__ void __launch_bounds__(kMfmaThreads, kArea ? 2 : kWgPerCu)
 triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ fa, const double *__restrict__ fr,
                      const double *__restrict__ q, uint32_t n_snps, uint32_t n_slabs, uint32_t nchunks, double n,
@@ -423,7 +426,8 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
     constexpr bool kF32Tier = kFp4 && !kRaw && !kN11 && !kArea && !kR32;
     constexpr bool kScore = kScoreW != 0;   // LD scores (score_epilogue): r32 operands, integer sums instead of hits
     static_assert(!kScore || kArea, "the LD-score epilogue runs on the band");
-    constexpr bool kBandF32 = kFp4 && kArea && !kScore;   // the band screens its steps in float32 first (area_epilogue)
+    static_assert(!kNbr || (kArea && !kScore), "the neighbour epilogue runs on the band");
+    constexpr bool kBandF32 = kFp4 && kArea && !kScore && !kNbr;   // the band screens its steps in float32 first (area_epilogue)
     float *ctab32 = reinterpret_cast<float *>(tickets + 8);                 // [128][4]: F32Col
     float *rtab32 = ctab32 + kSlab * 4u + wave * (kRows64 * 4u);            // [64][4]: F32Row, private to the wave
     uint32_t *qid = reinterpret_cast<uint32_t *>(ctab32 + kSlab * 4u + kMfmaWaves * kRows64 * 4u) + wave * kQueueCap;   // [kQueueCap]
@@ -687,7 +691,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             }
             bool rows_ordinary = false;
             typedef double d2s __attribute__((ext_vector_type(2)));
-            if constexpr (kScore) {   // LD scores: {a, 1 / sqrt(a r)} (r32_snp) and {position, annotation mask} per SNP
+            if constexpr (kScore || kNbr) {   // LD scores / neighbours: {a, 1 / sqrt(a r)} (r32_snp) and {position, annotation mask}
                 if (new_tile && tid < kSlab) {
                     const uint32_t j = t * kSlab + tid;
                     const R32Snp c = r32_snp(fa[j], fr[j], n);
@@ -1543,7 +1547,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
               }
             };
             auto area_epilogue = [&]() {
-              if constexpr (kArea && MM == 2 && !kScore) {
+              if constexpr (kArea && MM == 2 && !kScore && !kNbr) {
                 uint64_t slot = hit_slot, slot_end = hit_slot_end;
                 const double kthr = aa.k_thres;
                 const bool prefilter = aa.k_thres > 2.0;
@@ -1756,6 +1760,87 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 hit_slot_end = slot_end;
               }
             };
+            // ---- neighbour lists (ldx_ld_neighbors_dev): every band pair with s >= b, appended in both orientations ----
+            // Pair (i, j), i > j, pos_i - pos_j <= w (positions are non-decreasing): c = the r32 cell of the triangle (r32_cell,
+            // bit for bit), s = c *f32 c (one float32 multiply, as score_term), kept iff s >= b -- aa.k_thres holds the float32
+            // bound the host derived from the user's threshold, so `r^2 >= t` and `r^2 > t` are both this one comparison.  The
+            // -0.0f cell of a degenerate SNP and a cell with num == 0 give s = 0 < b: never kept.  A kept pair goes out as
+            // {i, j, c, s} and {j, i, c, s} through area_epilogue's appender (256-slot batches per wave, unused slots marked,
+            // stored records counted per row into aa.counts), so ldx_area_finish_ex_dev sorts them into a per-SNP CSR.
+            // Hits are rare: a (step, row tile) whose eight pairs per lane hold none costs one ballot and no append.
+            auto nbr_epilogue = [&]() {
+              if constexpr (kNbr && MM == 2) {
+                uint64_t slot = hit_slot, slot_end = hit_slot_end;
+                auto append = [&](bool keep, uint32_t qrow, uint32_t orow, float r, float s) {   // (area_epilogue's append)
+                    const unsigned long long mask = __ballot(keep);
+                    if (!mask) return;   // wave-uniform
+                    const uint32_t cnt = __builtin_popcountll(mask);
+                    if (slot + cnt > slot_end) {   // close the old batch (mark what is left invalid), open a new one
+                        for (uint64_t sl = slot + lane; sl < slot_end; sl += 64u)
+                            if (sl < aa.hit_cap) aa.hits[sl].query = 0xFFFFFFFFu;
+                        unsigned long long base = 0;
+                        if (lane == 0) base = atomicAdd(aa.n_hits, (unsigned long long)kHitBatch);
+                        base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
+                               __builtin_amdgcn_readfirstlane((uint32_t)base);
+                        slot = base;
+                        slot_end = base + kHitBatch;
+                    }
+                    if (keep) {
+                        const uint64_t sl = slot + __builtin_popcountll(mask & ((1ull << lane) - 1ull));
+                        if (sl < aa.hit_cap) {
+                            aa.hits[sl] = ldx_hit{qrow, orow, r, s};
+                            if (aa.counts) atomicAdd(&aa.counts[qrow], 1u);
+                        }
+                    }
+                    slot += cnt;
+                };
+                const double win = aa.flank, bound = aa.k_thres;
+                double ca[4], cs[4], cpos[4];   // this lane's four columns
+#pragma unroll
+                for (int tt = 0; tt < 4; ++tt) {
+                    const d2s c0 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32) * kStat);
+                    const d2s c1 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32) * kStat + 2u);
+                    ca[tt] = c0.x;
+                    cs[tt] = c0.y;
+                    cpos[tt] = c1.x;
+                }
+                const uint32_t j0 = t * kSlab + l32;   // column of tile tt: j0 + 32 tt
+#pragma unroll 1
+                for (int e = 0; e < 16; ++e) {
+#pragma unroll
+                    for (int m = 0; m < 2; ++m) {
+                        accel_t c4[4];   // ONE register-indexed read per accumulator, pinned (see area_epilogue)
+#pragma unroll
+                        for (int tt = 0; tt < 4; ++tt) {
+                            c4[tt] = acc[m][tt][e];
+                            asm volatile("" : "+v"(c4[tt]));
+                        }
+                        const uint32_t ri = 32u * m + (uint32_t)(e & 3) + 8u * (uint32_t)(e >> 2) + 4u * half;
+                        const d2s r0 = *reinterpret_cast<const d2s *>(rstat + ri * kStat);   // two addresses per wave: broadcast
+                        const d2s r1 = *reinterpret_cast<const d2s *>(rstat + ri * kStat + 2u);
+                        const uint32_t i = row0 + ri;
+                        float rc[4];
+                        bool keep[4];
+#pragma unroll
+                        for (int tt = 0; tt < 4; ++tt) {
+                            const double cnt = kFp4 ? (double)c4[tt] : (double)((uint32_t)c4[tt] >> 3);   // int8: 8 n11
+                            rc[tt] = r32_cell(cnt, n, r0.x, r0.y, ca[tt], cs[tt]).r;
+                            const float sq = rc[tt] * rc[tt];
+                            keep[tt] = i > j0 + 32u * tt && i < n_snps && r1.x - cpos[tt] <= win && (double)sq >= bound;
+                        }
+                        if (!__any(keep[0] || keep[1] || keep[2] || keep[3])) continue;   // wave-uniform
+#pragma unroll
+                        for (int tt = 0; tt < 4; ++tt) {
+                            const uint32_t j = j0 + 32u * tt;
+                            append(keep[tt], i, j, rc[tt], rc[tt] * rc[tt]);
+                            append(keep[tt], j, i, rc[tt], rc[tt] * rc[tt]);
+                        }
+                    }
+                }
+                hit_slot = slot;
+                hit_slot_end = slot_end;
+              }
+            };
             if constexpr (kScore) {
                 const uint32_t st = 1u + (uint32_t)aa.measure;   // words per SNP: column 0 and K categories
                 if (active) score_epilogue(st);
@@ -1774,7 +1859,8 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 return;
             }
             if constexpr (kArea) {
-                area_epilogue();
+                if constexpr (kNbr) nbr_epilogue();
+                else area_epilogue();
                 if (tid == 0) tickets[parity] = next_ticket;
                 if (!(ablate & 16)) __builtin_amdgcn_s_setprio(0);
 #ifdef LDX_TUNING
@@ -2305,7 +2391,127 @@ int score_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, cons
                    : launch_score<false, 1>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
 }
 
+// ---- neighbour lists on the band (ldx_ld_neighbors_dev) ----------------------------------------------------------------
+// the two-row query list {0, n - 1} the plan kernel reads (every SNP a query: the plan keeps every tile's whole band)
+__global__ void nbr_init_kernel(uint32_t n_snps, uint32_t *__restrict__ qrows)
+{
+    if (threadIdx.x == 0) {
+        qrows[0] = 0u;
+        qrows[1] = n_snps - 1u;
+    }
+}
+
+// the band's workspace (area_mfma's layout) + 256 bytes: the two query rows
+size_t nbr_mfma_workspace_bytes(uint32_t n_snps) { return area_mfma_workspace_bytes(n_snps) + 256u; }
+
+template <bool kFp4>
+static int launch_nbr(const void *alt, const double *fa, const double *fr, uint32_t n_snps, uint32_t n_hap, uint32_t T,
+                      uint32_t nch, uint64_t units, size_t lds, const AreaArgs &aa, uint32_t *sched, hipStream_t s)
+{
+    static std::atomic<uint64_t> opted{0};   // the dynamic LDS opt-in: once per device
+    int dev = 0;
+    LDX_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !((opted.load(std::memory_order_relaxed) >> dev) & 1u)) {
+        LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, true>,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (dev >= 0 && dev < 64) opted.fetch_or(1ull << dev, std::memory_order_relaxed);
+    }
+    triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, true><<<(uint32_t)device_cus() * 2u, kMfmaThreads, lds, s>>>(
+        (const uint4 *)alt, fa, fr, nullptr, n_snps, T, nch, (double)n_hap, 1.0 / (double)n_hap, 0, units * 8u,
+        (ldx_ld32 *)nullptr, nullptr, nullptr, 0u, 0u, 0u, sched, 0, nullptr, aa);
+    LDX_HIP(hipGetLastError());
+    return LDX_OK;
+}
+
+int nbr_mfma(const void *alt, const double *fa, const double *fr, uint32_t n_snps, uint32_t n_hap, const int64_t *positions,
+             int64_t window, float r2_bound, bool fp4, ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits, uint32_t *row_counts,
+             void *workspace, hipStream_t s)
+{
+    const uint32_t T = n_slabs(n_snps), nch = n_chunks(n_hap);
+    if ((uint64_t)T * nch * kSlab * 16u >= (1ull << 32)) {   // the K loop addresses the plane with 32-bit lane offsets
+        set_error("ldx_ld_neighbors_dev: a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", n_snps, n_hap);
+        return LDX_E_UNSUPPORTED;
+    }
+    if (row_counts) LDX_HIP(hipMemsetAsync(row_counts, 0, ((size_t)n_snps + 1u) * 4u, s));
+    if (n_snps < 2) {   // no pairs: no plan kernel to zero the slot counter
+        LDX_HIP(hipMemsetAsync(n_hits, 0, sizeof(uint64_t), s));
+        return LDX_OK;
+    }
+    // the band's buffers, carved as in area_mfma (its query mask stays unused)
+    char *w = (char *)workspace + ((size_t)n_snps + 255u) / 256u * 256u;
+    uint32_t *pass_base = (uint32_t *)w;
+    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
+    uint32_t *g_end = (uint32_t *)w;
+    w += ((size_t)T * 4u + 255u) / 256u * 256u;
+    uint32_t *g_begin = (uint32_t *)w;
+    w += ((size_t)T * 4u + 255u) / 256u * 256u;
+    uint32_t *first_base = (uint32_t *)w;
+    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
+    uint32_t *order = area_order_entries(n_snps) ? (uint32_t *)w : nullptr;
+    w += (area_order_entries(n_snps) * 4u + 255u) / 256u * 256u;
+    uint32_t *sched = (uint32_t *)w;
+    w += kAreaSchedWords * 4u;
+    uint32_t *qrows = (uint32_t *)w;   // [2]
+    nbr_init_kernel<<<1, 64, 0, s>>>(n_snps, qrows);
+    LDX_HIP(hipGetLastError());
+    // the plan keeps, per j-tile, the rows with pos <= pos(last column) + window (|delta| = window included), and zeroes the
+    // slot counter; nbr_epilogue applies the exact symmetric bound per pair
+    area_band_plan_kernel<<<1, 1024, 0, s>>>(positions, n_snps, T, window, qrows, 2u, g_begin, g_end, pass_base,
+                                             (unsigned long long *)n_hits, order, first_base, sched);
+    LDX_HIP(hipGetLastError());
+    AreaArgs aa{};
+    aa.f32 = f32_const((double)n_hap);
+    aa.pos = positions;
+    aa.is_query = nullptr;
+    aa.pass_base = pass_base;
+    aa.g_begin = g_begin;
+    aa.g_end = g_end;
+    aa.order = order;
+    aa.hits = hits;
+    aa.counts = row_counts;
+    aa.n_hits = (unsigned long long *)n_hits;
+    aa.hit_cap = hit_cap;
+    aa.flank = (double)window;
+    aa.k_thres = (double)r2_bound;   // neighbours: the float32 bound b on s = r *f32 r
+    const uint64_t units = ldx_triangle_units(n_snps) / 8u;   // 64-row units of the full triangle
+    const size_t lds = mfma_lds_bytes(kRows64, false, false);
+    if (fp4) return launch_nbr<true>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
+    return launch_nbr<false>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
+}
+
 }  // namespace ldx
+
+extern "C" size_t ldx_ld_neighbors_workspace_bytes(uint32_t n_snps, uint32_t n_hap)
+{
+    (void)n_hap;   // (the layout depends on the SNP count alone)
+    return ldx::nbr_mfma_workspace_bytes(n_snps ? n_snps : 1u);
+}
+
+extern "C" int ldx_ld_neighbors_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa,
+                                    const double *fr, uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window,
+                                    float r2_bound, int path, ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits,
+                                    uint32_t *row_counts, void *workspace, size_t workspace_bytes, void *stream)
+{
+    LDX_REQUIRE(alt && acnt && rcnt && fa && fr && positions && n_hits && workspace, "null pointer");
+    LDX_REQUIRE(hits || hit_cap == 0, "hits is null but hit_cap > 0");
+    LDX_REQUIRE(n_snps >= 1 && n_hap >= 1 && window >= 0, "bad shape");
+    LDX_REQUIRE(r2_bound > 0.0f, "r2_bound must be > 0 (and not NaN)");
+    LDX_REQUIRE(hit_cap < (1ull << 32), "hit_cap must be < 2^32 (the finished CSR's offsets are uint32)");
+    LDX_REQUIRE(((uintptr_t)workspace & 255u) == 0, "workspace must be 256-byte aligned");
+    LDX_REQUIRE(workspace_bytes >= ldx::nbr_mfma_workspace_bytes(n_snps), "workspace too small (see ldx_ld_neighbors_workspace_bytes)");
+    LDX_REQUIRE(path == LDX_PATH_AUTO || path == LDX_PATH_POPCOUNT || path == LDX_PATH_MFMA || path == LDX_PATH_FP4, "unknown path");
+    if (n_hap > LDX_MAX_HAPS) {
+        ldx::set_error("ldx_ld_neighbors_dev: n_hap %u > LDX_MAX_HAPS %u", n_hap, LDX_MAX_HAPS);
+        return LDX_E_UNSUPPORTED;
+    }
+    if (path == LDX_PATH_POPCOUNT) {
+        ldx::set_error("ldx_ld_neighbors_dev: neighbour lists run on the matrix-pipe band (LDX_PATH_FP4 / LDX_PATH_MFMA), not on the popcount kernels");
+        return LDX_E_UNSUPPORTED;
+    }
+    const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles: keep pos + window exact
+    return ldx::nbr_mfma(alt, fa, fr, n_snps, n_hap, positions, window < wmax ? window : wmax, r2_bound, path != LDX_PATH_MFMA,
+                         hits, hit_cap, n_hits, row_counts, workspace, (hipStream_t)stream);
+}
 
 extern "C" size_t ldx_ld_score_workspace_bytes(uint32_t n_snps, uint32_t n_hap)
 {

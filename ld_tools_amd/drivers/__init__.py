@@ -9,9 +9,11 @@ loop order).  Any object with pysam's ``VariantFile.fetch(chrom, start, end)`` /
 as the VCF source; pysam itself is only imported by the command-line shells.
 """
 from .area import AreaQueryResult, area_scan, get_inld_vars, write_area_file  # noqa: F401
+from .clump import ClumpTable, clump, write_clumped  # noqa: F401
 from .ingest import RaggedGenotypesError, codes_matrix, find_record, sample_genotypes  # noqa: F401
 from .ldscore import LDScoreTable, ld_scores, write_ldscore  # noqa: F401
 from .rmatrix import RMatrix, r_matrix, write_r_matrix  # noqa: F401
+from .prune import PruneTable, prune, write_prune  # noqa: F401
 from .lite import DifChrsError, NotInIntgenConvDbError, NotRsIdError, check_rs_id, ld_lite_table  # noqa: F401
 from .triangle import (TriangleMatrix, create_matrix, stream_triangle_table, triangle_matrix,  # noqa: F401
                        write_triangle_table)

@@ -3,6 +3,8 @@
     ld_triangle(panel)                      <- ld_triangle.py:133-230  (all row > col pairs)
     ld_area(panel, positions, queries, ...) <- ld_area.py:152-276      (windowed scan, thresholded hits)
     ld_score(panel, positions, ...)         LD scores: windowed sums of r^2 per SNP (LDSC's l2), optionally per category
+    ld_neighbors(panel, positions, ...)     per-SNP lists of the SNPs in the window with r^2 above a threshold
+    ld_clump / ld_prune                     greedy clumping (PLINK --clump) and priority pruning on those lists
     pair_counts(panel_i, panel_j)           <- calc_ld.py:32           (bit-exact n11 block)
     ld_from_counts(n, n11, a1, r1, a2, r2)  <- calc_ld.py:33-97        (the epilogue alone)
 
@@ -644,6 +646,38 @@ class LDScores:
         return adjust_l2(self.l2, self.m, self.n_hap if n_obs is None else int(n_obs))
 
 
+def _band_positions(panel: PackedPanel, positions, window_bp, window_snps, check_positions: bool, what: str):
+    """The band calls' positions and window: (device int64 positions, host copy or None, window).  ``window_snps`` counts
+    the window in SNPs (positions 0 .. n-1); otherwise ``positions`` must be non-decreasing, one per SNP (a device tensor is
+    checked on the device unless ``check_positions`` is False)."""
+    n = panel.n_snps
+    if panel.n_hap > _lib.MAX_HAPS:
+        raise _lib.LdxError(f"n_hap {panel.n_hap} > LDX_MAX_HAPS {_lib.MAX_HAPS}")
+    if window_snps is not None:
+        window = int(window_snps)
+        pos_h = np.arange(n, dtype=np.int64)
+        pos = torch.arange(n, dtype=torch.int64, device=panel.device)
+    else:
+        window = int(window_bp)
+        if positions is None:
+            raise _lib.LdxError(f"{what} needs positions (or window_snps)")
+        if isinstance(positions, torch.Tensor):
+            pos = positions.to(panel.device, dtype=torch.int64).contiguous()
+            if check_positions and pos.numel() > 1 and bool((pos[1:] < pos[:-1]).any().item()):
+                raise _lib.LdxError("positions must be non-decreasing (VCF order)")
+            pos_h = None
+        else:
+            pos_h = np.ascontiguousarray(np.asarray(positions, dtype=np.int64))
+            if pos_h.size > 1 and bool((pos_h[1:] < pos_h[:-1]).any()):
+                raise _lib.LdxError("positions must be non-decreasing (VCF order)")
+            pos = torch.as_tensor(pos_h).to(panel.device)
+        if pos.numel() != n:
+            raise _lib.LdxError("positions must have one entry per SNP")
+    if window < 0:
+        raise _lib.LdxError("the window must be >= 0")
+    return pos, pos_h, window
+
+
 def ld_score(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, window_snps: Optional[int] = None,
              annot=None, path: Optional[str] = None, workspace: Optional[torch.Tensor] = None,
              check_positions: bool = True) -> LDScores:
@@ -660,30 +694,7 @@ def ld_score(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, win
     """
     require_gpu()
     n = panel.n_snps
-    if panel.n_hap > _lib.MAX_HAPS:
-        raise _lib.LdxError(f"n_hap {panel.n_hap} > LDX_MAX_HAPS {_lib.MAX_HAPS}")
-    if window_snps is not None:
-        window = int(window_snps)
-        pos_h = np.arange(n, dtype=np.int64)
-        pos = torch.arange(n, dtype=torch.int64, device=panel.device)
-    else:
-        window = int(window_bp)
-        if positions is None:
-            raise _lib.LdxError("ld_score needs positions (or window_snps)")
-        if isinstance(positions, torch.Tensor):
-            pos = positions.to(panel.device, dtype=torch.int64).contiguous()
-            if check_positions and pos.numel() > 1 and bool((pos[1:] < pos[:-1]).any().item()):
-                raise _lib.LdxError("positions must be non-decreasing (VCF order)")
-            pos_h = None
-        else:
-            pos_h = np.ascontiguousarray(np.asarray(positions, dtype=np.int64))
-            if pos_h.size > 1 and bool((pos_h[1:] < pos_h[:-1]).any()):
-                raise _lib.LdxError("positions must be non-decreasing (VCF order)")
-            pos = torch.as_tensor(pos_h).to(panel.device)
-        if pos.numel() != n:
-            raise _lib.LdxError("positions must have one entry per SNP")
-    if window < 0:
-        raise _lib.LdxError("the window must be >= 0")
+    pos, pos_h, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_score")
     bits, k = (None, 0) if annot is None else pack_annot(annot, n)
     annot_d = torch.as_tensor(bits).to(panel.device) if k else None
     pcode = PATHS["fp4"] if path is None else PATHS[path]
@@ -702,6 +713,286 @@ def ld_score(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, win
         res.positions = pos      # type: ignore[assignment]
     res._keep = (pos, annot_d, workspace)   # alive until the launch is done (stream-ordered frees would allow reuse anyway)
     return res
+
+
+# --------------------------------------------------------------------------- neighbour lists, clumping, pruning
+NONE_U32 = 0xFFFFFFFF            # rank of a SNP that is not a candidate; owner of a SNP without one (include/ldx.h)
+SEL_INDEX, SEL_ASSIGNED, SEL_OUT = 1, 2, 3   # ldx_ld_select_dev's states (LDX_SEL_*)
+SELECT_BATCH = 32                # selection rounds enqueued between two reads of the undecided count
+
+
+def r2_bound(t: float, strict: bool = False) -> np.float32:
+    """The float32 bound b of ldx_ld_neighbors_dev for a threshold t > 0: ``r^2 >= t`` is s >= b with b the smallest float32
+    not below t, ``r^2 > t`` (strict) is s >= b with b the smallest float32 above t (s = r *f32 r is a float32)."""
+    t = float(t)
+    if not (0.0 < t < np.inf):
+        raise _lib.LdxError(f"the r^2 threshold must be a finite number > 0 (got {t})")
+    with np.errstate(over="ignore"):
+        b = np.float32(t)
+    if float(b) < t or (strict and float(b) == t):
+        b = np.nextafter(b, np.float32(np.inf), dtype=np.float32)
+    return np.float32(b)
+
+
+def live_snps(acnt, rcnt) -> np.ndarray:
+    """bool [n]: the SNP is not degenerate (a r > 0: it has ALT and REF codes)."""
+    return np.asarray(acnt, dtype=np.int64) * np.asarray(rcnt, dtype=np.int64) > 0
+
+
+def clump_ranks(pvalues, p1: float, p2: float, live) -> Tuple[np.ndarray, np.ndarray]:
+    """(rank uint32 [n], member_ok uint8 [n]) of ld_clump: candidates are the SNPs with p <= p1, ranked by (p, row); members
+    need p <= p2.  A SNP with a NaN p or a degenerate one (``live`` False) is neither.  Requires 0 < p1 <= p2."""
+    p = np.asarray(pvalues, dtype=np.float64)
+    live = np.asarray(live, dtype=bool)
+    if p.ndim != 1 or p.shape != live.shape:
+        raise _lib.LdxError(f"one p-value per SNP is needed ({live.size} SNPs, got shape {p.shape})")
+    if not (0.0 < float(p1) <= float(p2)):
+        raise _lib.LdxError(f"clumping needs 0 < p1 <= p2 (got p1 = {p1}, p2 = {p2})")
+    if bool((p < 0).any()):
+        raise _lib.LdxError("p-values must not be negative")
+    ok = live & ~np.isnan(p)
+    with np.errstate(invalid="ignore"):
+        cand = ok & (p <= p1)
+        member_ok = ok & (p <= p2)
+    rows = np.flatnonzero(cand)
+    order = rows[np.lexsort((rows, p[rows]))]
+    rank = np.full(p.size, NONE_U32, dtype=np.uint32)
+    rank[order] = np.arange(order.size, dtype=np.uint32)
+    return rank, member_ok.astype(np.uint8)
+
+
+def priority_ranks(priority, live) -> np.ndarray:
+    """rank uint32 [n] of ld_prune: the live SNPs by priority, highest first, ties by row; UINT32_MAX for the others."""
+    pr = np.asarray(priority, dtype=np.float64)
+    live = np.asarray(live, dtype=bool)
+    if pr.ndim != 1 or pr.shape != live.shape:
+        raise _lib.LdxError(f"one priority per SNP is needed ({live.size} SNPs, got shape {pr.shape})")
+    if bool(np.isnan(pr).any()):
+        raise _lib.LdxError("priorities must not be NaN")
+    rows = np.flatnonzero(live)
+    order = rows[np.lexsort((rows, -pr[rows]))]
+    rank = np.full(pr.size, NONE_U32, dtype=np.uint32)
+    rank[order] = np.arange(order.size, dtype=np.uint32)
+    return rank
+
+
+def select_host(offsets, nbr, rank, member_ok) -> Tuple[np.ndarray, np.ndarray]:
+    """The sequential rule ldx_ld_select_dev computes, as a plain loop (for small inputs and tests): take the candidates in
+    increasing rank; one not yet assigned becomes an index, and each neighbour not yet assigned with member_ok set is
+    assigned to it.  Returns (state uint8 [n]: SEL_INDEX / SEL_ASSIGNED / SEL_OUT, owner int64 [n]: -1 for none)."""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    nbr = np.asarray(nbr, dtype=np.int64)
+    rank = np.asarray(rank, dtype=np.uint32)
+    member_ok = np.asarray(member_ok).astype(bool)
+    n = rank.size
+    owner = np.full(n, -1, dtype=np.int64)
+    state = np.where(rank == NONE_U32, SEL_OUT, SEL_ASSIGNED).astype(np.uint8)
+    cands = np.flatnonzero(rank != NONE_U32)
+    for i in cands[np.argsort(rank[cands], kind="stable")].tolist():
+        if owner[i] >= 0:
+            continue
+        owner[i] = i
+        state[i] = SEL_INDEX
+        for j in nbr[offsets[i]:offsets[i + 1]].tolist():
+            if owner[j] < 0 and member_ok[j]:
+                owner[j] = i
+    return state, owner
+
+
+@dataclass
+class LDNeighbors:
+    """Per-SNP neighbour lists (ld_neighbors): for every SNP i the SNPs j != i with |pos_i - pos_j| <= window and r^2 above
+    the threshold, as a CSR on the device.  ``hits`` holds the ldx_hit records (int32 [m, 4]: row, neighbour, r bits, s
+    bits) sorted by (row, neighbour); row i's are [offsets[i], offsets[i + 1])."""
+
+    offsets: torch.Tensor   # int32 [n + 1]
+    hits: torch.Tensor      # int32 [m, 4]
+    n_snps: int
+    window: int
+    bound: np.float32       # the float32 bound on s = r *f32 r (r2_bound)
+
+    @property
+    def nbr(self) -> torch.Tensor:
+        """int32 [m]: the neighbour rows (a view of ``hits``)."""
+        return self.hits[:, 1]
+
+    @property
+    def r(self) -> torch.Tensor:
+        """float32 [m]: the signed r of each (row, neighbour) pair -- the r32 cell, bit for bit (a view of ``hits``)."""
+        return self.hits[:, 2].view(torch.float32)
+
+    def __len__(self) -> int:
+        return int(self.hits.shape[0])
+
+    def pairs(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(i int64, j int64, r float32) on the host: every neighbour pair once, with i < j, sorted by (i, j)."""
+        h = self.hits.cpu().numpy()
+        i, j = h[:, 0].astype(np.int64), h[:, 1].astype(np.int64)
+        once = i < j
+        return i[once], j[once], h[once, 2].view(np.float32)
+
+
+def ld_neighbors(panel: PackedPanel, positions=None, window_bp: int = 250_000, window_snps: Optional[int] = None,
+                 r2: float = 0.2, strict: bool = False, path: Optional[str] = None, hit_capacity: Optional[int] = None,
+                 workspace: Optional[torch.Tensor] = None, check_positions: bool = True) -> LDNeighbors:
+    """Neighbour lists on the matrix-pipe band (include/ldx.h, ldx_ld_neighbors_dev + ldx_area_finish_ex_dev): for every SNP
+    the SNPs j with |pos_i - pos_j| <= window, j != i, and r^2 >= ``r2`` (``strict``: r^2 > r2), where r is the r32 cell of
+    ld_triangle(fmt="r32") bit for bit and r^2 one float32 multiply.  Degenerate SNPs have no neighbours.
+
+    Positions and window as for ld_score.  ``path``: 'fp4' (default) or 'mfma' (the int8 band: identical lists).
+    ``hit_capacity``: record slots to start with (16 bytes each; default max(2^20, 32 n)); a call that needs more runs
+    again at the count the first run reserved.  ``workspace``: a uint8 device tensor of ldx_ld_neighbors_workspace_bytes()
+    bytes to reuse.  The host reads the record count once."""
+    require_gpu()
+    n = panel.n_snps
+    bound = r2_bound(r2, strict)
+    pos, _, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_neighbors")
+    pcode = PATHS["fp4"] if path is None else PATHS[path]
+    dev = panel.device
+    need = lib.ldx_ld_neighbors_workspace_bytes(n, panel.n_hap)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif workspace.numel() * workspace.element_size() < need:
+        raise _lib.LdxError(f"workspace too small: {need} bytes needed")
+    fin_bytes = lib.ldx_area_finish_workspace_bytes(n)
+    fin = torch.empty(fin_bytes, dtype=torch.uint8, device=dev)
+    counts = lib.ldx_area_finish_counts(fin.data_ptr())   # the band counts per row as it stores: no counting pass
+    cap = int(hit_capacity) if hit_capacity is not None else max(1 << 20, 32 * n)
+    n_hits = torch.zeros(1, dtype=torch.int64, device=dev)
+    summary = torch.zeros(2, dtype=torch.int64, device=dev)
+    offsets = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    for attempt in range(4):
+        if not 0 <= cap < (1 << 32):
+            raise _lib.LdxError(f"ld_neighbors: {cap} record slots needed; the CSR's offsets are uint32 (at most 2^32 - 1)")
+        raw = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+        hits = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+        check(lib.ldx_ld_neighbors_dev(panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(),
+                                       panel.fa.data_ptr(), panel.fr.data_ptr(), n, panel.n_hap, pos.data_ptr(), window,
+                                       float(bound), pcode, raw.data_ptr(), cap, n_hits.data_ptr(), counts,
+                                       workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr()),
+              "ldx_ld_neighbors_dev")
+        check(lib.ldx_area_finish_ex_dev(raw.data_ptr(), n_hits.data_ptr(), cap, n, hits.data_ptr(), offsets.data_ptr(),
+                                         summary.data_ptr(), fin.data_ptr(), fin_bytes, 1, _stream_ptr()),
+              "ldx_area_finish_ex_dev")
+        total, reserved = (int(x) for x in summary.tolist())
+        if reserved <= cap:
+            break
+        # the slots the run reserved (records + the batches' unused tails): the count a re-run needs, give or take the tails
+        # of a different work order -- hence the margin and, in the worst case, another run
+        cap = reserved + reserved // 64 + (1 << 16)
+    else:
+        raise _lib.LdxError("ld_neighbors: the record count did not settle")
+    del raw
+    return LDNeighbors(offsets, hits[:total], n, window, bound)
+
+
+def select_dev(nb: LDNeighbors, rank, member_ok, batch: int = SELECT_BATCH) -> Tuple[np.ndarray, np.ndarray, int]:
+    """ldx_ld_select_dev over a neighbour CSR, in batches of ``batch`` rounds until no candidate is undecided.  Returns
+    (state uint8 [n], owner int64 [n] with -1 for none, rounds enqueued).  More rounds than candidates raise LdxError."""
+    n = nb.n_snps
+    rank = np.ascontiguousarray(rank, dtype=np.uint32)
+    member_ok = np.ascontiguousarray(member_ok, dtype=np.uint8)
+    cand = rank != NONE_U32
+    n_cand = int(cand.sum())
+    if bool((cand & (member_ok == 0)).any()):
+        raise _lib.LdxError("every candidate must have member_ok set")
+    if n_cand and np.unique(rank[cand]).size != n_cand:
+        raise _lib.LdxError("candidate ranks must be distinct")
+    if n_cand == 0:
+        return np.full(n, SEL_OUT, dtype=np.uint8), np.full(n, -1, dtype=np.int64), 0
+    dev = nb.offsets.device
+    ws_bytes = lib.ldx_ld_select_workspace_bytes(n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    rank_d = torch.as_tensor(rank.view(np.int32)).to(dev)
+    ok_d = torch.as_tensor(member_ok).to(dev)
+    state = torch.empty(n, dtype=torch.uint8, device=dev)
+    owner = torch.empty(n, dtype=torch.int32, device=dev)
+    undecided = torch.empty(1, dtype=torch.int32, device=dev)
+    nbrs = nb.hits.data_ptr() if len(nb) else None
+    done = 0
+    while True:
+        check(lib.ldx_ld_select_dev(nbrs, nb.offsets.data_ptr(), n, rank_d.data_ptr(), ok_d.data_ptr(), done, int(batch),
+                                    state.data_ptr(), owner.data_ptr(), undecided.data_ptr(), ws.data_ptr(), ws_bytes,
+                                    _stream_ptr()), "ldx_ld_select_dev")
+        done += int(batch)
+        if int(undecided.item()) == 0:
+            break
+        if done >= n_cand:   # each round decides at least the lowest-ranked undecided candidate
+            raise _lib.LdxError(f"selection left candidates undecided after {done} rounds ({n_cand} candidates)")
+    own = owner.cpu().numpy().view(np.uint32)
+    return state.cpu().numpy(), np.where(own == NONE_U32, -1, own.astype(np.int64)), done
+
+
+@dataclass
+class Clumps:
+    """The clumps of ld_clump.  ``index``: the index rows in rank order (increasing p, then row); ``owner``: int64 [n], the
+    index row each SNP belongs to (its own row for an index, -1 for none); ``nan_p`` / ``degenerate``: rows left out of
+    clumping (neither candidates nor members)."""
+
+    index: np.ndarray
+    owner: np.ndarray
+    nan_p: np.ndarray
+    degenerate: np.ndarray
+    neighbors: LDNeighbors
+    rounds: int
+
+    def members(self, index_row: int) -> np.ndarray:
+        """int64: the rows assigned to this index (itself excluded), in row order."""
+        return np.flatnonzero((self.owner == int(index_row)) & (np.arange(self.owner.size) != int(index_row)))
+
+    def clumps(self):
+        """[(index row, member rows)] in rank order."""
+        return [(int(k), self.members(k)) for k in self.index]
+
+
+@dataclass
+class Pruned:
+    """The result of ld_prune: ``keep`` bool [n] (no two kept SNPs are neighbours), and the ranks it used."""
+
+    keep: np.ndarray
+    rank: np.ndarray
+    neighbors: LDNeighbors
+    rounds: int
+
+
+def _panel_live(panel: PackedPanel) -> np.ndarray:
+    return live_snps(panel.alt_counts(), panel.ref_counts())
+
+
+def ld_clump(panel: PackedPanel, positions, pvalues, p1: float = 1e-4, p2: float = 1e-2, r2: float = 0.5,
+             window_bp: int = 250_000, window_snps: Optional[int] = None, path: Optional[str] = None,
+             hit_capacity: Optional[int] = None) -> Clumps:
+    """Clumping (PLINK --clump's rule): take the SNPs with p <= p1 in increasing (p, row); one not yet in a clump becomes an
+    index and takes every SNP not yet in a clump with p <= p2 and r^2 >= r2 within the window.  r^2 is that of ld_neighbors
+    (the haplotype r of the ALT indicators, unrounded).  SNPs with a NaN p and degenerate SNPs take no part."""
+    live = _panel_live(panel)
+    rank, member_ok = clump_ranks(pvalues, p1, p2, live)
+    nb = ld_neighbors(panel, positions, window_bp=window_bp, window_snps=window_snps, r2=r2, strict=False, path=path,
+                      hit_capacity=hit_capacity)
+    state, owner, rounds = select_dev(nb, rank, member_ok)
+    idx = np.flatnonzero(state == SEL_INDEX)
+    idx = idx[np.argsort(rank[idx], kind="stable")]
+    p = np.asarray(pvalues, dtype=np.float64)
+    return Clumps(idx.astype(np.int64), owner, np.flatnonzero(np.isnan(p)), np.flatnonzero(~live), nb, rounds)
+
+
+def ld_prune(panel: PackedPanel, positions=None, r2: float = 0.2, window_bp: Optional[int] = None,
+             window_snps: Optional[int] = None, priority=None, path: Optional[str] = None,
+             hit_capacity: Optional[int] = None) -> Pruned:
+    """Priority pruning: take the SNPs in decreasing priority (default: the MAF min(fa, fr) of the panel), ties by row; one
+    with no kept neighbour is kept.  Neighbours are the SNPs within the window with r^2 > r2 (strict), as in ld_neighbors.
+    The kept set has no pair above the threshold inside the window.  Degenerate SNPs are never kept.  The window is
+    ``window_snps`` SNPs or ``window_bp`` in the units of ``positions`` (default 250 000 when positions are given)."""
+    live = _panel_live(panel)
+    if priority is None:
+        priority = np.minimum(panel.fa.cpu().numpy()[:panel.n_snps], panel.fr.cpu().numpy()[:panel.n_snps])
+    rank = priority_ranks(priority, live)
+    if window_snps is None and window_bp is None:
+        window_bp = 250_000
+    nb = ld_neighbors(panel, positions, window_bp=0 if window_bp is None else window_bp, window_snps=window_snps, r2=r2,
+                      strict=True, path=path, hit_capacity=hit_capacity)
+    state, _, rounds = select_dev(nb, rank, live.astype(np.uint8))
+    return Pruned(state == SEL_INDEX, rank, nb, rounds)
 
 
 # --------------------------------------------------------------------------- instrumentation
