@@ -346,6 +346,35 @@ int ldx_ld_score_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt
                      const uint8_t *annot, uint32_t n_annot, int path,
                      uint64_t *sums, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- banded LD matrix-vector products: R_w X and (R_w o R_w) X without the matrix, on the matrix-pipe band ---- */
+/* For every SNP i and right-hand side k < n_rhs (1 <= n_rhs <= 8), power in {1, 2}:
+ *     c_ij = the signed r cell of ldx_triangle_ex_dev(LDX_OUT_R32) for the pair, bit for bit; c_ii = (n - a_i) / r_i, the
+ *            diagonal of ldx_triangle_r_block_dev (-0.0f for a degenerate SNP)
+ *     v_ij = c_ij                          (power 1)
+ *          = c_ij *f32 c_ij                (power 2: ONE IEEE float32 multiply, the value ldx_ld_score_dev's term scales)
+ *     term = (int64) rint(2^40 * clamp((double)v_ij * (double)x[j][k], -2^22, 2^22))
+ *            -- the fp64 product of two float32 is exact (24 + 24 bits), the clamp and the scaling are exact: ONE rounding
+ *               (half to even), so every term is within 2^-41 of v_ij x_jk.  The clamp keeps the conversion defined; it is
+ *               only reachable with |x| or |c| far above 1
+ *     sums[i][k] = sum of term over j with |pos_i - pos_j| <= window      (j = i included; int64, two's-complement adds)
+ * so sums * 2^-40 is (R_w X)[i][k] with R_w the windowed signed-r matrix (power 2: its elementwise square, i.e. the LD score
+ * of a continuous annotation x).  The -0.0f cell of a degenerate SNP gives term 0 in both directions: its row is 0 and it
+ * adds 0 to every neighbour.  The sums are 64-bit integer atomics, so the result does not depend on the order of the work:
+ * bit-reproducible run to run, identical on both paths, and equal to a host sum of the terms over the r32 square.  A sum
+ * wraps only if one SNP's sum of |v x| over its window reaches 2^23 (with |x| <= 1 and without missing codes, |c| <= 1:
+ * 2^23 SNPs in one window -- more than a bit plane under 4 GiB holds at 5008 haplotypes).
+ *   x: float32 [n_snps][n_rhs], finite;  sums: int64 [n_snps][n_rhs], written by the call (no need to zero it);
+ *   positions, window, acnt / rcnt / fa / fr, path, n_hap: as for ldx_ld_score_dev (LDX_PATH_POPCOUNT and
+ *   n_hap > LDX_MAX_HAPS = LDX_E_UNSUPPORTED); n_rhs outside 1 .. 8 or power outside {1, 2} = LDX_E_ARG.
+ * workspace: ldx_ld_matvec_workspace_bytes() bytes, 256-byte aligned, no initialisation needed: one per launch that may be
+ * in flight (as for ldx_ld_score_dev).  The call only enqueues work on `stream`: no allocation, no synchronisation, no
+ * state in the library. */
+size_t ldx_ld_matvec_workspace_bytes(uint32_t n_snps, uint32_t n_hap);
+int ldx_ld_matvec_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
+                      uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window,
+                      const float *x, uint32_t n_rhs, int power, int path,
+                      int64_t *sums, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- LD neighbour lists on the matrix-pipe band (clumping and pruning, with ldx_ld_select_dev) ---- */
 /* Every ordered pair (i, j), i != j, with
  *     |pos_i - pos_j| <= window          (the inclusive, symmetric window of ldx_ld_score_dev; duplicate positions allowed)

@@ -135,6 +135,8 @@ SIGNATURES = {
     "ldx_area_band_passes_offset": (_sz, [_u32]),
     "ldx_ld_score_workspace_bytes": (_sz, [_u32, _u32]),
     "ldx_ld_score_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _i64, _vp, _u32, _int, _vp, _vp, _sz, _vp]),
+    "ldx_ld_matvec_workspace_bytes": (_sz, [_u32, _u32]),
+    "ldx_ld_matvec_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _i64, _vp, _u32, _int, _int, _vp, _vp, _sz, _vp]),
     "ldx_ld_neighbors_workspace_bytes": (_sz, [_u32, _u32]),
     "ldx_ld_neighbors_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _i64, C.c_float, _int, _vp, _u64, _vp, _vp,
                                     _vp, _sz, _vp]),

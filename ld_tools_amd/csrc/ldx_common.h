@@ -257,6 +257,19 @@ __device__ __forceinline__ uint64_t score_self_term(uint32_t a, uint32_t r, uint
     return score_term(r32_diag((double)a, (double)r, (double)n));
 }
 
+// Matrix-vector term of a value v (a signed r cell or its float32 square) and a float32 weight x (ldx_ld_matvec_dev,
+// include/ldx.h): rint(2^40 * clamp(v x, -+2^22)) as a two's-complement word.  The fp64 product of two float32 is exact, the
+// clamp and the scaling are exact: one rounding.  -0.0f (a degenerate SNP) and x = 0 give 0.
+__device__ __forceinline__ uint64_t prod_term(float v, float x)
+{
+    double p = (double)v * (double)x;
+    p = p < -0x1p22 ? -0x1p22 : p;
+    p = p > 0x1p22 ? 0x1p22 : p;
+    return (uint64_t)(int64_t)__builtin_rint(p * 0x1p40);
+}
+// the value the terms multiply: the cell (power 1) or its float32 square (power 2: the multiply of score_term)
+__device__ __forceinline__ float prod_value(float c, bool square) { return square ? c * c : c; }
+
 template <typename Cell>
 __device__ __forceinline__ Cell encode_cell(const LdK &k)
 {

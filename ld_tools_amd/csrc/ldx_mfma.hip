@@ -347,8 +347,11 @@ __device__ __forceinline__ uint64_t dpp_half_sum(uint64_t x)
 // and the categories, in sweeps of three words -- four or five spill).
 // kNbr (with kArea): the neighbour-list band (ldx_ld_neighbors_dev) -- the band's passes and K loop with nbr_epilogue, which
 // appends every pair with r *f32 r >= a float32 bound in both orientations, instead of the rounded hit scan.
+// kProdW (with kArea): the matrix-vector band (ldx_ld_matvec_dev) -- the LD-score band with prod_epilogue, score_epilogue's
+// weighted sibling: float32 weights per SNP instead of mask bits, the cell or its square instead of the square; kProdW is
+// the number of right-hand sides one sweep of the accumulators covers.
 template <bool kRaw, bool kN11, bool kArea = false, bool kFp4 = false, typename Cell = ldx_ld32, int kScoreW = 0,
-          bool kNbr = false>
+          bool kNbr = false, int kProdW = 0>
 __global__ void __launch_bounds__(kMfmaThreads, kArea ? 2 : kWgPerCu)
 triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ fa, const double *__restrict__ fr,
                      const double *__restrict__ q, uint32_t n_snps, uint32_t n_slabs, uint32_t nchunks, double n,
@@ -427,7 +430,9 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
     constexpr bool kScore = kScoreW != 0;   // LD scores (score_epilogue): r32 operands, integer sums instead of hits
     static_assert(!kScore || kArea, "the LD-score epilogue runs on the band");
     static_assert(!kNbr || (kArea && !kScore), "the neighbour epilogue runs on the band");
-    constexpr bool kBandF32 = kFp4 && kArea && !kScore && !kNbr;   // the band screens its steps in float32 first (area_epilogue)
+    constexpr bool kProd = kProdW != 0;     // matrix-vector products (prod_epilogue): the score band with float32 weights
+    static_assert(!kProd || (kArea && !kScore && !kNbr), "the matrix-vector epilogue runs on the band");
+    constexpr bool kBandF32 = kFp4 && kArea && !kScore && !kNbr && !kProd;   // the band screens its steps in float32 first (area_epilogue)
     float *ctab32 = reinterpret_cast<float *>(tickets + 8);                 // [128][4]: F32Col
     float *rtab32 = ctab32 + kSlab * 4u + wave * (kRows64 * 4u);            // [64][4]: F32Row, private to the wave
     uint32_t *qid = reinterpret_cast<uint32_t *>(ctab32 + kSlab * 4u + kMfmaWaves * kRows64 * 4u) + wave * kQueueCap;   // [kQueueCap]
@@ -437,6 +442,9 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                       wave * 64u;   // [64]: parked pairs deferred to the mirror batch (entry << 3 | pair)
     uint32_t *aq_id = reinterpret_cast<uint32_t *>(ctab32 + kSlab * 4u + kMfmaWaves * kRows64 * 4u) + wave * kAreaQueue;   // band: [kAreaQueue]
     uint32_t *aq_cnt = reinterpret_cast<uint32_t *>(ctab32 + kSlab * 4u + kMfmaWaves * kRows64 * 4u) + kMfmaWaves * kAreaQueue + wave * kAreaQueue;
+    // matrix-vector band: the waves' row-sum tables [4][64][8] uint64 take the place of the tables above, and behind them
+    // lie the waves' row weights [64][8] float32 (written per pass beside rstat)
+    auto prod_rows = [&](uint32_t w) { return ctab32 + kMfmaWaves * kRows64 * 16u + w * (kRows64 * 8u); };
     const F32Const fc32 = aa.f32;   // computed on the host (f32_const): kernel arguments live in scalar registers
     // The band (ld_area) hands its passes out PER XCD: the pass list -- j-tile-major, i.e. sorted by position -- is cut into
     // eight contiguous ranges, one per XCD, each with its own counter (sched[2 + 32 x]: the K-loop-token words, which the
@@ -691,7 +699,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             }
             bool rows_ordinary = false;
             typedef double d2s __attribute__((ext_vector_type(2)));
-            if constexpr (kScore || kNbr) {   // LD scores / neighbours: {a, 1 / sqrt(a r)} (r32_snp) and {position, annotation mask}
+            if constexpr (kScore || kNbr || kProd) {   // LD scores / neighbours / products: {a, 1 / sqrt(a r)} (r32_snp) and {position, annotation mask}
                 if (new_tile && tid < kSlab) {
                     const uint32_t j = t * kSlab + tid;
                     const R32Snp c = r32_snp(fa[j], fr[j], n);
@@ -704,6 +712,16 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 d2s *dst = reinterpret_cast<d2s *>(rstat + lane * kStat);
                 dst[0] = d2s{r.a, r.rs};
                 dst[1] = i < n_snps ? d2s{(double)aa.pos[i], (double)(aa.is_query ? aa.is_query[i] : (uint8_t)0)} : d2s{0.0, 0.0};
+                if constexpr (kProd) {   // this row's weights x[i][0 .. 8) (0 beyond n_rhs and beyond the panel): the wave's own table
+                    const float *const x = reinterpret_cast<const float *>(aa.counts);
+                    const uint32_t nr = (uint32_t)aa.measure & 15u;
+                    float xr[8];
+#pragma unroll
+                    for (uint32_t k = 0; k < 8u; ++k) xr[k] = (i < n_snps && k < nr) ? x[(size_t)i * nr + k] : 0.0f;
+                    v4f *xd = reinterpret_cast<v4f *>(prod_rows(wave) + lane * 8u);
+                    xd[0] = v4f{xr[0], xr[1], xr[2], xr[3]};
+                    xd[1] = v4f{xr[4], xr[5], xr[6], xr[7]};
+                }
             } else if constexpr (kR32) {   // signed r: {a, 1 / sqrt(a r)} per SNP (ldx_common.h, r32_snp) in the first two slots
                 if (new_tile && tid < kSlab) {
                     const uint32_t j = t * kSlab + tid;
@@ -909,7 +927,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             // to spare) in instruction arbitration: +2 % at 40k SNPs.
             if (ablate & 32) __builtin_amdgcn_s_setprio(0);
             else if (!(ablate & 16)) __builtin_amdgcn_s_setprio(3);
-            if constexpr (kScore) {
+            if constexpr (kScore || kProd) {
                 // LD scores: every wave is past its last read of the j-tile image -- the two image buffers hold the column
                 // sums of the waves until the next pass's prologue (after the barrier at the top of the loop) overwrites them.
                 // Inactive waves stay for the barriers and the column flush.
@@ -1546,8 +1564,111 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 }
               }
             };
+            // ---- matrix-vector products (ldx_ld_matvec_dev): score_epilogue with weights ----
+            // The same pairs, window test, row path (four columns, dpp_half_sum, lane 31 / 63 -> the wave's LDS row table) and
+            // column path (register sums over 32 rows, one shuffle, the four waves through the image buffers).  What differs:
+            // v = the cell (power 1) or its float32 square (power 2), and pair (i, j) adds prod_term(v, x[j][k]) to row i's
+            // word k and prod_term(v, x[i][k]) to column j's -- two terms per pair and right-hand side.  The row's weights are
+            // broadcast LDS reads beside rstat (prod_rows); the lane's four columns' weights are loaded from global memory
+            // into registers once per sweep (a table of them would push the workgroup past half a CU's LDS).  A sweep
+            // covers kProdW right-hand sides; further ones repeat it, recomputing r32_cell.
+            auto prod_epilogue = [&](uint32_t st, bool square) {
+              if constexpr (kProd) {
+                const double win = aa.flank;   // the window w (integer-valued)
+                const float *const x = reinterpret_cast<const float *>(aa.counts);   // [n_snps][st]
+                uint64_t *const rows_lds = reinterpret_cast<uint64_t *>(ctab32) + wave * (kRows64 * 8u);   // [64 rows][st]
+                const float *const xrow = prod_rows(wave);
+                uint32_t ln = lane;   // (lane-derived values recomputed from an opaque copy of the lane id: see epilogue_f32)
+                asm volatile("" : "+v"(ln));
+                const uint32_t l32e = ln & 31u, halfe = ln >> 5;
+                double ca[4], cs[4], cpos[4];   // this lane's four columns
+#pragma unroll
+                for (int tt = 0; tt < 4; ++tt) {
+                    const d2s c0 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32e) * kStat);
+                    const d2s c1 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32e) * kStat + 2u);
+                    ca[tt] = c0.x;
+                    cs[tt] = c0.y;
+                    cpos[tt] = c1.x;
+                }
+                const uint32_t j0 = t * kSlab + l32e;   // column of tile tt: j0 + 32 tt
+                for (uint32_t w0 = 0; w0 < st; w0 += (uint32_t)kProdW) {   // wave-uniform sweeps
+                    uint64_t csum[4][kProdW];
+                    float xc[4][kProdW];   // the columns' weights of this sweep (0 beyond st and beyond the panel)
+#pragma unroll
+                    for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+                        for (int c = 0; c < kProdW; ++c) {
+                            csum[tt][c] = 0;
+                            const uint32_t j = j0 + 32u * tt;
+                            xc[tt][c] = (j < n_snps && w0 + (uint32_t)c < st) ? x[(size_t)j * st + w0 + (uint32_t)c] : 0.0f;
+                        }
+#pragma unroll 1
+                    for (int e = 0; e < 16; ++e) {
+#pragma unroll
+                        for (int m = 0; m < 2; ++m) {
+                            accel_t c4[4];   // ONE register-indexed read per accumulator, pinned (see area_epilogue)
+#pragma unroll
+                            for (int tt = 0; tt < 4; ++tt) {
+                                c4[tt] = acc[m][tt][e];
+                                asm volatile("" : "+v"(c4[tt]));
+                            }
+                            const uint32_t ri = 32u * m + (uint32_t)(e & 3) + 8u * (uint32_t)(e >> 2) + 4u * halfe;
+                            const d2s r0 = *reinterpret_cast<const d2s *>(rstat + ri * kStat);   // two addresses per wave: broadcast
+                            const d2s r1 = *reinterpret_cast<const d2s *>(rstat + ri * kStat + 2u);
+                            float xr[kProdW];   // the row's weights: broadcast reads (zeros beyond st; kProdW divides 8: w0 + c < 8)
+#pragma unroll
+                            for (int c = 0; c < kProdW; ++c) xr[c] = xrow[ri * 8u + w0 + (uint32_t)c];
+                            const uint32_t i = row0 + ri;
+                            uint64_t rsum[kProdW];
+#pragma unroll
+                            for (int c = 0; c < kProdW; ++c) rsum[c] = 0;
+#pragma unroll
+                            for (int tt = 0; tt < 4; ++tt) {
+                                const double cnt = kFp4 ? (double)c4[tt] : (double)((uint32_t)c4[tt] >> 3);   // int8: 8 n11
+                                float v = prod_value(r32_cell(cnt, n, r0.x, r0.y, ca[tt], cs[tt]).r, square);
+                                const bool ok = i > j0 + 32u * tt && i < n_snps && r1.x - cpos[tt] <= win;
+                                v = ok ? v : 0.0f;   // (a pair outside the band: both terms 0)
+#pragma unroll
+                                for (int c = 0; c < kProdW; ++c) {
+                                    rsum[c] += prod_term(v, xc[tt][c]);
+                                    csum[tt][c] += prod_term(v, xr[c]);
+                                }
+                            }
+#pragma unroll
+                            for (int c = 0; c < kProdW; ++c) {
+                                if (w0 + (uint32_t)c >= st) break;   // wave-uniform
+                                const uint64_t tot = dpp_half_sum(rsum[c]);
+                                if (l32e == 31u) rows_lds[ri * st + w0 + (uint32_t)c] = tot;
+                            }
+                        }
+                    }
+                    // the halves' column sums meet: half 0 keeps column tiles 0, 1, half 1 tiles 2, 3 (one shuffle per pair)
+                    uint64_t *const my_cols = score_cols + (size_t)wave * (kSlab * 9u);
+#pragma unroll
+                    for (int c = 0; c < kProdW; ++c) {
+                        if (w0 + (uint32_t)c >= st) break;   // wave-uniform
+#pragma unroll
+                        for (int p = 0; p < 2; ++p) {
+                            const uint64_t send = halfe ? csum[p][c] : csum[2 + p][c];
+                            const uint64_t mine = halfe ? csum[2 + p][c] : csum[p][c];
+                            const uint64_t got = __shfl_xor(send, 32);
+                            my_cols[(32u * (2u * halfe + (uint32_t)p) + l32e) * st + w0 + (uint32_t)c] = mine + got;
+                        }
+                    }
+                }
+                // this wave's row totals -> sums (its own table: a wave-level barrier suffices)
+                __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): the table writes have landed
+                __builtin_amdgcn_wave_barrier();
+                uint64_t *const sums = reinterpret_cast<uint64_t *>(aa.hits);
+                for (uint32_t f = lane; f < kRows64 * st; f += 64u) {
+                    const uint32_t i = row0 + f / st;
+                    const uint64_t tot = rows_lds[f];
+                    if (tot != 0u && i < n_snps) atomicAdd(reinterpret_cast<unsigned long long *>(sums) + (size_t)i * st + f % st, (unsigned long long)tot);
+                }
+              }
+            };
             auto area_epilogue = [&]() {
-              if constexpr (kArea && MM == 2 && !kScore && !kNbr) {
+              if constexpr (kArea && MM == 2 && !kScore && !kNbr && !kProd) {
                 uint64_t slot = hit_slot, slot_end = hit_slot_end;
                 const double kthr = aa.k_thres;
                 const bool prefilter = aa.k_thres > 2.0;
@@ -1841,9 +1962,14 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 hit_slot_end = slot_end;
               }
             };
-            if constexpr (kScore) {
-                const uint32_t st = 1u + (uint32_t)aa.measure;   // words per SNP: column 0 and K categories
-                if (active) score_epilogue(st);
+            if constexpr (kScore || kProd) {
+                // words per SNP -- score: column 0 and K categories; products: the right-hand sides (bit 4 of measure: power 2)
+                const uint32_t st = kProd ? (uint32_t)aa.measure & 15u : 1u + (uint32_t)aa.measure;
+                if constexpr (kProd) {
+                    if (active) prod_epilogue(st, ((uint32_t)aa.measure & 16u) != 0u);
+                } else {
+                    if (active) score_epilogue(st);
+                }
                 block_sync();   // every wave's column sums are in LDS
                 uint64_t *const sums = reinterpret_cast<uint64_t *>(aa.hits);
                 for (uint32_t f = tid; f < kSlab * st; f += kMfmaThreads) {   // the four waves' sums, one atomic per word
@@ -2391,6 +2517,106 @@ int score_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, cons
                    : launch_score<false, 1>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
 }
 
+// ---- matrix-vector products on the band (ldx_ld_matvec_dev) ------------------------------------------------------------
+// Every SNP's own term (r32_diag or its float32 square, times its weights) WRITES its words -- the call needs no memset of
+// `sums` -- and the two-row query list {0, n - 1} the plan kernel reads, as score_init_kernel.
+__global__ void prod_init_kernel(const uint32_t *__restrict__ acnt, const uint32_t *__restrict__ rcnt,
+                                 const float *__restrict__ x, uint32_t st, bool square, uint32_t n_snps, uint32_t n_hap,
+                                 uint64_t *__restrict__ sums, uint32_t *__restrict__ qrows)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) {
+        qrows[0] = 0u;
+        qrows[1] = n_snps - 1u;
+    }
+    if (i >= n_snps) return;
+    const float v = prod_value(r32_diag((double)acnt[i], (double)rcnt[i], (double)n_hap), square);
+    for (uint32_t c = 0; c < st; ++c) sums[(size_t)i * st + c] = prod_term(v, x[(size_t)i * st + c]);
+}
+
+// the score band's workspace, made monotone in the SNP count: a panel too large for the band's ticket order (which the score
+// layout then drops) reserves the order's largest size instead
+size_t prod_mfma_workspace_bytes(uint32_t n_snps)
+{
+    return score_mfma_workspace_bytes(n_snps) + (area_order_entries(n_snps) ? 0u : kOrderCap * 4u);
+}
+
+constexpr int kProdSweep = 2;   // right-hand sides per sweep of the accumulators (divides 8: prod_epilogue)
+static_assert(8 % kProdSweep == 0, "a sweep's row-weight reads stay inside the row's eight");
+
+template <bool kFp4>
+static int launch_prod(const void *alt, const double *fa, const double *fr, uint32_t n_snps, uint32_t n_hap, uint32_t T,
+                       uint32_t nch, uint64_t units, size_t lds, const AreaArgs &aa, uint32_t *sched, hipStream_t s)
+{
+    static std::atomic<uint64_t> opted{0};   // the dynamic LDS opt-in: once per device (78 KiB)
+    int dev = 0;
+    LDX_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !((opted.load(std::memory_order_relaxed) >> dev) & 1u)) {
+        LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, false, kProdSweep>,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (dev >= 0 && dev < 64) opted.fetch_or(1ull << dev, std::memory_order_relaxed);
+    }
+    triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, false, kProdSweep><<<(uint32_t)device_cus() * 2u, kMfmaThreads, lds, s>>>(
+        (const uint4 *)alt, fa, fr, nullptr, n_snps, T, nch, (double)n_hap, 1.0 / (double)n_hap, 0, units * 8u,
+        (ldx_ld32 *)nullptr, nullptr, nullptr, 0u, 0u, 0u, sched, 0, nullptr, aa);
+    LDX_HIP(hipGetLastError());
+    return LDX_OK;
+}
+
+int prod_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
+              uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, const float *x, uint32_t n_rhs,
+              bool square, bool fp4, int64_t *sums, void *workspace, hipStream_t s)
+{
+    const uint32_t T = n_slabs(n_snps), nch = n_chunks(n_hap);
+    if ((uint64_t)T * nch * kSlab * 16u >= (1ull << 32)) {   // the K loop addresses the plane with 32-bit lane offsets
+        set_error("ldx_ld_matvec_dev: a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", n_snps, n_hap);
+        return LDX_E_UNSUPPORTED;
+    }
+    // the band's buffers, carved as in score_mfma
+    char *w = (char *)workspace + ((size_t)n_snps + 255u) / 256u * 256u;
+    uint32_t *pass_base = (uint32_t *)w;
+    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
+    uint32_t *g_end = (uint32_t *)w;
+    w += ((size_t)T * 4u + 255u) / 256u * 256u;
+    uint32_t *g_begin = (uint32_t *)w;
+    w += ((size_t)T * 4u + 255u) / 256u * 256u;
+    uint32_t *first_base = (uint32_t *)w;
+    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
+    uint32_t *order = area_order_entries(n_snps) ? (uint32_t *)w : nullptr;
+    w += (area_order_entries(n_snps) * 4u + 255u) / 256u * 256u;
+    uint32_t *sched = (uint32_t *)w;
+    w += kAreaSchedWords * 4u;
+    uint32_t *qrows = (uint32_t *)w;                               // [2]
+    unsigned long long *n_hits = (unsigned long long *)(w + 8);   // the plan kernel zeroes it; nothing reads it
+    prod_init_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(acnt, rcnt, x, n_rhs, square, n_snps, n_hap, (uint64_t *)sums, qrows);
+    LDX_HIP(hipGetLastError());
+    if (n_snps < 2) return LDX_OK;   // no pairs
+    // the plan keeps every pair with pos_i - pos_j <= window, as for the scores; prod_epilogue applies the exact bound per pair
+    area_band_plan_kernel<<<1, 1024, 0, s>>>(positions, n_snps, T, window, qrows, 2u, g_begin, g_end, pass_base, n_hits,
+                                             order, first_base, sched);
+    LDX_HIP(hipGetLastError());
+    AreaArgs aa{};
+    aa.f32 = f32_const((double)n_hap);
+    aa.pos = positions;
+    aa.is_query = nullptr;
+    aa.pass_base = pass_base;
+    aa.g_begin = g_begin;
+    aa.g_end = g_end;
+    aa.order = order;
+    aa.hits = (ldx_hit *)sums;                                         // products: the int64 sums [n_snps][n_rhs]
+    aa.counts = reinterpret_cast<uint32_t *>(const_cast<float *>(x));   // products: the float32 weights [n_snps][n_rhs] (read only)
+    aa.n_hits = n_hits;
+    aa.flank = (double)window;
+    aa.measure = (int)(n_rhs | (square ? 16u : 0u));                   // products: n_rhs, bit 4 = power 2
+    const uint64_t units = ldx_triangle_units(n_snps) / 8u;   // 64-row units of the full triangle
+    // + the row-sum tables [4][64][8] uint64 and the row-weight tables [4][64][8] float32
+    const size_t lds = mfma_lds_bytes(kRows64, false, false) + (size_t)kMfmaWaves * kRows64 * 8u * (sizeof(uint64_t) + sizeof(float));
+    static_assert(2u * (mfma_lds_bytes(kRows64, false, false) + (size_t)kMfmaWaves * kRows64 * 8u * 12u) <= 160u * 1024u,
+                  "two workgroups per CU");
+    if (fp4) return launch_prod<true>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
+    return launch_prod<false>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
+}
+
 // ---- neighbour lists on the band (ldx_ld_neighbors_dev) ----------------------------------------------------------------
 // the two-row query list {0, n - 1} the plan kernel reads (every SNP a query: the plan keeps every tile's whole band)
 __global__ void nbr_init_kernel(uint32_t n_snps, uint32_t *__restrict__ qrows)
@@ -2511,6 +2737,37 @@ extern "C" int ldx_ld_neighbors_dev(const void *alt, const uint32_t *acnt, const
     const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles: keep pos + window exact
     return ldx::nbr_mfma(alt, fa, fr, n_snps, n_hap, positions, window < wmax ? window : wmax, r2_bound, path != LDX_PATH_MFMA,
                          hits, hit_cap, n_hits, row_counts, workspace, (hipStream_t)stream);
+}
+
+extern "C" size_t ldx_ld_matvec_workspace_bytes(uint32_t n_snps, uint32_t n_hap)
+{
+    (void)n_hap;   // (the layout depends on the SNP count alone)
+    return ldx::prod_mfma_workspace_bytes(n_snps ? n_snps : 1u);
+}
+
+extern "C" int ldx_ld_matvec_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
+                                 uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, const float *x,
+                                 uint32_t n_rhs, int power, int path, int64_t *sums, void *workspace, size_t workspace_bytes,
+                                 void *stream)
+{
+    LDX_REQUIRE(alt && acnt && rcnt && fa && fr && positions && x && sums && workspace, "null pointer");
+    LDX_REQUIRE(n_rhs >= 1u && n_rhs <= 8u, "n_rhs must be 1 .. 8");
+    LDX_REQUIRE(power == 1 || power == 2, "power must be 1 or 2");
+    LDX_REQUIRE(n_snps >= 1 && n_hap >= 1 && window >= 0, "bad shape");
+    LDX_REQUIRE(((uintptr_t)workspace & 255u) == 0, "workspace must be 256-byte aligned");
+    LDX_REQUIRE(workspace_bytes >= ldx::prod_mfma_workspace_bytes(n_snps), "workspace too small (see ldx_ld_matvec_workspace_bytes)");
+    LDX_REQUIRE(path == LDX_PATH_AUTO || path == LDX_PATH_POPCOUNT || path == LDX_PATH_MFMA || path == LDX_PATH_FP4, "unknown path");
+    if (n_hap > LDX_MAX_HAPS) {
+        ldx::set_error("ldx_ld_matvec_dev: n_hap %u > LDX_MAX_HAPS %u", n_hap, LDX_MAX_HAPS);
+        return LDX_E_UNSUPPORTED;
+    }
+    if (path == LDX_PATH_POPCOUNT) {
+        ldx::set_error("ldx_ld_matvec_dev: the products run on the matrix-pipe band (LDX_PATH_FP4 / LDX_PATH_MFMA), not on the popcount kernels");
+        return LDX_E_UNSUPPORTED;
+    }
+    const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles: keep pos + window exact
+    return ldx::prod_mfma(alt, acnt, rcnt, fa, fr, n_snps, n_hap, positions, window < wmax ? window : wmax, x, n_rhs, power == 2,
+                          path != LDX_PATH_MFMA, sums, workspace, (hipStream_t)stream);
 }
 
 extern "C" size_t ldx_ld_score_workspace_bytes(uint32_t n_snps, uint32_t n_hap)

@@ -3,6 +3,8 @@
     ld_triangle(panel)                      <- ld_triangle.py:133-230  (all row > col pairs)
     ld_area(panel, positions, queries, ...) <- ld_area.py:152-276      (windowed scan, thresholded hits)
     ld_score(panel, positions, ...)         LD scores: windowed sums of r^2 per SNP (LDSC's l2), optionally per category
+    ld_matvec(panel, x, positions, ...)     R x (or R^2 x) over the window for up to 8 vectors, without the matrix
+    ld_ridge(panel, z, positions, ...)      (R + lam I) beta = z by conjugate gradients on ld_matvec
     ld_neighbors(panel, positions, ...)     per-SNP lists of the SNPs in the window with r^2 above a threshold
     ld_clump / ld_prune                     greedy clumping (PLINK --clump) and priority pruning on those lists
     pair_counts(panel_i, panel_j)           <- calc_ld.py:32           (bit-exact n11 block)
@@ -712,6 +714,230 @@ def ld_score(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, win
     if pos_h is None:   # positions stayed on the device: fetched with m
         res.positions = pos      # type: ignore[assignment]
     res._keep = (pos, annot_d, workspace)   # alive until the launch is done (stream-ordered frees would allow reuse anyway)
+    return res
+
+
+# --------------------------------------------------------------------------- R x without the matrix, ridge solves
+PROD_SCALE_BITS = 40             # sums are integers in units of 2^-40 (include/ldx.h, ldx_ld_matvec_dev)
+PROD_CLAMP = float(1 << 22)      # |v x| beyond it is clamped before scaling (keeps the int64 conversion defined)
+MAX_RHS = 8
+RIDGE_BATCH = 8                  # CG iterations enqueued between two reads of the convergence flags
+
+
+def prod_terms(v, x) -> np.ndarray:
+    """Host mirror of the kernel's term (include/ldx.h, ldx_ld_matvec_dev): rint(2^40 * clamp(v x, -+2^22)) as int64, from
+    float32 values v (r cells for power 1; ``prod_values(r, 2)`` for power 2) and float32 weights x, broadcast against each
+    other.  The fp64 product of two float32 is exact, so is the scaling: one round-half-even."""
+    v = np.asarray(v, dtype=np.float32).astype(np.float64)
+    x = np.asarray(x, dtype=np.float32).astype(np.float64)
+    p = np.clip(v * x, -PROD_CLAMP, PROD_CLAMP)
+    return np.rint(np.ldexp(p, PROD_SCALE_BITS)).astype(np.int64)
+
+
+def prod_values(r, power: int = 1) -> np.ndarray:
+    """The value the terms multiply: the float32 r cell (power 1) or r *f32 r, ONE float32 multiply (power 2: what
+    score_terms scales)."""
+    r = np.asarray(r, dtype=np.float32)
+    if power == 1:
+        return r
+    if power == 2:
+        return np.multiply(r, r, dtype=np.float32)
+    raise _lib.LdxError(f"power must be 1 or 2 (got {power!r})")
+
+
+def _pow2(e: torch.Tensor) -> torch.Tensor:
+    """2^e as float64 for an int64 tensor e in [-1022, 1023], built from the exponent bits: exact on every device."""
+    return ((e + 1023) << 52).view(torch.float64)
+
+
+def matvec_rhs(x, n_snps: int, power: int = 1, check_finite: bool = True, device=None):
+    """Validate and scale the right-hand sides of ld_matvec.  ``x``: [n] or [n, k] (1 <= k <= 8), numpy or torch, real.
+    Each column is multiplied by 2^-e, e the smallest integer with max |x| 2^-e <= 1 (the scaled maximum lies in (0.5, 1];
+    a column within (0.5, 1] already, a 0/1 annotation say, and an all-zero column keep e = 0) -- exact -- and only then
+    converted to float32.  Returns (x32 float32 [n, k] contiguous,
+    e int64 [k], squeeze: x was one-dimensional), tensors on ``device`` (default: where x is)."""
+    if power not in (1, 2):
+        raise _lib.LdxError(f"power must be 1 or 2 (got {power!r})")
+    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+    if t.is_complex() or t.dtype == torch.bool:
+        raise _lib.LdxError(f"x must be real (got {t.dtype})")
+    squeeze = t.ndim == 1
+    if squeeze:
+        t = t[:, None]
+    if t.ndim != 2 or t.shape[0] != n_snps:
+        raise _lib.LdxError(f"x must have shape [n_snps] or [n_snps, k] (n_snps = {n_snps}), got {tuple(x.shape)}")
+    if not 1 <= t.shape[1] <= MAX_RHS:
+        raise _lib.LdxError(f"1 to {MAX_RHS} right-hand sides per call (got {t.shape[1]})")
+    if device is not None:
+        t = t.to(device)
+    t = t.to(torch.float64)
+    if check_finite and not bool(torch.isfinite(t).all().item()):
+        raise _lib.LdxError("x must be finite")
+    big = t.abs().amax(dim=0)
+    mant, e = torch.frexp(big)                              # big = mant 2^e, mant in [0.5, 1)
+    e = e.to(torch.int64) - (mant == 0.5).to(torch.int64)   # the smallest e with big 2^-e <= 1 (a power of two: exactly 1)
+    e = torch.where(big > 0, e, torch.zeros_like(e)).clamp(-1000, 1000)
+    x32 = (t * _pow2(-e)).to(torch.float32).contiguous()
+    return x32, e, squeeze
+
+
+@dataclass
+class LDProduct:
+    """A banded LD matrix-vector product (ld_matvec).  ``sums``: the device int64 tensor [n, k] the kernel wrote, in units
+    of 2^(e_k - 40); ``exps``: device int64 [k], the columns' exponents e; ``x32``: the float32 values actually multiplied
+    (x 2^-e, rounded to float32 once)."""
+
+    sums: torch.Tensor
+    exps: torch.Tensor
+    x32: torch.Tensor
+    window: int
+    power: int
+    squeeze: bool = False
+
+    def values(self) -> torch.Tensor:
+        """float64 device tensor [n, k] ([n] for a one-dimensional x): sums 2^(e - 40), i.e. R_w x (power 2: (R_w o R_w) x)."""
+        y = self.sums.to(torch.float64) * _pow2(self.exps - PROD_SCALE_BITS)
+        return y[:, 0] if self.squeeze else y
+
+    def x(self) -> torch.Tensor:
+        """float64 device tensor: the vectors the product is exactly that of (x32 rescaled), shaped like ``values()``."""
+        y = self.x32.to(torch.float64) * _pow2(self.exps)
+        return y[:, 0] if self.squeeze else y
+
+
+def _matvec_launch(panel: PackedPanel, pos: torch.Tensor, window: int, x32: torch.Tensor, power: int, pcode: int,
+                   workspace: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    n, k = x32.shape
+    need = lib.ldx_ld_matvec_workspace_bytes(n, panel.n_hap)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=panel.device)
+    elif workspace.numel() * workspace.element_size() < need:
+        raise _lib.LdxError(f"workspace too small: {need} bytes needed")
+    sums = torch.empty((n, k), dtype=torch.int64, device=panel.device)
+    check(lib.ldx_ld_matvec_dev(panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), panel.fa.data_ptr(),
+                                panel.fr.data_ptr(), n, panel.n_hap, pos.data_ptr(), window, x32.data_ptr(), k, power, pcode,
+                                sums.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                _stream_ptr()), "ldx_ld_matvec_dev")
+    return sums, workspace
+
+
+def ld_matvec(panel: PackedPanel, x, positions=None, window_bp: int = 1_000_000, window_snps: Optional[int] = None,
+              power: int = 1, path: str = "auto", workspace: Optional[torch.Tensor] = None, check_positions: bool = True,
+              check_finite: bool = True) -> LDProduct:
+    """y = R_w x on the matrix-pipe band, without the matrix (include/ldx.h, ldx_ld_matvec_dev): for every SNP i the sum of
+    r_ij x_j over the SNPs j with |pos_i - pos_j| <= window (i included, r_ii = r_matrix()'s diagonal), r the signed r of
+    ld_triangle(fmt="r32") bit for bit; ``power=2`` sums r^2 x_j instead (r^2 one float32 multiply) -- the LD score of a
+    continuous annotation x.  ``x``: [n] or [n, k], k <= 8 right-hand sides in one band sweep; numpy or a device tensor,
+    float32 or float64.  Each column is scaled by a power of two to max |x| <= 1 and converted to float32 (matvec_rhs); the
+    kernel adds rint(2^40 r x) as 64-bit integers, so the result is reproducible run to run and identical on both paths,
+    every term within 2^-41 (times the column's scale) of exact.
+
+    Positions and window as for ld_score.  ``path``: 'auto' / 'fp4' (the FP4 band) or 'mfma' (the int8 band: identical
+    sums).  ``workspace``: a uint8 device tensor of ldx_ld_matvec_workspace_bytes() bytes to reuse (one per launch that may
+    be in flight).  The call is stream-ordered; with ``check_positions`` and ``check_finite`` off and device tensors in it
+    reads nothing on the host.  ``LDProduct.values()`` is the float64 result on the device."""
+    require_gpu()
+    pos, _, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_matvec")
+    x32, e, squeeze = matvec_rhs(x, panel.n_snps, power, check_finite, panel.device)
+    sums, workspace = _matvec_launch(panel, pos, window, x32, power, PATHS[path], workspace)
+    res = LDProduct(sums, e, x32, window, power, squeeze)
+    res._keep = (pos, workspace)   # alive until the launch is done
+    return res
+
+
+@dataclass
+class RidgeResult:
+    """ld_ridge's solution.  ``beta``: float64 device tensor shaped like z (NaN in a column reported ``indefinite``);
+    per column (numpy): ``iterations`` taken, ``converged`` (||r|| <= tol ||z|| on the recurrence residual),
+    ``indefinite`` (a direction with p.Ap <= 0 was met: the windowed matrix is not positive definite; no solution is
+    returned) and ``residual`` = ||r|| / ||z|| of the recurrence when the column stopped."""
+
+    beta: torch.Tensor
+    iterations: np.ndarray
+    converged: np.ndarray
+    indefinite: np.ndarray
+    residual: np.ndarray
+
+
+def cg_solve(product, z: torch.Tensor, lam: float, tol: float = 1e-6, max_iter: int = 1000,
+             batch: int = RIDGE_BATCH) -> RidgeResult:
+    """Conjugate gradients for (R + lam I) beta = z, the columns of ``z`` (float64 [n, k]) side by side with per-column
+    step sizes.  ``product(P)`` returns (R Q, Q) for a float64 [n, k] tensor P, Q being the vectors it really multiplied
+    (P rounded to what the product can represent; Q = P for an exact product): the recurrence then steps along Q, so beta
+    and the residual stay consistent with the products that were computed.  Step and update coefficients are the local
+    ones (alpha = p.r / p.Ap, the next direction A-orthogonalised against p), which hold for a rounded direction too.  A
+    column stops when ||r|| <= tol ||z|| or when p.Ap <= 0 (``indefinite``); a stopped column keeps its beta and multiplies
+    zeros from then on.  The flags are read on the host once per ``batch`` iterations."""
+    if z.ndim != 2:
+        raise _lib.LdxError("cg_solve: z must be [n, k]")
+    z = z.to(torch.float64)
+    k = z.shape[1]
+    lam = float(lam)
+    beta = torch.zeros_like(z)
+    r = z.clone()
+    z2 = (z * z).sum(dim=0)
+    bound = (float(tol) ** 2) * z2
+    rs = z2.clone()
+    converged = rs <= bound                       # an all-zero column: beta = 0
+    active = ~converged
+    indefinite = torch.zeros(k, dtype=torch.bool, device=z.device)
+    iters = torch.zeros(k, dtype=torch.int64, device=z.device)
+    zero = torch.zeros((), dtype=torch.float64, device=z.device)
+    p = torch.where(active, r, zero)
+    for it in range(int(max_iter)):
+        rq, p = product(p)
+        ap = rq + lam * p
+        pap = (p * ap).sum(dim=0)
+        bad = active & ~(pap > 0)                 # (a NaN counts as not positive)
+        indefinite |= bad
+        active = active & ~bad
+        alpha = torch.where(active, (p * r).sum(dim=0) / pap, zero)
+        beta = beta + alpha * p
+        r = r - alpha * ap
+        rs = torch.where(active, (r * r).sum(dim=0), rs)
+        iters += active
+        done = active & (rs <= bound)
+        converged |= done
+        active = active & ~done
+        gamma = torch.where(active, -(r * ap).sum(dim=0) / pap, zero)
+        p = torch.where(active, r + gamma * p, zero)
+        if (it + 1) % int(batch) == 0 and not bool(active.any().item()):
+            break
+    beta = torch.where(indefinite, torch.full_like(zero, float("nan")), beta)
+    z2h = z2.cpu().numpy()
+    res = np.sqrt(rs.cpu().numpy() / np.where(z2h > 0, z2h, 1.0))
+    return RidgeResult(beta, iters.cpu().numpy(), converged.cpu().numpy(), indefinite.cpu().numpy(), res)
+
+
+def ld_ridge(panel: PackedPanel, z, positions=None, window_bp: int = 1_000_000, window_snps: Optional[int] = None,
+             lam: float = 1.0, tol: float = 1e-6, max_iter: int = 1000, path: str = "auto",
+             check_positions: bool = True) -> RidgeResult:
+    """Solve (R_w + lam I) beta = z by conjugate gradients on ld_matvec -- ridge / infinitesimal polygenic scores from
+    summary statistics, R_w never formed.  ``z``: [n] or [n, k], k <= 8 columns solved side by side (one ld_matvec launch per
+    iteration for all of them).  Before each product the search direction is replaced by the float32 vector the kernel
+    really multiplies (LDProduct.x()), so the only product error left is the kernel's 2^-41 term rounding.  A windowed R
+    need not be positive definite: a column that meets p.Ap <= 0 is reported ``indefinite`` with NaN in beta (cg_solve)."""
+    dev = require_gpu()
+    pos, _, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_ridge")
+    zt = z if isinstance(z, torch.Tensor) else torch.as_tensor(np.asarray(z))
+    squeeze = zt.ndim == 1
+    matvec_rhs(zt, panel.n_snps)   # shape, column count, finiteness
+    zt = (zt[:, None] if squeeze else zt).to(panel.device, dtype=torch.float64)
+    if not (float(lam) >= 0.0 and np.isfinite(float(lam))):
+        raise _lib.LdxError(f"lam must be a finite number >= 0 (got {lam})")
+    ws = torch.empty(lib.ldx_ld_matvec_workspace_bytes(panel.n_snps, panel.n_hap), dtype=torch.uint8, device=panel.device)
+    pcode = PATHS[path]
+
+    def product(p):
+        x32, e, _ = matvec_rhs(p, panel.n_snps, 1, False)
+        sums, _ = _matvec_launch(panel, pos, window, x32, 1, pcode, ws)
+        lp = LDProduct(sums, e, x32, window, 1)
+        return lp.values(), lp.x()
+
+    res = cg_solve(product, zt, lam, tol, max_iter)
+    if squeeze:
+        res.beta = res.beta[:, 0]
+    del dev
     return res
 
 
