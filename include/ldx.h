@@ -111,6 +111,10 @@ typedef struct { uint16_t value; } ldx_k16one;
  *     cell = -0.0f                                      if a_i r_i == 0 or a_j r_j == 0 (the reference's degenerate SNPs:
  *                                                       its r^2 is the int 0 there, as in ldx_ld32)
  *     cell = float32 of num / sqrt(a_i r_i a_j r_j)     otherwise, within 4 float32 ulps of the exact value; +0.0f iff num == 0
+ *     cell = +1.0f / -1.0f exactly                      when num^2 == a_i r_i a_j r_j (an exact duplicate / complement of a row without
+ *                                                       missing codes): the fp64 arithmetic is within ~4 2^-53 of +-1, far inside half a
+ *                                                       float32 ulp, so ldx_ld_neighbors_dev keeps the pair at r2_bound = 1.0f (s = 1.0f)
+ *                                                       and drops it at the next float32 above 1
  * r > 0 when ALT alleles co-occur more often than independence predicts (D > 0); r^2 is the reference's unrounded r^2
  * (calc_ld.py:50,86-90), so with missing codes |r| may exceed 1.  Without missing codes r is the Pearson correlation of the
  * two 0/1 haplotype vectors.  Every kernel computes it with the same arithmetic: the cells are bit-identical across

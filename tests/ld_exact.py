@@ -1,0 +1,352 @@
+"""An exact oracle for the signed-r family (r32 cells, LD scores, neighbour lists, clumping, pruning, R x), computed from
+the allele codes with integers -- TEST INFRASTRUCTURE ONLY, a plain module (imported like tests/fakevcf.py).
+
+Written from the definitions in include/ldx.h alone; numpy and the standard library only.  With n = n_hap, a / r the
+counts of code 1 / code 0 per SNP (any other code is missing: in n only) and n11 the alt/alt count of a pair:
+
+    num  = n n11 - a_i a_j        int64, |num| < 2^27 at n <= 10 240
+    den2 = a_i r_i a_j r_j        int64, < 2^50
+    r    = num / sqrt(den2)       (float64: sqrt and the division round once each)
+    r^2  = num^2 / den2           (num^2 < 2^54 is an exact int64; the conversion and the division round once each)
+
+A SNP with a r == 0 is degenerate (its cells are -0.0f); a pair with num == 0 has the cell +0.0f.  The diagonal is the same
+formula at i = j, (n - a) / r.  n11 comes from a float32 GEMM of the 0/1 ALT plane: every partial sum is an integer
+<= 10 240 < 2^24, so it is exact in any summation order.
+
+Threshold decisions (neighbour lists keep a pair iff s = r *f32 r >= b, b the float32 bound of the threshold t): the
+contract puts the cell within 4 float32 ulps of exact r, a relative error of at most 4 2^-23, so s is within
+(1 + 4 2^-23)^2 (1 + 2^-24) - 1 < 8.6 2^-23 of exact r^2; b (the smallest float32 not below, or above, t) lies within
+2^-23 of t.  Together under 9.6 2^-23 < 2^-19, hence
+    decided in   num^2 >= t (1 + 2^-19) den2      every conforming kernel reports the pair
+    decided out  num^2 <= t (1 - 2^-19) den2      no conforming kernel reports it
+    ambiguous    otherwise                         either answer conforms
+evaluated in float64 and, for a pair within 2^-40 relative of an edge, with fractions.Fraction.
+"""
+from __future__ import annotations
+
+from fractions import Fraction
+
+import numpy as np
+
+MAX_HAPS = 10240                  # LDX_MAX_HAPS
+MARGIN = Fraction(1, 1 << 19)     # relative margin of a threshold decision (derived above)
+OUT, AMBIGUOUS, IN = 0, 1, 2      # decision classes
+
+
+def alt_counts_gemm(codes, block: int = 512) -> np.ndarray:
+    """n11 int64 [n, n] from a blocked float32 GEMM of the ALT plane (exact: every partial sum < 2^24)."""
+    codes = np.asarray(codes)
+    n, h = codes.shape
+    assert h < (1 << 24)
+    A = (codes == 1).astype(np.float32)
+    out = np.empty((n, n), dtype=np.int64)
+    for r0 in range(0, n, block):
+        blk = A[r0:r0 + block] @ A.T
+        out[r0:r0 + block] = blk.astype(np.int64)
+        assert np.array_equal(out[r0:r0 + block].astype(np.float32), blk)   # integers, nothing lost
+    return out
+
+
+class Exact:
+    """Exact pair statistics of one int8 code matrix [n_snps, n_hap] (1 = ALT, 0 = REF, anything else missing)."""
+
+    def __init__(self, codes):
+        codes = np.asarray(codes)
+        assert codes.ndim == 2 and codes.dtype == np.int8
+        self.n_snps, self.n_hap = codes.shape
+        assert 1 <= self.n_hap <= MAX_HAPS
+        n = np.int64(self.n_hap)
+        self.a = (codes == 1).sum(axis=1).astype(np.int64)
+        self.r = (codes == 0).sum(axis=1).astype(np.int64)
+        self.n11 = alt_counts_gemm(codes)
+        assert np.array_equal(np.diagonal(self.n11), self.a) and np.array_equal(self.n11, self.n11.T)
+        assert int(self.n11.max(initial=0)) <= self.n_hap
+        self.num = n * self.n11 - np.multiply.outer(self.a, self.a)
+        ar = self.a * self.r
+        self.den2 = np.multiply.outer(ar, ar)
+        # nothing overflows: the bounds of the module docstring, checked on the values themselves
+        assert int(np.abs(self.num).max(initial=0)) < (1 << 27) and int(ar.max(initial=0)) < (1 << 25)
+        assert int(self.den2.max(initial=0)) < (1 << 50) and int(self.den2.min(initial=0)) >= 0
+        self.num2 = self.num * self.num
+        assert int(self.num2.max(initial=0)) < (1 << 54)
+        self.live = ar > 0                         # bool [n]: not degenerate
+        self.degenerate = self.den2 == 0           # bool [n, n]: the cell is -0.0f
+        self.zero_num = (self.num == 0) & ~self.degenerate   # the cell is +0.0f
+        den = np.where(self.degenerate, 1, self.den2).astype(np.float64)
+        self.r64 = np.where(self.degenerate, 0.0, self.num.astype(np.float64) / np.sqrt(den))
+        self.r2_64 = np.where(self.degenerate, 0.0, self.num2.astype(np.float64) / den)
+        self._classes = {}
+
+    def diagonal(self) -> np.ndarray:
+        """float64 [n]: (n - a) / r, 0 for a degenerate SNP (whose cell is -0.0f)."""
+        return np.where(self.live, (self.n_hap - self.a) / np.where(self.live, self.r, 1).astype(np.float64), 0.0)
+
+    def _at_least(self, edge: Fraction) -> np.ndarray:
+        """bool [n, n]: num^2 >= edge * den2, exactly (degenerate pairs: False)."""
+        e = float(edge)
+        q = self.r2_64
+        sure = q >= e * (1.0 + 2.0 ** -40)
+        near = ~sure & (q > e * (1.0 - 2.0 ** -40)) & ~self.degenerate
+        out = sure & ~self.degenerate
+        for i, j in zip(*np.nonzero(near)):
+            out[i, j] = Fraction(int(self.num2[i, j])) >= edge * int(self.den2[i, j])
+        return out
+
+    def classes(self, t: float) -> np.ndarray:
+        """uint8 [n, n]: IN / OUT / AMBIGUOUS for r^2 against the threshold t (diagonal included; callers mask it)."""
+        t = float(t)
+        if t not in self._classes:
+            assert t > 0.0
+            ft = Fraction(t)
+            above_in = self._at_least(ft * (1 + MARGIN))
+            edge_out = ft * (1 - MARGIN)
+            above_out = self._at_least(edge_out)
+            # decided out is num^2 <= edge_out * den2: not above it, or exactly on it
+            e = float(edge_out)
+            on = above_out & (self.r2_64 <= e * (1.0 + 2.0 ** -40))
+            for i, j in zip(*np.nonzero(on)):
+                if Fraction(int(self.num2[i, j])) == edge_out * int(self.den2[i, j]):
+                    above_out[i, j] = False
+            c = np.full(self.num.shape, AMBIGUOUS, dtype=np.uint8)
+            c[~above_out] = OUT
+            c[above_in] = IN
+            c[self.degenerate] = OUT
+            self._classes[t] = c
+        return self._classes[t]
+
+
+def window_mask(positions, window: int) -> np.ndarray:
+    """bool [n, n]: |pos_i - pos_j| <= window (the diagonal included)."""
+    pos = np.asarray(positions, dtype=np.int64)
+    return np.abs(pos[:, None] - pos[None, :]) <= int(window)
+
+
+def pair_classes(ex: Exact, t: float, positions, window: int):
+    """(decided in, ambiguous, in-window) bool [n, n] of the ordered pairs i != j inside the window."""
+    w = window_mask(positions, window)
+    np.fill_diagonal(w, False)
+    c = ex.classes(t)
+    return (c == IN) & w, (c == AMBIGUOUS) & w, w
+
+
+def ulp32_err(got32, exact64) -> np.ndarray:
+    """|got - exact| in float32 ulps of the exact value (exact != 0): the ulp of x in [2^(e-1), 2^e) is 2^(e-24)."""
+    exact64 = np.asarray(exact64, dtype=np.float64)
+    _, e = np.frexp(exact64)
+    return np.abs(np.asarray(got32).astype(np.float64) - exact64) / np.ldexp(1.0, e - 24)
+
+
+def tile_crossing(mask) -> int:
+    """Ordered pairs of a bool [n, n] mask whose two SNPs lie in different 128-column tiles."""
+    n = mask.shape[0]
+    t = np.arange(n) // 128
+    return int((mask & (t[:, None] != t[None, :])).sum())
+
+
+def far_apart(mask, d: int = 32) -> int:
+    """Ordered pairs of a bool [n, n] mask that are d or more SNPs apart."""
+    k = np.arange(mask.shape[0])
+    return int((mask & (np.abs(k[:, None] - k[None, :]) >= d)).sum())
+
+
+# ---- the sequential greedy rule, with ranks from Python's sorted -------------------------------------------------------
+def greedy(order, neighbours, member_ok):
+    """Take the candidates in `order`; one not yet assigned becomes an index and takes every neighbour that is not yet
+    assigned and has member_ok.  neighbours[i]: iterable of rows.  Returns (index rows in order, owner int64 [n], -1 = none)."""
+    owner = [-1] * len(member_ok)
+    index = []
+    for i in order:
+        if owner[i] >= 0:
+            continue
+        owner[i] = i
+        index.append(i)
+        for j in neighbours[i]:
+            if owner[j] < 0 and member_ok[j]:
+                owner[j] = i
+    return index, np.asarray(owner, dtype=np.int64)
+
+
+def clump_exact(nbr_mask, pvalues, p1: float, p2: float, live):
+    """Clumping: candidates p <= p1 in increasing (p, row); members need p <= p2; NaN p and degenerate SNPs take no part."""
+    p = [float(x) for x in pvalues]
+    ok = [bool(l) and x == x for l, x in zip(live, p)]
+    order = [k for _, k in sorted((p[k], k) for k in range(len(p)) if ok[k] and p[k] <= p1)]
+    member_ok = [ok[k] and p[k] <= p2 for k in range(len(p))]
+    return greedy(order, [np.flatnonzero(row).tolist() for row in nbr_mask], member_ok)
+
+
+def prune_exact(nbr_mask, priority, live) -> np.ndarray:
+    """Pruning: the live SNPs in decreasing priority, ties by row; bool [n] keep mask."""
+    pr = [float(x) for x in priority]
+    order = [k for _, k in sorted((-pr[k], k) for k in range(len(pr)) if live[k])]
+    index, _ = greedy(order, [np.flatnonzero(row).tolist() for row in nbr_mask], [bool(l) for l in live])
+    keep = np.zeros(len(pr), dtype=bool)
+    keep[index] = True
+    return keep
+
+
+# ---- panels with LD that reaches across 128-column tiles ------------------------------------------------------------
+# synth's default LD blocks are 32 aligned SNPs: no pair with r^2 >= 0.2 is 32 or more SNPs apart or straddles a 128-column
+# tile boundary.  These use blocks longer than two tiles with a high copy probability.
+LONG_RANGE = {
+    "lr1000": dict(n_snps=1000, n_hap=1008, seed=5, block_len=333, rho=0.98, miss=0.01, mono=0.02),
+    "lr700": dict(n_snps=700, n_hap=333, seed=7, block_len=200, rho=0.98, miss=0.01, mono=0.02),
+    "lr2500": dict(n_snps=2500, n_hap=10240, seed=9, block_len=500, rho=0.985, miss=0.002, mono=0.02),
+}
+PLANT_DELTAS = (0, 1, 127)
+
+
+def long_range_codes(name: str) -> np.ndarray:
+    """The generated panel alone (what the pinned pair counts refer to)."""
+    from ld_tools_amd import synth
+    return synth.synth_codes_host(**LONG_RANGE[name])
+
+
+def plant_copies(codes):
+    """Plant exact duplicates and exact complements of complete rows at distances 128 k + delta, delta in PLANT_DELTAS,
+    in place.  Returns [(source row, planted row, +1 or -1)].  A source row is made complete (its missing codes become REF)
+    and must stay polymorphic; rows are taken from the front so that sources and targets never collide."""
+    n, h = codes.shape
+    plants = []
+    src = 3
+    for k in (1, 2, 3, 5):
+        for delta in PLANT_DELTAS:
+            for sign in (1, -1):
+                dst = src + 128 * k + delta
+                if dst >= n:
+                    continue
+                row = np.where(codes[src] == 1, 1, 0).astype(np.int8)
+                if row.min() == row.max():       # a monomorphic source: give it both alleles
+                    row[: h // 3 + 1] = 1
+                    row[h // 3 + 1:] = 0
+                codes[src] = row
+                codes[dst] = row if sign > 0 else 1 - row
+                plants.append((src, dst, sign))
+                src += 1
+    return plants
+
+
+_PANELS = {}
+
+
+def long_range_panel(name: str):
+    """(codes with planted copies, plants, Exact) of a long-range panel; built once per process, never modified."""
+    if name not in _PANELS:
+        codes = long_range_codes(name)
+        plants = plant_copies(codes) if codes.shape[1] >= 2 else []
+        codes.setflags(write=False)
+        _PANELS[name] = (codes, plants, Exact(codes))
+    return _PANELS[name]
+
+
+# ---- the cases of tests/test_gpu_exact_oracle.py, pinned on the CPU by tests/test_ld_exact_host.py ---------------------
+NEIGHBOUR_THRESHOLDS = (0.05, 0.2, 0.5, 0.8)
+AMBIGUOUS_SHARE_MAX = 1e-4        # of the in-window ordered pairs, per (panel, threshold, window)
+
+
+def score_windows(n: int, seed: int):
+    """(positions, window): self only, everything, a grid with many |delta| = w pairs, more than a tile, duplicate
+    positions (two windows), ragged spacing -- the seven cases of the LD-score and neighbour-list tests."""
+    rng = np.random.default_rng(seed)
+    grid = 1 + 100 * np.arange(n, dtype=np.int64)
+    dup = np.sort(rng.integers(1, max(2, n // 3), size=n)).astype(np.int64)
+    ragged = np.cumsum(rng.integers(0, 40, size=n)).astype(np.int64) + 7
+    return [(grid, 0), (grid, int(grid[-1])), (grid, 300), (grid, 100 * 129), (dup, 0), (dup, 2), (ragged, 150)]
+
+
+def neighbour_windows(n: int):
+    """(positions, window) of the neighbour-list comparisons: everything, 129 SNPs each side (more than one 128-column
+    tile), and ragged spacing with about 200 SNPs each side."""
+    grid = 1 + 100 * np.arange(n, dtype=np.int64)
+    ragged = np.cumsum(np.random.default_rng(n).integers(0, 40, size=n)).astype(np.int64) + 7
+    return [(grid, int(grid[-1])), (grid, 100 * 129), (ragged, 4000)]
+
+
+def clump_positions(n: int) -> np.ndarray:
+    return np.cumsum(np.random.default_rng(2).integers(0, 300, size=n)).astype(np.int64) + 1
+
+
+def clump_pvalues(n: int) -> np.ndarray:
+    """p-values with NaNs and ties."""
+    rng = np.random.default_rng(7)
+    pv = 10.0 ** -rng.uniform(0, 9, size=n)
+    pv[rng.random(n) < 0.05] = np.nan
+    pv[rng.random(n) < 0.1] = 3e-4
+    pv[::97] = 1e-5
+    return pv
+
+
+CLUMP_PANEL = dict(n_snps=1500, n_hap=2008, seed=19, miss=0.005, mono=0.03)
+# panel -> ([(p1, p2, r2, window)] for clumping, [(r2, window)] for pruning); 0.3 is ambiguous on lr1000 (2 pairs): not used
+CLUMP_CASES = {
+    "clump1500": ([(1e-4, 1e-2, 0.5, 250_000), (1e-3, 1e-3, 0.2, 20_000), (0.5, 1.0, 0.1, 5_000), (1e-6, 0.05, 0.8, 0)],
+                  [(0.2, 250_000), (0.5, 3_000), (0.1, 10_000)]),
+    "lr1000": ([(1e-3, 0.05, 0.2, 250_000), (0.5, 1.0, 0.5, 20_000), (1e-4, 1e-2, 0.2, 20_000)],
+               [(0.2, 250_000), (0.5, 20_000)]),
+}
+
+
+def clump_panel(name: str):
+    """(codes, Exact) of a clump / prune panel."""
+    if name == "clump1500":
+        if name not in _PANELS:
+            from ld_tools_amd import synth
+            codes = synth.synth_codes_host(**CLUMP_PANEL)
+            codes.setflags(write=False)
+            _PANELS[name] = (codes, [], Exact(codes))
+        return _PANELS[name][0], _PANELS[name][2]
+    codes, _, ex = long_range_panel(name)
+    return codes, ex
+
+
+# ---- small panels for the r32 cells: every haplotype count at which a kernel changes its tail handling ----------------
+EDGE_HAPS = (1, 2, 3, 37, 63, 64, 65, 257, 333, 1008, 5008, 10239, 10240)
+EDGE_SNPS = (1, 2, 127, 128, 129, 1000)
+
+
+def target_counts(h: int):
+    """(n, n11, a1, r1, a2, r2) of pairs near cancellation at h haplotypes: n n11 = a1 a2 exactly and one count either
+    side of it, without and with missing codes."""
+    out = []
+    if h % 4 == 0 and h >= 8:                    # a = r = h / 2: num = h (n11 - h / 4); at 10 240 both products are 5120^2 > 2^24
+        out += [(h, h // 4 + d, h // 2, h // 2, h // 2, h // 2) for d in (-1, 0, 1)]
+    if h % 3 == 0 and h >= 12:                   # a1 = h / 3, a2 = 3 k: n11 = k cancels (10 239 = 3 * 3413: 10 239 * 2000 > 2^24)
+        k = (h // 5) // 3 * 3 + 3
+        k = 6000 if h == 10239 else k
+        out += [(h, k // 3 + d, h // 3, h - h // 3, k, h - k) for d in (0, 1)]
+    if h >= 64:                                  # missing codes in both rows: a + r < n
+        a1, r1, a2, r2 = h // 3, h // 3, h // 2, h // 4
+        out += [(h, (a1 * a2) // h + d, a1, r1, a2, r2) for d in (0, 1)]
+    return out
+
+
+def edge_panel(n_snps: int, n_hap: int) -> np.ndarray:
+    """A generated panel with missing codes (in half of the rows) and monomorphic rows, plus -- as far as the rows last --
+    singleton rows and the count-targeted pairs of target_counts."""
+    from conftest import realise   # the fixtures' construction of two rows from six counts
+    from ld_tools_amd import synth
+    h = n_hap
+    codes = synth.synth_codes_host(n_snps, h, seed=n_snps + h, miss=0.01, miss_rows=0.5, mono=0.05)
+    special = []
+    if h >= 2:
+        one_alt = np.zeros(h, dtype=np.int8)
+        one_alt[0] = 1                           # a = 1
+        one_ref = np.ones(h, dtype=np.int8)
+        one_ref[h - 1] = 0                       # a = n - 1
+        special += [one_alt, one_ref]
+    if h >= 3:
+        lone_ref = np.full(h, 2, dtype=np.int8)  # r = 1, the rest ALT or missing
+        lone_ref[0] = 0
+        lone_ref[1:1 + (h - 1) // 2] = 1
+        both_one = np.full(h, 2, dtype=np.int8)  # a = r = 1, the rest missing
+        both_one[0], both_one[h - 1] = 1, 0
+        special += [lone_ref, both_one]
+    for cnt in target_counts(h):
+        g1, g2 = realise(*cnt)
+        special += [np.asarray(g1, dtype=np.int8), np.asarray(g2, dtype=np.int8)]
+    if n_snps >= 3 and special:
+        stride = max(1, (n_snps - 2) // len(special))
+        for k, row in enumerate(special):
+            if 1 + k * stride < n_snps:
+                codes[1 + k * stride] = row
+    return codes
