@@ -350,6 +350,42 @@ int ldx_ld_score_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt
                      const uint8_t *annot, uint32_t n_annot, int path,
                      uint64_t *sums, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- LD decay: sums of r^2 and pair counts per distance bin (the LD decay curve) on the matrix-pipe band ---- */
+/* A pair is every unordered i > j with
+ *     d = pos_i - pos_j <= window        (positions are non-decreasing, so d >= 0; duplicate positions give d = 0; i = j is
+ *                                         not a pair),
+ *     both SNPs non-degenerate (a r > 0), and -- if keep != NULL -- keep[i] and keep[j] both non-zero.
+ * For each pair, with c_ij the signed r cell of ldx_triangle_ex_dev(LDX_OUT_R32), bit for bit:
+ *     term = rint(2^32 * (c_ij *f32 c_ij))    the term ldx_ld_score_dev sums
+ *     b    = floor(d / bin_width)             EXACTLY (integer arithmetic on d: a pair at d = k bin_width lies in bin k,
+ *                                             one at d = k bin_width - 1 in bin k - 1)
+ *     sums[b] += term,  counts[b] += 1
+ * so sums[b] / 2^32 / counts[b] is the mean r^2 of the pairs whose distance lies in [b bin_width, (b + 1) bin_width).  The
+ * sums are 64-bit integer atomics: the result does not depend on the order of the work, it is bit-reproducible run to run,
+ * identical on both paths and equal to a host histogram of the terms of the r32 triangle.  Two identities follow: the
+ * counts add up to the number of in-window pairs of kept non-degenerate SNPs, and with keep = NULL
+ *     2 * (sum over b of sums[b]) + (sum over i of term(c_ii)) = sum over i of ldx_ld_score_dev's sums[i][0]
+ * on the same window (a degenerate SNP adds 0 on both sides).
+ *   positions: int64 [n_snps], NON-DECREASING; window >= 0 in their units (values above 2^52 act as 2^52);
+ *   bin_width >= 1 in the same units (else LDX_E_ARG); a width above the window gives the single bin 0;
+ *   n_bins: must equal min(window, 2^52) / bin_width + 1 and be <= LDX_DECAY_MAX_BINS (else LDX_E_ARG);
+ *   keep: uint8 [n_snps] or NULL (every SNP kept);
+ *   sums, counts: uint64 [n_bins] each, written by the call (no need to zero them);
+ *   acnt / rcnt from ldx_pack_codes_dev, fa / fr from ldx_snp_stats_dev;
+ *   path: LDX_PATH_AUTO / LDX_PATH_FP4 = the FP4 band, LDX_PATH_MFMA = the int8 band (identical outputs), LDX_PATH_POPCOUNT =
+ *         LDX_E_UNSUPPORTED; n_hap > LDX_MAX_HAPS and a bit plane of 4 GiB or more = LDX_E_UNSUPPORTED.
+ * workspace: ldx_ld_decay_workspace_bytes() bytes, 256-byte aligned, no initialisation needed (the score band's layout; its
+ * leading bytes hold the effective keep mask, kept AND non-degenerate): one per launch that may be in flight, as for
+ * ldx_ld_score_dev.  The call only enqueues work on `stream`: no allocation, no synchronisation, no state in the library.
+ * D' is not offered: the band's r32 family carries no D', and an unrounded D' would need a contract of its own. */
+#define LDX_DECAY_MAX_BINS 1024u
+size_t ldx_ld_decay_workspace_bytes(uint32_t n_snps, uint32_t n_hap);
+int ldx_ld_decay_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
+                     uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, int64_t bin_width,
+                     const uint8_t *keep, int path,
+                     uint64_t *sums, uint64_t *counts, uint32_t n_bins,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- banded LD matrix-vector products: R_w X and (R_w o R_w) X without the matrix, on the matrix-pipe band ---- */
 /* For every SNP i and right-hand side k < n_rhs (1 <= n_rhs <= 8), power in {1, 2}:
  *     c_ij = the signed r cell of ldx_triangle_ex_dev(LDX_OUT_R32) for the pair, bit for bit; c_ii = (n - a_i) / r_i, the

@@ -32,6 +32,7 @@ def cell_offset(r8, c, fmt="k16"):
 
 
 MAX_HAPS = 10240
+DECAY_MAX_BINS = 1024                    # LDX_DECAY_MAX_BINS
 FLAG_DPRIME_INT0 = 1
 FLAG_RSQ_INT0 = 2
 MEASURES = {"r_square": 0, "d_prime": 1}
@@ -135,6 +136,8 @@ SIGNATURES = {
     "ldx_area_band_passes_offset": (_sz, [_u32]),
     "ldx_ld_score_workspace_bytes": (_sz, [_u32, _u32]),
     "ldx_ld_score_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _i64, _vp, _u32, _int, _vp, _vp, _sz, _vp]),
+    "ldx_ld_decay_workspace_bytes": (_sz, [_u32, _u32]),
+    "ldx_ld_decay_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _i64, _i64, _vp, _int, _vp, _vp, _u32, _vp, _sz, _vp]),
     "ldx_ld_matvec_workspace_bytes": (_sz, [_u32, _u32]),
     "ldx_ld_matvec_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _i64, _vp, _u32, _int, _int, _vp, _vp, _sz, _vp]),
     "ldx_ld_neighbors_workspace_bytes": (_sz, [_u32, _u32]),

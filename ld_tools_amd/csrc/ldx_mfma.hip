@@ -350,8 +350,10 @@ __device__ __forceinline__ uint64_t dpp_half_sum(uint64_t x)
 // kProdW (with kArea): the matrix-vector band (ldx_ld_matvec_dev) -- the LD-score band with prod_epilogue, score_epilogue's
 // weighted sibling: float32 weights per SNP instead of mask bits, the cell or its square instead of the square; kProdW is
 // the number of right-hand sides one sweep of the accumulators covers.
+// kDecay (with kArea): the LD-decay band (ldx_ld_decay_dev) -- the band's passes and K loop with decay_epilogue, which adds
+// every pair's score term and a count to the bin of its distance in a per-workgroup LDS histogram, flushed once at the end.
 template <bool kRaw, bool kN11, bool kArea = false, bool kFp4 = false, typename Cell = ldx_ld32, int kScoreW = 0,
-          bool kNbr = false, int kProdW = 0>
+          bool kNbr = false, int kProdW = 0, bool kDecay = false>
 __global__ void __launch_bounds__(kMfmaThreads, kArea ? 2 : kWgPerCu)
 triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ fa, const double *__restrict__ fr,
                      const double *__restrict__ q, uint32_t n_snps, uint32_t n_slabs, uint32_t nchunks, double n,
@@ -432,7 +434,8 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
     static_assert(!kNbr || (kArea && !kScore), "the neighbour epilogue runs on the band");
     constexpr bool kProd = kProdW != 0;     // matrix-vector products (prod_epilogue): the score band with float32 weights
     static_assert(!kProd || (kArea && !kScore && !kNbr), "the matrix-vector epilogue runs on the band");
-    constexpr bool kBandF32 = kFp4 && kArea && !kScore && !kNbr && !kProd;   // the band screens its steps in float32 first (area_epilogue)
+    static_assert(!kDecay || (kArea && !kScore && !kNbr && !kProd), "the decay epilogue runs on the band");
+    constexpr bool kBandF32 = kFp4 && kArea && !kScore && !kNbr && !kProd && !kDecay;   // the band screens its steps in float32 first (area_epilogue)
     float *ctab32 = reinterpret_cast<float *>(tickets + 8);                 // [128][4]: F32Col
     float *rtab32 = ctab32 + kSlab * 4u + wave * (kRows64 * 4u);            // [64][4]: F32Row, private to the wave
     uint32_t *qid = reinterpret_cast<uint32_t *>(ctab32 + kSlab * 4u + kMfmaWaves * kRows64 * 4u) + wave * kQueueCap;   // [kQueueCap]
@@ -445,6 +448,11 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
     // matrix-vector band: the waves' row-sum tables [4][64][8] uint64 take the place of the tables above, and behind them
     // lie the waves' row weights [64][8] float32 (written per pass beside rstat)
     auto prod_rows = [&](uint32_t w) { return ctab32 + kMfmaWaves * kRows64 * 16u + w * (kRows64 * 8u); };
+    // decay band: the workgroup's histogram takes their place -- [n_bins] uint64 sums of terms, then [n_bins] uint64 pair
+    // counts (64-bit: no launch can wrap them).  Nothing else of this instantiation touches the region, so it lives from
+    // the zeroing below to the flush behind the ticket loop.
+    uint64_t *const decay_sum = reinterpret_cast<uint64_t *>(ctab32);
+    uint64_t *const decay_cnt = decay_sum + (kDecay ? (uint32_t)aa.measure : 0u);   // aa.measure: n_bins
     const F32Const fc32 = aa.f32;   // computed on the host (f32_const): kernel arguments live in scalar registers
     // The band (ld_area) hands its passes out PER XCD: the pass list -- j-tile-major, i.e. sorted by position -- is cut into
     // eight contiguous ranges, one per XCD, each with its own counter (sched[2 + 32 x]: the K-loop-token words, which the
@@ -482,6 +490,8 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
         ktok = sched + 2u + ((((xcc & 7u) * 8u + ((hw >> 13) & 7u)) * 2u + ((hw >> 12) & 1u)) * 16u + ((hw >> 8) & 15u));
     }
     uint32_t parity = 0;
+    if constexpr (kDecay)   // (the barrier at the top of the ticket loop orders it before the first epilogue)
+        for (uint32_t b = tid; b < 2u * (uint32_t)aa.measure; b += kMfmaThreads) decay_sum[b] = 0u;
     if (tid == 0) tickets[0] = kArea ? draw() : blockIdx.x;
 
     uint64_t hit_slot = 0, hit_slot_end = 0;   // area: this wave's unfilled part of its current batch of hit slots
@@ -699,7 +709,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             }
             bool rows_ordinary = false;
             typedef double d2s __attribute__((ext_vector_type(2)));
-            if constexpr (kScore || kNbr || kProd) {   // LD scores / neighbours / products: {a, 1 / sqrt(a r)} (r32_snp) and {position, annotation mask}
+            if constexpr (kScore || kNbr || kProd || kDecay) {   // LD scores / neighbours / products / decay: {a, 1 / sqrt(a r)} (r32_snp) and {position, annotation mask}
                 if (new_tile && tid < kSlab) {
                     const uint32_t j = t * kSlab + tid;
                     const R32Snp c = r32_snp(fa[j], fr[j], n);
@@ -1668,7 +1678,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
               }
             };
             auto area_epilogue = [&]() {
-              if constexpr (kArea && MM == 2 && !kScore && !kNbr && !kProd) {
+              if constexpr (kArea && MM == 2 && !kScore && !kNbr && !kProd && !kDecay) {
                 uint64_t slot = hit_slot, slot_end = hit_slot_end;
                 const double kthr = aa.k_thres;
                 const bool prefilter = aa.k_thres > 2.0;
@@ -1962,6 +1972,93 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 hit_slot_end = slot_end;
               }
             };
+            // ---- LD decay (ldx_ld_decay_dev): a histogram keyed by distance where score_epilogue reduces per SNP ----
+            // score_epilogue's sweep -- one pinned read per accumulator, rstat / cstat for {a, rs} and {position, mask}, the
+            // pair (i, j), i > j, with d = pos_i - pos_j <= w -- but the mask is the call's effective keep mask (kept AND not
+            // degenerate: decay_init_kernel), both SNPs must carry it, and the pair's term and a count of 1 go to bin
+            // floor(d / bin_width) of the workgroup's LDS histogram.  The bin is exact: q = (uint32)(d * (1 / width)) is within 1
+            // of the quotient (q < 1024, so the two roundings move d / width by < 2^-42), and the remainder d - q width -- an
+            // integer below 2^53 in magnitude, so the fma is exact -- corrects it.
+            // Accumulation: every lane with a pair issues its own LDS atomic pair (ds_add_u64 on the sum and on the count).
+            // Adjacent lanes hold adjacent columns of one row, so lanes of a half often share a bin and their atomics
+            // serialise on one address.  The alternative -- per column tile a ballot against the bin of the half's first
+            // active lane, and for a half that agrees a dpp_half_sum and ONE atomic pair from lane 31 / 63 -- is kept under
+            // -DLDX_AB_DECAY_UNIFORM: it adds the same integers but lost the A/B on the MI355X (100 000 x 5008, SNPs 500
+            // apart, +-250 kb: 0.33 ms per call against 0.23 ms): the ballots, lane reads and the DPP
+            // chain run for every column tile and cost more than the serialised atomics save.
+            auto decay_epilogue = [&]() {
+              if constexpr (kDecay && MM == 2) {
+                const double win = aa.flank, bw = aa.k_thres, rbw = 1.0 / bw;   // the window and the bin width (integer-valued)
+                const uint32_t last_bin = (uint32_t)aa.measure - 1u;
+                uint32_t ln = lane;   // (lane-derived values recomputed from an opaque copy of the lane id: see epilogue_f32)
+                asm volatile("" : "+v"(ln));
+                const uint32_t l32e = ln & 31u, halfe = ln >> 5;
+                double ca[4], cs[4], cpos[4];   // this lane's four columns
+                bool ckeep[4];
+#pragma unroll
+                for (int tt = 0; tt < 4; ++tt) {
+                    const d2s c0 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32e) * kStat);
+                    const d2s c1 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32e) * kStat + 2u);
+                    ca[tt] = c0.x;
+                    cs[tt] = c0.y;
+                    cpos[tt] = c1.x;
+                    ckeep[tt] = c1.y != 0.0;
+                }
+                const uint32_t j0 = t * kSlab + l32e;   // column of tile tt: j0 + 32 tt
+#pragma unroll 1
+                for (int e = 0; e < 16; ++e) {
+#pragma unroll
+                    for (int m = 0; m < 2; ++m) {
+                        accel_t c4[4];   // ONE register-indexed read per accumulator, pinned (see area_epilogue)
+#pragma unroll
+                        for (int tt = 0; tt < 4; ++tt) {
+                            c4[tt] = acc[m][tt][e];
+                            asm volatile("" : "+v"(c4[tt]));
+                        }
+                        const uint32_t ri = 32u * m + (uint32_t)(e & 3) + 8u * (uint32_t)(e >> 2) + 4u * halfe;
+                        const d2s r0 = *reinterpret_cast<const d2s *>(rstat + ri * kStat);   // two addresses per wave: broadcast
+                        const d2s r1 = *reinterpret_cast<const d2s *>(rstat + ri * kStat + 2u);
+                        const uint32_t i = row0 + ri;
+                        const bool rkeep = i < n_snps && r1.y != 0.0;
+#pragma unroll
+                        for (int tt = 0; tt < 4; ++tt) {
+                            const double cnt = kFp4 ? (double)c4[tt] : (double)((uint32_t)c4[tt] >> 3);   // int8: 8 n11
+                            uint64_t term = score_term(r32_cell(cnt, n, r0.x, r0.y, ca[tt], cs[tt]).r);
+                            const double d = r1.x - cpos[tt];
+                            const bool ok = rkeep && ckeep[tt] && i > j0 + 32u * tt && d <= win;
+                            const unsigned long long okm = __ballot(ok);
+                            if (!okm) continue;   // wave-uniform
+                            term = ok ? term : 0u;
+                            const double dd = ok ? d : 0.0;   // (0 <= dd <= w: the quotient is below n_bins)
+                            uint32_t b = (uint32_t)(dd * rbw);
+                            const double rem = __builtin_fma(-(double)b, bw, dd);
+                            b = rem < 0.0 ? b - 1u : (rem >= bw ? b + 1u : b);
+                            b = b < last_bin ? b : last_bin;   // (never taken: keeps every LDS address inside the histogram)
+#ifdef LDX_AB_DECAY_UNIFORM   // tuning: the wave-uniform form (see above); the product issues per-lane atomics
+                            const uint32_t ok_lo = (uint32_t)okm, ok_hi = (uint32_t)(okm >> 32);
+                            const uint32_t ref_lo = (uint32_t)__builtin_amdgcn_readlane((int)b, ok_lo ? __builtin_ctz(ok_lo) : 0);
+                            const uint32_t ref_hi = (uint32_t)__builtin_amdgcn_readlane((int)b, ok_hi ? 32 + __builtin_ctz(ok_hi) : 32);
+                            const uint32_t ref = halfe ? ref_hi : ref_lo, mine = halfe ? ok_hi : ok_lo;
+                            const unsigned long long dis = __ballot(ok && b != ref);
+                            const bool agree = (halfe ? (uint32_t)(dis >> 32) : (uint32_t)dis) == 0u;   // uniform per half
+                            const uint64_t hsum = dpp_half_sum(term);   // (every lane takes part: DPP reads its neighbours)
+                            if (agree ? (l32e == 31u && mine != 0u) : ok) {
+                                const uint32_t bin = agree ? ref : b;
+                                atomicAdd(reinterpret_cast<unsigned long long *>(decay_sum) + bin, (unsigned long long)(agree ? hsum : term));
+                                atomicAdd(reinterpret_cast<unsigned long long *>(decay_cnt) + bin,
+                                          (unsigned long long)(agree ? (uint32_t)__builtin_popcount(mine) : 1u));
+                            }
+#else
+                            if (ok) {
+                                atomicAdd(reinterpret_cast<unsigned long long *>(decay_sum) + b, (unsigned long long)term);
+                                atomicAdd(reinterpret_cast<unsigned long long *>(decay_cnt) + b, 1ull);
+                            }
+#endif
+                        }
+                    }
+                }
+              }
+            };
             if constexpr (kScore || kProd) {
                 // words per SNP -- score: column 0 and K categories; products: the right-hand sides (bit 4 of measure: power 2)
                 const uint32_t st = kProd ? (uint32_t)aa.measure & 15u : 1u + (uint32_t)aa.measure;
@@ -1986,6 +2083,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             }
             if constexpr (kArea) {
                 if constexpr (kNbr) nbr_epilogue();
+                else if constexpr (kDecay) decay_epilogue();
                 else area_epilogue();
                 if (tid == 0) tickets[parity] = next_ticket;
                 if (!(ablate & 16)) __builtin_amdgcn_s_setprio(0);
@@ -2048,6 +2146,17 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             if (short_pass) pass_body(std::integral_constant<int, 1>{});
             else pass_body(std::integral_constant<int, 2>{});
 #endif
+        }
+    }
+    if constexpr (kDecay) {   // the loop's last barrier is behind every wave's last epilogue: the histogram is complete
+        unsigned long long *const gsum = reinterpret_cast<unsigned long long *>(aa.hits);
+        unsigned long long *const gcnt = reinterpret_cast<unsigned long long *>(aa.counts);
+        for (uint32_t b = tid; b < (uint32_t)aa.measure; b += kMfmaThreads) {
+            const uint64_t c = decay_cnt[b];
+            if (c != 0u) {
+                atomicAdd(gsum + b, (unsigned long long)decay_sum[b]);
+                atomicAdd(gcnt + b, (unsigned long long)c);
+            }
         }
     }
     if (kArea)   // the unused slots of this wave's last batch
@@ -2517,6 +2626,103 @@ int score_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, cons
                    : launch_score<false, 1>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
 }
 
+// ---- LD decay on the band (ldx_ld_decay_dev) ---------------------------------------------------------------------------
+// Zeroes the two outputs -- the call needs no memset of them --, writes the effective keep mask the epilogue reads (kept
+// AND not degenerate, a r > 0) and the two-row query list {0, n - 1} of the plan kernel, as score_init_kernel.
+__global__ void decay_init_kernel(const uint32_t *__restrict__ acnt, const uint32_t *__restrict__ rcnt,
+                                  const uint8_t *__restrict__ keep, uint32_t n_snps, uint8_t *__restrict__ mask,
+                                  uint64_t *__restrict__ sums, uint64_t *__restrict__ counts, uint32_t n_bins,
+                                  uint32_t *__restrict__ qrows)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) {
+        qrows[0] = 0u;
+        qrows[1] = n_snps - 1u;
+    }
+    if (i < n_bins) {
+        sums[i] = 0u;
+        counts[i] = 0u;
+    }
+    if (i < n_snps) mask[i] = (!keep || keep[i] != 0) && acnt[i] != 0u && rcnt[i] != 0u;
+}
+
+// the score band's workspace: its leading n_snps bytes (the band's query mask, which the score band leaves unused) hold the
+// effective keep mask
+size_t decay_mfma_workspace_bytes(uint32_t n_snps) { return score_mfma_workspace_bytes(n_snps); }
+
+template <bool kFp4>
+static int launch_decay(const void *alt, const double *fa, const double *fr, uint32_t n_snps, uint32_t n_hap, uint32_t T,
+                        uint32_t nch, uint64_t units, size_t lds, const AreaArgs &aa, uint32_t *sched, hipStream_t s)
+{
+    static std::atomic<uint64_t> opted{0};   // the dynamic LDS opt-in: once per device (70 KiB)
+    int dev = 0;
+    LDX_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !((opted.load(std::memory_order_relaxed) >> dev) & 1u)) {
+        LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, false, 0, true>,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (dev >= 0 && dev < 64) opted.fetch_or(1ull << dev, std::memory_order_relaxed);
+    }
+    triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, false, 0, true><<<(uint32_t)device_cus() * 2u, kMfmaThreads, lds, s>>>(
+        (const uint4 *)alt, fa, fr, nullptr, n_snps, T, nch, (double)n_hap, 1.0 / (double)n_hap, 0, units * 8u,
+        (ldx_ld32 *)nullptr, nullptr, nullptr, 0u, 0u, 0u, sched, 0, nullptr, aa);
+    LDX_HIP(hipGetLastError());
+    return LDX_OK;
+}
+
+int decay_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
+               uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, int64_t bin_width,
+               const uint8_t *keep, bool fp4, uint64_t *sums, uint64_t *counts, uint32_t n_bins, void *workspace, hipStream_t s)
+{
+    const uint32_t T = n_slabs(n_snps), nch = n_chunks(n_hap);
+    if ((uint64_t)T * nch * kSlab * 16u >= (1ull << 32)) {   // the K loop addresses the plane with 32-bit lane offsets
+        set_error("ldx_ld_decay_dev: a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", n_snps, n_hap);
+        return LDX_E_UNSUPPORTED;
+    }
+    // the band's buffers, carved as in score_mfma; the query mask's bytes hold the effective keep mask
+    uint8_t *mask = (uint8_t *)workspace;
+    char *w = (char *)workspace + ((size_t)n_snps + 255u) / 256u * 256u;
+    uint32_t *pass_base = (uint32_t *)w;
+    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
+    uint32_t *g_end = (uint32_t *)w;
+    w += ((size_t)T * 4u + 255u) / 256u * 256u;
+    uint32_t *g_begin = (uint32_t *)w;
+    w += ((size_t)T * 4u + 255u) / 256u * 256u;
+    uint32_t *first_base = (uint32_t *)w;
+    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
+    uint32_t *order = area_order_entries(n_snps) ? (uint32_t *)w : nullptr;
+    w += (area_order_entries(n_snps) * 4u + 255u) / 256u * 256u;
+    uint32_t *sched = (uint32_t *)w;
+    w += kAreaSchedWords * 4u;
+    uint32_t *qrows = (uint32_t *)w;                               // [2]
+    unsigned long long *n_hits = (unsigned long long *)(w + 8);   // the plan kernel zeroes it; nothing reads it
+    const uint32_t n_init = n_snps > n_bins ? n_snps : n_bins;
+    decay_init_kernel<<<(n_init + 255u) / 256u, 256, 0, s>>>(acnt, rcnt, keep, n_snps, mask, sums, counts, n_bins, qrows);
+    LDX_HIP(hipGetLastError());
+    if (n_snps < 2) return LDX_OK;   // no pairs
+    // the score band's plan: every SNP a query, flank = window; decay_epilogue applies the exact bound per pair
+    area_band_plan_kernel<<<1, 1024, 0, s>>>(positions, n_snps, T, window, qrows, 2u, g_begin, g_end, pass_base, n_hits,
+                                             order, first_base, sched);
+    LDX_HIP(hipGetLastError());
+    AreaArgs aa{};
+    aa.f32 = f32_const((double)n_hap);
+    aa.pos = positions;
+    aa.is_query = mask;                        // decay: the effective keep mask
+    aa.pass_base = pass_base;
+    aa.g_begin = g_begin;
+    aa.g_end = g_end;
+    aa.order = order;
+    aa.hits = (ldx_hit *)sums;                 // decay: the uint64 sums [n_bins]
+    aa.counts = (uint32_t *)counts;            // decay: the uint64 counts [n_bins]
+    aa.n_hits = n_hits;
+    aa.flank = (double)window;
+    aa.k_thres = (double)bin_width;            // decay: the bin width (<= 2^52 + 1: exact)
+    aa.measure = (int)n_bins;
+    const uint64_t units = ldx_triangle_units(n_snps) / 8u;   // 64-row units of the full triangle
+    const size_t lds = mfma_lds_bytes(kRows64, false, false) + (size_t)n_bins * 2u * sizeof(uint64_t);   // + the histogram
+    return fp4 ? launch_decay<true>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s)
+               : launch_decay<false>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
+}
+
 // ---- matrix-vector products on the band (ldx_ld_matvec_dev) ------------------------------------------------------------
 // Every SNP's own term (r32_diag or its float32 square, times its weights) WRITES its words -- the call needs no memset of
 // `sums` -- and the two-row query list {0, n - 1} the plan kernel reads, as score_init_kernel.
@@ -2768,6 +2974,40 @@ extern "C" int ldx_ld_matvec_dev(const void *alt, const uint32_t *acnt, const ui
     const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles: keep pos + window exact
     return ldx::prod_mfma(alt, acnt, rcnt, fa, fr, n_snps, n_hap, positions, window < wmax ? window : wmax, x, n_rhs, power == 2,
                           path != LDX_PATH_MFMA, sums, workspace, (hipStream_t)stream);
+}
+
+extern "C" size_t ldx_ld_decay_workspace_bytes(uint32_t n_snps, uint32_t n_hap)
+{
+    (void)n_hap;   // (the layout depends on the SNP count alone)
+    return ldx::decay_mfma_workspace_bytes(n_snps ? n_snps : 1u);
+}
+
+extern "C" int ldx_ld_decay_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
+                                uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, int64_t bin_width,
+                                const uint8_t *keep, int path, uint64_t *sums, uint64_t *counts, uint32_t n_bins,
+                                void *workspace, size_t workspace_bytes, void *stream)
+{
+    LDX_REQUIRE(alt && acnt && rcnt && fa && fr && positions && sums && counts && workspace, "null pointer");
+    LDX_REQUIRE(n_snps >= 1 && n_hap >= 1 && window >= 0, "bad shape");
+    LDX_REQUIRE(bin_width >= 1, "bin_width must be >= 1");
+    const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles: keep pos + window exact
+    const int64_t w = window < wmax ? window : wmax;
+    LDX_REQUIRE(n_bins <= LDX_DECAY_MAX_BINS, "more than LDX_DECAY_MAX_BINS bins");
+    LDX_REQUIRE((int64_t)n_bins == w / bin_width + 1, "n_bins must be min(window, 2^52) / bin_width + 1");
+    LDX_REQUIRE(((uintptr_t)workspace & 255u) == 0, "workspace must be 256-byte aligned");
+    LDX_REQUIRE(workspace_bytes >= ldx::decay_mfma_workspace_bytes(n_snps), "workspace too small (see ldx_ld_decay_workspace_bytes)");
+    LDX_REQUIRE(path == LDX_PATH_AUTO || path == LDX_PATH_POPCOUNT || path == LDX_PATH_MFMA || path == LDX_PATH_FP4, "unknown path");
+    if (n_hap > LDX_MAX_HAPS) {
+        ldx::set_error("ldx_ld_decay_dev: n_hap %u > LDX_MAX_HAPS %u", n_hap, LDX_MAX_HAPS);
+        return LDX_E_UNSUPPORTED;
+    }
+    if (path == LDX_PATH_POPCOUNT) {
+        ldx::set_error("ldx_ld_decay_dev: LD decay runs on the matrix-pipe band (LDX_PATH_FP4 / LDX_PATH_MFMA), not on the popcount kernels");
+        return LDX_E_UNSUPPORTED;
+    }
+    // a width above the window puts every pair into bin 0, so any such width acts as 2^52 + 1 (exact in a double)
+    return ldx::decay_mfma(alt, acnt, rcnt, fa, fr, n_snps, n_hap, positions, w, bin_width <= wmax ? bin_width : wmax + 1, keep,
+                           path != LDX_PATH_MFMA, sums, counts, n_bins, workspace, (hipStream_t)stream);
 }
 
 extern "C" size_t ldx_ld_score_workspace_bytes(uint32_t n_snps, uint32_t n_hap)

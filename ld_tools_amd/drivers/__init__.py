@@ -10,6 +10,7 @@ as the VCF source; pysam itself is only imported by the command-line shells.
 """
 from .area import AreaQueryResult, area_scan, get_inld_vars, write_area_file  # noqa: F401
 from .clump import ClumpTable, clump, write_clumped  # noqa: F401
+from .decay import write_decay  # noqa: F401
 from .ingest import RaggedGenotypesError, codes_matrix, find_record, sample_genotypes  # noqa: F401
 from .ldscore import LDScoreTable, ld_scores, write_ldscore  # noqa: F401
 from .rmatrix import RMatrix, r_matrix, write_r_matrix  # noqa: F401

@@ -717,6 +717,154 @@ def ld_score(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, win
     return res
 
 
+# --------------------------------------------------------------------------- LD decay
+DECAY_WINDOW_MAX = 1 << 52      # larger windows act as 2^52 (include/ldx.h, ldx_ld_decay_dev)
+
+
+def decay_bins(window: int, bin_width: int) -> int:
+    """Number of bins of ldx_ld_decay_dev: min(window, 2^52) // bin_width + 1."""
+    return min(int(window), DECAY_WINDOW_MAX) // int(bin_width) + 1
+
+
+def decay_host(r, positions, window: int, bin_width: int, keep=None, live=None) -> Tuple[np.ndarray, np.ndarray]:
+    """Host mirror of ldx_ld_decay_dev over an r32 square (TriangleResult.r_matrix()): (sums, counts), uint64 [n_bins] each.
+    Pairs i > j with pos_i - pos_j <= window whose two SNPs are ``live`` (bool [n]: not degenerate; default: every SNP) and
+    kept; the term is score_terms of the cell, the bin floor(d / bin_width) in integers, the sums integer sums."""
+    r = np.asarray(r, dtype=np.float32)
+    n = r.shape[0]
+    pos = np.asarray(positions, dtype=np.int64)
+    window, bin_width = min(int(window), DECAY_WINDOW_MAX), int(bin_width)
+    if bin_width < 1:
+        raise _lib.LdxError("bin_width must be >= 1")
+    n_bins = decay_bins(window, bin_width)
+    ok = np.ones(n, dtype=bool) if live is None else np.asarray(live, dtype=bool).copy()
+    if keep is not None:
+        ok &= np.asarray(keep, dtype=bool)
+    rows, cols = np.tril_indices(n, -1)
+    d = pos[rows] - pos[cols]
+    sel = (d <= window) & ok[rows] & ok[cols]
+    rows, cols, d = rows[sel], cols[sel], d[sel]
+    b = d // bin_width
+    counts = np.bincount(b, minlength=n_bins).astype(np.uint64)
+    sums = np.zeros(n_bins, dtype=np.uint64)
+    np.add.at(sums, b, score_terms(r[rows, cols]))
+    return sums, counts
+
+
+@dataclass
+class LDDecay:
+    """LD decay curve of one panel (ld_decay).  ``sums`` / ``counts_dev`` are the device uint64 tensors [n_bins] the kernel
+    wrote (sums in units of 2^-32 r^2); bin b covers the distances [b bin_width, (b + 1) bin_width), the last bin ends at
+    ``window``.  The host arrays are fetched when first asked for."""
+
+    sums: torch.Tensor
+    counts_dev: torch.Tensor
+    bin_width: int
+    window: int
+    n_hap: int
+    _counts: Optional[np.ndarray] = None
+    _sum_r2: Optional[np.ndarray] = None
+
+    @property
+    def n_bins(self) -> int:
+        return int(self.sums.numel()) if self._counts is None else int(self._counts.size)
+
+    @property
+    def counts(self) -> np.ndarray:
+        """int64 [n_bins]: pairs per bin."""
+        if self._counts is None:
+            self._counts = self.counts_dev.cpu().numpy().astype(np.int64)
+        return self._counts
+
+    @property
+    def sum_r2(self) -> np.ndarray:
+        """float64 [n_bins]: sum of r^2 per bin (sums / 2^32)."""
+        if self._sum_r2 is None:
+            self._sum_r2 = self.sums.cpu().numpy().astype(np.float64) / SCORE_SCALE
+        return self._sum_r2
+
+    @property
+    def mean_r2(self) -> np.ndarray:
+        """float64 [n_bins]: mean r^2 per bin, NaN for an empty bin."""
+        c = self.counts
+        return np.where(c > 0, self.sum_r2 / np.maximum(c, 1), np.nan)
+
+    @property
+    def distance(self) -> np.ndarray:
+        """int64 [n_bins]: the start of every bin."""
+        return np.arange(self.n_bins, dtype=np.int64) * self.bin_width
+
+    def adjusted(self, n_obs: Optional[int] = None) -> np.ndarray:
+        """LDSC's unbiased estimate of the mean, (n - 1) / (n - 2) mean - 1 / (n - 2), n_obs defaulting to n_hap."""
+        return adjust_l2(self.mean_r2, 1.0, self.n_hap if n_obs is None else int(n_obs))
+
+    def rebin(self, edges) -> Tuple[np.ndarray, np.ndarray]:
+        """Merge the fine bins into coarser ones: (sum_r2, counts) of the distances [edges[k], edges[k + 1]), one entry per
+        consecutive pair of edges.  The edges are strictly increasing multiples of bin_width (an edge beyond the last bin
+        stands for its end); anything else raises."""
+        e = np.asarray(edges)
+        if e.ndim != 1 or e.size < 2 or not np.issubdtype(e.dtype, np.integer):
+            raise _lib.LdxError("rebin needs at least two integer edges")
+        e = e.astype(np.int64)
+        if (e < 0).any() or (np.diff(e) <= 0).any() or (e % self.bin_width != 0).any():
+            raise _lib.LdxError(f"rebin edges must be increasing multiples of the bin width {self.bin_width}")
+        idx = np.minimum(e // self.bin_width, self.n_bins)
+        cs = np.concatenate([[0.0], np.cumsum(self.sum_r2)])
+        cc = np.concatenate([[0], np.cumsum(self.counts)])
+        return cs[idx[1:]] - cs[idx[:-1]], cc[idx[1:]] - cc[idx[:-1]]
+
+
+def ld_decay(panel: PackedPanel, positions=None, window_bp: int = 250_000, window_snps: Optional[int] = None,
+             bin_bp: int = 1000, keep=None, path: Optional[str] = None, workspace: Optional[torch.Tensor] = None,
+             check_positions: bool = True) -> LDDecay:
+    """LD decay on the matrix-pipe band: per distance bin of width ``bin_bp``, the sum of r^2 and the number of pairs i > j
+    with pos_i - pos_j <= window, both SNPs non-degenerate and -- with ``keep`` (bool [n]) -- both kept (include/ldx.h,
+    ldx_ld_decay_dev).  r is the signed r of ld_triangle(fmt="r32"), bit for bit; the sums are exact integer sums of
+    rint(2^32 r^2) and the bins exact, so the result is reproducible run to run and identical on both paths.
+
+    ``window_snps`` counts the window, the distances and ``bin_bp`` in SNPs (positions 0 .. n-1).  At most DECAY_MAX_BINS
+    bins: coarser curves come from ``LDDecay.rebin``.  ``path``: 'fp4' (default) or 'mfma'.  ``workspace``: a uint8 device
+    tensor of ldx_ld_decay_workspace_bytes() bytes to reuse (one per launch that may be in flight).  The call is
+    stream-ordered: the host reads nothing until ``.counts`` / ``.sum_r2`` are asked for.
+    """
+    require_gpu()
+    n = panel.n_snps
+    pos, _, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_decay")
+    width = int(bin_bp)
+    if width < 1:
+        raise _lib.LdxError("bin_bp must be >= 1")
+    n_bins = decay_bins(window, width)
+    if n_bins > _lib.DECAY_MAX_BINS:
+        least = min(window, DECAY_WINDOW_MAX) // _lib.DECAY_MAX_BINS + 1
+        raise _lib.LdxError(f"{n_bins} bins > DECAY_MAX_BINS {_lib.DECAY_MAX_BINS}: the smallest admissible bin_bp for this "
+                            f"window is {least}")
+    keep_d = None
+    if keep is not None:
+        k = keep.cpu().numpy() if isinstance(keep, torch.Tensor) else np.asarray(keep)
+        if k.shape != (n,) or (k.dtype != bool and not np.isin(k, (0, 1)).all()):
+            raise _lib.LdxError(f"keep must be a boolean array of shape [{n}]")
+        keep_d = torch.as_tensor(np.ascontiguousarray(k.astype(np.uint8))).to(panel.device)
+    pcode = PATHS["fp4"] if path is None else PATHS[path]
+    need = lib.ldx_ld_decay_workspace_bytes(n, panel.n_hap)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=panel.device)
+    elif workspace.numel() * workspace.element_size() < need:
+        raise _lib.LdxError(f"workspace too small: {need} bytes needed")
+    sums = torch.empty(n_bins, dtype=torch.uint64, device=panel.device)
+    counts = torch.empty(n_bins, dtype=torch.uint64, device=panel.device)
+    _decay_launch(panel, pos, window, width, keep_d, pcode, sums, counts, workspace)
+    res = LDDecay(sums, counts, width, window, panel.n_hap)
+    res._keep = (pos, keep_d, workspace)   # alive until the launch is done
+    return res
+
+
+def _decay_launch(panel, pos, window, width, keep_d, pcode, sums, counts, workspace) -> None:
+    check(lib.ldx_ld_decay_dev(panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), panel.fa.data_ptr(),
+                               panel.fr.data_ptr(), panel.n_snps, panel.n_hap, pos.data_ptr(), window, width, _ptr(keep_d),
+                               pcode, sums.data_ptr(), counts.data_ptr(), sums.numel(), workspace.data_ptr(),
+                               workspace.numel() * workspace.element_size(), _stream_ptr()), "ldx_ld_decay_dev")
+
+
 # --------------------------------------------------------------------------- R x without the matrix, ridge solves
 PROD_SCALE_BITS = 40             # sums are integers in units of 2^-40 (include/ldx.h, ldx_ld_matvec_dev)
 PROD_CLAMP = float(1 << 22)      # |v x| beyond it is clamped before scaling (keeps the int64 conversion defined)
