@@ -386,6 +386,42 @@ int ldx_ld_decay_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt
                      uint64_t *sums, uint64_t *counts, uint32_t n_bins,
                      void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- haplotype blocks by the four-gamete test (Hudson & Kaplan 1985) on the matrix-pipe band ---- */
+/* Gametes of SNPs i > j, with A_x the set of haplotypes whose code is 1 (ALT) at SNP x, a_x = |A_x| and n = n_hap:
+ *     g11 = |A_i n A_j|,  g10 = a_i - g11,  g01 = a_j - g11,  g00 = n - a_i - a_j + g11.
+ * "Not ALT" is the other allele: a missing code or a second ALT allele counts with REF.  (The REF plane never enters the
+ * band; callers who want missing codes out of the test drop such SNPs with `keep`.)
+ * The pair is RECOMBINANT iff min(g11, g10, g01, g00) >= min_count, 1 <= min_count <= n_hap (else LDX_E_ARG).  It is
+ * evaluated iff both SNPs are kept (keep: uint8 [n_snps] or NULL = every SNP) and d = pos_i - pos_j <= window (positions
+ * int64, NON-DECREASING; duplicate positions give d = 0; values of window above 2^52 act as 2^52), as in ldx_ld_decay_dev.
+ * A monomorphic SNP is compatible with everything; it is masked out only if `keep` does it.
+ *     left[i] = 1 + max{ j < i : (i, j) recombinant },  0 if there is none          (uint32 [n_snps])
+ * The call writes every word of `left` (no memset by the caller; a relaunch into a used buffer gives the same array).  The
+ * predicate is integer arithmetic on exact counts: no rounding, identical on both paths, equal to a host count over the
+ * allele codes.
+ *   acnt from ldx_pack_codes_dev (the ALT counts; no frequency vector is read);
+ *   path: LDX_PATH_AUTO / LDX_PATH_FP4 = the FP4 band, LDX_PATH_MFMA = the int8 band (identical outputs), LDX_PATH_POPCOUNT =
+ *         LDX_E_UNSUPPORTED; n_hap > LDX_MAX_HAPS and a bit plane of 4 GiB or more = LDX_E_UNSUPPORTED.
+ * workspace: ldx_ld_fgt_workspace_bytes() bytes, 256-byte aligned, no initialisation needed (the score band's layout; its
+ * leading bytes hold the keep mask): one per launch that may be in flight.  The call only enqueues work on `stream`: no
+ * allocation, no synchronisation, no state in the library.
+ *
+ * ldx_ld_blocks_dev: the greedy left-to-right partition of the kept SNPs over `left` (the Hudson-Kaplan partition; not
+ * Haploview's block-picking order).  With s the current block's first SNP, kept SNP i starts a new block iff there is no
+ * current block, or left[i] >= s + 1, or pos_i - pos_s > window -- the window rule keeps "no recombinant pair inside a
+ * block" true, since every pair inside a block was tested.
+ *     block_of[i] (uint32 [n_snps]): the 0-based block of SNP i, 0xFFFFFFFF for a SNP not kept;
+ *     n_out[0]: the number of blocks;  n_out[1]: the block starts caused by the `left` rule (it outranks the window rule) --
+ *               Hudson & Kaplan's lower bound Rm on the number of recombination events, restricted to the window.
+ * One wave walks the SNPs (the scan is sequential in the number of blocks); the result stays on the device, so the two
+ * calls can be captured together.  Gabriel's D' confidence-interval blocks are not offered: the band carries no D'. */
+size_t ldx_ld_fgt_workspace_bytes(uint32_t n_snps, uint32_t n_hap);
+int ldx_ld_fgt_dev(const void *alt, const uint32_t *acnt, uint32_t n_snps, uint32_t n_hap, const int64_t *positions,
+                   int64_t window, uint32_t min_count, const uint8_t *keep, int path,
+                   uint32_t *left, void *workspace, size_t workspace_bytes, void *stream);
+int ldx_ld_blocks_dev(const uint32_t *left, const int64_t *positions, const uint8_t *keep, uint32_t n_snps, int64_t window,
+                      uint32_t *block_of, uint32_t *n_out, void *stream);
+
 /* ---- banded LD matrix-vector products: R_w X and (R_w o R_w) X without the matrix, on the matrix-pipe band ---- */
 /* For every SNP i and right-hand side k < n_rhs (1 <= n_rhs <= 8), power in {1, 2}:
  *     c_ij = the signed r cell of ldx_triangle_ex_dev(LDX_OUT_R32) for the pair, bit for bit; c_ii = (n - a_i) / r_i, the

@@ -138,6 +138,9 @@ SIGNATURES = {
     "ldx_ld_score_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _i64, _vp, _u32, _int, _vp, _vp, _sz, _vp]),
     "ldx_ld_decay_workspace_bytes": (_sz, [_u32, _u32]),
     "ldx_ld_decay_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _i64, _i64, _vp, _int, _vp, _vp, _u32, _vp, _sz, _vp]),
+    "ldx_ld_fgt_workspace_bytes": (_sz, [_u32, _u32]),
+    "ldx_ld_fgt_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _i64, _u32, _vp, _int, _vp, _vp, _sz, _vp]),
+    "ldx_ld_blocks_dev": (_int, [_vp, _vp, _vp, _u32, _i64, _vp, _vp, _vp]),
     "ldx_ld_matvec_workspace_bytes": (_sz, [_u32, _u32]),
     "ldx_ld_matvec_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _i64, _vp, _u32, _int, _int, _vp, _vp, _sz, _vp]),
     "ldx_ld_neighbors_workspace_bytes": (_sz, [_u32, _u32]),

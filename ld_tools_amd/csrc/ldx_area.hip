@@ -790,3 +790,84 @@ extern "C" int ldx_ld_select_dev(const ldx_hit *nbrs, const uint32_t *offsets, u
     LDX_HIP(hipGetLastError());
     return LDX_OK;
 }
+
+// ---- haplotype blocks from the four-gamete test (ldx_ld_blocks_dev): the greedy left-to-right partition ----------------
+// `left` is ldx_ld_fgt_dev's output.  With s the current block's first SNP, kept SNP i starts a new block iff there is no
+// current block, or left[i] >= s + 1 (a recombinant partner inside the block), or pos_i - pos_s > window (the pair (i, s) was
+// never tested).  The scan is sequential in the number of blocks: ONE wave walks the SNPs 64 at a time, a ballot finds the
+// first lane that breaks the current block, the block restarts there and the rest of the chunk is judged again.  Loads run
+// four chunks wide and one group ahead, so the walk pays one memory latency per 256 SNPs.
+namespace ldx {
+
+__global__ void __launch_bounds__(64) blocks_scan_kernel(const uint32_t *__restrict__ left, const int64_t *__restrict__ pos,
+                                                         const uint8_t *__restrict__ keep, uint32_t n_snps, int64_t window,
+                                                         uint32_t *__restrict__ block_of, uint32_t *__restrict__ n_out)
+{
+    constexpr uint32_t kG = 4u;   // chunks per group of loads
+    const uint32_t lane = threadIdx.x;
+    uint32_t lf[kG], nlf[kG];
+    int64_t ps[kG], nps[kG];
+    bool kp[kG], nkp[kG];
+    auto load = [&](uint32_t base) {
+#pragma unroll
+        for (uint32_t c = 0; c < kG; ++c) {
+            const uint64_t i = (uint64_t)base + 64u * c + lane;
+            const bool in = i < n_snps;
+            nlf[c] = in ? left[i] : 0u;
+            nps[c] = in ? pos[i] : 0;
+            nkp[c] = in && (!keep || keep[i] != 0);
+        }
+    };
+    load(0u);
+    bool have = false;          // wave-uniform: a block is open, [s, ...) with pos_s the position of its first SNP
+    uint32_t s = 0u, n_blocks = 0u, n_left = 0u;
+    int64_t pos_s = 0;
+    for (uint64_t base = 0; base < n_snps; base += 64u * kG) {
+#pragma unroll
+        for (uint32_t c = 0; c < kG; ++c) {
+            lf[c] = nlf[c];
+            ps[c] = nps[c];
+            kp[c] = nkp[c];
+        }
+        if (base + 64u * kG < n_snps) load((uint32_t)(base + 64u * kG));
+#pragma unroll
+        for (uint32_t c = 0; c < kG; ++c) {
+            const uint64_t i0 = base + 64u * c;
+            if (i0 >= n_snps) break;   // wave-uniform
+            uint32_t val = 0xFFFFFFFFu, cur = 0u;   // cur: the first lane not yet given to a block
+            for (;;) {
+                const bool mine = kp[c] && lane >= cur;
+                const bool brk = mine && (!have || lf[c] >= s + 1u || ps[c] - pos_s > window);
+                const unsigned long long m = __ballot(brk);
+                const uint32_t f = m ? (uint32_t)__builtin_ctzll(m) : 64u;
+                if (mine && lane < f) val = n_blocks - 1u;   // still the open block
+                if (!m) break;
+                // lane f's words through v_readlane (f is wave-uniform): s and pos_s stay in scalar registers
+                if (have && (uint32_t)__builtin_amdgcn_readlane((int)lf[c], (int)f) >= s + 1u) ++n_left;   // (the left rule outranks the window rule)
+                s = (uint32_t)i0 + f;
+                pos_s = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)((uint64_t)ps[c] >> 32), (int)f) << 32) |
+                                  (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)ps[c], (int)f));
+                have = true;
+                ++n_blocks;
+                cur = f;   // lane f opens the block: it no longer breaks, the lanes behind it are judged against it
+            }
+            if (i0 + lane < n_snps) block_of[i0 + lane] = val;
+        }
+    }
+    if (lane == 0u) {
+        n_out[0] = n_blocks;
+        n_out[1] = n_left;
+    }
+}
+
+}  // namespace ldx
+
+extern "C" int ldx_ld_blocks_dev(const uint32_t *left, const int64_t *positions, const uint8_t *keep, uint32_t n_snps,
+                                 int64_t window, uint32_t *block_of, uint32_t *n_out, void *stream)
+{
+    LDX_REQUIRE(left && positions && block_of && n_out, "null pointer");
+    LDX_REQUIRE(n_snps >= 1 && window >= 0, "bad shape");
+    ldx::blocks_scan_kernel<<<1, 64, 0, (hipStream_t)stream>>>(left, positions, keep, n_snps, window, block_of, n_out);
+    LDX_HIP(hipGetLastError());
+    return LDX_OK;
+}

@@ -352,8 +352,10 @@ __device__ __forceinline__ uint64_t dpp_half_sum(uint64_t x)
 // the number of right-hand sides one sweep of the accumulators covers.
 // kDecay (with kArea): the LD-decay band (ldx_ld_decay_dev) -- the band's passes and K loop with decay_epilogue, which adds
 // every pair's score term and a count to the bin of its distance in a per-workgroup LDS histogram, flushed once at the end.
+// kFgt (with kArea): the four-gamete band (ldx_ld_fgt_dev) -- the band's passes and K loop with fgt_epilogue, an integer
+// predicate on the counts (no r cell) reduced to the highest recombinant column of every row.
 template <bool kRaw, bool kN11, bool kArea = false, bool kFp4 = false, typename Cell = ldx_ld32, int kScoreW = 0,
-          bool kNbr = false, int kProdW = 0, bool kDecay = false>
+          bool kNbr = false, int kProdW = 0, bool kDecay = false, bool kFgt = false>
 __global__ void __launch_bounds__(kMfmaThreads, kArea ? 2 : kWgPerCu)
 triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ fa, const double *__restrict__ fr,
                      const double *__restrict__ q, uint32_t n_snps, uint32_t n_slabs, uint32_t nchunks, double n,
@@ -435,7 +437,8 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
     constexpr bool kProd = kProdW != 0;     // matrix-vector products (prod_epilogue): the score band with float32 weights
     static_assert(!kProd || (kArea && !kScore && !kNbr), "the matrix-vector epilogue runs on the band");
     static_assert(!kDecay || (kArea && !kScore && !kNbr && !kProd), "the decay epilogue runs on the band");
-    constexpr bool kBandF32 = kFp4 && kArea && !kScore && !kNbr && !kProd && !kDecay;   // the band screens its steps in float32 first (area_epilogue)
+    static_assert(!kFgt || (kArea && !kScore && !kNbr && !kProd && !kDecay), "the four-gamete epilogue runs on the band");
+    constexpr bool kBandF32 = kFp4 && kArea && !kScore && !kNbr && !kProd && !kDecay && !kFgt;   // the band screens its steps in float32 first (area_epilogue)
     float *ctab32 = reinterpret_cast<float *>(tickets + 8);                 // [128][4]: F32Col
     float *rtab32 = ctab32 + kSlab * 4u + wave * (kRows64 * 4u);            // [64][4]: F32Row, private to the wave
     uint32_t *qid = reinterpret_cast<uint32_t *>(ctab32 + kSlab * 4u + kMfmaWaves * kRows64 * 4u) + wave * kQueueCap;   // [kQueueCap]
@@ -709,7 +712,18 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             }
             bool rows_ordinary = false;
             typedef double d2s __attribute__((ext_vector_type(2)));
-            if constexpr (kScore || kNbr || kProd || kDecay) {   // LD scores / neighbours / products / decay: {a, 1 / sqrt(a r)} (r32_snp) and {position, annotation mask}
+            if constexpr (kFgt) {   // four-gamete test: {a, -} (aa.counts: the ALT counts) and {position, keep mask}
+                if (new_tile && tid < kSlab) {
+                    const uint32_t j = t * kSlab + tid;
+                    d2s *dst = reinterpret_cast<d2s *>(cstat + tid * kStat);
+                    dst[0] = d2s{j < n_snps ? (double)aa.counts[j] : 0.0, 0.0};
+                    dst[1] = j < n_snps ? d2s{(double)aa.pos[j], (double)aa.is_query[j]} : d2s{0.0, 0.0};
+                }
+                const uint32_t i = row0 + lane;
+                d2s *dst = reinterpret_cast<d2s *>(rstat + lane * kStat);
+                dst[0] = d2s{i < n_snps ? (double)aa.counts[i] : 0.0, 0.0};
+                dst[1] = i < n_snps ? d2s{(double)aa.pos[i], (double)aa.is_query[i]} : d2s{0.0, 0.0};
+            } else if constexpr (kScore || kNbr || kProd || kDecay) {   // LD scores / neighbours / products / decay: {a, 1 / sqrt(a r)} (r32_snp) and {position, annotation mask}
                 if (new_tile && tid < kSlab) {
                     const uint32_t j = t * kSlab + tid;
                     const R32Snp c = r32_snp(fa[j], fr[j], n);
@@ -1678,7 +1692,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
               }
             };
             auto area_epilogue = [&]() {
-              if constexpr (kArea && MM == 2 && !kScore && !kNbr && !kProd && !kDecay) {
+              if constexpr (kArea && MM == 2 && !kScore && !kNbr && !kProd && !kDecay && !kFgt) {
                 uint64_t slot = hit_slot, slot_end = hit_slot_end;
                 const double kthr = aa.k_thres;
                 const bool prefilter = aa.k_thres > 2.0;
@@ -2059,6 +2073,76 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 }
               }
             };
+            // ---- four-gamete test (ldx_ld_fgt_dev): per row, the highest recombinant column ----
+            // decay_epilogue's sweep -- one pinned read per accumulator, rstat / cstat for a and {position, keep mask}, the pair
+            // (i, j), i > j, with d = pos_i - pos_j <= w and both SNPs kept -- with an integer predicate in place of the r cell:
+            // the pair is recombinant iff min(n11, a_i - n11, a_j - n11, n - a_i - a_j + n11) >= min_count (aa.measure).  All four
+            // are counts of haplotypes, so the unsigned differences never wrap.
+            // Reduction: the lanes of a half hold the columns 32 tt + l32 of ONE row (half 0: row ri, half 1: row ri + 4), so the
+            // two 32-bit halves of a ballot are two rows' answers for one column tile and their highest set bits the highest
+            // recombinant columns: two 64-bit words per row (tiles 0-1, 2-3) and one count-leading-zeros, all in scalar
+            // registers.  The result is parked in the lane whose index is the row (each row is visited once per pass), and after the sweep every lane
+            // with a hit issues ONE atomicMax on left[i]: at most one per (row, wave, pass), none per pair.
+            auto fgt_epilogue = [&]() {
+              if constexpr (kFgt && MM == 2) {
+                const double win = aa.flank;
+                const uint32_t mc = (uint32_t)aa.measure, nh = (uint32_t)n;
+                uint32_t ln = lane;   // (lane-derived values recomputed from an opaque copy of the lane id: see epilogue_f32)
+                asm volatile("" : "+v"(ln));
+                const uint32_t l32e = ln & 31u;
+                uint32_t caj[4];   // this lane's four columns
+                double cpos[4];
+                bool ckeep[4];
+#pragma unroll
+                for (int tt = 0; tt < 4; ++tt) {
+                    const d2s c0 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32e) * kStat);
+                    const d2s c1 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32e) * kStat + 2u);
+                    caj[tt] = (uint32_t)c0.x;
+                    cpos[tt] = c1.x;
+                    ckeep[tt] = c1.y != 0.0;
+                }
+                const uint32_t j0 = t * kSlab + l32e;   // column of tile tt: j0 + 32 tt
+                const uint32_t halfe = ln >> 5;
+                uint32_t best = 0u;   // lane L: 1 + the highest recombinant column of row L in this tile, 0 if none
+#pragma unroll 1
+                for (int e = 0; e < 16; ++e) {
+#pragma unroll
+                    for (int m = 0; m < 2; ++m) {
+                        accel_t c4[4];   // ONE register-indexed read per accumulator, pinned (see area_epilogue)
+#pragma unroll
+                        for (int tt = 0; tt < 4; ++tt) {
+                            c4[tt] = acc[m][tt][e];
+                            asm volatile("" : "+v"(c4[tt]));
+                        }
+                        const uint32_t rlo = 32u * m + (uint32_t)(e & 3) + 8u * (uint32_t)(e >> 2);   // half 0's row; half 1: rlo + 4
+                        const uint32_t ri = rlo + 4u * halfe;
+                        const d2s r0 = *reinterpret_cast<const d2s *>(rstat + ri * kStat);   // two addresses per wave: broadcast
+                        const d2s r1 = *reinterpret_cast<const d2s *>(rstat + ri * kStat + 2u);
+                        const uint32_t i = row0 + ri;
+                        const uint32_t ai = (uint32_t)r0.x;
+                        const bool rkeep = r1.y != 0.0;   // (0 for a row beyond the panel)
+                        unsigned long long bm[4];
+#pragma unroll
+                        for (int tt = 0; tt < 4; ++tt) {
+                            const uint32_t g11 = kFp4 ? (uint32_t)c4[tt] : (uint32_t)c4[tt] >> 3;   // int8: 8 n11
+                            const uint32_t g10 = ai - g11, g01 = caj[tt] - g11, g00 = nh - ai - g01;
+                            const uint32_t lo = g11 < g10 ? g11 : g10, hi = g01 < g00 ? g01 : g00;
+                            const bool hit = (lo < hi ? lo : hi) >= mc && rkeep && ckeep[tt] && i > j0 + 32u * tt && r1.x - cpos[tt] <= win;
+                            bm[tt] = __ballot(hit);
+                        }
+                        if (!(bm[0] | bm[1] | bm[2] | bm[3])) continue;   // wave-uniform
+                        // columns 0-63 and 64-127 of the two rows (wave-uniform scalars)
+                        const unsigned long long lo01 = (bm[0] & 0xFFFFFFFFull) | (bm[1] << 32), lo23 = (bm[2] & 0xFFFFFFFFull) | (bm[3] << 32);
+                        const unsigned long long hi01 = (bm[0] >> 32) | (bm[1] & 0xFFFFFFFF00000000ull), hi23 = (bm[2] >> 32) | (bm[3] & 0xFFFFFFFF00000000ull);
+                        const uint32_t vlo = lo23 ? 128u - (uint32_t)__builtin_clzll(lo23) : (lo01 ? 64u - (uint32_t)__builtin_clzll(lo01) : 0u);
+                        const uint32_t vhi = hi23 ? 128u - (uint32_t)__builtin_clzll(hi23) : (hi01 ? 64u - (uint32_t)__builtin_clzll(hi01) : 0u);
+                        best = ln == rlo ? vlo : (ln == rlo + 4u ? vhi : best);
+                    }
+                }
+                const uint32_t i = row0 + ln;
+                if (best != 0u && i < n_snps) atomicMax(reinterpret_cast<uint32_t *>(aa.hits) + i, t * kSlab + best);
+              }
+            };
             if constexpr (kScore || kProd) {
                 // words per SNP -- score: column 0 and K categories; products: the right-hand sides (bit 4 of measure: power 2)
                 const uint32_t st = kProd ? (uint32_t)aa.measure & 15u : 1u + (uint32_t)aa.measure;
@@ -2084,6 +2168,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             if constexpr (kArea) {
                 if constexpr (kNbr) nbr_epilogue();
                 else if constexpr (kDecay) decay_epilogue();
+                else if constexpr (kFgt) fgt_epilogue();
                 else area_epilogue();
                 if (tid == 0) tickets[parity] = next_ticket;
                 if (!(ablate & 16)) __builtin_amdgcn_s_setprio(0);
@@ -2723,6 +2808,97 @@ int decay_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, cons
                : launch_decay<false>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
 }
 
+// ---- four-gamete test on the band (ldx_ld_fgt_dev) ---------------------------------------------------------------------
+// Zeroes `left` -- the call needs no memset of it --, writes the keep mask the epilogue reads (null: every SNP; monomorphic
+// SNPs stay in) and the two-row query list {0, n - 1} of the plan kernel, as decay_init_kernel.
+__global__ void fgt_init_kernel(const uint8_t *__restrict__ keep, uint32_t n_snps, uint8_t *__restrict__ mask,
+                                uint32_t *__restrict__ left, uint32_t *__restrict__ qrows)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) {
+        qrows[0] = 0u;
+        qrows[1] = n_snps - 1u;
+    }
+    if (i < n_snps) {
+        left[i] = 0u;
+        mask[i] = !keep || keep[i] != 0;
+    }
+}
+
+// the score band's workspace; its leading n_snps bytes hold the keep mask (as the decay band's)
+size_t fgt_mfma_workspace_bytes(uint32_t n_snps) { return score_mfma_workspace_bytes(n_snps); }
+
+template <bool kFp4>
+static int launch_fgt(const void *alt, uint32_t n_snps, uint32_t n_hap, uint32_t T, uint32_t nch, uint64_t units, size_t lds,
+                      const AreaArgs &aa, uint32_t *sched, hipStream_t s)
+{
+    static std::atomic<uint64_t> opted{0};   // the dynamic LDS opt-in: once per device
+    int dev = 0;
+    LDX_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !((opted.load(std::memory_order_relaxed) >> dev) & 1u)) {
+        LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, false, 0, false, true>,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (dev >= 0 && dev < 64) opted.fetch_or(1ull << dev, std::memory_order_relaxed);
+    }
+    // (fa / fr / q stay null: the four-gamete instantiation stages the ALT counts from aa.counts and reads no frequency)
+    triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, false, 0, false, true><<<(uint32_t)device_cus() * 2u, kMfmaThreads, lds, s>>>(
+        (const uint4 *)alt, nullptr, nullptr, nullptr, n_snps, T, nch, (double)n_hap, 1.0 / (double)n_hap, 0, units * 8u,
+        (ldx_ld32 *)nullptr, nullptr, nullptr, 0u, 0u, 0u, sched, 0, nullptr, aa);
+    LDX_HIP(hipGetLastError());
+    return LDX_OK;
+}
+
+int fgt_mfma(const void *alt, const uint32_t *acnt, uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window,
+             uint32_t min_count, const uint8_t *keep, bool fp4, uint32_t *left, void *workspace, hipStream_t s)
+{
+    const uint32_t T = n_slabs(n_snps), nch = n_chunks(n_hap);
+    if ((uint64_t)T * nch * kSlab * 16u >= (1ull << 32)) {   // the K loop addresses the plane with 32-bit lane offsets
+        set_error("ldx_ld_fgt_dev: a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", n_snps, n_hap);
+        return LDX_E_UNSUPPORTED;
+    }
+    // the band's buffers, carved as in score_mfma; the query mask's bytes hold the keep mask
+    uint8_t *mask = (uint8_t *)workspace;
+    char *w = (char *)workspace + ((size_t)n_snps + 255u) / 256u * 256u;
+    uint32_t *pass_base = (uint32_t *)w;
+    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
+    uint32_t *g_end = (uint32_t *)w;
+    w += ((size_t)T * 4u + 255u) / 256u * 256u;
+    uint32_t *g_begin = (uint32_t *)w;
+    w += ((size_t)T * 4u + 255u) / 256u * 256u;
+    uint32_t *first_base = (uint32_t *)w;
+    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
+    uint32_t *order = area_order_entries(n_snps) ? (uint32_t *)w : nullptr;
+    w += (area_order_entries(n_snps) * 4u + 255u) / 256u * 256u;
+    uint32_t *sched = (uint32_t *)w;
+    w += kAreaSchedWords * 4u;
+    uint32_t *qrows = (uint32_t *)w;                               // [2]
+    unsigned long long *n_hits = (unsigned long long *)(w + 8);   // the plan kernel zeroes it; nothing reads it
+    fgt_init_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(keep, n_snps, mask, left, qrows);
+    LDX_HIP(hipGetLastError());
+    if (n_snps < 2) return LDX_OK;   // no pairs
+    // the score band's plan: every SNP a query, flank = window; fgt_epilogue applies the exact bound per pair
+    area_band_plan_kernel<<<1, 1024, 0, s>>>(positions, n_snps, T, window, qrows, 2u, g_begin, g_end, pass_base, n_hits,
+                                             order, first_base, sched);
+    LDX_HIP(hipGetLastError());
+    AreaArgs aa{};
+    aa.f32 = f32_const((double)n_hap);
+    aa.pos = positions;
+    aa.is_query = mask;                        // fgt: the keep mask
+    aa.pass_base = pass_base;
+    aa.g_begin = g_begin;
+    aa.g_end = g_end;
+    aa.order = order;
+    aa.hits = (ldx_hit *)left;                 // fgt: the uint32 words left[n_snps]
+    aa.counts = const_cast<uint32_t *>(acnt);  // fgt: the ALT counts (read only)
+    aa.n_hits = n_hits;
+    aa.flank = (double)window;
+    aa.measure = (int)min_count;               // fgt: the smallest gamete count of a recombinant pair (<= n_hap)
+    const uint64_t units = ldx_triangle_units(n_snps) / 8u;   // 64-row units of the full triangle
+    const size_t lds = mfma_lds_bytes(kRows64, false, false);
+    return fp4 ? launch_fgt<true>(alt, n_snps, n_hap, T, nch, units, lds, aa, sched, s)
+               : launch_fgt<false>(alt, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
+}
+
 // ---- matrix-vector products on the band (ldx_ld_matvec_dev) ------------------------------------------------------------
 // Every SNP's own term (r32_diag or its float32 square, times its weights) WRITES its words -- the call needs no memset of
 // `sums` -- and the two-row query list {0, n - 1} the plan kernel reads, as score_init_kernel.
@@ -3008,6 +3184,35 @@ extern "C" int ldx_ld_decay_dev(const void *alt, const uint32_t *acnt, const uin
     // a width above the window puts every pair into bin 0, so any such width acts as 2^52 + 1 (exact in a double)
     return ldx::decay_mfma(alt, acnt, rcnt, fa, fr, n_snps, n_hap, positions, w, bin_width <= wmax ? bin_width : wmax + 1, keep,
                            path != LDX_PATH_MFMA, sums, counts, n_bins, workspace, (hipStream_t)stream);
+}
+
+extern "C" size_t ldx_ld_fgt_workspace_bytes(uint32_t n_snps, uint32_t n_hap)
+{
+    (void)n_hap;   // (the layout depends on the SNP count alone)
+    return ldx::fgt_mfma_workspace_bytes(n_snps ? n_snps : 1u);
+}
+
+extern "C" int ldx_ld_fgt_dev(const void *alt, const uint32_t *acnt, uint32_t n_snps, uint32_t n_hap, const int64_t *positions,
+                              int64_t window, uint32_t min_count, const uint8_t *keep, int path, uint32_t *left,
+                              void *workspace, size_t workspace_bytes, void *stream)
+{
+    LDX_REQUIRE(alt && acnt && positions && left && workspace, "null pointer");
+    LDX_REQUIRE(n_snps >= 1 && n_hap >= 1 && window >= 0, "bad shape");
+    LDX_REQUIRE(min_count >= 1 && min_count <= n_hap, "min_count must be 1 .. n_hap");
+    LDX_REQUIRE(((uintptr_t)workspace & 255u) == 0, "workspace must be 256-byte aligned");
+    LDX_REQUIRE(workspace_bytes >= ldx::fgt_mfma_workspace_bytes(n_snps), "workspace too small (see ldx_ld_fgt_workspace_bytes)");
+    LDX_REQUIRE(path == LDX_PATH_AUTO || path == LDX_PATH_POPCOUNT || path == LDX_PATH_MFMA || path == LDX_PATH_FP4, "unknown path");
+    if (n_hap > LDX_MAX_HAPS) {
+        ldx::set_error("ldx_ld_fgt_dev: n_hap %u > LDX_MAX_HAPS %u", n_hap, LDX_MAX_HAPS);
+        return LDX_E_UNSUPPORTED;
+    }
+    if (path == LDX_PATH_POPCOUNT) {
+        ldx::set_error("ldx_ld_fgt_dev: the four-gamete test runs on the matrix-pipe band (LDX_PATH_FP4 / LDX_PATH_MFMA), not on the popcount kernels");
+        return LDX_E_UNSUPPORTED;
+    }
+    const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles: keep pos + window exact
+    return ldx::fgt_mfma(alt, acnt, n_snps, n_hap, positions, window < wmax ? window : wmax, min_count, keep,
+                         path != LDX_PATH_MFMA, left, workspace, (hipStream_t)stream);
 }
 
 extern "C" size_t ldx_ld_score_workspace_bytes(uint32_t n_snps, uint32_t n_hap)

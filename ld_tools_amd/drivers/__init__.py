@@ -9,6 +9,7 @@ loop order).  Any object with pysam's ``VariantFile.fetch(chrom, start, end)`` /
 as the VCF source; pysam itself is only imported by the command-line shells.
 """
 from .area import AreaQueryResult, area_scan, get_inld_vars, write_area_file  # noqa: F401
+from .blocks import write_blocks  # noqa: F401
 from .clump import ClumpTable, clump, write_clumped  # noqa: F401
 from .decay import write_decay  # noqa: F401
 from .ingest import RaggedGenotypesError, codes_matrix, find_record, sample_genotypes  # noqa: F401

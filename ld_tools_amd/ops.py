@@ -865,6 +865,171 @@ def _decay_launch(panel, pos, window, width, keep_d, pcode, sums, counts, worksp
                                workspace.numel() * workspace.element_size(), _stream_ptr()), "ldx_ld_decay_dev")
 
 
+# --------------------------------------------------------------------------- haplotype blocks (four-gamete test)
+NOT_KEPT = 0xFFFFFFFF            # block_of of a SNP that is not kept (include/ldx.h, ldx_ld_blocks_dev)
+
+
+def blocks_host(left, positions, window: int, keep=None) -> Tuple[np.ndarray, int, int]:
+    """Host mirror of ldx_ld_blocks_dev, the scan only: (block_of uint32 [n], n_blocks, rm) from a ``left`` array
+    (ldx_ld_fgt_dev's output).  With s the current block's first SNP, kept SNP i starts a new block iff there is no current
+    block, or left[i] >= s + 1, or pos_i - pos_s > window; ``rm`` counts the starts the ``left`` rule caused (it outranks
+    the window rule)."""
+    left = np.asarray(left).astype(np.int64)
+    pos = np.asarray(positions, dtype=np.int64)
+    n = left.shape[0]
+    if pos.shape != (n,):
+        raise _lib.LdxError("positions must have one entry per SNP")
+    kept = np.ones(n, dtype=bool) if keep is None else np.asarray(keep).astype(bool)
+    block_of = np.full(n, NOT_KEPT, dtype=np.uint32)
+    s, n_blocks, rm = -1, 0, 0
+    for i in range(n):
+        if not kept[i]:
+            continue
+        by_left = s >= 0 and left[i] >= s + 1
+        if s < 0 or by_left or pos[i] - pos[s] > window:
+            rm += int(by_left)
+            s = i
+            n_blocks += 1
+        block_of[i] = n_blocks - 1
+    return block_of, n_blocks, rm
+
+
+@dataclass
+class LDBlocks:
+    """Haplotype blocks of one panel by the four-gamete test (ld_blocks).  ``left_dev`` / ``block_of_dev`` / ``n_out`` are
+    the device tensors the two calls wrote (int32 views of the uint32 words); the host arrays are fetched when first asked
+    for.  The partition is the greedy left-to-right one (Hudson & Kaplan), not Haploview's block-picking order."""
+
+    left_dev: torch.Tensor
+    block_of_dev: torch.Tensor
+    n_out: torch.Tensor
+    positions: object
+    window: int
+    min_count: int
+    keep: Optional[np.ndarray] = None
+    _host: Optional[tuple] = None
+
+    def _fetch(self) -> tuple:
+        if self._host is None:
+            left = self.left_dev.cpu().numpy().view(np.uint32)
+            block_of = self.block_of_dev.cpu().numpy().view(np.uint32)
+            n_out = self.n_out.cpu().numpy().view(np.uint32)
+            pos = self.positions.cpu().numpy() if isinstance(self.positions, torch.Tensor) else self.positions
+            kept = np.flatnonzero(block_of != NOT_KEPT)
+            b = block_of[kept].astype(np.int64)
+            first = np.ones(kept.size, dtype=bool)
+            first[1:] = b[1:] != b[:-1]
+            last = np.ones(kept.size, dtype=bool)
+            last[:-1] = first[1:]
+            self._host = (left, block_of, int(n_out[0]), int(n_out[1]), kept[first], kept[last],
+                          np.bincount(b, minlength=int(n_out[0])).astype(np.int64), np.asarray(pos, dtype=np.int64))
+        return self._host
+
+    @property
+    def left(self) -> np.ndarray:
+        """uint32 [n]: 1 + the nearest recombinant partner to the left, 0 if none."""
+        return self._fetch()[0]
+
+    @property
+    def block_of(self) -> np.ndarray:
+        """uint32 [n]: the 0-based block of every SNP, NOT_KEPT for a SNP that is not kept."""
+        return self._fetch()[1]
+
+    @property
+    def n_blocks(self) -> int:
+        return self._fetch()[2]
+
+    @property
+    def rm(self) -> int:
+        """Block starts caused by a recombinant pair: Hudson & Kaplan's Rm restricted to the window."""
+        return self._fetch()[3]
+
+    @property
+    def starts(self) -> np.ndarray:
+        """int64 [n_blocks]: the first SNP of every block."""
+        return self._fetch()[4]
+
+    @property
+    def ends(self) -> np.ndarray:
+        """int64 [n_blocks]: the last kept SNP of every block (inclusive)."""
+        return self._fetch()[5]
+
+    @property
+    def sizes(self) -> np.ndarray:
+        """int64 [n_blocks]: kept SNPs per block."""
+        return self._fetch()[6]
+
+    @property
+    def spans_bp(self) -> np.ndarray:
+        """int64 [n_blocks]: pos[end] - pos[start] of every block (<= window)."""
+        pos = self._fetch()[7]
+        return pos[self.ends] - pos[self.starts]
+
+
+def ld_blocks(panel: PackedPanel, positions=None, window_bp: int = 500_000, window_snps: Optional[int] = None,
+              min_count: int = 1, min_freq: Optional[float] = None, keep=None, maf_min: float = 0.0,
+              path: Optional[str] = None, workspace: Optional[torch.Tensor] = None,
+              check_positions: bool = True) -> LDBlocks:
+    """Haplotype blocks by the four-gamete test on the matrix-pipe band (include/ldx.h, ldx_ld_fgt_dev + ldx_ld_blocks_dev).
+    A pair i > j with pos_i - pos_j <= window, both SNPs kept, is recombinant when each of the four two-locus haplotypes
+    occurs at least ``min_count`` times ("not ALT" is the other allele: missing codes count with REF); ``left[i]`` is 1 +
+    the nearest recombinant partner to the left, and the blocks are the greedy left-to-right partition over it, cut by
+    the window as well, so no block holds a recombinant pair.  Integer arithmetic throughout: identical on both paths.
+
+    ``min_freq`` gives min_count = max(1, ceil(min_freq * n_hap)) (Haploview's rule: 0.01).  ``keep`` (bool [n]) and
+    ``maf_min`` (keeps min(a, n - a) / n >= maf_min) combine into the keep mask; monomorphic SNPs are otherwise kept (they
+    are compatible with everything).  ``window_snps`` counts the window in SNPs (positions 0 .. n-1).  ``path``: 'fp4'
+    (default) or 'mfma'.  ``workspace``: a uint8 device tensor of ldx_ld_fgt_workspace_bytes() bytes to reuse.  The call is
+    stream-ordered: the host reads nothing until a result property is asked for.
+    """
+    require_gpu()
+    n = panel.n_snps
+    pos, pos_h, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_blocks")
+    if min_freq is not None:
+        if not 0.0 <= float(min_freq) <= 1.0:
+            raise _lib.LdxError("min_freq must lie in [0, 1]")
+        min_count = max(1, int(np.ceil(float(min_freq) * panel.n_hap)))
+    min_count = int(min_count)
+    if not 1 <= min_count <= panel.n_hap:
+        raise _lib.LdxError(f"min_count must be 1 .. n_hap ({panel.n_hap}), got {min_count}")
+    kept = None
+    if keep is not None:
+        k = keep.cpu().numpy() if isinstance(keep, torch.Tensor) else np.asarray(keep)
+        if k.shape != (n,) or (k.dtype != bool and not np.isin(k, (0, 1)).all()):
+            raise _lib.LdxError(f"keep must be a boolean array of shape [{n}]")
+        kept = k.astype(bool)
+    if maf_min > 0.0:
+        a = panel.alt_counts().astype(np.int64)
+        common = np.minimum(a, panel.n_hap - a) >= float(maf_min) * panel.n_hap
+        kept = common if kept is None else kept & common
+    keep_d = None if kept is None else torch.as_tensor(np.ascontiguousarray(kept.astype(np.uint8))).to(panel.device)
+    pcode = PATHS["fp4"] if path is None else PATHS[path]
+    need = lib.ldx_ld_fgt_workspace_bytes(n, panel.n_hap)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=panel.device)
+    elif workspace.numel() * workspace.element_size() < need:
+        raise _lib.LdxError(f"workspace too small: {need} bytes needed")
+    left = torch.empty(n, dtype=torch.int32, device=panel.device)
+    block_of = torch.empty(n, dtype=torch.int32, device=panel.device)
+    n_out = torch.empty(2, dtype=torch.int32, device=panel.device)
+    _fgt_launch(panel, pos, window, min_count, keep_d, pcode, left, workspace)
+    _blocks_launch(left, pos, keep_d, n, window, block_of, n_out)
+    res = LDBlocks(left, block_of, n_out, pos if pos_h is None else pos_h, window, min_count, kept)
+    res._keep = (pos, keep_d, workspace)   # alive until the launches are done
+    return res
+
+
+def _fgt_launch(panel, pos, window, min_count, keep_d, pcode, left, workspace) -> None:
+    check(lib.ldx_ld_fgt_dev(panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.n_snps, panel.n_hap, pos.data_ptr(), window,
+                             min_count, _ptr(keep_d), pcode, left.data_ptr(), workspace.data_ptr(),
+                             workspace.numel() * workspace.element_size(), _stream_ptr()), "ldx_ld_fgt_dev")
+
+
+def _blocks_launch(left, pos, keep_d, n, window, block_of, n_out) -> None:
+    check(lib.ldx_ld_blocks_dev(left.data_ptr(), pos.data_ptr(), _ptr(keep_d), n, window, block_of.data_ptr(),
+                                n_out.data_ptr(), _stream_ptr()), "ldx_ld_blocks_dev")
+
+
 # --------------------------------------------------------------------------- R x without the matrix, ridge solves
 PROD_SCALE_BITS = 40             # sums are integers in units of 2^-40 (include/ldx.h, ldx_ld_matvec_dev)
 PROD_CLAMP = float(1 << 22)      # |v x| beyond it is clamped before scaling (keeps the int64 conversion defined)
