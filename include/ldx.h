@@ -422,6 +422,63 @@ int ldx_ld_fgt_dev(const void *alt, const uint32_t *acnt, uint32_t n_snps, uint3
 int ldx_ld_blocks_dev(const uint32_t *left, const int64_t *positions, const uint8_t *keep, uint32_t n_snps, int64_t window,
                       uint32_t *block_of, uint32_t *n_out, void *stream);
 
+/* ---- LD-independent regions: the cross-LD profile of the band and the optimal cuts over it ---- */
+/* ldx_ld_cross_dev: ldx_ld_score_dev's sweep -- the same pairs, window test, r cell and term -- with the two halves of every
+ * SNP's score kept apart.  For every pair i > j with pos_i - pos_j <= window (positions int64, NON-DECREASING; duplicates
+ * give distance 0; i = j is not a pair), with c_ij the signed r cell of ldx_triangle_ex_dev(LDX_OUT_R32), bit for bit:
+ *     term = rint(2^32 * (c_ij *f32 c_ij))     the term ldx_ld_score_dev sums (0 for the -0.0f cell of a degenerate SNP)
+ *     sides[i][0] += term                      i's LEFT partners   (uint64 [n_snps][2])
+ *     sides[j][1] += term                      j's RIGHT partners
+ * so sides[i][0] + sides[i][1] + term(c_ii) = ldx_ld_score_dev's sums[i][0] on the same window, and the sum of all left
+ * halves = the sum of all right halves = the sum of ldx_ld_decay_dev's sums with keep = NULL.  The call writes every word
+ * of `sides` (no memset by the caller; a relaunch into a used buffer gives the same array); the sums are 64-bit integer
+ * atomics: order-independent, bit-reproducible, identical on both paths, equal to a host sum over the r32 square.
+ * A scan then writes the CROSS-LD PROFILE, the LD that crosses a cut before SNP k:
+ *     cross[k] = sum of term over the pairs j < k <= i inside the window          (uint64 [n_snps + 1], k = 0 .. n_snps)
+ *              = cross[k - 1] + sides[k - 1][1] - sides[k - 1][0] modulo 2^64,  cross[0] = 0
+ * (pair (i, j) enters at k = j + 1 and leaves at k = i + 1, so cross[n_snps] = 0 too).  The true value is non-negative, so
+ * the modular sum is exact as long as it is below 2^64: cross[k] wraps only if the r^2 that straddles ONE cut reaches 2^32
+ * (without missing codes r^2 <= 1: 2^32 in-window pairs across one cut).  A half of `sides` wraps like ldx_ld_score_dev's sums.
+ * ldx_ld_cross_scan_dev is the scan alone (ldx_ld_cross_dev ends with it): one workgroup walks the array, any n_snps.
+ *   acnt / rcnt / fa / fr, positions, window (values above 2^52 act as 2^52), n_hap: as for ldx_ld_score_dev;
+ *   path: LDX_PATH_AUTO / LDX_PATH_FP4 = the FP4 band, LDX_PATH_MFMA = the int8 band (identical outputs), LDX_PATH_POPCOUNT =
+ *         LDX_E_UNSUPPORTED; n_hap > LDX_MAX_HAPS and a bit plane of 4 GiB or more = LDX_E_UNSUPPORTED.
+ * workspace: ldx_ld_cross_workspace_bytes() bytes, 256-byte aligned, no initialisation needed (the score band's layout): one
+ * per launch that may be in flight, as for ldx_ld_score_dev.  The calls only enqueue work on `stream`: no allocation, no
+ * synchronisation, no state in the library.
+ *
+ * ldx_ld_split_dev: the cuts of minimum total cross-LD with every region min_snps .. max_snps SNPs long (the objective of
+ * ldetect, Berisa & Pickrell 2016, and of bigsnpr's snp_ldsplit, with ADDITIVE cuts: the cost of a cut set is the sum over
+ * its cuts of the LD crossing each one, so a pair that straddles two cuts counts twice -- which needs a region narrower
+ * than the window).  A cut c is a boundary before SNP c, 0 < c < n.  With cost[k] = cross[k] >> 16 (units of 2^-16 r^2):
+ *     best[0] = 0
+ *     best[k] = min over p in [max(0, k - max_snps), k - min_snps] with best[p] feasible of best[p]
+ *               + (cost[k] if k < n else 0);                      infeasible if there is no such p     (k = 1 .. n)
+ *     prev[k] = the LARGEST p attaining that minimum
+ * and the cuts are the backtrack from n through prev, 0 excluded, written ascending:
+ *     cuts (uint32, room for n / min_snps entries; at most n / min_snps - 1 are written);
+ *     n_out[0] = the number of cuts;
+ *     n_out[1] = 0, or 1 if best[n] is infeasible (no m with m min_snps <= n <= m max_snps), or 2 if a sum wrapped; no cut
+ *                is written then and n_out[0] = 0.
+ * Sums saturate at 2^64 - 2, and a saturated best[n] is what "wrapped" means: the total cost of the optimal cuts reached
+ * 2^64 - 2, i.e. 2^48 of r^2 summed over the cuts (cost[k] < 2^48 always).  A saturated state that is not on the optimal
+ * path does not set the flag: costs are non-negative, so it cannot lie on a path with a smaller total.
+ *   cross: uint64 [n + 1] (ldx_ld_cross_dev's, or any array: only cross[1 .. n - 1] is read);
+ *   1 <= min_snps <= max_snps (else LDX_E_ARG); max_snps above n acts as n.
+ * ONE workgroup runs the recurrence: the min_snps states k .. k + min_snps - 1 depend only on best[p], p < k, so they are
+ * computed side by side, a barrier between such chunks; the range minimum costs O(1) per state through prefix / suffix
+ * arg-minima over blocks of max_snps - min_snps + 1 states (van Herk / Gil-Werman), each written once by a segmented scan.
+ * One lane backtracks at the end, so everything stays on the device and the call can be captured behind ldx_ld_cross_dev.
+ * workspace: ldx_ld_split_workspace_bytes(n) bytes (20 per state), 256-byte aligned, no initialisation needed. */
+size_t ldx_ld_cross_workspace_bytes(uint32_t n_snps, uint32_t n_hap);
+int ldx_ld_cross_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
+                     uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, int path,
+                     uint64_t *sides, uint64_t *cross, void *workspace, size_t workspace_bytes, void *stream);
+int ldx_ld_cross_scan_dev(const uint64_t *sides, uint32_t n_snps, uint64_t *cross, void *stream);
+size_t ldx_ld_split_workspace_bytes(uint32_t n);
+int ldx_ld_split_dev(const uint64_t *cross, uint32_t n, uint32_t min_snps, uint32_t max_snps,
+                     uint32_t *cuts, uint32_t *n_out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- banded LD matrix-vector products: R_w X and (R_w o R_w) X without the matrix, on the matrix-pipe band ---- */
 /* For every SNP i and right-hand side k < n_rhs (1 <= n_rhs <= 8), power in {1, 2}:
  *     c_ij = the signed r cell of ldx_triangle_ex_dev(LDX_OUT_R32) for the pair, bit for bit; c_ii = (n - a_i) / r_i, the

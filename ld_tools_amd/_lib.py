@@ -141,6 +141,11 @@ SIGNATURES = {
     "ldx_ld_fgt_workspace_bytes": (_sz, [_u32, _u32]),
     "ldx_ld_fgt_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _i64, _u32, _vp, _int, _vp, _vp, _sz, _vp]),
     "ldx_ld_blocks_dev": (_int, [_vp, _vp, _vp, _u32, _i64, _vp, _vp, _vp]),
+    "ldx_ld_cross_workspace_bytes": (_sz, [_u32, _u32]),
+    "ldx_ld_cross_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _i64, _int, _vp, _vp, _vp, _sz, _vp]),
+    "ldx_ld_cross_scan_dev": (_int, [_vp, _u32, _vp, _vp]),
+    "ldx_ld_split_workspace_bytes": (_sz, [_u32]),
+    "ldx_ld_split_dev": (_int, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _sz, _vp]),
     "ldx_ld_matvec_workspace_bytes": (_sz, [_u32, _u32]),
     "ldx_ld_matvec_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _i64, _vp, _u32, _int, _int, _vp, _vp, _sz, _vp]),
     "ldx_ld_neighbors_workspace_bytes": (_sz, [_u32, _u32]),

@@ -871,3 +871,238 @@ extern "C" int ldx_ld_blocks_dev(const uint32_t *left, const int64_t *positions,
     LDX_HIP(hipGetLastError());
     return LDX_OK;
 }
+
+// ---- LD-independent regions: the cross-LD profile's scan (ldx_ld_cross_scan_dev) and the optimal cuts (ldx_ld_split_dev) ---
+namespace ldx {
+
+constexpr uint32_t kScanThreads = 1024u, kScanPer = 4u;   // one tile of the scan: 4096 SNPs, four consecutive ones per thread
+
+// cross[0] = 0, cross[k] = cross[k - 1] + sides[k - 1][1] - sides[k - 1][0] modulo 2^64: an inclusive prefix sum of the
+// differences of the one-sided scores.  ONE workgroup walks the array tile by tile (a thread's four SNPs are 64 contiguous
+// bytes of `sides`), the running total carried in a register every thread holds: any n_snps, no second launch, no workspace.
+__global__ void __launch_bounds__(kScanThreads) cross_scan_kernel(const uint64_t *__restrict__ sides, uint32_t n_snps,
+                                                                  uint64_t *__restrict__ cross)
+{
+    __shared__ uint64_t wave_tot[kScanThreads / 64u];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint64_t carry = 0;   // cross[base]
+    if (tid == 0u) cross[0] = 0u;
+    for (uint64_t base = 0; base < n_snps; base += kScanThreads * kScanPer) {
+        uint64_t d[kScanPer], s = 0;
+#pragma unroll
+        for (uint32_t e = 0; e < kScanPer; ++e) {
+            const uint64_t m = base + (uint64_t)tid * kScanPer + e;
+            s += m < n_snps ? sides[2u * m + 1u] - sides[2u * m] : 0u;
+            d[e] = s;   // inclusive inside the thread
+        }
+        uint64_t x = s;   // inclusive over the wave
+#pragma unroll
+        for (uint32_t off = 1; off < 64u; off <<= 1) {
+            const uint64_t y = __shfl_up(x, off);
+            if (lane >= off) x += y;
+        }
+        if (lane == 63u) wave_tot[wave] = x;
+        block_sync();
+        uint64_t before = carry, total = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < kScanThreads / 64u; ++w) {
+            const uint64_t t = wave_tot[w];
+            before += w < wave ? t : 0u;
+            total += t;
+        }
+        before += x - s;   // the wave's lanes in front of this one
+#pragma unroll
+        for (uint32_t e = 0; e < kScanPer; ++e) {
+            const uint64_t m = base + (uint64_t)tid * kScanPer + e;
+            if (m < n_snps) cross[m + 1u] = before + d[e];
+        }
+        carry += total;
+        block_sync();   // wave_tot is free again
+    }
+}
+
+// -- the cuts.  States 0 .. n; best / prev / pre / suf live in the workspace.  INF marks an infeasible state, sums saturate
+// at SAT (include/ldx.h).  pre[p] / suf[p]: the arg-minimum of best over [block start, p] / [p, block end], the blocks being
+// the aligned runs of W = max_snps - min_snps + 1 states; ties go to the larger p throughout.  A state's window
+// [k - max_snps, k - min_snps] is W long (or starts at 0, a block start), so it is a suffix of one block and a prefix of the
+// next (or a prefix alone): two reads instead of W.
+constexpr uint64_t kSplitInf = ~0ull, kSplitSat = ~0ull - 1u;
+constexpr uint32_t kSplitNone = 0xFFFFFFFFu;
+
+struct SplitMin {   // a running arg-minimum: best[p] = v; head: a segment starts inside the run this stands for
+    uint64_t v;
+    uint32_t p;
+    uint32_t head;
+};
+
+__device__ inline bool split_better(uint64_t va, uint32_t pa, uint64_t vb, uint32_t pb) { return va < vb || (va == vb && pa > pb); }
+
+// a: the run scanned earlier, b: the run behind it (the segmented-scan operator: associative)
+__device__ inline SplitMin split_join(const SplitMin &a, const SplitMin &b)
+{
+    if (b.head) return b;
+    SplitMin r = split_better(a.v, a.p, b.v, b.p) ? a : b;
+    r.head = a.head;
+    return r;
+}
+
+// Segmented inclusive arg-min scan of best over the states [lo, hi], by the whole workgroup: forward (out = pre: segments
+// start where p % W == 0) or backward (out = suf: they start where p % W == W - 1).  `carry`: the run in front of the first
+// state (have_carry), else the first state starts a segment.  Ends behind a barrier: every out[] is visible to the workgroup.
+template <bool kBack>
+__device__ void split_scan(uint64_t lo, uint64_t hi, uint64_t W, const uint64_t *best, uint32_t *out, SplitMin carry,
+                           bool have_carry, SplitMin *wave_tot, SplitMin *tile_carry)
+{
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, nthreads = blockDim.x;
+    const uint64_t len = hi - lo + 1u;
+    for (uint64_t t0 = 0; t0 < len; t0 += nthreads) {
+        const uint64_t t = t0 + tid;
+        const bool valid = t < len;
+        const uint64_t q = valid ? (kBack ? hi - t : lo + t) : lo;
+        SplitMin e;
+        e.v = valid ? best[q] : kSplitInf;
+        e.p = (uint32_t)q;
+        e.head = valid && (q % W == (kBack ? W - 1u : 0u)) ? 1u : 0u;
+        SplitMin x = e;   // inclusive over the wave
+#pragma unroll
+        for (uint32_t off = 1; off < 64u; off <<= 1) {
+            SplitMin y;
+            y.v = __shfl_up(x.v, off);
+            y.p = __shfl_up(x.p, off);
+            y.head = __shfl_up(x.head, off);
+            if (lane >= off) x = split_join(y, x);
+        }
+        if (lane == 63u) wave_tot[wave] = x;
+        block_sync();
+        SplitMin acc = carry;
+        bool has = have_carry;
+        for (uint32_t w = 0; w < wave; ++w) {
+            acc = has ? split_join(acc, wave_tot[w]) : wave_tot[w];
+            has = true;
+        }
+        const SplitMin r = has ? split_join(acc, x) : x;
+        if (valid) out[q] = r.p;
+        if (tid == nthreads - 1u) *tile_carry = r;   // (only a full tile has a successor)
+        block_sync();
+        carry = *tile_carry;
+        have_carry = true;
+    }
+}
+
+__global__ void __launch_bounds__(1024) split_kernel(const uint64_t *__restrict__ cross, uint32_t n, uint32_t min_snps,
+                                                     uint32_t max_snps, uint64_t *best, uint32_t *prev, uint32_t *pre,
+                                                     uint32_t *suf, uint32_t *__restrict__ cuts, uint32_t *__restrict__ n_out)
+{
+    __shared__ SplitMin wave_tot[16];
+    __shared__ SplitMin tile_carry;
+    const uint32_t tid = threadIdx.x;
+    const uint64_t N = n, mn = min_snps, mx = max_snps, W = mx - mn + 1u;
+    // the arg-minima over the states [c, ce], just computed: pre for all of them, suf for every block that ends among them
+    auto publish = [&](uint64_t c, uint64_t ce) {
+        SplitMin carry{kSplitInf, 0u, 0u};
+        const bool have = c % W != 0u;
+        if (have) {
+            carry.p = pre[c - 1u];
+            carry.v = best[carry.p];
+        }
+        split_scan<false>(c, ce, W, best, pre, carry, have, wave_tot, &tile_carry);
+        const uint64_t done = (ce + 1u) / W;   // blocks complete so far; the last of them ends at done W - 1
+        if (done != 0u && done * W - 1u >= c)
+            split_scan<true>(c / W * W, done * W - 1u, W, best, suf, SplitMin{kSplitInf, 0u, 0u}, false, wave_tot, &tile_carry);
+    };
+    if (tid == 0u) {
+        best[0] = 0u;
+        prev[0] = kSplitNone;
+    }
+    block_sync();
+    publish(0u, 0u);
+    for (uint64_t c = 1; c <= N; c += mn) {   // a chunk: min_snps states that depend on earlier chunks alone
+        const uint64_t ce = c + mn - 1u < N ? c + mn - 1u : N;
+        for (uint64_t k = c + tid; k <= ce; k += blockDim.x) {
+            uint64_t v = kSplitInf;
+            uint32_t from = kSplitNone;
+            if (k >= mn) {
+                const uint64_t b = k - mn, a = k > mx ? k - mx : 0u;
+                uint32_t cand = pre[b];
+                uint64_t cv = best[cand];
+                if (a / W != b / W) {   // the window starts in the block before b's
+                    const uint32_t x = suf[a];
+                    const uint64_t xv = best[x];
+                    if (split_better(xv, x, cv, cand)) {
+                        cand = x;
+                        cv = xv;
+                    }
+                }
+                if (cv != kSplitInf) {
+                    const uint64_t cost = k < N ? cross[k] >> 16 : 0u;
+                    v = cv + cost;
+                    if (v < cv || v >= kSplitSat) v = kSplitSat;
+                    from = cand;
+                }
+            }
+            best[k] = v;
+            prev[k] = from;
+        }
+        block_sync();
+        publish(c, ce);
+    }
+    if (tid == 0u) {   // the backtrack: count, then write ascending
+        const uint64_t total = best[N];
+        uint32_t m = 0u, flag = 0u;
+        if (total == kSplitInf) flag = 1u;
+        else if (total == kSplitSat) flag = 2u;
+        else {
+            for (uint32_t k = prev[N]; k != 0u; k = prev[k]) ++m;
+            uint32_t at = m;
+            for (uint32_t k = prev[N]; k != 0u; k = prev[k]) cuts[--at] = k;
+        }
+        n_out[0] = m;
+        n_out[1] = flag;
+    }
+}
+
+static size_t split_carve(uint32_t n, void *base, uint64_t **best, uint32_t **prev, uint32_t **pre, uint32_t **suf)
+{
+    const size_t states = (size_t)n + 1u, a = align_up(states * 8u, 256), b = align_up(states * 4u, 256);
+    char *w = (char *)base;
+    if (w) {
+        *best = (uint64_t *)w;
+        *prev = (uint32_t *)(w + a);
+        *pre = (uint32_t *)(w + a + b);
+        *suf = (uint32_t *)(w + a + 2u * b);
+    }
+    return a + 3u * b;
+}
+
+}  // namespace ldx
+
+extern "C" int ldx_ld_cross_scan_dev(const uint64_t *sides, uint32_t n_snps, uint64_t *cross, void *stream)
+{
+    LDX_REQUIRE(sides && cross, "null pointer");
+    LDX_REQUIRE(n_snps >= 1, "bad shape");
+    ldx::cross_scan_kernel<<<1, ldx::kScanThreads, 0, (hipStream_t)stream>>>(sides, n_snps, cross);
+    LDX_HIP(hipGetLastError());
+    return LDX_OK;
+}
+
+extern "C" size_t ldx_ld_split_workspace_bytes(uint32_t n) { return ldx::split_carve(n, nullptr, nullptr, nullptr, nullptr, nullptr); }
+
+extern "C" int ldx_ld_split_dev(const uint64_t *cross, uint32_t n, uint32_t min_snps, uint32_t max_snps, uint32_t *cuts,
+                                uint32_t *n_out, void *workspace, size_t workspace_bytes, void *stream)
+{
+    LDX_REQUIRE(cross && cuts && n_out && workspace, "null pointer");
+    LDX_REQUIRE(n >= 1, "bad shape");
+    LDX_REQUIRE(min_snps >= 1 && min_snps <= max_snps, "need 1 <= min_snps <= max_snps");
+    LDX_REQUIRE(((uintptr_t)workspace & 255u) == 0, "workspace must be 256-byte aligned");
+    LDX_REQUIRE(workspace_bytes >= ldx_ld_split_workspace_bytes(n), "workspace too small (see ldx_ld_split_workspace_bytes)");
+    uint64_t *best = nullptr;
+    uint32_t *prev = nullptr, *pre = nullptr, *suf = nullptr;
+    ldx::split_carve(n, workspace, &best, &prev, &pre, &suf);
+    const uint32_t top = n > min_snps ? n : min_snps, mx = max_snps < top ? max_snps : top;   // a larger max_snps acts the same
+    // as many threads as a chunk or a block of the arg-minima has states (a barrier between 64 threads is the cheaper one)
+    const uint64_t widest = (uint64_t)min_snps > (uint64_t)mx - min_snps + 1u ? (uint64_t)min_snps : (uint64_t)mx - min_snps + 1u;
+    const uint32_t threads = widest >= 1024u ? 1024u : (uint32_t)((widest + 63u) / 64u * 64u);
+    ldx::split_kernel<<<1, threads, 0, (hipStream_t)stream>>>(cross, n, min_snps, mx, best, prev, pre, suf, cuts, n_out);
+    LDX_HIP(hipGetLastError());
+    return LDX_OK;
+}

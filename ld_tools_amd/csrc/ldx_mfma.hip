@@ -354,8 +354,11 @@ __device__ __forceinline__ uint64_t dpp_half_sum(uint64_t x)
 // every pair's score term and a count to the bin of its distance in a per-workgroup LDS histogram, flushed once at the end.
 // kFgt (with kArea): the four-gamete band (ldx_ld_fgt_dev) -- the band's passes and K loop with fgt_epilogue, an integer
 // predicate on the counts (no r cell) reduced to the highest recombinant column of every row.
+// kCross (with kScoreW = 1): the one-sided LD-score band (ldx_ld_cross_dev) -- score_epilogue unchanged up to its two flushes,
+// which keep the halves apart: the row path's totals (pair (i, j), i > j, seen from i: its LEFT partners) go to sides[i][0],
+// the column path's (seen from j: its RIGHT partners) to sides[j][1].  No register beside kScoreW = 1's.
 template <bool kRaw, bool kN11, bool kArea = false, bool kFp4 = false, typename Cell = ldx_ld32, int kScoreW = 0,
-          bool kNbr = false, int kProdW = 0, bool kDecay = false, bool kFgt = false>
+          bool kNbr = false, int kProdW = 0, bool kDecay = false, bool kFgt = false, bool kCross = false>
 __global__ void __launch_bounds__(kMfmaThreads, kArea ? 2 : kWgPerCu)
 triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ fa, const double *__restrict__ fr,
                      const double *__restrict__ q, uint32_t n_snps, uint32_t n_slabs, uint32_t nchunks, double n,
@@ -433,6 +436,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
     constexpr bool kF32Tier = kFp4 && !kRaw && !kN11 && !kArea && !kR32;
     constexpr bool kScore = kScoreW != 0;   // LD scores (score_epilogue): r32 operands, integer sums instead of hits
     static_assert(!kScore || kArea, "the LD-score epilogue runs on the band");
+    static_assert(!kCross || kScoreW == 1, "the one-sided sums are the score band's column 0, rows and columns apart");
     static_assert(!kNbr || (kArea && !kScore), "the neighbour epilogue runs on the band");
     constexpr bool kProd = kProdW != 0;     // matrix-vector products (prod_epilogue): the score band with float32 weights
     static_assert(!kProd || (kArea && !kScore && !kNbr), "the matrix-vector epilogue runs on the band");
@@ -1584,7 +1588,8 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 for (uint32_t f = lane; f < kRows64 * st; f += 64u) {
                     const uint32_t i = row0 + f / st;
                     const uint64_t v = rows_lds[f];
-                    if (v != 0u && i < n_snps) atomicAdd(reinterpret_cast<unsigned long long *>(sums) + (size_t)i * st + f % st, (unsigned long long)v);
+                    const size_t word = kCross ? (size_t)i * 2u : (size_t)i * st + f % st;   // cross: sides[i][0], the left half
+                    if (v != 0u && i < n_snps) atomicAdd(reinterpret_cast<unsigned long long *>(sums) + word, (unsigned long long)v);
                 }
               }
             };
@@ -2159,7 +2164,8 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                     for (uint32_t w = 0; w < (uint32_t)kMfmaWaves; ++w)
                         if (pass + w >= seg_begin && pass + w < seg_end) v += score_cols[w * (kSlab * 9u) + f];   // active waves only
                     const uint32_t j = t * kSlab + f / st;
-                    if (v != 0u && j < n_snps) atomicAdd(reinterpret_cast<unsigned long long *>(sums) + (size_t)j * st + f % st, (unsigned long long)v);
+                    const size_t word = kCross ? (size_t)j * 2u + 1u : (size_t)j * st + f % st;   // cross: sides[j][1], the right half
+                    if (v != 0u && j < n_snps) atomicAdd(reinterpret_cast<unsigned long long *>(sums) + word, (unsigned long long)v);
                 }
                 if (tid == 0) tickets[parity] = next_ticket;
                 if (!(ablate & 16)) __builtin_amdgcn_s_setprio(0);
@@ -2634,10 +2640,24 @@ __global__ void score_init_kernel(const uint32_t *__restrict__ acnt, const uint3
     for (uint32_t c = 0; c < st; ++c) sums[(size_t)i * st + c] = ((m >> c) & 1u) ? t : 0u;
 }
 
+// The one-sided band (ldx_ld_cross_dev): the diagonal is not a pair, so both halves start at 0 -- the call needs no memset of
+// `sides` --; the query list as above.
+__global__ void cross_init_kernel(uint32_t n_snps, uint64_t *__restrict__ sides, uint32_t *__restrict__ qrows)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) {
+        qrows[0] = 0u;
+        qrows[1] = n_snps - 1u;
+    }
+    if (i >= n_snps) return;
+    sides[(size_t)i * 2u] = 0u;
+    sides[(size_t)i * 2u + 1u] = 0u;
+}
+
 // the band's workspace (area_mfma's layout) + 256 bytes: the two query rows and the plan kernel's (unused) hit counter
 size_t score_mfma_workspace_bytes(uint32_t n_snps) { return area_mfma_workspace_bytes(n_snps) + 256u; }
 
-template <bool kFp4, int kW>
+template <bool kFp4, int kW, bool kCross = false>
 static int launch_score(const void *alt, const double *fa, const double *fr, uint32_t n_snps, uint32_t n_hap, uint32_t T,
                         uint32_t nch, uint64_t units, size_t lds, const AreaArgs &aa, uint32_t *sched, hipStream_t s)
 {
@@ -2645,24 +2665,26 @@ static int launch_score(const void *alt, const double *fa, const double *fr, uin
     int dev = 0;
     LDX_HIP(hipGetDevice(&dev));
     if (dev < 0 || dev >= 64 || !((opted.load(std::memory_order_relaxed) >> dev) & 1u)) {
-        LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, kW>,
+        LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, kW, false, 0, false, false, kCross>,
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         if (dev >= 0 && dev < 64) opted.fetch_or(1ull << dev, std::memory_order_relaxed);
     }
-    triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, kW><<<(uint32_t)device_cus() * 2u, kMfmaThreads, lds, s>>>(
+    triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, kW, false, 0, false, false, kCross><<<(uint32_t)device_cus() * 2u, kMfmaThreads, lds, s>>>(
         (const uint4 *)alt, fa, fr, nullptr, n_snps, T, nch, (double)n_hap, 1.0 / (double)n_hap, 0, units * 8u,
         (ldx_ld32 *)nullptr, nullptr, nullptr, 0u, 0u, 0u, sched, 0, nullptr, aa);
     LDX_HIP(hipGetLastError());
     return LDX_OK;
 }
 
+// `cross`: the one-sided band (ldx_ld_cross_dev) -- `sums` is then sides [n_snps][2], zeroed here, no annotation
 int score_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
                uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, const uint8_t *annot,
-               uint32_t n_annot, bool fp4, uint64_t *sums, void *workspace, hipStream_t s)
+               uint32_t n_annot, bool fp4, uint64_t *sums, void *workspace, hipStream_t s, bool cross = false,
+               const char *who = "ldx_ld_score_dev")
 {
     const uint32_t T = n_slabs(n_snps), nch = n_chunks(n_hap);
     if ((uint64_t)T * nch * kSlab * 16u >= (1ull << 32)) {   // the K loop addresses the plane with 32-bit lane offsets
-        set_error("ldx_ld_score_dev: a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", n_snps, n_hap);
+        set_error("%s: a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", who, n_snps, n_hap);
         return LDX_E_UNSUPPORTED;
     }
     // the band's buffers, carved as in area_mfma (its query mask stays unused)
@@ -2682,7 +2704,8 @@ int score_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, cons
     uint32_t *qrows = (uint32_t *)w;                               // [2]
     unsigned long long *n_hits = (unsigned long long *)(w + 8);   // the plan kernel zeroes it; nothing reads it
     const uint32_t st = 1u + n_annot;
-    score_init_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(acnt, rcnt, n_annot ? annot : nullptr, st, n_snps, n_hap, sums, qrows);
+    if (cross) cross_init_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(n_snps, sums, qrows);
+    else score_init_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(acnt, rcnt, n_annot ? annot : nullptr, st, n_snps, n_hap, sums, qrows);
     LDX_HIP(hipGetLastError());
     if (n_snps < 2) return LDX_OK;   // no pairs
     // the plan keeps, per j-tile, the rows with pos <= pos(last column) + window: every pair with pos_i - pos_j <= window
@@ -2704,6 +2727,9 @@ int score_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, cons
     aa.measure = (int)n_annot;                 // score: K
     const uint64_t units = ldx_triangle_units(n_snps) / 8u;   // 64-row units of the full triangle
     const size_t lds = mfma_lds_bytes(kRows64, false, false) + (size_t)kMfmaWaves * kRows64 * 9u * sizeof(uint64_t);   // + the row tables
+    if (cross)
+        return fp4 ? launch_score<true, 1, true>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s)
+                   : launch_score<false, 1, true>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
     if (fp4)
         return n_annot ? launch_score<true, 3>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s)
                        : launch_score<true, 1>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
@@ -3244,6 +3270,36 @@ extern "C" int ldx_ld_score_dev(const void *alt, const uint32_t *acnt, const uin
     const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles: keep pos + window exact
     return ldx::score_mfma(alt, acnt, rcnt, fa, fr, n_snps, n_hap, positions, window < wmax ? window : wmax, annot, n_annot,
                            path != LDX_PATH_MFMA, sums, workspace, (hipStream_t)stream);
+}
+
+extern "C" size_t ldx_ld_cross_workspace_bytes(uint32_t n_snps, uint32_t n_hap)
+{
+    (void)n_hap;   // (the layout depends on the SNP count alone)
+    return ldx::score_mfma_workspace_bytes(n_snps ? n_snps : 1u);
+}
+
+extern "C" int ldx_ld_cross_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
+                                uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, int path,
+                                uint64_t *sides, uint64_t *cross, void *workspace, size_t workspace_bytes, void *stream)
+{
+    LDX_REQUIRE(alt && acnt && rcnt && fa && fr && positions && sides && cross && workspace, "null pointer");
+    LDX_REQUIRE(n_snps >= 1 && n_hap >= 1 && window >= 0, "bad shape");
+    LDX_REQUIRE(((uintptr_t)workspace & 255u) == 0, "workspace must be 256-byte aligned");
+    LDX_REQUIRE(workspace_bytes >= ldx::score_mfma_workspace_bytes(n_snps), "workspace too small (see ldx_ld_cross_workspace_bytes)");
+    LDX_REQUIRE(path == LDX_PATH_AUTO || path == LDX_PATH_POPCOUNT || path == LDX_PATH_MFMA || path == LDX_PATH_FP4, "unknown path");
+    if (n_hap > LDX_MAX_HAPS) {
+        ldx::set_error("ldx_ld_cross_dev: n_hap %u > LDX_MAX_HAPS %u", n_hap, LDX_MAX_HAPS);
+        return LDX_E_UNSUPPORTED;
+    }
+    if (path == LDX_PATH_POPCOUNT) {
+        ldx::set_error("ldx_ld_cross_dev: the cross-LD profile runs on the matrix-pipe band (LDX_PATH_FP4 / LDX_PATH_MFMA), not on the popcount kernels");
+        return LDX_E_UNSUPPORTED;
+    }
+    const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles: keep pos + window exact
+    const int rc = ldx::score_mfma(alt, acnt, rcnt, fa, fr, n_snps, n_hap, positions, window < wmax ? window : wmax, nullptr, 0u,
+                                   path != LDX_PATH_MFMA, sides, workspace, (hipStream_t)stream, true, "ldx_ld_cross_dev");
+    if (rc != LDX_OK) return rc;
+    return ldx_ld_cross_scan_dev(sides, n_snps, cross, stream);   // the prefix sum of the one-sided scores (ldx_area.hip)
 }
 
 // ---- peak-rate probe for the matrix pipe: back-to-back int8 MFMAs on 8 independent accumulators,

@@ -16,6 +16,7 @@ from .ingest import RaggedGenotypesError, codes_matrix, find_record, sample_geno
 from .ldscore import LDScoreTable, ld_scores, write_ldscore  # noqa: F401
 from .rmatrix import RMatrix, r_matrix, write_r_matrix  # noqa: F401
 from .prune import PruneTable, prune, write_prune  # noqa: F401
+from .regions import write_regions  # noqa: F401
 from .lite import DifChrsError, NotInIntgenConvDbError, NotRsIdError, check_rs_id, ld_lite_table  # noqa: F401
 from .triangle import (TriangleMatrix, create_matrix, stream_triangle_table, triangle_matrix,  # noqa: F401
                        write_triangle_table)

@@ -5,6 +5,7 @@
     ld_score(panel, positions, ...)         LD scores: windowed sums of r^2 per SNP (LDSC's l2), optionally per category
     ld_matvec(panel, x, positions, ...)     R x (or R^2 x) over the window for up to 8 vectors, without the matrix
     ld_ridge(panel, z, positions, ...)      (R + lam I) beta = z by conjugate gradients on ld_matvec
+    ld_cross / ld_regions                   the cross-LD profile of the band and the LD-independent regions cut from it
     ld_neighbors(panel, positions, ...)     per-SNP lists of the SNPs in the window with r^2 above a threshold
     ld_clump / ld_prune                     greedy clumping (PLINK --clump) and priority pruning on those lists
     pair_counts(panel_i, panel_j)           <- calc_ld.py:32           (bit-exact n11 block)
@@ -682,7 +683,7 @@ def _band_positions(panel: PackedPanel, positions, window_bp, window_snps, check
 
 def ld_score(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, window_snps: Optional[int] = None,
              annot=None, path: Optional[str] = None, workspace: Optional[torch.Tensor] = None,
-             check_positions: bool = True) -> LDScores:
+             check_positions: bool = True, regions=None) -> LDScores:
     """LD scores on the matrix-pipe band: for every SNP i, the sum of r^2 over the SNPs j with |pos_i - pos_j| <= window
     (i itself included), and with ``annot`` (bool / 0-1 [n, K], K <= 8) the same sum per category over the j that carry it
     (include/ldx.h, ldx_ld_score_dev).  r is the signed r of ld_triangle(fmt="r32"), bit for bit; the sums are exact
@@ -693,10 +694,14 @@ def ld_score(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, win
     reuse (one per launch that may be in flight); by default one is allocated per call.  The call is stream-ordered: the
     host reads nothing until ``.l2`` / ``.m`` are asked for (a device tensor of positions is checked on the device unless
     ``check_positions`` is False).
+
+    ``regions`` (an LDRegions or a region_of array; default None: no change): the sums run over the SNPs of i's own region
+    only -- the positions go through region_positions, and ``LDScores.m`` counts over the same shifted positions.
+    ``window_bp=None`` then means whole regions.
     """
     require_gpu()
     n = panel.n_snps
-    pos, pos_h, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_score")
+    pos, pos_h, window = _region_band(panel, positions, window_bp, window_snps, regions, check_positions, "ld_score")
     bits, k = (None, 0) if annot is None else pack_annot(annot, n)
     annot_d = torch.as_tensor(bits).to(panel.device) if k else None
     pcode = PATHS["fp4"] if path is None else PATHS[path]
@@ -1030,6 +1035,342 @@ def _blocks_launch(left, pos, keep_d, n, window, block_of, n_out) -> None:
                                 n_out.data_ptr(), _stream_ptr()), "ldx_ld_blocks_dev")
 
 
+# --------------------------------------------------------------------------- LD-independent regions
+SPLIT_COST_SHIFT = 16            # cost[k] = cross[k] >> 16: units of 2^-16 r^2 (include/ldx.h, ldx_ld_split_dev)
+SPLIT_SAT = (1 << 64) - 2        # sums of costs saturate here; a total that reaches it counts as wrapped
+SPLIT_FLAGS = {1: "no cut set gives every region min_snps .. max_snps SNPs", 2: "the total cost reached 2^64 - 2"}
+REGION_POS_MAX = 1 << 62         # region_positions refuses shifted positions from here on
+
+
+def cross_host(r, positions, window: int, live=None) -> Tuple[np.ndarray, np.ndarray]:
+    """Host mirror of ldx_ld_cross_dev over an r32 square (TriangleResult.r_matrix()): (sides uint64 [n, 2], cross uint64
+    [n + 1]).  Pair i > j with pos_i - pos_j <= window (both SNPs ``live`` if given: a degenerate cell's term is 0 anyway)
+    adds score_terms of its cell to sides[i][0] and sides[j][1]; cross is the prefix sum of right - left modulo 2^64."""
+    r = np.asarray(r, dtype=np.float32)
+    n = r.shape[0]
+    pos = np.asarray(positions, dtype=np.int64)
+    if pos.shape != (n,):
+        raise _lib.LdxError("positions must have one entry per SNP")
+    window = min(int(window), DECAY_WINDOW_MAX)
+    rows, cols = np.tril_indices(n, -1)
+    sel = pos[rows] - pos[cols] <= window
+    if live is not None:
+        ok = np.asarray(live, dtype=bool)
+        sel &= ok[rows] & ok[cols]
+    rows, cols = rows[sel], cols[sel]
+    t = score_terms(r[rows, cols])
+    sides = np.zeros((n, 2), dtype=np.uint64)
+    np.add.at(sides[:, 0], rows, t)
+    np.add.at(sides[:, 1], cols, t)
+    cross = np.zeros(n + 1, dtype=np.uint64)
+    cross[1:] = np.cumsum(sides[:, 1] - sides[:, 0], dtype=np.uint64)   # (uint64 arithmetic wraps: modulo 2^64)
+    return sides, cross
+
+
+def cross_pairs(positions, window: int, live) -> np.ndarray:
+    """int64 [n + 1]: the pairs j < k <= i of ``live`` SNPs with pos_i - pos_j <= window, per cut k -- the number of terms
+    behind cross[k].  From window_bounds: a prefix sum of (right partners - left partners)."""
+    pos = np.asarray(positions, dtype=np.int64)
+    n = pos.shape[0]
+    lo, hi = window_bounds(pos, min(int(window), DECAY_WINDOW_MAX))
+    ok = np.asarray(live, dtype=bool)
+    pre = np.concatenate([[0], np.cumsum(ok.astype(np.int64))])
+    k = np.arange(n)
+    right = np.where(ok, pre[hi] - pre[k + 1], 0)
+    left = np.where(ok, pre[k] - pre[lo], 0)
+    return np.concatenate([[0], np.cumsum(right - left)]).astype(np.int64)
+
+
+def split_feasible(n: int, min_snps: int, max_snps: int) -> bool:
+    """Some m has m min_snps <= n <= m max_snps: n SNPs can be cut into regions of min_snps .. max_snps."""
+    m = -(-n // max_snps)
+    return m >= 1 and m * min_snps <= n
+
+
+def split_host(cross, min_snps: int, max_snps: int) -> Tuple[np.ndarray, int]:
+    """Host mirror of ldx_ld_split_dev's recurrence, a plain loop over the states: (cuts int64 ascending, total cost in
+    units of 2^-16 r^2).  best[k] = min over p in [max(0, k - max_snps), k - min_snps] of best[p], plus cross[k] >> 16 for
+    k < n; prev[k] the LARGEST p at the minimum; the cuts are the backtrack from n.  Raises LdxError when no cut set is
+    admissible or the total reaches 2^64 - 2 (where the kernel's sums saturate)."""
+    cross = np.asarray(cross, dtype=np.uint64)
+    n = cross.shape[0] - 1
+    min_snps, max_snps = int(min_snps), int(max_snps)
+    if n < 1 or not 1 <= min_snps <= max_snps:
+        raise _lib.LdxError("split_host needs n >= 1 and 1 <= min_snps <= max_snps")
+    cost = (cross >> np.uint64(SPLIT_COST_SHIFT)).astype(np.float64)   # < 2^48: exact; +inf marks an infeasible state
+    exact = [int(c) >> SPLIT_COST_SHIFT for c in cross.tolist()]
+    best = np.full(n + 1, np.inf)
+    total = [None] * (n + 1)        # the exact sums (Python integers) beside their float64 keys
+    prev = np.full(n + 1, -1, dtype=np.int64)
+    best[0], total[0] = 0.0, 0
+    fits = True                      # every sum so far is below 2^53: the float64 keys order the states exactly
+    for k in range(1, n + 1):
+        a, b = max(0, k - max_snps), k - min_snps
+        if b < 0:
+            continue
+        seg = best[a:b + 1]
+        if fits:
+            m = seg.min()
+            if not np.isfinite(m):
+                continue
+            p = b - int(np.argmin(seg[::-1]))            # the largest p at the minimum
+        else:
+            cand = [q for q in range(a, b + 1) if total[q] is not None]
+            if not cand:
+                continue
+            least = min(total[q] for q in cand)
+            p = max(q for q in cand if total[q] == least)
+        total[k] = total[p] + (exact[k] if k < n else 0)
+        best[k] = float(total[k])
+        prev[k] = p
+        fits = fits and total[k] < (1 << 53)
+    if total[n] is None:
+        raise _lib.LdxError(f"no cut set gives every region {min_snps} .. {max_snps} SNPs (n = {n})")
+    if total[n] >= SPLIT_SAT:
+        raise _lib.LdxError("the total cost of the cuts reached 2^64 - 2")
+    cuts = []
+    k = int(prev[n])
+    while k != 0:
+        cuts.append(k)
+        k = int(prev[k])
+    return np.asarray(cuts[::-1], dtype=np.int64), int(total[n])
+
+
+def region_positions(positions, region_of, window: Optional[int] = None) -> Tuple[np.ndarray, int]:
+    """Positions under which a band call sees only pairs of one region: (positions', window') with positions'_i =
+    positions_i + region_of_i (window + 1).  Distances inside a region are unchanged, any pair across a boundary is farther
+    than ``window`` apart, and the result is still non-decreasing.  ``region_of``: one integer per SNP, non-decreasing,
+    starting at 0.  ``window=None``: the largest region span (pos[last] - pos[first]), i.e. whole regions.  Raises LdxError
+    if the shifted positions would reach 2^62."""
+    pos = np.ascontiguousarray(np.asarray(positions, dtype=np.int64))
+    reg = np.asarray(region_of)
+    if reg.shape != pos.shape or pos.ndim != 1 or not (np.issubdtype(reg.dtype, np.integer) or reg.dtype == bool):
+        raise _lib.LdxError("region_of must hold one integer per SNP")
+    reg = reg.astype(np.int64)
+    if pos.size == 0:
+        raise _lib.LdxError("region_positions needs at least one SNP")
+    if reg[0] != 0 or bool((np.diff(reg) < 0).any()):
+        raise _lib.LdxError("region_of must be non-decreasing and start at 0")
+    if pos.size > 1 and bool((np.diff(pos) < 0).any()):
+        raise _lib.LdxError("positions must be non-decreasing (VCF order)")
+    if window is None:
+        first = np.concatenate([[True], reg[1:] != reg[:-1]])
+        last = np.concatenate([first[1:], [True]])
+        window = int((pos[last] - pos[first]).max())
+    window = int(window)
+    if window < 0:
+        raise _lib.LdxError("the window must be >= 0")
+    if int(pos[-1]) + int(reg[-1]) * (window + 1) >= REGION_POS_MAX or int(pos[0]) <= -REGION_POS_MAX:
+        raise _lib.LdxError("region_positions: the shifted positions would reach 2^62")
+    return pos + reg * np.int64(window + 1), window
+
+
+@dataclass
+class LDCross:
+    """One-sided LD scores and the cross-LD profile of one panel (ld_cross).  ``sides`` (uint64 [n, 2]: left, right) and
+    ``cross`` (uint64 [n + 1]) are the device tensors the call wrote, in units of 2^-32 r^2; the host arrays are fetched
+    when first asked for."""
+
+    sides: torch.Tensor
+    cross: torch.Tensor
+    positions: object
+    window: int
+    n_hap: int
+    panel: Optional[PackedPanel] = None
+    _host: Optional[tuple] = None
+    _pairs: Optional[np.ndarray] = None
+
+    def _fetch(self) -> tuple:
+        if self._host is None:
+            s = self.sides.cpu().numpy().astype(np.float64) / SCORE_SCALE
+            self._host = (s[:, 0].copy(), s[:, 1].copy(), self.cross.cpu().numpy().astype(np.float64) / SCORE_SCALE)
+        return self._host
+
+    @property
+    def left(self) -> np.ndarray:
+        """float64 [n]: the sum of r^2 over every SNP's in-window partners to its left (a one-sided LD score, self excluded)."""
+        return self._fetch()[0]
+
+    @property
+    def right(self) -> np.ndarray:
+        """float64 [n]: the same over the partners to its right."""
+        return self._fetch()[1]
+
+    @property
+    def cross_r2(self) -> np.ndarray:
+        """float64 [n + 1]: the sum of r^2 over the in-window pairs j < k <= i, per cut k."""
+        return self._fetch()[2]
+
+    @property
+    def live(self) -> np.ndarray:
+        return (self.panel.alt_counts().astype(np.int64) * self.panel.ref_counts().astype(np.int64)) > 0
+
+    @property
+    def pairs(self) -> np.ndarray:
+        """int64 [n + 1]: the in-window pairs of non-degenerate SNPs that straddle each cut (cross_pairs)."""
+        if self._pairs is None:
+            pos = self.positions.cpu().numpy() if isinstance(self.positions, torch.Tensor) else self.positions
+            self._pairs = cross_pairs(pos, self.window, self.live)
+        return self._pairs
+
+    @property
+    def mean_r2(self) -> np.ndarray:
+        """float64 [n + 1]: cross_r2 / pairs, NaN where no pair straddles the cut."""
+        c = self.pairs
+        return np.where(c > 0, self.cross_r2 / np.maximum(c, 1), np.nan)
+
+
+def _cross_launch(panel, pos, window, pcode, sides, cross, workspace) -> None:
+    check(lib.ldx_ld_cross_dev(panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), panel.fa.data_ptr(),
+                               panel.fr.data_ptr(), panel.n_snps, panel.n_hap, pos.data_ptr(), window, pcode,
+                               sides.data_ptr(), cross.data_ptr(), workspace.data_ptr(),
+                               workspace.numel() * workspace.element_size(), _stream_ptr()), "ldx_ld_cross_dev")
+
+
+def _split_launch(cross, n, min_snps, max_snps, cuts, n_out, workspace) -> None:
+    check(lib.ldx_ld_split_dev(cross.data_ptr(), n, min_snps, max_snps, cuts.data_ptr(), n_out.data_ptr(),
+                               workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr()),
+          "ldx_ld_split_dev")
+
+
+def ld_cross(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, window_snps: Optional[int] = None,
+             path: Optional[str] = None, workspace: Optional[torch.Tensor] = None, check_positions: bool = True) -> LDCross:
+    """The cross-LD profile on the matrix-pipe band (include/ldx.h, ldx_ld_cross_dev): ld_score's sweep with every SNP's
+    score kept in two halves -- the r^2 of its in-window partners to the left and to the right -- and their prefix sum
+    cross[k], the r^2 summed over the in-window pairs j < k <= i: the LD a region boundary before SNP k would cut.  r is
+    the signed r of ld_triangle(fmt="r32"), bit for bit; the sums are exact integer sums of rint(2^32 r^2): reproducible
+    run to run and identical on both paths.
+
+    Positions, window, ``path`` and ``workspace`` (ldx_ld_cross_workspace_bytes() bytes) as for ld_score.  The call is
+    stream-ordered: the host reads nothing until a result property is asked for."""
+    require_gpu()
+    n = panel.n_snps
+    pos, pos_h, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_cross")
+    pcode = PATHS["fp4"] if path is None else PATHS[path]
+    need = lib.ldx_ld_cross_workspace_bytes(n, panel.n_hap)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=panel.device)
+    elif workspace.numel() * workspace.element_size() < need:
+        raise _lib.LdxError(f"workspace too small: {need} bytes needed")
+    sides = torch.empty((n, 2), dtype=torch.uint64, device=panel.device)
+    cross = torch.empty(n + 1, dtype=torch.uint64, device=panel.device)
+    _cross_launch(panel, pos, window, pcode, sides, cross, workspace)
+    res = LDCross(sides, cross, pos if pos_h is None else pos_h, window, panel.n_hap, panel)
+    res._keep = (pos, workspace)   # alive until the launch is done
+    return res
+
+
+@dataclass
+class LDRegions:
+    """Approximately LD-independent regions of one panel (ld_regions): the cuts of minimum total cross-LD with every region
+    min_snps .. max_snps SNPs long.  ``cuts`` (int64, ascending): a cut c is a boundary before SNP c."""
+
+    cuts: np.ndarray
+    n_snps: int
+    positions: np.ndarray
+    window: int
+    min_snps: int
+    max_snps: int
+    cross: Optional[LDCross] = None
+    cuts_dev: Optional[torch.Tensor] = None
+
+    @property
+    def n_regions(self) -> int:
+        return int(self.cuts.size) + 1
+
+    @property
+    def starts(self) -> np.ndarray:
+        """int64 [n_regions]: the first SNP of every region."""
+        return np.concatenate([[0], self.cuts]).astype(np.int64)
+
+    @property
+    def ends(self) -> np.ndarray:
+        """int64 [n_regions]: the last SNP of every region (inclusive)."""
+        return np.concatenate([self.cuts - 1, [self.n_snps - 1]]).astype(np.int64)
+
+    @property
+    def sizes(self) -> np.ndarray:
+        return self.ends - self.starts + 1
+
+    @property
+    def region_of(self) -> np.ndarray:
+        """int64 [n]: the 0-based region of every SNP."""
+        return np.repeat(np.arange(self.n_regions, dtype=np.int64), self.sizes)
+
+    @property
+    def spans_bp(self) -> np.ndarray:
+        """int64 [n_regions]: pos[end] - pos[start] of every region."""
+        return self.positions[self.ends] - self.positions[self.starts]
+
+    @property
+    def cross_at_cuts(self) -> np.ndarray:
+        """float64 [n_regions - 1]: the r^2 that crosses each cut (LDCross.cross_r2 at the cuts)."""
+        return self.cross.cross_r2[self.cuts]
+
+    @property
+    def total_cross(self) -> float:
+        return float(self.cross_at_cuts.sum())
+
+
+def ld_regions(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, window_snps: Optional[int] = None,
+               min_snps: int = 100, max_snps: int = 10_000, path: Optional[str] = None) -> LDRegions:
+    """Split a panel into approximately LD-independent regions (include/ldx.h, ldx_ld_cross_dev + ldx_ld_split_dev): the cut
+    set that minimises the sum over its cuts of the in-window r^2 crossing each one, every region holding min_snps ..
+    max_snps SNPs -- the objective of ldetect (Berisa & Pickrell 2016) and bigsnpr's snp_ldsplit with additive cuts.  Costs
+    are compared as integers (cross >> 16, units of 2^-16 r^2) and ties go to the later cut, so the result is reproducible
+    and equal to split_host over the profile.  Both kernels run back to back on the stream; the cuts are read at the end.
+
+    Raises LdxError before any launch when no m has m min_snps <= n <= m max_snps, naming the nearest admissible
+    max_snps."""
+    require_gpu()
+    n = panel.n_snps
+    min_snps, max_snps = int(min_snps), int(max_snps)
+    if not 1 <= min_snps <= max_snps:
+        raise _lib.LdxError(f"need 1 <= min_snps <= max_snps (got {min_snps}, {max_snps})")
+    if not split_feasible(n, min_snps, max_snps):
+        if n < min_snps:
+            raise _lib.LdxError(f"{n} SNPs cannot form a region of min_snps = {min_snps}: no max_snps is admissible")
+        raise _lib.LdxError(f"{n} SNPs cannot be cut into regions of {min_snps} .. {max_snps} SNPs: the nearest admissible "
+                            f"max_snps is {-(-n // (n // min_snps))}")
+    cr = ld_cross(panel, positions, window_bp, window_snps, path)
+    cuts = torch.empty(max(1, n // min_snps), dtype=torch.int32, device=panel.device)
+    n_out = torch.empty(2, dtype=torch.int32, device=panel.device)
+    ws = torch.empty(lib.ldx_ld_split_workspace_bytes(n), dtype=torch.uint8, device=panel.device)
+    _split_launch(cr.cross, n, min_snps, min(max_snps, 0xFFFFFFFF), cuts, n_out, ws)
+    count, flag = (int(v) for v in n_out.cpu().numpy().view(np.uint32))
+    if flag:
+        raise _lib.LdxError(f"ldx_ld_split_dev: {SPLIT_FLAGS.get(flag, flag)}")
+    pos = cr.positions.cpu().numpy() if isinstance(cr.positions, torch.Tensor) else cr.positions
+    return LDRegions(cuts[:count].cpu().numpy().view(np.uint32).astype(np.int64), n, np.asarray(pos, dtype=np.int64),
+                     cr.window, min_snps, max_snps, cr, cuts)
+
+
+def _region_band(panel: PackedPanel, positions, window_bp, window_snps, regions, check_positions: bool, what: str):
+    """_band_positions, through region_positions when ``regions`` (an LDRegions or a region_of array) is given: the band then
+    sees the pairs inside a region only.  ``window_bp=None`` (whole regions) needs ``regions``.  With ``regions`` the
+    positions are read on the host."""
+    if regions is None:
+        if window_bp is None and window_snps is None:
+            raise _lib.LdxError(f"{what}: window_bp=None (whole regions) needs regions=")
+        return _band_positions(panel, positions, window_bp, window_snps, check_positions, what)
+    n = panel.n_snps
+    region_of = regions.region_of if isinstance(regions, LDRegions) else \
+        (regions.cpu().numpy() if isinstance(regions, torch.Tensor) else np.asarray(regions))
+    if window_snps is not None:
+        pos_h, window = np.arange(n, dtype=np.int64), int(window_snps)
+    else:
+        if positions is None:
+            raise _lib.LdxError(f"{what} needs positions (or window_snps)")
+        pos_h = positions.cpu().numpy() if isinstance(positions, torch.Tensor) else np.asarray(positions)
+        window = None if window_bp is None else int(window_bp)
+    if pos_h.shape != (n,):
+        raise _lib.LdxError("positions must have one entry per SNP")
+    if window is not None and window < 0:
+        raise _lib.LdxError("the window must be >= 0")
+    shifted, window = region_positions(pos_h, region_of, window)
+    return _band_positions(panel, shifted, window, None, check_positions, what)
+
+
 # --------------------------------------------------------------------------- R x without the matrix, ridge solves
 PROD_SCALE_BITS = 40             # sums are integers in units of 2^-40 (include/ldx.h, ldx_ld_matvec_dev)
 PROD_CLAMP = float(1 << 22)      # |v x| beyond it is clamped before scaling (keeps the int64 conversion defined)
@@ -1136,7 +1477,7 @@ def _matvec_launch(panel: PackedPanel, pos: torch.Tensor, window: int, x32: torc
 
 def ld_matvec(panel: PackedPanel, x, positions=None, window_bp: int = 1_000_000, window_snps: Optional[int] = None,
               power: int = 1, path: str = "auto", workspace: Optional[torch.Tensor] = None, check_positions: bool = True,
-              check_finite: bool = True) -> LDProduct:
+              check_finite: bool = True, regions=None) -> LDProduct:
     """y = R_w x on the matrix-pipe band, without the matrix (include/ldx.h, ldx_ld_matvec_dev): for every SNP i the sum of
     r_ij x_j over the SNPs j with |pos_i - pos_j| <= window (i included, r_ii = r_matrix()'s diagonal), r the signed r of
     ld_triangle(fmt="r32") bit for bit; ``power=2`` sums r^2 x_j instead (r^2 one float32 multiply) -- the LD score of a
@@ -1148,9 +1489,13 @@ def ld_matvec(panel: PackedPanel, x, positions=None, window_bp: int = 1_000_000,
     Positions and window as for ld_score.  ``path``: 'auto' / 'fp4' (the FP4 band) or 'mfma' (the int8 band: identical
     sums).  ``workspace``: a uint8 device tensor of ldx_ld_matvec_workspace_bytes() bytes to reuse (one per launch that may
     be in flight).  The call is stream-ordered; with ``check_positions`` and ``check_finite`` off and device tensors in it
-    reads nothing on the host.  ``LDProduct.values()`` is the float64 result on the device."""
+    reads nothing on the host.  ``LDProduct.values()`` is the float64 result on the device.
+
+    ``regions`` (an LDRegions or a region_of array; default None: no change) restricts the product to the block-diagonal
+    R_B x: r_ij counts only for i and j of one region (region_positions; the positions are then read on the host), and
+    ``window_bp=None`` means whole regions."""
     require_gpu()
-    pos, _, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_matvec")
+    pos, _, window = _region_band(panel, positions, window_bp, window_snps, regions, check_positions, "ld_matvec")
     x32, e, squeeze = matvec_rhs(x, panel.n_snps, power, check_finite, panel.device)
     sums, workspace = _matvec_launch(panel, pos, window, x32, power, PATHS[path], workspace)
     res = LDProduct(sums, e, x32, window, power, squeeze)
@@ -1224,14 +1569,19 @@ def cg_solve(product, z: torch.Tensor, lam: float, tol: float = 1e-6, max_iter: 
 
 def ld_ridge(panel: PackedPanel, z, positions=None, window_bp: int = 1_000_000, window_snps: Optional[int] = None,
              lam: float = 1.0, tol: float = 1e-6, max_iter: int = 1000, path: str = "auto",
-             check_positions: bool = True) -> RidgeResult:
+             check_positions: bool = True, regions=None) -> RidgeResult:
     """Solve (R_w + lam I) beta = z by conjugate gradients on ld_matvec -- ridge / infinitesimal polygenic scores from
     summary statistics, R_w never formed.  ``z``: [n] or [n, k], k <= 8 columns solved side by side (one ld_matvec launch per
     iteration for all of them).  Before each product the search direction is replaced by the float32 vector the kernel
     really multiplies (LDProduct.x()), so the only product error left is the kernel's 2^-41 term rounding.  A windowed R
-    need not be positive definite: a column that meets p.Ap <= 0 is reported ``indefinite`` with NaN in beta (cg_solve)."""
+    need not be positive definite: a column that meets p.Ap <= 0 is reported ``indefinite`` with NaN in beta (cg_solve).
+
+    ``regions`` (an LDRegions or a region_of array; default None: no change) solves with the block-diagonal R_B instead
+    (ld_matvec's ``regions``).  With whole-region windows (``window_bp=None``) and no missing codes every block is the
+    correlation matrix of its SNPs' ALT indicators, up to the float32 rounding of the cells -- positive semidefinite --, so
+    ``indefinite`` cannot then come from window truncation."""
     dev = require_gpu()
-    pos, _, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_ridge")
+    pos, _, window = _region_band(panel, positions, window_bp, window_snps, regions, check_positions, "ld_ridge")
     zt = z if isinstance(z, torch.Tensor) else torch.as_tensor(np.asarray(z))
     squeeze = zt.ndim == 1
     matvec_rhs(zt, panel.n_snps)   # shape, column count, finiteness
