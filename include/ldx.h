@@ -169,6 +169,29 @@ int ldx_snp_stats_dev(const uint32_t *acnt, const uint32_t *rcnt, uint32_t n_snp
  * ld_area.py:188-189.  freq4: double [n_snps]. */
 int ldx_alt_freq4_dev(const uint32_t *acnt, uint32_t n_snps, uint32_t n_hap, double *freq4, void *stream);
 
+/* ---- sample and SNP subsets of a packed panel: another answer to get_sample_names.py without the codes ---- */
+/* dst(i, h) = src(snp_idx[i], hap_idx[h]) in both planes, i < n_snps_dst, h < n_hap_dst, written in the tiled layout of
+ * ldx_plane_bytes(n_snps_dst, n_hap_dst) -- what ldx_pack_codes_dev would make of codes[snp_idx][:, hap_idx], byte for byte,
+ * counts included, without the codes: a population or gender subset of a resident panel, a SNP subset, a haplotype
+ * bootstrap.  Every operator works on the result as on any packed panel (ldx_snp_stats_dev gives its fa / fr / q).
+ *   snp_idx: uint32 [n_snps_dst] source rows, or NULL = identity (then n_snps_dst == n_snps_src, else LDX_E_ARG);
+ *   hap_idx: uint32 [n_hap_dst] source haplotypes, or NULL = identity (then n_hap_dst == n_hap_src, else LDX_E_ARG);
+ *   indices come in ANY order and MAY REPEAT; n_hap_dst may exceed n_hap_src; n_hap_src and n_hap_dst both lie in
+ *   1 .. LDX_MAX_HAPS (else LDX_E_UNSUPPORTED).
+ * Out-of-range indices have a meaning (a _dev entry cannot report from inside the launch) and are never a stray read:
+ *   a haplotype index >= n_hap_src is a MISSING CALL: zero bits in both planes at that destination haplotype (in n only);
+ *   a SNP index >= n_snps_src is an ALL-MISSING ROW: zero bits in both planes, a = r = 0, a degenerate SNP.
+ * The call writes EVERY byte of both destination planes (pad haplotypes and pad rows as zero bits) and EVERY word of
+ * acnt_dst / rcnt_dst up to ldx_padded_snps(n_snps_dst) (pad rows 0): the caller zeroes nothing, and a launch into a used
+ * buffer gives the same bytes.  The counts are popcounts of the bits just assembled, stored by the workgroup that owns the
+ * rows: no atomics, no memset.
+ * Source and destination must not overlap (checked on the plane extents: LDX_E_ARG).  ref_src, ref_dst and rcnt_dst are NULL
+ * together (an ALT-only subset), as ref / rcnt of ldx_pack_codes_dev.  The source's pad bits must be zero, as every producer
+ * in this library leaves them.  The call only enqueues ONE kernel on `stream`: no allocation, no synchronisation, no state. */
+int ldx_panel_select_dev(const void *alt_src, const void *ref_src, uint32_t n_snps_src, uint32_t n_hap_src,
+                         const uint32_t *snp_idx, uint32_t n_snps_dst, const uint32_t *hap_idx, uint32_t n_hap_dst,
+                         void *alt_dst, void *ref_dst, uint32_t *acnt_dst, uint32_t *rcnt_dst, void *stream);
+
 /* ---- bit-exact contract: the alt/alt haplotype count of calc_ld.py:32 ------------------ */
 /* n11[i][j] = popcount(alt_i[row i] & alt_j[row j]) for all rows of panel I against all rows of
  * panel J (may be the same plane).  n11 is dense row-major uint32 [n_i][ld]. */

@@ -108,6 +108,7 @@ SIGNATURES = {
     "ldx_tile_plane_dev": (_int, [_vp, _u32, _u32, _sz, _vp, _vp, _vp]),
     "ldx_snp_stats_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
     "ldx_alt_freq4_dev": (_int, [_vp, _u32, _u32, _vp, _vp]),
+    "ldx_panel_select_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "ldx_pair_counts_dev": (_int, [_vp, _u32, _vp, _u32, _u32, _vp, _sz, _vp]),
     "ldx_ld_from_counts_dev": (_int, [_u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ldx_triangle_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _vp, _vp, _vp, _vp]),

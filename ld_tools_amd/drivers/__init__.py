@@ -12,8 +12,8 @@ from .area import AreaQueryResult, area_scan, get_inld_vars, write_area_file  # 
 from .blocks import write_blocks  # noqa: F401
 from .clump import ClumpTable, clump, write_clumped  # noqa: F401
 from .decay import write_decay  # noqa: F401
-from .ingest import RaggedGenotypesError, codes_matrix, find_record, sample_genotypes  # noqa: F401
-from .ldscore import LDScoreTable, ld_scores, write_ldscore  # noqa: F401
+from .ingest import RaggedGenotypesError, codes_matrix, find_record, haplotype_columns, sample_genotypes  # noqa: F401
+from .ldscore import LDScoreTable, ld_scores, ld_scores_by_group, write_ldscore  # noqa: F401
 from .rmatrix import RMatrix, r_matrix, write_r_matrix  # noqa: F401
 from .prune import PruneTable, prune, write_prune  # noqa: F401
 from .regions import write_regions  # noqa: F401

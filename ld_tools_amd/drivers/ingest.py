@@ -32,6 +32,15 @@ def sample_genotypes(rec, sample_names: Sequence[str]) -> list:
     return genotypes
 
 
+def haplotype_columns(carried_names: Sequence[str], chosen_names: Sequence[str], ploidy: int = 2) -> np.ndarray:
+    """Columns of the chosen samples in a panel packed from ``sample_genotypes(rec, carried_names)``: sample s of the
+    carried ones holds the columns ``ploidy * s + phase``.  Returned in carried (ascending column) order as int64, each
+    sample once; a chosen name that is not carried is skipped, as ``sample_genotypes`` skips it."""
+    chosen = set(chosen_names)
+    cols = [ploidy * s + phase for s, name in enumerate(carried_names) if name in chosen for phase in range(ploidy)]
+    return np.asarray(cols, dtype=np.int64)
+
+
 def find_record(vcf, chrom, pos: int, rs_id: str):
     """The record the reference works with for [pos, rs_id] (ld_triangle.py:160-165, ld_area.py:153-159):
     the first record of fetch(chrom, pos - 1, pos) whose id equals rs_id; None if there is none."""

@@ -11,14 +11,14 @@ from __future__ import annotations
 
 import gzip
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import Dict, List, Mapping, Optional, Sequence
 
 import numpy as np
 
 from .._lib import LdxError
 from ..ops import LDScores, ld_score
 from ..panel import PackedPanel
-from .ingest import RaggedGenotypesError, codes_matrix
+from .ingest import RaggedGenotypesError, codes_matrix, haplotype_columns
 from .triangle import fetch_variants
 
 
@@ -45,17 +45,14 @@ class LDScoreTable:
         return v[:, 1:] if self.annot is not None else v[:, :1]
 
 
-def ld_scores(vcf, chrom, chrom_rows: Sequence[Sequence], sample_names: Sequence[str], window_bp: int = 1_000_000,
-              annot=None, annot_names: Optional[Sequence[str]] = None, adjust: bool = True) -> LDScoreTable:
-    """LD scores of one chromosome's variants, from the inputs of ``r_matrix`` (VCF rows [pos, rsID]; each record fetched
-    once).  ``annot``: bool / 0-1 [len(chrom_rows), K], K <= 8, one row per input row; ``annot_names``: K column names
-    (default A0, A1, ...).  ``adjust``: write LDSC's unbiased r^2 (LDScores.adjusted) rather than r^2.  Mixed-ploidy panels
-    (genotype lists of different lengths) are out of scope: LdxError."""
+def _fetch_panel(what, vcf, chrom, chrom_rows, sample_names, annot, annot_names):
+    """One fetch_variants pass and one packed panel: (cv, kept variant indices, annot rows of the kept variants or None,
+    column names, panel)."""
     order = sorted(range(len(chrom_rows)), key=lambda k: chrom_rows[k][0])   # fetch_variants' stable sort
     cv = fetch_variants(vcf, chrom, chrom_rows, sample_names)
     keep = [k for k, rec in enumerate(cv.recs) if rec is not None]
     if not keep:
-        raise LdxError(f"ld_scores: no variant of chromosome {chrom} has a matching record")
+        raise LdxError(f"{what}: no variant of chromosome {chrom} has a matching record")
     ann = None
     names: List[str] = []
     if annot is not None:
@@ -63,24 +60,68 @@ def ld_scores(vcf, chrom, chrom_rows: Sequence[Sequence], sample_names: Sequence
         if a.ndim == 1:
             a = a[:, None]
         if a.shape[0] != len(chrom_rows):
-            raise LdxError("ld_scores: annot needs one row per input row")
+            raise LdxError(f"{what}: annot needs one row per input row")
         if a.dtype != bool and not np.isin(a, (0, 1)).all():
-            raise LdxError("ld_scores: annot must be boolean or 0/1")
+            raise LdxError(f"{what}: annot must be boolean or 0/1")
         ann = a.astype(bool)[np.asarray(order, dtype=np.int64)][np.asarray(keep, dtype=np.int64)]
         names = list(annot_names) if annot_names is not None else [f"A{k}" for k in range(ann.shape[1])]
         if len(names) != ann.shape[1]:
-            raise LdxError("ld_scores: one name per annotation column")
+            raise LdxError(f"{what}: one name per annotation column")
     try:
         codes = codes_matrix([cv.genotypes[k] for k in keep])
     except ZeroDivisionError as exc:   # a record that carries none of the samples
-        raise LdxError(f"ld_scores: a variant of chromosome {chrom} has no genotype of the selected samples") from exc
+        raise LdxError(f"{what}: a variant of chromosome {chrom} has no genotype of the selected samples") from exc
     except RaggedGenotypesError as exc:
-        raise LdxError(f"ld_scores: mixed ploidy on chromosome {chrom} ({exc}); LD scores need one haplotype count") from exc
-    panel = PackedPanel.from_codes(codes)
+        raise LdxError(f"{what}: mixed ploidy on chromosome {chrom} ({exc}); LD scores need one haplotype count") from exc
+    return cv, keep, ann, names, PackedPanel.from_codes(codes)
+
+
+def ld_scores(vcf, chrom, chrom_rows: Sequence[Sequence], sample_names: Sequence[str], window_bp: int = 1_000_000,
+              annot=None, annot_names: Optional[Sequence[str]] = None, adjust: bool = True) -> LDScoreTable:
+    """LD scores of one chromosome's variants, from the inputs of ``r_matrix`` (VCF rows [pos, rsID]; each record fetched
+    once).  ``annot``: bool / 0-1 [len(chrom_rows), K], K <= 8, one row per input row; ``annot_names``: K column names
+    (default A0, A1, ...).  ``adjust``: write LDSC's unbiased r^2 (LDScores.adjusted) rather than r^2.  Mixed-ploidy panels
+    (genotype lists of different lengths) are out of scope: LdxError."""
+    cv, keep, ann, names, panel = _fetch_panel("ld_scores", vcf, chrom, chrom_rows, sample_names, annot, annot_names)
     poss = [cv.poss[k] for k in keep]
     res = ld_score(panel, np.asarray(poss, dtype=np.int64), window_bp=window_bp, annot=ann)
     fa = panel.alt_counts().astype(np.float64) / panel.n_hap
     return LDScoreTable(str(chrom), [cv.rs_ids[k] for k in keep], poss, fa, ann, names, res, adjust)
+
+
+def ld_scores_by_group(vcf, chrom, chrom_rows: Sequence[Sequence], groups: Mapping[str, Sequence[str]],
+                       window_bp: int = 1_000_000, annot=None, annot_names: Optional[Sequence[str]] = None,
+                       adjust: bool = True) -> Dict[str, LDScoreTable]:
+    """``ld_scores`` for several sample groups (label -> sample names: populations, genders) of one chromosome from ONE pass
+    over the VCF: the union of the groups is fetched and packed once, each group is then a haplotype subset of that panel
+    taken on the device (PackedPanel.select) and scored.  Every table equals ``ld_scores`` on its group alone.  The other
+    arguments are those of ``ld_scores``.  The samples must be diploid in every record (a panel whose haplotype count is not
+    twice the number of carried samples -- haploid or mixed-ploidy calls -- is an LdxError), and a group none of whose
+    samples is carried is one too."""
+    what = "ld_scores_by_group"
+    if not groups:
+        raise LdxError(f"{what}: no groups")
+    union = list(dict.fromkeys(name for members in groups.values() for name in members))
+    cv, keep, ann, names, panel = _fetch_panel(what, vcf, chrom, chrom_rows, union, annot, annot_names)
+    carried = [name for name in union if name in cv.recs[keep[0]].samples]
+    if any([name for name in union if name in cv.recs[k].samples] != carried for k in keep[1:]):
+        raise LdxError(f"{what}: the records of chromosome {chrom} do not all carry the same samples")
+    if panel.n_hap != 2 * len(carried):
+        raise LdxError(f"{what}: {panel.n_hap} haplotypes for {len(carried)} carried samples on chromosome {chrom}: "
+                       "haploid or mixed-ploidy calls; the groups' columns are only known for diploid samples")
+    poss = [cv.poss[k] for k in keep]
+    pos = np.asarray(poss, dtype=np.int64)
+    rs_ids = [cv.rs_ids[k] for k in keep]
+    tables: Dict[str, LDScoreTable] = {}
+    for label, members in groups.items():
+        cols = haplotype_columns(carried, members)
+        if cols.size == 0:
+            raise LdxError(f"{what}: no sample of group {label!r} is carried by the records of chromosome {chrom}")
+        sub = panel.select(haplotypes=cols)
+        res = ld_score(sub, pos, window_bp=window_bp, annot=ann)
+        fa = sub.alt_counts().astype(np.float64) / sub.n_hap
+        tables[label] = LDScoreTable(str(chrom), list(rs_ids), list(poss), fa, ann, list(names), res, adjust)
+    return tables
 
 
 def write_ldscore(base: str, table: LDScoreTable) -> List[str]:

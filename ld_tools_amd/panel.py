@@ -74,6 +74,30 @@ def encode_codes(genotypes) -> np.ndarray:
     return out
 
 
+def select_index(x, size: int, what: str) -> np.ndarray:
+    """A SNP or haplotype selection as uint32 source indices: a boolean mask of length ``size`` gives its set positions in
+    ascending order, an integer index list (numpy, list or torch) is kept in its order, repeats included.  Raises LdxError
+    for a mask of another length, a non-integer dtype, a negative value, a value >= size and an empty selection.  Pure numpy
+    (``what`` names the axis in the messages)."""
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    arr = np.asarray(x)
+    if arr.ndim != 1:
+        raise _lib.LdxError(f"select: {what} must be one-dimensional, got shape {arr.shape}")
+    if arr.dtype == bool:
+        if arr.size != size:
+            raise _lib.LdxError(f"select: the {what} mask has {arr.size} entries for {size}")
+        arr = np.flatnonzero(arr)
+    if arr.size == 0:
+        raise _lib.LdxError(f"select: no {what} selected")
+    if arr.dtype.kind not in "iu":
+        raise _lib.LdxError(f"select: {what} must be integer indices or a boolean mask, not {arr.dtype}")
+    lo, hi = int(arr.min()), int(arr.max())
+    if lo < 0 or hi >= size:
+        raise _lib.LdxError(f"select: {what} index {lo if lo < 0 else hi} outside 0..{size - 1}")
+    return np.ascontiguousarray(arr, dtype=np.uint32)
+
+
 @dataclass
 class PackedPanel:
     """Device-resident packed genotype panel (one chromosome / one sample selection)."""
@@ -132,7 +156,10 @@ class PackedPanel:
     def pack_from(self, codes: torch.Tensor) -> None:
         """(Re)pack this panel from a device int8 matrix of its shape, on the current stream."""
         s = _stream_ptr()
-        check(lib.ldx_pack_codes_dev(codes.data_ptr(), self.n_snps, self.n_hap, codes.stride(0),
+        # one row has no row stride to speak of: numpy and torch report whatever the view's history left (codes[[i]][:, cols]
+        # is a contiguous [1][n] matrix with stride 1), and the entry wants a leading dimension >= n_hap
+        ld = codes.stride(0) if self.n_snps > 1 else max(codes.stride(0), self.n_hap)
+        check(lib.ldx_pack_codes_dev(codes.data_ptr(), self.n_snps, self.n_hap, ld,
                                      self.alt.data_ptr(), self.ref.data_ptr(), self.acnt.data_ptr(),
                                      self.rcnt.data_ptr(), s), "ldx_pack_codes_dev")
         self.refresh_stats()
@@ -141,6 +168,53 @@ class PackedPanel:
         check(lib.ldx_snp_stats_dev(self.acnt.data_ptr(), self.rcnt.data_ptr(), self.n_snps, self.n_hap,
                                     self.fa.data_ptr(), self.fr.data_ptr(), self.q.data_ptr(), _stream_ptr()),
               "ldx_snp_stats_dev")
+
+    # ------------------------------------------------------------------ subsets
+    def select(self, snps=None, haplotypes=None, out: Optional["PackedPanel"] = None) -> "PackedPanel":
+        """The panel of the chosen SNPs and / or haplotypes of this one (include/ldx.h, ldx_panel_select_dev): row i,
+        haplotype h of the result is row snps[i], haplotype haplotypes[h] of this panel -- what ``from_codes`` makes of
+        ``codes[snps][:, haplotypes]``, byte for byte, straight from the bit planes on the current stream.  Each argument is
+        an integer index array (numpy, list or torch, host or device; any order, repeats allowed: a bootstrap) or a boolean
+        mask of the source length; None keeps the axis.  ``out``: a panel of the result's shape to write into (every byte of
+        it is written).  Indices are checked on the host first: out-of-range and negative ones raise LdxError."""
+        require_gpu()
+        if snps is None and haplotypes is None:
+            raise _lib.LdxError("select: give snps, haplotypes or both")
+        si = None if snps is None else select_index(snps, self.n_snps, "SNP")
+        hi = None if haplotypes is None else select_index(haplotypes, self.n_hap, "haplotype")
+        n_snps = self.n_snps if si is None else int(si.size)
+        n_hap = self.n_hap if hi is None else int(hi.size)
+        if n_hap > _lib.MAX_HAPS:
+            raise _lib.LdxError(f"select: {n_hap} haplotypes selected, more than {_lib.MAX_HAPS} (LDX_MAX_HAPS)")
+        if out is None:
+            dev = self.device
+            pb, npad = lib.ldx_plane_bytes(n_snps, n_hap), lib.ldx_padded_snps(n_snps)
+            e = lambda n, dt: torch.empty(n, dtype=dt, device=dev)  # noqa: E731  (the call writes every byte)
+            out = PackedPanel(n_snps, n_hap, e(pb, torch.uint8), e(pb, torch.uint8), e(npad, torch.int32),
+                              e(npad, torch.int32), e(npad, torch.float64), e(npad, torch.float64), e(npad, torch.float64))
+        elif out is self:
+            raise _lib.LdxError("select: out must not be the source panel")
+        elif (out.n_snps, out.n_hap) != (n_snps, n_hap) or out.device != self.device:
+            raise _lib.LdxError(f"select: out is a {out.n_snps} x {out.n_hap} panel on {out.device}, "
+                                f"the selection is {n_snps} x {n_hap} on {self.device}")
+        to_dev = lambda a: None if a is None else torch.from_numpy(a.view(np.int32)).to(self.device)  # noqa: E731
+        sd, hd = to_dev(si), to_dev(hi)
+        check(lib.ldx_panel_select_dev(self.alt.data_ptr(), self.ref.data_ptr(), self.n_snps, self.n_hap,
+                                       _ptr(sd), n_snps, _ptr(hd), n_hap, out.alt.data_ptr(), out.ref.data_ptr(),
+                                       out.acnt.data_ptr(), out.rcnt.data_ptr(), _stream_ptr()), "ldx_panel_select_dev")
+        out.refresh_stats()
+        return out
+
+    def split(self, labels) -> dict:
+        """``{label: the panel of that label's haplotypes, in source order}`` for one hashable label per haplotype (a
+        population or gender per haplotype: the reference's -e / -g choice, answered for every value at once)."""
+        labels = list(labels)
+        if len(labels) != self.n_hap:
+            raise _lib.LdxError(f"split: {len(labels)} labels for {self.n_hap} haplotypes")
+        columns: dict = {}
+        for h, label in enumerate(labels):
+            columns.setdefault(label, []).append(h)
+        return {label: self.select(haplotypes=np.asarray(cols, dtype=np.uint32)) for label, cols in columns.items()}
 
     # ------------------------------------------------------------------ geometry
     @property
