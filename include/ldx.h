@@ -581,6 +581,54 @@ int ldx_ld_select_dev(const ldx_hit *nbrs, const uint32_t *offsets, uint32_t n_s
                       const uint8_t *member_ok, uint32_t first_round, uint32_t n_rounds, uint8_t *state, uint32_t *owner,
                       uint32_t *undecided, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- genotype-dosage LD (unphased r): the r32 triangle, LD scores and neighbour lists over individuals ---- */
+/* The entries above correlate haplotypes (n = n_hap phased ALT indicators).  These correlate the ALT DOSAGE of individuals,
+ * which does not depend on phase: what PLINK --r2 / --indep-pairwise and ldsc.py --l2 compute.  Individual k owns haplotypes
+ * 2k and 2k + 1 of the panel (n_hap even, N = n_hap / 2), and
+ *     g_ik = number of code-1 alleles of individual k at SNP i  (0, 1 or 2)
+ *     a_i = sum_k g_ik  (= acnt[i])     hom_i = #{k : g_ik = 2}     Q_i = sum_k g_ik^2 = a_i + 2 hom_i
+ *     S_ij = sum_k g_ik g_jk            num = N S_ij - a_i a_j      v_i = N Q_i - a_i^2
+ *     r_ij = num / sqrt(v_i v_j)        degenerate (cell -0.0f) iff v_i v_j == 0
+ * -- all integers (below 2^28 for n_hap <= LDX_MAX_HAPS), so a cell is within 4 float32 ulps of the exact r, +0.0f exactly
+ * when num == 0, and -0.0f exactly on a degenerate pair.  v_i == 0 for a SNP without variance among the DOSAGES: no ALT
+ * allele, every allele ALT, and also every individual heterozygous (a_i r_i > 0 there: the haplotype entries call it live).
+ * Missing data: g counts code 1 ONLY.  Every other code (REF, missing, a second ALT allele) contributes 0, so a missing call
+ * acts as REF -- a documented imputation -- and a multi-allelic site gives the one-vs-rest dosage of its code-1 allele.
+ *
+ * ldx_dosage_stats_dev: from the tiled ALT plane and acnt (ldx_pack_codes_dev / ldx_tile_plane_dev) writes, per row of the
+ * padded panel (ldx_padded_snps; pad rows: zeros -- every byte is written, no memset needed),
+ *     hom[i]   uint32     popcount(w & (w >> 1) & 0x5555...) over the row's words
+ *     gstat[i] double[2]  {a_i, rs_i},  rs_i = v_i > 0 ? 1 / sqrt((double)v_i) : 0
+ * The cell is r32_cell(S, N, a_i, rs_i, a_j, rs_j) of the haplotype entries (num exact in fp64, then two products): the
+ * same epilogue with another per-SNP table and another count.  S comes from the FP4 matrix kernel at the haplotype rate (the
+ * B operand carries the individual's dosage); no other kernel counts it, so
+ *     n_hap odd = LDX_E_ARG;  path LDX_PATH_MFMA / LDX_PATH_POPCOUNT = LDX_E_UNSUPPORTED (LDX_PATH_AUTO = LDX_PATH_FP4);
+ *     n_hap > LDX_MAX_HAPS, or a bit plane of 4 GiB or more = LDX_E_UNSUPPORTED.
+ *
+ * ldx_triangle_dosage_dev: ldx_triangle_ex_dev(out_format = LDX_OUT_R32) with dosage cells -- same units, cell order,
+ * workspace (ldx_triangle_workspace_bytes, or NULL) and zero cells outside the triangle.
+ * ldx_triangle_r_block_dosage_dev: ldx_triangle_r_block_dev over such strips; the diagonal is +1.0f for v_i > 0, -0.0f
+ * otherwise.
+ * ldx_ld_score_dosage_dev: ldx_ld_score_dev over the dosage cells -- same window, annotation words, workspace
+ * (ldx_ld_score_workspace_bytes) and integer terms rint(2^32 c *f32 c); a SNP's own term is 2^32 for v_i > 0 and 0 otherwise.
+ * `sums` equal the host sum of those terms over the dosage r32 matrix, bit for bit, whatever the order of the launch.
+ * ldx_ld_neighbors_dosage_dev: ldx_ld_neighbors_dev over the dosage cells -- same records, slots, row_counts and workspace
+ * (ldx_ld_neighbors_workspace_bytes).
+ * All calls only enqueue work on `stream`. */
+int ldx_dosage_stats_dev(const void *alt, const uint32_t *acnt, uint32_t n_snps, uint32_t n_hap, uint32_t *hom, double *gstat,
+                         void *stream);
+int ldx_triangle_dosage_dev(const void *alt, const double *gstat, uint32_t n_snps, uint32_t n_hap, uint64_t unit_begin,
+                            uint64_t unit_end, int path, ldx_r32 *out, void *workspace, size_t workspace_bytes, void *stream);
+int ldx_triangle_r_block_dosage_dev(const ldx_r32 *strips, uint32_t n_snps, const double *gstat, uint32_t row_begin,
+                                    uint32_t row_end, uint32_t col_begin, uint32_t col_end, float *out, size_t ld_out,
+                                    void *stream);
+int ldx_ld_score_dosage_dev(const void *alt, const double *gstat, uint32_t n_snps, uint32_t n_hap, const int64_t *positions,
+                            int64_t window, const uint8_t *annot, uint32_t n_annot, int path, uint64_t *sums, void *workspace,
+                            size_t workspace_bytes, void *stream);
+int ldx_ld_neighbors_dosage_dev(const void *alt, const double *gstat, uint32_t n_snps, uint32_t n_hap, const int64_t *positions,
+                                int64_t window, float r2_bound, int path, ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits,
+                                uint32_t *row_counts, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- synthetic panels: deterministic, identical on host and device ------ */
 /* codes int8 [n_snps][ld_codes] receive global SNPs [snp_offset, snp_offset + n_snps) (a rank's
  * shard).  thresholds: per-SNP ALT probability * 2^64 (computed on the host, see

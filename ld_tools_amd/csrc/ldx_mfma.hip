@@ -138,6 +138,28 @@ __device__ __forceinline__ v4i expand32_b4(uint32_t w)
     return v4i{(int)((w << 2) & 0x44444444u), (int)(w & 0x22222222u), (int)((w) & 0x44444444u), (int)(t & 0x22222222u)};   // 2, 1, 2, 1
 }
 
+// Genotype dosage (kDosage; DESIGN.md, "Dosage LD"): the A operand stays the haplotype bit (0.5 / 1 / 0.5 / 1), the B operand
+// carries, at the place of haplotype h, the ALT dosage g in {0, 1, 2} of the INDIVIDUAL of h -- haplotypes 2k and 2k + 1, two
+// adjacent bits of one word -- times the factor that makes the product g: 2 g against A's 0.5 (E2M1 0100 = 2, 0110 = 4), g
+// against A's 1 (0010 = 1, 0100 = 2).  With s = w >> 1 the even bits of o = w | s, n = w & s, x = w ^ s say g >= 1, g == 2,
+// g == 1; every mask below picks a bit that comes from an even position, so o, n and x need no mask of their own.  The
+// accumulators then hold S = sum over individuals of g_i g_j exactly (every product <= 2, S <= 2 n_hap < 2^24).  18 VALU per
+// 32 haplotypes where expand32_b4 takes 6; MFMA count, A side and LDS image are the haplotype kernel's.
+__device__ __forceinline__ v4i expand32_b4_dosage(uint32_t w)
+{
+    const uint32_t s = w >> 1, o = w | s, n = w & s, x = w ^ s;
+    return v4i{(int)(((o << 2) & 0x44444444u) | ((n << 1) & 0x22222222u)),    // individual 2q:     2 g
+               (int)(((x << 1) & 0x22222222u) | ((n << 2) & 0x44444444u)),    //                      g
+               (int)((o & 0x44444444u) | ((n >> 1) & 0x22222222u)),           // individual 2q + 1: 2 g
+               (int)(((x >> 1) & 0x22222222u) | (n & 0x44444444u))};          //                      g
+}
+template <bool kDosage>
+__device__ __forceinline__ v4i expand_b_fp4(uint32_t w)
+{
+    if constexpr (kDosage) return expand32_b4_dosage(w);
+    else return expand32_b4(w);
+}
+
 // tuning-only build variants (python ld_tools_amd/build.py --out libldx_x.so -DLDX_AB_...; results are wrong)
 #ifdef LDX_AB_NOAEXP
 #define EXPAND_A(x) v4i{(int)(x), 1, 1, 1}
@@ -152,7 +174,7 @@ __device__ __forceinline__ v4i expand32_b4(uint32_t w)
 #ifdef LDX_AB_NOBWRITE   // no expansion and no LDS write of the j-tile image (what a pre-expanded, DMA-fed image would save)
 #define BWRITE(dst, x) asm volatile("" : : "v"(x))
 #else
-#define BWRITE(dst, x) dst = (kFp4 ? expand32_b4(x) : EXPAND_B(x))
+#define BWRITE(dst, x) dst = (kFp4 ? expand_b_fp4<kDosage>(x) : EXPAND_B(x))
 #endif
 
 // In-chunk stamps (build with -DLDX_CHUNK_STAMPS on top of -DLDX_TUNING): s_memtime at six points of ONE chunk
@@ -345,6 +367,9 @@ __device__ __forceinline__ uint64_t dpp_half_sum(uint64_t x)
 // kScoreW (with kArea): the LD-score band (ldx_ld_score_dev) -- the band's passes and K loop with score_epilogue instead of
 // the hit scan; kScoreW is the number of `sums` words one sweep of the accumulators reduces (1: column 0 only; 5: column 0
 // and the categories, in sweeps of three words -- four or five spill).
+// kDosage (FP4; the r32 triangle, the LD-score band and the neighbour band): genotype-dosage r -- the B image is
+// expand32_b4_dosage's, `fa` holds the per-SNP table gstat {a, 1 / sqrt(v)} of ldx_dosage_stats_dev in place of the
+// frequencies (`fr` is not read) and `n` is the number of individuals; the epilogues are the haplotype ones unchanged.
 // kNbr (with kArea): the neighbour-list band (ldx_ld_neighbors_dev) -- the band's passes and K loop with nbr_epilogue, which
 // appends every pair with r *f32 r >= a float32 bound in both orientations, instead of the rounded hit scan.
 // kProdW (with kArea): the matrix-vector band (ldx_ld_matvec_dev) -- the LD-score band with prod_epilogue, score_epilogue's
@@ -358,7 +383,7 @@ __device__ __forceinline__ uint64_t dpp_half_sum(uint64_t x)
 // which keep the halves apart: the row path's totals (pair (i, j), i > j, seen from i: its LEFT partners) go to sides[i][0],
 // the column path's (seen from j: its RIGHT partners) to sides[j][1].  No register beside kScoreW = 1's.
 template <bool kRaw, bool kN11, bool kArea = false, bool kFp4 = false, typename Cell = ldx_ld32, int kScoreW = 0,
-          bool kNbr = false, int kProdW = 0, bool kDecay = false, bool kFgt = false, bool kCross = false>
+          bool kNbr = false, int kProdW = 0, bool kDecay = false, bool kFgt = false, bool kCross = false, bool kDosage = false>
 __global__ void __launch_bounds__(kMfmaThreads, kArea ? 2 : kWgPerCu)
 triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ fa, const double *__restrict__ fr,
                      const double *__restrict__ q, uint32_t n_snps, uint32_t n_slabs, uint32_t nchunks, double n,
@@ -442,6 +467,17 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
     static_assert(!kProd || (kArea && !kScore && !kNbr), "the matrix-vector epilogue runs on the band");
     static_assert(!kDecay || (kArea && !kScore && !kNbr && !kProd), "the decay epilogue runs on the band");
     static_assert(!kFgt || (kArea && !kScore && !kNbr && !kProd && !kDecay), "the four-gamete epilogue runs on the band");
+    static_assert(!kDosage || (kFp4 && !kCross && ((kR32 && !kArea) || (kScore && !kProd) || kNbr)),
+                  "dosage r: the FP4 r32 triangle, the LD-score band and the neighbour band");
+    // the per-SNP {a, rs} of the r32 epilogues: r32_snp of the frequencies, or row x of the dosage table
+    auto snp_ars = [&](uint32_t x) {
+        if constexpr (kDosage) {
+            const double *const g = fa + 2u * (size_t)x;   // gstat[x] = {a, 1 / sqrt(v)} (pad rows: 0, 0)
+            return R32Snp{g[0], g[1]};
+        } else {
+            return r32_snp(fa[x], fr[x], n);
+        }
+    };
     constexpr bool kBandF32 = kFp4 && kArea && !kScore && !kNbr && !kProd && !kDecay && !kFgt;   // the band screens its steps in float32 first (area_epilogue)
     float *ctab32 = reinterpret_cast<float *>(tickets + 8);                 // [128][4]: F32Col
     float *rtab32 = ctab32 + kSlab * 4u + wave * (kRows64 * 4u);            // [64][4]: F32Row, private to the wave
@@ -730,13 +766,13 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             } else if constexpr (kScore || kNbr || kProd || kDecay) {   // LD scores / neighbours / products / decay: {a, 1 / sqrt(a r)} (r32_snp) and {position, annotation mask}
                 if (new_tile && tid < kSlab) {
                     const uint32_t j = t * kSlab + tid;
-                    const R32Snp c = r32_snp(fa[j], fr[j], n);
+                    const R32Snp c = snp_ars(j);
                     d2s *dst = reinterpret_cast<d2s *>(cstat + tid * kStat);
                     dst[0] = d2s{c.a, c.rs};
                     dst[1] = j < n_snps ? d2s{(double)aa.pos[j], (double)(aa.is_query ? aa.is_query[j] : (uint8_t)0)} : d2s{0.0, 0.0};
                 }
                 const uint32_t i = row0 + lane;
-                const R32Snp r = r32_snp(fa[i], fr[i], n);
+                const R32Snp r = snp_ars(i);
                 d2s *dst = reinterpret_cast<d2s *>(rstat + lane * kStat);
                 dst[0] = d2s{r.a, r.rs};
                 dst[1] = i < n_snps ? d2s{(double)aa.pos[i], (double)(aa.is_query ? aa.is_query[i] : (uint8_t)0)} : d2s{0.0, 0.0};
@@ -753,11 +789,11 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             } else if constexpr (kR32) {   // signed r: {a, 1 / sqrt(a r)} per SNP (ldx_common.h, r32_snp) in the first two slots
                 if (new_tile && tid < kSlab) {
                     const uint32_t j = t * kSlab + tid;
-                    const R32Snp c = r32_snp(fa[j], fr[j], n);
+                    const R32Snp c = snp_ars(j);
                     *reinterpret_cast<d2s *>(cstat + tid * kStat) = d2s{c.a, c.rs};
                 }
                 const uint32_t i = row0 + (MM == 1 ? l32 : lane);   // (a half-height unit's lanes 32-63 repeat rows 0-31)
-                const R32Snp r = r32_snp(fa[i], fr[i], n);
+                const R32Snp r = snp_ars(i);
                 if (lane < kStatRows) *reinterpret_cast<d2s *>(rstat + lane * kStat) = d2s{r.a, r.rs};
             } else if (!kRaw) {   // epilogue operands -> LDS (every wave is past its previous epilogue: barrier above)
                 if (new_tile && tid < kSlab) {
@@ -2255,7 +2291,8 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             if (sl < aa.hit_cap) aa.hits[sl].query = 0xFFFFFFFFu;
 }
 
-template <bool kRaw, bool kN11, bool kFp4, typename Cell>
+// kDosage: `fa` is the dosage table gstat, `fr` / `q` are unused, and the kernel's n is the number of individuals
+template <bool kRaw, bool kN11, bool kFp4, typename Cell, bool kDosage = false>
 static int launch_mfma(const void *alt, const double *fa, const double *fr, const double *q, uint32_t n_snps,
                        uint32_t n_hap, uint64_t unit_begin, uint64_t unit_end, Cell *out, ldx_ld64 *out_raw,
                        uint32_t *out_n11, uint32_t *sched, hipStream_t s)
@@ -2271,7 +2308,7 @@ static int launch_mfma(const void *alt, const double *fa, const double *fr, cons
         int dev = 0;
         LDX_HIP(hipGetDevice(&dev));
         if (dev < 0 || dev >= 64 || !((opted.load(std::memory_order_relaxed) >> dev) & 1u)) {
-            LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<kRaw, kN11, false, kFp4, Cell>,
+            LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<kRaw, kN11, false, kFp4, Cell, 0, false, 0, false, false, false, kDosage>,
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             if (dev >= 0 && dev < 64) opted.fetch_or(1ull << dev, std::memory_order_relaxed);
         }
@@ -2321,8 +2358,9 @@ static int launch_mfma(const void *alt, const double *fa, const double *fr, cons
         LDX_HIP(hipMemsetAsync(stamps, 0, stamp_words * 8, s));
     }
 #endif
-    triangle_mfma_kernel<kRaw, kN11, false, kFp4, Cell><<<(uint32_t)grid, kMfmaThreads, lds, s>>>(
-        (const uint4 *)alt, fa, fr, q, n_snps, n_slabs(n_snps), nch, (double)n_hap, 1.0 / (double)n_hap, unit_begin,
+    const double n_obs = kDosage ? (double)(n_hap / 2u) : (double)n_hap;
+    triangle_mfma_kernel<kRaw, kN11, false, kFp4, Cell, 0, false, 0, false, false, false, kDosage><<<(uint32_t)grid, kMfmaThreads, lds, s>>>(
+        (const uint4 *)alt, fa, fr, q, n_snps, n_slabs(n_snps), nch, n_obs, 1.0 / n_obs, unit_begin,
         unit_end, out, out_raw, out_n11, p_begin, p_end, n_short, sched, ablate, stamps, tri_args);
     LDX_HIP(hipGetLastError());
 #ifdef LDX_TUNING
@@ -2376,6 +2414,14 @@ int triangle_mfma(const void *alt, const double *fa, const double *fr, const dou
     if (out_n11) LDX_GO(false, true, ldx_ld32);
     LDX_GO(false, false, ldx_ld32);
 #undef LDX_GO
+}
+
+// the dosage r32 triangle (ldx_triangle_dosage_dev): the FP4 kernel only
+int triangle_dosage_mfma(const void *alt, const double *gstat, uint32_t n_snps, uint32_t n_hap, uint64_t unit_begin,
+                         uint64_t unit_end, ldx_r32 *out, void *workspace, hipStream_t s)
+{
+    return launch_mfma<false, false, true, ldx_r32, true>(alt, gstat, nullptr, nullptr, n_snps, n_hap, unit_begin, unit_end, out,
+                                                          nullptr, nullptr, (uint32_t *)workspace, s);
 }
 
 }  // namespace ldx
@@ -2657,7 +2703,7 @@ __global__ void cross_init_kernel(uint32_t n_snps, uint64_t *__restrict__ sides,
 // the band's workspace (area_mfma's layout) + 256 bytes: the two query rows and the plan kernel's (unused) hit counter
 size_t score_mfma_workspace_bytes(uint32_t n_snps) { return area_mfma_workspace_bytes(n_snps) + 256u; }
 
-template <bool kFp4, int kW, bool kCross = false>
+template <bool kFp4, int kW, bool kCross = false, bool kDosage = false>
 static int launch_score(const void *alt, const double *fa, const double *fr, uint32_t n_snps, uint32_t n_hap, uint32_t T,
                         uint32_t nch, uint64_t units, size_t lds, const AreaArgs &aa, uint32_t *sched, hipStream_t s)
 {
@@ -2665,22 +2711,39 @@ static int launch_score(const void *alt, const double *fa, const double *fr, uin
     int dev = 0;
     LDX_HIP(hipGetDevice(&dev));
     if (dev < 0 || dev >= 64 || !((opted.load(std::memory_order_relaxed) >> dev) & 1u)) {
-        LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, kW, false, 0, false, false, kCross>,
+        LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, kW, false, 0, false, false, kCross, kDosage>,
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         if (dev >= 0 && dev < 64) opted.fetch_or(1ull << dev, std::memory_order_relaxed);
     }
-    triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, kW, false, 0, false, false, kCross><<<(uint32_t)device_cus() * 2u, kMfmaThreads, lds, s>>>(
-        (const uint4 *)alt, fa, fr, nullptr, n_snps, T, nch, (double)n_hap, 1.0 / (double)n_hap, 0, units * 8u,
+    const double n_obs = kDosage ? (double)(n_hap / 2u) : (double)n_hap;   // dosage: `fa` is gstat, n the individuals
+    triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, kW, false, 0, false, false, kCross, kDosage><<<(uint32_t)device_cus() * 2u, kMfmaThreads, lds, s>>>(
+        (const uint4 *)alt, fa, fr, nullptr, n_snps, T, nch, n_obs, 1.0 / n_obs, 0, units * 8u,
         (ldx_ld32 *)nullptr, nullptr, nullptr, 0u, 0u, 0u, sched, 0, nullptr, aa);
     LDX_HIP(hipGetLastError());
     return LDX_OK;
 }
 
+// the dosage band's own terms: r_ii = +1.0f (term 2^32) for v_i > 0, -0.0f (term 0) otherwise -- gstat[i][1] = 1 / sqrt(v_i) or 0
+__global__ void score_init_dosage_kernel(const double *__restrict__ gstat, const uint8_t *__restrict__ annot, uint32_t st,
+                                         uint32_t n_snps, uint64_t *__restrict__ sums, uint32_t *__restrict__ qrows)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) {
+        qrows[0] = 0u;
+        qrows[1] = n_snps - 1u;
+    }
+    if (i >= n_snps) return;
+    const uint64_t t = score_term(gstat[2u * (size_t)i + 1u] > 0.0 ? 1.0f : -0.0f);
+    const uint32_t m = annot ? ((uint32_t)annot[i] << 1) | 1u : 1u;   // bit c selects word c
+    for (uint32_t c = 0; c < st; ++c) sums[(size_t)i * st + c] = ((m >> c) & 1u) ? t : 0u;
+}
+
 // `cross`: the one-sided band (ldx_ld_cross_dev) -- `sums` is then sides [n_snps][2], zeroed here, no annotation
+// `gstat` (ldx_ld_score_dosage_dev; FP4, not cross): the dosage table in place of acnt / rcnt / fa / fr
 int score_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
                uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, const uint8_t *annot,
                uint32_t n_annot, bool fp4, uint64_t *sums, void *workspace, hipStream_t s, bool cross = false,
-               const char *who = "ldx_ld_score_dev")
+               const char *who = "ldx_ld_score_dev", const double *gstat = nullptr)
 {
     const uint32_t T = n_slabs(n_snps), nch = n_chunks(n_hap);
     if ((uint64_t)T * nch * kSlab * 16u >= (1ull << 32)) {   // the K loop addresses the plane with 32-bit lane offsets
@@ -2705,6 +2768,7 @@ int score_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, cons
     unsigned long long *n_hits = (unsigned long long *)(w + 8);   // the plan kernel zeroes it; nothing reads it
     const uint32_t st = 1u + n_annot;
     if (cross) cross_init_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(n_snps, sums, qrows);
+    else if (gstat) score_init_dosage_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(gstat, n_annot ? annot : nullptr, st, n_snps, sums, qrows);
     else score_init_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(acnt, rcnt, n_annot ? annot : nullptr, st, n_snps, n_hap, sums, qrows);
     LDX_HIP(hipGetLastError());
     if (n_snps < 2) return LDX_OK;   // no pairs
@@ -2727,6 +2791,9 @@ int score_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, cons
     aa.measure = (int)n_annot;                 // score: K
     const uint64_t units = ldx_triangle_units(n_snps) / 8u;   // 64-row units of the full triangle
     const size_t lds = mfma_lds_bytes(kRows64, false, false) + (size_t)kMfmaWaves * kRows64 * 9u * sizeof(uint64_t);   // + the row tables
+    if (gstat)
+        return n_annot ? launch_score<true, 3, false, true>(alt, gstat, nullptr, n_snps, n_hap, T, nch, units, lds, aa, sched, s)
+                       : launch_score<true, 1, false, true>(alt, gstat, nullptr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
     if (cross)
         return fp4 ? launch_score<true, 1, true>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s)
                    : launch_score<false, 1, true>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
@@ -3038,7 +3105,7 @@ __global__ void nbr_init_kernel(uint32_t n_snps, uint32_t *__restrict__ qrows)
 // the band's workspace (area_mfma's layout) + 256 bytes: the two query rows
 size_t nbr_mfma_workspace_bytes(uint32_t n_snps) { return area_mfma_workspace_bytes(n_snps) + 256u; }
 
-template <bool kFp4>
+template <bool kFp4, bool kDosage = false>
 static int launch_nbr(const void *alt, const double *fa, const double *fr, uint32_t n_snps, uint32_t n_hap, uint32_t T,
                       uint32_t nch, uint64_t units, size_t lds, const AreaArgs &aa, uint32_t *sched, hipStream_t s)
 {
@@ -3046,12 +3113,13 @@ static int launch_nbr(const void *alt, const double *fa, const double *fr, uint3
     int dev = 0;
     LDX_HIP(hipGetDevice(&dev));
     if (dev < 0 || dev >= 64 || !((opted.load(std::memory_order_relaxed) >> dev) & 1u)) {
-        LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, true>,
+        LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, true, 0, false, false, false, kDosage>,
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         if (dev >= 0 && dev < 64) opted.fetch_or(1ull << dev, std::memory_order_relaxed);
     }
-    triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, true><<<(uint32_t)device_cus() * 2u, kMfmaThreads, lds, s>>>(
-        (const uint4 *)alt, fa, fr, nullptr, n_snps, T, nch, (double)n_hap, 1.0 / (double)n_hap, 0, units * 8u,
+    const double n_obs = kDosage ? (double)(n_hap / 2u) : (double)n_hap;   // dosage: `fa` is gstat, n the individuals
+    triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, true, 0, false, false, false, kDosage><<<(uint32_t)device_cus() * 2u, kMfmaThreads, lds, s>>>(
+        (const uint4 *)alt, fa, fr, nullptr, n_snps, T, nch, n_obs, 1.0 / n_obs, 0, units * 8u,
         (ldx_ld32 *)nullptr, nullptr, nullptr, 0u, 0u, 0u, sched, 0, nullptr, aa);
     LDX_HIP(hipGetLastError());
     return LDX_OK;
@@ -3059,11 +3127,11 @@ static int launch_nbr(const void *alt, const double *fa, const double *fr, uint3
 
 int nbr_mfma(const void *alt, const double *fa, const double *fr, uint32_t n_snps, uint32_t n_hap, const int64_t *positions,
              int64_t window, float r2_bound, bool fp4, ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits, uint32_t *row_counts,
-             void *workspace, hipStream_t s)
+             void *workspace, hipStream_t s, const char *who = "ldx_ld_neighbors_dev", const double *gstat = nullptr)
 {
     const uint32_t T = n_slabs(n_snps), nch = n_chunks(n_hap);
     if ((uint64_t)T * nch * kSlab * 16u >= (1ull << 32)) {   // the K loop addresses the plane with 32-bit lane offsets
-        set_error("ldx_ld_neighbors_dev: a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", n_snps, n_hap);
+        set_error("%s: a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", who, n_snps, n_hap);
         return LDX_E_UNSUPPORTED;
     }
     if (row_counts) LDX_HIP(hipMemsetAsync(row_counts, 0, ((size_t)n_snps + 1u) * 4u, s));
@@ -3109,6 +3177,7 @@ int nbr_mfma(const void *alt, const double *fa, const double *fr, uint32_t n_snp
     aa.k_thres = (double)r2_bound;   // neighbours: the float32 bound b on s = r *f32 r
     const uint64_t units = ldx_triangle_units(n_snps) / 8u;   // 64-row units of the full triangle
     const size_t lds = mfma_lds_bytes(kRows64, false, false);
+    if (gstat) return launch_nbr<true, true>(alt, gstat, nullptr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);   // (ldx_ld_neighbors_dosage_dev)
     if (fp4) return launch_nbr<true>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
     return launch_nbr<false>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
 }
@@ -3145,6 +3214,78 @@ extern "C" int ldx_ld_neighbors_dev(const void *alt, const uint32_t *acnt, const
     const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles: keep pos + window exact
     return ldx::nbr_mfma(alt, fa, fr, n_snps, n_hap, positions, window < wmax ? window : wmax, r2_bound, path != LDX_PATH_MFMA,
                          hits, hit_cap, n_hits, row_counts, workspace, (hipStream_t)stream);
+}
+
+// the dosage entries' shared argument rules: an even number of haplotypes within LDX_MAX_HAPS, the FP4 kernel only
+static int dosage_args_ok(const char *who, uint32_t n_hap, int path)
+{
+    if (n_hap % 2u != 0u) {
+        ldx::set_error("%s: n_hap %u is odd (dosage pairs haplotypes 2k and 2k + 1 into individuals)", who, n_hap);
+        return LDX_E_ARG;
+    }
+    if (n_hap > LDX_MAX_HAPS) {
+        ldx::set_error("%s: n_hap %u > LDX_MAX_HAPS %u", who, n_hap, LDX_MAX_HAPS);
+        return LDX_E_UNSUPPORTED;
+    }
+    if (path != LDX_PATH_AUTO && path != LDX_PATH_FP4) {
+        ldx::set_error("%s: genotype-dosage r runs on the FP4 matrix kernel only (LDX_PATH_AUTO / LDX_PATH_FP4)", who);
+        return LDX_E_UNSUPPORTED;
+    }
+    return LDX_OK;
+}
+
+extern "C" int ldx_ld_neighbors_dosage_dev(const void *alt, const double *gstat, uint32_t n_snps, uint32_t n_hap,
+                                           const int64_t *positions, int64_t window, float r2_bound, int path, ldx_hit *hits,
+                                           uint64_t hit_cap, uint64_t *n_hits, uint32_t *row_counts, void *workspace,
+                                           size_t workspace_bytes, void *stream)
+{
+    LDX_REQUIRE(alt && gstat && positions && n_hits && workspace, "null pointer");
+    LDX_REQUIRE(hits || hit_cap == 0, "hits is null but hit_cap > 0");
+    LDX_REQUIRE(n_snps >= 1 && n_hap >= 1 && window >= 0, "bad shape");
+    LDX_REQUIRE(r2_bound > 0.0f, "r2_bound must be > 0 (and not NaN)");
+    LDX_REQUIRE(hit_cap < (1ull << 32), "hit_cap must be < 2^32 (the finished CSR's offsets are uint32)");
+    LDX_REQUIRE(((uintptr_t)workspace & 255u) == 0, "workspace must be 256-byte aligned");
+    LDX_REQUIRE(workspace_bytes >= ldx::nbr_mfma_workspace_bytes(n_snps), "workspace too small (see ldx_ld_neighbors_workspace_bytes)");
+    LDX_REQUIRE(path == LDX_PATH_AUTO || path == LDX_PATH_POPCOUNT || path == LDX_PATH_MFMA || path == LDX_PATH_FP4, "unknown path");
+    if (const int rc = dosage_args_ok(__func__, n_hap, path)) return rc;
+    const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles: keep pos + window exact
+    return ldx::nbr_mfma(alt, nullptr, nullptr, n_snps, n_hap, positions, window < wmax ? window : wmax, r2_bound, true, hits,
+                         hit_cap, n_hits, row_counts, workspace, (hipStream_t)stream, __func__, gstat);
+}
+
+extern "C" int ldx_ld_score_dosage_dev(const void *alt, const double *gstat, uint32_t n_snps, uint32_t n_hap,
+                                       const int64_t *positions, int64_t window, const uint8_t *annot, uint32_t n_annot,
+                                       int path, uint64_t *sums, void *workspace, size_t workspace_bytes, void *stream)
+{
+    LDX_REQUIRE(alt && gstat && positions && sums && workspace, "null pointer");
+    LDX_REQUIRE(n_annot <= 8u, "at most 8 annotation categories");
+    LDX_REQUIRE(annot || n_annot == 0u, "annot is null but n_annot > 0");
+    LDX_REQUIRE(n_snps >= 1 && n_hap >= 1 && window >= 0, "bad shape");
+    LDX_REQUIRE(((uintptr_t)workspace & 255u) == 0, "workspace must be 256-byte aligned");
+    LDX_REQUIRE(workspace_bytes >= ldx::score_mfma_workspace_bytes(n_snps), "workspace too small (see ldx_ld_score_workspace_bytes)");
+    LDX_REQUIRE(path == LDX_PATH_AUTO || path == LDX_PATH_POPCOUNT || path == LDX_PATH_MFMA || path == LDX_PATH_FP4, "unknown path");
+    if (const int rc = dosage_args_ok(__func__, n_hap, path)) return rc;
+    const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles: keep pos + window exact
+    return ldx::score_mfma(alt, nullptr, nullptr, nullptr, nullptr, n_snps, n_hap, positions, window < wmax ? window : wmax, annot,
+                           n_annot, true, sums, workspace, (hipStream_t)stream, false, __func__, gstat);
+}
+
+extern "C" int ldx_triangle_dosage_dev(const void *alt, const double *gstat, uint32_t n_snps, uint32_t n_hap,
+                                       uint64_t unit_begin, uint64_t unit_end, int path, ldx_r32 *out, void *workspace,
+                                       size_t workspace_bytes, void *stream)
+{
+    LDX_REQUIRE(!workspace || workspace_bytes >= ldx::triangle_mfma_workspace_bytes(),
+                "workspace too small (see ldx_triangle_workspace_bytes)");
+    LDX_REQUIRE(!workspace || ((uintptr_t)workspace & 255u) == 0, "workspace must be 256-byte aligned");
+    LDX_REQUIRE(alt && gstat && out, "null pointer");
+    LDX_REQUIRE(path == LDX_PATH_AUTO || path == LDX_PATH_POPCOUNT || path == LDX_PATH_MFMA || path == LDX_PATH_FP4, "unknown path");
+    LDX_REQUIRE(n_snps >= 1 && n_hap >= 1, "bad shape");
+    if (const int rc = dosage_args_ok(__func__, n_hap, path)) return rc;
+    const uint64_t U = ldx_triangle_units(n_snps);
+    if (unit_end > U) unit_end = U;
+    if (unit_begin >= unit_end) return LDX_OK;
+    const int rc = ldx::triangle_dosage_mfma(alt, gstat, n_snps, n_hap, unit_begin, unit_end, out, workspace, (hipStream_t)stream);
+    return rc == ldx::kNoMatrixPath ? LDX_E_UNSUPPORTED : rc;   // a bit plane of 4 GiB or more (message set): no other kernel counts dosages
 }
 
 extern "C" size_t ldx_ld_matvec_workspace_bytes(uint32_t n_snps, uint32_t n_hap)

@@ -144,9 +144,52 @@ __global__ void alt_freq4_kernel(const uint32_t *__restrict__ acnt, uint32_t n_s
     if (i < n_snps) out[i] = round4_k((double)acnt[i] / n) / 1e4;
 }
 
+// Genotype-dosage statistics per SNP (ldx_dosage_stats_dev): one wavefront per row of the padded panel, a lane per 32-bit
+// word of the tiled ALT plane.  Haplotypes 2k and 2k + 1 -- individual k -- are bits 2k % 32 and 2k % 32 + 1 of one word, so
+// the individuals with both alleles ALT are the even bits of w & (w >> 1).  With a = acnt[i] (the sum of the dosages g),
+// Q = a + 2 hom (the sum of g^2) and N individuals, v = N Q - a^2 is N^2 times the dosage variance: an integer below 2^27.
+// gstat[i] = {a, 1 / sqrt(v)} (0 for v == 0) is what r32_cell takes per SNP (ldx_common.h); pad rows get zeros.
+__global__ void __launch_bounds__(256) dosage_stats_kernel(const uint32_t *__restrict__ tiled, const uint32_t *__restrict__ acnt,
+                                                           uint32_t n_snps, uint32_t n_pad, uint32_t n_ind, uint32_t nchunks,
+                                                           uint32_t *__restrict__ hom, double *__restrict__ gstat)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t row = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (row >= n_pad) return;   // wave-uniform
+    const uint32_t slab = row / kSlab, rin = row % kSlab;
+    uint32_t c = 0;
+    if (row < n_snps)
+        for (uint32_t w = lane; w < nchunks * 4u; w += 64u) {
+            const uint32_t v = tiled[(((size_t)slab * nchunks + (w >> 2)) * kSlab + rin) * 4u + (w & 3u)];
+            c += __builtin_popcount(v & (v >> 1) & 0x55555555u);
+        }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+    if (lane != 0) return;
+    const uint64_t a = row < n_snps ? acnt[row] : 0u;
+    const uint64_t nq = (uint64_t)n_ind * (a + 2u * (uint64_t)c), aa = a * a;
+    const double v = nq > aa ? (double)(nq - aa) : 0.0;   // (Cauchy-Schwarz: N Q >= a^2)
+    hom[row] = c;
+    gstat[2u * (size_t)row] = (double)a;
+    gstat[2u * (size_t)row + 1u] = v > 0.0 ? 1.0 / __builtin_sqrt(v) : 0.0;
+}
+
 }  // namespace ldx
 
 using namespace ldx;
+
+extern "C" int ldx_dosage_stats_dev(const void *alt, const uint32_t *acnt, uint32_t n_snps, uint32_t n_hap, uint32_t *hom,
+                                    double *gstat, void *stream)
+{
+    LDX_REQUIRE(alt && acnt && hom && gstat, "null pointer");
+    LDX_REQUIRE(n_snps > 0 && n_hap > 0, "bad shape");
+    LDX_REQUIRE(n_hap % 2u == 0u, "n_hap is odd (dosage pairs haplotypes 2k and 2k + 1 into individuals)");
+    const uint32_t npad = ldx_padded_snps(n_snps);
+    dosage_stats_kernel<<<npad / 4u, 256, 0, (hipStream_t)stream>>>((const uint32_t *)alt, acnt, n_snps, npad, n_hap / 2u,
+                                                                    n_chunks(n_hap), hom, gstat);
+    LDX_HIP(hipGetLastError());
+    return LDX_OK;
+}
 
 extern "C" int ldx_pack_codes_dev(const int8_t *codes, uint32_t n_snps, uint32_t n_hap, size_t ld_codes,
                                   void *alt, void *ref, uint32_t *acnt, uint32_t *rcnt, void *stream)

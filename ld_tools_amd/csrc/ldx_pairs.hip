@@ -359,7 +359,10 @@ __global__ void triangle_dense_kernel(const Cell *__restrict__ strips, uint32_t 
 // every strip cell is read once for its two places.  LDS rows are XOR-swizzled (column c of block row p at p * 128 +
 // (c ^ p)), so that the row-wise reads of the lower tile and the column-wise reads of the upper one are both free of bank
 // conflicts.  Tile (x, y) of the grid with x < y is left to the workgroup of (y, x) when that one exists.
+// kDosage (ldx_triangle_r_block_dosage_dev): the strips hold dosage r, `acnt` is the dosage table gstat (two doubles per SNP)
+// and the diagonal is +1.0f where gstat[i][1] = 1 / sqrt(v_i) is positive, -0.0f otherwise; `rcnt` and `n` are not read.
 constexpr uint32_t kRbThreads = 256;
+template <bool kDosage>
 __global__ void __launch_bounds__(kRbThreads)
 r_block_kernel(const float4 *__restrict__ strips, uint32_t n_slabs, const uint32_t *__restrict__ acnt,
                const uint32_t *__restrict__ rcnt, double n, uint32_t r0, uint32_t r1, uint32_t c0, uint32_t c1,
@@ -396,7 +399,8 @@ r_block_kernel(const float4 *__restrict__ strips, uint32_t n_slabs, const uint32
             if (i < r0 || i >= r1) continue;
             float v;
             if (i == j) {
-                v = r32_diag((double)acnt[i], (double)rcnt[i], n);
+                if constexpr (kDosage) v = reinterpret_cast<const double *>(acnt)[2u * (size_t)i + 1u] > 0.0 ? 1.0f : -0.0f;
+                else v = r32_diag((double)acnt[i], (double)rcnt[i], n);
             } else {
                 const uint32_t p = (i > j ? i : j) - hi * kSlab, q = (i > j ? j : i) - lo * kSlab;   // strip cell (max, min)
                 v = blk[p * kSlab + (q ^ p)];
@@ -669,9 +673,28 @@ extern "C" int ldx_triangle_r_block_dev(const ldx_r32 *strips, uint32_t n_snps, 
     if (row_begin == row_end || col_begin == col_end) return LDX_OK;
     const uint32_t tr0 = row_begin / kSlab, tr1 = (row_end + kSlab - 1u) / kSlab;
     const uint32_t tc0 = col_begin / kSlab, tc1 = (col_end + kSlab - 1u) / kSlab;
-    r_block_kernel<<<dim3(tc1 - tc0, tr1 - tr0), kRbThreads, 0, (hipStream_t)stream>>>(
+    r_block_kernel<false><<<dim3(tc1 - tc0, tr1 - tr0), kRbThreads, 0, (hipStream_t)stream>>>(
         (const float4 *)strips, ldx::n_slabs(n_snps), acnt, rcnt, (double)n_hap, row_begin, row_end, col_begin, col_end, tr0,
         tr1, tc0, tc1, out, ld_out);
+    LDX_HIP(hipGetLastError());
+    return LDX_OK;
+}
+
+extern "C" int ldx_triangle_r_block_dosage_dev(const ldx_r32 *strips, uint32_t n_snps, const double *gstat, uint32_t row_begin,
+                                               uint32_t row_end, uint32_t col_begin, uint32_t col_end, float *out,
+                                               size_t ld_out, void *stream)
+{
+    LDX_REQUIRE(strips && gstat && out, "null pointer");
+    LDX_REQUIRE(n_snps >= 1, "bad shape");
+    LDX_REQUIRE(row_begin <= row_end && row_end <= n_snps && col_begin <= col_end && col_end <= n_snps,
+                "block outside the matrix");
+    LDX_REQUIRE(ld_out >= col_end - col_begin, "ld_out smaller than the block's width");
+    if (row_begin == row_end || col_begin == col_end) return LDX_OK;
+    const uint32_t tr0 = row_begin / kSlab, tr1 = (row_end + kSlab - 1u) / kSlab;
+    const uint32_t tc0 = col_begin / kSlab, tc1 = (col_end + kSlab - 1u) / kSlab;
+    r_block_kernel<true><<<dim3(tc1 - tc0, tr1 - tr0), kRbThreads, 0, (hipStream_t)stream>>>(
+        (const float4 *)strips, ldx::n_slabs(n_snps), reinterpret_cast<const uint32_t *>(gstat), nullptr, 0.0, row_begin, row_end,
+        col_begin, col_end, tr0, tr1, tc0, tc1, out, ld_out);
     LDX_HIP(hipGetLastError());
     return LDX_OK;
 }

@@ -354,11 +354,15 @@ def gather_hits(query, oppos, ld32, group=None):
 
 
 def ld_area_sharded(panel, positions, queries=None, flank: int = 100000, measure: str = "r_square", thres: float = 0.8,
-                    group=None, gather: bool = True):
+                    group=None, gather: bool = True, dosage: bool = False):
     """ld_area over all ranks: every rank holds the full panel (all_gather_panel) and scans ITS range of the query list
     (query_partition); no data-path exchange during the scan.  With ``gather`` the hit lists are then all-gathered
     (gather_hits) and every rank returns the complete AreaHits, identical to the single-GPU ld_area; without it each
-    rank keeps its own hits (the writers of ld_area.py:261-292 are per query, so a rank can write its own files)."""
+    rank keeps its own hits (the writers of ld_area.py:261-292 are per query, so a rank can write its own files).
+    ``dosage`` is refused: the sharded scans have no genotype-dosage form (neither has ld_triangle's ``unit_range``)."""
+    if dosage:
+        from ._lib import LdxError
+        raise LdxError("ld_area_sharded: no genotype-dosage form (the multi-GPU operators compute haplotype LD only)")
     import numpy as np
     import torch.distributed as dist
 

@@ -3,9 +3,10 @@ inputs of drivers/ldscore.py plus one p-value per input row and runs ops.ld_clum
 then the greedy selection on the device).
 
 The rule is PLINK ``--clump``'s: the SNPs with p <= p1, most significant first, each one not yet in a clump becoming an
-index that takes every SNP not yet in a clump with p <= p2 and r^2 >= r2 within the window.  But r is the haplotype r of
-the ALT-allele indicators over the panel's haplotypes (include/ldx.h, LDX_OUT_R32), not PLINK's genotype-based estimate,
-so the file follows PLINK's layout while its values need not match PLINK's.
+index that takes every SNP not yet in a clump with p <= p2 and r^2 >= r2 within the window.  By default r is the haplotype
+r of the ALT-allele indicators over the panel's haplotypes (include/ldx.h, LDX_OUT_R32), not PLINK's genotype-based estimate,
+so the file follows PLINK's layout while its values need not match PLINK's; ``dosage=True`` takes the genotype correlation of
+the ALT dosages over the samples instead (ldx_ld_neighbors_dosage_dev; a missing call counts as REF), PLINK's r.
 """
 from __future__ import annotations
 
@@ -59,14 +60,15 @@ def chrom_panel(vcf, chrom, chrom_rows: Sequence[Sequence], sample_names: Sequen
 
 
 def clump(vcf, chrom, chrom_rows: Sequence[Sequence], sample_names: Sequence[str], pvalues: Sequence[float],
-          p1: float = 1e-4, p2: float = 1e-2, r2: float = 0.5, window_bp: int = 250_000) -> ClumpTable:
-    """Clumps of one chromosome's variants (VCF rows [pos, rsID], one p-value per input row)."""
+          p1: float = 1e-4, p2: float = 1e-2, r2: float = 0.5, window_bp: int = 250_000, dosage: bool = False) -> ClumpTable:
+    """Clumps of one chromosome's variants (VCF rows [pos, rsID], one p-value per input row).  ``dosage``: genotype-dosage
+    r (ops.ld_clump)."""
     p_in = np.asarray(pvalues, dtype=np.float64)
     if p_in.shape != (len(chrom_rows),):
         raise LdxError("clump: one p-value per input row is needed")
     panel, rows, rs_ids, poss = chrom_panel(vcf, chrom, chrom_rows, sample_names, "clump")
     p = p_in[rows]
-    res = ld_clump(panel, np.asarray(poss, dtype=np.int64), p, p1=p1, p2=p2, r2=r2, window_bp=window_bp)
+    res = ld_clump(panel, np.asarray(poss, dtype=np.int64), p, p1=p1, p2=p2, r2=r2, window_bp=window_bp, dosage=dosage)
     return ClumpTable(str(chrom), rs_ids, poss, p, res)
 
 

@@ -3,9 +3,12 @@
 stratified LDSC read.  Not a reference workflow: it takes the inputs of drivers/rmatrix.py and runs ops.ld_score on the
 matrix-pipe band (include/ldx.h, ldx_ld_score_dev).
 
-r is the haplotype-based correlation of the ALT-allele indicators with n = n_hap (include/ldx.h, LDX_OUT_R32), and the
-unbiased estimate (``adjust``) uses n_obs = n_hap.  ``ldsc.py --l2`` estimates r^2 from diploid dosages over the samples
-instead, so its values are close to these but not identical.
+Two modes.  By default r is the haplotype-based correlation of the ALT-allele indicators with n = n_hap (include/ldx.h,
+LDX_OUT_R32), and the unbiased estimate (``adjust``) uses n_obs = n_hap: the right r for a phased reference panel, close to
+``ldsc.py --l2``'s values but not identical.  With ``dosage=True`` r is the genotype correlation of the ALT dosages 0 / 1 / 2
+over the N = n_hap / 2 samples (include/ldx.h, ldx_ld_score_dosage_dev) -- phase-free, so it also suits unphased calls -- with
+n_obs = N and ``M_5_50`` from the dosage allele frequency a / (2 N): the quantities ``ldsc.py --l2`` computes.  LDSC has no
+missing genotypes; here a missing call would count as REF, so a panel with one is refused unless ``missing="ref"`` says so.
 """
 from __future__ import annotations
 
@@ -29,7 +32,7 @@ class LDScoreTable:
     chrom: str
     rs_ids: List[str]
     poss: List[int]
-    alt_freqs_exact: np.ndarray       # float64 a / n_hap per variant (the MAF filter of M_5_50)
+    alt_freqs_exact: np.ndarray       # float64 a / n_hap per variant (the MAF filter of M_5_50; dosage: a / (2 N), the same number)
     annot: Optional[np.ndarray]       # bool [n, K] in row order, or None
     annot_names: List[str]
     scores: LDScores
@@ -76,29 +79,55 @@ def _fetch_panel(what, vcf, chrom, chrom_rows, sample_names, annot, annot_names)
     return cv, keep, ann, names, PackedPanel.from_codes(codes)
 
 
+def _check_missing_arg(what: str, dosage: bool, missing: Optional[str]) -> None:
+    if missing not in (None, "ref"):
+        raise LdxError(f"{what}: missing must be None or 'ref' (got {missing!r})")
+    if missing is not None and not dosage:
+        raise LdxError(f"{what}: missing= belongs to dosage=True (the haplotype r leaves such calls out of both counts)")
+
+
+def _check_complete(what: str, panel: PackedPanel, chrom, missing: Optional[str]) -> None:
+    """dosage mode: every call must be REF or the first ALT allele unless the caller accepted the REF imputation."""
+    if missing == "ref":
+        return
+    short = panel.alt_counts().astype(np.int64) + panel.ref_counts().astype(np.int64) < panel.n_hap
+    if short.any():
+        raise LdxError(f"{what}: {int(short.sum())} variant(s) of chromosome {chrom} carry a call that is neither REF nor the "
+                       "first ALT allele (missing or multi-allelic); the dosage counts it as REF -- pass missing='ref' to "
+                       "accept that")
+
+
 def ld_scores(vcf, chrom, chrom_rows: Sequence[Sequence], sample_names: Sequence[str], window_bp: int = 1_000_000,
-              annot=None, annot_names: Optional[Sequence[str]] = None, adjust: bool = True) -> LDScoreTable:
+              annot=None, annot_names: Optional[Sequence[str]] = None, adjust: bool = True, dosage: bool = False,
+              missing: Optional[str] = None) -> LDScoreTable:
     """LD scores of one chromosome's variants, from the inputs of ``r_matrix`` (VCF rows [pos, rsID]; each record fetched
     once).  ``annot``: bool / 0-1 [len(chrom_rows), K], K <= 8, one row per input row; ``annot_names``: K column names
     (default A0, A1, ...).  ``adjust``: write LDSC's unbiased r^2 (LDScores.adjusted) rather than r^2.  Mixed-ploidy panels
-    (genotype lists of different lengths) are out of scope: LdxError."""
+    (genotype lists of different lengths) are out of scope: LdxError.  ``dosage``: genotype-dosage r over the samples, n_obs =
+    N (the module docstring); a kept variant with a call that is neither REF nor the first ALT allele (a + r < n) then raises
+    LdxError unless ``missing="ref"`` accepts that such calls count as REF."""
+    _check_missing_arg("ld_scores", dosage, missing)
     cv, keep, ann, names, panel = _fetch_panel("ld_scores", vcf, chrom, chrom_rows, sample_names, annot, annot_names)
     poss = [cv.poss[k] for k in keep]
-    res = ld_score(panel, np.asarray(poss, dtype=np.int64), window_bp=window_bp, annot=ann)
+    if dosage:
+        _check_complete("ld_scores", panel, chrom, missing)
+    res = ld_score(panel, np.asarray(poss, dtype=np.int64), window_bp=window_bp, annot=ann, dosage=dosage)
     fa = panel.alt_counts().astype(np.float64) / panel.n_hap
     return LDScoreTable(str(chrom), [cv.rs_ids[k] for k in keep], poss, fa, ann, names, res, adjust)
 
 
 def ld_scores_by_group(vcf, chrom, chrom_rows: Sequence[Sequence], groups: Mapping[str, Sequence[str]],
                        window_bp: int = 1_000_000, annot=None, annot_names: Optional[Sequence[str]] = None,
-                       adjust: bool = True) -> Dict[str, LDScoreTable]:
+                       adjust: bool = True, dosage: bool = False, missing: Optional[str] = None) -> Dict[str, LDScoreTable]:
     """``ld_scores`` for several sample groups (label -> sample names: populations, genders) of one chromosome from ONE pass
     over the VCF: the union of the groups is fetched and packed once, each group is then a haplotype subset of that panel
     taken on the device (PackedPanel.select) and scored.  Every table equals ``ld_scores`` on its group alone.  The other
     arguments are those of ``ld_scores``.  The samples must be diploid in every record (a panel whose haplotype count is not
     twice the number of carried samples -- haploid or mixed-ploidy calls -- is an LdxError), and a group none of whose
-    samples is carried is one too."""
+    samples is carried is one too.  ``dosage`` / ``missing`` as for ``ld_scores`` (a group's columns are whole samples, so
+    its individuals stay pairs of adjacent haplotypes)."""
     what = "ld_scores_by_group"
+    _check_missing_arg(what, dosage, missing)
     if not groups:
         raise LdxError(f"{what}: no groups")
     union = list(dict.fromkeys(name for members in groups.values() for name in members))
@@ -109,6 +138,8 @@ def ld_scores_by_group(vcf, chrom, chrom_rows: Sequence[Sequence], groups: Mappi
     if panel.n_hap != 2 * len(carried):
         raise LdxError(f"{what}: {panel.n_hap} haplotypes for {len(carried)} carried samples on chromosome {chrom}: "
                        "haploid or mixed-ploidy calls; the groups' columns are only known for diploid samples")
+    if dosage:
+        _check_complete(what, panel, chrom, missing)
     poss = [cv.poss[k] for k in keep]
     pos = np.asarray(poss, dtype=np.int64)
     rs_ids = [cv.rs_ids[k] for k in keep]
@@ -118,7 +149,7 @@ def ld_scores_by_group(vcf, chrom, chrom_rows: Sequence[Sequence], groups: Mappi
         if cols.size == 0:
             raise LdxError(f"{what}: no sample of group {label!r} is carried by the records of chromosome {chrom}")
         sub = panel.select(haplotypes=cols)
-        res = ld_score(sub, pos, window_bp=window_bp, annot=ann)
+        res = ld_score(sub, pos, window_bp=window_bp, annot=ann, dosage=dosage)
         fa = sub.alt_counts().astype(np.float64) / sub.n_hap
         tables[label] = LDScoreTable(str(chrom), list(rs_ids), list(poss), fa, ann, list(names), res, adjust)
     return tables
@@ -126,7 +157,8 @@ def ld_scores_by_group(vcf, chrom, chrom_rows: Sequence[Sequence], groups: Mappi
 
 def write_ldscore(base: str, table: LDScoreTable) -> List[str]:
     """``{base}.l2.ldscore.gz``: tab-separated CHR, SNP, BP and one column per category ({name}L2; L2 without an
-    annotation), values as %.3f, degenerate variants (no ALT or no REF allele) left out; ``{base}.l2.M``: one line, per
+    annotation), values as %.3f, degenerate variants (no ALT or no REF allele; a dosage table: no variance among the samples'
+    dosages) left out; ``{base}.l2.M``: one line, per
     column the number of written variants in the category; ``{base}.l2.M_5_50``: the same for MAF = min(fa, 1 - fa) > 0.05.
     Returns the three paths."""
     live = table.scores.live

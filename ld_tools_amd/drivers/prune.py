@@ -4,9 +4,10 @@ the device).
 
 Pruning here is priority clumping -- the SNPs in decreasing priority (default: minor allele frequency), each one kept
 unless a kept SNP within the window has r^2 above the threshold with it -- not ``--indep-pairwise``'s sliding-window step
-algorithm.  And r is the haplotype r of the ALT-allele indicators over the panel's haplotypes (include/ldx.h,
-LDX_OUT_R32), not PLINK's genotype-based estimate.  So the files follow PLINK's layout while the sets need not match
-PLINK's.
+algorithm.  By default r is the haplotype r of the ALT-allele indicators over the panel's haplotypes (include/ldx.h,
+LDX_OUT_R32); ``dosage=True`` takes PLINK's own r, the genotype correlation of the ALT dosages over the samples
+(ldx_ld_neighbors_dosage_dev; a missing call counts as REF).  Either way the files follow PLINK's layout while the sets
+need not match ``--indep-pairwise``'s, whose rule differs.
 """
 from __future__ import annotations
 
@@ -30,12 +31,12 @@ class PruneTable:
 
 
 def prune(vcf, chrom, chrom_rows: Sequence[Sequence], sample_names: Sequence[str], r2: float = 0.2,
-          window_bp: int = 250_000, priority: Optional[Sequence[float]] = None) -> PruneTable:
+          window_bp: int = 250_000, priority: Optional[Sequence[float]] = None, dosage: bool = False) -> PruneTable:
     """Pruning of one chromosome's variants (VCF rows [pos, rsID]); ``priority``: one value per input row (higher first),
-    default the minor allele frequency."""
+    default the minor allele frequency.  ``dosage``: genotype-dosage r (ops.ld_prune)."""
     panel, rows, rs_ids, poss = chrom_panel(vcf, chrom, chrom_rows, sample_names, "prune")
     pr = None if priority is None else np.asarray(priority, dtype=np.float64)[rows]
-    res = ld_prune(panel, np.asarray(poss, dtype=np.int64), r2=r2, window_bp=window_bp, priority=pr)
+    res = ld_prune(panel, np.asarray(poss, dtype=np.int64), r2=r2, window_bp=window_bp, priority=pr, dosage=dosage)
     return PruneTable(str(chrom), rs_ids, poss, res)
 
 

@@ -1,6 +1,7 @@
 """Signed-r LD matrix of one chromosome: the square matrix of r between ALT-allele indicators, unrounded, with the variant
 list that fixes its allele orientation -- what fine-mapping, colocalisation, summary-statistics imputation and LD-aware PRS
-read from a phased reference panel.  Not a reference workflow: the reference only writes rounded r^2 / D' tables
+read from a phased reference panel; with ``dosage=True`` the genotype correlation of the ALT dosages over the samples instead
+(include/ldx.h, ldx_triangle_dosage_dev), which needs no phase.  Not a reference workflow: the reference only writes rounded r^2 / D' tables
 (drivers/triangle.py); this driver takes the same inputs and runs the r32 cell format (include/ldx.h, LDX_OUT_R32)."""
 from __future__ import annotations
 
@@ -34,9 +35,9 @@ class RMatrix:
         return len(self.rs_ids)
 
 
-def r_matrix(vcf, chrom, chrom_rows: Sequence[Sequence], sample_names: Sequence[str]) -> RMatrix:
+def r_matrix(vcf, chrom, chrom_rows: Sequence[Sequence], sample_names: Sequence[str], dosage: bool = False) -> RMatrix:
     """The r32 triangle of one chromosome's variants, from the inputs of ``triangle_matrix`` (VCF rows [pos, rsID]; each
-    record fetched once).  Mixed-ploidy panels (genotype lists of different lengths) are out of scope: LdxError."""
+    record fetched once).  ``dosage``: genotype-dosage r over the samples (a missing call counts as REF).  Mixed-ploidy panels (genotype lists of different lengths) are out of scope: LdxError."""
     cv = fetch_variants(vcf, chrom, chrom_rows, sample_names)
     keep = [k for k, rec in enumerate(cv.recs) if rec is not None]
     if not keep:
@@ -48,7 +49,7 @@ def r_matrix(vcf, chrom, chrom_rows: Sequence[Sequence], sample_names: Sequence[
     except RaggedGenotypesError as exc:
         raise LdxError(f"r_matrix: mixed ploidy on chromosome {chrom} ({exc}); signed r needs one haplotype count") from exc
     panel = PackedPanel.from_codes(codes)
-    res = ld_triangle(panel, fmt="r32")
+    res = ld_triangle(panel, fmt="r32", dosage=dosage)
     return RMatrix(chrom, [cv.rs_ids[k] for k in keep], [cv.poss[k] for k in keep], [cv.recs[k].ref for k in keep],
                    [cv.recs[k].alts[0] for k in keep], panel.alt_freq4().cpu().numpy().tolist(), res)
 

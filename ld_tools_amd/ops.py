@@ -79,6 +79,7 @@ class TriangleResult:
     ws: Optional[torch.Tensor] = None        # the matrix kernel's pass-scheduler workspace (include/ldx.h, ldx_triangle_ex_dev):
                                              # zeroed once here, re-armed by every launch; one per result buffer, because two
                                              # launches that may overlap write different buffers
+    dosage: bool = False                     # r32 only: the cells are genotype-dosage r (ld_triangle(dosage=True))
 
     @property
     def fmt(self) -> str:
@@ -183,7 +184,8 @@ class TriangleResult:
         """Block [rows[0], rows[1]) x [cols[0], cols[1]) (default: everything) of the symmetric square matrix of signed r, as a
         float32 device tensor: (i, j) and (j, i) both hold the strip cell of max(i, j), min(i, j); the diagonal is
         (n - a_i) / r_i -- 1.0 for a polymorphic SNP without missing codes, -0.0 for a degenerate one
-        (ldx_triangle_r_block_dev).  Needs an unsharded r32 result."""
+        (ldx_triangle_r_block_dev).  A dosage result has its own diagonal: 1.0 where the dosage has variance (v_i > 0), -0.0
+        otherwise (ldx_triangle_r_block_dosage_dev).  Needs an unsharded r32 result."""
         if self.r32 is None:
             raise _lib.LdxError(f"r_matrix() needs an r32 result (this one is {self.fmt})")
         if not self.unsharded:
@@ -198,6 +200,11 @@ class TriangleResult:
         out = torch.empty((r1 - r0, c1 - c0), dtype=torch.float32, device=self.r32.device)
         if out.numel():
             p = self.panel
+            if self.dosage:
+                check(lib.ldx_triangle_r_block_dosage_dev(self.r32.data_ptr(), n, p.dosage_stats()[1].data_ptr(), r0, r1, c0, c1,
+                                                          out.data_ptr(), c1 - c0, _stream_ptr()),
+                      "ldx_triangle_r_block_dosage_dev")
+                return out
             check(lib.ldx_triangle_r_block_dev(self.r32.data_ptr(), n, p.acnt.data_ptr(), p.rcnt.data_ptr(), p.n_hap,
                                                r0, r1, c0, c1, out.data_ptr(), c1 - c0, _stream_ptr()),
                   "ldx_triangle_r_block_dev")
@@ -206,8 +213,12 @@ class TriangleResult:
 
 def ld_triangle(panel: PackedPanel, unit_range: Optional[Tuple[int, int]] = None, want_raw: bool = False,
                 want_n11: bool = False, out: Optional[TriangleResult] = None, fmt: str = "ld32",
-                path: Optional[str] = None) -> TriangleResult:
+                path: Optional[str] = None, dosage: bool = False) -> TriangleResult:
     """All row > col pairs of the panel: var_1 = row, var_2 = col (ld_triangle.py:193-194).
+
+    ``dosage=True`` (with ``fmt='r32'`` and the whole triangle only): the cells are the genotype-dosage correlation -- r of
+    the ALT dosages 0 / 1 / 2 of the n_hap / 2 individuals (haplotypes 2k and 2k + 1), which does not depend on phase: PLINK's
+    and LDSC's r (include/ldx.h, ldx_triangle_dosage_dev).  It runs on the FP4 kernel only.
 
     ``unit_range`` restricts the work to a contiguous slice of the unit list (multi-GPU sharding);
     ``out`` re-uses the buffers of a previous result of the same shape (benchmark loops); ``fmt`` picks the cell
@@ -228,6 +239,15 @@ def ld_triangle(panel: PackedPanel, unit_range: Optional[Tuple[int, int]] = None
         raise _lib.LdxError("the one-measure formats take no side output")
     if fmt == "r32" and want_n11:
         raise _lib.LdxError("the r32 format takes no side output")
+    if dosage:
+        if fmt != "r32":
+            raise _lib.LdxError(f"ld_triangle: dosage=True needs fmt='r32' (got {fmt!r}): the rounded measures are haplotype statistics")
+        if unit_range is not None:
+            raise _lib.LdxError("ld_triangle: dosage=True does not take unit_range (no sharded dosage triangle)")
+        if panel.n_hap % 2:
+            raise _lib.LdxError(f"ld_triangle: dosage=True needs an even n_hap (got {panel.n_hap}): individual k owns haplotypes 2k and 2k + 1")
+    if out is not None and out.dosage != bool(dosage):
+        raise _lib.LdxError("ld_triangle: `out` was made with another `dosage`")
     if out is None:
         out = TriangleResult(panel.n_snps, u0, u1,
                              torch.empty((cells, 2), dtype=torch.float32, device=dev) if fmt == "ld32" else None,
@@ -236,7 +256,8 @@ def ld_triangle(panel: PackedPanel, unit_range: Optional[Tuple[int, int]] = None
                              torch.empty((cells, 2), dtype=torch.int16, device=dev) if fmt == "k16" else None,
                              k16one=torch.empty(cells, dtype=torch.int16, device=dev) if fmt in _lib.ONE_MEASURE else None,
                              one_fmt=fmt if fmt in _lib.ONE_MEASURE else None,
-                             r32=torch.empty(cells, dtype=torch.float32, device=dev) if fmt == "r32" else None)
+                             r32=torch.empty(cells, dtype=torch.float32, device=dev) if fmt == "r32" else None,
+                             dosage=bool(dosage))
     elif (out.n_snps, out.unit_begin, out.unit_end, out.fmt) != (panel.n_snps, u0, u1, fmt):
         raise _lib.LdxError("ld_triangle: `out` has a different shape or format")
     out.panel = panel
@@ -244,6 +265,11 @@ def ld_triangle(panel: PackedPanel, unit_range: Optional[Tuple[int, int]] = None
         pcode = lib.ldx_get_triangle_path() if path is None else PATHS[path]
         if out.ws is None and pcode != PATHS["popcount"]:
             out.ws = torch.zeros(lib.ldx_triangle_workspace_bytes(), dtype=torch.uint8, device=dev)
+        if dosage:
+            check(lib.ldx_triangle_dosage_dev(panel.alt.data_ptr(), panel.dosage_stats()[1].data_ptr(), panel.n_snps, panel.n_hap,
+                                              u0, u1, pcode, out.r32.data_ptr(), _ptr(out.ws),
+                                              0 if out.ws is None else out.ws.numel(), _stream_ptr()), "ldx_triangle_dosage_dev")
+            return out
         check(lib.ldx_triangle_ex_dev(panel.alt.data_ptr(), panel.fa.data_ptr(), panel.fr.data_ptr(),
                                       panel.q.data_ptr(), panel.n_snps, panel.n_hap, u0, u1, pcode,
                                       _lib.FORMATS[fmt], out.cells.data_ptr(), _ptr(out.raw), _ptr(out.n11),
@@ -545,6 +571,38 @@ def ld_area(panel: PackedPanel, positions, queries: Optional[Sequence[int]] = No
     return AreaHits(qrow, orow, ld32, count_pairs, offsets, band)
 
 
+# --------------------------------------------------------------------------- genotype dosage
+def dosage_host(codes) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Host mirror of ldx_dosage_stats_dev (include/ldx.h) in pure numpy: ``(a, hom, v)`` int64 [n_snps] from an allele-code
+    matrix [n_snps][n_hap], n_hap even.  Individual k owns haplotypes 2k and 2k + 1; its dosage g counts code 1 ONLY (REF,
+    missing and any other allele count 0); a = sum g, hom = #{g == 2}, v = N (a + 2 hom) - a^2 with N = n_hap / 2 -- N^2 times
+    the variance of g, 0 exactly for the SNPs the dosage operators treat as degenerate."""
+    c = np.asarray(codes)
+    if c.ndim != 2 or c.shape[1] % 2:
+        raise _lib.LdxError(f"dosage_host: codes must be [n_snps][n_hap] with an even n_hap, got shape {c.shape}")
+    alt = (c == 1)
+    g = alt[:, 0::2].astype(np.int64) + alt[:, 1::2].astype(np.int64)
+    a = g.sum(axis=1)
+    hom = (g == 2).sum(axis=1)
+    n_ind = c.shape[1] // 2
+    return a, hom, n_ind * (a + 2 * hom) - a * a
+
+
+def _dosage_refused(what: str, dosage) -> None:
+    """The operators without a dosage form refuse the flag: none of them may silently compute haplotype r."""
+    if dosage:
+        raise _lib.LdxError(f"{what}: no genotype-dosage form (dosage=True is available for ld_triangle(fmt='r32'), ld_score, "
+                            "ld_neighbors, ld_prune and ld_clump)")
+
+
+def _dosage_check(what: str, panel: PackedPanel, regions=None) -> None:
+    """Argument rules of the dosage operators, checked before anything touches the device."""
+    if regions is not None:
+        raise _lib.LdxError(f"{what}: regions= together with dosage=True is not available")
+    if panel.n_hap % 2:
+        raise _lib.LdxError(f"{what}: dosage=True needs an even n_hap (got {panel.n_hap}): individual k owns haplotypes 2k and 2k + 1")
+
+
 # --------------------------------------------------------------------------- LD scores
 SCORE_SCALE = float(1 << 32)    # sums are integers in units of 2^-32 r^2 (include/ldx.h, ldx_ld_score_dev)
 MAX_ANNOT = 8
@@ -623,10 +681,14 @@ class LDScores:
     _l2: Optional[np.ndarray] = None
     _m: Optional[np.ndarray] = None
     _live: Optional[np.ndarray] = None
+    dosage: bool = False                     # the sums are over genotype-dosage r (ld_score(dosage=True))
 
     @property
     def live(self) -> np.ndarray:
-        """bool [n]: the SNP is not degenerate (a r > 0: it has ALT and REF codes)."""
+        """bool [n]: the SNP is not degenerate (a r > 0: it has ALT and REF codes; a dosage result: v > 0, the dosage varies
+        among the individuals)."""
+        if self._live is None and self.dosage:
+            self._live = self.panel.dosage_live()
         if self._live is None:
             self._live = (self.panel.alt_counts().astype(np.int64) * self.panel.ref_counts().astype(np.int64)) > 0
         return self._live
@@ -645,8 +707,10 @@ class LDScores:
         return self._m
 
     def adjusted(self, n_obs: Optional[int] = None) -> np.ndarray:
-        """LDSC's unbiased r^2 estimate summed over the windows (adjust_l2), n_obs defaulting to n_hap."""
-        return adjust_l2(self.l2, self.m, self.n_hap if n_obs is None else int(n_obs))
+        """LDSC's unbiased r^2 estimate summed over the windows (adjust_l2), n_obs defaulting to n_hap -- for a dosage
+        result to the number of individuals, n_hap / 2."""
+        default = self.n_hap // 2 if self.dosage else self.n_hap
+        return adjust_l2(self.l2, self.m, default if n_obs is None else int(n_obs))
 
 
 def _band_positions(panel: PackedPanel, positions, window_bp, window_snps, check_positions: bool, what: str):
@@ -683,7 +747,7 @@ def _band_positions(panel: PackedPanel, positions, window_bp, window_snps, check
 
 def ld_score(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, window_snps: Optional[int] = None,
              annot=None, path: Optional[str] = None, workspace: Optional[torch.Tensor] = None,
-             check_positions: bool = True, regions=None) -> LDScores:
+             check_positions: bool = True, regions=None, dosage: bool = False) -> LDScores:
     """LD scores on the matrix-pipe band: for every SNP i, the sum of r^2 over the SNPs j with |pos_i - pos_j| <= window
     (i itself included), and with ``annot`` (bool / 0-1 [n, K], K <= 8) the same sum per category over the j that carry it
     (include/ldx.h, ldx_ld_score_dev).  r is the signed r of ld_triangle(fmt="r32"), bit for bit; the sums are exact
@@ -698,7 +762,13 @@ def ld_score(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, win
     ``regions`` (an LDRegions or a region_of array; default None: no change): the sums run over the SNPs of i's own region
     only -- the positions go through region_positions, and ``LDScores.m`` counts over the same shifted positions.
     ``window_bp=None`` then means whole regions.
+
+    ``dosage=True``: r is the genotype-dosage r of ld_triangle(fmt="r32", dosage=True), bit for bit -- what ldsc.py --l2 sums
+    (include/ldx.h, ldx_ld_score_dosage_dev; the FP4 band only, not together with ``regions``).  ``LDScores.live`` is then
+    v > 0 and ``adjusted()`` defaults to n_obs = n_hap / 2.
     """
+    if dosage:
+        _dosage_check("ld_score", panel, regions)
     require_gpu()
     n = panel.n_snps
     pos, pos_h, window = _region_band(panel, positions, window_bp, window_snps, regions, check_positions, "ld_score")
@@ -711,11 +781,17 @@ def ld_score(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, win
     elif workspace.numel() * workspace.element_size() < need:
         raise _lib.LdxError(f"workspace too small: {need} bytes needed")
     sums = torch.empty((n, 1 + k), dtype=torch.uint64, device=panel.device)
-    check(lib.ldx_ld_score_dev(panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), panel.fa.data_ptr(),
-                               panel.fr.data_ptr(), n, panel.n_hap, pos.data_ptr(), window, _ptr(annot_d), k, pcode,
-                               sums.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                               _stream_ptr()), "ldx_ld_score_dev")
-    res = LDScores(sums, pos_h, window, panel.n_hap, bits, k, panel)
+    if dosage:
+        check(lib.ldx_ld_score_dosage_dev(panel.alt.data_ptr(), panel.dosage_stats()[1].data_ptr(), n, panel.n_hap,
+                                          pos.data_ptr(), window, _ptr(annot_d), k, pcode, sums.data_ptr(),
+                                          workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr()),
+              "ldx_ld_score_dosage_dev")
+    else:
+        check(lib.ldx_ld_score_dev(panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), panel.fa.data_ptr(),
+                                   panel.fr.data_ptr(), n, panel.n_hap, pos.data_ptr(), window, _ptr(annot_d), k, pcode,
+                                   sums.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                   _stream_ptr()), "ldx_ld_score_dev")
+    res = LDScores(sums, pos_h, window, panel.n_hap, bits, k, panel, dosage=bool(dosage))
     if pos_h is None:   # positions stayed on the device: fetched with m
         res.positions = pos      # type: ignore[assignment]
     res._keep = (pos, annot_d, workspace)   # alive until the launch is done (stream-ordered frees would allow reuse anyway)
@@ -821,7 +897,7 @@ class LDDecay:
 
 def ld_decay(panel: PackedPanel, positions=None, window_bp: int = 250_000, window_snps: Optional[int] = None,
              bin_bp: int = 1000, keep=None, path: Optional[str] = None, workspace: Optional[torch.Tensor] = None,
-             check_positions: bool = True) -> LDDecay:
+             check_positions: bool = True, dosage: bool = False) -> LDDecay:
     """LD decay on the matrix-pipe band: per distance bin of width ``bin_bp``, the sum of r^2 and the number of pairs i > j
     with pos_i - pos_j <= window, both SNPs non-degenerate and -- with ``keep`` (bool [n]) -- both kept (include/ldx.h,
     ldx_ld_decay_dev).  r is the signed r of ld_triangle(fmt="r32"), bit for bit; the sums are exact integer sums of
@@ -831,7 +907,9 @@ def ld_decay(panel: PackedPanel, positions=None, window_bp: int = 250_000, windo
     bins: coarser curves come from ``LDDecay.rebin``.  ``path``: 'fp4' (default) or 'mfma'.  ``workspace``: a uint8 device
     tensor of ldx_ld_decay_workspace_bytes() bytes to reuse (one per launch that may be in flight).  The call is
     stream-ordered: the host reads nothing until ``.counts`` / ``.sum_r2`` are asked for.
-    """
+    
+    ``dosage`` is refused: this operator has no genotype-dosage form, and it never computes haplotype r in its place."""
+    _dosage_refused("ld_decay", dosage)
     require_gpu()
     n = panel.n_snps
     pos, _, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_decay")
@@ -974,7 +1052,7 @@ class LDBlocks:
 def ld_blocks(panel: PackedPanel, positions=None, window_bp: int = 500_000, window_snps: Optional[int] = None,
               min_count: int = 1, min_freq: Optional[float] = None, keep=None, maf_min: float = 0.0,
               path: Optional[str] = None, workspace: Optional[torch.Tensor] = None,
-              check_positions: bool = True) -> LDBlocks:
+              check_positions: bool = True, dosage: bool = False) -> LDBlocks:
     """Haplotype blocks by the four-gamete test on the matrix-pipe band (include/ldx.h, ldx_ld_fgt_dev + ldx_ld_blocks_dev).
     A pair i > j with pos_i - pos_j <= window, both SNPs kept, is recombinant when each of the four two-locus haplotypes
     occurs at least ``min_count`` times ("not ALT" is the other allele: missing codes count with REF); ``left[i]`` is 1 +
@@ -986,7 +1064,9 @@ def ld_blocks(panel: PackedPanel, positions=None, window_bp: int = 500_000, wind
     are compatible with everything).  ``window_snps`` counts the window in SNPs (positions 0 .. n-1).  ``path``: 'fp4'
     (default) or 'mfma'.  ``workspace``: a uint8 device tensor of ldx_ld_fgt_workspace_bytes() bytes to reuse.  The call is
     stream-ordered: the host reads nothing until a result property is asked for.
-    """
+    
+    ``dosage`` is refused: this operator has no genotype-dosage form, and it never computes haplotype r in its place."""
+    _dosage_refused("ld_blocks", dosage)
     require_gpu()
     n = panel.n_snps
     pos, pos_h, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_blocks")
@@ -1234,7 +1314,8 @@ def _split_launch(cross, n, min_snps, max_snps, cuts, n_out, workspace) -> None:
 
 
 def ld_cross(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, window_snps: Optional[int] = None,
-             path: Optional[str] = None, workspace: Optional[torch.Tensor] = None, check_positions: bool = True) -> LDCross:
+             path: Optional[str] = None, workspace: Optional[torch.Tensor] = None, check_positions: bool = True,
+             dosage: bool = False) -> LDCross:
     """The cross-LD profile on the matrix-pipe band (include/ldx.h, ldx_ld_cross_dev): ld_score's sweep with every SNP's
     score kept in two halves -- the r^2 of its in-window partners to the left and to the right -- and their prefix sum
     cross[k], the r^2 summed over the in-window pairs j < k <= i: the LD a region boundary before SNP k would cut.  r is
@@ -1242,7 +1323,9 @@ def ld_cross(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, win
     run to run and identical on both paths.
 
     Positions, window, ``path`` and ``workspace`` (ldx_ld_cross_workspace_bytes() bytes) as for ld_score.  The call is
-    stream-ordered: the host reads nothing until a result property is asked for."""
+    stream-ordered: the host reads nothing until a result property is asked for.
+    ``dosage`` is refused: this operator has no genotype-dosage form, and it never computes haplotype r in its place."""
+    _dosage_refused("ld_cross", dosage)
     require_gpu()
     n = panel.n_snps
     pos, pos_h, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_cross")
@@ -1477,7 +1560,7 @@ def _matvec_launch(panel: PackedPanel, pos: torch.Tensor, window: int, x32: torc
 
 def ld_matvec(panel: PackedPanel, x, positions=None, window_bp: int = 1_000_000, window_snps: Optional[int] = None,
               power: int = 1, path: str = "auto", workspace: Optional[torch.Tensor] = None, check_positions: bool = True,
-              check_finite: bool = True, regions=None) -> LDProduct:
+              check_finite: bool = True, regions=None, dosage: bool = False) -> LDProduct:
     """y = R_w x on the matrix-pipe band, without the matrix (include/ldx.h, ldx_ld_matvec_dev): for every SNP i the sum of
     r_ij x_j over the SNPs j with |pos_i - pos_j| <= window (i included, r_ii = r_matrix()'s diagonal), r the signed r of
     ld_triangle(fmt="r32") bit for bit; ``power=2`` sums r^2 x_j instead (r^2 one float32 multiply) -- the LD score of a
@@ -1493,7 +1576,9 @@ def ld_matvec(panel: PackedPanel, x, positions=None, window_bp: int = 1_000_000,
 
     ``regions`` (an LDRegions or a region_of array; default None: no change) restricts the product to the block-diagonal
     R_B x: r_ij counts only for i and j of one region (region_positions; the positions are then read on the host), and
-    ``window_bp=None`` means whole regions."""
+    ``window_bp=None`` means whole regions.
+    ``dosage`` is refused: this operator has no genotype-dosage form, and it never computes haplotype r in its place."""
+    _dosage_refused("ld_matvec", dosage)
     require_gpu()
     pos, _, window = _region_band(panel, positions, window_bp, window_snps, regions, check_positions, "ld_matvec")
     x32, e, squeeze = matvec_rhs(x, panel.n_snps, power, check_finite, panel.device)
@@ -1699,6 +1784,7 @@ class LDNeighbors:
     n_snps: int
     window: int
     bound: np.float32       # the float32 bound on s = r *f32 r (r2_bound)
+    dosage: bool = False    # r is the genotype-dosage r (ld_neighbors(dosage=True))
 
     @property
     def nbr(self) -> torch.Tensor:
@@ -1723,7 +1809,7 @@ class LDNeighbors:
 
 def ld_neighbors(panel: PackedPanel, positions=None, window_bp: int = 250_000, window_snps: Optional[int] = None,
                  r2: float = 0.2, strict: bool = False, path: Optional[str] = None, hit_capacity: Optional[int] = None,
-                 workspace: Optional[torch.Tensor] = None, check_positions: bool = True) -> LDNeighbors:
+                 workspace: Optional[torch.Tensor] = None, check_positions: bool = True, dosage: bool = False) -> LDNeighbors:
     """Neighbour lists on the matrix-pipe band (include/ldx.h, ldx_ld_neighbors_dev + ldx_area_finish_ex_dev): for every SNP
     the SNPs j with |pos_i - pos_j| <= window, j != i, and r^2 >= ``r2`` (``strict``: r^2 > r2), where r is the r32 cell of
     ld_triangle(fmt="r32") bit for bit and r^2 one float32 multiply.  Degenerate SNPs have no neighbours.
@@ -1731,7 +1817,12 @@ def ld_neighbors(panel: PackedPanel, positions=None, window_bp: int = 250_000, w
     Positions and window as for ld_score.  ``path``: 'fp4' (default) or 'mfma' (the int8 band: identical lists).
     ``hit_capacity``: record slots to start with (16 bytes each; default max(2^20, 32 n)); a call that needs more runs
     again at the count the first run reserved.  ``workspace``: a uint8 device tensor of ldx_ld_neighbors_workspace_bytes()
-    bytes to reuse.  The host reads the record count once."""
+    bytes to reuse.  The host reads the record count once.
+
+    ``dosage=True``: r is the genotype-dosage r of ld_triangle(fmt="r32", dosage=True), bit for bit (include/ldx.h,
+    ldx_ld_neighbors_dosage_dev; the FP4 band only); SNPs whose dosage does not vary (v == 0) have no neighbours."""
+    if dosage:
+        _dosage_check("ld_neighbors", panel)
     require_gpu()
     n = panel.n_snps
     bound = r2_bound(r2, strict)
@@ -1755,11 +1846,18 @@ def ld_neighbors(panel: PackedPanel, positions=None, window_bp: int = 250_000, w
             raise _lib.LdxError(f"ld_neighbors: {cap} record slots needed; the CSR's offsets are uint32 (at most 2^32 - 1)")
         raw = torch.empty((cap, 4), dtype=torch.int32, device=dev)
         hits = torch.empty((cap, 4), dtype=torch.int32, device=dev)
-        check(lib.ldx_ld_neighbors_dev(panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(),
-                                       panel.fa.data_ptr(), panel.fr.data_ptr(), n, panel.n_hap, pos.data_ptr(), window,
-                                       float(bound), pcode, raw.data_ptr(), cap, n_hits.data_ptr(), counts,
-                                       workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr()),
-              "ldx_ld_neighbors_dev")
+        if dosage:
+            check(lib.ldx_ld_neighbors_dosage_dev(panel.alt.data_ptr(), panel.dosage_stats()[1].data_ptr(), n, panel.n_hap,
+                                                  pos.data_ptr(), window, float(bound), pcode, raw.data_ptr(), cap,
+                                                  n_hits.data_ptr(), counts, workspace.data_ptr(),
+                                                  workspace.numel() * workspace.element_size(), _stream_ptr()),
+                  "ldx_ld_neighbors_dosage_dev")
+        else:
+            check(lib.ldx_ld_neighbors_dev(panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(),
+                                           panel.fa.data_ptr(), panel.fr.data_ptr(), n, panel.n_hap, pos.data_ptr(), window,
+                                           float(bound), pcode, raw.data_ptr(), cap, n_hits.data_ptr(), counts,
+                                           workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr()),
+                  "ldx_ld_neighbors_dev")
         check(lib.ldx_area_finish_ex_dev(raw.data_ptr(), n_hits.data_ptr(), cap, n, hits.data_ptr(), offsets.data_ptr(),
                                          summary.data_ptr(), fin.data_ptr(), fin_bytes, 1, _stream_ptr()),
               "ldx_area_finish_ex_dev")
@@ -1772,7 +1870,7 @@ def ld_neighbors(panel: PackedPanel, positions=None, window_bp: int = 250_000, w
     else:
         raise _lib.LdxError("ld_neighbors: the record count did not settle")
     del raw
-    return LDNeighbors(offsets, hits[:total], n, window, bound)
+    return LDNeighbors(offsets, hits[:total], n, window, bound, bool(dosage))
 
 
 def select_dev(nb: LDNeighbors, rank, member_ok, batch: int = SELECT_BATCH) -> Tuple[np.ndarray, np.ndarray, int]:
@@ -1844,20 +1942,24 @@ class Pruned:
     rounds: int
 
 
-def _panel_live(panel: PackedPanel) -> np.ndarray:
-    return live_snps(panel.alt_counts(), panel.ref_counts())
+def _panel_live(panel: PackedPanel, dosage: bool = False) -> np.ndarray:
+    """The SNPs that can have a neighbour: a r > 0, or for the dosage lists v > 0."""
+    return panel.dosage_live() if dosage else live_snps(panel.alt_counts(), panel.ref_counts())
 
 
 def ld_clump(panel: PackedPanel, positions, pvalues, p1: float = 1e-4, p2: float = 1e-2, r2: float = 0.5,
              window_bp: int = 250_000, window_snps: Optional[int] = None, path: Optional[str] = None,
-             hit_capacity: Optional[int] = None) -> Clumps:
+             hit_capacity: Optional[int] = None, dosage: bool = False) -> Clumps:
     """Clumping (PLINK --clump's rule): take the SNPs with p <= p1 in increasing (p, row); one not yet in a clump becomes an
     index and takes every SNP not yet in a clump with p <= p2 and r^2 >= r2 within the window.  r^2 is that of ld_neighbors
-    (the haplotype r of the ALT indicators, unrounded).  SNPs with a NaN p and degenerate SNPs take no part."""
-    live = _panel_live(panel)
+    (the haplotype r of the ALT indicators, unrounded; ``dosage=True``: the genotype-dosage r, PLINK's own).  SNPs with a
+    NaN p and degenerate SNPs (dosage: v == 0) take no part."""
+    if dosage:
+        _dosage_check("ld_clump", panel)
+    live = _panel_live(panel, dosage)
     rank, member_ok = clump_ranks(pvalues, p1, p2, live)
     nb = ld_neighbors(panel, positions, window_bp=window_bp, window_snps=window_snps, r2=r2, strict=False, path=path,
-                      hit_capacity=hit_capacity)
+                      hit_capacity=hit_capacity, dosage=dosage)
     state, owner, rounds = select_dev(nb, rank, member_ok)
     idx = np.flatnonzero(state == SEL_INDEX)
     idx = idx[np.argsort(rank[idx], kind="stable")]
@@ -1867,19 +1969,26 @@ def ld_clump(panel: PackedPanel, positions, pvalues, p1: float = 1e-4, p2: float
 
 def ld_prune(panel: PackedPanel, positions=None, r2: float = 0.2, window_bp: Optional[int] = None,
              window_snps: Optional[int] = None, priority=None, path: Optional[str] = None,
-             hit_capacity: Optional[int] = None) -> Pruned:
+             hit_capacity: Optional[int] = None, dosage: bool = False) -> Pruned:
     """Priority pruning: take the SNPs in decreasing priority (default: the MAF min(fa, fr) of the panel), ties by row; one
     with no kept neighbour is kept.  Neighbours are the SNPs within the window with r^2 > r2 (strict), as in ld_neighbors.
     The kept set has no pair above the threshold inside the window.  Degenerate SNPs are never kept.  The window is
-    ``window_snps`` SNPs or ``window_bp`` in the units of ``positions`` (default 250 000 when positions are given)."""
-    live = _panel_live(panel)
+    ``window_snps`` SNPs or ``window_bp`` in the units of ``positions`` (default 250 000 when positions are given).
+    ``dosage=True``: the neighbours are those of the genotype-dosage r (PLINK --indep-pairwise's r), SNPs with v == 0 are
+    never kept, and the default priority is the dosage MAF min(f, 1 - f), f = a / n_hap."""
+    if dosage:
+        _dosage_check("ld_prune", panel)
+    live = _panel_live(panel, dosage)
+    if priority is None and dosage:
+        f = panel.fa.cpu().numpy()[:panel.n_snps]
+        priority = np.minimum(f, 1.0 - f)
     if priority is None:
         priority = np.minimum(panel.fa.cpu().numpy()[:panel.n_snps], panel.fr.cpu().numpy()[:panel.n_snps])
     rank = priority_ranks(priority, live)
     if window_snps is None and window_bp is None:
         window_bp = 250_000
     nb = ld_neighbors(panel, positions, window_bp=0 if window_bp is None else window_bp, window_snps=window_snps, r2=r2,
-                      strict=True, path=path, hit_capacity=hit_capacity)
+                      strict=True, path=path, hit_capacity=hit_capacity, dosage=dosage)
     state, _, rounds = select_dev(nb, rank, live.astype(np.uint8))
     return Pruned(state == SEL_INDEX, rank, nb, rounds)
 

@@ -168,6 +168,28 @@ class PackedPanel:
         check(lib.ldx_snp_stats_dev(self.acnt.data_ptr(), self.rcnt.data_ptr(), self.n_snps, self.n_hap,
                                     self.fa.data_ptr(), self.fr.data_ptr(), self.q.data_ptr(), _stream_ptr()),
               "ldx_snp_stats_dev")
+        self.__dict__.pop("_dosage", None)   # the counts changed: dosage_stats() recomputes
+
+    def dosage_stats(self):
+        """``(hom, gstat)`` of include/ldx.h, ldx_dosage_stats_dev, on the device and cached until the panel is repacked:
+        ``hom`` int32 [padded_snps] (bit pattern of uint32), the individuals with both alleles ALT, and ``gstat`` float64
+        [padded_snps][2] = {a, 1 / sqrt(v)} with v = N (a + 2 hom) - a^2 (0 where v == 0): the per-SNP table of the dosage
+        operators.  Individual k owns haplotypes 2k and 2k + 1, so ``n_hap`` must be even."""
+        got = self.__dict__.get("_dosage")
+        if got is None:
+            if self.n_hap % 2:
+                raise _lib.LdxError(f"dosage: n_hap={self.n_hap} is odd (individual k owns haplotypes 2k and 2k + 1)")
+            npad = self.padded_snps
+            hom = torch.empty(npad, dtype=torch.int32, device=self.device)
+            gstat = torch.empty((npad, 2), dtype=torch.float64, device=self.device)
+            check(lib.ldx_dosage_stats_dev(self.alt.data_ptr(), self.acnt.data_ptr(), self.n_snps, self.n_hap,
+                                           hom.data_ptr(), gstat.data_ptr(), _stream_ptr()), "ldx_dosage_stats_dev")
+            got = self.__dict__["_dosage"] = (hom, gstat)
+        return got
+
+    def dosage_live(self) -> np.ndarray:
+        """bool [n_snps]: the SNPs whose dosage has variance among the individuals (v > 0)."""
+        return self.dosage_stats()[1][: self.n_snps, 1].cpu().numpy() > 0.0
 
     # ------------------------------------------------------------------ subsets
     def select(self, snps=None, haplotypes=None, out: Optional["PackedPanel"] = None) -> "PackedPanel":
@@ -220,6 +242,11 @@ class PackedPanel:
     @property
     def padded_snps(self) -> int:
         return lib.ldx_padded_snps(self.n_snps)
+
+    @property
+    def n_ind(self) -> int:
+        """Individuals of the dosage operators: n_hap // 2 (haplotypes 2k and 2k + 1 belong to individual k)."""
+        return self.n_hap // 2
 
     @property
     def n_pairs(self) -> int:
