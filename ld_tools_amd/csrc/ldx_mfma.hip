@@ -2558,82 +2558,141 @@ static size_t area_order_entries(uint32_t n_snps)
     return (worst <= kOrderCap && T < 4096u) ? worst : 0u;   // (T < 4096: an order entry packs tile and pass-in-tile in 12 bits each)
 }
 
+// The band's workspace, one description for every operator: the query mask's bytes (the decay and four-gamete bands keep
+// their keep mask there, the others leave them unused), the plan kernel's tables, the ticket order (absent beyond
+// area_order_entries' reach) and the ticket counters -- ld_area's layout ends here --, then the whole-panel operators' 256-byte
+// tail: the two query rows and, at byte 8, a hit counter for the plan kernel to zero where the operator has none of its own.
+// The ticket counters are words of THIS call's workspace, zeroed by the plan kernel in front of the band kernel, so that a
+// captured ld_area plan graph carries its own: two plans replayed on two streams at once share nothing.
+// (ldx_area_band_passes_offset in ldx_area.hip reads pass_base[T] at its offset in this layout.)
+struct BandWs {
+    uint8_t *mask;                 // [n_snps]
+    uint32_t *pass_base;           // [T + 1]
+    uint32_t *g_end, *g_begin;     // [T]
+    uint32_t *first_base;          // [T + 1] tiles with at least one pass before tile t
+    uint32_t *order;               // [area_order_entries] or null
+    uint32_t *sched;               // [kAreaSchedWords]
+    uint32_t *qrows;               // [2]   (tail)
+    unsigned long long *n_hits;    //       (tail)
+};
+
+// sizes and carves it: returns the byte count, and with a base the pointers too (a null base: the size only)
+static size_t band_carve(BandWs &w, void *base, uint32_t n_snps, bool tail = true)
+{
+    const size_t T = n_slabs(n_snps), n_order = area_order_entries(n_snps);
+    size_t off = 0;
+    char *b = (char *)base;
+    auto take = [&](size_t bytes) { char *p = b ? b + off : nullptr; off += (bytes + 255u) / 256u * 256u; return p; };
+    w.mask = (uint8_t *)take(n_snps);
+    w.pass_base = (uint32_t *)take((T + 1u) * 4u);
+    w.g_end = (uint32_t *)take(T * 4u);
+    w.g_begin = (uint32_t *)take(T * 4u);
+    w.first_base = (uint32_t *)take((T + 1u) * 4u);
+    w.order = n_order ? (uint32_t *)take(n_order * 4u) : nullptr;
+    w.sched = (uint32_t *)take(kAreaSchedWords * 4u);
+    char *t = tail ? take(256u) : nullptr;
+    w.qrows = (uint32_t *)t;
+    w.n_hits = t ? (unsigned long long *)(t + 8) : nullptr;
+    return off;
+}
+
 size_t area_mfma_workspace_bytes(uint32_t n_snps)
 {
-    const size_t T = n_slabs(n_snps);
-    return ((size_t)n_snps + 255u) / 256u * 256u + 2u * (((T + 1u) * 4u + 255u) / 256u * 256u) + 2u * ((T * 4u + 255u) / 256u * 256u) +
-           (area_order_entries(n_snps) * 4u + 255u) / 256u * 256u + kAreaSchedWords * 4u;
+    BandWs w;
+    return band_carve(w, nullptr, n_snps, false);
 }
+
+// the band kernel's K loop addresses the plane with 32-bit lane offsets
+static int band_plane_check(const char *who, uint32_t n_snps, uint32_t n_hap)
+{
+    if ((uint64_t)n_slabs(n_snps) * n_chunks(n_hap) * kSlab * 16u >= (1ull << 32)) {
+        set_error("%s: a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", who, n_snps, n_hap);
+        return LDX_E_UNSUPPORTED;
+    }
+    return LDX_OK;
+}
+
+// the whole-panel operators' plan: the two-row query list {0, n - 1} their init kernels wrote makes every SNP a query, so the
+// plan keeps, per j-tile, the rows with pos <= pos(last column) + window -- every pair with pos_i - pos_j <= window (|delta| =
+// window included); each operator's epilogue applies the exact symmetric bound per pair.  Zeroes `n_hits`.
+static int band_plan(const BandWs &w, uint32_t n_snps, const int64_t *positions, int64_t window, unsigned long long *n_hits,
+                     hipStream_t s)
+{
+    area_band_plan_kernel<<<1, 1024, 0, s>>>(positions, n_snps, n_slabs(n_snps), window, w.qrows, 2u, w.g_begin, w.g_end,
+                                             w.pass_base, n_hits, w.order, w.first_base, w.sched);
+    LDX_HIP(hipGetLastError());
+    return LDX_OK;
+}
+
+// the AreaArgs members that mean the same to every operator; is_query, hits, counts, hit_cap, k_thres and measure are each
+// operator's own
+static AreaArgs band_args(const BandWs &w, uint32_t n_hap, const int64_t *positions, int64_t flank, unsigned long long *n_hits)
+{
+    AreaArgs aa{};
+    aa.f32 = f32_const((double)n_hap);
+    aa.pos = positions;
+    aa.pass_base = w.pass_base;
+    aa.g_begin = w.g_begin;
+    aa.g_end = w.g_end;
+    aa.order = w.order;
+    aa.n_hits = n_hits;
+    aa.flank = (double)flank;
+    return aa;
+}
+
+// One band launch on two workgroups per CU.  kKernel: an instantiation of triangle_mfma_kernel with kArea, named once per
+// operator below.  Above 64 KiB the dynamic LDS size needs the opt-in attribute: once per device and instantiation.
+// n_obs: the observations per SNP (the haplotypes; the individuals for dosage, whose `fa` is gstat).
+template <auto kKernel>
+static int band_launch(const void *alt, const double *fa, const double *fr, const double *q, uint32_t n_snps, uint32_t n_hap,
+                       double n_obs, size_t lds, unsigned long long *stamps, const AreaArgs &aa, uint32_t *sched, hipStream_t s)
+{
+    static std::atomic<uint64_t> opted{0};
+    int dev = 0;
+    LDX_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !((opted.load(std::memory_order_relaxed) >> dev) & 1u)) {
+        LDX_HIP(hipFuncSetAttribute((const void *)kKernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (dev >= 0 && dev < 64) opted.fetch_or(1ull << dev, std::memory_order_relaxed);
+    }
+    const uint64_t units = ldx_triangle_units(n_snps) / 8u;   // 64-row units of the full triangle
+    kKernel<<<(uint32_t)device_cus() * 2u, kMfmaThreads, lds, s>>>(
+        (const uint4 *)alt, fa, fr, q, n_snps, n_slabs(n_snps), n_chunks(n_hap), n_obs, 1.0 / n_obs, 0, units * 8u,
+        (ldx_ld32 *)nullptr, nullptr, nullptr, 0u, 0u, 0u, sched, 0, stamps, aa);
+    LDX_HIP(hipGetLastError());
+    return LDX_OK;
+}
+
+template <bool kFp4>
+constexpr auto kAreaBand = triangle_mfma_kernel<false, false, true, kFp4>;
 
 int area_mfma(const void *alt, const double *fa, const double *fr, const double *q, uint32_t n_snps, uint32_t n_hap,
               const int64_t *positions, const uint32_t *queries, uint32_t n_query, int64_t flank, int measure, double thres,
               ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits, uint32_t *query_counts, void *workspace, bool fp4, hipStream_t s)
 {
-    const uint32_t T = n_slabs(n_snps), nch = n_chunks(n_hap);
-    if ((uint64_t)T * nch * kSlab * 16u >= (1ull << 32)) {   // the K loop addresses the plane with 32-bit lane offsets
-        set_error("ld_area on the matrix pipe: a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", n_snps, n_hap);
-        return kNoMatrixPath;
-    }
-    char *w = (char *)workspace;
-    uint8_t *is_query = (uint8_t *)w;
-    w += ((size_t)n_snps + 255u) / 256u * 256u;
-    uint32_t *pass_base = (uint32_t *)w;
-    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
-    uint32_t *g_end = (uint32_t *)w;
-    w += ((size_t)T * 4u + 255u) / 256u * 256u;
-    uint32_t *g_begin = (uint32_t *)w;
-    w += ((size_t)T * 4u + 255u) / 256u * 256u;
-    uint32_t *first_base = (uint32_t *)w;   // [T + 1] tiles with at least one pass before tile t
-    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
-    uint32_t *order = area_order_entries(n_snps) ? (uint32_t *)w : nullptr;
-    w += (area_order_entries(n_snps) * 4u + 255u) / 256u * 256u;
-    // The band's ticket counters: 256 words of THIS call's workspace, zeroed by the plan kernel in front of the band kernel
-    // (round 5, ADVICE r04: they used to be the (device, stream) slot of g_sched, and every ld_area plan graph -- captured
-    // on torch's one shared capture stream -- had the same slot baked in: two plans replayed on two streams at once shared
-    // their counters).  Concurrent scans need distinct workspaces anyway.
-    uint32_t *sched = (uint32_t *)w;
+    if (band_plane_check("ld_area on the matrix pipe", n_snps, n_hap)) return kNoMatrixPath;
+    BandWs w;
+    band_carve(w, workspace, n_snps, false);
     if (n_query == n_snps) {   // ascending distinct rows: every SNP is a query -- no mask at all
-        is_query = nullptr;
+        w.mask = nullptr;
     } else {
-        LDX_HIP(hipMemsetAsync(is_query, 0, n_snps, s));
-        area_mask_kernel<<<(n_query + 255u) / 256u, 256, 0, s>>>(queries, n_query, is_query);
+        LDX_HIP(hipMemsetAsync(w.mask, 0, n_snps, s));
+        area_mask_kernel<<<(n_query + 255u) / 256u, 256, 0, s>>>(queries, n_query, w.mask);
         LDX_HIP(hipGetLastError());
     }
-    area_band_plan_kernel<<<1, 1024, 0, s>>>(positions, n_snps, T, flank, queries, n_query, g_begin, g_end, pass_base,
-                                             (unsigned long long *)n_hits, order, first_base, sched);
+    area_band_plan_kernel<<<1, 1024, 0, s>>>(positions, n_snps, n_slabs(n_snps), flank, queries, n_query, w.g_begin, w.g_end,
+                                             w.pass_base, (unsigned long long *)n_hits, w.order, w.first_base, w.sched);
     LDX_HIP(hipGetLastError());
-    const size_t lds = mfma_lds_bytes(kRows64, false, true);
-    {   // above 64 KiB the dynamic LDS size needs the opt-in attribute: once per device
-        static std::atomic<uint64_t> opted{0};
-        int dev = 0;
-        LDX_HIP(hipGetDevice(&dev));
-        if (dev < 0 || dev >= 64 || !((opted.load(std::memory_order_relaxed) >> dev) & 1u)) {
-            LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<false, false, true, true>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<false, false, true, false>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            if (dev >= 0 && dev < 64) opted.fetch_or(1ull << dev, std::memory_order_relaxed);
-        }
-    }
-    const int cus = device_cus();
-    AreaArgs aa{};
-    aa.f32 = f32_const((double)n_hap);
-    aa.pos = positions;
-    aa.is_query = is_query;
-    aa.pass_base = pass_base;
-    aa.g_begin = g_begin;
-    aa.g_end = g_end;
-    aa.order = order;
+    AreaArgs aa = band_args(w, n_hap, positions, flank, (unsigned long long *)n_hits);
+    aa.is_query = w.mask;
     aa.hits = hits;
     aa.counts = query_counts;
-    aa.n_hits = (unsigned long long *)n_hits;
     aa.hit_cap = hit_cap;
-    aa.flank = (double)flank;
     aa.k_thres = thres_to_k(thres);
     aa.measure = measure;
-    const uint64_t units = ldx_triangle_units(n_snps) / 8u;   // 64-row units of the full triangle
+    const size_t lds = mfma_lds_bytes(kRows64, false, true);
     unsigned long long *stamps = nullptr;
 #ifdef LDX_TUNING   // in-kernel stamps of the band (env LDX_STAMPS=file), as in launch_mfma
+    const int cus = device_cus();
     const char *stamp_file = getenv("LDX_STAMPS");
     const size_t stamp_words = (size_t)cus * 2u * kMfmaWaves * kStampStride;
     if (stamp_file) {
@@ -2641,15 +2700,9 @@ int area_mfma(const void *alt, const double *fa, const double *fr, const double 
         LDX_HIP(hipMemsetAsync(stamps, 0, stamp_words * 8, s));
     }
 #endif
-    if (fp4)
-        triangle_mfma_kernel<false, false, true, true><<<(uint32_t)cus * 2u, kMfmaThreads, lds, s>>>(
-            (const uint4 *)alt, fa, fr, q, n_snps, T, nch, (double)n_hap, 1.0 / (double)n_hap, 0, units * 8u,
-            (ldx_ld32 *)nullptr, nullptr, nullptr, 0u, 0u, 0u, sched, 0, stamps, aa);
-    else
-        triangle_mfma_kernel<false, false, true, false><<<(uint32_t)cus * 2u, kMfmaThreads, lds, s>>>(
-            (const uint4 *)alt, fa, fr, q, n_snps, T, nch, (double)n_hap, 1.0 / (double)n_hap, 0, units * 8u,
-            (ldx_ld32 *)nullptr, nullptr, nullptr, 0u, 0u, 0u, sched, 0, nullptr, aa);
-    LDX_HIP(hipGetLastError());
+    const int rc = fp4 ? band_launch<kAreaBand<true>>(alt, fa, fr, q, n_snps, n_hap, (double)n_hap, lds, stamps, aa, w.sched, s)
+                       : band_launch<kAreaBand<false>>(alt, fa, fr, q, n_snps, n_hap, (double)n_hap, lds, nullptr, aa, w.sched, s);   // (the stamps are the FP4 flavour's)
+    if (rc != LDX_OK) return rc;
 #ifdef LDX_TUNING
     if (stamps) {   // tuning only: synchronous; the file holds the stamps of the LAST launch
         unsigned long long *h = (unsigned long long *)malloc(stamp_words * 8);
@@ -2700,28 +2753,15 @@ __global__ void cross_init_kernel(uint32_t n_snps, uint64_t *__restrict__ sides,
     sides[(size_t)i * 2u + 1u] = 0u;
 }
 
-// the band's workspace (area_mfma's layout) + 256 bytes: the two query rows and the plan kernel's (unused) hit counter
-size_t score_mfma_workspace_bytes(uint32_t n_snps) { return area_mfma_workspace_bytes(n_snps) + 256u; }
+// the band's workspace with its tail: the two query rows and the plan kernel's (unused) hit counter
+size_t score_mfma_workspace_bytes(uint32_t n_snps)
+{
+    BandWs w;
+    return band_carve(w, nullptr, n_snps);
+}
 
 template <bool kFp4, int kW, bool kCross = false, bool kDosage = false>
-static int launch_score(const void *alt, const double *fa, const double *fr, uint32_t n_snps, uint32_t n_hap, uint32_t T,
-                        uint32_t nch, uint64_t units, size_t lds, const AreaArgs &aa, uint32_t *sched, hipStream_t s)
-{
-    static std::atomic<uint64_t> opted{0};   // the dynamic LDS opt-in: once per device (72 KiB)
-    int dev = 0;
-    LDX_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !((opted.load(std::memory_order_relaxed) >> dev) & 1u)) {
-        LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, kW, false, 0, false, false, kCross, kDosage>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (dev >= 0 && dev < 64) opted.fetch_or(1ull << dev, std::memory_order_relaxed);
-    }
-    const double n_obs = kDosage ? (double)(n_hap / 2u) : (double)n_hap;   // dosage: `fa` is gstat, n the individuals
-    triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, kW, false, 0, false, false, kCross, kDosage><<<(uint32_t)device_cus() * 2u, kMfmaThreads, lds, s>>>(
-        (const uint4 *)alt, fa, fr, nullptr, n_snps, T, nch, n_obs, 1.0 / n_obs, 0, units * 8u,
-        (ldx_ld32 *)nullptr, nullptr, nullptr, 0u, 0u, 0u, sched, 0, nullptr, aa);
-    LDX_HIP(hipGetLastError());
-    return LDX_OK;
-}
+constexpr auto kScoreBand = triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, kW, false, 0, false, false, kCross, kDosage>;
 
 // the dosage band's own terms: r_ii = +1.0f (term 2^32) for v_i > 0, -0.0f (term 0) otherwise -- gstat[i][1] = 1 / sqrt(v_i) or 0
 __global__ void score_init_dosage_kernel(const double *__restrict__ gstat, const uint8_t *__restrict__ annot, uint32_t st,
@@ -2745,63 +2785,30 @@ int score_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, cons
                uint32_t n_annot, bool fp4, uint64_t *sums, void *workspace, hipStream_t s, bool cross = false,
                const char *who = "ldx_ld_score_dev", const double *gstat = nullptr)
 {
-    const uint32_t T = n_slabs(n_snps), nch = n_chunks(n_hap);
-    if ((uint64_t)T * nch * kSlab * 16u >= (1ull << 32)) {   // the K loop addresses the plane with 32-bit lane offsets
-        set_error("%s: a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", who, n_snps, n_hap);
-        return LDX_E_UNSUPPORTED;
-    }
-    // the band's buffers, carved as in area_mfma (its query mask stays unused)
-    char *w = (char *)workspace + ((size_t)n_snps + 255u) / 256u * 256u;
-    uint32_t *pass_base = (uint32_t *)w;
-    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
-    uint32_t *g_end = (uint32_t *)w;
-    w += ((size_t)T * 4u + 255u) / 256u * 256u;
-    uint32_t *g_begin = (uint32_t *)w;
-    w += ((size_t)T * 4u + 255u) / 256u * 256u;
-    uint32_t *first_base = (uint32_t *)w;
-    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
-    uint32_t *order = area_order_entries(n_snps) ? (uint32_t *)w : nullptr;
-    w += (area_order_entries(n_snps) * 4u + 255u) / 256u * 256u;
-    uint32_t *sched = (uint32_t *)w;
-    w += kAreaSchedWords * 4u;
-    uint32_t *qrows = (uint32_t *)w;                               // [2]
-    unsigned long long *n_hits = (unsigned long long *)(w + 8);   // the plan kernel zeroes it; nothing reads it
+    if (const int rc = band_plane_check(who, n_snps, n_hap)) return rc;
+    BandWs w;   // (the query mask stays unused)
+    band_carve(w, workspace, n_snps);
     const uint32_t st = 1u + n_annot;
-    if (cross) cross_init_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(n_snps, sums, qrows);
-    else if (gstat) score_init_dosage_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(gstat, n_annot ? annot : nullptr, st, n_snps, sums, qrows);
-    else score_init_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(acnt, rcnt, n_annot ? annot : nullptr, st, n_snps, n_hap, sums, qrows);
+    if (cross) cross_init_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(n_snps, sums, w.qrows);
+    else if (gstat) score_init_dosage_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(gstat, n_annot ? annot : nullptr, st, n_snps, sums, w.qrows);
+    else score_init_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(acnt, rcnt, n_annot ? annot : nullptr, st, n_snps, n_hap, sums, w.qrows);
     LDX_HIP(hipGetLastError());
     if (n_snps < 2) return LDX_OK;   // no pairs
-    // the plan keeps, per j-tile, the rows with pos <= pos(last column) + window: every pair with pos_i - pos_j <= window
-    // (|delta| = window included); score_epilogue applies the exact symmetric bound per pair
-    area_band_plan_kernel<<<1, 1024, 0, s>>>(positions, n_snps, T, window, qrows, 2u, g_begin, g_end, pass_base, n_hits,
-                                             order, first_base, sched);
-    LDX_HIP(hipGetLastError());
-    AreaArgs aa{};
-    aa.f32 = f32_const((double)n_hap);
-    aa.pos = positions;
+    if (const int rc = band_plan(w, n_snps, positions, window, w.n_hits, s)) return rc;   // (nothing reads the hit counter)
+    AreaArgs aa = band_args(w, n_hap, positions, window, w.n_hits);
     aa.is_query = n_annot ? annot : nullptr;   // score: the annotation masks (null: none)
-    aa.pass_base = pass_base;
-    aa.g_begin = g_begin;
-    aa.g_end = g_end;
-    aa.order = order;
     aa.hits = (ldx_hit *)sums;                 // score: the uint64 sums [n_snps][1 + n_annot]
-    aa.n_hits = n_hits;
-    aa.flank = (double)window;
     aa.measure = (int)n_annot;                 // score: K
-    const uint64_t units = ldx_triangle_units(n_snps) / 8u;   // 64-row units of the full triangle
     const size_t lds = mfma_lds_bytes(kRows64, false, false) + (size_t)kMfmaWaves * kRows64 * 9u * sizeof(uint64_t);   // + the row tables
-    if (gstat)
-        return n_annot ? launch_score<true, 3, false, true>(alt, gstat, nullptr, n_snps, n_hap, T, nch, units, lds, aa, sched, s)
-                       : launch_score<true, 1, false, true>(alt, gstat, nullptr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
-    if (cross)
-        return fp4 ? launch_score<true, 1, true>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s)
-                   : launch_score<false, 1, true>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
-    if (fp4)
-        return n_annot ? launch_score<true, 3>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s)
-                       : launch_score<true, 1>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
-    return n_annot ? launch_score<false, 3>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s)
-                   : launch_score<false, 1>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
+    const double n_obs = gstat ? (double)(n_hap / 2u) : (double)n_hap;   // dosage: gstat in `fa`'s place, n the individuals
+#define LDX_GO(...)                                                                                                  \
+    band_launch<kScoreBand<__VA_ARGS__>>(alt, gstat ? gstat : fa, gstat ? nullptr : fr, nullptr, n_snps, n_hap, n_obs, lds, \
+                                         nullptr, aa, w.sched, s)
+    if (gstat) return n_annot ? LDX_GO(true, 3, false, true) : LDX_GO(true, 1, false, true);
+    if (cross) return fp4 ? LDX_GO(true, 1, true) : LDX_GO(false, 1, true);
+    if (fp4) return n_annot ? LDX_GO(true, 3) : LDX_GO(true, 1);
+    return n_annot ? LDX_GO(false, 3) : LDX_GO(false, 1);
+#undef LDX_GO
 }
 
 // ---- LD decay on the band (ldx_ld_decay_dev) ---------------------------------------------------------------------------
@@ -2829,76 +2836,29 @@ __global__ void decay_init_kernel(const uint32_t *__restrict__ acnt, const uint3
 size_t decay_mfma_workspace_bytes(uint32_t n_snps) { return score_mfma_workspace_bytes(n_snps); }
 
 template <bool kFp4>
-static int launch_decay(const void *alt, const double *fa, const double *fr, uint32_t n_snps, uint32_t n_hap, uint32_t T,
-                        uint32_t nch, uint64_t units, size_t lds, const AreaArgs &aa, uint32_t *sched, hipStream_t s)
-{
-    static std::atomic<uint64_t> opted{0};   // the dynamic LDS opt-in: once per device (70 KiB)
-    int dev = 0;
-    LDX_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !((opted.load(std::memory_order_relaxed) >> dev) & 1u)) {
-        LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, false, 0, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (dev >= 0 && dev < 64) opted.fetch_or(1ull << dev, std::memory_order_relaxed);
-    }
-    triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, false, 0, true><<<(uint32_t)device_cus() * 2u, kMfmaThreads, lds, s>>>(
-        (const uint4 *)alt, fa, fr, nullptr, n_snps, T, nch, (double)n_hap, 1.0 / (double)n_hap, 0, units * 8u,
-        (ldx_ld32 *)nullptr, nullptr, nullptr, 0u, 0u, 0u, sched, 0, nullptr, aa);
-    LDX_HIP(hipGetLastError());
-    return LDX_OK;
-}
+constexpr auto kDecayBand = triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, false, 0, true>;
 
 int decay_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
                uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, int64_t bin_width,
                const uint8_t *keep, bool fp4, uint64_t *sums, uint64_t *counts, uint32_t n_bins, void *workspace, hipStream_t s)
 {
-    const uint32_t T = n_slabs(n_snps), nch = n_chunks(n_hap);
-    if ((uint64_t)T * nch * kSlab * 16u >= (1ull << 32)) {   // the K loop addresses the plane with 32-bit lane offsets
-        set_error("ldx_ld_decay_dev: a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", n_snps, n_hap);
-        return LDX_E_UNSUPPORTED;
-    }
-    // the band's buffers, carved as in score_mfma; the query mask's bytes hold the effective keep mask
-    uint8_t *mask = (uint8_t *)workspace;
-    char *w = (char *)workspace + ((size_t)n_snps + 255u) / 256u * 256u;
-    uint32_t *pass_base = (uint32_t *)w;
-    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
-    uint32_t *g_end = (uint32_t *)w;
-    w += ((size_t)T * 4u + 255u) / 256u * 256u;
-    uint32_t *g_begin = (uint32_t *)w;
-    w += ((size_t)T * 4u + 255u) / 256u * 256u;
-    uint32_t *first_base = (uint32_t *)w;
-    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
-    uint32_t *order = area_order_entries(n_snps) ? (uint32_t *)w : nullptr;
-    w += (area_order_entries(n_snps) * 4u + 255u) / 256u * 256u;
-    uint32_t *sched = (uint32_t *)w;
-    w += kAreaSchedWords * 4u;
-    uint32_t *qrows = (uint32_t *)w;                               // [2]
-    unsigned long long *n_hits = (unsigned long long *)(w + 8);   // the plan kernel zeroes it; nothing reads it
+    if (const int rc = band_plane_check("ldx_ld_decay_dev", n_snps, n_hap)) return rc;
+    BandWs w;   // (the query mask's bytes hold the effective keep mask)
+    band_carve(w, workspace, n_snps);
     const uint32_t n_init = n_snps > n_bins ? n_snps : n_bins;
-    decay_init_kernel<<<(n_init + 255u) / 256u, 256, 0, s>>>(acnt, rcnt, keep, n_snps, mask, sums, counts, n_bins, qrows);
+    decay_init_kernel<<<(n_init + 255u) / 256u, 256, 0, s>>>(acnt, rcnt, keep, n_snps, w.mask, sums, counts, n_bins, w.qrows);
     LDX_HIP(hipGetLastError());
     if (n_snps < 2) return LDX_OK;   // no pairs
-    // the score band's plan: every SNP a query, flank = window; decay_epilogue applies the exact bound per pair
-    area_band_plan_kernel<<<1, 1024, 0, s>>>(positions, n_snps, T, window, qrows, 2u, g_begin, g_end, pass_base, n_hits,
-                                             order, first_base, sched);
-    LDX_HIP(hipGetLastError());
-    AreaArgs aa{};
-    aa.f32 = f32_const((double)n_hap);
-    aa.pos = positions;
-    aa.is_query = mask;                        // decay: the effective keep mask
-    aa.pass_base = pass_base;
-    aa.g_begin = g_begin;
-    aa.g_end = g_end;
-    aa.order = order;
+    if (const int rc = band_plan(w, n_snps, positions, window, w.n_hits, s)) return rc;   // (nothing reads the hit counter)
+    AreaArgs aa = band_args(w, n_hap, positions, window, w.n_hits);
+    aa.is_query = w.mask;                      // decay: the effective keep mask
     aa.hits = (ldx_hit *)sums;                 // decay: the uint64 sums [n_bins]
     aa.counts = (uint32_t *)counts;            // decay: the uint64 counts [n_bins]
-    aa.n_hits = n_hits;
-    aa.flank = (double)window;
     aa.k_thres = (double)bin_width;            // decay: the bin width (<= 2^52 + 1: exact)
     aa.measure = (int)n_bins;
-    const uint64_t units = ldx_triangle_units(n_snps) / 8u;   // 64-row units of the full triangle
     const size_t lds = mfma_lds_bytes(kRows64, false, false) + (size_t)n_bins * 2u * sizeof(uint64_t);   // + the histogram
-    return fp4 ? launch_decay<true>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s)
-               : launch_decay<false>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
+    return fp4 ? band_launch<kDecayBand<true>>(alt, fa, fr, nullptr, n_snps, n_hap, (double)n_hap, lds, nullptr, aa, w.sched, s)
+               : band_launch<kDecayBand<false>>(alt, fa, fr, nullptr, n_snps, n_hap, (double)n_hap, lds, nullptr, aa, w.sched, s);
 }
 
 // ---- four-gamete test on the band (ldx_ld_fgt_dev) ---------------------------------------------------------------------
@@ -2922,74 +2882,27 @@ __global__ void fgt_init_kernel(const uint8_t *__restrict__ keep, uint32_t n_snp
 size_t fgt_mfma_workspace_bytes(uint32_t n_snps) { return score_mfma_workspace_bytes(n_snps); }
 
 template <bool kFp4>
-static int launch_fgt(const void *alt, uint32_t n_snps, uint32_t n_hap, uint32_t T, uint32_t nch, uint64_t units, size_t lds,
-                      const AreaArgs &aa, uint32_t *sched, hipStream_t s)
-{
-    static std::atomic<uint64_t> opted{0};   // the dynamic LDS opt-in: once per device
-    int dev = 0;
-    LDX_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !((opted.load(std::memory_order_relaxed) >> dev) & 1u)) {
-        LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, false, 0, false, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (dev >= 0 && dev < 64) opted.fetch_or(1ull << dev, std::memory_order_relaxed);
-    }
-    // (fa / fr / q stay null: the four-gamete instantiation stages the ALT counts from aa.counts and reads no frequency)
-    triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, false, 0, false, true><<<(uint32_t)device_cus() * 2u, kMfmaThreads, lds, s>>>(
-        (const uint4 *)alt, nullptr, nullptr, nullptr, n_snps, T, nch, (double)n_hap, 1.0 / (double)n_hap, 0, units * 8u,
-        (ldx_ld32 *)nullptr, nullptr, nullptr, 0u, 0u, 0u, sched, 0, nullptr, aa);
-    LDX_HIP(hipGetLastError());
-    return LDX_OK;
-}
+constexpr auto kFgtBand = triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, false, 0, false, true>;
 
 int fgt_mfma(const void *alt, const uint32_t *acnt, uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window,
              uint32_t min_count, const uint8_t *keep, bool fp4, uint32_t *left, void *workspace, hipStream_t s)
 {
-    const uint32_t T = n_slabs(n_snps), nch = n_chunks(n_hap);
-    if ((uint64_t)T * nch * kSlab * 16u >= (1ull << 32)) {   // the K loop addresses the plane with 32-bit lane offsets
-        set_error("ldx_ld_fgt_dev: a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", n_snps, n_hap);
-        return LDX_E_UNSUPPORTED;
-    }
-    // the band's buffers, carved as in score_mfma; the query mask's bytes hold the keep mask
-    uint8_t *mask = (uint8_t *)workspace;
-    char *w = (char *)workspace + ((size_t)n_snps + 255u) / 256u * 256u;
-    uint32_t *pass_base = (uint32_t *)w;
-    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
-    uint32_t *g_end = (uint32_t *)w;
-    w += ((size_t)T * 4u + 255u) / 256u * 256u;
-    uint32_t *g_begin = (uint32_t *)w;
-    w += ((size_t)T * 4u + 255u) / 256u * 256u;
-    uint32_t *first_base = (uint32_t *)w;
-    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
-    uint32_t *order = area_order_entries(n_snps) ? (uint32_t *)w : nullptr;
-    w += (area_order_entries(n_snps) * 4u + 255u) / 256u * 256u;
-    uint32_t *sched = (uint32_t *)w;
-    w += kAreaSchedWords * 4u;
-    uint32_t *qrows = (uint32_t *)w;                               // [2]
-    unsigned long long *n_hits = (unsigned long long *)(w + 8);   // the plan kernel zeroes it; nothing reads it
-    fgt_init_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(keep, n_snps, mask, left, qrows);
+    if (const int rc = band_plane_check("ldx_ld_fgt_dev", n_snps, n_hap)) return rc;
+    BandWs w;   // (the query mask's bytes hold the keep mask)
+    band_carve(w, workspace, n_snps);
+    fgt_init_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(keep, n_snps, w.mask, left, w.qrows);
     LDX_HIP(hipGetLastError());
     if (n_snps < 2) return LDX_OK;   // no pairs
-    // the score band's plan: every SNP a query, flank = window; fgt_epilogue applies the exact bound per pair
-    area_band_plan_kernel<<<1, 1024, 0, s>>>(positions, n_snps, T, window, qrows, 2u, g_begin, g_end, pass_base, n_hits,
-                                             order, first_base, sched);
-    LDX_HIP(hipGetLastError());
-    AreaArgs aa{};
-    aa.f32 = f32_const((double)n_hap);
-    aa.pos = positions;
-    aa.is_query = mask;                        // fgt: the keep mask
-    aa.pass_base = pass_base;
-    aa.g_begin = g_begin;
-    aa.g_end = g_end;
-    aa.order = order;
+    if (const int rc = band_plan(w, n_snps, positions, window, w.n_hits, s)) return rc;   // (nothing reads the hit counter)
+    AreaArgs aa = band_args(w, n_hap, positions, window, w.n_hits);
+    aa.is_query = w.mask;                      // fgt: the keep mask
     aa.hits = (ldx_hit *)left;                 // fgt: the uint32 words left[n_snps]
     aa.counts = const_cast<uint32_t *>(acnt);  // fgt: the ALT counts (read only)
-    aa.n_hits = n_hits;
-    aa.flank = (double)window;
     aa.measure = (int)min_count;               // fgt: the smallest gamete count of a recombinant pair (<= n_hap)
-    const uint64_t units = ldx_triangle_units(n_snps) / 8u;   // 64-row units of the full triangle
     const size_t lds = mfma_lds_bytes(kRows64, false, false);
-    return fp4 ? launch_fgt<true>(alt, n_snps, n_hap, T, nch, units, lds, aa, sched, s)
-               : launch_fgt<false>(alt, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
+    // (fa / fr / q stay null: the four-gamete instantiation stages the ALT counts from aa.counts and reads no frequency)
+    return fp4 ? band_launch<kFgtBand<true>>(alt, nullptr, nullptr, nullptr, n_snps, n_hap, (double)n_hap, lds, nullptr, aa, w.sched, s)
+               : band_launch<kFgtBand<false>>(alt, nullptr, nullptr, nullptr, n_snps, n_hap, (double)n_hap, lds, nullptr, aa, w.sched, s);
 }
 
 // ---- matrix-vector products on the band (ldx_ld_matvec_dev) ------------------------------------------------------------
@@ -3020,76 +2933,29 @@ constexpr int kProdSweep = 2;   // right-hand sides per sweep of the accumulator
 static_assert(8 % kProdSweep == 0, "a sweep's row-weight reads stay inside the row's eight");
 
 template <bool kFp4>
-static int launch_prod(const void *alt, const double *fa, const double *fr, uint32_t n_snps, uint32_t n_hap, uint32_t T,
-                       uint32_t nch, uint64_t units, size_t lds, const AreaArgs &aa, uint32_t *sched, hipStream_t s)
-{
-    static std::atomic<uint64_t> opted{0};   // the dynamic LDS opt-in: once per device (78 KiB)
-    int dev = 0;
-    LDX_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !((opted.load(std::memory_order_relaxed) >> dev) & 1u)) {
-        LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, false, kProdSweep>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (dev >= 0 && dev < 64) opted.fetch_or(1ull << dev, std::memory_order_relaxed);
-    }
-    triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, false, kProdSweep><<<(uint32_t)device_cus() * 2u, kMfmaThreads, lds, s>>>(
-        (const uint4 *)alt, fa, fr, nullptr, n_snps, T, nch, (double)n_hap, 1.0 / (double)n_hap, 0, units * 8u,
-        (ldx_ld32 *)nullptr, nullptr, nullptr, 0u, 0u, 0u, sched, 0, nullptr, aa);
-    LDX_HIP(hipGetLastError());
-    return LDX_OK;
-}
+constexpr auto kProdBand = triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, false, kProdSweep>;
 
 int prod_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
               uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, const float *x, uint32_t n_rhs,
               bool square, bool fp4, int64_t *sums, void *workspace, hipStream_t s)
 {
-    const uint32_t T = n_slabs(n_snps), nch = n_chunks(n_hap);
-    if ((uint64_t)T * nch * kSlab * 16u >= (1ull << 32)) {   // the K loop addresses the plane with 32-bit lane offsets
-        set_error("ldx_ld_matvec_dev: a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", n_snps, n_hap);
-        return LDX_E_UNSUPPORTED;
-    }
-    // the band's buffers, carved as in score_mfma
-    char *w = (char *)workspace + ((size_t)n_snps + 255u) / 256u * 256u;
-    uint32_t *pass_base = (uint32_t *)w;
-    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
-    uint32_t *g_end = (uint32_t *)w;
-    w += ((size_t)T * 4u + 255u) / 256u * 256u;
-    uint32_t *g_begin = (uint32_t *)w;
-    w += ((size_t)T * 4u + 255u) / 256u * 256u;
-    uint32_t *first_base = (uint32_t *)w;
-    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
-    uint32_t *order = area_order_entries(n_snps) ? (uint32_t *)w : nullptr;
-    w += (area_order_entries(n_snps) * 4u + 255u) / 256u * 256u;
-    uint32_t *sched = (uint32_t *)w;
-    w += kAreaSchedWords * 4u;
-    uint32_t *qrows = (uint32_t *)w;                               // [2]
-    unsigned long long *n_hits = (unsigned long long *)(w + 8);   // the plan kernel zeroes it; nothing reads it
-    prod_init_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(acnt, rcnt, x, n_rhs, square, n_snps, n_hap, (uint64_t *)sums, qrows);
+    if (const int rc = band_plane_check("ldx_ld_matvec_dev", n_snps, n_hap)) return rc;
+    BandWs w;   // (the query mask stays unused)
+    band_carve(w, workspace, n_snps);
+    prod_init_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(acnt, rcnt, x, n_rhs, square, n_snps, n_hap, (uint64_t *)sums, w.qrows);
     LDX_HIP(hipGetLastError());
     if (n_snps < 2) return LDX_OK;   // no pairs
-    // the plan keeps every pair with pos_i - pos_j <= window, as for the scores; prod_epilogue applies the exact bound per pair
-    area_band_plan_kernel<<<1, 1024, 0, s>>>(positions, n_snps, T, window, qrows, 2u, g_begin, g_end, pass_base, n_hits,
-                                             order, first_base, sched);
-    LDX_HIP(hipGetLastError());
-    AreaArgs aa{};
-    aa.f32 = f32_const((double)n_hap);
-    aa.pos = positions;
-    aa.is_query = nullptr;
-    aa.pass_base = pass_base;
-    aa.g_begin = g_begin;
-    aa.g_end = g_end;
-    aa.order = order;
+    if (const int rc = band_plan(w, n_snps, positions, window, w.n_hits, s)) return rc;   // (nothing reads the hit counter)
+    AreaArgs aa = band_args(w, n_hap, positions, window, w.n_hits);
     aa.hits = (ldx_hit *)sums;                                         // products: the int64 sums [n_snps][n_rhs]
     aa.counts = reinterpret_cast<uint32_t *>(const_cast<float *>(x));   // products: the float32 weights [n_snps][n_rhs] (read only)
-    aa.n_hits = n_hits;
-    aa.flank = (double)window;
     aa.measure = (int)(n_rhs | (square ? 16u : 0u));                   // products: n_rhs, bit 4 = power 2
-    const uint64_t units = ldx_triangle_units(n_snps) / 8u;   // 64-row units of the full triangle
     // + the row-sum tables [4][64][8] uint64 and the row-weight tables [4][64][8] float32
     const size_t lds = mfma_lds_bytes(kRows64, false, false) + (size_t)kMfmaWaves * kRows64 * 8u * (sizeof(uint64_t) + sizeof(float));
     static_assert(2u * (mfma_lds_bytes(kRows64, false, false) + (size_t)kMfmaWaves * kRows64 * 8u * 12u) <= 160u * 1024u,
                   "two workgroups per CU");
-    if (fp4) return launch_prod<true>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
-    return launch_prod<false>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
+    return fp4 ? band_launch<kProdBand<true>>(alt, fa, fr, nullptr, n_snps, n_hap, (double)n_hap, lds, nullptr, aa, w.sched, s)
+               : band_launch<kProdBand<false>>(alt, fa, fr, nullptr, n_snps, n_hap, (double)n_hap, lds, nullptr, aa, w.sched, s);
 }
 
 // ---- neighbour lists on the band (ldx_ld_neighbors_dev) ----------------------------------------------------------------
@@ -3102,119 +2968,51 @@ __global__ void nbr_init_kernel(uint32_t n_snps, uint32_t *__restrict__ qrows)
     }
 }
 
-// the band's workspace (area_mfma's layout) + 256 bytes: the two query rows
-size_t nbr_mfma_workspace_bytes(uint32_t n_snps) { return area_mfma_workspace_bytes(n_snps) + 256u; }
+// the score band's workspace (the tail's hit counter stays unused: the caller's n_hits is the slot counter)
+size_t nbr_mfma_workspace_bytes(uint32_t n_snps) { return score_mfma_workspace_bytes(n_snps); }
 
 template <bool kFp4, bool kDosage = false>
-static int launch_nbr(const void *alt, const double *fa, const double *fr, uint32_t n_snps, uint32_t n_hap, uint32_t T,
-                      uint32_t nch, uint64_t units, size_t lds, const AreaArgs &aa, uint32_t *sched, hipStream_t s)
-{
-    static std::atomic<uint64_t> opted{0};   // the dynamic LDS opt-in: once per device
-    int dev = 0;
-    LDX_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !((opted.load(std::memory_order_relaxed) >> dev) & 1u)) {
-        LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, true, 0, false, false, false, kDosage>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (dev >= 0 && dev < 64) opted.fetch_or(1ull << dev, std::memory_order_relaxed);
-    }
-    const double n_obs = kDosage ? (double)(n_hap / 2u) : (double)n_hap;   // dosage: `fa` is gstat, n the individuals
-    triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, true, 0, false, false, false, kDosage><<<(uint32_t)device_cus() * 2u, kMfmaThreads, lds, s>>>(
-        (const uint4 *)alt, fa, fr, nullptr, n_snps, T, nch, n_obs, 1.0 / n_obs, 0, units * 8u,
-        (ldx_ld32 *)nullptr, nullptr, nullptr, 0u, 0u, 0u, sched, 0, nullptr, aa);
-    LDX_HIP(hipGetLastError());
-    return LDX_OK;
-}
+constexpr auto kNbrBand = triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, true, 0, false, false, false, kDosage>;
 
 int nbr_mfma(const void *alt, const double *fa, const double *fr, uint32_t n_snps, uint32_t n_hap, const int64_t *positions,
              int64_t window, float r2_bound, bool fp4, ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits, uint32_t *row_counts,
              void *workspace, hipStream_t s, const char *who = "ldx_ld_neighbors_dev", const double *gstat = nullptr)
 {
-    const uint32_t T = n_slabs(n_snps), nch = n_chunks(n_hap);
-    if ((uint64_t)T * nch * kSlab * 16u >= (1ull << 32)) {   // the K loop addresses the plane with 32-bit lane offsets
-        set_error("%s: a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", who, n_snps, n_hap);
-        return LDX_E_UNSUPPORTED;
-    }
+    if (const int rc = band_plane_check(who, n_snps, n_hap)) return rc;
     if (row_counts) LDX_HIP(hipMemsetAsync(row_counts, 0, ((size_t)n_snps + 1u) * 4u, s));
     if (n_snps < 2) {   // no pairs: no plan kernel to zero the slot counter
         LDX_HIP(hipMemsetAsync(n_hits, 0, sizeof(uint64_t), s));
         return LDX_OK;
     }
-    // the band's buffers, carved as in area_mfma (its query mask stays unused)
-    char *w = (char *)workspace + ((size_t)n_snps + 255u) / 256u * 256u;
-    uint32_t *pass_base = (uint32_t *)w;
-    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
-    uint32_t *g_end = (uint32_t *)w;
-    w += ((size_t)T * 4u + 255u) / 256u * 256u;
-    uint32_t *g_begin = (uint32_t *)w;
-    w += ((size_t)T * 4u + 255u) / 256u * 256u;
-    uint32_t *first_base = (uint32_t *)w;
-    w += (((size_t)T + 1u) * 4u + 255u) / 256u * 256u;
-    uint32_t *order = area_order_entries(n_snps) ? (uint32_t *)w : nullptr;
-    w += (area_order_entries(n_snps) * 4u + 255u) / 256u * 256u;
-    uint32_t *sched = (uint32_t *)w;
-    w += kAreaSchedWords * 4u;
-    uint32_t *qrows = (uint32_t *)w;   // [2]
-    nbr_init_kernel<<<1, 64, 0, s>>>(n_snps, qrows);
+    BandWs w;   // (the query mask stays unused)
+    band_carve(w, workspace, n_snps);
+    nbr_init_kernel<<<1, 64, 0, s>>>(n_snps, w.qrows);
     LDX_HIP(hipGetLastError());
-    // the plan keeps, per j-tile, the rows with pos <= pos(last column) + window (|delta| = window included), and zeroes the
-    // slot counter; nbr_epilogue applies the exact symmetric bound per pair
-    area_band_plan_kernel<<<1, 1024, 0, s>>>(positions, n_snps, T, window, qrows, 2u, g_begin, g_end, pass_base,
-                                             (unsigned long long *)n_hits, order, first_base, sched);
-    LDX_HIP(hipGetLastError());
-    AreaArgs aa{};
-    aa.f32 = f32_const((double)n_hap);
-    aa.pos = positions;
-    aa.is_query = nullptr;
-    aa.pass_base = pass_base;
-    aa.g_begin = g_begin;
-    aa.g_end = g_end;
-    aa.order = order;
+    if (const int rc = band_plan(w, n_snps, positions, window, (unsigned long long *)n_hits, s)) return rc;   // (zeroes the slot counter)
+    AreaArgs aa = band_args(w, n_hap, positions, window, (unsigned long long *)n_hits);
     aa.hits = hits;
     aa.counts = row_counts;
-    aa.n_hits = (unsigned long long *)n_hits;
     aa.hit_cap = hit_cap;
-    aa.flank = (double)window;
     aa.k_thres = (double)r2_bound;   // neighbours: the float32 bound b on s = r *f32 r
-    const uint64_t units = ldx_triangle_units(n_snps) / 8u;   // 64-row units of the full triangle
     const size_t lds = mfma_lds_bytes(kRows64, false, false);
-    if (gstat) return launch_nbr<true, true>(alt, gstat, nullptr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);   // (ldx_ld_neighbors_dosage_dev)
-    if (fp4) return launch_nbr<true>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
-    return launch_nbr<false>(alt, fa, fr, n_snps, n_hap, T, nch, units, lds, aa, sched, s);
+    if (gstat)   // (ldx_ld_neighbors_dosage_dev) `fa` is gstat, n the individuals
+        return band_launch<kNbrBand<true, true>>(alt, gstat, nullptr, nullptr, n_snps, n_hap, (double)(n_hap / 2u), lds, nullptr, aa, w.sched, s);
+    return fp4 ? band_launch<kNbrBand<true>>(alt, fa, fr, nullptr, n_snps, n_hap, (double)n_hap, lds, nullptr, aa, w.sched, s)
+               : band_launch<kNbrBand<false>>(alt, fa, fr, nullptr, n_snps, n_hap, (double)n_hap, lds, nullptr, aa, w.sched, s);
 }
 
 }  // namespace ldx
 
-extern "C" size_t ldx_ld_neighbors_workspace_bytes(uint32_t n_snps, uint32_t n_hap)
-{
-    (void)n_hap;   // (the layout depends on the SNP count alone)
-    return ldx::nbr_mfma_workspace_bytes(n_snps ? n_snps : 1u);
-}
-
-extern "C" int ldx_ld_neighbors_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa,
-                                    const double *fr, uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window,
-                                    float r2_bound, int path, ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits,
-                                    uint32_t *row_counts, void *workspace, size_t workspace_bytes, void *stream)
-{
-    LDX_REQUIRE(alt && acnt && rcnt && fa && fr && positions && n_hits && workspace, "null pointer");
-    LDX_REQUIRE(hits || hit_cap == 0, "hits is null but hit_cap > 0");
-    LDX_REQUIRE(n_snps >= 1 && n_hap >= 1 && window >= 0, "bad shape");
-    LDX_REQUIRE(r2_bound > 0.0f, "r2_bound must be > 0 (and not NaN)");
-    LDX_REQUIRE(hit_cap < (1ull << 32), "hit_cap must be < 2^32 (the finished CSR's offsets are uint32)");
-    LDX_REQUIRE(((uintptr_t)workspace & 255u) == 0, "workspace must be 256-byte aligned");
-    LDX_REQUIRE(workspace_bytes >= ldx::nbr_mfma_workspace_bytes(n_snps), "workspace too small (see ldx_ld_neighbors_workspace_bytes)");
-    LDX_REQUIRE(path == LDX_PATH_AUTO || path == LDX_PATH_POPCOUNT || path == LDX_PATH_MFMA || path == LDX_PATH_FP4, "unknown path");
-    if (n_hap > LDX_MAX_HAPS) {
-        ldx::set_error("ldx_ld_neighbors_dev: n_hap %u > LDX_MAX_HAPS %u", n_hap, LDX_MAX_HAPS);
-        return LDX_E_UNSUPPORTED;
-    }
-    if (path == LDX_PATH_POPCOUNT) {
-        ldx::set_error("ldx_ld_neighbors_dev: neighbour lists run on the matrix-pipe band (LDX_PATH_FP4 / LDX_PATH_MFMA), not on the popcount kernels");
-        return LDX_E_UNSUPPORTED;
-    }
-    const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles: keep pos + window exact
-    return ldx::nbr_mfma(alt, fa, fr, n_snps, n_hap, positions, window < wmax ? window : wmax, r2_bound, path != LDX_PATH_MFMA,
-                         hits, hit_cap, n_hits, row_counts, workspace, (hipStream_t)stream);
-}
+// the band entries' workspace sizes: the layout depends on the SNP count alone
+#define LDX_BAND_WORKSPACE_BYTES(entry, size_fn) \
+    extern "C" size_t entry(uint32_t n_snps, uint32_t n_hap) { (void)n_hap; return ldx::size_fn(n_snps ? n_snps : 1u); }
+LDX_BAND_WORKSPACE_BYTES(ldx_ld_neighbors_workspace_bytes, nbr_mfma_workspace_bytes)
+LDX_BAND_WORKSPACE_BYTES(ldx_ld_matvec_workspace_bytes, prod_mfma_workspace_bytes)
+LDX_BAND_WORKSPACE_BYTES(ldx_ld_decay_workspace_bytes, decay_mfma_workspace_bytes)
+LDX_BAND_WORKSPACE_BYTES(ldx_ld_fgt_workspace_bytes, fgt_mfma_workspace_bytes)
+LDX_BAND_WORKSPACE_BYTES(ldx_ld_score_workspace_bytes, score_mfma_workspace_bytes)
+LDX_BAND_WORKSPACE_BYTES(ldx_ld_cross_workspace_bytes, score_mfma_workspace_bytes)
+#undef LDX_BAND_WORKSPACE_BYTES
 
 // the dosage entries' shared argument rules: an even number of haplotypes within LDX_MAX_HAPS, the FP4 kernel only
 static int dosage_args_ok(const char *who, uint32_t n_hap, int path)
@@ -3234,6 +3032,50 @@ static int dosage_args_ok(const char *who, uint32_t n_hap, int path)
     return LDX_OK;
 }
 
+// The band entries' shared argument rules, after each entry's own: the workspace (`need` bytes, `size_fn` names the entry's
+// *_workspace_bytes), the path, n_hap within LDX_MAX_HAPS and no popcount band (`what` runs on the matrix pipe; null: a dosage
+// entry, dosage_args_ok's rules instead).  Then clamps *window: positions and window travel as doubles, keep pos + window exact.
+static int band_args_ok(const char *who, const void *workspace, size_t workspace_bytes, size_t need, const char *size_fn,
+                        uint32_t n_hap, int path, const char *what, int64_t *window)
+{
+    auto fail = [&](const char *msg) { ldx::set_error("%s: %s", who, msg); return LDX_E_ARG; };
+    if (((uintptr_t)workspace & 255u) != 0) return fail("workspace must be 256-byte aligned");
+    if (workspace_bytes < need) {
+        ldx::set_error("%s: workspace too small (see %s)", who, size_fn);
+        return LDX_E_ARG;
+    }
+    if (path != LDX_PATH_AUTO && path != LDX_PATH_POPCOUNT && path != LDX_PATH_MFMA && path != LDX_PATH_FP4) return fail("unknown path");
+    if (!what) {
+        if (const int rc = dosage_args_ok(who, n_hap, path)) return rc;
+    } else if (n_hap > LDX_MAX_HAPS) {
+        ldx::set_error("%s: n_hap %u > LDX_MAX_HAPS %u", who, n_hap, LDX_MAX_HAPS);
+        return LDX_E_UNSUPPORTED;
+    } else if (path == LDX_PATH_POPCOUNT) {
+        ldx::set_error("%s: %s on the matrix-pipe band (LDX_PATH_FP4 / LDX_PATH_MFMA), not on the popcount kernels", who, what);
+        return LDX_E_UNSUPPORTED;
+    }
+    const int64_t wmax = (int64_t)1 << 52;
+    if (*window > wmax) *window = wmax;
+    return LDX_OK;
+}
+
+extern "C" int ldx_ld_neighbors_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa,
+                                    const double *fr, uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window,
+                                    float r2_bound, int path, ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits,
+                                    uint32_t *row_counts, void *workspace, size_t workspace_bytes, void *stream)
+{
+    LDX_REQUIRE(alt && acnt && rcnt && fa && fr && positions && n_hits && workspace, "null pointer");
+    LDX_REQUIRE(hits || hit_cap == 0, "hits is null but hit_cap > 0");
+    LDX_REQUIRE(n_snps >= 1 && n_hap >= 1 && window >= 0, "bad shape");
+    LDX_REQUIRE(r2_bound > 0.0f, "r2_bound must be > 0 (and not NaN)");
+    LDX_REQUIRE(hit_cap < (1ull << 32), "hit_cap must be < 2^32 (the finished CSR's offsets are uint32)");
+    if (const int rc = band_args_ok(__func__, workspace, workspace_bytes, ldx::nbr_mfma_workspace_bytes(n_snps),
+                                    "ldx_ld_neighbors_workspace_bytes", n_hap, path, "neighbour lists run", &window))
+        return rc;
+    return ldx::nbr_mfma(alt, fa, fr, n_snps, n_hap, positions, window, r2_bound, path != LDX_PATH_MFMA, hits, hit_cap, n_hits,
+                         row_counts, workspace, (hipStream_t)stream);
+}
+
 extern "C" int ldx_ld_neighbors_dosage_dev(const void *alt, const double *gstat, uint32_t n_snps, uint32_t n_hap,
                                            const int64_t *positions, int64_t window, float r2_bound, int path, ldx_hit *hits,
                                            uint64_t hit_cap, uint64_t *n_hits, uint32_t *row_counts, void *workspace,
@@ -3244,13 +3086,11 @@ extern "C" int ldx_ld_neighbors_dosage_dev(const void *alt, const double *gstat,
     LDX_REQUIRE(n_snps >= 1 && n_hap >= 1 && window >= 0, "bad shape");
     LDX_REQUIRE(r2_bound > 0.0f, "r2_bound must be > 0 (and not NaN)");
     LDX_REQUIRE(hit_cap < (1ull << 32), "hit_cap must be < 2^32 (the finished CSR's offsets are uint32)");
-    LDX_REQUIRE(((uintptr_t)workspace & 255u) == 0, "workspace must be 256-byte aligned");
-    LDX_REQUIRE(workspace_bytes >= ldx::nbr_mfma_workspace_bytes(n_snps), "workspace too small (see ldx_ld_neighbors_workspace_bytes)");
-    LDX_REQUIRE(path == LDX_PATH_AUTO || path == LDX_PATH_POPCOUNT || path == LDX_PATH_MFMA || path == LDX_PATH_FP4, "unknown path");
-    if (const int rc = dosage_args_ok(__func__, n_hap, path)) return rc;
-    const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles: keep pos + window exact
-    return ldx::nbr_mfma(alt, nullptr, nullptr, n_snps, n_hap, positions, window < wmax ? window : wmax, r2_bound, true, hits,
-                         hit_cap, n_hits, row_counts, workspace, (hipStream_t)stream, __func__, gstat);
+    if (const int rc = band_args_ok(__func__, workspace, workspace_bytes, ldx::nbr_mfma_workspace_bytes(n_snps),
+                                    "ldx_ld_neighbors_workspace_bytes", n_hap, path, nullptr, &window))
+        return rc;
+    return ldx::nbr_mfma(alt, nullptr, nullptr, n_snps, n_hap, positions, window, r2_bound, true, hits, hit_cap, n_hits,
+                         row_counts, workspace, (hipStream_t)stream, __func__, gstat);
 }
 
 extern "C" int ldx_ld_score_dosage_dev(const void *alt, const double *gstat, uint32_t n_snps, uint32_t n_hap,
@@ -3261,13 +3101,11 @@ extern "C" int ldx_ld_score_dosage_dev(const void *alt, const double *gstat, uin
     LDX_REQUIRE(n_annot <= 8u, "at most 8 annotation categories");
     LDX_REQUIRE(annot || n_annot == 0u, "annot is null but n_annot > 0");
     LDX_REQUIRE(n_snps >= 1 && n_hap >= 1 && window >= 0, "bad shape");
-    LDX_REQUIRE(((uintptr_t)workspace & 255u) == 0, "workspace must be 256-byte aligned");
-    LDX_REQUIRE(workspace_bytes >= ldx::score_mfma_workspace_bytes(n_snps), "workspace too small (see ldx_ld_score_workspace_bytes)");
-    LDX_REQUIRE(path == LDX_PATH_AUTO || path == LDX_PATH_POPCOUNT || path == LDX_PATH_MFMA || path == LDX_PATH_FP4, "unknown path");
-    if (const int rc = dosage_args_ok(__func__, n_hap, path)) return rc;
-    const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles: keep pos + window exact
-    return ldx::score_mfma(alt, nullptr, nullptr, nullptr, nullptr, n_snps, n_hap, positions, window < wmax ? window : wmax, annot,
-                           n_annot, true, sums, workspace, (hipStream_t)stream, false, __func__, gstat);
+    if (const int rc = band_args_ok(__func__, workspace, workspace_bytes, ldx::score_mfma_workspace_bytes(n_snps),
+                                    "ldx_ld_score_workspace_bytes", n_hap, path, nullptr, &window))
+        return rc;
+    return ldx::score_mfma(alt, nullptr, nullptr, nullptr, nullptr, n_snps, n_hap, positions, window, annot, n_annot, true, sums,
+                           workspace, (hipStream_t)stream, false, __func__, gstat);
 }
 
 extern "C" int ldx_triangle_dosage_dev(const void *alt, const double *gstat, uint32_t n_snps, uint32_t n_hap,
@@ -3288,12 +3126,6 @@ extern "C" int ldx_triangle_dosage_dev(const void *alt, const double *gstat, uin
     return rc == ldx::kNoMatrixPath ? LDX_E_UNSUPPORTED : rc;   // a bit plane of 4 GiB or more (message set): no other kernel counts dosages
 }
 
-extern "C" size_t ldx_ld_matvec_workspace_bytes(uint32_t n_snps, uint32_t n_hap)
-{
-    (void)n_hap;   // (the layout depends on the SNP count alone)
-    return ldx::prod_mfma_workspace_bytes(n_snps ? n_snps : 1u);
-}
-
 extern "C" int ldx_ld_matvec_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
                                  uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, const float *x,
                                  uint32_t n_rhs, int power, int path, int64_t *sums, void *workspace, size_t workspace_bytes,
@@ -3303,26 +3135,11 @@ extern "C" int ldx_ld_matvec_dev(const void *alt, const uint32_t *acnt, const ui
     LDX_REQUIRE(n_rhs >= 1u && n_rhs <= 8u, "n_rhs must be 1 .. 8");
     LDX_REQUIRE(power == 1 || power == 2, "power must be 1 or 2");
     LDX_REQUIRE(n_snps >= 1 && n_hap >= 1 && window >= 0, "bad shape");
-    LDX_REQUIRE(((uintptr_t)workspace & 255u) == 0, "workspace must be 256-byte aligned");
-    LDX_REQUIRE(workspace_bytes >= ldx::prod_mfma_workspace_bytes(n_snps), "workspace too small (see ldx_ld_matvec_workspace_bytes)");
-    LDX_REQUIRE(path == LDX_PATH_AUTO || path == LDX_PATH_POPCOUNT || path == LDX_PATH_MFMA || path == LDX_PATH_FP4, "unknown path");
-    if (n_hap > LDX_MAX_HAPS) {
-        ldx::set_error("ldx_ld_matvec_dev: n_hap %u > LDX_MAX_HAPS %u", n_hap, LDX_MAX_HAPS);
-        return LDX_E_UNSUPPORTED;
-    }
-    if (path == LDX_PATH_POPCOUNT) {
-        ldx::set_error("ldx_ld_matvec_dev: the products run on the matrix-pipe band (LDX_PATH_FP4 / LDX_PATH_MFMA), not on the popcount kernels");
-        return LDX_E_UNSUPPORTED;
-    }
-    const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles: keep pos + window exact
-    return ldx::prod_mfma(alt, acnt, rcnt, fa, fr, n_snps, n_hap, positions, window < wmax ? window : wmax, x, n_rhs, power == 2,
-                          path != LDX_PATH_MFMA, sums, workspace, (hipStream_t)stream);
-}
-
-extern "C" size_t ldx_ld_decay_workspace_bytes(uint32_t n_snps, uint32_t n_hap)
-{
-    (void)n_hap;   // (the layout depends on the SNP count alone)
-    return ldx::decay_mfma_workspace_bytes(n_snps ? n_snps : 1u);
+    if (const int rc = band_args_ok(__func__, workspace, workspace_bytes, ldx::prod_mfma_workspace_bytes(n_snps),
+                                    "ldx_ld_matvec_workspace_bytes", n_hap, path, "the products run", &window))
+        return rc;
+    return ldx::prod_mfma(alt, acnt, rcnt, fa, fr, n_snps, n_hap, positions, window, x, n_rhs, power == 2, path != LDX_PATH_MFMA,
+                          sums, workspace, (hipStream_t)stream);
 }
 
 extern "C" int ldx_ld_decay_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
@@ -3333,30 +3150,16 @@ extern "C" int ldx_ld_decay_dev(const void *alt, const uint32_t *acnt, const uin
     LDX_REQUIRE(alt && acnt && rcnt && fa && fr && positions && sums && counts && workspace, "null pointer");
     LDX_REQUIRE(n_snps >= 1 && n_hap >= 1 && window >= 0, "bad shape");
     LDX_REQUIRE(bin_width >= 1, "bin_width must be >= 1");
-    const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles: keep pos + window exact
-    const int64_t w = window < wmax ? window : wmax;
+    const int64_t wmax = (int64_t)1 << 52;   // the window's clamp (band_args_ok), needed here for the bin count
+    if (window > wmax) window = wmax;
     LDX_REQUIRE(n_bins <= LDX_DECAY_MAX_BINS, "more than LDX_DECAY_MAX_BINS bins");
-    LDX_REQUIRE((int64_t)n_bins == w / bin_width + 1, "n_bins must be min(window, 2^52) / bin_width + 1");
-    LDX_REQUIRE(((uintptr_t)workspace & 255u) == 0, "workspace must be 256-byte aligned");
-    LDX_REQUIRE(workspace_bytes >= ldx::decay_mfma_workspace_bytes(n_snps), "workspace too small (see ldx_ld_decay_workspace_bytes)");
-    LDX_REQUIRE(path == LDX_PATH_AUTO || path == LDX_PATH_POPCOUNT || path == LDX_PATH_MFMA || path == LDX_PATH_FP4, "unknown path");
-    if (n_hap > LDX_MAX_HAPS) {
-        ldx::set_error("ldx_ld_decay_dev: n_hap %u > LDX_MAX_HAPS %u", n_hap, LDX_MAX_HAPS);
-        return LDX_E_UNSUPPORTED;
-    }
-    if (path == LDX_PATH_POPCOUNT) {
-        ldx::set_error("ldx_ld_decay_dev: LD decay runs on the matrix-pipe band (LDX_PATH_FP4 / LDX_PATH_MFMA), not on the popcount kernels");
-        return LDX_E_UNSUPPORTED;
-    }
+    LDX_REQUIRE((int64_t)n_bins == window / bin_width + 1, "n_bins must be min(window, 2^52) / bin_width + 1");
+    if (const int rc = band_args_ok(__func__, workspace, workspace_bytes, ldx::decay_mfma_workspace_bytes(n_snps),
+                                    "ldx_ld_decay_workspace_bytes", n_hap, path, "LD decay runs", &window))
+        return rc;
     // a width above the window puts every pair into bin 0, so any such width acts as 2^52 + 1 (exact in a double)
-    return ldx::decay_mfma(alt, acnt, rcnt, fa, fr, n_snps, n_hap, positions, w, bin_width <= wmax ? bin_width : wmax + 1, keep,
-                           path != LDX_PATH_MFMA, sums, counts, n_bins, workspace, (hipStream_t)stream);
-}
-
-extern "C" size_t ldx_ld_fgt_workspace_bytes(uint32_t n_snps, uint32_t n_hap)
-{
-    (void)n_hap;   // (the layout depends on the SNP count alone)
-    return ldx::fgt_mfma_workspace_bytes(n_snps ? n_snps : 1u);
+    return ldx::decay_mfma(alt, acnt, rcnt, fa, fr, n_snps, n_hap, positions, window, bin_width <= wmax ? bin_width : wmax + 1,
+                           keep, path != LDX_PATH_MFMA, sums, counts, n_bins, workspace, (hipStream_t)stream);
 }
 
 extern "C" int ldx_ld_fgt_dev(const void *alt, const uint32_t *acnt, uint32_t n_snps, uint32_t n_hap, const int64_t *positions,
@@ -3366,26 +3169,11 @@ extern "C" int ldx_ld_fgt_dev(const void *alt, const uint32_t *acnt, uint32_t n_
     LDX_REQUIRE(alt && acnt && positions && left && workspace, "null pointer");
     LDX_REQUIRE(n_snps >= 1 && n_hap >= 1 && window >= 0, "bad shape");
     LDX_REQUIRE(min_count >= 1 && min_count <= n_hap, "min_count must be 1 .. n_hap");
-    LDX_REQUIRE(((uintptr_t)workspace & 255u) == 0, "workspace must be 256-byte aligned");
-    LDX_REQUIRE(workspace_bytes >= ldx::fgt_mfma_workspace_bytes(n_snps), "workspace too small (see ldx_ld_fgt_workspace_bytes)");
-    LDX_REQUIRE(path == LDX_PATH_AUTO || path == LDX_PATH_POPCOUNT || path == LDX_PATH_MFMA || path == LDX_PATH_FP4, "unknown path");
-    if (n_hap > LDX_MAX_HAPS) {
-        ldx::set_error("ldx_ld_fgt_dev: n_hap %u > LDX_MAX_HAPS %u", n_hap, LDX_MAX_HAPS);
-        return LDX_E_UNSUPPORTED;
-    }
-    if (path == LDX_PATH_POPCOUNT) {
-        ldx::set_error("ldx_ld_fgt_dev: the four-gamete test runs on the matrix-pipe band (LDX_PATH_FP4 / LDX_PATH_MFMA), not on the popcount kernels");
-        return LDX_E_UNSUPPORTED;
-    }
-    const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles: keep pos + window exact
-    return ldx::fgt_mfma(alt, acnt, n_snps, n_hap, positions, window < wmax ? window : wmax, min_count, keep,
-                         path != LDX_PATH_MFMA, left, workspace, (hipStream_t)stream);
-}
-
-extern "C" size_t ldx_ld_score_workspace_bytes(uint32_t n_snps, uint32_t n_hap)
-{
-    (void)n_hap;   // (the layout depends on the SNP count alone)
-    return ldx::score_mfma_workspace_bytes(n_snps ? n_snps : 1u);
+    if (const int rc = band_args_ok(__func__, workspace, workspace_bytes, ldx::fgt_mfma_workspace_bytes(n_snps),
+                                    "ldx_ld_fgt_workspace_bytes", n_hap, path, "the four-gamete test runs", &window))
+        return rc;
+    return ldx::fgt_mfma(alt, acnt, n_snps, n_hap, positions, window, min_count, keep, path != LDX_PATH_MFMA, left, workspace,
+                         (hipStream_t)stream);
 }
 
 extern "C" int ldx_ld_score_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
@@ -3397,26 +3185,11 @@ extern "C" int ldx_ld_score_dev(const void *alt, const uint32_t *acnt, const uin
     LDX_REQUIRE(n_annot <= 8u, "at most 8 annotation categories");
     LDX_REQUIRE(annot || n_annot == 0u, "annot is null but n_annot > 0");
     LDX_REQUIRE(n_snps >= 1 && n_hap >= 1 && window >= 0, "bad shape");
-    LDX_REQUIRE(((uintptr_t)workspace & 255u) == 0, "workspace must be 256-byte aligned");
-    LDX_REQUIRE(workspace_bytes >= ldx::score_mfma_workspace_bytes(n_snps), "workspace too small (see ldx_ld_score_workspace_bytes)");
-    LDX_REQUIRE(path == LDX_PATH_AUTO || path == LDX_PATH_POPCOUNT || path == LDX_PATH_MFMA || path == LDX_PATH_FP4, "unknown path");
-    if (n_hap > LDX_MAX_HAPS) {
-        ldx::set_error("ldx_ld_score_dev: n_hap %u > LDX_MAX_HAPS %u", n_hap, LDX_MAX_HAPS);
-        return LDX_E_UNSUPPORTED;
-    }
-    if (path == LDX_PATH_POPCOUNT) {
-        ldx::set_error("ldx_ld_score_dev: LD scores run on the matrix-pipe band (LDX_PATH_FP4 / LDX_PATH_MFMA), not on the popcount kernels");
-        return LDX_E_UNSUPPORTED;
-    }
-    const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles: keep pos + window exact
-    return ldx::score_mfma(alt, acnt, rcnt, fa, fr, n_snps, n_hap, positions, window < wmax ? window : wmax, annot, n_annot,
-                           path != LDX_PATH_MFMA, sums, workspace, (hipStream_t)stream);
-}
-
-extern "C" size_t ldx_ld_cross_workspace_bytes(uint32_t n_snps, uint32_t n_hap)
-{
-    (void)n_hap;   // (the layout depends on the SNP count alone)
-    return ldx::score_mfma_workspace_bytes(n_snps ? n_snps : 1u);
+    if (const int rc = band_args_ok(__func__, workspace, workspace_bytes, ldx::score_mfma_workspace_bytes(n_snps),
+                                    "ldx_ld_score_workspace_bytes", n_hap, path, "LD scores run", &window))
+        return rc;
+    return ldx::score_mfma(alt, acnt, rcnt, fa, fr, n_snps, n_hap, positions, window, annot, n_annot, path != LDX_PATH_MFMA, sums,
+                           workspace, (hipStream_t)stream);
 }
 
 extern "C" int ldx_ld_cross_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
@@ -3425,20 +3198,11 @@ extern "C" int ldx_ld_cross_dev(const void *alt, const uint32_t *acnt, const uin
 {
     LDX_REQUIRE(alt && acnt && rcnt && fa && fr && positions && sides && cross && workspace, "null pointer");
     LDX_REQUIRE(n_snps >= 1 && n_hap >= 1 && window >= 0, "bad shape");
-    LDX_REQUIRE(((uintptr_t)workspace & 255u) == 0, "workspace must be 256-byte aligned");
-    LDX_REQUIRE(workspace_bytes >= ldx::score_mfma_workspace_bytes(n_snps), "workspace too small (see ldx_ld_cross_workspace_bytes)");
-    LDX_REQUIRE(path == LDX_PATH_AUTO || path == LDX_PATH_POPCOUNT || path == LDX_PATH_MFMA || path == LDX_PATH_FP4, "unknown path");
-    if (n_hap > LDX_MAX_HAPS) {
-        ldx::set_error("ldx_ld_cross_dev: n_hap %u > LDX_MAX_HAPS %u", n_hap, LDX_MAX_HAPS);
-        return LDX_E_UNSUPPORTED;
-    }
-    if (path == LDX_PATH_POPCOUNT) {
-        ldx::set_error("ldx_ld_cross_dev: the cross-LD profile runs on the matrix-pipe band (LDX_PATH_FP4 / LDX_PATH_MFMA), not on the popcount kernels");
-        return LDX_E_UNSUPPORTED;
-    }
-    const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles: keep pos + window exact
-    const int rc = ldx::score_mfma(alt, acnt, rcnt, fa, fr, n_snps, n_hap, positions, window < wmax ? window : wmax, nullptr, 0u,
-                                   path != LDX_PATH_MFMA, sides, workspace, (hipStream_t)stream, true, "ldx_ld_cross_dev");
+    if (const int rc = band_args_ok(__func__, workspace, workspace_bytes, ldx::score_mfma_workspace_bytes(n_snps),
+                                    "ldx_ld_cross_workspace_bytes", n_hap, path, "the cross-LD profile runs", &window))
+        return rc;
+    const int rc = ldx::score_mfma(alt, acnt, rcnt, fa, fr, n_snps, n_hap, positions, window, nullptr, 0u, path != LDX_PATH_MFMA,
+                                   sides, workspace, (hipStream_t)stream, true, __func__);
     if (rc != LDX_OK) return rc;
     return ldx_ld_cross_scan_dev(sides, n_snps, cross, stream);   // the prefix sum of the one-sided scores (ldx_area.hip)
 }

@@ -51,6 +51,22 @@ def get_area_path() -> str:
     return next(k for k, v in PATHS.items() if v == code)
 
 
+def _band_path(path: Optional[str]) -> int:
+    """The band operators' path code: the FP4 band unless another is named."""
+    return PATHS["fp4" if path is None else path]
+
+
+def _band_workspace(size_fn, panel: PackedPanel, workspace: Optional[torch.Tensor]) -> torch.Tensor:
+    """A band operator's workspace: the caller's, checked against ``size_fn`` (its ldx_ld_*_workspace_bytes), or a new one
+    (the call's first kernels set what they read: no initialisation)."""
+    need = size_fn(panel.n_snps, panel.n_hap)
+    if workspace is None:
+        return torch.empty(need, dtype=torch.uint8, device=panel.device)
+    if workspace.numel() * workspace.element_size() < need:
+        raise _lib.LdxError(f"workspace too small: {need} bytes needed")
+    return workspace
+
+
 # --------------------------------------------------------------------------- triangle
 @dataclass
 class TriangleResult:
@@ -774,12 +790,8 @@ def ld_score(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, win
     pos, pos_h, window = _region_band(panel, positions, window_bp, window_snps, regions, check_positions, "ld_score")
     bits, k = (None, 0) if annot is None else pack_annot(annot, n)
     annot_d = torch.as_tensor(bits).to(panel.device) if k else None
-    pcode = PATHS["fp4"] if path is None else PATHS[path]
-    need = lib.ldx_ld_score_workspace_bytes(n, panel.n_hap)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=panel.device)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise _lib.LdxError(f"workspace too small: {need} bytes needed")
+    pcode = _band_path(path)
+    workspace = _band_workspace(lib.ldx_ld_score_workspace_bytes, panel, workspace)
     sums = torch.empty((n, 1 + k), dtype=torch.uint64, device=panel.device)
     if dosage:
         check(lib.ldx_ld_score_dosage_dev(panel.alt.data_ptr(), panel.dosage_stats()[1].data_ptr(), n, panel.n_hap,
@@ -927,12 +939,8 @@ def ld_decay(panel: PackedPanel, positions=None, window_bp: int = 250_000, windo
         if k.shape != (n,) or (k.dtype != bool and not np.isin(k, (0, 1)).all()):
             raise _lib.LdxError(f"keep must be a boolean array of shape [{n}]")
         keep_d = torch.as_tensor(np.ascontiguousarray(k.astype(np.uint8))).to(panel.device)
-    pcode = PATHS["fp4"] if path is None else PATHS[path]
-    need = lib.ldx_ld_decay_workspace_bytes(n, panel.n_hap)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=panel.device)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise _lib.LdxError(f"workspace too small: {need} bytes needed")
+    pcode = _band_path(path)
+    workspace = _band_workspace(lib.ldx_ld_decay_workspace_bytes, panel, workspace)
     sums = torch.empty(n_bins, dtype=torch.uint64, device=panel.device)
     counts = torch.empty(n_bins, dtype=torch.uint64, device=panel.device)
     _decay_launch(panel, pos, window, width, keep_d, pcode, sums, counts, workspace)
@@ -1088,12 +1096,8 @@ def ld_blocks(panel: PackedPanel, positions=None, window_bp: int = 500_000, wind
         common = np.minimum(a, panel.n_hap - a) >= float(maf_min) * panel.n_hap
         kept = common if kept is None else kept & common
     keep_d = None if kept is None else torch.as_tensor(np.ascontiguousarray(kept.astype(np.uint8))).to(panel.device)
-    pcode = PATHS["fp4"] if path is None else PATHS[path]
-    need = lib.ldx_ld_fgt_workspace_bytes(n, panel.n_hap)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=panel.device)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise _lib.LdxError(f"workspace too small: {need} bytes needed")
+    pcode = _band_path(path)
+    workspace = _band_workspace(lib.ldx_ld_fgt_workspace_bytes, panel, workspace)
     left = torch.empty(n, dtype=torch.int32, device=panel.device)
     block_of = torch.empty(n, dtype=torch.int32, device=panel.device)
     n_out = torch.empty(2, dtype=torch.int32, device=panel.device)
@@ -1329,12 +1333,8 @@ def ld_cross(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, win
     require_gpu()
     n = panel.n_snps
     pos, pos_h, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_cross")
-    pcode = PATHS["fp4"] if path is None else PATHS[path]
-    need = lib.ldx_ld_cross_workspace_bytes(n, panel.n_hap)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=panel.device)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise _lib.LdxError(f"workspace too small: {need} bytes needed")
+    pcode = _band_path(path)
+    workspace = _band_workspace(lib.ldx_ld_cross_workspace_bytes, panel, workspace)
     sides = torch.empty((n, 2), dtype=torch.uint64, device=panel.device)
     cross = torch.empty(n + 1, dtype=torch.uint64, device=panel.device)
     _cross_launch(panel, pos, window, pcode, sides, cross, workspace)
@@ -1545,11 +1545,7 @@ class LDProduct:
 def _matvec_launch(panel: PackedPanel, pos: torch.Tensor, window: int, x32: torch.Tensor, power: int, pcode: int,
                    workspace: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
     n, k = x32.shape
-    need = lib.ldx_ld_matvec_workspace_bytes(n, panel.n_hap)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=panel.device)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise _lib.LdxError(f"workspace too small: {need} bytes needed")
+    workspace = _band_workspace(lib.ldx_ld_matvec_workspace_bytes, panel, workspace)
     sums = torch.empty((n, k), dtype=torch.int64, device=panel.device)
     check(lib.ldx_ld_matvec_dev(panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), panel.fa.data_ptr(),
                                 panel.fr.data_ptr(), n, panel.n_hap, pos.data_ptr(), window, x32.data_ptr(), k, power, pcode,
@@ -1827,13 +1823,9 @@ def ld_neighbors(panel: PackedPanel, positions=None, window_bp: int = 250_000, w
     n = panel.n_snps
     bound = r2_bound(r2, strict)
     pos, _, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_neighbors")
-    pcode = PATHS["fp4"] if path is None else PATHS[path]
+    pcode = _band_path(path)
     dev = panel.device
-    need = lib.ldx_ld_neighbors_workspace_bytes(n, panel.n_hap)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise _lib.LdxError(f"workspace too small: {need} bytes needed")
+    workspace = _band_workspace(lib.ldx_ld_neighbors_workspace_bytes, panel, workspace)
     fin_bytes = lib.ldx_area_finish_workspace_bytes(n)
     fin = torch.empty(fin_bytes, dtype=torch.uint8, device=dev)
     counts = lib.ldx_area_finish_counts(fin.data_ptr())   # the band counts per row as it stores: no counting pass

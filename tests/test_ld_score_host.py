@@ -29,6 +29,24 @@ def test_workspace_bytes_is_pure_arithmetic():
     assert lib.ldx_ld_score_workspace_bytes(0, 1) == lib.ldx_ld_score_workspace_bytes(1, 1)
 
 
+def test_band_workspace_sizes_are_pinned():
+    """The byte counts of the band workspaces, recorded from the library before the layout moved into one carve function
+    (64 haplotypes; 524 160 SNPs is the last panel with a ticket order, T = 4095, 524 161 the first without)."""
+    from ld_tools_amd import _lib
+    lib = _lib.lib
+    ns = (0, 1, 128, 129, 1000, 100_000, 524_160, 524_161, 600_000)
+    band = (2816, 2816, 2816, 2816, 3584, 727_808, 17_368_320, 591_616, 677_120)
+    sizes = {"score": band, "cross": band, "decay": band, "fgt": band, "neighbors": band,
+             "matvec": band[:7] + (17_368_832, 17_454_336)}      # no order: the order's largest size instead
+    for name, want in sizes.items():
+        fn = getattr(lib, f"ldx_ld_{name}_workspace_bytes")
+        assert tuple(fn(n, 64) for n in ns) == want, name
+    assert tuple(lib.ldx_area_workspace_bytes(n, 64, 1) for n in ns) == (
+        8960, 9216, 9216, 9216, 9216, 727_552, 17_368_064, 591_360, 676_864)
+    assert tuple(lib.ldx_area_workspace_bytes(n, 64, n) for n in ns) == (
+        8960, 9216, 9216, 17_920, 70_144, 6_816_256, 35_692_032, 35_700_992, 40_860_928)
+
+
 def test_score_terms_at_the_edges():
     from ld_tools_amd.ops import score_terms
     f = np.float32
