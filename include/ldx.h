@@ -629,6 +629,56 @@ int ldx_ld_neighbors_dosage_dev(const void *alt, const double *gstat, uint32_t n
                                 int64_t window, float r2_bound, int path, ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits,
                                 uint32_t *row_counts, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- stored bands: signed r of every in-window pair, kept --------------------------------------------------------------
+ * The band operators above reduce the in-window r cells and drop them; these entries KEEP them, 4 bytes per unordered pair,
+ * with no threshold and no sort -- the windowed LD matrix of a whole chromosome -- and consume what was kept.
+ *
+ * Layout.  For non-decreasing positions and window >= 0 (values above 2^52 act as 2^52):
+ *     lo[i]      = min{ j <= i : pos_i - pos_j <= window }              uint32 [n_snps]
+ *     offsets[0] = 0,  offsets[i + 1] = offsets[i] + (i - lo[i])        uint64 [n_snps + 1]
+ *     cell (i, j), lo[i] <= j < i, lives at values[offsets[i] + (j - lo[i])]
+ * Lower band only: every unordered in-window pair once, no diagonal; offsets[n_snps] is the number of cells.
+ * ldx_ld_band_layout_dev writes every word of lo and offsets (one workgroup, any n_snps, no workspace).
+ *
+ * ldx_ld_band_dev: for every pair i > j with pos_i - pos_j <= window, values[offsets[i] + j - lo[i]] = the signed r cell of
+ * ldx_triangle_ex_dev(LDX_OUT_R32), bit for bit (-0.0f for a degenerate pair); ldx_ld_band_dosage_dev: the cell of
+ * ldx_triangle_dosage_dev.  Both paths (LDX_PATH_FP4 = LDX_PATH_AUTO, LDX_PATH_MFMA) store identical bytes.  The call writes
+ * every one of the offsets[n_snps] cells -- no memset, a relaunch into a used buffer gives the same bytes -- and nothing
+ * else: the kernel stores only where lo[i] <= j < i and the index is < n_cells (passed by value), so a lo / offsets pair
+ * that is not the layout of `positions` / `window` gives wrong or missing cells, never a write outside values[0, n_cells).
+ * workspace: ldx_ld_band_workspace_bytes() bytes (the LD-score band's layout), 256-byte aligned, no initialisation needed:
+ * one per launch that may be in flight.  LDX_PATH_POPCOUNT, n_hap > LDX_MAX_HAPS and a bit plane of 4 GiB or more =
+ * LDX_E_UNSUPPORTED; the dosage form follows the dosage entries' rules (even n_hap, FP4 only).
+ *
+ * ldx_band_score_dev: cross-panel LD scores of two bands that share ONE layout (same positions, same window; the panels may
+ * differ in their haplotypes, and either band may be a dosage band).  With T(a, b) = (int64) rint(2^32 (a *f32 b)) -- one
+ * IEEE float32 multiply, exact scaling, round-half-even -- every stored cell adds T(c1_ij, c2_ij) to sums[i] and to sums[j],
+ * and SNP i's own term is T(diag1[i], diag2[i]) (both diagonals NULL: no own term).  sums is int64 [n_snps], written by the
+ * call (no memset); the additions are 64-bit integer ones, so the result does not depend on their order.  values2 ==
+ * values1 is allowed: with diag = the r32 diagonal of ldx_triangle_r_block_dev the sums then equal ldx_ld_score_dev's
+ * sums[i][0], bit for bit.
+ *
+ * ldx_band_matvec_dev: ldx_ld_matvec_dev from a stored band -- the same term (fp64 product of the cell, or of its float32
+ * square for power 2, and the float32 weight, clamped to +-2^22, rint(2^40 .)), cell (i, j) feeding row i with x[j] and row j
+ * with x[i], SNP i's own term from diag[i] (NULL: none); 1 <= n_rhs <= 8, x and sums [n_snps][n_rhs].  With the band of
+ * ldx_ld_band_dev and the r32 diagonal the sums equal ldx_ld_matvec_dev's on the same window, bit for bit.
+ *
+ * A band pointer may be NULL when its layout holds no cell.  All calls only enqueue work on `stream` and keep no state. */
+int ldx_ld_band_layout_dev(const int64_t *positions, uint32_t n_snps, int64_t window, uint32_t *lo, uint64_t *offsets,
+                           void *stream);
+size_t ldx_ld_band_workspace_bytes(uint32_t n_snps, uint32_t n_hap);
+int ldx_ld_band_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
+                    uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, int path, const uint32_t *lo,
+                    const uint64_t *offsets, float *values, uint64_t n_cells, void *workspace, size_t workspace_bytes,
+                    void *stream);
+int ldx_ld_band_dosage_dev(const void *alt, const double *gstat, uint32_t n_snps, uint32_t n_hap, const int64_t *positions,
+                           int64_t window, int path, const uint32_t *lo, const uint64_t *offsets, float *values,
+                           uint64_t n_cells, void *workspace, size_t workspace_bytes, void *stream);
+int ldx_band_score_dev(const float *values1, const float *values2, const float *diag1, const float *diag2, const uint32_t *lo,
+                       const uint64_t *offsets, uint32_t n_snps, int64_t *sums, void *stream);
+int ldx_band_matvec_dev(const float *values, const float *diag, const uint32_t *lo, const uint64_t *offsets, uint32_t n_snps,
+                        const float *x, uint32_t n_rhs, int power, int64_t *sums, void *stream);
+
 /* ---- synthetic panels: deterministic, identical on host and device ------ */
 /* codes int8 [n_snps][ld_codes] receive global SNPs [snp_offset, snp_offset + n_snps) (a rank's
  * shard).  thresholds: per-SNP ALT probability * 2^64 (computed on the host, see

@@ -158,6 +158,12 @@ SIGNATURES = {
     "ldx_ld_score_dosage_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _i64, _vp, _u32, _int, _vp, _vp, _sz, _vp]),
     "ldx_ld_neighbors_dosage_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _i64, C.c_float, _int, _vp, _u64, _vp, _vp, _vp, _sz,
                                            _vp]),
+    "ldx_ld_band_layout_dev": (_int, [_vp, _u32, _i64, _vp, _vp, _vp]),
+    "ldx_ld_band_workspace_bytes": (_sz, [_u32, _u32]),
+    "ldx_ld_band_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _i64, _int, _vp, _vp, _vp, _u64, _vp, _sz, _vp]),
+    "ldx_ld_band_dosage_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _i64, _int, _vp, _vp, _vp, _u64, _vp, _sz, _vp]),
+    "ldx_band_score_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "ldx_band_matvec_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _vp, _u32, _int, _vp, _vp]),
     "ldx_ld_select_workspace_bytes": (_sz, [_u32]),
     "ldx_ld_select_dev": (_int, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ldx_set_area_path": (_int, [_int]),

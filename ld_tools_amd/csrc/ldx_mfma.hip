@@ -382,8 +382,11 @@ __device__ __forceinline__ uint64_t dpp_half_sum(uint64_t x)
 // kCross (with kScoreW = 1): the one-sided LD-score band (ldx_ld_cross_dev) -- score_epilogue unchanged up to its two flushes,
 // which keep the halves apart: the row path's totals (pair (i, j), i > j, seen from i: its LEFT partners) go to sides[i][0],
 // the column path's (seen from j: its RIGHT partners) to sides[j][1].  No register beside kScoreW = 1's.
+// kStore (with kArea): the band store (ldx_ld_band_dev) -- the band's passes and K loop with store_epilogue, which writes
+// every in-window r cell to its word of the caller's lower-band layout (lo / offsets) instead of reducing it.
 template <bool kRaw, bool kN11, bool kArea = false, bool kFp4 = false, typename Cell = ldx_ld32, int kScoreW = 0,
-          bool kNbr = false, int kProdW = 0, bool kDecay = false, bool kFgt = false, bool kCross = false, bool kDosage = false>
+          bool kNbr = false, int kProdW = 0, bool kDecay = false, bool kFgt = false, bool kCross = false, bool kDosage = false,
+          bool kStore = false>
 __global__ void __launch_bounds__(kMfmaThreads, kArea ? 2 : kWgPerCu)
 triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ fa, const double *__restrict__ fr,
                      const double *__restrict__ q, uint32_t n_snps, uint32_t n_slabs, uint32_t nchunks, double n,
@@ -467,8 +470,9 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
     static_assert(!kProd || (kArea && !kScore && !kNbr), "the matrix-vector epilogue runs on the band");
     static_assert(!kDecay || (kArea && !kScore && !kNbr && !kProd), "the decay epilogue runs on the band");
     static_assert(!kFgt || (kArea && !kScore && !kNbr && !kProd && !kDecay), "the four-gamete epilogue runs on the band");
-    static_assert(!kDosage || (kFp4 && !kCross && ((kR32 && !kArea) || (kScore && !kProd) || kNbr)),
-                  "dosage r: the FP4 r32 triangle, the LD-score band and the neighbour band");
+    static_assert(!kStore || (kArea && !kScore && !kNbr && !kProd && !kDecay && !kFgt), "the band store's epilogue runs on the band");
+    static_assert(!kDosage || (kFp4 && !kCross && ((kR32 && !kArea) || (kScore && !kProd) || kNbr || kStore)),
+                  "dosage r: the FP4 r32 triangle, the LD-score band, the neighbour band and the band store");
     // the per-SNP {a, rs} of the r32 epilogues: r32_snp of the frequencies, or row x of the dosage table
     auto snp_ars = [&](uint32_t x) {
         if constexpr (kDosage) {
@@ -478,7 +482,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             return r32_snp(fa[x], fr[x], n);
         }
     };
-    constexpr bool kBandF32 = kFp4 && kArea && !kScore && !kNbr && !kProd && !kDecay && !kFgt;   // the band screens its steps in float32 first (area_epilogue)
+    constexpr bool kBandF32 = kFp4 && kArea && !kScore && !kNbr && !kProd && !kDecay && !kFgt && !kStore;   // the band screens its steps in float32 first (area_epilogue)
     float *ctab32 = reinterpret_cast<float *>(tickets + 8);                 // [128][4]: F32Col
     float *rtab32 = ctab32 + kSlab * 4u + wave * (kRows64 * 4u);            // [64][4]: F32Row, private to the wave
     uint32_t *qid = reinterpret_cast<uint32_t *>(ctab32 + kSlab * 4u + kMfmaWaves * kRows64 * 4u) + wave * kQueueCap;   // [kQueueCap]
@@ -495,6 +499,10 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
     // counts (64-bit: no launch can wrap them).  Nothing else of this instantiation touches the region, so it lives from
     // the zeroing below to the flush behind the ticket loop.
     uint64_t *const decay_sum = reinterpret_cast<uint64_t *>(ctab32);
+    // band store: each wave's row table takes their place -- offsets[i] ([64] uint64) and lo[i] ([64] uint32) of its 64 rows,
+    // 12 bytes per row, written per pass beside rstat and read by the same wave only
+    uint64_t *const store_off = reinterpret_cast<uint64_t *>(ctab32) + wave * (kRows64 * 3u / 2u);
+    uint32_t *const store_lo = reinterpret_cast<uint32_t *>(store_off + kRows64);
     uint64_t *const decay_cnt = decay_sum + (kDecay ? (uint32_t)aa.measure : 0u);   // aa.measure: n_bins
     const F32Const fc32 = aa.f32;   // computed on the host (f32_const): kernel arguments live in scalar registers
     // The band (ld_area) hands its passes out PER XCD: the pass list -- j-tile-major, i.e. sorted by position -- is cut into
@@ -763,6 +771,17 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 d2s *dst = reinterpret_cast<d2s *>(rstat + lane * kStat);
                 dst[0] = d2s{i < n_snps ? (double)aa.counts[i] : 0.0, 0.0};
                 dst[1] = i < n_snps ? d2s{(double)aa.pos[i], (double)aa.is_query[i]} : d2s{0.0, 0.0};
+            } else if constexpr (kStore) {   // band store: {a, 1 / sqrt(a r)} (r32_snp) and the rows' places in the layout
+                if (new_tile && tid < kSlab) {
+                    const R32Snp c = snp_ars(t * kSlab + tid);
+                    *reinterpret_cast<d2s *>(cstat + tid * kStat) = d2s{c.a, c.rs};
+                }
+                const uint32_t i = row0 + lane;
+                const R32Snp r = snp_ars(i);
+                *reinterpret_cast<d2s *>(rstat + lane * kStat) = d2s{r.a, r.rs};
+                // aa.counts: lo, aa.is_query: offsets.  A row beyond the panel gets lo = 2^32 - 1: no column reaches it
+                store_lo[lane] = i < n_snps ? aa.counts[i] : 0xFFFFFFFFu;
+                store_off[lane] = i < n_snps ? reinterpret_cast<const uint64_t *>(aa.is_query)[i] : 0u;
             } else if constexpr (kScore || kNbr || kProd || kDecay) {   // LD scores / neighbours / products / decay: {a, 1 / sqrt(a r)} (r32_snp) and {position, annotation mask}
                 if (new_tile && tid < kSlab) {
                     const uint32_t j = t * kSlab + tid;
@@ -1733,7 +1752,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
               }
             };
             auto area_epilogue = [&]() {
-              if constexpr (kArea && MM == 2 && !kScore && !kNbr && !kProd && !kDecay && !kFgt) {
+              if constexpr (kArea && MM == 2 && !kScore && !kNbr && !kProd && !kDecay && !kFgt && !kStore) {
                 uint64_t slot = hit_slot, slot_end = hit_slot_end;
                 const double kthr = aa.k_thres;
                 const bool prefilter = aa.k_thres > 2.0;
@@ -2184,6 +2203,57 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 if (best != 0u && i < n_snps) atomicMax(reinterpret_cast<uint32_t *>(aa.hits) + i, t * kSlab + best);
               }
             };
+            // ---- band store (ldx_ld_band_dev): every in-window cell to its word of the lower-band layout ----
+            // nbr_epilogue's sweep -- one pinned read per accumulator, rstat / cstat for {a, rs} -- with the layout in place of
+            // the positions: cell (i, j) belongs to the band iff lo[i] <= j < i (lo is what the window means: ldx_ld_band_layout_dev)
+            // and lives at values[offsets[i] + j - lo[i]].  c = the r32 cell of the triangle (r32_cell, bit for bit; -0.0f for a
+            // degenerate pair).  The lanes of a half hold the columns 32 tt + l32 of ONE row, i.e. 32 consecutive words of a band
+            // row per store instruction and half.  Every store is guarded by the layout test AND by index < n_cells
+            // (aa.hit_cap, by value): a lo / offsets pair that is not the layout of this call's positions and window gives wrong
+            // cells, never a write outside `values`.  Each (i, j) is visited by exactly one lane of one pass: no cell is
+            // written twice, none is left out, whatever the buffer held.
+            auto store_epilogue = [&]() {
+              if constexpr (kStore && MM == 2) {
+                float *const values = reinterpret_cast<float *>(aa.hits);
+                const uint64_t n_cells = aa.hit_cap;
+                uint32_t ln = lane;   // (lane-derived values recomputed from an opaque copy of the lane id: see epilogue_f32)
+                asm volatile("" : "+v"(ln));
+                const uint32_t l32e = ln & 31u, halfe = ln >> 5;
+                double ca[4], cs[4];   // this lane's four columns
+#pragma unroll
+                for (int tt = 0; tt < 4; ++tt) {
+                    const d2s c0 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32e) * kStat);
+                    ca[tt] = c0.x;
+                    cs[tt] = c0.y;
+                }
+                const uint32_t j0 = t * kSlab + l32e;   // column of tile tt: j0 + 32 tt
+#pragma unroll 1
+                for (int e = 0; e < 16; ++e) {
+#pragma unroll
+                    for (int m = 0; m < 2; ++m) {
+                        accel_t c4[4];   // ONE register-indexed read per accumulator, pinned (see area_epilogue)
+#pragma unroll
+                        for (int tt = 0; tt < 4; ++tt) {
+                            c4[tt] = acc[m][tt][e];
+                            asm volatile("" : "+v"(c4[tt]));
+                        }
+                        const uint32_t ri = 32u * m + (uint32_t)(e & 3) + 8u * (uint32_t)(e >> 2) + 4u * halfe;
+                        const d2s r0 = *reinterpret_cast<const d2s *>(rstat + ri * kStat);   // two addresses per wave: broadcast
+                        const uint32_t i = row0 + ri;
+                        const uint32_t lo_i = store_lo[ri];
+                        const uint64_t off_i = store_off[ri];
+#pragma unroll
+                        for (int tt = 0; tt < 4; ++tt) {
+                            const double cnt = kFp4 ? (double)c4[tt] : (double)((uint32_t)c4[tt] >> 3);   // int8: 8 n11
+                            const float c = r32_cell(cnt, n, r0.x, r0.y, ca[tt], cs[tt]).r;
+                            const uint32_t j = j0 + 32u * tt;
+                            const uint64_t idx = off_i + (uint64_t)(j - lo_i);   // (wraps for j < lo_i: excluded below)
+                            if (j < i && j >= lo_i && idx < n_cells) __builtin_nontemporal_store(c, values + idx);
+                        }
+                    }
+                }
+              }
+            };
             if constexpr (kScore || kProd) {
                 // words per SNP -- score: column 0 and K categories; products: the right-hand sides (bit 4 of measure: power 2)
                 const uint32_t st = kProd ? (uint32_t)aa.measure & 15u : 1u + (uint32_t)aa.measure;
@@ -2211,6 +2281,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 if constexpr (kNbr) nbr_epilogue();
                 else if constexpr (kDecay) decay_epilogue();
                 else if constexpr (kFgt) fgt_epilogue();
+                else if constexpr (kStore) store_epilogue();
                 else area_epilogue();
                 if (tid == 0) tickets[parity] = next_ticket;
                 if (!(ablate & 16)) __builtin_amdgcn_s_setprio(0);
@@ -2286,7 +2357,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             }
         }
     }
-    if (kArea)   // the unused slots of this wave's last batch
+    if (kArea && !kStore)   // the unused slots of this wave's last batch
         for (uint64_t sl = hit_slot + lane; sl < hit_slot_end; sl += 64u)
             if (sl < aa.hit_cap) aa.hits[sl].query = 0xFFFFFFFFu;
 }
@@ -3001,6 +3072,38 @@ int nbr_mfma(const void *alt, const double *fa, const double *fr, uint32_t n_snp
                : band_launch<kNbrBand<false>>(alt, fa, fr, nullptr, n_snps, n_hap, (double)n_hap, lds, nullptr, aa, w.sched, s);
 }
 
+// ---- the band store (ldx_ld_band_dev) ----------------------------------------------------------------------------------
+// the score band's workspace (the query mask and the tail's hit counter stay unused)
+size_t store_mfma_workspace_bytes(uint32_t n_snps) { return score_mfma_workspace_bytes(n_snps); }
+
+template <bool kFp4, bool kDosage = false>
+constexpr auto kStoreBand = triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, false, 0, false, false, false, kDosage, true>;
+
+// `gstat` (ldx_ld_band_dosage_dev; FP4): the dosage table in place of fa / fr, n the individuals
+int store_mfma(const void *alt, const double *fa, const double *fr, uint32_t n_snps, uint32_t n_hap, const int64_t *positions,
+               int64_t window, bool fp4, const uint32_t *lo, const uint64_t *offsets, float *values, uint64_t n_cells,
+               void *workspace, hipStream_t s, const char *who, const double *gstat = nullptr)
+{
+    if (const int rc = band_plane_check(who, n_snps, n_hap)) return rc;
+    if (n_snps < 2 || n_cells == 0u) return LDX_OK;   // no pairs, or no room for one: nothing to store
+    BandWs w;   // (the query mask stays unused)
+    band_carve(w, workspace, n_snps);
+    nbr_init_kernel<<<1, 64, 0, s>>>(n_snps, w.qrows);
+    LDX_HIP(hipGetLastError());
+    if (const int rc = band_plan(w, n_snps, positions, window, w.n_hits, s)) return rc;   // (nothing reads the hit counter)
+    // values, lo, offsets and n_cells travel in members this epilogue does not otherwise use: AreaArgs keeps its size
+    AreaArgs aa = band_args(w, n_hap, positions, window, w.n_hits);
+    aa.hits = (ldx_hit *)values;                               // store: the float32 cells [n_cells]
+    aa.counts = const_cast<uint32_t *>(lo);                    // store: lo [n_snps] (read only)
+    aa.is_query = reinterpret_cast<const uint8_t *>(offsets);  // store: offsets [n_snps + 1] uint64 (read only)
+    aa.hit_cap = n_cells;                                      // store: no index at or beyond it is written
+    const size_t lds = mfma_lds_bytes(kRows64, false, false) + (size_t)kMfmaWaves * kRows64 * 12u;   // + the waves' row tables
+    if (gstat)
+        return band_launch<kStoreBand<true, true>>(alt, gstat, nullptr, nullptr, n_snps, n_hap, (double)(n_hap / 2u), lds, nullptr, aa, w.sched, s);
+    return fp4 ? band_launch<kStoreBand<true>>(alt, fa, fr, nullptr, n_snps, n_hap, (double)n_hap, lds, nullptr, aa, w.sched, s)
+               : band_launch<kStoreBand<false>>(alt, fa, fr, nullptr, n_snps, n_hap, (double)n_hap, lds, nullptr, aa, w.sched, s);
+}
+
 }  // namespace ldx
 
 // the band entries' workspace sizes: the layout depends on the SNP count alone
@@ -3012,6 +3115,7 @@ LDX_BAND_WORKSPACE_BYTES(ldx_ld_decay_workspace_bytes, decay_mfma_workspace_byte
 LDX_BAND_WORKSPACE_BYTES(ldx_ld_fgt_workspace_bytes, fgt_mfma_workspace_bytes)
 LDX_BAND_WORKSPACE_BYTES(ldx_ld_score_workspace_bytes, score_mfma_workspace_bytes)
 LDX_BAND_WORKSPACE_BYTES(ldx_ld_cross_workspace_bytes, score_mfma_workspace_bytes)
+LDX_BAND_WORKSPACE_BYTES(ldx_ld_band_workspace_bytes, store_mfma_workspace_bytes)
 #undef LDX_BAND_WORKSPACE_BYTES
 
 // the dosage entries' shared argument rules: an even number of haplotypes within LDX_MAX_HAPS, the FP4 kernel only
@@ -3091,6 +3195,36 @@ extern "C" int ldx_ld_neighbors_dosage_dev(const void *alt, const double *gstat,
         return rc;
     return ldx::nbr_mfma(alt, nullptr, nullptr, n_snps, n_hap, positions, window, r2_bound, true, hits, hit_cap, n_hits,
                          row_counts, workspace, (hipStream_t)stream, __func__, gstat);
+}
+
+extern "C" int ldx_ld_band_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
+                               uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, int path,
+                               const uint32_t *lo, const uint64_t *offsets, float *values, uint64_t n_cells, void *workspace,
+                               size_t workspace_bytes, void *stream)
+{
+    LDX_REQUIRE(alt && acnt && rcnt && fa && fr && positions && lo && offsets && workspace, "null pointer");
+    LDX_REQUIRE(values || n_cells == 0, "values is null but n_cells > 0");
+    LDX_REQUIRE(n_snps >= 1 && n_hap >= 1 && window >= 0, "bad shape");
+    if (const int rc = band_args_ok(__func__, workspace, workspace_bytes, ldx::store_mfma_workspace_bytes(n_snps),
+                                    "ldx_ld_band_workspace_bytes", n_hap, path, "the band store runs", &window))
+        return rc;
+    return ldx::store_mfma(alt, fa, fr, n_snps, n_hap, positions, window, path != LDX_PATH_MFMA, lo, offsets, values, n_cells,
+                           workspace, (hipStream_t)stream, __func__);
+}
+
+extern "C" int ldx_ld_band_dosage_dev(const void *alt, const double *gstat, uint32_t n_snps, uint32_t n_hap,
+                                      const int64_t *positions, int64_t window, int path, const uint32_t *lo,
+                                      const uint64_t *offsets, float *values, uint64_t n_cells, void *workspace,
+                                      size_t workspace_bytes, void *stream)
+{
+    LDX_REQUIRE(alt && gstat && positions && lo && offsets && workspace, "null pointer");
+    LDX_REQUIRE(values || n_cells == 0, "values is null but n_cells > 0");
+    LDX_REQUIRE(n_snps >= 1 && n_hap >= 1 && window >= 0, "bad shape");
+    if (const int rc = band_args_ok(__func__, workspace, workspace_bytes, ldx::store_mfma_workspace_bytes(n_snps),
+                                    "ldx_ld_band_workspace_bytes", n_hap, path, nullptr, &window))
+        return rc;
+    return ldx::store_mfma(alt, nullptr, nullptr, n_snps, n_hap, positions, window, true, lo, offsets, values, n_cells, workspace,
+                           (hipStream_t)stream, __func__, gstat);
 }
 
 extern "C" int ldx_ld_score_dosage_dev(const void *alt, const double *gstat, uint32_t n_snps, uint32_t n_hap,

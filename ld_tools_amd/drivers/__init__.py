@@ -9,6 +9,8 @@ loop order).  Any object with pysam's ``VariantFile.fetch(chrom, start, end)`` /
 as the VCF source; pysam itself is only imported by the command-line shells.
 """
 from .area import AreaQueryResult, area_scan, get_inld_vars, write_area_file  # noqa: F401
+from .band import (BandMatrix, CrossScoreTable, band_matrix, cross_scores_by_group, write_band,  # noqa: F401
+                   write_cross_score)
 from .blocks import write_blocks  # noqa: F401
 from .clump import ClumpTable, clump, write_clumped  # noqa: F401
 from .decay import write_decay  # noqa: F401

@@ -5,6 +5,8 @@
     ld_score(panel, positions, ...)         LD scores: windowed sums of r^2 per SNP (LDSC's l2), optionally per category
     ld_matvec(panel, x, positions, ...)     R x (or R^2 x) over the window for up to 8 vectors, without the matrix
     ld_ridge(panel, z, positions, ...)      (R + lam I) beta = z by conjugate gradients on ld_matvec
+    ld_band(panel, positions, ...)          the windowed LD matrix KEPT: signed r of every in-window pair, 4 bytes each
+    ld_cross_score(band_a, band_b)          cross-panel LD scores (sum of r1 r2 over the window) from two stored bands
     ld_cross / ld_regions                   the cross-LD profile of the band and the LD-independent regions cut from it
     ld_neighbors(panel, positions, ...)     per-SNP lists of the SNPs in the window with r^2 above a threshold
     ld_clump / ld_prune                     greedy clumping (PLINK --clump) and priority pruning on those lists
@@ -1650,7 +1652,7 @@ def cg_solve(product, z: torch.Tensor, lam: float, tol: float = 1e-6, max_iter: 
 
 def ld_ridge(panel: PackedPanel, z, positions=None, window_bp: int = 1_000_000, window_snps: Optional[int] = None,
              lam: float = 1.0, tol: float = 1e-6, max_iter: int = 1000, path: str = "auto",
-             check_positions: bool = True, regions=None) -> RidgeResult:
+             check_positions: bool = True, regions=None, band: Optional["LDBand"] = None) -> RidgeResult:
     """Solve (R_w + lam I) beta = z by conjugate gradients on ld_matvec -- ridge / infinitesimal polygenic scores from
     summary statistics, R_w never formed.  ``z``: [n] or [n, k], k <= 8 columns solved side by side (one ld_matvec launch per
     iteration for all of them).  Before each product the search direction is replaced by the float32 vector the kernel
@@ -1660,21 +1662,38 @@ def ld_ridge(panel: PackedPanel, z, positions=None, window_bp: int = 1_000_000, 
     ``regions`` (an LDRegions or a region_of array; default None: no change) solves with the block-diagonal R_B instead
     (ld_matvec's ``regions``).  With whole-region windows (``window_bp=None``) and no missing codes every block is the
     correlation matrix of its SNPs' ALT indicators, up to the float32 rounding of the cells -- positive semidefinite --, so
-    ``indefinite`` cannot then come from window truncation."""
+    ``indefinite`` cannot then come from window truncation.
+
+    ``band`` (an LDBand of this panel from ld_band; default None: no change): every product is read from the stored band
+    (LDBand.matvec: a sweep over the stored cells, the same int64 sums as ld_matvec on the band's window, hence the same iterates)
+    instead of re-deriving every r cell on the matrix cores; positions and window are then the band's, and ``positions``,
+    the window arguments, ``path`` and ``regions`` are not read."""
+    if band is not None:
+        if band.dosage:
+            raise _lib.LdxError("ld_ridge: band= needs a haplotype band (ld_matvec has no genotype-dosage form)")
+        if band.n_snps != panel.n_snps:
+            raise _lib.LdxError(f"ld_ridge: band= holds {band.n_snps} SNPs, the panel {panel.n_snps}")
     dev = require_gpu()
-    pos, _, window = _region_band(panel, positions, window_bp, window_snps, regions, check_positions, "ld_ridge")
+    if band is not None:
+        pos, window = None, band.window
+    else:
+        pos, _, window = _region_band(panel, positions, window_bp, window_snps, regions, check_positions, "ld_ridge")
     zt = z if isinstance(z, torch.Tensor) else torch.as_tensor(np.asarray(z))
     squeeze = zt.ndim == 1
     matvec_rhs(zt, panel.n_snps)   # shape, column count, finiteness
     zt = (zt[:, None] if squeeze else zt).to(panel.device, dtype=torch.float64)
     if not (float(lam) >= 0.0 and np.isfinite(float(lam))):
         raise _lib.LdxError(f"lam must be a finite number >= 0 (got {lam})")
-    ws = torch.empty(lib.ldx_ld_matvec_workspace_bytes(panel.n_snps, panel.n_hap), dtype=torch.uint8, device=panel.device)
+    ws = None if band is not None else \
+        torch.empty(lib.ldx_ld_matvec_workspace_bytes(panel.n_snps, panel.n_hap), dtype=torch.uint8, device=panel.device)
     pcode = PATHS[path]
 
     def product(p):
         x32, e, _ = matvec_rhs(p, panel.n_snps, 1, False)
-        sums, _ = _matvec_launch(panel, pos, window, x32, 1, pcode, ws)
+        if band is not None:
+            sums = band._matvec_launch(x32, 1)
+        else:
+            sums, _ = _matvec_launch(panel, pos, window, x32, 1, pcode, ws)
         lp = LDProduct(sums, e, x32, window, 1)
         return lp.values(), lp.x()
 
@@ -1683,6 +1702,232 @@ def ld_ridge(panel: PackedPanel, z, positions=None, window_bp: int = 1_000_000, 
         res.beta = res.beta[:, 0]
     del dev
     return res
+
+
+# --------------------------------------------------------------------------- stored bands
+CROSS_SCALE = SCORE_SCALE        # cross-score sums are integers in units of 2^-32 r1 r2 (include/ldx.h, ldx_band_score_dev)
+BAND_WINDOW_MAX = 1 << 52        # larger windows act as 2^52 (include/ldx.h, "stored bands")
+
+
+def band_layout_host(positions, window: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Host mirror of ldx_ld_band_layout_dev (include/ldx.h): ``(lo uint32 [n], offsets uint64 [n + 1])`` of the lower band of
+    ``window`` over non-decreasing positions -- lo[i] the first j <= i with pos_i - pos_j <= window, offsets the prefix sum
+    of i - lo[i]; cell (i, j), lo[i] <= j < i, is word offsets[i] + j - lo[i]."""
+    pos = np.asarray(positions, dtype=np.int64)
+    window = min(int(window), BAND_WINDOW_MAX)
+    if window < 0:
+        raise _lib.LdxError("the window must be >= 0")
+    if pos.ndim != 1 or pos.size < 1:
+        raise _lib.LdxError("positions must be a non-empty vector")
+    if pos.size > 1 and bool((pos[1:] < pos[:-1]).any()):
+        raise _lib.LdxError("positions must be non-decreasing (VCF order)")
+    lo, _ = window_bounds(pos, window)
+    offsets = np.zeros(pos.size + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum(np.arange(pos.size, dtype=np.int64) - lo).astype(np.uint64)
+    return lo.astype(np.uint32), offsets
+
+
+def cross_terms(a, b) -> np.ndarray:
+    """Host mirror of the cross-score term (include/ldx.h, ldx_band_score_dev): T(a, b) = rint(2^32 * (a *f32 b)) as int64,
+    from float32 cells.  One float32 multiply, then exact scaling and round-half-even; T(c, c) is score_terms(c)."""
+    p = np.multiply(np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32), dtype=np.float32)
+    return np.rint(np.ldexp(p.astype(np.float64), 32)).astype(np.int64)
+
+
+def _same_layout(a: "LDBand", b: "LDBand") -> bool:
+    """Two bands share a layout: same SNP count, window and positions (compared where they live)."""
+    if a.n_snps != b.n_snps or a.window != b.window or a.n_cells != b.n_cells:
+        return False
+    pa, pb = a.positions, b.positions
+    if pa is pb:
+        return True
+    if isinstance(pa, torch.Tensor) and isinstance(pb, torch.Tensor):
+        return bool(torch.equal(pa, pb.to(pa.device)))
+    ha = pa.cpu().numpy() if isinstance(pa, torch.Tensor) else np.asarray(pa)
+    hb = pb.cpu().numpy() if isinstance(pb, torch.Tensor) else np.asarray(pb)
+    return bool(np.array_equal(ha, hb))
+
+
+@dataclass
+class LDBand:
+    """The windowed LD matrix of one panel, stored (ld_band; include/ldx.h, "stored bands").  ``values``: float32 device
+    tensor [n_cells], the signed r of every pair i > j with pos_i - pos_j <= window, once each -- ld_triangle(fmt="r32")'s
+    cells bit for bit (its ``dosage=True`` cells for a dosage band); ``lo`` (int32 bit pattern of uint32 [n]) and
+    ``offsets`` (int64 bit pattern of uint64 [n + 1]): cell (i, j), lo[i] <= j < i, is ``values[offsets[i] + j - lo[i]]``;
+    ``diag``: float32 [n], r_matrix()'s diagonal (not part of ``values``).  ``positions``: what ld_band was given (numpy, or
+    the device tensor); ``window``: the window in their units."""
+
+    values: torch.Tensor
+    lo: torch.Tensor
+    offsets: torch.Tensor
+    diag: torch.Tensor
+    positions: object
+    window: int
+    dosage: bool = False
+    n_hap: int = 0
+    _host: Optional[tuple] = None
+
+    @property
+    def n_snps(self) -> int:
+        return int(self.lo.numel())
+
+    @property
+    def n_cells(self) -> int:
+        return int(self.values.numel())
+
+    def layout(self) -> Tuple[np.ndarray, np.ndarray]:
+        """``(lo, offsets)`` as int64 numpy arrays, fetched once."""
+        if self._host is None:
+            self._host = (self.lo.cpu().numpy().view(np.uint32).astype(np.int64),
+                          self.offsets.cpu().numpy().view(np.uint64).astype(np.int64))
+        return self._host
+
+    def row(self, i: int) -> Tuple[np.ndarray, np.ndarray]:
+        """``(columns, r)`` of row i's stored cells: the SNPs j < i inside the window, ascending, and their float32 r."""
+        lo, off = self.layout()
+        i = int(i)
+        if not 0 <= i < self.n_snps:
+            raise _lib.LdxError(f"row {i} outside 0..{self.n_snps - 1}")
+        return np.arange(lo[i], i, dtype=np.int64), self.values[int(off[i]): int(off[i + 1])].cpu().numpy()
+
+    def to_csr(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The symmetric windowed matrix as ``(indptr int64 [n + 1], indices int64, data float32)`` numpy arrays, rows
+        sorted by column: both orientations of every stored pair and the diagonal (scipy.sparse.csr_matrix takes the
+        triple as it is; nothing here needs scipy)."""
+        lo, off = self.layout()
+        n = self.n_snps
+        vals = self.values.cpu().numpy()
+        diag = self.diag.cpu().numpy()
+        length = np.arange(n, dtype=np.int64) - lo
+        rows_l = np.repeat(np.arange(n, dtype=np.int64), length)                 # the stored cells' (i, j)
+        cols_l = np.arange(off[n], dtype=np.int64) - np.repeat(off[:-1] - lo, length)
+        ii = np.concatenate([rows_l, np.arange(n, dtype=np.int64), cols_l])
+        jj = np.concatenate([cols_l, np.arange(n, dtype=np.int64), rows_l])
+        dd = np.concatenate([vals, diag, vals])
+        order = np.lexsort((jj, ii))
+        indptr = np.zeros(n + 1, dtype=np.int64)
+        indptr[1:] = np.cumsum(np.bincount(ii, minlength=n))
+        return indptr, jj[order], dd[order].astype(np.float32)
+
+    def to_dense(self, rows: Optional[Tuple[int, int]] = None) -> np.ndarray:
+        """float32 [r1 - r0, r1 - r0] numpy square of the rows / columns ``rows`` = (r0, r1) (default: all -- for small
+        checks): the stored cells in both orientations, the diagonal, and +0.0 outside the window."""
+        lo, off = self.layout()
+        r0, r1 = (0, self.n_snps) if rows is None else (int(rows[0]), int(rows[1]))
+        if not 0 <= r0 <= r1 <= self.n_snps:
+            raise _lib.LdxError(f"rows {rows} outside 0..{self.n_snps}")
+        out = np.zeros((r1 - r0, r1 - r0), dtype=np.float32)
+        if r1 == r0:
+            return out
+        vals = self.values[int(off[r0]): int(off[r1])].cpu().numpy()
+        diag = self.diag[r0:r1].cpu().numpy()
+        for i in range(r0, r1):
+            j0 = max(int(lo[i]), r0)
+            seg = vals[int(off[i] - off[r0]) + (j0 - int(lo[i])): int(off[i + 1] - off[r0])]
+            out[i - r0, j0 - r0: i - r0] = seg
+            out[j0 - r0: i - r0, i - r0] = seg
+            out[i - r0, i - r0] = diag[i - r0]
+        return out
+
+    def _matvec_launch(self, x32: torch.Tensor, power: int) -> torch.Tensor:
+        n, k = x32.shape
+        sums = torch.empty((n, k), dtype=torch.int64, device=self.values.device)
+        check(lib.ldx_band_matvec_dev(_ptr(self.values) if self.n_cells else None, self.diag.data_ptr(), self.lo.data_ptr(),
+                                      self.offsets.data_ptr(), n, x32.data_ptr(), k, power, sums.data_ptr(), _stream_ptr()),
+              "ldx_band_matvec_dev")
+        return sums
+
+    def matvec(self, x, power: int = 1, check_finite: bool = True) -> LDProduct:
+        """ld_matvec from the stored band (include/ldx.h, ldx_band_matvec_dev): the same right-hand-side scaling, terms and
+        int64 sums -- bit for bit ld_matvec's on the band's window for a haplotype band -- as one sweep over ``values``
+        instead of a pass over the panel on the matrix cores (about three times faster than ld_matvec with
+        one right-hand side; with eight it is currently slower, so keep ld_matvec for wide batches)."""
+        x32, e, squeeze = matvec_rhs(x, self.n_snps, power, check_finite, self.values.device)
+        require_gpu()
+        return LDProduct(self._matvec_launch(x32, power), e, x32, self.window, power, squeeze)
+
+
+def ld_band(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, window_snps: Optional[int] = None,
+            path: Optional[str] = None, workspace: Optional[torch.Tensor] = None, check_positions: bool = True,
+            dosage: bool = False) -> LDBand:
+    """The windowed (band) LD matrix, kept: the signed r of every pair i > j with pos_i - pos_j <= window, 4 bytes per
+    unordered pair, no threshold and no sort (include/ldx.h, ldx_ld_band_dev) -- ld_triangle(fmt="r32")'s cells bit for bit,
+    written by the band kernel as it computes them.  Positions and window as for ld_score.  ``path``: 'fp4' (default) or
+    'mfma' (the int8 band: identical bytes).  ``workspace``: a uint8 device tensor of ldx_ld_band_workspace_bytes() bytes to
+    reuse.  ``dosage=True``: genotype-dosage r (ld_triangle(fmt="r32", dosage=True)'s cells; the FP4 band, an even n_hap).
+
+    The layout is computed on the device; its total, offsets[n], is read back once to size ``values`` -- the call's only
+    synchronisation (besides the check of a device tensor of positions, unless ``check_positions`` is False)."""
+    if dosage:
+        _dosage_check("ld_band", panel)
+    require_gpu()
+    n = panel.n_snps
+    pos, pos_h, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_band")
+    window = min(window, BAND_WINDOW_MAX)
+    pcode = _band_path(path)
+    workspace = _band_workspace(lib.ldx_ld_band_workspace_bytes, panel, workspace)
+    dev = panel.device
+    lo = torch.empty(n, dtype=torch.int32, device=dev)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    check(lib.ldx_ld_band_layout_dev(pos.data_ptr(), n, window, lo.data_ptr(), offsets.data_ptr(), _stream_ptr()),
+          "ldx_ld_band_layout_dev")
+    n_cells = int(offsets[n].item())
+    values = torch.empty(n_cells, dtype=torch.float32, device=dev)
+    ws_bytes = workspace.numel() * workspace.element_size()
+    if dosage:
+        gstat = panel.dosage_stats()[1]
+        check(lib.ldx_ld_band_dosage_dev(panel.alt.data_ptr(), gstat.data_ptr(), n, panel.n_hap, pos.data_ptr(), window, pcode,
+                                         lo.data_ptr(), offsets.data_ptr(), _ptr(values) if n_cells else None, n_cells,
+                                         workspace.data_ptr(), ws_bytes, _stream_ptr()), "ldx_ld_band_dosage_dev")
+        live = gstat[:n, 1] > 0.0
+        diag = torch.where(live, torch.ones((), dtype=torch.float32, device=dev),
+                           torch.full((), -0.0, dtype=torch.float32, device=dev))
+    else:
+        check(lib.ldx_ld_band_dev(panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), panel.fa.data_ptr(),
+                                  panel.fr.data_ptr(), n, panel.n_hap, pos.data_ptr(), window, pcode, lo.data_ptr(),
+                                  offsets.data_ptr(), _ptr(values) if n_cells else None, n_cells, workspace.data_ptr(),
+                                  ws_bytes, _stream_ptr()), "ldx_ld_band_dev")
+        # r_matrix()'s diagonal (ldx_common.h, r32_diag): (n - a) / r in fp64, rounded to float32 once; -0.0f where a r == 0
+        a, r = panel.acnt[:n].to(torch.float64), panel.rcnt[:n].to(torch.float64)
+        live = (a * r) != 0
+        quot = ((float(panel.n_hap) - a) / torch.where(live, r, torch.ones_like(r))).to(torch.float32)
+        diag = torch.where(live, quot, torch.full((), -0.0, dtype=torch.float32, device=dev))
+    res = LDBand(values, lo, offsets, diag.contiguous(), pos if pos_h is None else pos_h, window, bool(dosage), panel.n_hap)
+    res._keep = (pos, workspace)   # alive until the launch is done
+    return res
+
+
+class CrossScores(np.ndarray):
+    """ld_cross_score's result: a float64 [n] array (sums 2^-32) that also carries ``sums``, the exact int64 sums."""
+
+    sums: np.ndarray
+
+
+def ld_cross_score(band_a: LDBand, band_b: LDBand) -> np.ndarray:
+    """Cross-panel LD scores from two stored bands that share a layout (same positions, same window; the panels may hold
+    different haplotypes -- two populations' ``PackedPanel.select`` / ``split`` panels of one union panel -- and either band
+    may be a dosage band): for every SNP i the sum of r1_ij r2_ij over the SNPs j with |pos_i - pos_j| <= window, i itself
+    included (include/ldx.h, ldx_band_score_dev).  Every term is rint(2^32 (r1 *f32 r2)), added as a 64-bit integer: the
+    result is reproducible and symmetric in its arguments.  Returns the scores as float64 [n] (sums 2^-32); the exact int64
+    sums are its ``.sums``.  ``ld_cross_score(b, b)`` is ld_score's column 0, bit for bit.  Raises LdxError when the layouts
+    differ."""
+    if not isinstance(band_a, LDBand) or not isinstance(band_b, LDBand):
+        raise _lib.LdxError("ld_cross_score takes two LDBand results of ld_band")
+    if not _same_layout(band_a, band_b):
+        raise _lib.LdxError("ld_cross_score: the bands do not share a layout (same positions and the same window needed)")
+    require_gpu()
+    n = band_a.n_snps
+    if band_a.values.device != band_b.values.device:
+        raise _lib.LdxError("ld_cross_score: the bands live on different devices")
+    sums = torch.empty(n, dtype=torch.int64, device=band_a.values.device)
+    has = band_a.n_cells > 0
+    check(lib.ldx_band_score_dev(_ptr(band_a.values) if has else None, _ptr(band_b.values) if has else None,
+                                 band_a.diag.data_ptr(), band_b.diag.data_ptr(), band_a.lo.data_ptr(),
+                                 band_a.offsets.data_ptr(), n, sums.data_ptr(), _stream_ptr()), "ldx_band_score_dev")
+    sums_h = sums.cpu().numpy()
+    out = (sums_h.astype(np.float64) / CROSS_SCALE).view(CrossScores)
+    out.sums = sums_h
+    return out
 
 
 # --------------------------------------------------------------------------- neighbour lists, clumping, pruning
