@@ -1,7 +1,7 @@
 // Stored LD bands (include/ldx.h, "Stored bands"): the lower-band layout of a window over sorted positions
 // (ldx_ld_band_layout_dev) and the two consumers of bands that ldx_ld_band_dev stored -- cross-panel scores
 // (ldx_band_score_dev) and matrix-vector products (ldx_band_matvec_dev).  The store itself is an epilogue of the band
-// kernel (ldx_mfma.hip, kStore).  Plain HIP: the consumers stream the band's 4 bytes per stored pair.
+// kernel (ldx_mfma.hip, BandOp::Store).  Plain HIP: the consumers stream the band's 4 bytes per stored pair.
 #include "ldx_common.h"
 
 namespace ldx {

@@ -231,9 +231,29 @@ __device__ unsigned long long g_dbg[8];   // tuning builds (-DLDX_TUNING): event
 static std::atomic<int> g_forced_short{-1};   // >= 0: number of halved passes per launch (ldx_debug_force_short_passes)
 
 
-// Arguments of the banded (ld_area) use of the kernel: the same passes, K loop and operand staging; the pass list is
-// cut to the units a window of +-flank can reach, and the epilogue turns every pair into up to two thresholded
-// hits, (query = row, opposing = column) and (query = column, opposing = row)  (ld_area.py:152-276).
+// What triangle_mfma_kernel does with the counts: None is the triangle, every other value a band operator (the kernel's
+// header says which epilogue each one runs).
+enum class BandOp { None, Hits, Score, Cross, Nbr, Prod, Decay, Fgt, Store };
+
+// Arguments of the banded use of the kernel: the same passes, K loop and operand staging; the pass list is cut to the
+// units a window of +-flank can reach.  Hits (ld_area, for which the struct was made) turns every pair into up to two
+// thresholded hits, (query = row, opposing = column) and (query = column, opposing = row)  (ld_area.py:152-276); the other
+// operators reuse its members -- the struct must not grow, see below -- as this table says ("-": not read; pos, pass_base,
+// g_begin, g_end, order and f32 mean the same to all; n_hits is the counter the plan kernel zeroes, read by Hits and Nbr
+// alone; flank is the window of every operator but Hits, which calls it the flank):
+//
+//   BandOp  hits                             counts                        is_query              hit_cap  k_thres          measure
+//   Hits    ldx_hit records                  hits per query row, or null   query mask; null: all capacity 1e4 x threshold  LDX_MEASURE_*
+//   Score   uint64 sums [n_snps][1 + K]      -                             annotation masks/null -        -                K
+//   Cross   uint64 sides [n_snps][2]         -                             null                  -        -                0
+//   Nbr     ldx_hit records {i, j, r, r * r} records per row, or null      null                  capacity float32 bound    -
+//                                                                                                         on r *f32 r
+//   Prod    int64 sums [n_snps][n_rhs]       float32 x [n_snps][n_rhs]     null                  -        -                n_rhs | power 2 << 4
+//   Decay   uint64 sums [n_bins]             uint64 pair counts [n_bins]   effective keep mask   -        bin width        n_bins
+//   Fgt     uint32 left [n_snps]             ALT counts [n_snps]           keep mask             -        -                min_count
+//   Store   float32 values [n_cells]         uint32 lo [n_snps]            uint64 offsets        n_cells  -                -
+//                                                                          [n_snps + 1]
+//   None    (the triangle reads f32 alone)
 struct AreaArgs {
     const int64_t *pos;            // [n_snps] ascending 1-based positions
     const uint8_t *is_query;       // [n_snps] 1 = the SNP is a query; null = every SNP is
@@ -250,8 +270,9 @@ struct AreaArgs {
     uint64_t hit_cap;              // band
     double flank, k_thres;
     int measure;
-    F32Const f32;                  // the fp32 epilogue tier's constants (triangle launches use only this member and the next)
+    F32Const f32;                  // the fp32 epilogue tier's constants (triangle launches use only this member)
 };
+static_assert(sizeof(AreaArgs) == 112, "AreaArgs must not grow: see the comment inside it");
 // an entry of the band's ticket order: kAreaDecoded | tile << 12 | pass inside the tile (both < 4096 whenever the order exists:
 // area_order_entries); plain pass indices (no order: panels beyond ~512 000 SNPs) are < 2^30
 constexpr uint32_t kAreaDecoded = 1u << 30;
@@ -360,40 +381,125 @@ __device__ __forceinline__ uint64_t dpp_half_sum(uint64_t x)
     return ((uint64_t)hi << 32) | lo;
 }
 
+// What the band epilogues of the kernel below share, as text: macros, like the K loop's LDX_CHUNK, because the shared
+// part must compile to the instructions it compiled to when every epilogue spelled it out.  (As lambdas -- a column loader
+// that returns a struct, a sweep that calls a generic body -- the same work came out in another instruction and register
+// order in every band instantiation: the first simplification passes see a lambda's captures as loads through its closure.)
+// LDX_HIT_APPENDER: the Hits and Nbr epilogues' `append(keep, qrow, orow, a, b)` -- one record {qrow, orow, a, b} per lane
+// with `keep` into the wave's current batch of 256 slots, slot .. slot_end (the epilogue hands them back to hit_slot /
+// hit_slot_end); a full batch is closed (what is left of it marked invalid) and a new one drawn from aa.n_hits; stored
+// records are counted per row into aa.counts: only stored hits, what the scatter will place.
+#define LDX_HIT_APPENDER                                                                                            \
+    uint64_t slot = hit_slot, slot_end = hit_slot_end;                                                              \
+    auto append = [&](bool keep, uint32_t qrow, uint32_t orow, float rec_a, float rec_b) {                          \
+        const unsigned long long mask = __ballot(keep);                                                             \
+        if (!mask) return; /* wave-uniform */                                                                       \
+        const uint32_t cnt = __builtin_popcountll(mask);                                                            \
+        if (slot + cnt > slot_end) {                                                                                \
+            for (uint64_t sl = slot + lane; sl < slot_end; sl += 64u)                                               \
+                if (sl < aa.hit_cap) aa.hits[sl].query = 0xFFFFFFFFu;                                               \
+            unsigned long long base = 0;                                                                            \
+            if (lane == 0) base = atomicAdd(aa.n_hits, (unsigned long long)kHitBatch);                              \
+            base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |             \
+                   __builtin_amdgcn_readfirstlane((uint32_t)base);                                                  \
+            slot = base;                                                                                            \
+            slot_end = base + kHitBatch;                                                                            \
+        }                                                                                                           \
+        if (keep) {                                                                                                 \
+            const uint64_t sl = slot + __builtin_popcountll(mask & ((1ull << lane) - 1ull));                        \
+            if (sl < aa.hit_cap) {                                                                                  \
+                aa.hits[sl] = ldx_hit{qrow, orow, rec_a, rec_b};                                                    \
+                if (aa.counts) atomicAdd(&aa.counts[qrow], 1u);                                                     \
+            }                                                                                                       \
+        }                                                                                                           \
+        slot += cnt;                                                                                                \
+    };
+// LDX_BAND_LANE: the lane's half and column, recomputed from an opaque copy of the lane id (see epilogue_f32).
+#define LDX_BAND_LANE                                                                                               \
+    uint32_t ln = lane;                                                                                             \
+    asm volatile("" : "+v"(ln));                                                                                    \
+    [[maybe_unused]] const uint32_t l32e = ln & 31u, halfe = ln >> 5;
+// LDX_BAND_COLS(l32x, per_col): this lane's four columns 32 tt + l32x of the j-tile from cstat -- ca, cs = its slots {a, s},
+// cpos = the position, j0 + 32 tt = the column's index; per_col is a statement for column tt that sees both slot pairs,
+// c0 = {a, s} and c1 = {position, mask}
+#define LDX_BAND_COLS(l32x, per_col)                                                                                \
+    [[maybe_unused]] double ca[4], cs[4], cpos[4];                                                                  \
+    _Pragma("unroll") for (int tt = 0; tt < 4; ++tt) {                                                              \
+        const d2s c0 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + (l32x)) * kStat);                         \
+        [[maybe_unused]] const d2s c1 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + (l32x)) * kStat + 2u);   \
+        ca[tt] = c0.x;                                                                                              \
+        cs[tt] = c0.y;                                                                                              \
+        cpos[tt] = c1.x;                                                                                            \
+        per_col;                                                                                                    \
+    }                                                                                                               \
+    const uint32_t j0 = t * kSlab + (l32x);
+// LDX_BAND_SWEEP_BEGIN(halfx) ... LDX_BAND_SWEEP_END: the sixteen steps over the wave's 2 x 4 accumulator tiles.  The text
+// between them is the body of one (step e, row tile m) -- `continue` goes to the next -- and sees: c4[tt], the lane's four
+// accumulators (ONE register-indexed read each, pinned: see area_epilogue); ri, the lane's row inside the wave's 64 (half 0:
+// rlo, half 1: rlo + 4); i = row0 + ri; r0 = {a, s} and r1 = {position, mask}, the row's rstat slots (two addresses per wave:
+// broadcast reads).  The step loop is not unrolled (see `epilogue`).
+#define LDX_BAND_SWEEP_BEGIN(halfx)                                                                                 \
+    _Pragma("unroll 1") for (int e = 0; e < 16; ++e) {                                                              \
+        _Pragma("unroll") for (int m = 0; m < 2; ++m) {                                                             \
+            accel_t c4[4];                                                                                          \
+            _Pragma("unroll") for (int tt = 0; tt < 4; ++tt) {                                                      \
+                c4[tt] = acc[m][tt][e];                                                                             \
+                asm volatile("" : "+v"(c4[tt]));                                                                    \
+            }                                                                                                       \
+            [[maybe_unused]] const uint32_t rlo = 32u * m + (uint32_t)(e & 3) + 8u * (uint32_t)(e >> 2);            \
+            const uint32_t ri = rlo + 4u * (halfx);                                                                 \
+            const d2s r0 = *reinterpret_cast<const d2s *>(rstat + ri * kStat);                                      \
+            [[maybe_unused]] const d2s r1 = *reinterpret_cast<const d2s *>(rstat + ri * kStat + 2u);                \
+            const uint32_t i = row0 + ri;
+#define LDX_BAND_SWEEP_END                                                                                          \
+        }                                                                                                           \
+    }
+
 // kFp4: the counting runs on v_mfma_f32_32x32x64_f8f6f4 with FP4 operands (expand32_a4 / expand32_b4) instead of
 // v_mfma_i32_32x32x32_i8: a K-block is then 256 haplotypes -- two 128-haplotype chunks, one per lane half -- in four
 // steps of 64, so the loop below keeps its shape (per step 8 MFMAs, 4 fragment reads, one quarter of the thread's share
 // of a later block's j-tile image) with `nblocks` = nchunks / 2 iterations and ~16 instead of ~28 VALU per step.
-// kScoreW (with kArea): the LD-score band (ldx_ld_score_dev) -- the band's passes and K loop with score_epilogue instead of
-// the hit scan; kScoreW is the number of `sums` words one sweep of the accumulators reduces (1: column 0 only; 5: column 0
-// and the categories, in sweeps of three words -- four or five spill).
-// kDosage (FP4; the r32 triangle, the LD-score band and the neighbour band): genotype-dosage r -- the B image is
+// kDosage (FP4; the r32 triangle and the Score, Nbr and Store bands): genotype-dosage r -- the B image is
 // expand32_b4_dosage's, `fa` holds the per-SNP table gstat {a, 1 / sqrt(v)} of ldx_dosage_stats_dev in place of the
 // frequencies (`fr` is not read) and `n` is the number of individuals; the epilogues are the haplotype ones unchanged.
-// kNbr (with kArea): the neighbour-list band (ldx_ld_neighbors_dev) -- the band's passes and K loop with nbr_epilogue, which
-// appends every pair with r *f32 r >= a float32 bound in both orientations, instead of the rounded hit scan.
-// kProdW (with kArea): the matrix-vector band (ldx_ld_matvec_dev) -- the LD-score band with prod_epilogue, score_epilogue's
-// weighted sibling: float32 weights per SNP instead of mask bits, the cell or its square instead of the square; kProdW is
-// the number of right-hand sides one sweep of the accumulators covers.
-// kDecay (with kArea): the LD-decay band (ldx_ld_decay_dev) -- the band's passes and K loop with decay_epilogue, which adds
-// every pair's score term and a count to the bin of its distance in a per-workgroup LDS histogram, flushed once at the end.
-// kFgt (with kArea): the four-gamete band (ldx_ld_fgt_dev) -- the band's passes and K loop with fgt_epilogue, an integer
-// predicate on the counts (no r cell) reduced to the highest recombinant column of every row.
-// kCross (with kScoreW = 1): the one-sided LD-score band (ldx_ld_cross_dev) -- score_epilogue unchanged up to its two flushes,
-// which keep the halves apart: the row path's totals (pair (i, j), i > j, seen from i: its LEFT partners) go to sides[i][0],
-// the column path's (seen from j: its RIGHT partners) to sides[j][1].  No register beside kScoreW = 1's.
-// kStore (with kArea): the band store (ldx_ld_band_dev) -- the band's passes and K loop with store_epilogue, which writes
-// every in-window r cell to its word of the caller's lower-band layout (lo / offsets) instead of reducing it.
-template <bool kRaw, bool kN11, bool kArea = false, bool kFp4 = false, typename Cell = ldx_ld32, int kScoreW = 0,
-          bool kNbr = false, int kProdW = 0, bool kDecay = false, bool kFgt = false, bool kCross = false, bool kDosage = false,
-          bool kStore = false>
-__global__ void __launch_bounds__(kMfmaThreads, kArea ? 2 : kWgPerCu)
+// kOp: what the launch does with the counts.  Every value but None runs the band's passes and K loop (AreaArgs above says
+// what the operator's arguments hold) and differs in its cstat / rstat staging and its epilogue alone:
+//   None   the triangle: dense cells (`epilogue`, epilogue_f32, epilogue_r32).
+//   Hits   ld_area (ldx_area_scan_dev): area_epilogue, the rounded hit scan.
+//   Score  LD scores (ldx_ld_score_dev): score_epilogue, a reduction where the scan appends.  kSweep is the number of `sums`
+//          words one sweep of the accumulators reduces (1: column 0 only; 5 words -- column 0 and the categories -- go in
+//          sweeps of three: four or five spill).
+//   Cross  one-sided LD scores (ldx_ld_cross_dev): score_epilogue with kSweep = 1, unchanged up to its two flushes, which keep
+//          the halves apart: the row path's totals (pair (i, j), i > j, seen from i: its LEFT partners) go to sides[i][0],
+//          the column path's (seen from j: its RIGHT partners) to sides[j][1].  No register beside Score's at kSweep = 1.
+//   Nbr    neighbour lists (ldx_ld_neighbors_dev): nbr_epilogue, which appends every pair with r *f32 r >= a float32 bound in
+//          both orientations, instead of the rounded hit scan.
+//   Prod   matrix-vector products (ldx_ld_matvec_dev): prod_epilogue, score_epilogue's weighted sibling: float32 weights per
+//          SNP instead of mask bits, the cell or its square instead of the square; kSweep is the number of right-hand sides
+//          one sweep of the accumulators covers.
+//   Decay  LD decay (ldx_ld_decay_dev): decay_epilogue, which adds every pair's score term and a count to the bin of its
+//          distance in a per-workgroup LDS histogram, flushed once at the end.
+//   Fgt    the four-gamete test (ldx_ld_fgt_dev): fgt_epilogue, an integer predicate on the counts (no r cell) reduced to
+//          the highest recombinant column of every row.
+//   Store  the band store (ldx_ld_band_dev): store_epilogue, which writes every in-window r cell to its word of the caller's
+//          lower-band layout (lo / offsets) instead of reducing it.
+template <bool kRaw, bool kN11, BandOp kOp = BandOp::None, bool kFp4 = false, typename Cell = ldx_ld32, int kSweep = 0,
+          bool kDosage = false>
+__global__ void __launch_bounds__(kMfmaThreads, kOp != BandOp::None ? 2 : kWgPerCu)
 triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ fa, const double *__restrict__ fr,
                      const double *__restrict__ q, uint32_t n_snps, uint32_t n_slabs, uint32_t nchunks, double n,
                      double rn, uint64_t u_begin, uint64_t u_end, Cell *__restrict__ out, ldx_ld64 *__restrict__ raw,
                      uint32_t *__restrict__ n11, uint32_t p_begin, uint32_t p_end_arg, uint32_t n_short, uint32_t *sched,
                      int ablate_arg, unsigned long long *stamps, AreaArgs aa)
 {
+    // the operator, once, under the names the body reads
+    constexpr bool kArea = kOp != BandOp::None;                          // any band operator: the plan's passes, two workgroups per CU
+    constexpr bool kCross = kOp == BandOp::Cross;
+    constexpr bool kScore = kOp == BandOp::Score || kCross;              // score_epilogue: r32 operands, integer sums instead of hits
+    constexpr bool kNbr = kOp == BandOp::Nbr, kProd = kOp == BandOp::Prod, kDecay = kOp == BandOp::Decay;
+    constexpr bool kFgt = kOp == BandOp::Fgt, kStore = kOp == BandOp::Store;
+    static_assert((kSweep != 0) == (kScore || kProd), "kSweep: the words (Score, Cross) or right-hand sides (Prod) per accumulator sweep");
+    static_assert(!kCross || kSweep == 1, "the one-sided sums are the score band's column 0, rows and columns apart");
     const uint32_t p_end = kArea ? aa.pass_base[n_slabs] : p_end_arg;   // area: the plan kernel's total
     // Tickets: first the passes [p_begin, p_end - n_short) whole, then each of the last n_short passes as TWO
     // half-height tickets (rows 0..31 / 32..63 of the pass's four units): finer work items for the end of the
@@ -462,16 +568,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
     // fp32 tier (ldx_common.h, ld_multi_f32): its per-SNP tables and each wave's queue of lane-steps for the fp64 tier
     constexpr bool kR32 = std::is_same<Cell, ldx_r32>::value;   // signed r cells: epilogue_r32, none of the rounding tiers
     constexpr bool kF32Tier = kFp4 && !kRaw && !kN11 && !kArea && !kR32;
-    constexpr bool kScore = kScoreW != 0;   // LD scores (score_epilogue): r32 operands, integer sums instead of hits
-    static_assert(!kScore || kArea, "the LD-score epilogue runs on the band");
-    static_assert(!kCross || kScoreW == 1, "the one-sided sums are the score band's column 0, rows and columns apart");
-    static_assert(!kNbr || (kArea && !kScore), "the neighbour epilogue runs on the band");
-    constexpr bool kProd = kProdW != 0;     // matrix-vector products (prod_epilogue): the score band with float32 weights
-    static_assert(!kProd || (kArea && !kScore && !kNbr), "the matrix-vector epilogue runs on the band");
-    static_assert(!kDecay || (kArea && !kScore && !kNbr && !kProd), "the decay epilogue runs on the band");
-    static_assert(!kFgt || (kArea && !kScore && !kNbr && !kProd && !kDecay), "the four-gamete epilogue runs on the band");
-    static_assert(!kStore || (kArea && !kScore && !kNbr && !kProd && !kDecay && !kFgt), "the band store's epilogue runs on the band");
-    static_assert(!kDosage || (kFp4 && !kCross && ((kR32 && !kArea) || (kScore && !kProd) || kNbr || kStore)),
+    static_assert(!kDosage || (kFp4 && ((kR32 && !kArea) || kOp == BandOp::Score || kNbr || kStore)),
                   "dosage r: the FP4 r32 triangle, the LD-score band, the neighbour band and the band store");
     // the per-SNP {a, rs} of the r32 epilogues: r32_snp of the frequencies, or row x of the dosage table
     auto snp_ars = [&](uint32_t x) {
@@ -482,7 +579,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             return r32_snp(fa[x], fr[x], n);
         }
     };
-    constexpr bool kBandF32 = kFp4 && kArea && !kScore && !kNbr && !kProd && !kDecay && !kFgt && !kStore;   // the band screens its steps in float32 first (area_epilogue)
+    constexpr bool kBandF32 = kFp4 && kOp == BandOp::Hits;   // the band screens its steps in float32 first (area_epilogue)
     float *ctab32 = reinterpret_cast<float *>(tickets + 8);                 // [128][4]: F32Col
     float *rtab32 = ctab32 + kSlab * 4u + wave * (kRows64 * 4u);            // [64][4]: F32Row, private to the wave
     uint32_t *qid = reinterpret_cast<uint32_t *>(ctab32 + kSlab * 4u + kMfmaWaves * kRows64 * 4u) + wave * kQueueCap;   // [kQueueCap]
@@ -503,7 +600,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
     // 12 bytes per row, written per pass beside rstat and read by the same wave only
     uint64_t *const store_off = reinterpret_cast<uint64_t *>(ctab32) + wave * (kRows64 * 3u / 2u);
     uint32_t *const store_lo = reinterpret_cast<uint32_t *>(store_off + kRows64);
-    uint64_t *const decay_cnt = decay_sum + (kDecay ? (uint32_t)aa.measure : 0u);   // aa.measure: n_bins
+    uint64_t *const decay_cnt = decay_sum + (kDecay ? (uint32_t)aa.measure : 0u);   // n_bins
     const F32Const fc32 = aa.f32;   // computed on the host (f32_const): kernel arguments live in scalar registers
     // The band (ld_area) hands its passes out PER XCD: the pass list -- j-tile-major, i.e. sorted by position -- is cut into
     // eight contiguous ranges, one per XCD, each with its own counter (sched[2 + 32 x]: the K-loop-token words, which the
@@ -632,6 +729,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             typedef std::conditional_t<kFp4, v16f, v16i> acc_t;
             typedef std::conditional_t<kFp4, float, int> accel_t;   // one accumulator element: n11 (FP4) or 8 * n11 (int8)
             auto count_of = [](accel_t x) { if constexpr (kFp4) return (uint32_t)x; else return (uint32_t)x >> 3; };
+            auto count_f64 = [](accel_t x) { if constexpr (kFp4) return (double)x; else return (double)((uint32_t)x >> 3); };   // (FP4: no detour through an integer)
             acc_t acc[MM][4];
 #pragma unroll
             for (int m = 0; m < MM; ++m)
@@ -760,7 +858,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             }
             bool rows_ordinary = false;
             typedef double d2s __attribute__((ext_vector_type(2)));
-            if constexpr (kFgt) {   // four-gamete test: {a, -} (aa.counts: the ALT counts) and {position, keep mask}
+            if constexpr (kFgt) {   // four-gamete test: {a, -} (the ALT counts) and {position, keep mask}
                 if (new_tile && tid < kSlab) {
                     const uint32_t j = t * kSlab + tid;
                     d2s *dst = reinterpret_cast<d2s *>(cstat + tid * kStat);
@@ -779,7 +877,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 const uint32_t i = row0 + lane;
                 const R32Snp r = snp_ars(i);
                 *reinterpret_cast<d2s *>(rstat + lane * kStat) = d2s{r.a, r.rs};
-                // aa.counts: lo, aa.is_query: offsets.  A row beyond the panel gets lo = 2^32 - 1: no column reaches it
+                // lo and offsets (AreaArgs' table).  A row beyond the panel gets lo = 2^32 - 1: no column reaches it
                 store_lo[lane] = i < n_snps ? aa.counts[i] : 0xFFFFFFFFu;
                 store_off[lane] = i < n_snps ? reinterpret_cast<const uint64_t *>(aa.is_query)[i] : 0u;
             } else if constexpr (kScore || kNbr || kProd || kDecay) {   // LD scores / neighbours / products / decay: {a, 1 / sqrt(a r)} (r32_snp) and {position, annotation mask}
@@ -1528,7 +1626,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                         Cell o4[4];
 #pragma unroll
                         for (int tt = 0; tt < 4; ++tt) {
-                            const double cnt = kFp4 ? (double)c4[tt] : (double)((uint32_t)c4[tt] >> 3);   // int8: 8 n11
+                            const double cnt = count_f64(c4[tt]);
                             o4[tt] = r32_cell(cnt, n, rw.x, rw.y, ca[tt], cs[tt]);
                             if (!all_valid && !(i > j0 + 32u * tt && i < n_snps)) o4[tt] = zero_cell<Cell>();
                         }
@@ -1537,6 +1635,23 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                     }
                 }
               }
+            };
+            // finish_pass: the next pass's ticket goes to LDS and the wave drops its epilogue priority; stamps_c (tuning builds):
+            // the pass's last stamp and the wave's pass count
+            auto finish_pass = [&](auto stamps_c) {
+                if (tid == 0) tickets[parity] = next_ticket;
+                if (!(ablate & 16)) __builtin_amdgcn_s_setprio(0);
+#ifdef LDX_TUNING
+                if constexpr (decltype(stamps_c)::value) {
+                    LDX_STAMP(3);
+                    ++npass;
+                    if (my_stamps && lane == 0) {
+                        my_stamps[3] = npass;
+                        my_stamps[4] = __builtin_amdgcn_s_memrealtime();
+                        my_stamps[5] = __builtin_amdgcn_s_memtime();
+                    }
+                }
+#endif
             };
             // ---- ld_area: thresholded hits instead of a dense result ----
             // Pair (i, j), i > j, pos_i >= pos_j, serves two ordered pairs of the reference's loop:
@@ -1555,77 +1670,51 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             // holds its four columns for 32 rows and sums them in registers; the two halves meet through one shuffle, the four
             // waves through LDS (the image buffers, free after the barrier above).  Every word then goes to global memory
             // once per pass and destination, as a 64-bit integer atomic (order-independent: bit-reproducible).  A sweep covers
-            // kScoreW words (registers: 4 x kScoreW column sums beside the 128 accumulators); categories beyond it take a
+            // kSweep words (registers: 4 x kSweep column sums beside the 128 accumulators); categories beyond it take a
             // second sweep over the same accumulators.
             uint64_t *const score_cols = reinterpret_cast<uint64_t *>(bexp);   // [4 waves][128 columns][1 + K]
             auto score_epilogue = [&](uint32_t st) {
               if constexpr (kScore) {
                 const double win = aa.flank;   // the window w (integer-valued)
                 uint64_t *const rows_lds = reinterpret_cast<uint64_t *>(ctab32) + wave * (kRows64 * 9u);   // [64 rows][1 + K]
-                uint32_t ln = lane;   // (lane-derived values recomputed from an opaque copy of the lane id: see epilogue_f32)
-                asm volatile("" : "+v"(ln));
-                const uint32_t l32e = ln & 31u, halfe = ln >> 5;
-                double ca[4], cs[4], cpos[4];   // this lane's four columns
-                uint32_t cmask[4];              // (annotation << 1) | 1: bit c selects word c
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt) {
-                    const d2s c0 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32e) * kStat);
-                    const d2s c1 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32e) * kStat + 2u);
-                    ca[tt] = c0.x;
-                    cs[tt] = c0.y;
-                    cpos[tt] = c1.x;
-                    cmask[tt] = ((uint32_t)c1.y << 1) | 1u;
-                }
-                const uint32_t j0 = t * kSlab + l32e;   // column of tile tt: j0 + 32 tt
-                for (uint32_t w0 = 0; w0 < st; w0 += (uint32_t)kScoreW) {   // wave-uniform sweeps
-                    uint64_t csum[4][kScoreW];
+                LDX_BAND_LANE
+                uint32_t cmask[4];   // (annotation << 1) | 1: bit c selects word c
+                LDX_BAND_COLS(l32e, cmask[tt] = ((uint32_t)c1.y << 1) | 1u)
+                for (uint32_t w0 = 0; w0 < st; w0 += (uint32_t)kSweep) {   // wave-uniform sweeps
+                    uint64_t csum[4][kSweep];
 #pragma unroll
                     for (int tt = 0; tt < 4; ++tt)
 #pragma unroll
-                        for (int c = 0; c < kScoreW; ++c) csum[tt][c] = 0;
-#pragma unroll 1
-                    for (int e = 0; e < 16; ++e) {
-#pragma unroll
-                        for (int m = 0; m < 2; ++m) {
-                            accel_t c4[4];   // ONE register-indexed read per accumulator, pinned (see area_epilogue)
-#pragma unroll
-                            for (int tt = 0; tt < 4; ++tt) {
-                                c4[tt] = acc[m][tt][e];
-                                asm volatile("" : "+v"(c4[tt]));
-                            }
-                            const uint32_t ri = 32u * m + (uint32_t)(e & 3) + 8u * (uint32_t)(e >> 2) + 4u * halfe;
-                            const d2s r0 = *reinterpret_cast<const d2s *>(rstat + ri * kStat);   // two addresses per wave: broadcast
-                            const d2s r1 = *reinterpret_cast<const d2s *>(rstat + ri * kStat + 2u);
+                        for (int c = 0; c < kSweep; ++c) csum[tt][c] = 0;
+                    LDX_BAND_SWEEP_BEGIN(halfe)
                             const uint32_t rmask = (((uint32_t)r1.y << 1) | 1u) >> w0;
-                            const uint32_t i = row0 + ri;
-                            uint64_t rsum[kScoreW];
+                            uint64_t rsum[kSweep];
 #pragma unroll
-                            for (int c = 0; c < kScoreW; ++c) rsum[c] = 0;
+                            for (int c = 0; c < kSweep; ++c) rsum[c] = 0;
 #pragma unroll
                             for (int tt = 0; tt < 4; ++tt) {
-                                const double cnt = kFp4 ? (double)c4[tt] : (double)((uint32_t)c4[tt] >> 3);   // int8: 8 n11
+                                const double cnt = count_f64(c4[tt]);
                                 uint64_t term = score_term(r32_cell(cnt, n, r0.x, r0.y, ca[tt], cs[tt]).r);
                                 const bool ok = i > j0 + 32u * tt && i < n_snps && r1.x - cpos[tt] <= win;
                                 term = ok ? term : 0u;
                                 const uint32_t cm = cmask[tt] >> w0;
 #pragma unroll
-                                for (int c = 0; c < kScoreW; ++c) {
+                                for (int c = 0; c < kSweep; ++c) {
                                     rsum[c] += ((cm >> c) & 1u) ? term : 0u;
                                     csum[tt][c] += ((rmask >> c) & 1u) ? term : 0u;
                                 }
                             }
 #pragma unroll
-                            for (int c = 0; c < kScoreW; ++c) {
+                            for (int c = 0; c < kSweep; ++c) {
                                 if (w0 + (uint32_t)c >= st) break;   // wave-uniform
                                 const uint64_t v = dpp_half_sum(rsum[c]);
                                 if (l32e == 31u) rows_lds[ri * st + w0 + (uint32_t)c] = v;
                             }
-                        }
-                    }
+                    LDX_BAND_SWEEP_END
                     // the halves' column sums meet: half 0 keeps column tiles 0, 1, half 1 tiles 2, 3 (one shuffle per pair)
                     uint64_t *const my_cols = score_cols + (size_t)wave * (kSlab * 9u);
 #pragma unroll
-                    for (int c = 0; c < kScoreW; ++c) {
+                    for (int c = 0; c < kSweep; ++c) {
                         if (w0 + (uint32_t)c >= st) break;   // wave-uniform
 #pragma unroll
                         for (int p = 0; p < 2; ++p) {
@@ -1655,81 +1744,56 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             // word k and prod_term(v, x[i][k]) to column j's -- two terms per pair and right-hand side.  The row's weights are
             // broadcast LDS reads beside rstat (prod_rows); the lane's four columns' weights are loaded from global memory
             // into registers once per sweep (a table of them would push the workgroup past half a CU's LDS).  A sweep
-            // covers kProdW right-hand sides; further ones repeat it, recomputing r32_cell.
+            // covers kSweep right-hand sides; further ones repeat it, recomputing r32_cell.
             auto prod_epilogue = [&](uint32_t st, bool square) {
               if constexpr (kProd) {
                 const double win = aa.flank;   // the window w (integer-valued)
                 const float *const x = reinterpret_cast<const float *>(aa.counts);   // [n_snps][st]
                 uint64_t *const rows_lds = reinterpret_cast<uint64_t *>(ctab32) + wave * (kRows64 * 8u);   // [64 rows][st]
                 const float *const xrow = prod_rows(wave);
-                uint32_t ln = lane;   // (lane-derived values recomputed from an opaque copy of the lane id: see epilogue_f32)
-                asm volatile("" : "+v"(ln));
-                const uint32_t l32e = ln & 31u, halfe = ln >> 5;
-                double ca[4], cs[4], cpos[4];   // this lane's four columns
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt) {
-                    const d2s c0 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32e) * kStat);
-                    const d2s c1 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32e) * kStat + 2u);
-                    ca[tt] = c0.x;
-                    cs[tt] = c0.y;
-                    cpos[tt] = c1.x;
-                }
-                const uint32_t j0 = t * kSlab + l32e;   // column of tile tt: j0 + 32 tt
-                for (uint32_t w0 = 0; w0 < st; w0 += (uint32_t)kProdW) {   // wave-uniform sweeps
-                    uint64_t csum[4][kProdW];
-                    float xc[4][kProdW];   // the columns' weights of this sweep (0 beyond st and beyond the panel)
+                LDX_BAND_LANE
+                LDX_BAND_COLS(l32e, )
+                for (uint32_t w0 = 0; w0 < st; w0 += (uint32_t)kSweep) {   // wave-uniform sweeps
+                    uint64_t csum[4][kSweep];
+                    float xc[4][kSweep];   // the columns' weights of this sweep (0 beyond st and beyond the panel)
 #pragma unroll
                     for (int tt = 0; tt < 4; ++tt)
 #pragma unroll
-                        for (int c = 0; c < kProdW; ++c) {
+                        for (int c = 0; c < kSweep; ++c) {
                             csum[tt][c] = 0;
                             const uint32_t j = j0 + 32u * tt;
                             xc[tt][c] = (j < n_snps && w0 + (uint32_t)c < st) ? x[(size_t)j * st + w0 + (uint32_t)c] : 0.0f;
                         }
-#pragma unroll 1
-                    for (int e = 0; e < 16; ++e) {
+                    LDX_BAND_SWEEP_BEGIN(halfe)
+                            float xr[kSweep];   // the row's weights: broadcast reads (zeros beyond st; kSweep divides 8: w0 + c < 8)
 #pragma unroll
-                        for (int m = 0; m < 2; ++m) {
-                            accel_t c4[4];   // ONE register-indexed read per accumulator, pinned (see area_epilogue)
+                            for (int c = 0; c < kSweep; ++c) xr[c] = xrow[ri * 8u + w0 + (uint32_t)c];
+                            uint64_t rsum[kSweep];
 #pragma unroll
-                            for (int tt = 0; tt < 4; ++tt) {
-                                c4[tt] = acc[m][tt][e];
-                                asm volatile("" : "+v"(c4[tt]));
-                            }
-                            const uint32_t ri = 32u * m + (uint32_t)(e & 3) + 8u * (uint32_t)(e >> 2) + 4u * halfe;
-                            const d2s r0 = *reinterpret_cast<const d2s *>(rstat + ri * kStat);   // two addresses per wave: broadcast
-                            const d2s r1 = *reinterpret_cast<const d2s *>(rstat + ri * kStat + 2u);
-                            float xr[kProdW];   // the row's weights: broadcast reads (zeros beyond st; kProdW divides 8: w0 + c < 8)
-#pragma unroll
-                            for (int c = 0; c < kProdW; ++c) xr[c] = xrow[ri * 8u + w0 + (uint32_t)c];
-                            const uint32_t i = row0 + ri;
-                            uint64_t rsum[kProdW];
-#pragma unroll
-                            for (int c = 0; c < kProdW; ++c) rsum[c] = 0;
+                            for (int c = 0; c < kSweep; ++c) rsum[c] = 0;
 #pragma unroll
                             for (int tt = 0; tt < 4; ++tt) {
-                                const double cnt = kFp4 ? (double)c4[tt] : (double)((uint32_t)c4[tt] >> 3);   // int8: 8 n11
+                                const double cnt = count_f64(c4[tt]);
                                 float v = prod_value(r32_cell(cnt, n, r0.x, r0.y, ca[tt], cs[tt]).r, square);
                                 const bool ok = i > j0 + 32u * tt && i < n_snps && r1.x - cpos[tt] <= win;
                                 v = ok ? v : 0.0f;   // (a pair outside the band: both terms 0)
 #pragma unroll
-                                for (int c = 0; c < kProdW; ++c) {
+                                for (int c = 0; c < kSweep; ++c) {
                                     rsum[c] += prod_term(v, xc[tt][c]);
                                     csum[tt][c] += prod_term(v, xr[c]);
                                 }
                             }
 #pragma unroll
-                            for (int c = 0; c < kProdW; ++c) {
+                            for (int c = 0; c < kSweep; ++c) {
                                 if (w0 + (uint32_t)c >= st) break;   // wave-uniform
                                 const uint64_t tot = dpp_half_sum(rsum[c]);
                                 if (l32e == 31u) rows_lds[ri * st + w0 + (uint32_t)c] = tot;
                             }
-                        }
-                    }
+                    LDX_BAND_SWEEP_END
                     // the halves' column sums meet: half 0 keeps column tiles 0, 1, half 1 tiles 2, 3 (one shuffle per pair)
                     uint64_t *const my_cols = score_cols + (size_t)wave * (kSlab * 9u);
 #pragma unroll
-                    for (int c = 0; c < kProdW; ++c) {
+                    for (int c = 0; c < kSweep; ++c) {
                         if (w0 + (uint32_t)c >= st) break;   // wave-uniform
 #pragma unroll
                         for (int p = 0; p < 2; ++p) {
@@ -1752,34 +1816,11 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
               }
             };
             auto area_epilogue = [&]() {
-              if constexpr (kArea && MM == 2 && !kScore && !kNbr && !kProd && !kDecay && !kFgt && !kStore) {
-                uint64_t slot = hit_slot, slot_end = hit_slot_end;
+              if constexpr (kOp == BandOp::Hits && MM == 2) {
+                LDX_HIT_APPENDER
                 const double kthr = aa.k_thres;
                 const bool prefilter = aa.k_thres > 2.0;
                 const double kcand = aa.k_thres - 2.0;
-                auto append = [&](bool keep, uint32_t qrow, uint32_t orow, ldx_ld32 v) {
-                    const unsigned long long mask = __ballot(keep);
-                    if (!mask) return;   // wave-uniform
-                    const uint32_t cnt = __builtin_popcountll(mask);
-                    if (slot + cnt > slot_end) {   // close the old batch (mark what is left invalid), open a new one
-                        for (uint64_t sl = slot + lane; sl < slot_end; sl += 64u)
-                            if (sl < aa.hit_cap) aa.hits[sl].query = 0xFFFFFFFFu;
-                        unsigned long long base = 0;
-                        if (lane == 0) base = atomicAdd(aa.n_hits, (unsigned long long)kHitBatch);
-                        base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-                               __builtin_amdgcn_readfirstlane((uint32_t)base);
-                        slot = base;
-                        slot_end = base + kHitBatch;
-                    }
-                    if (keep) {
-                        const uint64_t sl = slot + __builtin_popcountll(mask & ((1ull << lane) - 1ull));
-                        if (sl < aa.hit_cap) {
-                            aa.hits[sl] = ldx_hit{qrow, orow, v.r_square, v.d_prime};
-                            if (aa.counts) atomicAdd(&aa.counts[qrow], 1u);   // only stored hits: what the scatter will place
-                        }
-                    }
-                    slot += cnt;
-                };
                 // Float32 screen of a whole step (r^2 thresholds): hits are rare, and the fp64 prefilter below still costs every
                 // (step, column tile) three 16-byte LDS reads per lane and ~7 double-rate instructions per pair.  With this lane's
                 // four columns held in registers as {ah, al, c = sqrt(k) / s2} and the step's two rows read as {a, s1} (s = 10 /
@@ -1859,8 +1900,8 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                         const float vb = aa.measure == LDX_MEASURE_RSQ ? rb.r_square : rb.d_prime;
                         const double ka = va != va ? __builtin_inf() : __builtin_rint((double)va * 1e4);
                         const double kb = vb != vb ? __builtin_inf() : __builtin_rint((double)vb * 1e4);
-                        append(in_a && ka >= kthr, i, j, ra);                              // ld_area.py:248
-                        append(in_b && kb >= kthr, j, i, rb);
+                        append(in_a && ka >= kthr, i, j, ra.r_square, ra.d_prime);         // ld_area.py:248
+                        append(in_b && kb >= kthr, j, i, rb.r_square, rb.d_prime);
                     }
                     aqn = 0;
                     __builtin_amdgcn_wave_barrier();   // (the next pushes overwrite entries this loop has read)
@@ -1970,65 +2011,20 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             // bit for bit), s = c *f32 c (one float32 multiply, as score_term), kept iff s >= b -- aa.k_thres holds the float32
             // bound the host derived from the user's threshold, so `r^2 >= t` and `r^2 > t` are both this one comparison.  The
             // -0.0f cell of a degenerate SNP and a cell with num == 0 give s = 0 < b: never kept.  A kept pair goes out as
-            // {i, j, c, s} and {j, i, c, s} through area_epilogue's appender (256-slot batches per wave, unused slots marked,
+            // {i, j, c, s} and {j, i, c, s} through LDX_HIT_APPENDER's append (256-slot batches per wave, unused slots marked,
             // stored records counted per row into aa.counts), so ldx_area_finish_ex_dev sorts them into a per-SNP CSR.
             // Hits are rare: a (step, row tile) whose eight pairs per lane hold none costs one ballot and no append.
             auto nbr_epilogue = [&]() {
               if constexpr (kNbr && MM == 2) {
-                uint64_t slot = hit_slot, slot_end = hit_slot_end;
-                auto append = [&](bool keep, uint32_t qrow, uint32_t orow, float r, float s) {   // (area_epilogue's append)
-                    const unsigned long long mask = __ballot(keep);
-                    if (!mask) return;   // wave-uniform
-                    const uint32_t cnt = __builtin_popcountll(mask);
-                    if (slot + cnt > slot_end) {   // close the old batch (mark what is left invalid), open a new one
-                        for (uint64_t sl = slot + lane; sl < slot_end; sl += 64u)
-                            if (sl < aa.hit_cap) aa.hits[sl].query = 0xFFFFFFFFu;
-                        unsigned long long base = 0;
-                        if (lane == 0) base = atomicAdd(aa.n_hits, (unsigned long long)kHitBatch);
-                        base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-                               __builtin_amdgcn_readfirstlane((uint32_t)base);
-                        slot = base;
-                        slot_end = base + kHitBatch;
-                    }
-                    if (keep) {
-                        const uint64_t sl = slot + __builtin_popcountll(mask & ((1ull << lane) - 1ull));
-                        if (sl < aa.hit_cap) {
-                            aa.hits[sl] = ldx_hit{qrow, orow, r, s};
-                            if (aa.counts) atomicAdd(&aa.counts[qrow], 1u);
-                        }
-                    }
-                    slot += cnt;
-                };
+                LDX_HIT_APPENDER
                 const double win = aa.flank, bound = aa.k_thres;
-                double ca[4], cs[4], cpos[4];   // this lane's four columns
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt) {
-                    const d2s c0 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32) * kStat);
-                    const d2s c1 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32) * kStat + 2u);
-                    ca[tt] = c0.x;
-                    cs[tt] = c0.y;
-                    cpos[tt] = c1.x;
-                }
-                const uint32_t j0 = t * kSlab + l32;   // column of tile tt: j0 + 32 tt
-#pragma unroll 1
-                for (int e = 0; e < 16; ++e) {
-#pragma unroll
-                    for (int m = 0; m < 2; ++m) {
-                        accel_t c4[4];   // ONE register-indexed read per accumulator, pinned (see area_epilogue)
-#pragma unroll
-                        for (int tt = 0; tt < 4; ++tt) {
-                            c4[tt] = acc[m][tt][e];
-                            asm volatile("" : "+v"(c4[tt]));
-                        }
-                        const uint32_t ri = 32u * m + (uint32_t)(e & 3) + 8u * (uint32_t)(e >> 2) + 4u * half;
-                        const d2s r0 = *reinterpret_cast<const d2s *>(rstat + ri * kStat);   // two addresses per wave: broadcast
-                        const d2s r1 = *reinterpret_cast<const d2s *>(rstat + ri * kStat + 2u);
-                        const uint32_t i = row0 + ri;
+                LDX_BAND_COLS(l32, )   // (the kernel's own l32 / half, not the opaque copies)
+                LDX_BAND_SWEEP_BEGIN(half)
                         float rc[4];
                         bool keep[4];
 #pragma unroll
                         for (int tt = 0; tt < 4; ++tt) {
-                            const double cnt = kFp4 ? (double)c4[tt] : (double)((uint32_t)c4[tt] >> 3);   // int8: 8 n11
+                            const double cnt = count_f64(c4[tt]);
                             rc[tt] = r32_cell(cnt, n, r0.x, r0.y, ca[tt], cs[tt]).r;
                             const float sq = rc[tt] * rc[tt];
                             keep[tt] = i > j0 + 32u * tt && i < n_snps && r1.x - cpos[tt] <= win && (double)sq >= bound;
@@ -2040,8 +2036,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                             append(keep[tt], i, j, rc[tt], rc[tt] * rc[tt]);
                             append(keep[tt], j, i, rc[tt], rc[tt] * rc[tt]);
                         }
-                    }
-                }
+                LDX_BAND_SWEEP_END
                 hit_slot = slot;
                 hit_slot_end = slot_end;
               }
@@ -2064,39 +2059,14 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
               if constexpr (kDecay && MM == 2) {
                 const double win = aa.flank, bw = aa.k_thres, rbw = 1.0 / bw;   // the window and the bin width (integer-valued)
                 const uint32_t last_bin = (uint32_t)aa.measure - 1u;
-                uint32_t ln = lane;   // (lane-derived values recomputed from an opaque copy of the lane id: see epilogue_f32)
-                asm volatile("" : "+v"(ln));
-                const uint32_t l32e = ln & 31u, halfe = ln >> 5;
-                double ca[4], cs[4], cpos[4];   // this lane's four columns
+                LDX_BAND_LANE
                 bool ckeep[4];
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt) {
-                    const d2s c0 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32e) * kStat);
-                    const d2s c1 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32e) * kStat + 2u);
-                    ca[tt] = c0.x;
-                    cs[tt] = c0.y;
-                    cpos[tt] = c1.x;
-                    ckeep[tt] = c1.y != 0.0;
-                }
-                const uint32_t j0 = t * kSlab + l32e;   // column of tile tt: j0 + 32 tt
-#pragma unroll 1
-                for (int e = 0; e < 16; ++e) {
-#pragma unroll
-                    for (int m = 0; m < 2; ++m) {
-                        accel_t c4[4];   // ONE register-indexed read per accumulator, pinned (see area_epilogue)
-#pragma unroll
-                        for (int tt = 0; tt < 4; ++tt) {
-                            c4[tt] = acc[m][tt][e];
-                            asm volatile("" : "+v"(c4[tt]));
-                        }
-                        const uint32_t ri = 32u * m + (uint32_t)(e & 3) + 8u * (uint32_t)(e >> 2) + 4u * halfe;
-                        const d2s r0 = *reinterpret_cast<const d2s *>(rstat + ri * kStat);   // two addresses per wave: broadcast
-                        const d2s r1 = *reinterpret_cast<const d2s *>(rstat + ri * kStat + 2u);
-                        const uint32_t i = row0 + ri;
+                LDX_BAND_COLS(l32e, ckeep[tt] = c1.y != 0.0)
+                LDX_BAND_SWEEP_BEGIN(halfe)
                         const bool rkeep = i < n_snps && r1.y != 0.0;
 #pragma unroll
                         for (int tt = 0; tt < 4; ++tt) {
-                            const double cnt = kFp4 ? (double)c4[tt] : (double)((uint32_t)c4[tt] >> 3);   // int8: 8 n11
+                            const double cnt = count_f64(c4[tt]);
                             uint64_t term = score_term(r32_cell(cnt, n, r0.x, r0.y, ca[tt], cs[tt]).r);
                             const double d = r1.x - cpos[tt];
                             const bool ok = rkeep && ckeep[tt] && i > j0 + 32u * tt && d <= win;
@@ -2129,8 +2099,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                             }
 #endif
                         }
-                    }
-                }
+                LDX_BAND_SWEEP_END
               }
             };
             // ---- four-gamete test (ldx_ld_fgt_dev): per row, the highest recombinant column ----
@@ -2147,44 +2116,18 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
               if constexpr (kFgt && MM == 2) {
                 const double win = aa.flank;
                 const uint32_t mc = (uint32_t)aa.measure, nh = (uint32_t)n;
-                uint32_t ln = lane;   // (lane-derived values recomputed from an opaque copy of the lane id: see epilogue_f32)
-                asm volatile("" : "+v"(ln));
-                const uint32_t l32e = ln & 31u;
-                uint32_t caj[4];   // this lane's four columns
-                double cpos[4];
+                LDX_BAND_LANE
+                uint32_t caj[4];   // the columns' ALT counts
                 bool ckeep[4];
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt) {
-                    const d2s c0 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32e) * kStat);
-                    const d2s c1 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32e) * kStat + 2u);
-                    caj[tt] = (uint32_t)c0.x;
-                    cpos[tt] = c1.x;
-                    ckeep[tt] = c1.y != 0.0;
-                }
-                const uint32_t j0 = t * kSlab + l32e;   // column of tile tt: j0 + 32 tt
-                const uint32_t halfe = ln >> 5;
+                LDX_BAND_COLS(l32e, (caj[tt] = (uint32_t)c0.x, ckeep[tt] = c1.y != 0.0))
                 uint32_t best = 0u;   // lane L: 1 + the highest recombinant column of row L in this tile, 0 if none
-#pragma unroll 1
-                for (int e = 0; e < 16; ++e) {
-#pragma unroll
-                    for (int m = 0; m < 2; ++m) {
-                        accel_t c4[4];   // ONE register-indexed read per accumulator, pinned (see area_epilogue)
-#pragma unroll
-                        for (int tt = 0; tt < 4; ++tt) {
-                            c4[tt] = acc[m][tt][e];
-                            asm volatile("" : "+v"(c4[tt]));
-                        }
-                        const uint32_t rlo = 32u * m + (uint32_t)(e & 3) + 8u * (uint32_t)(e >> 2);   // half 0's row; half 1: rlo + 4
-                        const uint32_t ri = rlo + 4u * halfe;
-                        const d2s r0 = *reinterpret_cast<const d2s *>(rstat + ri * kStat);   // two addresses per wave: broadcast
-                        const d2s r1 = *reinterpret_cast<const d2s *>(rstat + ri * kStat + 2u);
-                        const uint32_t i = row0 + ri;
+                LDX_BAND_SWEEP_BEGIN(halfe)
                         const uint32_t ai = (uint32_t)r0.x;
                         const bool rkeep = r1.y != 0.0;   // (0 for a row beyond the panel)
                         unsigned long long bm[4];
 #pragma unroll
                         for (int tt = 0; tt < 4; ++tt) {
-                            const uint32_t g11 = kFp4 ? (uint32_t)c4[tt] : (uint32_t)c4[tt] >> 3;   // int8: 8 n11
+                            const uint32_t g11 = kFp4 ? (uint32_t)c4[tt] : (uint32_t)c4[tt] >> 3;   // int8: 8 n11 (count_of here reorders a v_min3_u32's operands)
                             const uint32_t g10 = ai - g11, g01 = caj[tt] - g11, g00 = nh - ai - g01;
                             const uint32_t lo = g11 < g10 ? g11 : g10, hi = g01 < g00 ? g01 : g00;
                             const bool hit = (lo < hi ? lo : hi) >= mc && rkeep && ckeep[tt] && i > j0 + 32u * tt && r1.x - cpos[tt] <= win;
@@ -2197,8 +2140,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                         const uint32_t vlo = lo23 ? 128u - (uint32_t)__builtin_clzll(lo23) : (lo01 ? 64u - (uint32_t)__builtin_clzll(lo01) : 0u);
                         const uint32_t vhi = hi23 ? 128u - (uint32_t)__builtin_clzll(hi23) : (hi01 ? 64u - (uint32_t)__builtin_clzll(hi01) : 0u);
                         best = ln == rlo ? vlo : (ln == rlo + 4u ? vhi : best);
-                    }
-                }
+                LDX_BAND_SWEEP_END
                 const uint32_t i = row0 + ln;
                 if (best != 0u && i < n_snps) atomicMax(reinterpret_cast<uint32_t *>(aa.hits) + i, t * kSlab + best);
               }
@@ -2216,42 +2158,20 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
               if constexpr (kStore && MM == 2) {
                 float *const values = reinterpret_cast<float *>(aa.hits);
                 const uint64_t n_cells = aa.hit_cap;
-                uint32_t ln = lane;   // (lane-derived values recomputed from an opaque copy of the lane id: see epilogue_f32)
-                asm volatile("" : "+v"(ln));
-                const uint32_t l32e = ln & 31u, halfe = ln >> 5;
-                double ca[4], cs[4];   // this lane's four columns
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt) {
-                    const d2s c0 = *reinterpret_cast<const d2s *>(cstat + (32u * tt + l32e) * kStat);
-                    ca[tt] = c0.x;
-                    cs[tt] = c0.y;
-                }
-                const uint32_t j0 = t * kSlab + l32e;   // column of tile tt: j0 + 32 tt
-#pragma unroll 1
-                for (int e = 0; e < 16; ++e) {
-#pragma unroll
-                    for (int m = 0; m < 2; ++m) {
-                        accel_t c4[4];   // ONE register-indexed read per accumulator, pinned (see area_epilogue)
-#pragma unroll
-                        for (int tt = 0; tt < 4; ++tt) {
-                            c4[tt] = acc[m][tt][e];
-                            asm volatile("" : "+v"(c4[tt]));
-                        }
-                        const uint32_t ri = 32u * m + (uint32_t)(e & 3) + 8u * (uint32_t)(e >> 2) + 4u * halfe;
-                        const d2s r0 = *reinterpret_cast<const d2s *>(rstat + ri * kStat);   // two addresses per wave: broadcast
-                        const uint32_t i = row0 + ri;
+                LDX_BAND_LANE
+                LDX_BAND_COLS(l32e, )   // (cpos and the sweep's r1 stay unread: the layout is the window)
+                LDX_BAND_SWEEP_BEGIN(halfe)
                         const uint32_t lo_i = store_lo[ri];
                         const uint64_t off_i = store_off[ri];
 #pragma unroll
                         for (int tt = 0; tt < 4; ++tt) {
-                            const double cnt = kFp4 ? (double)c4[tt] : (double)((uint32_t)c4[tt] >> 3);   // int8: 8 n11
+                            const double cnt = count_f64(c4[tt]);
                             const float c = r32_cell(cnt, n, r0.x, r0.y, ca[tt], cs[tt]).r;
                             const uint32_t j = j0 + 32u * tt;
                             const uint64_t idx = off_i + (uint64_t)(j - lo_i);   // (wraps for j < lo_i: excluded below)
                             if (j < i && j >= lo_i && idx < n_cells) __builtin_nontemporal_store(c, values + idx);
                         }
-                    }
-                }
+                LDX_BAND_SWEEP_END
               }
             };
             if constexpr (kScore || kProd) {
@@ -2273,8 +2193,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                     const size_t word = kCross ? (size_t)j * 2u + 1u : (size_t)j * st + f % st;   // cross: sides[j][1], the right half
                     if (v != 0u && j < n_snps) atomicAdd(reinterpret_cast<unsigned long long *>(sums) + word, (unsigned long long)v);
                 }
-                if (tid == 0) tickets[parity] = next_ticket;
-                if (!(ablate & 16)) __builtin_amdgcn_s_setprio(0);
+                finish_pass(std::false_type{});   // (these two bands never stamped their passes)
                 return;
             }
             if constexpr (kArea) {
@@ -2283,17 +2202,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 else if constexpr (kFgt) fgt_epilogue();
                 else if constexpr (kStore) store_epilogue();
                 else area_epilogue();
-                if (tid == 0) tickets[parity] = next_ticket;
-                if (!(ablate & 16)) __builtin_amdgcn_s_setprio(0);
-#ifdef LDX_TUNING
-                LDX_STAMP(3);
-                ++npass;
-                if (my_stamps && lane == 0) {
-                    my_stamps[3] = npass;
-                    my_stamps[4] = __builtin_amdgcn_s_memrealtime();
-                    my_stamps[5] = __builtin_amdgcn_s_memtime();
-                }
-#endif
+                finish_pass(std::true_type{});
                 return;
             }
             // `inside`: the unit lies wholly below the diagonal, inside the panel and inside [u_begin, u_end) (no validity
@@ -2323,17 +2232,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
                 if (clean && !(ablate & 512)) epilogue(std::true_type{});
                 else epilogue(std::false_type{});
             }
-            if (tid == 0) tickets[parity] = next_ticket;
-            if (!(ablate & 16)) __builtin_amdgcn_s_setprio(0);
-#ifdef LDX_TUNING
-            LDX_STAMP(3);
-            ++npass;
-            if (my_stamps && lane == 0) {
-                my_stamps[3] = npass;
-                my_stamps[4] = __builtin_amdgcn_s_memrealtime();
-                my_stamps[5] = __builtin_amdgcn_s_memtime();
-            }
-#endif
+            finish_pass(std::true_type{});
         };
         if constexpr (kArea) {
             pass_body(std::integral_constant<int, 2>{});
@@ -2362,6 +2261,12 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
             if (sl < aa.hit_cap) aa.hits[sl].query = 0xFFFFFFFFu;
 }
 
+#undef LDX_HIT_APPENDER
+#undef LDX_BAND_LANE
+#undef LDX_BAND_COLS
+#undef LDX_BAND_SWEEP_BEGIN
+#undef LDX_BAND_SWEEP_END
+
 // kDosage: `fa` is the dosage table gstat, `fr` / `q` are unused, and the kernel's n is the number of individuals
 template <bool kRaw, bool kN11, bool kFp4, typename Cell, bool kDosage = false>
 static int launch_mfma(const void *alt, const double *fa, const double *fr, const double *q, uint32_t n_snps,
@@ -2379,7 +2284,7 @@ static int launch_mfma(const void *alt, const double *fa, const double *fr, cons
         int dev = 0;
         LDX_HIP(hipGetDevice(&dev));
         if (dev < 0 || dev >= 64 || !((opted.load(std::memory_order_relaxed) >> dev) & 1u)) {
-            LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<kRaw, kN11, false, kFp4, Cell, 0, false, 0, false, false, false, kDosage>,
+            LDX_HIP(hipFuncSetAttribute((const void *)triangle_mfma_kernel<kRaw, kN11, BandOp::None, kFp4, Cell, 0, kDosage>,
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             if (dev >= 0 && dev < 64) opted.fetch_or(1ull << dev, std::memory_order_relaxed);
         }
@@ -2430,7 +2335,7 @@ static int launch_mfma(const void *alt, const double *fa, const double *fr, cons
     }
 #endif
     const double n_obs = kDosage ? (double)(n_hap / 2u) : (double)n_hap;
-    triangle_mfma_kernel<kRaw, kN11, false, kFp4, Cell, 0, false, 0, false, false, false, kDosage><<<(uint32_t)grid, kMfmaThreads, lds, s>>>(
+    triangle_mfma_kernel<kRaw, kN11, BandOp::None, kFp4, Cell, 0, kDosage><<<(uint32_t)grid, kMfmaThreads, lds, s>>>(
         (const uint4 *)alt, fa, fr, q, n_snps, n_slabs(n_snps), nch, n_obs, 1.0 / n_obs, unit_begin,
         unit_end, out, out_raw, out_n11, p_begin, p_end, n_short, sched, ablate, stamps, tri_args);
     LDX_HIP(hipGetLastError());
@@ -2696,7 +2601,7 @@ static int band_plan(const BandWs &w, uint32_t n_snps, const int64_t *positions,
 }
 
 // the AreaArgs members that mean the same to every operator; is_query, hits, counts, hit_cap, k_thres and measure are each
-// operator's own
+// operator's own: the table at AreaArgs says what they hold
 static AreaArgs band_args(const BandWs &w, uint32_t n_hap, const int64_t *positions, int64_t flank, unsigned long long *n_hits)
 {
     AreaArgs aa{};
@@ -2734,7 +2639,7 @@ static int band_launch(const void *alt, const double *fa, const double *fr, cons
 }
 
 template <bool kFp4>
-constexpr auto kAreaBand = triangle_mfma_kernel<false, false, true, kFp4>;
+constexpr auto kAreaBand = triangle_mfma_kernel<false, false, BandOp::Hits, kFp4>;
 
 int area_mfma(const void *alt, const double *fa, const double *fr, const double *q, uint32_t n_snps, uint32_t n_hap,
               const int64_t *positions, const uint32_t *queries, uint32_t n_query, int64_t flank, int measure, double thres,
@@ -2832,7 +2737,7 @@ size_t score_mfma_workspace_bytes(uint32_t n_snps)
 }
 
 template <bool kFp4, int kW, bool kCross = false, bool kDosage = false>
-constexpr auto kScoreBand = triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, kW, false, 0, false, false, kCross, kDosage>;
+constexpr auto kScoreBand = triangle_mfma_kernel<false, false, kCross ? BandOp::Cross : BandOp::Score, kFp4, ldx_ld32, kW, kDosage>;
 
 // the dosage band's own terms: r_ii = +1.0f (term 2^32) for v_i > 0, -0.0f (term 0) otherwise -- gstat[i][1] = 1 / sqrt(v_i) or 0
 __global__ void score_init_dosage_kernel(const double *__restrict__ gstat, const uint8_t *__restrict__ annot, uint32_t st,
@@ -2867,9 +2772,9 @@ int score_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, cons
     if (n_snps < 2) return LDX_OK;   // no pairs
     if (const int rc = band_plan(w, n_snps, positions, window, w.n_hits, s)) return rc;   // (nothing reads the hit counter)
     AreaArgs aa = band_args(w, n_hap, positions, window, w.n_hits);
-    aa.is_query = n_annot ? annot : nullptr;   // score: the annotation masks (null: none)
-    aa.hits = (ldx_hit *)sums;                 // score: the uint64 sums [n_snps][1 + n_annot]
-    aa.measure = (int)n_annot;                 // score: K
+    aa.is_query = n_annot ? annot : nullptr;   // (AreaArgs' table, rows Score and Cross)
+    aa.hits = (ldx_hit *)sums;
+    aa.measure = (int)n_annot;
     const size_t lds = mfma_lds_bytes(kRows64, false, false) + (size_t)kMfmaWaves * kRows64 * 9u * sizeof(uint64_t);   // + the row tables
     const double n_obs = gstat ? (double)(n_hap / 2u) : (double)n_hap;   // dosage: gstat in `fa`'s place, n the individuals
 #define LDX_GO(...)                                                                                                  \
@@ -2907,7 +2812,7 @@ __global__ void decay_init_kernel(const uint32_t *__restrict__ acnt, const uint3
 size_t decay_mfma_workspace_bytes(uint32_t n_snps) { return score_mfma_workspace_bytes(n_snps); }
 
 template <bool kFp4>
-constexpr auto kDecayBand = triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, false, 0, true>;
+constexpr auto kDecayBand = triangle_mfma_kernel<false, false, BandOp::Decay, kFp4>;
 
 int decay_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
                uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, int64_t bin_width,
@@ -2922,10 +2827,10 @@ int decay_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, cons
     if (n_snps < 2) return LDX_OK;   // no pairs
     if (const int rc = band_plan(w, n_snps, positions, window, w.n_hits, s)) return rc;   // (nothing reads the hit counter)
     AreaArgs aa = band_args(w, n_hap, positions, window, w.n_hits);
-    aa.is_query = w.mask;                      // decay: the effective keep mask
-    aa.hits = (ldx_hit *)sums;                 // decay: the uint64 sums [n_bins]
-    aa.counts = (uint32_t *)counts;            // decay: the uint64 counts [n_bins]
-    aa.k_thres = (double)bin_width;            // decay: the bin width (<= 2^52 + 1: exact)
+    aa.is_query = w.mask;                      // (AreaArgs' table, row Decay)
+    aa.hits = (ldx_hit *)sums;
+    aa.counts = (uint32_t *)counts;
+    aa.k_thres = (double)bin_width;            // (<= 2^52 + 1: exact)
     aa.measure = (int)n_bins;
     const size_t lds = mfma_lds_bytes(kRows64, false, false) + (size_t)n_bins * 2u * sizeof(uint64_t);   // + the histogram
     return fp4 ? band_launch<kDecayBand<true>>(alt, fa, fr, nullptr, n_snps, n_hap, (double)n_hap, lds, nullptr, aa, w.sched, s)
@@ -2953,7 +2858,7 @@ __global__ void fgt_init_kernel(const uint8_t *__restrict__ keep, uint32_t n_snp
 size_t fgt_mfma_workspace_bytes(uint32_t n_snps) { return score_mfma_workspace_bytes(n_snps); }
 
 template <bool kFp4>
-constexpr auto kFgtBand = triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, false, 0, false, true>;
+constexpr auto kFgtBand = triangle_mfma_kernel<false, false, BandOp::Fgt, kFp4>;
 
 int fgt_mfma(const void *alt, const uint32_t *acnt, uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window,
              uint32_t min_count, const uint8_t *keep, bool fp4, uint32_t *left, void *workspace, hipStream_t s)
@@ -2966,10 +2871,10 @@ int fgt_mfma(const void *alt, const uint32_t *acnt, uint32_t n_snps, uint32_t n_
     if (n_snps < 2) return LDX_OK;   // no pairs
     if (const int rc = band_plan(w, n_snps, positions, window, w.n_hits, s)) return rc;   // (nothing reads the hit counter)
     AreaArgs aa = band_args(w, n_hap, positions, window, w.n_hits);
-    aa.is_query = w.mask;                      // fgt: the keep mask
-    aa.hits = (ldx_hit *)left;                 // fgt: the uint32 words left[n_snps]
-    aa.counts = const_cast<uint32_t *>(acnt);  // fgt: the ALT counts (read only)
-    aa.measure = (int)min_count;               // fgt: the smallest gamete count of a recombinant pair (<= n_hap)
+    aa.is_query = w.mask;                      // (AreaArgs' table, row Fgt)
+    aa.hits = (ldx_hit *)left;
+    aa.counts = const_cast<uint32_t *>(acnt);  // (read only)
+    aa.measure = (int)min_count;               // (<= n_hap)
     const size_t lds = mfma_lds_bytes(kRows64, false, false);
     // (fa / fr / q stay null: the four-gamete instantiation stages the ALT counts from aa.counts and reads no frequency)
     return fp4 ? band_launch<kFgtBand<true>>(alt, nullptr, nullptr, nullptr, n_snps, n_hap, (double)n_hap, lds, nullptr, aa, w.sched, s)
@@ -3004,7 +2909,7 @@ constexpr int kProdSweep = 2;   // right-hand sides per sweep of the accumulator
 static_assert(8 % kProdSweep == 0, "a sweep's row-weight reads stay inside the row's eight");
 
 template <bool kFp4>
-constexpr auto kProdBand = triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, false, kProdSweep>;
+constexpr auto kProdBand = triangle_mfma_kernel<false, false, BandOp::Prod, kFp4, ldx_ld32, kProdSweep>;
 
 int prod_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const double *fa, const double *fr,
               uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, const float *x, uint32_t n_rhs,
@@ -3018,9 +2923,9 @@ int prod_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const
     if (n_snps < 2) return LDX_OK;   // no pairs
     if (const int rc = band_plan(w, n_snps, positions, window, w.n_hits, s)) return rc;   // (nothing reads the hit counter)
     AreaArgs aa = band_args(w, n_hap, positions, window, w.n_hits);
-    aa.hits = (ldx_hit *)sums;                                         // products: the int64 sums [n_snps][n_rhs]
-    aa.counts = reinterpret_cast<uint32_t *>(const_cast<float *>(x));   // products: the float32 weights [n_snps][n_rhs] (read only)
-    aa.measure = (int)(n_rhs | (square ? 16u : 0u));                   // products: n_rhs, bit 4 = power 2
+    aa.hits = (ldx_hit *)sums;                                         // (AreaArgs' table, row Prod)
+    aa.counts = reinterpret_cast<uint32_t *>(const_cast<float *>(x));   // (read only)
+    aa.measure = (int)(n_rhs | (square ? 16u : 0u));
     // + the row-sum tables [4][64][8] uint64 and the row-weight tables [4][64][8] float32
     const size_t lds = mfma_lds_bytes(kRows64, false, false) + (size_t)kMfmaWaves * kRows64 * 8u * (sizeof(uint64_t) + sizeof(float));
     static_assert(2u * (mfma_lds_bytes(kRows64, false, false) + (size_t)kMfmaWaves * kRows64 * 8u * 12u) <= 160u * 1024u,
@@ -3043,7 +2948,7 @@ __global__ void nbr_init_kernel(uint32_t n_snps, uint32_t *__restrict__ qrows)
 size_t nbr_mfma_workspace_bytes(uint32_t n_snps) { return score_mfma_workspace_bytes(n_snps); }
 
 template <bool kFp4, bool kDosage = false>
-constexpr auto kNbrBand = triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, true, 0, false, false, false, kDosage>;
+constexpr auto kNbrBand = triangle_mfma_kernel<false, false, BandOp::Nbr, kFp4, ldx_ld32, 0, kDosage>;
 
 int nbr_mfma(const void *alt, const double *fa, const double *fr, uint32_t n_snps, uint32_t n_hap, const int64_t *positions,
              int64_t window, float r2_bound, bool fp4, ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits, uint32_t *row_counts,
@@ -3064,7 +2969,7 @@ int nbr_mfma(const void *alt, const double *fa, const double *fr, uint32_t n_snp
     aa.hits = hits;
     aa.counts = row_counts;
     aa.hit_cap = hit_cap;
-    aa.k_thres = (double)r2_bound;   // neighbours: the float32 bound b on s = r *f32 r
+    aa.k_thres = (double)r2_bound;   // (AreaArgs' table, row Nbr)
     const size_t lds = mfma_lds_bytes(kRows64, false, false);
     if (gstat)   // (ldx_ld_neighbors_dosage_dev) `fa` is gstat, n the individuals
         return band_launch<kNbrBand<true, true>>(alt, gstat, nullptr, nullptr, n_snps, n_hap, (double)(n_hap / 2u), lds, nullptr, aa, w.sched, s);
@@ -3077,7 +2982,7 @@ int nbr_mfma(const void *alt, const double *fa, const double *fr, uint32_t n_snp
 size_t store_mfma_workspace_bytes(uint32_t n_snps) { return score_mfma_workspace_bytes(n_snps); }
 
 template <bool kFp4, bool kDosage = false>
-constexpr auto kStoreBand = triangle_mfma_kernel<false, false, true, kFp4, ldx_ld32, 0, false, 0, false, false, false, kDosage, true>;
+constexpr auto kStoreBand = triangle_mfma_kernel<false, false, BandOp::Store, kFp4, ldx_ld32, 0, kDosage>;
 
 // `gstat` (ldx_ld_band_dosage_dev; FP4): the dosage table in place of fa / fr, n the individuals
 int store_mfma(const void *alt, const double *fa, const double *fr, uint32_t n_snps, uint32_t n_hap, const int64_t *positions,
@@ -3091,12 +2996,12 @@ int store_mfma(const void *alt, const double *fa, const double *fr, uint32_t n_s
     nbr_init_kernel<<<1, 64, 0, s>>>(n_snps, w.qrows);
     LDX_HIP(hipGetLastError());
     if (const int rc = band_plan(w, n_snps, positions, window, w.n_hits, s)) return rc;   // (nothing reads the hit counter)
-    // values, lo, offsets and n_cells travel in members this epilogue does not otherwise use: AreaArgs keeps its size
+    // values, lo, offsets and n_cells travel in members this epilogue does not otherwise use (AreaArgs' table, row Store)
     AreaArgs aa = band_args(w, n_hap, positions, window, w.n_hits);
-    aa.hits = (ldx_hit *)values;                               // store: the float32 cells [n_cells]
-    aa.counts = const_cast<uint32_t *>(lo);                    // store: lo [n_snps] (read only)
-    aa.is_query = reinterpret_cast<const uint8_t *>(offsets);  // store: offsets [n_snps + 1] uint64 (read only)
-    aa.hit_cap = n_cells;                                      // store: no index at or beyond it is written
+    aa.hits = (ldx_hit *)values;
+    aa.counts = const_cast<uint32_t *>(lo);                    // (read only)
+    aa.is_query = reinterpret_cast<const uint8_t *>(offsets);  // (read only)
+    aa.hit_cap = n_cells;                                      // no index at or beyond it is written
     const size_t lds = mfma_lds_bytes(kRows64, false, false) + (size_t)kMfmaWaves * kRows64 * 12u;   // + the waves' row tables
     if (gstat)
         return band_launch<kStoreBand<true, true>>(alt, gstat, nullptr, nullptr, n_snps, n_hap, (double)(n_hap / 2u), lds, nullptr, aa, w.sched, s);

@@ -5,7 +5,7 @@
 
   * one K-block of the 64-row unit's K loop (32 FP4 MFMAs), by instruction class;
   * one step of the fp32 epilogue tier (8 pairs), by instruction class, with the vector instructions by opcode.
-Kernel: triangle_mfma_kernel<false, false, false, true, ldx_k16> (no side outputs, FP4, 4-byte cells).  The K-block is taken
+Kernel: triangle_mfma_kernel<false, false, BandOp::None, true, ldx_k16> (no side outputs, the triangle, FP4, 4-byte cells).  The K-block is taken
 between the 33rd and the 65th MFMA of the kernel's larger MFMA cluster (the second block of the 64-row loop), the step between
 two consecutive pairs of 16-byte non-temporal stores of the n > 4096 instantiation of the step loop (the window includes
 the not-taken park path)."""
@@ -32,7 +32,7 @@ for obj in sorted(os.listdir(d)):
         m = re.match(r"^[0-9a-f]+ <(.*)>:$", ln)
         if m:
             func = m.group(1)
-        elif ln.startswith("\t") and func and "triangle_mfma_kernelILb0ELb0ELb0ELb1E7ldx_k16" in func:
+        elif ln.startswith("\t") and func and "triangle_mfma_kernelILb0ELb0ELNS_6BandOpE0ELb1E7ldx_k16" in func:
             ins.append(ln.split("//")[0].strip())
 if not ins:
     sys.exit("kernel not found in " + lib)
