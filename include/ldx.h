@@ -679,6 +679,49 @@ int ldx_band_score_dev(const float *values1, const float *values2, const float *
 int ldx_band_matvec_dev(const float *values, const float *diag, const uint32_t *lo, const uint64_t *offsets, uint32_t n_snps,
                         const float *x, uint32_t n_rhs, int power, int64_t *sums, void *stream);
 
+/* ---- rectangular LD: the rows of one SNP set against the rows of another, over the same haplotypes -------------------------
+ * Every entry above that produces r pairs one panel with itself (the triangle, or a window of it).  These pair the n_i rows of
+ * panel I with the n_j rows of panel J -- two tiled bit planes (ldx_plane_bytes) over the SAME n_hap haplotypes, for instance
+ * two sub-panels of ldx_panel_select_dev: lead SNPs x a chromosome, an rsID list x itself in the caller's order, chromosome A
+ * x chromosome B.  alt_i == alt_j is allowed (a panel against itself: the full square).  A kernel of its own on the FP4 matrix
+ * cores (ldx_rect.hip); no workspace, no library state.
+ *
+ * The cell of (row i of I, row j of J) is the signed r cell of ldx_triangle_ex_dev(LDX_OUT_R32) for those two SNPs, bit for
+ * bit: r32 arithmetic on the exact count, -0.0f on a degenerate pair, +0.0f iff num == 0, within 4 float32 ulps of the exact r
+ * otherwise.  The rectangle knows nothing about the identity of SNPs: where row i of I and row j of J are the same variant
+ * the cell is still that pair formula (n n11 - a a) / (a r) in the r32 arithmetic -- within 4 ulps of the exact diagonal
+ * (n - a) / r, -0.0f for a degenerate SNP -- and NOT the one-division diagonal of ldx_triangle_r_block_dev.
+ *   acnt / rcnt: uint32 [n] per side, from ldx_pack_codes_dev / ldx_panel_select_dev (only the first n words are read);
+ *   dosage forms: gstat per side from ldx_dosage_stats_dev, the cell is ldx_triangle_dosage_dev's (n = n_hap / 2 individuals).
+ *
+ * ldx_ld_rect_dev / ldx_ld_rect_dosage_dev: out[i * ld_out + j] = the cell, float32, for i < n_i and j < n_j.  Every one of
+ * these n_i x n_j words is written (no memset) and nothing else: the columns [n_j, ld_out) of a wider row keep their bytes.
+ *
+ * ldx_ld_rect_hits_dev / ldx_ld_rect_hits_dosage_dev: every pair with s = c *f32 c >= r2_bound (ONE IEEE float32 multiply;
+ * r2_bound a float32 > 0, so a degenerate pair and a cell with num == 0 are never kept: ldx_ld_neighbors_dev's rule) is stored
+ * as the record {query = i, oppos = j, r_square = c, d_prime = s} -- once per (i, j): the orientation is the rectangle's.
+ * hits: capacity hit_cap, written in arbitrary order; *n_hits (device uint64, zeroed by the call) receives the number of slots
+ * RESERVED (batches of 256 per wave; unused slots carry query == UINT32_MAX), as for ldx_area_scan_dev: if it exceeds hit_cap
+ * only the first hit_cap slots were stored -- retry with a larger buffer.  ldx_area_finish_ex_dev(n_snps = n_i, counts_ready
+ * = 0) turns the slots into a CSR over the rows of I: records sorted by (i, j), row i's at [offsets[i], offsets[i + 1]).
+ *
+ * Argument rules, checked before any HIP call (ldx_last_error() names the argument): a null pointer, n_i or n_j = 0, ld_out <
+ * n_j, r2_bound not > 0, an odd n_hap in the dosage forms = LDX_E_ARG; n_hap > LDX_MAX_HAPS, or a bit plane of 4 GiB or more
+ * on either side = LDX_E_UNSUPPORTED.  All calls only enqueue work on `stream`. */
+int ldx_ld_rect_dev(const void *alt_i, const uint32_t *acnt_i, const uint32_t *rcnt_i, uint32_t n_i,
+                    const void *alt_j, const uint32_t *acnt_j, const uint32_t *rcnt_j, uint32_t n_j,
+                    uint32_t n_hap, float *out, size_t ld_out, void *stream);
+int ldx_ld_rect_dosage_dev(const void *alt_i, const double *gstat_i, uint32_t n_i,
+                           const void *alt_j, const double *gstat_j, uint32_t n_j,
+                           uint32_t n_hap, float *out, size_t ld_out, void *stream);
+int ldx_ld_rect_hits_dev(const void *alt_i, const uint32_t *acnt_i, const uint32_t *rcnt_i, uint32_t n_i,
+                         const void *alt_j, const uint32_t *acnt_j, const uint32_t *rcnt_j, uint32_t n_j,
+                         uint32_t n_hap, float r2_bound, ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits, void *stream);
+int ldx_ld_rect_hits_dosage_dev(const void *alt_i, const double *gstat_i, uint32_t n_i,
+                                const void *alt_j, const double *gstat_j, uint32_t n_j,
+                                uint32_t n_hap, float r2_bound, ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits,
+                                void *stream);
+
 /* ---- synthetic panels: deterministic, identical on host and device ------ */
 /* codes int8 [n_snps][ld_codes] receive global SNPs [snp_offset, snp_offset + n_snps) (a rank's
  * shard).  thresholds: per-SNP ALT probability * 2^64 (computed on the host, see

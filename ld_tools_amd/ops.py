@@ -10,6 +10,8 @@
     ld_cross / ld_regions                   the cross-LD profile of the band and the LD-independent regions cut from it
     ld_neighbors(panel, positions, ...)     per-SNP lists of the SNPs in the window with r^2 above a threshold
     ld_clump / ld_prune                     greedy clumping (PLINK --clump) and priority pruning on those lists
+    ld_rect(panel_i, panel_j)               signed r of every SNP of one set against every SNP of another (dense float32)
+    ld_rect_hits(panel_i, panel_j, r2=...)  the pairs of that rectangle with r^2 above a threshold, as a CSR
     pair_counts(panel_i, panel_j)           <- calc_ld.py:32           (bit-exact n11 block)
     ld_from_counts(n, n11, a1, r1, a2, r2)  <- calc_ld.py:33-97        (the epilogue alone)
 
@@ -2228,6 +2230,154 @@ def ld_prune(panel: PackedPanel, positions=None, r2: float = 0.2, window_bp: Opt
                       strict=True, path=path, hit_capacity=hit_capacity, dosage=dosage)
     state, _, rounds = select_dev(nb, rank, live.astype(np.uint8))
     return Pruned(state == SEL_INDEX, rank, nb, rounds)
+
+
+# --------------------------------------------------------------------------- rectangular LD (two SNP sets)
+def _rect_panels(what: str, panel_i: PackedPanel, panel_j: Optional[PackedPanel], dosage: bool) -> PackedPanel:
+    """The rectangle's argument rules, checked before anything touches the device; returns panel J."""
+    pj = panel_i if panel_j is None else panel_j
+    if not isinstance(panel_i, PackedPanel) or not isinstance(pj, PackedPanel):
+        raise _lib.LdxError(f"{what}: panel_i and panel_j must be PackedPanels")
+    if pj.n_hap != panel_i.n_hap:
+        raise _lib.LdxError(f"{what}: the panels differ in haplotype count (n_hap {panel_i.n_hap} and {pj.n_hap}): "
+                            "the rectangle pairs SNPs over the SAME haplotypes")
+    if pj.device != panel_i.device:
+        raise _lib.LdxError(f"{what}: the panels are on different devices ({panel_i.device} and {pj.device})")
+    if dosage and panel_i.n_hap % 2:
+        raise _lib.LdxError(f"{what}: dosage=True needs an even n_hap (got {panel_i.n_hap}): individual k owns haplotypes "
+                            "2k and 2k + 1")
+    return pj
+
+
+def ld_rect(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, dosage: bool = False,
+            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Signed r of every SNP of ``panel_i`` against every SNP of ``panel_j`` (None: ``panel_i`` itself, the full square) over
+    the same haplotypes: float32 [n_i, n_j] on the device (include/ldx.h, ldx_ld_rect_dev).  Cell (i, j) is the r32 cell of
+    ld_triangle(fmt="r32") for those two SNPs bit for bit -- -0.0f on a degenerate pair, +0.0f iff the covariance is 0 --
+    also where the two rows are the same variant (the pair formula, not the triangle's one-division diagonal).  The two
+    panels are typically ``PackedPanel.select(snps=...)`` sub-panels of one panel, or two chromosomes of one sample set.
+
+    ``dosage=True``: the genotype-dosage r of ld_triangle(fmt="r32", dosage=True) (even n_hap).  ``out``: a float32 device
+    tensor [n_i, >= n_j] with unit column stride to write into; its row stride is taken as it is and the columns beyond n_j
+    are left untouched.  The view out[:, :n_j] is returned."""
+    pj = _rect_panels("ld_rect", panel_i, panel_j, dosage)
+    n_i, n_j = panel_i.n_snps, pj.n_snps
+    if out is not None:
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != n_i
+                or out.shape[1] < n_j or (out.shape[1] > 1 and out.stride(1) != 1) or out.device != panel_i.device):
+            raise _lib.LdxError(f"ld_rect: out must be a float32 [{n_i}, >= {n_j}] tensor with unit column stride on "
+                                f"{panel_i.device}")
+        ld_out = out.stride(0) if n_i > 1 else max(out.stride(0), out.shape[1])
+        if ld_out < n_j:
+            raise _lib.LdxError(f"ld_rect: out has row stride {ld_out} < n_j = {n_j}")
+    require_gpu()
+    if out is None:
+        out = torch.empty((n_i, n_j), dtype=torch.float32, device=panel_i.device)
+        ld_out = n_j
+    if dosage:
+        check(lib.ldx_ld_rect_dosage_dev(panel_i.alt.data_ptr(), panel_i.dosage_stats()[1].data_ptr(), n_i,
+                                         pj.alt.data_ptr(), pj.dosage_stats()[1].data_ptr(), n_j, panel_i.n_hap,
+                                         out.data_ptr(), ld_out, _stream_ptr()), "ldx_ld_rect_dosage_dev")
+    else:
+        check(lib.ldx_ld_rect_dev(panel_i.alt.data_ptr(), panel_i.acnt.data_ptr(), panel_i.rcnt.data_ptr(), n_i,
+                                  pj.alt.data_ptr(), pj.acnt.data_ptr(), pj.rcnt.data_ptr(), n_j, panel_i.n_hap,
+                                  out.data_ptr(), ld_out, _stream_ptr()), "ldx_ld_rect_dev")
+    return out[:, :n_j]
+
+
+def rect_hits_host(r, bound) -> Tuple[np.ndarray, np.ndarray]:
+    """Host mirror of ldx_ld_rect_hits_dev's rule on a float32 matrix ``r`` of r32 cells: the (i, j), as two int64 arrays in
+    (i, j) order, with ``np.multiply(r, r, dtype=np.float32) >= bound`` and r not -0.0f (a degenerate pair is never a hit,
+    whatever the bound)."""
+    r = np.asarray(r)
+    if r.dtype != np.float32 or r.ndim != 2:
+        raise _lib.LdxError(f"rect_hits_host: r must be a float32 matrix, got {r.dtype} with shape {r.shape}")
+    with np.errstate(over="ignore", invalid="ignore"):
+        s = np.multiply(r, r, dtype=np.float32)
+        keep = (s >= np.float32(bound)) & (r.view(np.uint32) != np.uint32(0x80000000))
+    i, j = np.nonzero(keep)   # row-major: sorted by (i, j)
+    return i.astype(np.int64), j.astype(np.int64)
+
+
+@dataclass
+class LDRectHits:
+    """The pairs of a rectangle above an r^2 threshold (ld_rect_hits) as a CSR over the rows of panel I, on the device.
+    ``hits`` holds the ldx_hit records (int32 [m, 4]: i, j, r bits, s bits with s = r *f32 r) sorted by (i, j); row i's are
+    [offsets[i], offsets[i + 1])."""
+
+    offsets: torch.Tensor   # int32 [n_i + 1]
+    hits: torch.Tensor      # int32 [m, 4]
+    n_i: int
+    n_j: int
+    bound: np.float32       # the float32 bound on s (r2_bound)
+    dosage: bool = False
+
+    @property
+    def j(self) -> torch.Tensor:
+        """int32 [m]: the panel-J rows (a view of ``hits``)."""
+        return self.hits[:, 1]
+
+    @property
+    def r(self) -> torch.Tensor:
+        """float32 [m]: the signed r of each pair -- the ld_rect cell, bit for bit (a view of ``hits``)."""
+        return self.hits[:, 2].view(torch.float32)
+
+    def __len__(self) -> int:
+        return int(self.hits.shape[0])
+
+    def pairs(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(i int64, j int64, r float32) on the host, sorted by (i, j)."""
+        h = self.hits.cpu().numpy()
+        return h[:, 0].astype(np.int64), h[:, 1].astype(np.int64), np.ascontiguousarray(h[:, 2]).view(np.float32)
+
+
+def ld_rect_hits(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, r2: float = 0.2, strict: bool = False,
+                 dosage: bool = False, hit_capacity: Optional[int] = None) -> LDRectHits:
+    """The pairs (row i of ``panel_i``, row j of ``panel_j``) with r^2 >= ``r2`` (``strict``: r^2 > r2), where r is the
+    ld_rect cell bit for bit and r^2 one float32 multiply -- ld_neighbors' rule without a window, once per (i, j)
+    (include/ldx.h, ldx_ld_rect_hits_dev + ldx_area_finish_ex_dev).  Degenerate pairs are never hits.
+
+    ``hit_capacity``: record slots to start with (16 bytes each; default max(2^20, 32 (n_i + n_j))); a call that needs more
+    runs again at the count the first run reserved plus ld_neighbors' margin, at most four times.  The host reads the
+    record count once per run."""
+    pj = _rect_panels("ld_rect_hits", panel_i, panel_j, dosage)
+    bound = r2_bound(r2, strict)
+    require_gpu()
+    n_i, n_j = panel_i.n_snps, pj.n_snps
+    dev = panel_i.device
+    fin_bytes = lib.ldx_area_finish_workspace_bytes(n_i)
+    fin = torch.empty(fin_bytes, dtype=torch.uint8, device=dev)
+    cap = int(hit_capacity) if hit_capacity is not None else max(1 << 20, 32 * (n_i + n_j))
+    n_hits = torch.zeros(1, dtype=torch.int64, device=dev)
+    summary = torch.zeros(2, dtype=torch.int64, device=dev)
+    offsets = torch.empty(n_i + 1, dtype=torch.int32, device=dev)
+    for attempt in range(4):
+        if not 0 <= cap < (1 << 32):
+            raise _lib.LdxError(f"ld_rect_hits: {cap} record slots needed; the CSR's offsets are uint32 (at most 2^32 - 1)")
+        raw = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+        hits = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+        if dosage:
+            check(lib.ldx_ld_rect_hits_dosage_dev(panel_i.alt.data_ptr(), panel_i.dosage_stats()[1].data_ptr(), n_i,
+                                                  pj.alt.data_ptr(), pj.dosage_stats()[1].data_ptr(), n_j, panel_i.n_hap,
+                                                  float(bound), raw.data_ptr(), cap, n_hits.data_ptr(), _stream_ptr()),
+                  "ldx_ld_rect_hits_dosage_dev")
+        else:
+            check(lib.ldx_ld_rect_hits_dev(panel_i.alt.data_ptr(), panel_i.acnt.data_ptr(), panel_i.rcnt.data_ptr(), n_i,
+                                           pj.alt.data_ptr(), pj.acnt.data_ptr(), pj.rcnt.data_ptr(), n_j, panel_i.n_hap,
+                                           float(bound), raw.data_ptr(), cap, n_hits.data_ptr(), _stream_ptr()),
+                  "ldx_ld_rect_hits_dev")
+        # the finishing step counts the stored records per row itself (counts_ready = 0): rows are panel I's
+        check(lib.ldx_area_finish_ex_dev(raw.data_ptr(), n_hits.data_ptr(), cap, n_i, hits.data_ptr(), offsets.data_ptr(),
+                                         summary.data_ptr(), fin.data_ptr(), fin_bytes, 0, _stream_ptr()),
+              "ldx_area_finish_ex_dev")
+        total, reserved = (int(x) for x in summary.tolist())
+        if reserved <= cap:
+            break
+        cap = reserved + reserved // 64 + (1 << 16)   # ld_neighbors' margin: the batches' tails differ with the work order
+    else:
+        raise _lib.LdxError("ld_rect_hits: the record count did not settle")
+    del raw
+    return LDRectHits(offsets, hits[:total], n_i, n_j, bound, bool(dosage))
 
 
 # --------------------------------------------------------------------------- instrumentation
