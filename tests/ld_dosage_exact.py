@@ -88,6 +88,35 @@ class DosageExact(lx.Exact):
         return self.live.astype(np.float64)
 
 
+class DosageExactBlock(lx.ExactBlock):
+    """ExactBlock's dosage counterpart: the rows of one code matrix against the rows of another over the same individuals
+    (n_hap even) -- the off-diagonal block of DosageExact(stacked), each attribute [n_i, n_j]."""
+
+    def __init__(self, codes_i, codes_j):   # (not ExactBlock.__init__: other counts, the same attribute names)
+        codes_i, codes_j = np.asarray(codes_i), np.asarray(codes_j)
+        assert codes_i.ndim == codes_j.ndim == 2 and codes_i.dtype == codes_j.dtype == np.int8
+        assert codes_i.shape[1] == codes_j.shape[1]
+        self.n_i, self.n_j, self.n_hap = codes_i.shape[0], codes_j.shape[0], codes_i.shape[1]
+        assert 2 <= self.n_hap <= MAX_HAPS and self.n_hap % 2 == 0
+        self.n_ind = self.n_hap // 2
+        N = np.int64(self.n_ind)
+        g_i, g_j = dosages(codes_i), dosages(codes_j)
+        self.a_i, self.a_j = g_i.sum(axis=1), g_j.sum(axis=1)
+        self.v_i = N * (g_i * g_i).sum(axis=1) - self.a_i * self.a_i
+        self.v_j = N * (g_j * g_j).sum(axis=1) - self.a_j * self.a_j
+        for v in (self.v_i, self.v_j):
+            assert int(v.min(initial=0)) >= 0 and int(v.max(initial=0)) <= int(N) ** 2 < (1 << 25)
+        assert 4 * self.n_ind < (1 << 24)
+        G, H = g_i.astype(np.float32), g_j.astype(np.float32)
+        self.S = np.empty((self.n_i, self.n_j), dtype=np.int64)
+        for r0 in range(0, self.n_i, 512):
+            blk = G[r0:r0 + 512] @ H.T
+            self.S[r0:r0 + 512] = blk.astype(np.int64)
+            assert np.array_equal(self.S[r0:r0 + 512].astype(np.float32), blk)   # integers, nothing lost
+        assert int(self.S.max(initial=0)) <= 4 * self.n_ind
+        self._finish(N * self.S - np.multiply.outer(self.a_i, self.a_j), np.multiply.outer(self.v_i, self.v_j))
+
+
 # ---- the panels of tests/test_gpu_ld_dosage.py, pinned on the CPU by tests/test_ld_dosage_host.py -----------------------
 # n_snps x n_hap: everything degenerate; the tiny case (n_hap % 4 == 2: the last individual sits in the upper half of the
 # last nibble group); the chunk tail; the K-block boundary (256 haplotypes) from both sides; three tiles (diagonal,

@@ -115,6 +115,53 @@ class Exact:
         return self._classes[t]
 
 
+def alt_counts_block(codes_i, codes_j, block: int = 512) -> np.ndarray:
+    """n11 int64 [n_i, n_j] from a blocked float32 GEMM of the two ALT planes (exact, as in alt_counts_gemm)."""
+    codes_i, codes_j = np.asarray(codes_i), np.asarray(codes_j)
+    assert codes_i.shape[1] == codes_j.shape[1] < (1 << 24)
+    A, B = (codes_i == 1).astype(np.float32), (codes_j == 1).astype(np.float32)
+    out = np.empty((A.shape[0], B.shape[0]), dtype=np.int64)
+    for r0 in range(0, A.shape[0], block):
+        blk = A[r0:r0 + block] @ B.T
+        out[r0:r0 + block] = blk.astype(np.int64)
+        assert np.array_equal(out[r0:r0 + block].astype(np.float32), blk)   # integers, nothing lost
+    return out
+
+
+class ExactBlock:
+    """Exact pair statistics of the rows of one code matrix against the rows of another over the same haplotypes: the
+    attributes of Exact that a cell check reads (num, den2, num2, degenerate, zero_num, r64, r2_64), each [n_i, n_j] -- the
+    off-diagonal block of Exact(stacked) without its two squares (tests/test_ld_rect_host.py pins that they are equal)."""
+
+    def __init__(self, codes_i, codes_j):
+        codes_i, codes_j = np.asarray(codes_i), np.asarray(codes_j)
+        assert codes_i.ndim == codes_j.ndim == 2 and codes_i.dtype == codes_j.dtype == np.int8
+        assert codes_i.shape[1] == codes_j.shape[1]
+        self.n_i, self.n_j, self.n_hap = codes_i.shape[0], codes_j.shape[0], codes_i.shape[1]
+        assert 1 <= self.n_hap <= MAX_HAPS
+        n = np.int64(self.n_hap)
+        self.a_i, self.a_j = ((c == 1).sum(axis=1).astype(np.int64) for c in (codes_i, codes_j))
+        self.r_i, self.r_j = ((c == 0).sum(axis=1).astype(np.int64) for c in (codes_i, codes_j))
+        self.n11 = alt_counts_block(codes_i, codes_j)
+        assert int(self.n11.max(initial=0)) <= self.n_hap
+        ar_i, ar_j = self.a_i * self.r_i, self.a_j * self.r_j
+        assert int(max(ar_i.max(initial=0), ar_j.max(initial=0))) < (1 << 25)
+        self._finish(n * self.n11 - np.multiply.outer(self.a_i, self.a_j), np.multiply.outer(ar_i, ar_j))
+
+    def _finish(self, num, den2):
+        """The derived attributes, with Exact's bounds checked on the values themselves."""
+        self.num, self.den2 = num, den2
+        assert int(np.abs(num).max(initial=0)) < (1 << 27)
+        assert int(den2.max(initial=0)) < (1 << 50) and int(den2.min(initial=0)) >= 0
+        self.num2 = num * num
+        assert int(self.num2.max(initial=0)) < (1 << 54)
+        self.degenerate = den2 == 0
+        self.zero_num = (num == 0) & ~self.degenerate
+        den = np.where(self.degenerate, 1, den2).astype(np.float64)
+        self.r64 = np.where(self.degenerate, 0.0, num.astype(np.float64) / np.sqrt(den))
+        self.r2_64 = np.where(self.degenerate, 0.0, self.num2.astype(np.float64) / den)
+
+
 def window_mask(positions, window: int) -> np.ndarray:
     """bool [n, n]: |pos_i - pos_j| <= window (the diagonal included)."""
     pos = np.asarray(positions, dtype=np.int64)

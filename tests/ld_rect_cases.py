@@ -20,6 +20,18 @@ EDGE_CASES = (
 )
 HITS_CASE = ((300, 130), 1008)      # two I blocks, two J slabs, both last tiles partial
 FAMILY = 100                        # rows [0, FAMILY) of the hits panel's side I are noisy copies of FAMILY / 20 base rows
+# the walk (tile_of, ldx_rect.hip): workgroups are numbered inside bands of 16 I blocks of 256 rows.  One full band; 16 + 1
+# with one row in the last block; 16 + 2; the long side on J (35 slabs under one band); 16 + 16 + 1
+I_BLOCK, BAND_BLOCKS = 256, 16
+WALK_CASES = (
+    ((4096, 130), 64),
+    ((4097, 130), 254),
+    ((4353, 257), 254),
+    ((130, 4353), 254),
+    ((8200, 130), 64),
+)
+WALK_HITS_CASE = ((4353, 257), 254)
+WALK_SWAPPED = ((130, 4353), 254)   # WALK_HITS_CASE's two panels swapped, side I cut to 130 rows: see walk_codes
 
 
 def random_codes(n_snps: int, n_hap: int, rng, miss: float = 0.005) -> np.ndarray:
@@ -74,6 +86,27 @@ def pair_codes(n_i: int, n_j: int, n_hap: int, seed: int, family: int = 0):
             src[flip & (src != 2)] ^= 1
             cj[b] = src
     return ci, cj
+
+
+def pair_seed(shape, n_hap: int) -> int:
+    return 1000 * shape[0] + shape[1] + n_hap
+
+
+def walk_codes(shape, n_hap: int):
+    """The two code matrices of a WALK_CASES entry: pair_codes, so copies and complements are planted across the sides.
+    (130, 4353) takes the panels of (4353, 257) swapped -- side I is the first 130 rows of that case's side J, side J its
+    side I -- so that its cells are the transpose of that case's first 130 columns."""
+    if (shape, n_hap) == WALK_SWAPPED:
+        ci, cj = walk_codes(*WALK_HITS_CASE)
+        assert ci.shape[0] == shape[1] and cj.shape[0] >= shape[0]
+        return np.ascontiguousarray(cj[:shape[0]]), ci
+    return pair_codes(shape[0], shape[1], n_hap, seed=pair_seed(shape, n_hap))
+
+
+def walk_bands(n_i: int):
+    """I blocks per band of the walk, in order: [16, 16, ..., the rest]."""
+    blocks = (n_i + I_BLOCK - 1) // I_BLOCK
+    return [min(BAND_BLOCKS, blocks - b) for b in range(0, blocks, BAND_BLOCKS)]
 
 
 def triangle_panel():

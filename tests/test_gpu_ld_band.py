@@ -17,6 +17,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "tests"))
 
 import fakevcf  # noqa: E402
+import ld_band_cases as bc  # noqa: E402
 import ld_dosage_exact as dx  # noqa: E402
 import ld_exact as lx  # noqa: E402
 
@@ -305,3 +306,280 @@ def test_driver(gpu, tmp_path):
         assert out[0].split("\t") == ["CHR", "SNP", "BP", f"{ga}_{gb}L2"]
         assert [ln.split("\t")[1] for ln in out[1:]] == [tab.rs_ids[k] for k in keep]
         assert [ln.split("\t")[3] for ln in out[1:]] == ["%.3f" % tab.scores[k] for k in keep]
+
+
+# ======================================================================================================================
+# Past the first tile and span: the layout kernel's 4096-SNP tiles and its carry, the sweep's 2048-column spans, the store
+# over dozens of 128-column tiles (tests/ld_band_cases.py; tests/test_ld_band_host.py pins what the cases cover).
+# ======================================================================================================================
+CANARY64 = 0x5CA1AB1E5CA1AB1E
+GARBAGE64 = 0x5A5A5A5A12345678    # what `sums` holds before a consumer runs: the calls need no memset
+
+
+@pytest.mark.parametrize("n", bc.layout_sizes + (bc.layout_size_64,))
+def test_layout_kernel_past_one_tile(gpu, n):
+    """ldx_ld_band_layout_dev alone on uploaded positions (it needs no panel): lo and offsets bit for bit the host mirror's
+    over arrays pre-filled with 0xFF bytes, the canary words behind lo[n] and offsets[n + 1] untouched."""
+    import torch
+    from ld_tools_amd import _lib, ops
+    from ld_tools_amd.panel import _stream_ptr
+    cases = bc.position_cases_64(n) if n == bc.layout_size_64 else bc.position_cases(n)
+    for k, (pos, w) in enumerate(cases):
+        want_lo, want_off = ops.band_layout_host(pos, w)
+        pos_d = torch.as_tensor(pos).to(gpu)
+        lo = torch.full((n + 16,), -1, dtype=torch.int32, device=gpu)
+        off = torch.full((n + 1 + 16,), -1, dtype=torch.int64, device=gpu)
+        lo[n:] = CANARY
+        off[n + 1:] = CANARY64
+        _lib.check(_lib.lib.ldx_ld_band_layout_dev(pos_d.data_ptr(), n, w, lo.data_ptr(), off.data_ptr(), _stream_ptr()),
+                   "ldx_ld_band_layout_dev")
+        torch.cuda.synchronize()
+        got_lo, got_off = lo.cpu().numpy().view(np.uint32), off.cpu().numpy().view(np.uint64)
+        bad = np.flatnonzero(got_lo[:n] != want_lo)
+        assert bad.size == 0, f"n {n}, case {k} (window {w}): lo differs first at SNP {bad[0]} (tile {bad[0] // bc.LAYOUT_TILE})"
+        bad = np.flatnonzero(got_off[:n + 1] != want_off)
+        assert bad.size == 0, (f"n {n}, case {k} (window {w}): offsets differ first at {bad[0]} (tile "
+                               f"{(max(int(bad[0]), 1) - 1) // bc.LAYOUT_TILE}): {got_off[bad[0]]} for {want_off[bad[0]]}")
+        assert (got_lo[n:] == CANARY).all() and (got_off[n + 1:] == CANARY64).all()
+    if n == bc.layout_size_64:
+        assert int(ops.band_layout_host(*cases[0])[1][n]) > 1 << 32        # the carry crossed 32 bits
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_layout(k):
+    """(positions, window, lo, offsets, rows, cols) of sweep case k on the host; computed once, shared, read-only."""
+    from ld_tools_amd import ops
+    pos, w = bc.sweep_cases()[k]
+    lo, off = ops.band_layout_host(pos, w)
+    rows, cols = bc.cell_rows_cols(lo, off)
+    for a in (pos, lo, off, rows, cols):
+        a.setflags(write=False)
+    return pos, w, lo, off, rows, cols
+
+
+@functools.lru_cache(maxsize=None)
+def synthetic_band(k, big, second=False):
+    """An LDBand over synthetic cells on sweep case k's layout -- the consumers are defined on any float32 cells (include/ldx.h,
+    "stored bands") -- with a random diagonal (some -0.0f); (band, cells on the host, diagonal on the host)."""
+    import torch
+    from ld_tools_amd import ops
+    pos, w, lo, off, rows, cols = sweep_layout(k)
+    n = len(pos)
+    dev = torch.device("cuda", 0)
+    v = bc.synthetic_cells(rows.size, bc.CELL_SEEDS[k] + (100 if second else 0), big=big)
+    rng = np.random.default_rng(1000 + k + (100 if second else 0))
+    d = rng.uniform(-1.25, 1.25, n).astype(np.float32)
+    d[rng.random(n) < 0.02] = np.float32(-0.0)
+    v.setflags(write=False)
+    d.setflags(write=False)
+    band = ops.LDBand(torch.as_tensor(np.array(v)).to(dev), torch.as_tensor(lo.view(np.int32).copy()).to(dev),
+                      torch.as_tensor(off.view(np.int64).copy()).to(dev), torch.as_tensor(np.array(d)).to(dev), pos, w, False, 0)
+    return band, v, d
+
+
+def raw_score(b1, b2, diagonals=True):
+    """ldx_band_score_dev into sums full of garbage; int64 [n] on the host."""
+    import torch
+    from ld_tools_amd import _lib
+    from ld_tools_amd.panel import _stream_ptr
+    n = b1.n_snps
+    sums = torch.full((n,), GARBAGE64, dtype=torch.int64, device=b1.values.device)
+    _lib.check(_lib.lib.ldx_band_score_dev(b1.values.data_ptr(), b2.values.data_ptr(), b1.diag.data_ptr() if diagonals else None,
+                                           b2.diag.data_ptr() if diagonals else None, b1.lo.data_ptr(), b1.offsets.data_ptr(), n,
+                                           sums.data_ptr(), _stream_ptr()), "ldx_band_score_dev")
+    return sums.cpu().numpy()
+
+
+def raw_matvec(b, x32, power, diagonal=True):
+    """ldx_band_matvec_dev on float32 [n, k] weights into sums full of garbage; int64 [n, k] on the host."""
+    import torch
+    from ld_tools_amd import _lib
+    from ld_tools_amd.panel import _stream_ptr
+    n, k = x32.shape
+    x_d = torch.as_tensor(np.ascontiguousarray(x32)).to(b.values.device)
+    sums = torch.full((n, k), GARBAGE64, dtype=torch.int64, device=b.values.device)
+    _lib.check(_lib.lib.ldx_band_matvec_dev(b.values.data_ptr(), b.diag.data_ptr() if diagonal else None, b.lo.data_ptr(),
+                                            b.offsets.data_ptr(), n, x_d.data_ptr(), k, power, sums.data_ptr(), _stream_ptr()),
+               "ldx_band_matvec_dev")
+    return sums.cpu().numpy()
+
+
+def first_difference(got, want, what):
+    """Fail with the first differing SNP, its 16-row group and how far it reaches back."""
+    bad = np.argwhere(np.asarray(got) != np.asarray(want))
+    assert bad.size == 0, f"{what}: {len(bad)} sums differ, the first at {bad[0].tolist()} (16-row group {int(bad[0][0]) // 16})"
+
+
+@pytest.mark.parametrize("k", range(3), ids=["everything", "grid2100", "clustered"])
+def test_score_sweep_past_one_span(gpu, k):
+    """ldx_band_score_dev on synthetic cells: the host's exact integer sum of T over the stored cells, to both SNPs of every
+    cell, plus T of the diagonals -- in either order of the bands, with NULL diagonals, and through ops.ld_cross_score."""
+    from ld_tools_amd import ops
+    pos, w, lo, off, rows, cols = sweep_layout(k)
+    n = len(pos)
+    b1, v1, d1 = synthetic_band(k, False)
+    b2, v2, d2 = synthetic_band(k, False, second=True)
+    assert not np.array_equal(v1, v2) and float(np.abs(v1).max()) <= 1.0 and float(np.abs(v2).max()) <= 1.0   # T is defined
+    terms = ops.cross_terms(v1, v2)
+    pairs = bc.pair_sums(n, rows, cols, terms)
+    want = pairs + ops.cross_terms(d1, d2)
+    first_difference(raw_score(b1, b2), want, f"score, case {k}")
+    first_difference(raw_score(b2, b1), want, f"score, case {k}, swapped")
+    first_difference(raw_score(b1, b2, diagonals=False), pairs, f"score, case {k}, no diagonals")
+    got = ops.ld_cross_score(b1, b2)
+    assert got.sums.dtype == np.int64 and np.array_equal(got.sums, want)
+
+
+@functools.lru_cache(maxsize=None)
+def host_matvec(k, big, power):
+    """(x float32 [n, 8], x32 the scaled weights, pair sums int64 [n, 8], own terms int64 [n, 8]) of sweep case k: the
+    integer sums of prod_terms over the stored cells in wrapping int64, one column per thread; computed once per
+    (case, big, power) and shared by the widths."""
+    from concurrent.futures import ThreadPoolExecutor
+    from test_gpu_exact_oracle import rhs
+    from ld_tools_amd import ops
+    pos, w, lo, off, rows, cols = sweep_layout(k)
+    n = len(pos)
+    _, v, d = synthetic_band(k, big)
+    x = rhs(n, n)
+    x32 = ops.matvec_rhs(x, n, power)[0].cpu().numpy()
+    pv = ops.prod_values(v, power)
+    own = ops.prod_terms(ops.prod_values(d, power)[:, None], x32)
+
+    def column(c):
+        xc = np.ascontiguousarray(x32[:, c])
+        s = np.zeros(n, dtype=np.int64)
+        with np.errstate(over="ignore"):
+            np.add.at(s, rows, ops.prod_terms(pv, xc[cols]))     # cell (i, j) feeds row i with the value at j ...
+            np.add.at(s, cols, ops.prod_terms(pv, xc[rows]))     # ... and column j with the value at i
+        return s
+
+    with ThreadPoolExecutor(max_workers=8) as pool:
+        pairs = np.stack(list(pool.map(column, range(8))), axis=1)
+    for a in (x, x32, pairs, own):
+        a.setflags(write=False)
+    return x, x32, pairs, own
+
+
+@pytest.mark.parametrize("big", [False, True], ids=["unit", "big"])
+@pytest.mark.parametrize("k", range(3), ids=["everything", "grid2100", "clustered"])
+def test_matvec_sweep_past_one_span(gpu, k, big):
+    """ldx_band_matvec_dev on synthetic cells, powers 1 and 2, widths 1, 3 (a pass of two and a pass of one) and 8: the
+    host's wrapping int64 sums of prod_terms.  ``big``: cells of +-2^22 .. 2^30 reach the clamp, and SNPs that collect
+    several wrap (tests/test_ld_band_host.py pins both)."""
+    from ld_tools_amd import ops
+    b, v, d = synthetic_band(k, big)
+    for power in (1, 2):
+        x, x32, pairs, own = host_matvec(k, big, power)
+        with np.errstate(over="ignore"):
+            want = pairs + own
+        for cols in ([1], [4, 5, 6], list(range(8))):
+            got = raw_matvec(b, x32[:, cols], power)
+            first_difference(got, want[:, cols], f"matvec, case {k}, big {big}, power {power}, columns {cols}")
+        via = b.matvec(x[:, [4, 5, 6]], power=power)             # the Python entry scales the columns itself
+        assert np.array_equal(via.x32.cpu().numpy(), x32[:, [4, 5, 6]])
+        first_difference(via.sums.cpu().numpy(), want[:, [4, 5, 6]], f"LDBand.matvec, case {k}, big {big}, power {power}")
+        if k == 2:
+            first_difference(raw_matvec(b, x32[:, [0, 3]], power, diagonal=False), pairs[:, [0, 3]],
+                             f"matvec, case {k}, big {big}, power {power}, no diagonal")
+
+
+# ---- the store at size -------------------------------------------------------------------------------------------------
+STORE_SHAPE = (4500, 130)          # 36 tiles of 128 columns; 130 is even: the dosage form applies
+STORE_SPECIAL = (2045, 2048, 4497)  # a monomorphic, an all-ALT and an all-missing row from each: both sides of a tile edge, the last tile
+
+
+@functools.lru_cache(maxsize=None)
+def store_case():
+    """(codes, panel, haplotype r32 square, dosage r32 square) of the 4500-SNP panel: computed once, shared, read-only."""
+    from ld_tools_amd import PackedPanel, ld_triangle, synth
+    n, h = STORE_SHAPE
+    codes = synth.synth_codes_host(n, h, seed=3 * n + h, block_len=200, rho=0.97, miss=0.01, miss_rows=0.5)
+    for r0 in STORE_SPECIAL:
+        codes[r0], codes[r0 + 1], codes[r0 + 2] = 0, 1, 2
+    assert STORE_SPECIAL[0] + 2 == 2047 and STORE_SPECIAL[1] % 128 == 0 and STORE_SPECIAL[2] // 128 == (n - 1) // 128
+    p = PackedPanel.from_codes(codes)
+    codes.setflags(write=False)
+    R = ld_triangle(p, fmt="r32").r_matrix().cpu().numpy()
+    Rd = ld_triangle(p, fmt="r32", dosage=True).r_matrix().cpu().numpy()
+    R.setflags(write=False)
+    Rd.setflags(write=False)
+    return codes, p, R, Rd
+
+
+def first_cell_difference(got, want, lo, off, what):
+    bad = np.flatnonzero(bits(got) != bits(want))
+    if bad.size:
+        i = int(np.searchsorted(off.astype(np.int64), bad[0], side="right")) - 1
+        j = int(lo[i]) + int(bad[0]) - int(off[i])
+        raise AssertionError(f"{what}: {bad.size} cells differ, the first is word {bad[0]} = cell ({i}, {j}): row tile {i // 128}, "
+                             f"column tile {j // 128}, {(i // 128) - (j // 128)} tiles apart")
+
+
+@pytest.mark.parametrize("k", range(3), ids=["everything", "grid2100", "clustered"])
+def test_store_past_three_tiles(gpu, k):
+    """The store epilogue over bands of up to 36 tiles: values, lo / offsets and diag against the r32 squares, both paths and
+    the dosage form, and a relaunch into a NaN-filled buffer with canary words behind it."""
+    import torch
+    from ld_tools_amd import ops
+    codes, p, R, Rd = store_case()
+    n = STORE_SHAPE[0]
+    pos, w, lo, off, rows, cols = sweep_layout(k)
+    pos_d = torch.as_tensor(pos).to(gpu)
+    wants = {False: band_cells(R, lo, n), True: band_cells(Rd, lo, n)}
+    assert wants[False].size == int(off[n]) and (bits(wants[False]) == 0x80000000).any()   # degenerate rows take part
+    for dosage, path in ((False, "fp4"), (False, "mfma"), (True, "fp4")):
+        square, want = (Rd, wants[True]) if dosage else (R, wants[False])
+        what = f"store, case {k}, {path}, dosage {dosage}"
+        b = ops.ld_band(p, pos, window_bp=w, path=path, dosage=dosage)
+        assert np.array_equal(b.lo.cpu().numpy().view(np.uint32), lo), what
+        assert np.array_equal(b.offsets.cpu().numpy().view(np.uint64), off), what
+        assert b.n_cells == int(off[n]) and b.dosage == dosage and b.window == w
+        first_cell_difference(b.values.cpu().numpy(), want, lo, off, what)
+        assert np.array_equal(bits(b.diag.cpu().numpy()), bits(np.diagonal(square))), what
+        buf = torch.full((b.n_cells + 64,), float("nan"), dtype=torch.float32, device=gpu)
+        buf[b.n_cells:].view(torch.int32).fill_(CANARY)
+        raw_store(p, pos_d, w, b.lo, b.offsets, buf, b.n_cells, path, dosage)
+        back = buf.cpu().numpy()
+        first_cell_difference(back[:b.n_cells], want, lo, off, what + ", relaunch")
+        assert (back[b.n_cells:].view(np.uint32) == CANARY).all(), what
+        del b, buf
+
+
+def test_real_band_at_size_feeds_the_consumers(gpu):
+    """The 4500-SNP panel's band with 2100 SNPs each side, tied to the operators that are proven at size: its self score is
+    ld_score's column 0 and its products are ld_matvec's, bit for bit."""
+    from ld_tools_amd import ops
+    codes, p, R, Rd = store_case()
+    n = STORE_SHAPE[0]
+    pos, w, lo, off, rows, cols = sweep_layout(1)
+    b = ops.ld_band(p, pos, window_bp=w)
+    got = ops.ld_cross_score(b, b)
+    want = ops.ld_score(p, pos, window_bp=w).sums.cpu().numpy().view(np.uint64)[:, 0]
+    first_difference(got.sums.view(np.uint64), want, "self score at 4500")
+    from test_gpu_exact_oracle import rhs
+    x = rhs(n, n)[:, [1, 3, 6]]
+    for power in (1, 2):
+        mine = b.matvec(x, power=power)
+        ref = ops.ld_matvec(p, x, pos, window_bp=w, power=power)
+        assert mine.sums.shape == (n, 3) and np.array_equal(mine.exps.cpu().numpy(), ref.exps.cpu().numpy())
+        first_difference(mine.sums.cpu().numpy(), ref.sums.cpu().numpy(), f"band matvec at 4500, power {power}")
+
+
+def test_stored_cells_at_the_lds_limit_against_the_exact_oracle(gpu):
+    """lr2500 (2500 x 10240 = LDX_MAX_HAPS, LD across tiles): the stored cells of the everything window (20 tiles) and of
+    129 SNPs each side against exact counts -- -0.0f iff degenerate, +0.0f iff num == 0, else within 4 ulps with num's sign."""
+    from test_gpu_exact_oracle import check_cells
+    from ld_tools_amd import PackedPanel, ops
+    codes, _, ex = lx.long_range_panel("lr2500")
+    n = ex.n_snps
+    p = PackedPanel.from_codes(np.array(codes), gpu)
+    windows = lx.neighbour_windows(n)
+    for pos, w in (windows[0], windows[1]):
+        lo, off = ops.band_layout_host(pos, w)
+        rows, cols = bc.cell_rows_cols(lo, off)
+        b = ops.ld_band(p, pos, window_bp=w)
+        assert b.n_cells == rows.size > 0
+        worst = check_cells(b.values.cpu().numpy(), ex, rows, cols, f"lr2500 band, window {w}")
+        print(f"lr2500 band, window {w}: {rows.size} cells, worst error {worst:.3f} float32 ulps")
+        del b

@@ -60,17 +60,23 @@ def pair(shape, n_hap, family=0):
 
 
 def check_block(got32, ex, n_i, what):
-    """The off-diagonal block [0, n_i) x [n_i, n) of an oracle over the stacked codes against the rectangle's cells."""
+    """The rectangle's cells against an oracle: the off-diagonal block [0, n_i) x [n_i, n) of an Exact / DosageExact over the
+    stacked codes, or an ExactBlock / DosageExactBlock of the two sides (which IS that block)."""
+    def field(name):
+        a = getattr(ex, name)
+        return a if isinstance(ex, lx.ExactBlock) else a[:n_i, n_i:]
+
     b = np.ascontiguousarray(got32).view(np.uint32)
-    deg = ex.degenerate[:n_i, n_i:]
-    zero = ex.zero_num[:n_i, n_i:]
+    deg = field("degenerate")
+    zero = field("zero_num")
+    assert deg.shape == b.shape
     assert np.array_equal(b == NEG0, deg), f"{what}: -0.0f <=> degenerate"
     assert np.array_equal(b == POS0, zero), f"{what}: +0.0f <=> num == 0"
-    one = (ex.num2[:n_i, n_i:] == ex.den2[:n_i, n_i:]) & ~deg   # num^2 == den2: exactly +1.0f / -1.0f (include/ldx.h)
-    assert np.array_equal(got32[one], np.sign(ex.num[:n_i, n_i:][one]).astype(np.float32)), f"{what}: |r| = 1 cells"
+    one = (field("num2") == field("den2")) & ~deg   # num^2 == den2: exactly +1.0f / -1.0f (include/ldx.h)
+    assert np.array_equal(got32[one], np.sign(field("num")[one]).astype(np.float32)), f"{what}: |r| = 1 cells"
     rest = ~deg & ~zero
     if rest.any():
-        err = lx.ulp32_err(got32[rest], ex.r64[:n_i, n_i:][rest])
+        err = lx.ulp32_err(got32[rest], field("r64")[rest])
         print(f"{what}: {int(rest.sum())} cells, max error {float(err.max()):.3f} float32 ulps")
         assert float(err.max()) <= ULPS, f"{what}: {float(err.max())} ulps"
     return int(rest.sum())
@@ -156,6 +162,78 @@ def test_rect_writes_its_cells_and_nothing_else(gpu, shape, n_hap):
     assert (b[:, n_j:] == fill).all() and (b[n_i:] == fill).all()
     assert np.array_equal(b[:n_i, :n_j], bits(ops.ld_rect(pi, pj)))
     assert not np.isnan(buf[:n_i, :n_j].cpu().numpy()).any()
+
+
+# ---- 4b. the walk: full bands of 16 I blocks, band indices above 0, a short last band ----------------------------------------
+_WALK = {}
+
+
+def walk_pair(shape, n_hap):
+    """(codes_i, codes_j, panel_i, panel_j) of one walk case, built once and left unchanged."""
+    from ld_tools_amd import PackedPanel
+    key = (shape, n_hap)
+    if key not in _WALK:
+        ci, cj = rc.walk_codes(shape, n_hap)
+        _WALK[key] = (ci, cj, PackedPanel.from_codes(ci), PackedPanel.from_codes(cj))
+    return _WALK[key]
+
+
+def walk_cells(gpu, shape, n_hap, dosage):
+    """ops.ld_rect of a walk case into the inside of a padded buffer full of a NaN payload: every cell of [n_i, n_j]
+    written, every word outside it intact.  Returns the cells on the host."""
+    import torch
+    from ld_tools_amd import ops
+    _, _, pi, pj = walk_pair(shape, n_hap)
+    n_i, n_j = shape
+    fill = 0x7FC12345   # a quiet NaN with a payload no kernel produces
+    buf = torch.full((n_i + 3, n_j + 5), fill, dtype=torch.int32, device=gpu).view(torch.float32)
+    ret = ops.ld_rect(pi, pj, dosage=dosage, out=buf[:n_i])
+    assert ret.data_ptr() == buf.data_ptr() and ret.shape == (n_i, n_j) and ret.stride(0) == n_j + 5
+    b = bits(buf)
+    assert (b[:, n_j:] == fill).all() and (b[n_i:] == fill).all(), f"{shape}: a word outside the rectangle was written"
+    left = np.argwhere(b[:n_i, :n_j] == fill)
+    assert left.size == 0, f"{shape}: {len(left)} cells never written, the first at {left[0].tolist()}"
+    return np.ascontiguousarray(b[:n_i, :n_j]).view(np.float32)
+
+
+@pytest.mark.parametrize("shape,n_hap", rc.WALK_CASES, ids=[f"{s[0]}x{s[1]}x{h}" for s, h in rc.WALK_CASES])
+def test_rect_walk_past_one_band_against_the_exact_oracle(gpu, shape, n_hap):
+    """tile_of beyond its first band (tests/test_ld_rect_host.py pins what the table covers): a mis-numbered workgroup
+    leaves a tile unwritten, writes one twice with another tile's rows, or pairs the wrong rows -- the fill word, the
+    surroundings and the exact oracle of the two sides see each."""
+    ci, cj, _, _ = walk_pair(shape, n_hap)
+    got = walk_cells(gpu, shape, n_hap, False)
+    check_block(got, lx.ExactBlock(ci, cj), shape[0], f"walk, haplotype r {shape} x {n_hap}")
+    gd = walk_cells(gpu, shape, n_hap, True)
+    check_block(gd, dx.DosageExactBlock(ci, cj), shape[0], f"walk, dosage r {shape} x {n_hap}")
+
+
+@pytest.mark.parametrize("dosage", [False, True])
+def test_rect_walk_swapped_sides_are_bit_transposes(gpu, dosage):
+    """(130, 4353) is (4353, 257) with the sides swapped and the short side cut to 130 rows (rc.walk_codes): the long side
+    walks 18 I blocks in two bands in one call and 35 J slabs under one band in the other -- the same cells, transposed."""
+    (long_shape, h), (short_shape, h2) = rc.WALK_HITS_CASE, rc.WALK_SWAPPED
+    assert h == h2
+    a = walk_cells(gpu, long_shape, h, dosage)
+    b = walk_cells(gpu, short_shape, h2, dosage)
+    assert np.array_equal(a[:, :short_shape[0]].view(np.uint32), b.view(np.uint32).T)
+
+
+def test_rect_walk_hits_are_the_host_mirror_of_the_dense_cells(gpu):
+    """The hit lists over two bands of I blocks, and again from a buffer of one batch (the overflow re-run)."""
+    from ld_tools_amd import ops
+    shape, n_hap = rc.WALK_HITS_CASE
+    _, _, pi, pj = walk_pair(shape, n_hap)
+    r_host = walk_cells(gpu, shape, n_hap, False)
+    m = assert_hits(ops.ld_rect_hits(pi, pj, r2=0.2), r_host, ops.r2_bound(0.2), "walk, r2 >= 0.2")
+    i = expect_hits(r_host, ops.r2_bound(0.2))[0]
+    assert (i >= 4096).any() and (i < 4096).any()          # hits in both bands
+    waves = len(set((i // 64).tolist()))
+    assert waves >= 2                                      # two waves with a hit reserve two batches of 256: more than the buffer
+    small = ops.ld_rect_hits(pi, pj, r2=0.2, hit_capacity=256)
+    assert assert_hits(small, r_host, ops.r2_bound(0.2), "walk, r2 >= 0.2 from a 256-slot buffer") == m
+    hd = ops.ld_rect_hits(pi, pj, r2=0.2, dosage=True, hit_capacity=256)
+    assert_hits(hd, walk_cells(gpu, shape, n_hap, True), ops.r2_bound(0.2), "walk, dosage, r2 >= 0.2")
 
 
 # ---- 5. hits -----------------------------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@ import pytest
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "tests"))
 
+import ld_band_cases as bc  # noqa: E402
 import ld_exact as lx  # noqa: E402
 
 NEW_SYMBOLS = ["ldx_ld_band_layout_dev", "ldx_ld_band_workspace_bytes", "ldx_ld_band_dev", "ldx_ld_band_dosage_dev",
@@ -62,6 +63,95 @@ def test_band_layout_host_is_the_definition():
         ops.band_layout_host([3, 2, 5], 1)
     with pytest.raises(ops._lib.LdxError, match=">= 0"):
         ops.band_layout_host([1, 2, 5], -1)
+
+
+def matrix_layout(pos, w, block=512):
+    """lo[i] = min{j <= i : pos_i - pos_j <= w} from the n x n comparison (in row blocks), offsets its running sum."""
+    n = len(pos)
+    lo = np.empty(n, dtype=np.uint32)
+    cols = np.arange(n)
+    for r0 in range(0, n, block):
+        rows = np.arange(r0, min(r0 + block, n))
+        inside = ((pos[rows, None] - pos[None, :]) <= w) & (cols[None, :] <= rows[:, None])
+        lo[rows] = inside.argmax(axis=1)                                  # the first True of the row
+    offsets = np.zeros(n + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum(np.arange(n, dtype=np.int64) - lo.astype(np.int64)).astype(np.uint64)
+    return lo, offsets
+
+
+def test_band_layout_host_is_the_definition_past_one_tile():
+    """The position cases of the GPU layout test (tests/ld_band_cases.py) at 4097 SNPs -- one more than the layout kernel's
+    tile -- against the n x n definition: the host mirror is what the device layout is compared with."""
+    from ld_tools_amd import ops
+    n = 4097
+    cases = bc.position_cases(n)
+    assert len(cases) == 9
+    for pos, w in cases:
+        assert pos.dtype == np.int64 and pos.shape == (n,) and (np.diff(pos) >= 0).all()
+        lo, offsets = ops.band_layout_host(pos, w)
+        mlo, moff = matrix_layout(pos, min(w, 1 << 52))
+        assert np.array_equal(lo, mlo) and np.array_equal(offsets, moff), w
+    windows = sorted({w for _, w in cases})
+    assert windows[0] == 0 and windows[-1] == 1 << 62 and max(int(p[-1]) for p, _ in cases) > 1 << 50
+
+
+def test_the_sweep_cases_and_cells_cover_what_they_must():
+    """Conditions on the INPUTS of the GPU tests of the two consumers and the store (tests/test_gpu_ld_band.py): the reaches,
+    the jump of lo inside a 16-row group, the clamp and a wrapping sum.  If one fails, the seed or the share of big cells
+    changes -- not the condition."""
+    from ld_tools_amd import ops
+    n = 4500
+    cases = bc.sweep_cases(n)
+    assert len(cases) == 3
+    reach_max, jump_with_reach = 0, False
+    for pos, w in cases:
+        lo, off = ops.band_layout_host(pos, w)
+        lo = lo.astype(np.int64)
+        reach = np.arange(n) - lo
+        reach_max = max(reach_max, int(reach.max()))
+        assert reach.max() > bc.SWEEP_SPAN                                # every case walks a second span
+        first = lo[0::bc.SWEEP_ROWS]
+        last = lo[np.minimum(np.arange(0, n, bc.SWEEP_ROWS) + bc.SWEEP_ROWS - 1, n - 1)]
+        jump_with_reach |= bool(((last > first) & (reach[0::bc.SWEEP_ROWS] > bc.SWEEP_SPAN)).any())
+    assert reach_max > 2 * bc.SWEEP_SPAN                                  # ... and one a third
+    assert jump_with_reach
+    # the grid with 2100 SNPs each side: after the first rows no group's first column is a multiple of the span
+    lo = ops.band_layout_host(*cases[1])[0].astype(np.int64)
+    jmin = lo[0::bc.SWEEP_ROWS]
+    assert (jmin > 0).any() and (jmin[jmin > 0] % bc.SWEEP_SPAN != 0).all() and (np.arange(n) - lo).max() == 2100
+    # clustered, window 0: lo jumps at a row that is no multiple of 16
+    lo = ops.band_layout_host(*cases[2])[0].astype(np.int64)
+    jumps = np.flatnonzero(np.diff(lo) > 0) + 1
+    assert jumps.size and (jumps % bc.SWEEP_ROWS != 0).any() and (np.arange(n) - lo).max() == 2499
+    # the cells: specials present, nothing non-finite; big: terms at the clamp and a power-1 sum that wraps
+    pos, w = cases[2]
+    lo, off = ops.band_layout_host(pos, w)
+    rows, cols = bc.cell_rows_cols(lo, off)
+    assert rows.size == int(off[n]) and (cols < rows).all() and (cols >= lo[rows]).all()
+    plain = bc.synthetic_cells(rows.size, seed=bc.CELL_SEEDS[2])
+    pb = plain.view(np.uint32)
+    assert (np.abs(plain) <= 1).all() and (pb == 0).any() and (pb == 0x80000000).any() and (plain == 1).any() and (plain == -1).any()
+    assert ((np.abs(plain) > 0) & (np.abs(plain) < 2.0 ** -19)).any()
+    big = bc.synthetic_cells(rows.size, seed=bc.CELL_SEEDS[2], big=True)
+    assert np.isfinite(big).all() and 0 < int((np.abs(big) >= 2.0 ** 22).sum()) < rows.size // 1024
+    for v in (2.0 ** 22, 2.0 ** 23, 2.0 ** 30):
+        assert (big == v).any() and (big == -v).any()
+    from test_gpu_exact_oracle import rhs
+    x32 = ops.matvec_rhs(rhs(n, n), n)[0].numpy()[:, 1]                   # the GPU test's right-hand sides; column 1: uniform
+    t_row, t_col = ops.prod_terms(big, x32[cols]), ops.prod_terms(big, x32[rows])
+    assert int((np.abs(t_row) == 1 << 62).sum()) > 0 and int((np.abs(t_col) == 1 << 62).sum()) > 0
+    wrapped = np.zeros(n, dtype=np.int64)
+    with np.errstate(over="ignore"):
+        np.add.at(wrapped, rows, t_row)
+        np.add.at(wrapped, cols, t_col)
+    # the same sums without wrapping: 32-bit halves added as int64 (4500 terms of 32 bits: no overflow), joined as Python ints
+    hi, lo32 = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    for idx, t in ((rows, t_row), (cols, t_col)):
+        np.add.at(hi, idx, t >> 32)
+        np.add.at(lo32, idx, t & 0xFFFFFFFF)
+    true = [(int(h) << 32) + int(l) for h, l in zip(hi, lo32)]
+    assert all(s % (1 << 64) == int(wv) % (1 << 64) for s, wv in zip(true, wrapped))
+    assert sum(1 for s in true if not -(1 << 63) <= s < (1 << 63)) >= 1
 
 
 def test_cross_terms_are_one_float32_multiply_then_exact_scaling():

@@ -14,6 +14,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "tests"))
 
 import fakevcf  # noqa: E402
+import ld_dosage_exact as dx  # noqa: E402
 import ld_exact as lx  # noqa: E402
 import ld_rect_cases as rc  # noqa: E402
 
@@ -188,6 +189,59 @@ def test_the_gpu_tests_panels_hold_what_the_tests_rely_on():
     exd = lx.Exact(codes)
     assert (~exd.live[rows]).any() and set(rows.tolist()) & set(cols.tolist()) and len(set(rows.tolist())) < rows.size
     assert (codes == 2).any() and (~exd.live).sum() >= 8
+
+
+BLOCK_ATTRS = ("num", "den2", "num2", "degenerate", "zero_num", "r64", "r2_64")
+
+
+@pytest.mark.parametrize("shape", rc.SHAPES, ids=str)
+def test_exact_block_is_the_off_diagonal_block_of_the_stacked_oracle(shape):
+    """ExactBlock / DosageExactBlock (the oracles of the walk cases, whose stacked squares would be too heavy) against
+    Exact(stacked) / DosageExact(stacked): every attribute a cell check reads, equal."""
+    n_i, n_j = shape
+    ci, cj = rc.pair_codes(n_i, n_j, 254, seed=rc.pair_seed(shape, 254))
+    stacked = np.concatenate([ci, cj])
+    for block, full in ((lx.ExactBlock(ci, cj), lx.Exact(stacked)), (dx.DosageExactBlock(ci, cj), dx.DosageExact(stacked))):
+        assert isinstance(block, lx.ExactBlock)
+        for name in BLOCK_ATTRS:
+            got, want = getattr(block, name), getattr(full, name)[:n_i, n_i:]
+            assert got.shape == (n_i, n_j) and got.dtype == want.dtype, name
+            assert np.array_equal(got, want), (type(block).__name__, name)
+    # the other orientation is the transpose
+    back = lx.ExactBlock(cj, ci)
+    assert np.array_equal(back.num, lx.ExactBlock(ci, cj).num.T) and np.array_equal(back.den2, lx.ExactBlock(ci, cj).den2.T)
+
+
+def test_walk_cases_cover_what_they_must():
+    """The walk of rect_kernel (tile_of): bands of 16 I blocks of 256 rows.  The table must hold a band of exactly 16 blocks
+    that is the whole grid, a band index >= 2, a last band shorter than 16 after a full one (of one block, of one ROW, and of
+    two blocks), and the long side on J under one partial band."""
+    assert (rc.I_BLOCK, rc.BAND_BLOCKS) == (256, 16)
+    bands = {case: rc.walk_bands(case[0][0]) for case in rc.WALK_CASES}
+    assert len(bands) == len(rc.WALK_CASES) == 5
+    assert [16] in bands.values()                                          # one full band, nothing after it
+    assert any(len(b) >= 3 for b in bands.values())                        # a band index >= 2
+    assert any(len(b) >= 2 and b[-2] == 16 and b[-1] < 16 for b in bands.values())
+    assert bands[((4096, 130), 64)] == [16] and bands[((4097, 130), 254)] == [16, 1] and 4097 % rc.I_BLOCK == 1
+    assert bands[((4353, 257), 254)] == [16, 2] and bands[((8200, 130), 64)] == [16, 16, 1]
+    assert bands[((130, 4353), 254)] == [1] and (4353 + 127) // 128 == 35
+    assert rc.WALK_HITS_CASE in rc.WALK_CASES and rc.WALK_SWAPPED in rc.WALK_CASES
+    for (shape, n_hap) in rc.WALK_CASES:
+        assert n_hap % 2 == 0                                              # the dosage form applies
+        assert shape[0] % rc.I_BLOCK != 0 or shape == (4096, 130)          # partial last blocks but for the exact band
+    # the planted copies reach across the sides at size, and the swapped case is the hits case's transpose
+    ci, cj = rc.walk_codes(*rc.WALK_HITS_CASE)
+    si, sj = rc.walk_codes(*rc.WALK_SWAPPED)
+    assert ci.shape == (4353, 254) and cj.shape == (257, 254) and si.shape == (130, 254) and sj.shape == (4353, 254)
+    assert np.array_equal(si, cj[:130]) and np.array_equal(sj, ci)
+    ex = lx.ExactBlock(ci, cj)
+    one = (ex.num2 == ex.den2) & ~ex.degenerate
+    assert int((one & (ex.num > 0)).sum()) >= 10 and int((one & (ex.num < 0)).sum()) >= 10
+    assert ex.degenerate.any() and ex.zero_num.any()
+    rows_hit = np.flatnonzero(one.any(axis=1))
+    assert (rows_hit >= 4096).any() and (rows_hit < 4096).any()            # |r| = 1 cells in both bands
+    hits = int((ex.r2_64 >= 0.21).sum())
+    assert 0 < hits and int((ex.r2_64 >= 0.19).sum()) < ex.num.size // 4
 
 
 # ---- drivers/rect.py without a device ----------------------------------------------------------------------------------------
