@@ -722,6 +722,62 @@ int ldx_ld_rect_hits_dosage_dev(const void *alt_i, const double *gstat_i, uint32
                                 uint32_t n_hap, float r2_bound, ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits,
                                 void *stream);
 
+/* ---- unphased LD by EM: maximum-likelihood r and D' of every row of one SNP set against every row of another ---------------
+ * The dosage entries above give Weir's composite r of the genotypes.  These give what PLINK --r2 dprime / --ld and Haploview
+ * compute from unphased genotypes: the maximum-likelihood two-locus haplotype frequency, the double heterozygotes resolved by
+ * EM (Hill 1974), and from it r and D'.  Panels, individuals and dosages are those of the dosage entries: n_hap even, N =
+ * n_hap / 2, individual k owns haplotypes 2k and 2k + 1, g in {0, 1, 2} counts code-1 alleles only (a missing code or a second
+ * ALT acts as REF), T = 2 N.  For row i of I and row j of J:
+ *     a_i = sum_k g_ik (= acnt[i])    a_j likewise
+ *     S   = sum_k g_ik g_jk           (the dosage entries' S, <= 4 N)
+ *     H   = #{k : g_ik = 1 and g_jk = 1}      (double heterozygotes, <= N)
+ *   haplotypes of known phase (integers >= 0; S - H is always even):
+ *     n1 = (S - H) / 2          ALT.ALT        n2 = a_i - n1 - H         ALT.REF
+ *     n3 = a_j - n1 - H         REF.ALT        n4 = T - a_i - a_j + n1   REF.REF         n1 + n2 + n3 + n4 + 2 H = T
+ *   x in [0, H] = expected number of double heterozygotes in coupling phase:
+ *     h1 = n1 + x, h4 = n4 + x, h2 = n2 + H - x, h3 = n3 + H - x
+ *     g(x) = x h2 h3 - (H - x) h1 h4      (a cubic with leading coefficient 2, g(0) <= 0 <= g(H))
+ *     l(x) = n1 ln h1 + n2 ln h2 + n3 ln h3 + n4 ln h4 + H ln(h1 h4 + h2 h3)         (0 ln 0 = 0)
+ * l' has the sign of -g, so the local maxima of l on [0, H] are the roots of g on its rising branches, at most two.  x* is
+ * the maximiser of l over [0, H]; where both local maxima have the same l in the kernel's own fp64 evaluation, x* is the
+ * SMALLER x.  Then
+ *     p = (n1 + x*) / T,  pA = a_i / T,  pB = a_j / T,  D = p - pA pB
+ *     r  = D / sqrt(pA (1 - pA) pB (1 - pB))
+ *     D' = |D| / Dmax,  Dmax = min(pA (1 - pB), (1 - pA) pB) if D >= 0,  min(pA pB, (1 - pA)(1 - pB)) if D < 0
+ * (calc_ld.py's convention: D' >= 0, the sign lives in r).  Cells are float32:
+ *   degenerate pair (a_i in {0, T} or a_j in {0, T}): both cells -0.0f.  An all-heterozygous SNP (pA = 1/2) is LIVE here,
+ *     unlike in the dosage entries.
+ *   H = 0: x* = 0, the pair is fully phased; r is then +0.0f iff T n1 - a_i a_j = 0.  No other exact-zero promise is made.
+ *   accuracy: each cell is within 2 float32 ulps of the exact value plus 2^-40 absolute.
+ *   determinism: a cell is a function of (N, a_i, a_j, S, H) only, evaluated in fp64 by an arithmetic symmetric in the two
+ *     SNPs: rephasing, permuting individuals, or swapping the sides (transposed output) gives bit-identical cells.
+ * S and H come from the FP4 matrix cores in one K loop (ldx_em.hip: S as the dosage rectangle counts it, H from the het bits
+ * (w ^ (w >> 1)) & 0x5555...); no workspace, no library state.
+ *
+ * ldx_ld_em_rect_dev: out_r[i * ld_out + j] = r, out_dprime[i * ld_out + j] = D' for i < n_i, j < n_j.  Either output may be
+ *   NULL, not both.  Exactly the n_i x n_j words of each given output are written: the columns [n_j, ld_out) keep their bytes.
+ * ldx_ld_em_rect_hits_dev: every pair with r *f32 r >= r2_bound (ONE IEEE float32 multiply; r2_bound a float32 > 0, so a
+ *   degenerate pair is never kept) as the record {query = i, oppos = j, r_square = the r cell, d_prime = the D' cell}.  Slots,
+ *   batches, *n_hits and overflow are ldx_ld_rect_hits_dev's; ldx_area_finish_ex_dev(n_snps = n_i, counts_ready = 0) finishes.
+ * ldx_ld_em_counts_dev: S[i * ld + j], H[i * ld + j] = the two counts as uint32 (no acnt needed): what the K loop produced.
+ * ldx_ld_em_from_counts_dev: the epilogue alone on m tuples (a1[k], a2[k], S[k], H[k]) of n_ind individuals -- the device
+ *   function the kernel calls: r[k], dprime[k] the cells, x[k] = x* as a double.  Any output may be NULL.  A tuple that is no
+ *   genotype table (S - H odd, a negative n, a > 2 n_ind, H > n_ind) gives NaN in every output.
+ *
+ * Argument rules, checked before any HIP call (ldx_last_error() names the argument): a null pointer, n_i, n_j, m or n_ind = 0,
+ * ld < n_j, r2_bound not > 0, an odd n_hap = LDX_E_ARG; n_hap > LDX_MAX_HAPS (n_ind > LDX_MAX_HAPS / 2), or a bit plane of
+ * 4 GiB or more on either side = LDX_E_UNSUPPORTED.  All calls only enqueue work on `stream`. */
+int ldx_ld_em_rect_dev(const void *alt_i, const uint32_t *acnt_i, uint32_t n_i,
+                       const void *alt_j, const uint32_t *acnt_j, uint32_t n_j,
+                       uint32_t n_hap, float *out_r, float *out_dprime, size_t ld_out, void *stream);
+int ldx_ld_em_rect_hits_dev(const void *alt_i, const uint32_t *acnt_i, uint32_t n_i,
+                            const void *alt_j, const uint32_t *acnt_j, uint32_t n_j,
+                            uint32_t n_hap, float r2_bound, ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits, void *stream);
+int ldx_ld_em_counts_dev(const void *alt_i, uint32_t n_i, const void *alt_j, uint32_t n_j, uint32_t n_hap,
+                         uint32_t *S, uint32_t *H, size_t ld, void *stream);
+int ldx_ld_em_from_counts_dev(uint32_t n_ind, size_t m, const uint32_t *a1, const uint32_t *a2, const uint32_t *S,
+                              const uint32_t *H, float *r, float *dprime, double *x, void *stream);
+
 /* ---- synthetic panels: deterministic, identical on host and device ------ */
 /* codes int8 [n_snps][ld_codes] receive global SNPs [snp_offset, snp_offset + n_snps) (a rank's
  * shard).  thresholds: per-SNP ALT probability * 2^64 (computed on the host, see

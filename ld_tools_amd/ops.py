@@ -12,6 +12,8 @@
     ld_clump / ld_prune                     greedy clumping (PLINK --clump) and priority pruning on those lists
     ld_rect(panel_i, panel_j)               signed r of every SNP of one set against every SNP of another (dense float32)
     ld_rect_hits(panel_i, panel_j, r2=...)  the pairs of that rectangle with r^2 above a threshold, as a CSR
+    ld_em(panel_i, panel_j)                 unphased LD by maximum likelihood: EM r and D' of two SNP sets (dense float32)
+    ld_em_hits(panel_i, panel_j, r2=...)    the pairs of that rectangle whose EM r^2 reaches a threshold, with their D'
     pair_counts(panel_i, panel_j)           <- calc_ld.py:32           (bit-exact n11 block)
     ld_from_counts(n, n11, a1, r1, a2, r2)  <- calc_ld.py:33-97        (the epilogue alone)
 
@@ -2311,6 +2313,7 @@ class LDRectHits:
     n_j: int
     bound: np.float32       # the float32 bound on s (r2_bound)
     dosage: bool = False
+    em: bool = False        # ld_em_hits: r is the EM r and column 3 of ``hits`` the D' cell instead of s
 
     @property
     def j(self) -> torch.Tensor:
@@ -2321,6 +2324,13 @@ class LDRectHits:
     def r(self) -> torch.Tensor:
         """float32 [m]: the signed r of each pair -- the ld_rect cell, bit for bit (a view of ``hits``)."""
         return self.hits[:, 2].view(torch.float32)
+
+    @property
+    def dprime(self) -> torch.Tensor:
+        """float32 [m]: the D' of each pair -- the ld_em cell, bit for bit (ld_em_hits only; a view of ``hits``)."""
+        if not self.em:
+            raise _lib.LdxError("LDRectHits.dprime: only ld_em_hits records carry D'")
+        return self.hits[:, 3].view(torch.float32)
 
     def __len__(self) -> int:
         return int(self.hits.shape[0])
@@ -2344,18 +2354,8 @@ def ld_rect_hits(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, r2
     bound = r2_bound(r2, strict)
     require_gpu()
     n_i, n_j = panel_i.n_snps, pj.n_snps
-    dev = panel_i.device
-    fin_bytes = lib.ldx_area_finish_workspace_bytes(n_i)
-    fin = torch.empty(fin_bytes, dtype=torch.uint8, device=dev)
-    cap = int(hit_capacity) if hit_capacity is not None else max(1 << 20, 32 * (n_i + n_j))
-    n_hits = torch.zeros(1, dtype=torch.int64, device=dev)
-    summary = torch.zeros(2, dtype=torch.int64, device=dev)
-    offsets = torch.empty(n_i + 1, dtype=torch.int32, device=dev)
-    for attempt in range(4):
-        if not 0 <= cap < (1 << 32):
-            raise _lib.LdxError(f"ld_rect_hits: {cap} record slots needed; the CSR's offsets are uint32 (at most 2^32 - 1)")
-        raw = torch.empty((cap, 4), dtype=torch.int32, device=dev)
-        hits = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+
+    def launch(raw, cap, n_hits):
         if dosage:
             check(lib.ldx_ld_rect_hits_dosage_dev(panel_i.alt.data_ptr(), panel_i.dosage_stats()[1].data_ptr(), n_i,
                                                   pj.alt.data_ptr(), pj.dosage_stats()[1].data_ptr(), n_j, panel_i.n_hap,
@@ -2366,6 +2366,27 @@ def ld_rect_hits(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, r2
                                            pj.alt.data_ptr(), pj.acnt.data_ptr(), pj.rcnt.data_ptr(), n_j, panel_i.n_hap,
                                            float(bound), raw.data_ptr(), cap, n_hits.data_ptr(), _stream_ptr()),
                   "ldx_ld_rect_hits_dev")
+
+    offsets, hits = _rect_hits_run("ld_rect_hits", launch, n_i, n_j, panel_i.device, hit_capacity)
+    return LDRectHits(offsets, hits, n_i, n_j, bound, bool(dosage))
+
+
+def _rect_hits_run(what: str, launch, n_i: int, n_j: int, dev, hit_capacity: Optional[int]):
+    """The hit entries' buffers and retry loop: ``launch(raw, cap, n_hits)`` enqueues one run into ``cap`` record slots,
+    ldx_area_finish_ex_dev sorts what it stored into a CSR over the rows of panel I; a run that reserved more slots than it
+    had runs again at the reserved count plus ld_neighbors' margin, at most four times.  Returns (offsets, sorted records)."""
+    fin_bytes = lib.ldx_area_finish_workspace_bytes(n_i)
+    fin = torch.empty(fin_bytes, dtype=torch.uint8, device=dev)
+    cap = int(hit_capacity) if hit_capacity is not None else max(1 << 20, 32 * (n_i + n_j))
+    n_hits = torch.zeros(1, dtype=torch.int64, device=dev)
+    summary = torch.zeros(2, dtype=torch.int64, device=dev)
+    offsets = torch.empty(n_i + 1, dtype=torch.int32, device=dev)
+    for attempt in range(4):
+        if not 0 <= cap < (1 << 32):
+            raise _lib.LdxError(f"{what}: {cap} record slots needed; the CSR's offsets are uint32 (at most 2^32 - 1)")
+        raw = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+        hits = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+        launch(raw, cap, n_hits)
         # the finishing step counts the stored records per row itself (counts_ready = 0): rows are panel I's
         check(lib.ldx_area_finish_ex_dev(raw.data_ptr(), n_hits.data_ptr(), cap, n_i, hits.data_ptr(), offsets.data_ptr(),
                                          summary.data_ptr(), fin.data_ptr(), fin_bytes, 0, _stream_ptr()),
@@ -2375,9 +2396,219 @@ def ld_rect_hits(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, r2
             break
         cap = reserved + reserved // 64 + (1 << 16)   # ld_neighbors' margin: the batches' tails differ with the work order
     else:
-        raise _lib.LdxError("ld_rect_hits: the record count did not settle")
+        raise _lib.LdxError(f"{what}: the record count did not settle")
     del raw
-    return LDRectHits(offsets, hits[:total], n_i, n_j, bound, bool(dosage))
+    return offsets, hits[:total]
+
+
+# --------------------------------------------------------------------------- unphased LD by EM (two SNP sets)
+@dataclass
+class LDEm:
+    """ld_em's two matrices on the device, float32 [n_i, n_j] each (None where only the other was asked for)."""
+
+    r: Optional[torch.Tensor]
+    dprime: Optional[torch.Tensor]
+
+
+def _em_out(what: str, name: str, out, n_i: int, n_j: int, dev):
+    """An output matrix of ld_em: checked as ld_rect checks ``out``; returns (tensor, row stride)."""
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != n_i
+            or out.shape[1] < n_j or (out.shape[1] > 1 and out.stride(1) != 1) or out.device != dev):
+        raise _lib.LdxError(f"{what}: {name} must be a float32 [{n_i}, >= {n_j}] tensor with unit column stride on {dev}")
+    ld = out.stride(0) if n_i > 1 else max(out.stride(0), out.shape[1])
+    if ld < n_j:
+        raise _lib.LdxError(f"{what}: {name} has row stride {ld} < n_j = {n_j}")
+    return out, ld
+
+
+def ld_em(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, out_r=None, out_dprime=None,
+          want_r: bool = True, want_dprime: bool = True) -> LDEm:
+    """Unphased LD by maximum likelihood of every SNP of ``panel_i`` against every SNP of ``panel_j`` (None: ``panel_i``
+    itself) over the same individuals (even n_hap; individual k owns haplotypes 2k and 2k + 1): the EM haplotype frequency of
+    the genotype table, and from it ``.r`` and ``.dprime``, float32 [n_i, n_j] on the device (include/ldx.h, "unphased LD by
+    EM", ldx_ld_em_rect_dev) -- what PLINK --r2 dprime computes.  -0.0f in both on a degenerate pair; D' >= 0, the sign lives
+    in r.
+
+    ``out_r`` / ``out_dprime``: float32 device tensors [n_i, >= n_j] with unit column stride and one row stride to write into;
+    the columns beyond n_j are left untouched.  ``want_r`` / ``want_dprime`` = False leaves that matrix out (None in the
+    result); not both."""
+    pj = _rect_panels("ld_em", panel_i, panel_j, True)
+    n_i, n_j, dev = panel_i.n_snps, pj.n_snps, panel_i.device
+    if not ((want_r or out_r is not None) or (want_dprime or out_dprime is not None)):
+        raise _lib.LdxError("ld_em: neither r nor D' was asked for")
+    lds = []
+    if out_r is not None:
+        out_r, ld = _em_out("ld_em", "out_r", out_r, n_i, n_j, dev)
+        lds.append(ld)
+    if out_dprime is not None:
+        out_dprime, ld = _em_out("ld_em", "out_dprime", out_dprime, n_i, n_j, dev)
+        lds.append(ld)
+    if len(set(lds)) > 1:
+        raise _lib.LdxError(f"ld_em: out_r and out_dprime differ in row stride ({lds[0]} and {lds[1]}); the entry takes one")
+    require_gpu()
+    ld = lds[0] if lds else n_j
+    if out_r is None and want_r:
+        out_r = torch.empty((n_i, ld), dtype=torch.float32, device=dev)
+    if out_dprime is None and want_dprime:
+        out_dprime = torch.empty((n_i, ld), dtype=torch.float32, device=dev)
+    check(lib.ldx_ld_em_rect_dev(panel_i.alt.data_ptr(), panel_i.acnt.data_ptr(), n_i, pj.alt.data_ptr(), pj.acnt.data_ptr(),
+                                 n_j, panel_i.n_hap, out_r.data_ptr() if out_r is not None else None,
+                                 out_dprime.data_ptr() if out_dprime is not None else None, ld, _stream_ptr()),
+          "ldx_ld_em_rect_dev")
+    return LDEm(out_r[:, :n_j] if out_r is not None else None, out_dprime[:, :n_j] if out_dprime is not None else None)
+
+
+def ld_em_hits(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, r2: float = 0.2, strict: bool = False,
+               hit_capacity: Optional[int] = None) -> LDRectHits:
+    """The pairs (row i of ``panel_i``, row j of ``panel_j``) whose EM r has r^2 >= ``r2`` (``strict``: r^2 > r2): r the ld_em
+    cell bit for bit, r^2 one float32 multiply (include/ldx.h, ldx_ld_em_rect_hits_dev + ldx_area_finish_ex_dev).  The result
+    is ld_rect_hits' CSR with ``em`` set: column 3 of ``hits`` holds the D' cell (``.dprime``).  Buffers and retries are
+    ld_rect_hits'."""
+    pj = _rect_panels("ld_em_hits", panel_i, panel_j, True)
+    bound = r2_bound(r2, strict)
+    require_gpu()
+    n_i, n_j = panel_i.n_snps, pj.n_snps
+
+    def launch(raw, cap, n_hits):
+        check(lib.ldx_ld_em_rect_hits_dev(panel_i.alt.data_ptr(), panel_i.acnt.data_ptr(), n_i, pj.alt.data_ptr(),
+                                          pj.acnt.data_ptr(), n_j, panel_i.n_hap, float(bound), raw.data_ptr(), cap,
+                                          n_hits.data_ptr(), _stream_ptr()), "ldx_ld_em_rect_hits_dev")
+
+    offsets, hits = _rect_hits_run("ld_em_hits", launch, n_i, n_j, panel_i.device, hit_capacity)
+    return LDRectHits(offsets, hits, n_i, n_j, bound, False, True)
+
+
+def ld_em_counts(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The two pair counts the EM starts from, as the kernel's K loop produced them: (S, H), int32 [n_i, n_j] each on the
+    device -- S = sum_k g_ik g_jk, H = the number of individuals heterozygous at both SNPs (ldx_ld_em_counts_dev)."""
+    pj = _rect_panels("ld_em_counts", panel_i, panel_j, True)
+    require_gpu()
+    n_i, n_j, dev = panel_i.n_snps, pj.n_snps, panel_i.device
+    S = torch.empty((n_i, n_j), dtype=torch.int32, device=dev)
+    H = torch.empty((n_i, n_j), dtype=torch.int32, device=dev)
+    check(lib.ldx_ld_em_counts_dev(panel_i.alt.data_ptr(), n_i, pj.alt.data_ptr(), n_j, panel_i.n_hap, S.data_ptr(),
+                                   H.data_ptr(), n_j, _stream_ptr()), "ldx_ld_em_counts_dev")
+    return S, H
+
+
+def ld_em_from_counts(n_ind: int, a_i, a_j, S, H, device: Optional[torch.device] = None):
+    """The EM epilogue alone on a list of count tuples of ``n_ind`` individuals -- the device function of ld_em's kernel
+    (ldx_ld_em_from_counts_dev).  Returns (r float32, dprime float32, x float64) device tensors [m]; a tuple that is no
+    genotype table gives NaN in all three."""
+    require_gpu()
+    dev = device or torch.device("cuda", torch.cuda.current_device())
+    cols = []
+    for name, v in (("a_i", a_i), ("a_j", a_j), ("S", S), ("H", H)):
+        v = np.ascontiguousarray(v.cpu().numpy() if hasattr(v, "cpu") else v).reshape(-1)
+        if v.size and (int(v.min()) < 0 or int(v.max()) >= (1 << 32)):
+            raise _lib.LdxError(f"ld_em_from_counts: {name} must hold uint32 values")
+        cols.append(torch.from_numpy(v.astype(np.int64).astype(np.uint32).view(np.int32)).to(dev))
+    m = int(cols[0].numel())
+    if any(int(c.numel()) != m for c in cols):
+        raise _lib.LdxError("ld_em_from_counts: a_i, a_j, S and H differ in length")
+    r = torch.empty(m, dtype=torch.float32, device=dev)
+    dprime = torch.empty(m, dtype=torch.float32, device=dev)
+    x = torch.empty(m, dtype=torch.float64, device=dev)
+    check(lib.ldx_ld_em_from_counts_dev(int(n_ind), m, cols[0].data_ptr(), cols[1].data_ptr(), cols[2].data_ptr(),
+                                        cols[3].data_ptr(), r.data_ptr(), dprime.data_ptr(), x.data_ptr(), _stream_ptr()),
+          "ldx_ld_em_from_counts_dev")
+    return r, dprime, x
+
+
+def _em_root_host(g, dg, lo, hi, glo, ghi):
+    """em_root of ldx_em.hip: Newton steps kept inside [lo, hi] (g(lo) <= 0 <= g(hi)), bisection otherwise."""
+    if glo == 0.0:
+        return lo
+    if ghi == 0.0:
+        return hi
+    x = 0.5 * (lo + hi)
+    dxold = dx = hi - lo
+    gx, dgx = g(x), dg(x)
+    for _ in range(128):
+        if gx == 0.0:
+            break
+        if gx < 0.0:
+            lo = x
+        else:
+            hi = x
+        bisect = ((x - hi) * dgx - gx) * ((x - lo) * dgx - gx) > 0.0 or abs(2.0 * gx) > abs(dxold * dgx)
+        dxold = dx
+        if bisect:
+            dx = 0.5 * (hi - lo)
+            xn = lo + dx
+        else:
+            dx = gx / dgx
+            xn = x - dx
+        if xn == x:
+            break
+        x = xn
+        gx, dgx = g(x), dg(x)
+    return x
+
+
+def em_host(n_ind: int, a_i: int, a_j: int, S: int, H: int) -> Tuple[float, float, float]:
+    """The kernel's epilogue restated in Python floats (fp64): (x*, r, D') of one count tuple (include/ldx.h, "unphased LD
+    by EM"; ldx_em.hip, em_cell).  Documentation and a CPU reference: it follows the device path for path -- H = 0 closed
+    form; g monotone or one rising branch with a sign change: one bracketed Newton root, no logarithm; two candidates: the
+    larger l, the smaller x on a tie -- but is not promised to match it bit for bit.  A degenerate pair gives (0, -0.0, -0.0),
+    a tuple that is no genotype table three NaNs."""
+    import math
+    N, ai, aj, S, H = int(n_ind), int(a_i), int(a_j), int(S), int(H)
+    T = 2 * N
+    n1 = (S - H) // 2
+    n2, n3, n4 = ai - n1 - H, aj - n1 - H, T - ai - aj + n1
+    if ai > T or aj > T or H > N or S < H or (S - H) % 2 or min(ai, aj, S, H, n2, n3, n4) < 0:
+        return math.nan, math.nan, math.nan
+    if ai in (0, T) or aj in (0, T):
+        return 0.0, -0.0, -0.0
+    x = 0.0
+    if H > 0:
+        f1, f4, m2, m3, Hf = float(n1), float(n4), float(n2 + H), float(n3 + H), float(H)
+
+        def g(x):
+            return x * ((m2 - x) * (m3 - x)) - (Hf - x) * ((f1 + x) * (f4 + x))
+
+        def dg(x):
+            h1, h4, h2, h3 = f1 + x, f4 + x, m2 - x, m3 - x
+            return (h2 * h3 - x * (h2 + h3)) + (h1 * h4 - (Hf - x) * (h1 + h4))
+
+        def loglik(x):
+            h1, h4, h2, h3 = f1 + x, f4 + x, m2 - x, m3 - x
+            l14 = (n1 * math.log(h1) if n1 else 0.0) + (n4 * math.log(h4) if n4 else 0.0)
+            l23 = (n2 * math.log(h2) if n2 else 0.0) + (n3 * math.log(h3) if n3 else 0.0)
+            return (l14 + l23) + Hf * math.log(h1 * h4 + h2 * h3)
+
+        g0, gH = -float(H * n1 * n4), float(H * n2 * n3)
+        c2 = n1 + n4 - n2 - n3 - 3 * H
+        c1 = (n2 + H) * (n3 + H) - H * (n1 + n4) + n1 * n4
+        disc = c2 * c2 - 6 * c1
+        if disc <= 0:
+            x = _em_root_host(g, dg, 0.0, Hf, g0, gH)
+        else:
+            sq = math.sqrt(float(disc))
+            xa, xb = (-c2 - sq) / 6.0, (-c2 + sq) / 6.0
+            have1 = have2 = False
+            if xa > 0.0:
+                hi1 = min(xa, Hf)
+                ghi1 = g(hi1) if xa < Hf else gH
+                have1 = ghi1 >= 0.0
+            if xb < Hf:
+                lo2 = max(xb, 0.0)
+                glo2 = g(lo2) if xb > 0.0 else g0
+                have2 = glo2 <= 0.0
+            if have1 and have2:
+                x1, x2 = _em_root_host(g, dg, 0.0, hi1, g0, ghi1), _em_root_host(g, dg, lo2, Hf, glo2, gH)
+                x = x2 if loglik(x2) > loglik(x1) else x1
+            elif have1:
+                x = _em_root_host(g, dg, 0.0, hi1, g0, ghi1)
+            elif have2:
+                x = _em_root_host(g, dg, lo2, Hf, glo2, gH)
+            else:
+                x = _em_root_host(g, dg, 0.0, Hf, g0, gH)
+    dn = float(T) * x + float(T * n1 - ai * aj)
+    r = dn / math.sqrt(float(ai * (T - ai)) * float(aj * (T - aj)))
+    dmax = min(ai * (T - aj), (T - ai) * aj) if dn >= 0.0 else min(ai * aj, (T - ai) * (T - aj))
+    return x, r, abs(dn) / float(dmax)
 
 
 # --------------------------------------------------------------------------- instrumentation
