@@ -43,6 +43,41 @@ bool check_recip(uint32_t n)
     return true;
 }
 
+int plane_check(const char *who, const char *arg, uint32_t n_snps, uint32_t n_hap)
+{
+    if ((uint64_t)n_slabs(n_snps) * n_chunks(n_hap) * kSlab * 16u < (1ull << 32)) return LDX_OK;
+    if (arg) set_error("%s: %s is a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", who, arg, n_snps, n_hap);
+    else set_error("%s: a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", who, n_snps, n_hap);
+    return LDX_E_UNSUPPORTED;
+}
+
+int rect_args_ok(const char *who, uint32_t n_i, uint32_t n_j, uint32_t n_hap, const char *odd_reason, uint32_t tile_rows)
+{
+    LDX_ARG_REQUIRE(n_i != 0u && n_j != 0u, "%s: %s is 0", who, n_i == 0u ? "n_i" : "n_j");
+    LDX_ARG_REQUIRE(n_hap != 0u, "%s: n_hap is 0", who);
+    LDX_ARG_REQUIRE(!odd_reason || n_hap % 2u == 0u, "%s: n_hap %u is odd (%s)", who, n_hap, odd_reason);
+    if (n_hap > LDX_MAX_HAPS) {
+        set_error("%s: n_hap %u > LDX_MAX_HAPS %u", who, n_hap, LDX_MAX_HAPS);
+        return LDX_E_UNSUPPORTED;
+    }
+    if (const int rc = plane_check(who, "alt_i", n_i, n_hap)) return rc;
+    if (const int rc = plane_check(who, "alt_j", n_j, n_hap)) return rc;
+    if ((uint64_t)((n_i + tile_rows - 1u) / tile_rows) * n_slabs(n_j) >= (1ull << 31)) {
+        set_error("%s: n_i x n_j = %u x %u needs 2^31 or more tiles of %u x 128", who, n_i, n_j, tile_rows);
+        return LDX_E_UNSUPPORTED;
+    }
+    return LDX_OK;
+}
+
+int hit_args_ok(const char *who, float r2_bound, const ldx_hit *hits, uint64_t hit_cap, const uint64_t *n_hits)
+{
+    LDX_ARG_PTR(who, n_hits);
+    LDX_ARG_REQUIRE(hits != nullptr || hit_cap == 0u, "%s: hits is a null pointer but hit_cap is %llu", who,
+                    (unsigned long long)hit_cap);
+    LDX_ARG_REQUIRE(r2_bound > 0.0f, "%s: r2_bound must be a float32 > 0 (got %g)", who, (double)r2_bound);
+    return LDX_OK;
+}
+
 }  // namespace ldx
 
 using namespace ldx;

@@ -9,17 +9,14 @@
 //      opposing rows through the same LDS-tile / scalar-row inner loop as ld_triangle, the fp64 epilogue
 //      with var_1 = query, var_2 = opposing (ld_area.py:242-243), the window / self filter
 //      (ld_area.py:174-177,222), the threshold on the ROUNDED measure (ld_area.py:248) and hit append.
-// Hits are appended through per-wave slot batches (one global atomic per 256 slots); unused slots are
-// marked invalid (query == UINT32_MAX).
+// Hits are appended through HitAppender (ldx_common.h): per-wave slot batches, one global atomic per 256 slots, unused
+// slots marked invalid (query == UINT32_MAX).
 #include <atomic>
 
 #include "ldx_common.h"
 #include "ldx_tile.h"
 
 namespace ldx {
-
-constexpr uint32_t kBatch = 256;   // hit slots a wave reserves per atomic
-constexpr uint32_t kInvalid = 0xFFFFFFFFu;
 
 struct AreaWs {          // carved out of the caller's workspace
     uint4 *qalt;         // tiled plane of the gathered query rows
@@ -67,7 +64,7 @@ __global__ void __launch_bounds__(256) area_gather_kernel(const uint4 *__restric
     for (uint32_t c = lane; c < nchunks; c += 64u) dst[(size_t)c * kSlab] = real ? src[(size_t)c * kSlab] : zero;
     if (lane == 0) {
         w.qpos[k] = real ? pos[row] : INT64_MAX;
-        w.qrow[k] = real ? row : kInvalid;
+        w.qrow[k] = real ? row : kHitInvalid;
         w.qfa[k] = real ? fa[row] : 0.0;
         w.qfr[k] = real ? fr[row] : 0.0;
         w.qq[k] = real ? q[row] : 0.0;
@@ -142,8 +139,7 @@ area_scan_kernel(const uint4 *__restrict__ alt, const uint4 *__restrict__ qalt, 
     const uint64_t b0 = total * blockIdx.x / gridDim.x;
     const uint64_t b1 = total * (blockIdx.x + 1) / gridDim.x;
 
-    // per-wave hit slots: [slot, slot_end) is the unfilled part of the current batch
-    uint64_t slot = 0, slot_end = 0;
+    HitAppender hit{hits, hit_cap, n_hits, lane, query_counts};
 
     if (b0 < b1) {
         uint32_t lo = 0, hi = T;   // largest t with unit_base[t] <= b0
@@ -183,7 +179,7 @@ area_scan_kernel(const uint4 *__restrict__ alt, const uint4 *__restrict__ qalt, 
 #pragma unroll
                     for (int jj = 0; jj < 2; ++jj) {
                         const uint32_t o = jj ? o1 : o0;
-                        bool keep = qrow != kInvalid && ov[jj] && o != qrow && low < po[jj] && po[jj] <= high;
+                        bool keep = qrow != kHitInvalid && ov[jj] && o != qrow && low < po[jj] && po[jj] <= high;
                         ldx_ld32 res = {0.0f, 0.0f};
                         if (keep) {
                             const LdRaw lr = ld_epilogue((double)acc.v[r][jj] / n, fa1, fr1, q1, fa2[jj], fr2[jj]);
@@ -191,29 +187,7 @@ area_scan_kernel(const uint4 *__restrict__ alt, const uint4 *__restrict__ qalt, 
                             keep = (measure == LDX_MEASURE_RSQ ? lk.kr : lk.kd) >= k_thres;   // ld_area.py:248
                             res = encode_cell<ldx_ld32>(lk);
                         }
-                        const unsigned long long m = __ballot(keep);
-                        if (m) {   // wave-uniform
-                            const uint32_t cnt = __builtin_popcountll(m);
-                            if (slot + cnt > slot_end) {
-                                // close the old batch (mark what is left invalid), open a new one
-                                for (uint64_t s = slot + lane; s < slot_end; s += 64u)
-                                    if (s < hit_cap) hits[s].query = kInvalid;
-                                unsigned long long base = 0;
-                                if (lane == 0) base = atomicAdd(n_hits, (unsigned long long)kBatch);
-                                base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-                                       __builtin_amdgcn_readfirstlane((uint32_t)base);
-                                slot = base;
-                                slot_end = base + kBatch;
-                            }
-                            if (keep) {
-                                const uint64_t s = slot + __builtin_popcountll(m & ((1ull << lane) - 1ull));
-                                if (s < hit_cap) {
-                                    hits[s] = ldx_hit{qrow, o, res.r_square, res.d_prime};
-                                    if (query_counts) atomicAdd(&query_counts[qrow], 1u);   // only stored hits
-                                }
-                            }
-                            slot += cnt;
-                        }
+                        hit.append(keep, qrow, o, res.r_square, res.d_prime);
                     }
                 }
             }
@@ -221,8 +195,7 @@ area_scan_kernel(const uint4 *__restrict__ alt, const uint4 *__restrict__ qalt, 
             ++t;
         }
     }
-    for (uint64_t s = slot + lane; s < slot_end; s += 64u)
-        if (s < hit_cap) hits[s].query = kInvalid;
+    hit.close();
 }
 
 // ---- finishing on the device: raw slots (arbitrary order, with unused slots) -> hits in (query, opposing) order ----
@@ -235,7 +208,7 @@ __global__ void area_count_kernel(const ldx_hit *__restrict__ raw, const unsigne
     const uint64_t lim = *n_reserved < cap ? *n_reserved : cap;
     if (s >= lim) return;
     const uint32_t qv = raw[s].query;
-    if (qv < n_snps) atomicAdd(&counts[qv], 1u);   // kInvalid marks an unused slot
+    if (qv < n_snps) atomicAdd(&counts[qv], 1u);   // kHitInvalid marks an unused slot
 }
 
 // single workgroup: offsets[k] = sum of counts[0..k), offsets[n_snps] = all hits; cursor = a copy for the scatter;

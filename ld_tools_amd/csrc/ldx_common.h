@@ -86,6 +86,27 @@ int area_mfma(const void *alt, const double *fa, const double *fr, const double 
         }                                                          \
     } while (0)
 
+// the same with a message of the entry's own (printf form), and the first null pointer of a list, by name
+#define LDX_ARG_REQUIRE(cond, ...)           \
+    do {                                     \
+        if (!(cond)) {                       \
+            ::ldx::set_error(__VA_ARGS__);   \
+            return LDX_E_ARG;                \
+        }                                    \
+    } while (0)
+#define LDX_ARG_PTR(who, ptr) LDX_ARG_REQUIRE((ptr) != nullptr, "%s: %s is a null pointer", who, #ptr)
+
+// Argument rules that several host entries share (ldx_api.hip); each sets the message and returns its code, LDX_OK if it holds.
+// plane_check: the matrix kernels address a bit plane with 32-bit lane offsets, so one of 4 GiB or more is LDX_E_UNSUPPORTED;
+// `arg` names the plane in the message ("alt_i is a bit plane ..."), null where the entry has only one.
+int plane_check(const char *who, const char *arg, uint32_t n_snps, uint32_t n_hap);
+// The rectangle entries' shape rules (ldx_rect.hip, ldx_em.hip), in this order: n_i, n_j, n_hap non-zero; n_hap even where
+// `odd_reason` (the words in the message's brackets) is non-null; n_hap within LDX_MAX_HAPS; both planes; fewer than 2^31
+// tiles of tile_rows x 128.  Each entry has checked its own pointers before; everything returns before any HIP call.
+int rect_args_ok(const char *who, uint32_t n_i, uint32_t n_j, uint32_t n_hap, const char *odd_reason, uint32_t tile_rows);
+// The hit-list entries' own rules: a counter, a buffer for every slot, a float32 bound > 0 (so that no zero cell passes).
+int hit_args_ok(const char *who, float r2_bound, const ldx_hit *hits, uint64_t hit_cap, const uint64_t *n_hits);
+
 __host__ __device__ inline uint32_t n_slabs(uint32_t n_snps) { return (n_snps + kSlab - 1) / kSlab; }
 // chunks of 128 haplotypes per row, allocated in PAIRS (256 haplotypes): the FP4 matrix kernel consumes two chunks
 // per K-block (one per lane half), so a row always holds an even number of chunks; pad chunks are zero bits
@@ -93,6 +114,58 @@ __host__ __device__ inline uint32_t n_chunks(uint32_t n_hap) { return (n_hap + 2
 
 // first unit of j-tile t: t*G - 8*t*(t-1), G = groups in the padded panel
 __host__ __device__ inline uint64_t tile_base(uint64_t t, uint64_t G) { return t * G - 8u * t * (t - 1u); }
+
+// ---- the hit-slot protocol: how every kernel that emits ldx_hit records fills the caller's slot buffer -------------------
+// A wave owns a BATCH of kHitBatch consecutive slots, slot .. slot_end, drawn with one atomic add from *n_hits (which thus
+// counts slots reserved, not records).  A record goes to the next slot of the batch; a batch that cannot take all records of
+// one append is closed -- what is left of it marked unused (query = kHitInvalid) -- and a new one drawn; the wave's last batch
+// is closed at the end of the kernel.  Nothing is stored at or beyond hit_cap: *n_hits > hit_cap tells the caller to come
+// back with a larger buffer.  So every slot below min(*n_hits, hit_cap) holds a record or the mark, which is exactly what the
+// consumer, ldx_area_finish_ex_dev (ldx_area.hip), relies on.  `counts`, where given, receives the STORED records per query
+// row: what the consumer's scatter will place.
+// Users: area_scan_kernel, rect_kernel, em_kernel.  The band epilogues of triangle_mfma_kernel keep the same protocol as the
+// text of a macro (LDX_HIT_APPENDER, ldx_mfma.hip), because that kernel's instruction stream must not move.
+constexpr uint32_t kHitBatch = 256;              // slots a wave reserves per atomic
+constexpr uint32_t kHitInvalid = 0xFFFFFFFFu;    // `query` of an unused slot
+struct HitAppender {
+    ldx_hit *hits;
+    uint64_t hit_cap;
+    unsigned long long *n_hits;
+    uint32_t lane;
+    uint32_t *counts = nullptr;
+    uint64_t slot = 0, slot_end = 0;   // the unfilled part of the wave's current batch
+
+    // marks what is left of the current batch
+    __device__ __forceinline__ void close() const
+    {
+        for (uint64_t sl = slot + lane; sl < slot_end; sl += 64u)
+            if (sl < hit_cap) hits[sl].query = kHitInvalid;
+    }
+    // one record {i, j, a, b} per lane with `keep`; called by the whole wave
+    __device__ __forceinline__ void append(bool keep, uint32_t i, uint32_t j, float a, float b)
+    {
+        const unsigned long long mask = __ballot(keep);
+        if (!mask) return;   // wave-uniform
+        const uint32_t cnt = __builtin_popcountll(mask);
+        if (slot + cnt > slot_end) {
+            close();
+            unsigned long long base = 0;
+            if (lane == 0) base = atomicAdd(n_hits, (unsigned long long)kHitBatch);
+            base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
+                   __builtin_amdgcn_readfirstlane((uint32_t)base);
+            slot = base;
+            slot_end = base + kHitBatch;
+        }
+        if (keep) {
+            const uint64_t sl = slot + __builtin_popcountll(mask & ((1ull << lane) - 1ull));
+            if (sl < hit_cap) {
+                hits[sl] = ldx_hit{i, j, a, b};
+                if (counts) atomicAdd(&counts[i], 1u);
+            }
+        }
+        slot += cnt;
+    }
+};
 
 // ---- the epilogue: calc_ld.py:33-97 mirrored op for op in fp64 (compile with -ffp-contract=off) ----
 // Inputs: f11 = n11/n, and the per-SNP frequencies fa = a/n, fr = r/n, q1 = fa1*fr1.

@@ -3,7 +3,8 @@
 // from it r and D' -- dense float32 cells (ldx_ld_em_rect_dev), the pairs whose r *f32 r reaches a bound
 // (ldx_ld_em_rect_hits_dev), the two pair counts alone (ldx_ld_em_counts_dev) and the epilogue alone on a list of count
 // tuples (ldx_ld_em_from_counts_dev).  One kernel of its own, em_kernel, beside the rectangle's (ldx_rect.hip), whose
-// counting scheme, LDS image, walk and hit appender it follows:
+// counting scheme and LDS image it follows; the FP4 expanders and the walk are the shared ones of ldx_fp4.h, the hit appender
+// HitAppender of ldx_common.h:
 //   * counting: with the allele counts a_i, a_j fixed, the EM needs TWO pair counts, not the nine cells of the 3 x 3 table:
 //     S = sum_k g_ik g_jk (the dosage rectangle's count: expand32_a4 x expand32_b4_dosage) and H = #{k : g_ik = g_jk = 1}.
 //     The het bit of individual k, x = (w ^ (w >> 1)) & 0x5555..., sits on haplotype slot 2k only: expand32_a4(x) on the I
@@ -20,16 +21,13 @@
 //     wave packs (S, H) of its 64 x 64 cells into one word each, in the LDS the images no longer need (4 x 16 KiB), and a
 //     rolled loop over the 64 rows has lane = column: one em_cell per lane and trip, 256-byte row-major stores per wave (128
 //     per half-wave).  em_cell is a function of (N, a_i, a_j, S, H) alone, in an arithmetic symmetric in the two SNPs.
-//   * walk: tile_of of ldx_rect.hip with I blocks of 128 rows, 32 to a band (the same 4096-row bands).
-#include "ldx_common.h"
+//   * walk: tile_of (ldx_fp4.h) with I blocks of 128 rows, 32 to a band (the rectangle's 4096-row bands).
+#include "ldx_fp4.h"
 
 namespace ldx {
 namespace em {
 
 typedef int v2i __attribute__((ext_vector_type(2)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
 
 constexpr uint32_t kWaves = 4, kThreads = kWaves * 64u;
 constexpr uint32_t kWaveRows = 64, kWaveCols = 64;    // a wave's cells: 2 x 2 accumulator tiles of 32 x 32, twice (S and H)
@@ -40,34 +38,16 @@ constexpr uint32_t kImageH = 4u * 2u * kSlab * 8u;    // bytes of one H image: [
 constexpr uint32_t kImage = kImageS + kImageH;        // one buffer of the K loop: 24 KiB
 constexpr uint32_t kStage = kWaves * kWaveRows * kWaveCols * 4u;   // the epilogue's packed counts: 64 KiB
 constexpr uint32_t kLdsBytes = kStage > 2u * kImage ? kStage : 2u * kImage;
-constexpr uint32_t kHitBatch = 256;                   // hit slots a wave reserves per atomic (as in ldx_rect.hip)
 constexpr uint32_t kPackShift = 13;                   // packed cell = S << 13 | H  (H <= 5120 < 2^13, S <= 20480 < 2^15)
 constexpr int kRootTrips = 128;                       // bound of the root search (bisection alone needs ~70 from [0, 5120])
 
 enum Mode : int { kDense = 0, kHits = 1, kCounts = 2 };
 
-// FP4 (E2M1) operands, re-stated op for op as in ldx_rect.hip / ldx_mfma.hip: a nibble with one bit at position p in
-// {0, 1, 2} reads 0.5 / 1 / 2; A keeps a haplotype bit at its place in the nibble, B carries it at 2 - p.
-__device__ __forceinline__ v4i expand32_a4(uint32_t w)
-{
-    const uint32_t t = w >> 2;
-    return v4i{(int)(w & 0x11111111u), (int)(w & 0x22222222u), (int)(t & 0x11111111u), (int)(t & 0x22222222u)};   // 0.5, 1, 0.5, 1
-}
-__device__ __forceinline__ v4i expand32_b4_dosage(uint32_t w)
-{
-    const uint32_t s = w >> 1, o = w | s, n = w & s, x = w ^ s;
-    return v4i{(int)(((o << 2) & 0x44444444u) | ((n << 1) & 0x22222222u)),    // individual 2q:     2 g
-               (int)(((x << 1) & 0x22222222u) | ((n << 2) & 0x44444444u)),    //                      g
-               (int)((o & 0x44444444u) | ((n >> 1) & 0x22222222u)),           // individual 2q + 1: 2 g
-               (int)(((x >> 1) & 0x22222222u) | (n & 0x44444444u))};          //                      g
-}
 // the het bits of a word's 16 individuals, on their even haplotype slots
 __device__ __forceinline__ uint32_t het_bits(uint32_t w) { return (w ^ (w >> 1)) & 0x55555555u; }
 // expand32_a4 / expand32_b4 of a het word: the odd slots are empty, so registers 1 and 3 are zero and only 0 and 2 are kept
 __device__ __forceinline__ v2i het_a4(uint32_t x) { return v2i{(int)(x & 0x11111111u), (int)((x >> 2) & 0x11111111u)}; }   // 0.5, 0.5
 __device__ __forceinline__ v2i het_b4(uint32_t x) { return v2i{(int)((x << 2) & 0x44444444u), (int)(x & 0x44444444u)}; }   // 2, 2
-
-__device__ __forceinline__ uint32_t word_of(const uint4 &v, int w) { return w == 0 ? v.x : (w == 1 ? v.y : (w == 2 ? v.z : v.w)); }
 
 // ---- the epilogue: (N, a_i, a_j, S, H) -> x*, r, D' in fp64 (include/ldx.h has the definitions) ------------------------------
 // Everything that enters is an integer below 2^53, every expression is symmetric in the two SNPs (n2 <-> n3 under the swap:
@@ -205,16 +185,6 @@ struct Args {
     unsigned long long *n_hits;
 };
 
-// ldx_rect.hip's walk: bands of kBandTiles I blocks; inside a band the J slab is the slow index
-__device__ __forceinline__ void tile_of(uint32_t b, uint32_t Ti, uint32_t Tj, uint32_t &ti, uint32_t &tj)
-{
-    const uint32_t per_band = kBandTiles * Tj;
-    const uint32_t band = b / per_band, rem = b - band * per_band;
-    const uint32_t left = Ti - band * kBandTiles, gi = left < kBandTiles ? left : kBandTiles;
-    tj = rem / gi;
-    ti = band * kBandTiles + (rem - tj * gi);
-}
-
 template <int kMode>
 __global__ void __launch_bounds__(kThreads, 2) em_kernel(Args p)
 {
@@ -226,7 +196,7 @@ __global__ void __launch_bounds__(kThreads, 2) em_kernel(Args p)
     const uint32_t wr = wave >> 1, wc = wave & 1u;   // the wave's 64 rows / 64 columns inside the 128 x 128 tile
     const uint32_t Ti = n_slabs(p.n_i), Tj = n_slabs(p.n_j);
     uint32_t ti, tj;
-    tile_of(blockIdx.x, Ti, Tj, ti, tj);
+    tile_of<kBandTiles>(blockIdx.x, Ti, Tj, ti, tj);
     const uint32_t nblocks = p.nblocks, nchunks = 2u * nblocks;
 
     if constexpr (kMode != kCounts) {
@@ -356,31 +326,7 @@ __global__ void __launch_bounds__(kThreads, 2) em_kernel(Args p)
     const uint32_t j = tj * kSlab + wc * kWaveCols + lane;
     const bool col_ok = j < p.n_j;
     [[maybe_unused]] const uint32_t a_j = kMode != kCounts ? cstat[wc * kWaveCols + lane] : 0u;
-    // hits: the wave's current batch of slots (the protocol of rect_kernel, which ldx_area_finish_ex_dev consumes)
-    [[maybe_unused]] uint64_t slot = 0, slot_end = 0;
-    [[maybe_unused]] auto close_batch = [&]() {
-        for (uint64_t sl = slot + lane; sl < slot_end; sl += 64u)
-            if (sl < p.hit_cap) p.hits[sl].query = 0xFFFFFFFFu;
-    };
-    [[maybe_unused]] auto append = [&](bool keep, uint32_t i, float r, float d) {
-        const unsigned long long mask = __ballot(keep);
-        if (!mask) return;   // wave-uniform
-        const uint32_t cnt = __builtin_popcountll(mask);
-        if (slot + cnt > slot_end) {
-            close_batch();
-            unsigned long long base = 0;
-            if (lane == 0) base = atomicAdd(p.n_hits, (unsigned long long)kHitBatch);
-            base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-                   __builtin_amdgcn_readfirstlane((uint32_t)base);
-            slot = base;
-            slot_end = base + kHitBatch;
-        }
-        if (keep) {
-            const uint64_t sl = slot + __builtin_popcountll(mask & ((1ull << lane) - 1ull));
-            if (sl < p.hit_cap) p.hits[sl] = ldx_hit{i, j, r, d};
-        }
-        slot += cnt;
-    };
+    [[maybe_unused]] HitAppender hit{p.hits, p.hit_cap, p.n_hits, lane};
     const uint32_t row0 = ti * kSlab + wr * kWaveRows;
     const uint32_t rows = row0 < p.n_i ? (p.n_i - row0 < kWaveRows ? p.n_i - row0 : kWaveRows) : 0u;   // wave-uniform
     for (uint32_t rr = 0; rr < rows; ++rr) {
@@ -397,14 +343,14 @@ __global__ void __launch_bounds__(kThreads, 2) em_kernel(Args p)
             Cell c{-0.0f, -0.0f, 0.0};
             if (col_ok) c = em_cell(p.n_ind, a_i, a_j, S, H);
             if constexpr (kMode == kHits) {
-                append(col_ok && c.r * c.r >= p.bound, i, c.r, c.dprime);   // ONE float32 multiply; -0.0f gives 0 < bound
+                hit.append(col_ok && c.r * c.r >= p.bound, i, j, c.r, c.dprime);   // ONE float32 multiply; -0.0f gives 0 < bound
             } else if (col_ok) {
                 if (p.out_r) __builtin_nontemporal_store(c.r, p.out_r + (size_t)i * p.ld + j);
                 if (p.out_d) __builtin_nontemporal_store(c.dprime, p.out_d + (size_t)i * p.ld + j);
             }
         }
     }
-    if constexpr (kMode == kHits) close_batch();   // what is left of the wave's last batch
+    if constexpr (kMode == kHits) hit.close();   // what is left of the wave's last batch
 }
 
 // the epilogue alone: one thread per tuple
@@ -417,43 +363,6 @@ __global__ void __launch_bounds__(256) from_counts_kernel(uint32_t n_ind, size_t
     if (r) r[k] = c.r;
     if (dprime) dprime[k] = c.dprime;
     if (x) x[k] = c.x;
-}
-
-static int plane_check(const char *who, const char *arg, uint32_t n_snps, uint32_t n_hap)
-{
-    if ((uint64_t)n_slabs(n_snps) * n_chunks(n_hap) * kSlab * 16u >= (1ull << 32)) {
-        set_error("%s: %s is a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", who, arg, n_snps, n_hap);
-        return LDX_E_UNSUPPORTED;
-    }
-    return LDX_OK;
-}
-
-// the rectangle forms' shared argument rules (each entry has checked its own pointers): everything returns before any HIP call
-static int args_ok(const char *who, uint32_t n_i, uint32_t n_j, uint32_t n_hap)
-{
-    if (n_i == 0u || n_j == 0u) {
-        set_error("%s: %s is 0", who, n_i == 0u ? "n_i" : "n_j");
-        return LDX_E_ARG;
-    }
-    if (n_hap == 0u) {
-        set_error("%s: n_hap is 0", who);
-        return LDX_E_ARG;
-    }
-    if (n_hap % 2u != 0u) {
-        set_error("%s: n_hap %u is odd (haplotypes 2k and 2k + 1 are the two alleles of individual k)", who, n_hap);
-        return LDX_E_ARG;
-    }
-    if (n_hap > LDX_MAX_HAPS) {
-        set_error("%s: n_hap %u > LDX_MAX_HAPS %u", who, n_hap, LDX_MAX_HAPS);
-        return LDX_E_UNSUPPORTED;
-    }
-    if (const int rc = plane_check(who, "alt_i", n_i, n_hap)) return rc;
-    if (const int rc = plane_check(who, "alt_j", n_j, n_hap)) return rc;
-    if ((uint64_t)n_slabs(n_i) * n_slabs(n_j) >= (1ull << 31)) {
-        set_error("%s: n_i x n_j = %u x %u needs 2^31 or more tiles of 128 x 128", who, n_i, n_j);
-        return LDX_E_UNSUPPORTED;
-    }
-    return LDX_OK;
 }
 
 static Args make_args(const void *alt_i, const uint32_t *acnt_i, uint32_t n_i, const void *alt_j, const uint32_t *acnt_j,
@@ -482,26 +391,22 @@ static int launch(const Args &p, hipStream_t s)
 
 using namespace ldx;
 
-#define LDX_EM_REQUIRE(cond, ...)            \
-    do {                                     \
-        if (!(cond)) {                       \
-            ::ldx::set_error(__VA_ARGS__);   \
-            return LDX_E_ARG;                \
-        }                                    \
-    } while (0)
-// the first null pointer of a list, by name
-#define LDX_EM_PTR(who, ptr) LDX_EM_REQUIRE((ptr) != nullptr, "%s: %s is a null pointer", who, #ptr)
+// the rectangle forms' shape rules: rect_args_ok (ldx_common.h) with this kernel's I block; every form pairs haplotypes
+static int args_ok(const char *who, uint32_t n_i, uint32_t n_j, uint32_t n_hap)
+{
+    return rect_args_ok(who, n_i, n_j, n_hap, "haplotypes 2k and 2k + 1 are the two alleles of individual k", kSlab);
+}
 
 extern "C" int ldx_ld_em_rect_dev(const void *alt_i, const uint32_t *acnt_i, uint32_t n_i, const void *alt_j,
                                   const uint32_t *acnt_j, uint32_t n_j, uint32_t n_hap, float *out_r, float *out_dprime,
                                   size_t ld_out, void *stream)
 {
     const char *const who = "ldx_ld_em_rect_dev";
-    LDX_EM_PTR(who, alt_i); LDX_EM_PTR(who, acnt_i);
-    LDX_EM_PTR(who, alt_j); LDX_EM_PTR(who, acnt_j);
-    LDX_EM_REQUIRE(out_r != nullptr || out_dprime != nullptr, "%s: out_r and out_dprime are both null pointers", who);
-    LDX_EM_REQUIRE(ld_out >= n_j, "%s: ld_out %zu < n_j %u", who, ld_out, n_j);
-    if (const int rc = em::args_ok(who, n_i, n_j, n_hap)) return rc;
+    LDX_ARG_PTR(who, alt_i); LDX_ARG_PTR(who, acnt_i);
+    LDX_ARG_PTR(who, alt_j); LDX_ARG_PTR(who, acnt_j);
+    LDX_ARG_REQUIRE(out_r != nullptr || out_dprime != nullptr, "%s: out_r and out_dprime are both null pointers", who);
+    LDX_ARG_REQUIRE(ld_out >= n_j, "%s: ld_out %zu < n_j %u", who, ld_out, n_j);
+    if (const int rc = args_ok(who, n_i, n_j, n_hap)) return rc;
     em::Args p = em::make_args(alt_i, acnt_i, n_i, alt_j, acnt_j, n_j, n_hap);
     p.out_r = out_r, p.out_d = out_dprime, p.ld = ld_out;
     return em::launch<em::kDense>(p, (hipStream_t)stream);
@@ -512,13 +417,10 @@ extern "C" int ldx_ld_em_rect_hits_dev(const void *alt_i, const uint32_t *acnt_i
                                        uint64_t hit_cap, uint64_t *n_hits, void *stream)
 {
     const char *const who = "ldx_ld_em_rect_hits_dev";
-    LDX_EM_PTR(who, alt_i); LDX_EM_PTR(who, acnt_i);
-    LDX_EM_PTR(who, alt_j); LDX_EM_PTR(who, acnt_j);
-    LDX_EM_PTR(who, n_hits);
-    LDX_EM_REQUIRE(hits != nullptr || hit_cap == 0u, "%s: hits is a null pointer but hit_cap is %llu", who,
-                   (unsigned long long)hit_cap);
-    LDX_EM_REQUIRE(r2_bound > 0.0f, "%s: r2_bound must be a float32 > 0 (got %g)", who, (double)r2_bound);
-    if (const int rc = em::args_ok(who, n_i, n_j, n_hap)) return rc;
+    LDX_ARG_PTR(who, alt_i); LDX_ARG_PTR(who, acnt_i);
+    LDX_ARG_PTR(who, alt_j); LDX_ARG_PTR(who, acnt_j);
+    if (const int rc = hit_args_ok(who, r2_bound, hits, hit_cap, n_hits)) return rc;
+    if (const int rc = args_ok(who, n_i, n_j, n_hap)) return rc;
     em::Args p = em::make_args(alt_i, acnt_i, n_i, alt_j, acnt_j, n_j, n_hap);
     p.bound = r2_bound, p.hits = hits, p.hit_cap = hit_cap, p.n_hits = (unsigned long long *)n_hits;
     LDX_HIP(hipMemsetAsync(n_hits, 0, sizeof(uint64_t), (hipStream_t)stream));   // the slot counter starts at 0
@@ -529,10 +431,10 @@ extern "C" int ldx_ld_em_counts_dev(const void *alt_i, uint32_t n_i, const void 
                                     uint32_t *S, uint32_t *H, size_t ld, void *stream)
 {
     const char *const who = "ldx_ld_em_counts_dev";
-    LDX_EM_PTR(who, alt_i); LDX_EM_PTR(who, alt_j);
-    LDX_EM_PTR(who, S); LDX_EM_PTR(who, H);
-    LDX_EM_REQUIRE(ld >= n_j, "%s: ld %zu < n_j %u", who, ld, n_j);
-    if (const int rc = em::args_ok(who, n_i, n_j, n_hap)) return rc;
+    LDX_ARG_PTR(who, alt_i); LDX_ARG_PTR(who, alt_j);
+    LDX_ARG_PTR(who, S); LDX_ARG_PTR(who, H);
+    LDX_ARG_REQUIRE(ld >= n_j, "%s: ld %zu < n_j %u", who, ld, n_j);
+    if (const int rc = args_ok(who, n_i, n_j, n_hap)) return rc;
     em::Args p = em::make_args(alt_i, nullptr, n_i, alt_j, nullptr, n_j, n_hap);
     p.out_s = S, p.out_h = H, p.ld = ld;
     return em::launch<em::kCounts>(p, (hipStream_t)stream);
@@ -542,9 +444,9 @@ extern "C" int ldx_ld_em_from_counts_dev(uint32_t n_ind, size_t m, const uint32_
                                          const uint32_t *H, float *r, float *dprime, double *x, void *stream)
 {
     const char *const who = "ldx_ld_em_from_counts_dev";
-    LDX_EM_PTR(who, a1); LDX_EM_PTR(who, a2); LDX_EM_PTR(who, S); LDX_EM_PTR(who, H);
-    LDX_EM_REQUIRE(n_ind > 0u, "%s: n_ind is 0", who);
-    LDX_EM_REQUIRE(m > 0u, "%s: m is 0", who);
+    LDX_ARG_PTR(who, a1); LDX_ARG_PTR(who, a2); LDX_ARG_PTR(who, S); LDX_ARG_PTR(who, H);
+    LDX_ARG_REQUIRE(n_ind > 0u, "%s: n_ind is 0", who);
+    LDX_ARG_REQUIRE(m > 0u, "%s: m is 0", who);
     if (n_ind > LDX_MAX_HAPS / 2u) {
         set_error("%s: n_ind %u > LDX_MAX_HAPS / 2 = %u", who, n_ind, LDX_MAX_HAPS / 2u);
         return LDX_E_UNSUPPORTED;

@@ -1,7 +1,7 @@
 // ld_triangle / ld_area on the matrix cores: n11 = G . G^T fused with the LD epilogue (calc_ld.py:30-97 for 8192 pairs per
 // wave unit).  One kernel template, triangle_mfma_kernel, in two counting forms:
 //   * kFp4 = true (the default path): v_mfma_f32_32x32x64_f8f6f4 with FP4 (E2M1) operands.  A haplotype bit becomes the
-//     nibble of its own 4-bit group with one AND per eight haplotypes (expand32_a4 / expand32_b4): the A operand keeps the bit
+//     nibble of its own 4-bit group with one AND per eight haplotypes (expand32_a4 / expand32_b4, ldx_fp4.h): the A operand keeps the bit
 //     at position p of the nibble, the B operand at 2 - p, every co-occurrence multiplies to exactly 1 and the fp32
 //     accumulators hold n11 exactly (< 2^24).  64 haplotypes per 32 cycles and SIMD: twice the int8 rate.
 //   * kFp4 = false (LDX_PATH_MFMA, the comparison path): v_mfma_i32_32x32x32_i8, bits expanded to bytes; accumulators hold
@@ -33,17 +33,15 @@
 #include <type_traits>
 
 #include "ldx_common.h"
+#include "ldx_fp4.h"
 #include "ldx_tile.h"
 
 namespace ldx {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 typedef unsigned v2u __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
 
 // global loads the compiler does not track (see the K loop): the caller waits with s_waitcnt vmcnt(N).
 // The K loop's form: a SCALAR base (the plane + the K-block's offset: SALU) and a 32-bit per-lane byte offset that does not
@@ -119,40 +117,7 @@ __device__ __forceinline__ v4i expand16_a(uint32_t word, uint32_t sel0, uint32_t
     return r;
 }
 
-// ---- FP4 (E2M1) operands for v_mfma_f32_32x32x64_f8f6f4: twice the int8 rate (64 haplotypes per 32 cycles) -----------
-// A nibble with ONE bit at position p in {0, 1, 2} reads 0.5 / 1 / 2 (position 3 is the sign: -0), so a haplotype bit
-// becomes the nibble of its own 4-bit group with NO data movement -- one AND per eight haplotypes -- as long as the
-// other operand carries the bit at position 2 - p: every co-occurrence multiplies to 1 and the fp32 accumulators hold
-// n11 exactly (< 2^24).  The K order inside an instruction is free (both operands use the same one): register v of an
-// operand holds haplotypes {v, v + 4, ..., v + 28} of the 32-bit word for v < 2, and {2, 6, ...} / {3, 7, ...} of the
-// word shifted down by two for v = 2, 3.  5 VALU per 32 haplotypes on the A side, 6 on the B side (the int8 forms
-// above: 14 and 24).  tools/probes/fp4rate.hip checks the exactness and the rate on the device.
-__device__ __forceinline__ v4i expand32_a4(uint32_t w)
-{
-    const uint32_t t = w >> 2;
-    return v4i{(int)(w & 0x11111111u), (int)(w & 0x22222222u), (int)(t & 0x11111111u), (int)(t & 0x22222222u)};   // 0.5, 1, 0.5, 1
-}
-__device__ __forceinline__ v4i expand32_b4(uint32_t w)
-{
-    const uint32_t t = w >> 2;
-    return v4i{(int)((w << 2) & 0x44444444u), (int)(w & 0x22222222u), (int)((w) & 0x44444444u), (int)(t & 0x22222222u)};   // 2, 1, 2, 1
-}
-
-// Genotype dosage (kDosage; DESIGN.md, "Dosage LD"): the A operand stays the haplotype bit (0.5 / 1 / 0.5 / 1), the B operand
-// carries, at the place of haplotype h, the ALT dosage g in {0, 1, 2} of the INDIVIDUAL of h -- haplotypes 2k and 2k + 1, two
-// adjacent bits of one word -- times the factor that makes the product g: 2 g against A's 0.5 (E2M1 0100 = 2, 0110 = 4), g
-// against A's 1 (0010 = 1, 0100 = 2).  With s = w >> 1 the even bits of o = w | s, n = w & s, x = w ^ s say g >= 1, g == 2,
-// g == 1; every mask below picks a bit that comes from an even position, so o, n and x need no mask of their own.  The
-// accumulators then hold S = sum over individuals of g_i g_j exactly (every product <= 2, S <= 2 n_hap < 2^24).  18 VALU per
-// 32 haplotypes where expand32_b4 takes 6; MFMA count, A side and LDS image are the haplotype kernel's.
-__device__ __forceinline__ v4i expand32_b4_dosage(uint32_t w)
-{
-    const uint32_t s = w >> 1, o = w | s, n = w & s, x = w ^ s;
-    return v4i{(int)(((o << 2) & 0x44444444u) | ((n << 1) & 0x22222222u)),    // individual 2q:     2 g
-               (int)(((x << 1) & 0x22222222u) | ((n << 2) & 0x44444444u)),    //                      g
-               (int)((o & 0x44444444u) | ((n >> 1) & 0x22222222u)),           // individual 2q + 1: 2 g
-               (int)(((x >> 1) & 0x22222222u) | (n & 0x44444444u))};          //                      g
-}
+// the FP4 kernel's B operand (ldx_fp4.h has the encoding): the haplotype bit, or the dosage of its individual
 template <bool kDosage>
 __device__ __forceinline__ v4i expand_b_fp4(uint32_t w)
 {
@@ -187,11 +152,6 @@ __device__ __forceinline__ v4i expand_b_fp4(uint32_t w)
 #else
 #define LDX_CSTAMP(k)
 #endif
-
-__device__ __forceinline__ uint32_t word_of(const uint4 &v, int w)
-{
-    return w == 0 ? v.x : (w == 1 ? v.y : (w == 2 ? v.z : v.w));
-}
 
 // this thread's share of the j-tile expansion for one chunk: row = tid / 2, 64 haplotypes (tid % 2)
 __device__ __forceinline__ void expand_b_share(uint2 bits, unsigned char *buf, uint32_t tid)
@@ -276,7 +236,6 @@ static_assert(sizeof(AreaArgs) == 112, "AreaArgs must not grow: see the comment 
 // an entry of the band's ticket order: kAreaDecoded | tile << 12 | pass inside the tile (both < 4096 whenever the order exists:
 // area_order_entries); plain pass indices (no order: panels beyond ~512 000 SNPs) are < 2^30
 constexpr uint32_t kAreaDecoded = 1u << 30;
-constexpr uint32_t kHitBatch = 256;   // hit slots a wave reserves per atomic (as in ldx_area.hip)
 constexpr uint32_t kAreaQueue = 256;  // band: candidate pairs a wave collects before it evaluates them, one per lane
 #ifdef LDX_MM1   // tuning build with three workgroups per CU: 53 KB of LDS each
 constexpr uint32_t kQueueCap = 32;
@@ -385,10 +344,9 @@ __device__ __forceinline__ uint64_t dpp_half_sum(uint64_t x)
 // part must compile to the instructions it compiled to when every epilogue spelled it out.  (As lambdas -- a column loader
 // that returns a struct, a sweep that calls a generic body -- the same work came out in another instruction and register
 // order in every band instantiation: the first simplification passes see a lambda's captures as loads through its closure.)
-// LDX_HIT_APPENDER: the Hits and Nbr epilogues' `append(keep, qrow, orow, a, b)` -- one record {qrow, orow, a, b} per lane
-// with `keep` into the wave's current batch of 256 slots, slot .. slot_end (the epilogue hands them back to hit_slot /
-// hit_slot_end); a full batch is closed (what is left of it marked invalid) and a new one drawn from aa.n_hits; stored
-// records are counted per row into aa.counts: only stored hits, what the scatter will place.
+// LDX_HIT_APPENDER: the Hits and Nbr epilogues' `append(keep, qrow, orow, a, b)` -- HitAppender::append (ldx_common.h, which
+// states the slot protocol) as text, for the reason above: the wave's current batch is slot .. slot_end, which the epilogue
+// hands back to hit_slot / hit_slot_end; stored records are counted per row into aa.counts.
 #define LDX_HIT_APPENDER                                                                                            \
     uint64_t slot = hit_slot, slot_end = hit_slot_end;                                                              \
     auto append = [&](bool keep, uint32_t qrow, uint32_t orow, float rec_a, float rec_b) {                          \
@@ -397,7 +355,7 @@ __device__ __forceinline__ uint64_t dpp_half_sum(uint64_t x)
         const uint32_t cnt = __builtin_popcountll(mask);                                                            \
         if (slot + cnt > slot_end) {                                                                                \
             for (uint64_t sl = slot + lane; sl < slot_end; sl += 64u)                                               \
-                if (sl < aa.hit_cap) aa.hits[sl].query = 0xFFFFFFFFu;                                               \
+                if (sl < aa.hit_cap) aa.hits[sl].query = kHitInvalid;                                               \
             unsigned long long base = 0;                                                                            \
             if (lane == 0) base = atomicAdd(aa.n_hits, (unsigned long long)kHitBatch);                              \
             base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |             \
@@ -2258,7 +2216,7 @@ triangle_mfma_kernel(const uint4 *__restrict__ alt, const double *__restrict__ f
     }
     if (kArea && !kStore)   // the unused slots of this wave's last batch
         for (uint64_t sl = hit_slot + lane; sl < hit_slot_end; sl += 64u)
-            if (sl < aa.hit_cap) aa.hits[sl].query = 0xFFFFFFFFu;
+            if (sl < aa.hit_cap) aa.hits[sl].query = kHitInvalid;
 }
 
 #undef LDX_HIT_APPENDER
@@ -2274,10 +2232,9 @@ static int launch_mfma(const void *alt, const double *fa, const double *fr, cons
                        uint32_t *out_n11, uint32_t *sched, hipStream_t s)
 {
     const uint32_t nch = n_chunks(n_hap);
-    if ((uint64_t)n_slabs(n_snps) * nch * kSlab * 16u >= (1ull << 32)) {   // the K loop addresses the plane with 32-bit lane offsets
-        set_error("ld_triangle on the matrix pipe: a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", n_snps, n_hap);
-        return kNoMatrixPath;   // LDX_PATH_AUTO: the popcount kernel; an explicit matrix-pipe path: LDX_E_UNSUPPORTED
-    }
+    // (the K loop addresses the plane with 32-bit lane offsets)  LDX_PATH_AUTO: the popcount kernel; an explicit matrix-pipe
+    // path: LDX_E_UNSUPPORTED
+    if (plane_check("ld_triangle on the matrix pipe", nullptr, n_snps, n_hap)) return kNoMatrixPath;
     const size_t lds = mfma_lds_bytes(kStatRows, kFp4 && !kRaw && !kN11 && !std::is_same<Cell, ldx_r32>::value);
     if (lds > 64u * 1024u) {   // above 64 KiB the dynamic LDS size needs the opt-in attribute: once per device
         static std::atomic<uint64_t> opted{0};   // one bit per device ordinal, per instantiation
@@ -2578,16 +2535,6 @@ size_t area_mfma_workspace_bytes(uint32_t n_snps)
     return band_carve(w, nullptr, n_snps, false);
 }
 
-// the band kernel's K loop addresses the plane with 32-bit lane offsets
-static int band_plane_check(const char *who, uint32_t n_snps, uint32_t n_hap)
-{
-    if ((uint64_t)n_slabs(n_snps) * n_chunks(n_hap) * kSlab * 16u >= (1ull << 32)) {
-        set_error("%s: a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", who, n_snps, n_hap);
-        return LDX_E_UNSUPPORTED;
-    }
-    return LDX_OK;
-}
-
 // the whole-panel operators' plan: the two-row query list {0, n - 1} their init kernels wrote makes every SNP a query, so the
 // plan keeps, per j-tile, the rows with pos <= pos(last column) + window -- every pair with pos_i - pos_j <= window (|delta| =
 // window included); each operator's epilogue applies the exact symmetric bound per pair.  Zeroes `n_hits`.
@@ -2645,7 +2592,7 @@ int area_mfma(const void *alt, const double *fa, const double *fr, const double 
               const int64_t *positions, const uint32_t *queries, uint32_t n_query, int64_t flank, int measure, double thres,
               ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits, uint32_t *query_counts, void *workspace, bool fp4, hipStream_t s)
 {
-    if (band_plane_check("ld_area on the matrix pipe", n_snps, n_hap)) return kNoMatrixPath;
+    if (plane_check("ld_area on the matrix pipe", nullptr, n_snps, n_hap)) return kNoMatrixPath;
     BandWs w;
     band_carve(w, workspace, n_snps, false);
     if (n_query == n_snps) {   // ascending distinct rows: every SNP is a query -- no mask at all
@@ -2761,7 +2708,7 @@ int score_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, cons
                uint32_t n_annot, bool fp4, uint64_t *sums, void *workspace, hipStream_t s, bool cross = false,
                const char *who = "ldx_ld_score_dev", const double *gstat = nullptr)
 {
-    if (const int rc = band_plane_check(who, n_snps, n_hap)) return rc;
+    if (const int rc = plane_check(who, nullptr, n_snps, n_hap)) return rc;
     BandWs w;   // (the query mask stays unused)
     band_carve(w, workspace, n_snps);
     const uint32_t st = 1u + n_annot;
@@ -2818,7 +2765,7 @@ int decay_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, cons
                uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, int64_t bin_width,
                const uint8_t *keep, bool fp4, uint64_t *sums, uint64_t *counts, uint32_t n_bins, void *workspace, hipStream_t s)
 {
-    if (const int rc = band_plane_check("ldx_ld_decay_dev", n_snps, n_hap)) return rc;
+    if (const int rc = plane_check("ldx_ld_decay_dev", nullptr, n_snps, n_hap)) return rc;
     BandWs w;   // (the query mask's bytes hold the effective keep mask)
     band_carve(w, workspace, n_snps);
     const uint32_t n_init = n_snps > n_bins ? n_snps : n_bins;
@@ -2863,7 +2810,7 @@ constexpr auto kFgtBand = triangle_mfma_kernel<false, false, BandOp::Fgt, kFp4>;
 int fgt_mfma(const void *alt, const uint32_t *acnt, uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window,
              uint32_t min_count, const uint8_t *keep, bool fp4, uint32_t *left, void *workspace, hipStream_t s)
 {
-    if (const int rc = band_plane_check("ldx_ld_fgt_dev", n_snps, n_hap)) return rc;
+    if (const int rc = plane_check("ldx_ld_fgt_dev", nullptr, n_snps, n_hap)) return rc;
     BandWs w;   // (the query mask's bytes hold the keep mask)
     band_carve(w, workspace, n_snps);
     fgt_init_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(keep, n_snps, w.mask, left, w.qrows);
@@ -2915,7 +2862,7 @@ int prod_mfma(const void *alt, const uint32_t *acnt, const uint32_t *rcnt, const
               uint32_t n_snps, uint32_t n_hap, const int64_t *positions, int64_t window, const float *x, uint32_t n_rhs,
               bool square, bool fp4, int64_t *sums, void *workspace, hipStream_t s)
 {
-    if (const int rc = band_plane_check("ldx_ld_matvec_dev", n_snps, n_hap)) return rc;
+    if (const int rc = plane_check("ldx_ld_matvec_dev", nullptr, n_snps, n_hap)) return rc;
     BandWs w;   // (the query mask stays unused)
     band_carve(w, workspace, n_snps);
     prod_init_kernel<<<(n_snps + 255u) / 256u, 256, 0, s>>>(acnt, rcnt, x, n_rhs, square, n_snps, n_hap, (uint64_t *)sums, w.qrows);
@@ -2954,7 +2901,7 @@ int nbr_mfma(const void *alt, const double *fa, const double *fr, uint32_t n_snp
              int64_t window, float r2_bound, bool fp4, ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits, uint32_t *row_counts,
              void *workspace, hipStream_t s, const char *who = "ldx_ld_neighbors_dev", const double *gstat = nullptr)
 {
-    if (const int rc = band_plane_check(who, n_snps, n_hap)) return rc;
+    if (const int rc = plane_check(who, nullptr, n_snps, n_hap)) return rc;
     if (row_counts) LDX_HIP(hipMemsetAsync(row_counts, 0, ((size_t)n_snps + 1u) * 4u, s));
     if (n_snps < 2) {   // no pairs: no plan kernel to zero the slot counter
         LDX_HIP(hipMemsetAsync(n_hits, 0, sizeof(uint64_t), s));
@@ -2989,7 +2936,7 @@ int store_mfma(const void *alt, const double *fa, const double *fr, uint32_t n_s
                int64_t window, bool fp4, const uint32_t *lo, const uint64_t *offsets, float *values, uint64_t n_cells,
                void *workspace, hipStream_t s, const char *who, const double *gstat = nullptr)
 {
-    if (const int rc = band_plane_check(who, n_snps, n_hap)) return rc;
+    if (const int rc = plane_check(who, nullptr, n_snps, n_hap)) return rc;
     if (n_snps < 2 || n_cells == 0u) return LDX_OK;   // no pairs, or no room for one: nothing to store
     BandWs w;   // (the query mask stays unused)
     band_carve(w, workspace, n_snps);

@@ -4,8 +4,8 @@
 // (ldx_mfma.hip), with which it shares the counting scheme and the cell arithmetic but no code object:
 //   * counting: v_mfma_f32_32x32x64_f8f6f4 with FP4 operands (cbsz = blgp = 4, scale 0).  The A operand of a haplotype bit is
 //     expand32_a4's nibble, the B operand expand32_b4's (dosage: expand32_b4_dosage's), every co-occurrence multiplies to
-//     exactly 1 and the fp32 accumulators hold n11 (dosage: S = sum g_i g_j) exactly, < 2^24.  The three expanders are
-//     re-stated below, op for op as in ldx_mfma.hip.
+//     exactly 1 and the fp32 accumulators hold n11 (dosage: S = sum g_i g_j) exactly, < 2^24.  The expanders and
+//     their exactness argument are the triangle's own: ldx_fp4.h.
 //   * tile: a workgroup (4 waves, two workgroups per CU) owns 256 rows of I x one 128-row slab of J; a wave 64 x 128 = 2 x 4
 //     accumulator tiles of 32 x 32 (128 registers).  J sits on the accumulator's COLUMN side (col = lane & 31), so a
 //     half-wave holds 32 consecutive cells of one output row: 128-byte row-major stores.
@@ -14,18 +14,17 @@
 //     block_sync per K-block); a lane loads the 16 bytes of its own I rows and expands them in registers.  The next
 //     K-block's global loads are issued before the current block's 32 MFMAs.  Plain HIP: the compiler tracks every load.
 //   * walk: workgroups are numbered so that consecutive ones share ONE J slab and differ in their I block, inside bands of
-//     kBandTiles I blocks (4096 rows); DESIGN.md, "Rectangular LD", has the reasoning and the budget.
+//     kBandTiles I blocks (4096 rows): tile_of (ldx_fp4.h), which em_kernel walks too; DESIGN.md, "Rectangular LD", has the
+//     reasoning and the budget.
+//   * hits: HitAppender (ldx_common.h), the slot protocol that ldx_area_finish_ex_dev consumes.
 //   * epilogue: every cell is r32_cell(count, n, a_i, rs_i, a_j, rs_j) (ldx_common.h) with the per-SNP {a, rs} of r32_snp --
 //     bit for bit the r32 triangle's cell for the same two SNPs.  The rectangle knows nothing about the identity of SNPs:
 //     where row i of I and row j of J are the same variant the cell is still r32_cell, NOT r32_diag.
-#include "ldx_common.h"
+#include "ldx_fp4.h"
 
 namespace ldx {
 namespace rect {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
 typedef double d2 __attribute__((ext_vector_type(2)));
 
 constexpr uint32_t kWaves = 4, kThreads = kWaves * 64u;
@@ -34,33 +33,6 @@ constexpr uint32_t kTileRows = kWaves * kWaveRows;    // I rows per workgroup: 2
 constexpr uint32_t kBandTiles = 16;                   // I blocks per band of the walk
 constexpr uint32_t kImageVecs = 4u * 2u * kSlab;      // 16-byte vectors of one J image: [4 steps][2 halves][128 rows]
 constexpr uint32_t kBlockVecs = 2u * kSlab;           // 16-byte vectors of one K-block of a slab in the plane (two chunks)
-constexpr uint32_t kHitBatch = 256;                   // hit slots a wave reserves per atomic (as in ldx_mfma.hip / ldx_area.hip)
-
-// FP4 (E2M1) operands: a nibble with one bit at position p in {0, 1, 2} reads 0.5 / 1 / 2.  A keeps a haplotype bit at its
-// place in the nibble, B carries it at 2 - p: every product is 1.  Register v of an operand holds haplotypes {v, v + 4, ...}
-// of the 32-bit word for v < 2 and {2, 6, ...} / {3, 7, ...} of the word shifted down by two for v = 2, 3.
-__device__ __forceinline__ v4i expand32_a4(uint32_t w)
-{
-    const uint32_t t = w >> 2;
-    return v4i{(int)(w & 0x11111111u), (int)(w & 0x22222222u), (int)(t & 0x11111111u), (int)(t & 0x22222222u)};   // 0.5, 1, 0.5, 1
-}
-__device__ __forceinline__ v4i expand32_b4(uint32_t w)
-{
-    const uint32_t t = w >> 2;
-    return v4i{(int)((w << 2) & 0x44444444u), (int)(w & 0x22222222u), (int)((w) & 0x44444444u), (int)(t & 0x22222222u)};   // 2, 1, 2, 1
-}
-// dosage: at the place of haplotype h the ALT dosage g of h's individual (haplotypes 2k, 2k + 1) times the factor that makes
-// the product with A's 0.5 / 1 equal g; the accumulators then hold sum g_i g_j exactly ("Dosage LD")
-__device__ __forceinline__ v4i expand32_b4_dosage(uint32_t w)
-{
-    const uint32_t s = w >> 1, o = w | s, n = w & s, x = w ^ s;
-    return v4i{(int)(((o << 2) & 0x44444444u) | ((n << 1) & 0x22222222u)),    // individual 2q:     2 g
-               (int)(((x << 1) & 0x22222222u) | ((n << 2) & 0x44444444u)),    //                      g
-               (int)((o & 0x44444444u) | ((n >> 1) & 0x22222222u)),           // individual 2q + 1: 2 g
-               (int)(((x >> 1) & 0x22222222u) | (n & 0x44444444u))};          //                      g
-}
-
-__device__ __forceinline__ uint32_t word_of(const uint4 &v, int w) { return w == 0 ? v.x : (w == 1 ? v.y : (w == 2 ? v.z : v.w)); }
 
 // One side's per-SNP tables: the haplotype form reads acnt / rcnt, the dosage form gstat (ldx_dosage_stats_dev).
 struct Side {
@@ -96,18 +68,6 @@ __device__ __forceinline__ d2 snp_ars(const Side &s, uint32_t x)
     }
 }
 
-// Workgroup b -> (I block ti, J slab tj).  Bands of kBandTiles I blocks; inside a band the J slab is the slow index, so that
-// consecutive workgroups (which the dispatcher deals round-robin to the XCDs) share one J slab and each XCD keeps returning to
-// the same two I blocks of the band while the J slabs stream past.
-__device__ __forceinline__ void tile_of(uint32_t b, uint32_t Ti, uint32_t Tj, uint32_t &ti, uint32_t &tj)
-{
-    const uint32_t per_band = kBandTiles * Tj;
-    const uint32_t band = b / per_band, rem = b - band * per_band;
-    const uint32_t left = Ti - band * kBandTiles, gi = left < kBandTiles ? left : kBandTiles;
-    tj = rem / gi;
-    ti = band * kBandTiles + (rem - tj * gi);
-}
-
 template <bool kHits, bool kDosage>
 __global__ void __launch_bounds__(kThreads, 2) rect_kernel(Args p)
 {
@@ -118,7 +78,7 @@ __global__ void __launch_bounds__(kThreads, 2) rect_kernel(Args p)
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t Ti = (p.si.n + kTileRows - 1u) / kTileRows, Tj = n_slabs(p.sj.n);
     uint32_t ti, tj;
-    tile_of(blockIdx.x, Ti, Tj, ti, tj);
+    tile_of<kBandTiles>(blockIdx.x, Ti, Tj, ti, tj);
     const uint32_t nblocks = p.nblocks, nchunks = 2u * nblocks;
 
     if (tid < kSlab) cstat[tid] = snp_ars<kDosage>(p.sj, tj * kSlab + tid);
@@ -221,33 +181,7 @@ __global__ void __launch_bounds__(kThreads, 2) rect_kernel(Args p)
         cs[tt] = c.y;
     }
     const double n = p.n;
-    // hits: this wave's current batch of slots (the protocol of LDX_HIT_APPENDER, ldx_mfma.hip, which ldx_area_finish_ex_dev
-    // consumes): batches of kHitBatch drawn from *n_hits, a closed batch's unused slots marked invalid, only slots below
-    // hit_cap written
-    [[maybe_unused]] uint64_t slot = 0, slot_end = 0;
-    [[maybe_unused]] auto close_batch = [&]() {
-        for (uint64_t sl = slot + lane; sl < slot_end; sl += 64u)
-            if (sl < p.hit_cap) p.hits[sl].query = 0xFFFFFFFFu;
-    };
-    [[maybe_unused]] auto append = [&](bool keep, uint32_t i, uint32_t j, float r, float s) {
-        const unsigned long long mask = __ballot(keep);
-        if (!mask) return;   // wave-uniform
-        const uint32_t cnt = __builtin_popcountll(mask);
-        if (slot + cnt > slot_end) {
-            close_batch();
-            unsigned long long base = 0;
-            if (lane == 0) base = atomicAdd(p.n_hits, (unsigned long long)kHitBatch);
-            base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-                   __builtin_amdgcn_readfirstlane((uint32_t)base);
-            slot = base;
-            slot_end = base + kHitBatch;
-        }
-        if (keep) {
-            const uint64_t sl = slot + __builtin_popcountll(mask & ((1ull << lane) - 1ull));
-            if (sl < p.hit_cap) p.hits[sl] = ldx_hit{i, j, r, s};
-        }
-        slot += cnt;
-    };
+    [[maybe_unused]] HitAppender hit{p.hits, p.hit_cap, p.n_hits, lane};
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
 #pragma unroll
@@ -268,7 +202,7 @@ __global__ void __launch_bounds__(kThreads, 2) rect_kernel(Args p)
                 }
                 if (!__any(keep[0] || keep[1] || keep[2] || keep[3])) continue;   // wave-uniform
 #pragma unroll
-                for (int tt = 0; tt < 4; ++tt) append(keep[tt], i, j0 + 32u * tt, c4[tt], s4[tt]);
+                for (int tt = 0; tt < 4; ++tt) hit.append(keep[tt], i, j0 + 32u * tt, c4[tt], s4[tt]);
             } else {
                 if (i < p.si.n) {
                     float *const row = p.out + (size_t)i * p.ld_out;
@@ -279,45 +213,7 @@ __global__ void __launch_bounds__(kThreads, 2) rect_kernel(Args p)
             }
         }
     }
-    if constexpr (kHits) close_batch();   // what is left of the wave's last batch
-}
-
-static int plane_check(const char *who, const char *arg, uint32_t n_snps, uint32_t n_hap)
-{
-    if ((uint64_t)n_slabs(n_snps) * n_chunks(n_hap) * kSlab * 16u >= (1ull << 32)) {
-        set_error("%s: %s is a bit plane of 4 GiB or more (%u SNPs x %u haplotypes)", who, arg, n_snps, n_hap);
-        return LDX_E_UNSUPPORTED;
-    }
-    return LDX_OK;
-}
-
-// the four entries' shared argument rules (each entry has checked its own pointers): everything here returns before any HIP call
-static int args_ok(const char *who, uint32_t n_i, uint32_t n_j, uint32_t n_hap, bool dosage)
-{
-    if (n_i == 0u || n_j == 0u) {
-        set_error("%s: %s is 0", who, n_i == 0u ? "n_i" : "n_j");
-        return LDX_E_ARG;
-    }
-    if (n_hap == 0u) {
-        set_error("%s: n_hap is 0", who);
-        return LDX_E_ARG;
-    }
-    if (dosage && n_hap % 2u != 0u) {
-        set_error("%s: n_hap %u is odd (dosage pairs haplotypes 2k and 2k + 1 into individuals)", who, n_hap);
-        return LDX_E_ARG;
-    }
-    if (n_hap > LDX_MAX_HAPS) {
-        set_error("%s: n_hap %u > LDX_MAX_HAPS %u", who, n_hap, LDX_MAX_HAPS);
-        return LDX_E_UNSUPPORTED;
-    }
-    if (const int rc = plane_check(who, "alt_i", n_i, n_hap)) return rc;
-    if (const int rc = plane_check(who, "alt_j", n_j, n_hap)) return rc;
-    const uint64_t tiles = (uint64_t)((n_i + kTileRows - 1u) / kTileRows) * n_slabs(n_j);
-    if (tiles >= (1ull << 31)) {
-        set_error("%s: n_i x n_j = %u x %u needs 2^31 or more tiles of 256 x 128", who, n_i, n_j);
-        return LDX_E_UNSUPPORTED;
-    }
-    return LDX_OK;
+    if constexpr (kHits) hit.close();   // what is left of the wave's last batch
 }
 
 template <bool kHits, bool kDosage>
@@ -364,26 +260,23 @@ static int hits(Args p, float r2_bound, ldx_hit *hit_buf, uint64_t hit_cap, uint
 
 using namespace ldx;
 
-#define LDX_RECT_REQUIRE(cond, ...)          \
-    do {                                     \
-        if (!(cond)) {                       \
-            ::ldx::set_error(__VA_ARGS__);   \
-            return LDX_E_ARG;                \
-        }                                    \
-    } while (0)
-// the first null pointer of a list, by name
-#define LDX_RECT_PTR(who, ptr) LDX_RECT_REQUIRE((ptr) != nullptr, "%s: %s is a null pointer", who, #ptr)
+// the four entries' shape rules: rect_args_ok (ldx_common.h) with this kernel's I block and the dosage form's parity rule
+static int args_ok(const char *who, uint32_t n_i, uint32_t n_j, uint32_t n_hap, bool dosage)
+{
+    return rect_args_ok(who, n_i, n_j, n_hap, dosage ? "dosage pairs haplotypes 2k and 2k + 1 into individuals" : nullptr,
+                        rect::kTileRows);
+}
 
 extern "C" int ldx_ld_rect_dev(const void *alt_i, const uint32_t *acnt_i, const uint32_t *rcnt_i, uint32_t n_i,
                                const void *alt_j, const uint32_t *acnt_j, const uint32_t *rcnt_j, uint32_t n_j, uint32_t n_hap,
                                float *out, size_t ld_out, void *stream)
 {
     const char *const who = "ldx_ld_rect_dev";
-    LDX_RECT_PTR(who, alt_i); LDX_RECT_PTR(who, acnt_i); LDX_RECT_PTR(who, rcnt_i);
-    LDX_RECT_PTR(who, alt_j); LDX_RECT_PTR(who, acnt_j); LDX_RECT_PTR(who, rcnt_j);
-    LDX_RECT_PTR(who, out);
-    LDX_RECT_REQUIRE(ld_out >= n_j, "%s: ld_out %zu < n_j %u", who, ld_out, n_j);
-    if (const int rc = rect::args_ok(who, n_i, n_j, n_hap, false)) return rc;
+    LDX_ARG_PTR(who, alt_i); LDX_ARG_PTR(who, acnt_i); LDX_ARG_PTR(who, rcnt_i);
+    LDX_ARG_PTR(who, alt_j); LDX_ARG_PTR(who, acnt_j); LDX_ARG_PTR(who, rcnt_j);
+    LDX_ARG_PTR(who, out);
+    LDX_ARG_REQUIRE(ld_out >= n_j, "%s: ld_out %zu < n_j %u", who, ld_out, n_j);
+    if (const int rc = args_ok(who, n_i, n_j, n_hap, false)) return rc;
     return rect::dense(rect::make_args(alt_i, acnt_i, rcnt_i, nullptr, n_i, alt_j, acnt_j, rcnt_j, nullptr, n_j, n_hap, false),
                        out, ld_out, false, (hipStream_t)stream);
 }
@@ -392,21 +285,14 @@ extern "C" int ldx_ld_rect_dosage_dev(const void *alt_i, const double *gstat_i, 
                                       const double *gstat_j, uint32_t n_j, uint32_t n_hap, float *out, size_t ld_out, void *stream)
 {
     const char *const who = "ldx_ld_rect_dosage_dev";
-    LDX_RECT_PTR(who, alt_i); LDX_RECT_PTR(who, gstat_i);
-    LDX_RECT_PTR(who, alt_j); LDX_RECT_PTR(who, gstat_j);
-    LDX_RECT_PTR(who, out);
-    LDX_RECT_REQUIRE(ld_out >= n_j, "%s: ld_out %zu < n_j %u", who, ld_out, n_j);
-    if (const int rc = rect::args_ok(who, n_i, n_j, n_hap, true)) return rc;
+    LDX_ARG_PTR(who, alt_i); LDX_ARG_PTR(who, gstat_i);
+    LDX_ARG_PTR(who, alt_j); LDX_ARG_PTR(who, gstat_j);
+    LDX_ARG_PTR(who, out);
+    LDX_ARG_REQUIRE(ld_out >= n_j, "%s: ld_out %zu < n_j %u", who, ld_out, n_j);
+    if (const int rc = args_ok(who, n_i, n_j, n_hap, true)) return rc;
     return rect::dense(rect::make_args(alt_i, nullptr, nullptr, gstat_i, n_i, alt_j, nullptr, nullptr, gstat_j, n_j, n_hap, true),
                        out, ld_out, true, (hipStream_t)stream);
 }
-
-// the hit entries' own rules: a bound > 0 (so that no zero cell passes), a buffer for every slot, a counter
-#define LDX_RECT_HIT_RULES(who)                                                                                          \
-    LDX_RECT_PTR(who, n_hits);                                                                                           \
-    LDX_RECT_REQUIRE(hits != nullptr || hit_cap == 0u, "%s: hits is a null pointer but hit_cap is %llu", who,            \
-                     (unsigned long long)hit_cap);                                                                       \
-    LDX_RECT_REQUIRE(r2_bound > 0.0f, "%s: r2_bound must be a float32 > 0 (got %g)", who, (double)r2_bound);
 
 extern "C" int ldx_ld_rect_hits_dev(const void *alt_i, const uint32_t *acnt_i, const uint32_t *rcnt_i, uint32_t n_i,
                                     const void *alt_j, const uint32_t *acnt_j, const uint32_t *rcnt_j, uint32_t n_j,
@@ -414,10 +300,10 @@ extern "C" int ldx_ld_rect_hits_dev(const void *alt_i, const uint32_t *acnt_i, c
                                     void *stream)
 {
     const char *const who = "ldx_ld_rect_hits_dev";
-    LDX_RECT_PTR(who, alt_i); LDX_RECT_PTR(who, acnt_i); LDX_RECT_PTR(who, rcnt_i);
-    LDX_RECT_PTR(who, alt_j); LDX_RECT_PTR(who, acnt_j); LDX_RECT_PTR(who, rcnt_j);
-    LDX_RECT_HIT_RULES(who)
-    if (const int rc = rect::args_ok(who, n_i, n_j, n_hap, false)) return rc;
+    LDX_ARG_PTR(who, alt_i); LDX_ARG_PTR(who, acnt_i); LDX_ARG_PTR(who, rcnt_i);
+    LDX_ARG_PTR(who, alt_j); LDX_ARG_PTR(who, acnt_j); LDX_ARG_PTR(who, rcnt_j);
+    if (const int rc = hit_args_ok(who, r2_bound, hits, hit_cap, n_hits)) return rc;
+    if (const int rc = args_ok(who, n_i, n_j, n_hap, false)) return rc;
     return rect::hits(rect::make_args(alt_i, acnt_i, rcnt_i, nullptr, n_i, alt_j, acnt_j, rcnt_j, nullptr, n_j, n_hap, false),
                       r2_bound, hits, hit_cap, n_hits, false, (hipStream_t)stream);
 }
@@ -427,10 +313,10 @@ extern "C" int ldx_ld_rect_hits_dosage_dev(const void *alt_i, const double *gsta
                                            uint64_t hit_cap, uint64_t *n_hits, void *stream)
 {
     const char *const who = "ldx_ld_rect_hits_dosage_dev";
-    LDX_RECT_PTR(who, alt_i); LDX_RECT_PTR(who, gstat_i);
-    LDX_RECT_PTR(who, alt_j); LDX_RECT_PTR(who, gstat_j);
-    LDX_RECT_HIT_RULES(who)
-    if (const int rc = rect::args_ok(who, n_i, n_j, n_hap, true)) return rc;
+    LDX_ARG_PTR(who, alt_i); LDX_ARG_PTR(who, gstat_i);
+    LDX_ARG_PTR(who, alt_j); LDX_ARG_PTR(who, gstat_j);
+    if (const int rc = hit_args_ok(who, r2_bound, hits, hit_cap, n_hits)) return rc;
+    if (const int rc = args_ok(who, n_i, n_j, n_hap, true)) return rc;
     return rect::hits(rect::make_args(alt_i, nullptr, nullptr, gstat_i, n_i, alt_j, nullptr, nullptr, gstat_j, n_j, n_hap, true),
                       r2_bound, hits, hit_cap, n_hits, true, (hipStream_t)stream);
 }

@@ -2251,6 +2251,25 @@ def _rect_panels(what: str, panel_i: PackedPanel, panel_j: Optional[PackedPanel]
     return pj
 
 
+def _rect_out(what: str, name: str, out, n_i: int, n_j: int, dev):
+    """An output matrix of ld_rect / ld_em: a float32 [n_i, >= n_j] tensor with unit column stride on ``dev``; returns
+    (tensor, row stride)."""
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != n_i
+            or out.shape[1] < n_j or (out.shape[1] > 1 and out.stride(1) != 1) or out.device != dev):
+        raise _lib.LdxError(f"{what}: {name} must be a float32 [{n_i}, >= {n_j}] tensor with unit column stride on {dev}")
+    ld = out.stride(0) if n_i > 1 else max(out.stride(0), out.shape[1])
+    if ld < n_j:
+        raise _lib.LdxError(f"{what}: {name} has row stride {ld} < n_j = {n_j}")
+    return out, ld
+
+
+def _rect_side(panel: PackedPanel, dosage: bool) -> tuple:
+    """One side's arguments of the rectangle entries: alt, gstat, n (dosage) or alt, acnt, rcnt, n."""
+    if dosage:
+        return panel.alt.data_ptr(), panel.dosage_stats()[1].data_ptr(), panel.n_snps
+    return panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), panel.n_snps
+
+
 def ld_rect(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, dosage: bool = False,
             out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Signed r of every SNP of ``panel_i`` against every SNP of ``panel_j`` (None: ``panel_i`` itself, the full square) over
@@ -2265,25 +2284,14 @@ def ld_rect(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, dosage:
     pj = _rect_panels("ld_rect", panel_i, panel_j, dosage)
     n_i, n_j = panel_i.n_snps, pj.n_snps
     if out is not None:
-        if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != n_i
-                or out.shape[1] < n_j or (out.shape[1] > 1 and out.stride(1) != 1) or out.device != panel_i.device):
-            raise _lib.LdxError(f"ld_rect: out must be a float32 [{n_i}, >= {n_j}] tensor with unit column stride on "
-                                f"{panel_i.device}")
-        ld_out = out.stride(0) if n_i > 1 else max(out.stride(0), out.shape[1])
-        if ld_out < n_j:
-            raise _lib.LdxError(f"ld_rect: out has row stride {ld_out} < n_j = {n_j}")
+        out, ld_out = _rect_out("ld_rect", "out", out, n_i, n_j, panel_i.device)
     require_gpu()
     if out is None:
         out = torch.empty((n_i, n_j), dtype=torch.float32, device=panel_i.device)
         ld_out = n_j
-    if dosage:
-        check(lib.ldx_ld_rect_dosage_dev(panel_i.alt.data_ptr(), panel_i.dosage_stats()[1].data_ptr(), n_i,
-                                         pj.alt.data_ptr(), pj.dosage_stats()[1].data_ptr(), n_j, panel_i.n_hap,
-                                         out.data_ptr(), ld_out, _stream_ptr()), "ldx_ld_rect_dosage_dev")
-    else:
-        check(lib.ldx_ld_rect_dev(panel_i.alt.data_ptr(), panel_i.acnt.data_ptr(), panel_i.rcnt.data_ptr(), n_i,
-                                  pj.alt.data_ptr(), pj.acnt.data_ptr(), pj.rcnt.data_ptr(), n_j, panel_i.n_hap,
-                                  out.data_ptr(), ld_out, _stream_ptr()), "ldx_ld_rect_dev")
+    entry = "ldx_ld_rect_dosage_dev" if dosage else "ldx_ld_rect_dev"
+    check(getattr(lib, entry)(*_rect_side(panel_i, dosage), *_rect_side(pj, dosage), panel_i.n_hap, out.data_ptr(), ld_out,
+                              _stream_ptr()), entry)
     return out[:, :n_j]
 
 
@@ -2355,17 +2363,11 @@ def ld_rect_hits(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, r2
     require_gpu()
     n_i, n_j = panel_i.n_snps, pj.n_snps
 
+    entry = "ldx_ld_rect_hits_dosage_dev" if dosage else "ldx_ld_rect_hits_dev"
+
     def launch(raw, cap, n_hits):
-        if dosage:
-            check(lib.ldx_ld_rect_hits_dosage_dev(panel_i.alt.data_ptr(), panel_i.dosage_stats()[1].data_ptr(), n_i,
-                                                  pj.alt.data_ptr(), pj.dosage_stats()[1].data_ptr(), n_j, panel_i.n_hap,
-                                                  float(bound), raw.data_ptr(), cap, n_hits.data_ptr(), _stream_ptr()),
-                  "ldx_ld_rect_hits_dosage_dev")
-        else:
-            check(lib.ldx_ld_rect_hits_dev(panel_i.alt.data_ptr(), panel_i.acnt.data_ptr(), panel_i.rcnt.data_ptr(), n_i,
-                                           pj.alt.data_ptr(), pj.acnt.data_ptr(), pj.rcnt.data_ptr(), n_j, panel_i.n_hap,
-                                           float(bound), raw.data_ptr(), cap, n_hits.data_ptr(), _stream_ptr()),
-                  "ldx_ld_rect_hits_dev")
+        check(getattr(lib, entry)(*_rect_side(panel_i, dosage), *_rect_side(pj, dosage), panel_i.n_hap, float(bound),
+                                  raw.data_ptr(), cap, n_hits.data_ptr(), _stream_ptr()), entry)
 
     offsets, hits = _rect_hits_run("ld_rect_hits", launch, n_i, n_j, panel_i.device, hit_capacity)
     return LDRectHits(offsets, hits, n_i, n_j, bound, bool(dosage))
@@ -2410,17 +2412,6 @@ class LDEm:
     dprime: Optional[torch.Tensor]
 
 
-def _em_out(what: str, name: str, out, n_i: int, n_j: int, dev):
-    """An output matrix of ld_em: checked as ld_rect checks ``out``; returns (tensor, row stride)."""
-    if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != n_i
-            or out.shape[1] < n_j or (out.shape[1] > 1 and out.stride(1) != 1) or out.device != dev):
-        raise _lib.LdxError(f"{what}: {name} must be a float32 [{n_i}, >= {n_j}] tensor with unit column stride on {dev}")
-    ld = out.stride(0) if n_i > 1 else max(out.stride(0), out.shape[1])
-    if ld < n_j:
-        raise _lib.LdxError(f"{what}: {name} has row stride {ld} < n_j = {n_j}")
-    return out, ld
-
-
 def ld_em(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, out_r=None, out_dprime=None,
           want_r: bool = True, want_dprime: bool = True) -> LDEm:
     """Unphased LD by maximum likelihood of every SNP of ``panel_i`` against every SNP of ``panel_j`` (None: ``panel_i``
@@ -2438,10 +2429,10 @@ def ld_em(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, out_r=Non
         raise _lib.LdxError("ld_em: neither r nor D' was asked for")
     lds = []
     if out_r is not None:
-        out_r, ld = _em_out("ld_em", "out_r", out_r, n_i, n_j, dev)
+        out_r, ld = _rect_out("ld_em", "out_r", out_r, n_i, n_j, dev)
         lds.append(ld)
     if out_dprime is not None:
-        out_dprime, ld = _em_out("ld_em", "out_dprime", out_dprime, n_i, n_j, dev)
+        out_dprime, ld = _rect_out("ld_em", "out_dprime", out_dprime, n_i, n_j, dev)
         lds.append(ld)
     if len(set(lds)) > 1:
         raise _lib.LdxError(f"ld_em: out_r and out_dprime differ in row stride ({lds[0]} and {lds[1]}); the entry takes one")

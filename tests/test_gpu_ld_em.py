@@ -282,42 +282,52 @@ def test_argument_rules(gpu):
     ai, ci_, aj, cj_ = pi.alt.data_ptr(), pi.acnt.data_ptr(), pj.alt.data_ptr(), pj.acnt.data_ptr()
     o, w, hp, nh = out.data_ptr(), words.data_ptr(), hits.data_ptr(), n_hits.data_ptr()
 
-    def refused(rc_, code, word):
-        assert rc_ == code, (rc_, code, word)
-        assert word in lib.ldx_last_error().decode(), (word, lib.ldx_last_error().decode())
+    who = ""
+
+    def refused(rc_, code, message):
+        """the code and the WHOLE message, word for word (callers match on the words)"""
+        assert rc_ == code, (rc_, code, message)
+        assert lib.ldx_last_error().decode() == f"{who}: {message}"
 
     E_ARG, E_UNSUPPORTED = -1, -3
     assert _lib.E_NAMES[E_ARG] == "LDX_E_ARG" and _lib.E_NAMES[E_UNSUPPORTED] == "LDX_E_UNSUPPORTED"
-    dense = lib.ldx_ld_em_rect_dev
-    refused(dense(None, ci_, n_i, aj, cj_, n_j, h, o, o, n_j, None), E_ARG, "alt_i")
-    refused(dense(ai, None, n_i, aj, cj_, n_j, h, o, o, n_j, None), E_ARG, "acnt_i")
-    refused(dense(ai, ci_, n_i, None, cj_, n_j, h, o, o, n_j, None), E_ARG, "alt_j")
-    refused(dense(ai, ci_, n_i, aj, None, n_j, h, o, o, n_j, None), E_ARG, "acnt_j")
-    refused(dense(ai, ci_, n_i, aj, cj_, n_j, h, None, None, n_j, None), E_ARG, "out_r")
-    refused(dense(ai, ci_, 0, aj, cj_, n_j, h, o, o, n_j, None), E_ARG, "n_i")
-    refused(dense(ai, ci_, n_i, aj, cj_, 0, h, o, o, n_j, None), E_ARG, "n_j")
-    refused(dense(ai, ci_, n_i, aj, cj_, n_j, h, o, o, n_j - 1, None), E_ARG, "ld_out")
-    refused(dense(ai, ci_, n_i, aj, cj_, n_j, 255, o, o, n_j, None), E_ARG, "odd")
-    refused(dense(ai, ci_, n_i, aj, cj_, n_j, 10242, o, o, n_j, None), E_UNSUPPORTED, "LDX_MAX_HAPS")
-    refused(dense(ai, ci_, 1 << 22, aj, cj_, n_j, 10240, o, o, n_j, None), E_UNSUPPORTED, "alt_i")   # a 5 GiB plane
-    refused(dense(ai, ci_, n_i, aj, cj_, 1 << 22, 10240, o, o, 1 << 22, None), E_UNSUPPORTED, "alt_j")
-    hit = lib.ldx_ld_em_rect_hits_dev
-    refused(hit(ai, ci_, n_i, aj, cj_, n_j, h, 0.0, hp, 256, nh, None), E_ARG, "r2_bound")
-    refused(hit(ai, ci_, n_i, aj, cj_, n_j, h, float("nan"), hp, 256, nh, None), E_ARG, "r2_bound")
-    refused(hit(ai, ci_, n_i, aj, cj_, n_j, h, 0.2, None, 256, nh, None), E_ARG, "hits")
-    refused(hit(ai, ci_, n_i, aj, cj_, n_j, h, 0.2, hp, 256, None, None), E_ARG, "n_hits")
-    refused(hit(ai, ci_, n_i, aj, cj_, n_j, 255, 0.2, hp, 256, nh, None), E_ARG, "odd")
-    cnt = lib.ldx_ld_em_counts_dev
-    refused(cnt(None, n_i, aj, n_j, h, w, w, n_j, None), E_ARG, "alt_i")
-    refused(cnt(ai, n_i, aj, n_j, h, None, w, n_j, None), E_ARG, "S")
-    refused(cnt(ai, n_i, aj, n_j, h, w, None, n_j, None), E_ARG, "H")
-    refused(cnt(ai, n_i, aj, n_j, h, w, w, n_j - 1, None), E_ARG, "ld")
-    refused(cnt(ai, n_i, aj, n_j, 10242, w, w, n_j, None), E_UNSUPPORTED, "LDX_MAX_HAPS")
-    lst = lib.ldx_ld_em_from_counts_dev
-    refused(lst(3, 4, None, w, w, w, o, o, None, None), E_ARG, "a1")
-    refused(lst(3, 0, w, w, w, w, o, o, None, None), E_ARG, "m")
-    refused(lst(0, 4, w, w, w, w, o, o, None, None), E_ARG, "n_ind")
-    refused(lst(5121, 4, w, w, w, w, o, o, None, None), E_UNSUPPORTED, "n_ind")
+    null, odd = "{} is a null pointer", "n_hap 255 is odd (haplotypes 2k and 2k + 1 are the two alleles of individual k)"
+    plane = "{} is a bit plane of 4 GiB or more (4194304 SNPs x 10240 haplotypes)"
+    bound = "r2_bound must be a float32 > 0 (got {})"
+    dense, who = lib.ldx_ld_em_rect_dev, "ldx_ld_em_rect_dev"
+    refused(dense(None, ci_, n_i, aj, cj_, n_j, h, o, o, n_j, None), E_ARG, null.format("alt_i"))
+    refused(dense(ai, None, n_i, aj, cj_, n_j, h, o, o, n_j, None), E_ARG, null.format("acnt_i"))
+    refused(dense(ai, ci_, n_i, None, cj_, n_j, h, o, o, n_j, None), E_ARG, null.format("alt_j"))
+    refused(dense(ai, ci_, n_i, aj, None, n_j, h, o, o, n_j, None), E_ARG, null.format("acnt_j"))
+    refused(dense(ai, ci_, n_i, aj, cj_, n_j, h, None, None, n_j, None), E_ARG, "out_r and out_dprime are both null pointers")
+    refused(dense(ai, ci_, 0, aj, cj_, n_j, h, o, o, n_j, None), E_ARG, "n_i is 0")
+    refused(dense(ai, ci_, n_i, aj, cj_, 0, h, o, o, n_j, None), E_ARG, "n_j is 0")
+    refused(dense(ai, ci_, n_i, aj, cj_, n_j, h, o, o, n_j - 1, None), E_ARG, "ld_out 256 < n_j 257")
+    refused(dense(ai, ci_, n_i, aj, cj_, n_j, 255, o, o, n_j, None), E_ARG, odd)
+    refused(dense(ai, ci_, n_i, aj, cj_, n_j, 10242, o, o, n_j, None), E_UNSUPPORTED, "n_hap 10242 > LDX_MAX_HAPS 10240")
+    refused(dense(ai, ci_, 1 << 22, aj, cj_, n_j, 10240, o, o, n_j, None), E_UNSUPPORTED, plane.format("alt_i"))   # a 5 GiB plane
+    refused(dense(ai, ci_, n_i, aj, cj_, 1 << 22, 10240, o, o, 1 << 22, None), E_UNSUPPORTED, plane.format("alt_j"))
+    refused(dense(ai, ci_, 1 << 26, aj, cj_, 1 << 26, 64, o, o, 1 << 26, None), E_UNSUPPORTED,
+            "n_i x n_j = 67108864 x 67108864 needs 2^31 or more tiles of 128 x 128")
+    refused(dense(ai, ci_, 0, aj, cj_, 0, 255, o, o, n_j, None), E_ARG, "n_i is 0")   # the first broken rule speaks
+    hit, who = lib.ldx_ld_em_rect_hits_dev, "ldx_ld_em_rect_hits_dev"
+    refused(hit(ai, ci_, n_i, aj, cj_, n_j, h, 0.0, hp, 256, nh, None), E_ARG, bound.format("0"))
+    refused(hit(ai, ci_, n_i, aj, cj_, n_j, h, float("nan"), hp, 256, nh, None), E_ARG, bound.format("nan"))
+    refused(hit(ai, ci_, n_i, aj, cj_, n_j, h, 0.2, None, 256, nh, None), E_ARG, "hits is a null pointer but hit_cap is 256")
+    refused(hit(ai, ci_, n_i, aj, cj_, n_j, h, 0.2, hp, 256, None, None), E_ARG, null.format("n_hits"))
+    refused(hit(ai, ci_, n_i, aj, cj_, n_j, 255, 0.2, hp, 256, nh, None), E_ARG, odd)
+    refused(hit(ai, ci_, n_i, aj, cj_, n_j, 255, 0.0, None, 256, None, None), E_ARG, null.format("n_hits"))
+    cnt, who = lib.ldx_ld_em_counts_dev, "ldx_ld_em_counts_dev"
+    refused(cnt(None, n_i, aj, n_j, h, w, w, n_j, None), E_ARG, null.format("alt_i"))
+    refused(cnt(ai, n_i, aj, n_j, h, None, w, n_j, None), E_ARG, null.format("S"))
+    refused(cnt(ai, n_i, aj, n_j, h, w, None, n_j, None), E_ARG, null.format("H"))
+    refused(cnt(ai, n_i, aj, n_j, h, w, w, n_j - 1, None), E_ARG, "ld 256 < n_j 257")
+    refused(cnt(ai, n_i, aj, n_j, 10242, w, w, n_j, None), E_UNSUPPORTED, "n_hap 10242 > LDX_MAX_HAPS 10240")
+    lst, who = lib.ldx_ld_em_from_counts_dev, "ldx_ld_em_from_counts_dev"
+    refused(lst(3, 4, None, w, w, w, o, o, None, None), E_ARG, null.format("a1"))
+    refused(lst(3, 0, w, w, w, w, o, o, None, None), E_ARG, "m is 0")
+    refused(lst(0, 4, w, w, w, w, o, o, None, None), E_ARG, "n_ind is 0")
+    refused(lst(5121, 4, w, w, w, w, o, o, None, None), E_UNSUPPORTED, "n_ind 5121 > LDX_MAX_HAPS / 2 = 5120")
     # the Python layer's own rules
     from ld_tools_amd import PackedPanel, ops
     odd = PackedPanel.from_codes(rc.random_codes(4, 255, np.random.default_rng(1)))

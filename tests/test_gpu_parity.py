@@ -1564,6 +1564,37 @@ def test_area_repeated_calls_replay_a_graph_and_stay_correct(gpu):
     assert len(small) > 4096 and same(small, again)
 
 
+def test_area_popcount_scan_from_a_hit_buffer_that_is_too_small(gpu):
+    """The popcount scan's hit appender (HitAppender, csrc/ldx_common.h) with far fewer slots than hits: waves close batches
+    and draw new ones, most of them at or beyond the capacity, where nothing may be stored; the retry then takes the reserved
+    count.  300 SNPs x 128 haplotypes, every row a query, every other row in its window: 89 700 pairs, of which well over
+    half have a rounded r^2 >= 0.002 (r^2 of independent rows is about 1 / 128), against 4096 slots.  The result equals, field
+    by field, the same call with ample capacity and the FP4 band's."""
+    import torch
+    from ld_tools_amd import PackedPanel, ld_area, ops, synth
+
+    n, h, cap = 300, 128, 4096
+    p = PackedPanel.from_codes(synth.synth_codes_device(n, h, seed=33))
+    pos = synth.synth_positions(n, step=500)
+    args = (p, pos, None, 500 * n, "r_square", 0.002)
+    old = ops.get_area_path()
+    try:
+        ops.set_area_path("popcount")
+        small = ld_area(*args, hit_capacity=cap, use_graph=False)
+        ample = ld_area(*args, hit_capacity=1 << 20, use_graph=False)
+        ops.set_area_path("fp4")
+        band = ld_area(*args, hit_capacity=1 << 20, use_graph=False)
+    finally:
+        ops.set_area_path(old)
+    assert len(small) > 4 * cap, len(small)                                  # the precondition: several times the buffer
+    assert small.band_passes is None and band.band_passes > 0               # the scan, and the band
+    for other in (ample, band):
+        assert len(small) == len(other)
+        assert torch.equal(small.query, other.query) and torch.equal(small.oppos, other.oppos)
+        assert torch.equal(small.ld32.view(torch.int32), other.ld32.view(torch.int32))
+        assert torch.equal(small.offsets, other.offsets)
+
+
 def test_planes_of_4gib_or_more_use_the_popcount_kernels(gpu):
     """The matrix kernels address the bit plane with 32-bit lane offsets: a plane of 4 GiB or more (3.4 M SNPs x 10 240
     haplotypes here, zero planes) is LDX_E_UNSUPPORTED on an explicit matrix-pipe path and runs the popcount kernel on auto."""

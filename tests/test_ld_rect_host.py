@@ -67,6 +67,13 @@ def test_entries_refuse_bad_arguments_before_any_launch():
                n_hits=ptr):
         return lib.ldx_ld_rect_hits_dosage_dev(alt_i, gstat_i, n_i, alt_j, gstat_j, n_j, n_hap, bound, buf, cap, n_hits, None)
 
+    who = {dense: "ldx_ld_rect_dev", dense_d: "ldx_ld_rect_dosage_dev", hits: "ldx_ld_rect_hits_dev",
+           hits_d: "ldx_ld_rect_hits_dosage_dev"}
+
+    def said(fn, message):
+        """the WHOLE message, word for word (callers match on the words)"""
+        return err() == f"{who[fn]}: {message}"
+
     # null pointers, each named
     for fn, names in ((dense, ("alt_i", "acnt_i", "rcnt_i", "alt_j", "acnt_j", "rcnt_j", "out")),
                       (dense_d, ("alt_i", "gstat_i", "alt_j", "gstat_j", "out")),
@@ -74,25 +81,37 @@ def test_entries_refuse_bad_arguments_before_any_launch():
                       (hits_d, ("alt_i", "gstat_i", "alt_j", "gstat_j", "n_hits"))):
         for name in names:
             assert fn(**{name: None}) == E_ARG, (fn.__name__, name)
-            assert name in err() and "null" in err(), err()
+            assert said(fn, f"{name} is a null pointer"), err()
     for fn in (hits, hits_d):
-        assert fn(buf=None) == E_ARG and "hits" in err()
-        for bad in (0.0, -0.5, float("nan")):
-            assert fn(bound=bad) == E_ARG and "r2_bound" in err()
+        assert fn(buf=None) == E_ARG and said(fn, "hits is a null pointer but hit_cap is 256"), err()
+        for bad, shown in ((0.0, "0"), (-0.5, "-0.5"), (float("nan"), "nan")):
+            assert fn(bound=bad) == E_ARG and said(fn, f"r2_bound must be a float32 > 0 (got {shown})"), err()
+        assert fn(bound=0.0, buf=None, n_hits=None, n_i=0) == E_ARG and said(fn, "n_hits is a null pointer")   # the first rule
+        assert fn(bound=0.0, buf=None, n_i=0) == E_ARG and said(fn, "hits is a null pointer but hit_cap is 256")
+        assert fn(bound=0.0, n_i=0) == E_ARG and said(fn, "r2_bound must be a float32 > 0 (got 0)")
     # shapes
+    plane = "{} is a bit plane of 4 GiB or more (16777216 SNPs x 10240 haplotypes)"
     for fn in (dense, dense_d, hits, hits_d):
-        assert fn(n_i=0) == E_ARG and "n_i" in err()
-        assert fn(n_j=0) == E_ARG and "n_j" in err()
-        assert fn(n_hap=_lib.MAX_HAPS + 2) == E_UNSUPPORTED and "n_hap" in err() and "LDX_MAX_HAPS" in err()
-        assert fn(n_i=1 << 24, n_hap=10240) == E_UNSUPPORTED and "alt_i" in err() and "4 GiB" in err()
-        assert fn(n_j=1 << 24, n_hap=10240, **({"ld_out": 1 << 24} if fn in (dense, dense_d) else {})) == E_UNSUPPORTED
-        assert "alt_j" in err() and "4 GiB" in err()
+        wide = {"ld_out": 1 << 26} if fn in (dense, dense_d) else {}
+        assert fn(n_i=0) == E_ARG and said(fn, "n_i is 0"), err()
+        assert fn(n_j=0) == E_ARG and said(fn, "n_j is 0"), err()
+        assert fn(n_i=0, n_j=0, n_hap=0) == E_ARG and said(fn, "n_i is 0"), err()
+        assert fn(n_hap=0) == E_ARG and said(fn, "n_hap is 0"), err()
+        assert fn(n_hap=_lib.MAX_HAPS + 2) == E_UNSUPPORTED and said(fn, "n_hap 10242 > LDX_MAX_HAPS 10240"), err()
+        assert fn(n_i=1 << 24, n_hap=10240) == E_UNSUPPORTED and said(fn, plane.format("alt_i")), err()
+        assert fn(n_j=1 << 24, n_hap=10240, **wide) == E_UNSUPPORTED and said(fn, plane.format("alt_j")), err()
+        assert fn(n_i=1 << 24, n_j=1 << 24, n_hap=10240, **wide) == E_UNSUPPORTED and said(fn, plane.format("alt_i")), err()
+        assert fn(n_i=1 << 26, n_j=1 << 26, n_hap=64, **wide) == E_UNSUPPORTED, err()
+        assert said(fn, "n_i x n_j = 67108864 x 67108864 needs 2^31 or more tiles of 256 x 128"), err()
     for fn in (dense, dense_d):
-        assert fn(ld_out=49) == E_ARG and "ld_out" in err()
+        assert fn(ld_out=49) == E_ARG and said(fn, "ld_out 49 < n_j 50"), err()
+        assert fn(ld_out=49, n_i=0) == E_ARG and said(fn, "ld_out 49 < n_j 50"), err()
     for fn in (dense_d, hits_d):
-        assert fn(n_hap=63) == E_ARG and "n_hap" in err() and "odd" in err()
+        for n_hap in (63, _lib.MAX_HAPS + 1):                                # (parity speaks before the limit)
+            assert fn(n_hap=n_hap) == E_ARG, err()
+            assert said(fn, f"n_hap {n_hap} is odd (dosage pairs haplotypes 2k and 2k + 1 into individuals)"), err()
     for fn in (dense, hits):
-        assert fn(n_hap=63, n_i=0) == E_ARG                                 # (an odd n_hap is fine for haplotype r)
+        assert fn(n_hap=63, n_i=0) == E_ARG and said(fn, "n_i is 0")        # (an odd n_hap is fine for haplotype r)
 
 
 def test_python_argument_rules_come_before_the_device():
