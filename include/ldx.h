@@ -722,6 +722,49 @@ int ldx_ld_rect_hits_dosage_dev(const void *alt_i, const double *gstat_i, uint32
                                 uint32_t n_hap, float r2_bound, ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits,
                                 void *stream);
 
+/* ---- pairwise-complete LD: the rectangle's r over the observations called at BOTH SNPs -----------------------------------
+ * The entries above keep every haplotype in n and leave a missing call out of the allele counts (the dosage forms count it as
+ * REF).  PLINK --r2, Haploview and the LDpred / bigsnpr readers compute each pair's correlation over the samples called at both
+ * variants instead.  These entries do that for the rectangle; they take BOTH bit planes of a panel (called = alt | ref) and its
+ * acnt / rcnt tables.  For row x of I and row y of J over the same n_hap haplotypes:
+ *
+ * haplotype form (dosage = 0).  Haplotype h is jointly called when both codes are 0 or 1.
+ *     n = #{h jointly called}    a = #{x = 1 and y called}    b = #{x called and y = 1}    c = #{x = 1 and y = 1}       (<= 10 240)
+ *     num = fma(c, n, -(a b))    v_x = a (n - a)    v_y = b (n - b)
+ * dosage form (dosage != 0; n_hap even, individual k owns haplotypes 2k and 2k + 1).  An individual is called at a SNP when
+ * BOTH of its codes are 0 or 1 -- a half-missing genotype is missing (PLINK's rule, not the dosage entries' missing = REF);
+ * g = the ALT dosage of a called individual.  Over the individuals called at both SNPs:
+ *     N    A = sum g_x    B = sum g_y    HA = #{g_x = 2}    HB = #{g_y = 2}    S = sum g_x g_y
+ *     num = fma(S, N, -(A B))    v_x = N (A + 2 HA) - A^2    v_y = N (B + 2 HB) - B^2
+ * the cell, in fp64 with every operation rounded as written (r32_cell's arithmetic on the pair's own counts):
+ *     rs = 1 / sqrt(v) (0 for v = 0);   cell = (float)(num (rs_x rs_y));   -0.0f where either variance is 0 (n = 0 and N = 0
+ *     included);   +0.0f exactly where num = 0.
+ * Consequences: a pair of rows without a missing code gives the ldx_ld_rect_dev (ldx_ld_rect_dosage_dev) cell bit for bit;
+ * every cell is within 4 float32 ulps of the exact r of its counts; the cell is a function of the integers alone, symmetric in
+ * the two SNPs: swapped sides give the transpose, permuted individuals (dosage form: rephased genotypes too) the same bits.
+ * The integers come from the FP4 matrix cores (ldx_pwc.hip); a tile none of whose SNPs has a missing code counts c (S) alone
+ * and reads the rest from acnt -- through the same cell functions, so a cell does not depend on its tile.  No workspace.
+ *
+ * ldx_ld_rect_pw_dev: out[i * ld_out + j] = the cell for i < n_i, j < n_j; exactly these words are written.
+ * ldx_ld_rect_pw_hits_dev: ldx_ld_rect_hits_dev's records, rule (ONE float32 multiply against r2_bound > 0; -0.0f never a hit),
+ *   slots and overflow protocol; ldx_area_finish_ex_dev(n_snps = n_i, counts_ready = 0) finishes.
+ * ldx_ld_rect_pw_counts_dev: counts[(s * n_i + i) * ld + j] = integer s of the pair as uint32, s in the order n a b c (4 sets)
+ *   or N A B HA HB S (6 sets): what the K loop produced, before any float.
+ *
+ * Argument rules and codes are ldx_ld_rect_dev's, checked before any HIP call: a null pointer, n_i or n_j = 0, ld < n_j,
+ * r2_bound not > 0, an odd n_hap with dosage = LDX_E_ARG; n_hap > LDX_MAX_HAPS or a bit plane of 4 GiB or more =
+ * LDX_E_UNSUPPORTED.  All calls only enqueue work on `stream`. */
+int ldx_ld_rect_pw_dev(const void *alt_i, const void *ref_i, const uint32_t *acnt_i, const uint32_t *rcnt_i, uint32_t n_i,
+                       const void *alt_j, const void *ref_j, const uint32_t *acnt_j, const uint32_t *rcnt_j, uint32_t n_j,
+                       uint32_t n_hap, int dosage, float *out, size_t ld_out, void *stream);
+int ldx_ld_rect_pw_hits_dev(const void *alt_i, const void *ref_i, const uint32_t *acnt_i, const uint32_t *rcnt_i, uint32_t n_i,
+                            const void *alt_j, const void *ref_j, const uint32_t *acnt_j, const uint32_t *rcnt_j, uint32_t n_j,
+                            uint32_t n_hap, int dosage, float r2_bound, ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits,
+                            void *stream);
+int ldx_ld_rect_pw_counts_dev(const void *alt_i, const void *ref_i, const uint32_t *acnt_i, const uint32_t *rcnt_i, uint32_t n_i,
+                              const void *alt_j, const void *ref_j, const uint32_t *acnt_j, const uint32_t *rcnt_j, uint32_t n_j,
+                              uint32_t n_hap, int dosage, uint32_t *counts, size_t ld, void *stream);
+
 /* ---- unphased LD by EM: maximum-likelihood r and D' of every row of one SNP set against every row of another ---------------
  * The dosage entries above give Weir's composite r of the genotypes.  These give what PLINK --r2 dprime / --ld and Haploview
  * compute from unphased genotypes: the maximum-likelihood two-locus haplotype frequency, the double heterozygotes resolved by

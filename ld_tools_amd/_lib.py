@@ -168,6 +168,10 @@ SIGNATURES = {
     "ldx_ld_rect_dosage_dev": (_int, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _sz, _vp]),
     "ldx_ld_rect_hits_dev": (_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, C.c_float, _vp, _u64, _vp, _vp]),
     "ldx_ld_rect_hits_dosage_dev": (_int, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, C.c_float, _vp, _u64, _vp, _vp]),
+    "ldx_ld_rect_pw_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _int, _vp, _sz, _vp]),
+    "ldx_ld_rect_pw_hits_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _int, C.c_float, _vp, _u64,
+                                       _vp, _vp]),
+    "ldx_ld_rect_pw_counts_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _int, _vp, _sz, _vp]),
     "ldx_ld_em_rect_dev": (_int, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _sz, _vp]),
     "ldx_ld_em_rect_hits_dev": (_int, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, C.c_float, _vp, _u64, _vp, _vp]),
     "ldx_ld_em_counts_dev": (_int, [_vp, _u32, _vp, _u32, _u32, _vp, _vp, _sz, _vp]),

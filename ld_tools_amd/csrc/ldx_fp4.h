@@ -1,5 +1,5 @@
 // What the FP4 counting kernels share (triangle_mfma_kernel of ldx_mfma.hip, rect_kernel of ldx_rect.hip, em_kernel of
-// ldx_em.hip): the operand encoding -- the exactness argument of the whole library, written once -- and the rectangle walk.
+// ldx_em.hip, pwc_kernel of ldx_pwc.hip): the operand encoding -- the exactness argument of the whole library, written once -- and the rectangle walk.
 #pragma once
 
 #include "ldx_common.h"
@@ -43,6 +43,43 @@ __device__ __forceinline__ v4i expand32_b4_dosage(uint32_t w)
                (int)(((x << 1) & 0x22222222u) | ((n << 2) & 0x44444444u)),    //                      g
                (int)((o & 0x44444444u) | ((n >> 1) & 0x22222222u)),           // individual 2q + 1: 2 g
                (int)(((x >> 1) & 0x22222222u) | (n & 0x44444444u))};          //                      g
+}
+
+// Pairwise-complete dosage LD (ldx_pwc.hip; DESIGN.md, "Pairwise-complete LD"): counts over the individuals CALLED at both SNPs
+// need per-INDIVIDUAL operands.  An individual's bit -- called q, heterozygous t, homozygous ALT n -- lives on its EVEN
+// haplotype slot, which is registers 0 and 2 of an operand (slots 4k and 4k + 2 of the word); registers 1 and 3, the odd
+// slots, are then free and carry a second per-individual bit that only meets a partner parked on the odd slots too.
+//   A side (0.5 / 1):  expand32_a4_dosage  g / 2 on the even slot (het 0001 = 0.5, hom 0010 = 1);
+//                      even_a4(z)          0.5 where z has the individual's bit (em_kernel's het_a4, as four registers);
+//                      odd_a4(z)           1 on the ODD slot of the individual (0010), nothing on the even one.
+//   B side (2 / 4 / 1): expand32_b4_dosage  2 g on the even slot (and g on the odd one, which the three A operands above
+//                                          multiply by 0);
+//                      expand32_b4_called_hom(q, n)  2 on the even slot where q (0100), 1 on the odd slot where n (0010).
+// Every product is g_x g_y, g, or 1 -- an integer <= 4 -- and every sum at most 4 N <= 20 480 < 2^24: exact in any order.  The
+// words that enter are made by ind_called and by masking ALT with both slots of it, so that a half-missing genotype is missing.
+__device__ __forceinline__ uint32_t ind_called(uint32_t alt, uint32_t ref)
+{
+    const uint32_t c = alt | ref;
+    return c & (c >> 1) & 0x55555555u;
+}
+__device__ __forceinline__ v4i even_a4(uint32_t z)
+{
+    return v4i{(int)(z & 0x11111111u), 0, (int)((z >> 2) & 0x11111111u), 0};   // 0.5, -, 0.5, -
+}
+__device__ __forceinline__ v4i odd_a4(uint32_t z)
+{
+    return v4i{0, (int)((z << 1) & 0x22222222u), 0, (int)((z >> 1) & 0x22222222u)};   // -, 1, -, 1
+}
+__device__ __forceinline__ v4i expand32_a4_dosage(uint32_t w)
+{
+    const uint32_t s = w >> 1, n = w & s, x = w ^ s;   // every mask picks a bit that comes from an even position
+    return v4i{(int)((x & 0x11111111u) | ((n << 1) & 0x22222222u)), 0,           // individual 2q:     g / 2
+               (int)(((x >> 2) & 0x11111111u) | ((n >> 1) & 0x22222222u)), 0};   // individual 2q + 1: g / 2
+}
+__device__ __forceinline__ v4i expand32_b4_called_hom(uint32_t q, uint32_t n)
+{
+    return v4i{(int)((q << 2) & 0x44444444u), (int)((n << 1) & 0x22222222u),     // individual 2q:     2 q, n
+               (int)(q & 0x44444444u), (int)((n >> 1) & 0x22222222u)};           // individual 2q + 1: 2 q, n
 }
 
 // word w of the 16 bytes (128 haplotypes) a lane holds of one row and chunk

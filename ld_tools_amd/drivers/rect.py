@@ -41,6 +41,7 @@ class RectMatrix:
     cols: RectSide
     dosage: bool
     r: object                         # float32 [n_i, n_j] device tensor: r[a, b] = signed r of rows' variant a and cols' variant b
+    missing: object = None            # None, or "pairwise": r over the calls present at both variants (ops.ld_rect)
 
 
 def carried_samples(rec, sample_names: Sequence[str]) -> tuple:
@@ -88,17 +89,20 @@ def read_sides(vcf, chrom_i, rows_i, chrom_j, rows_j, sample_names: Sequence[str
 
 
 def rect_matrix(vcf, chrom_i, rows_i: Sequence[Sequence], chrom_j, rows_j: Sequence[Sequence], sample_names: Sequence[str],
-                dosage: bool = False) -> RectMatrix:
+                dosage: bool = False, missing=None) -> RectMatrix:
     """Signed r of the variants ``rows_i`` of chromosome ``chrom_i`` against the variants ``rows_j`` of ``chrom_j`` (VCF rows
     [pos, rsID], as for ``r_matrix``; the same chromosome twice for two rsID lists).  ``dosage``: genotype-dosage r over the
-    samples (a missing call counts as REF; even haplotype count).  Mixed ploidy and samples that differ between the two sides
-    are out of scope: LdxError."""
+    samples (a missing call counts as REF; even haplotype count).  ``missing="pairwise"``: every pair over the calls present
+    at both variants (``ops.ld_rect``; missing and multi-allelic calls are left out pair by pair, as PLINK --r2 does).  Mixed
+    ploidy and samples that differ between the two sides are out of scope: LdxError."""
+    if missing is not None and missing != "pairwise":
+        raise LdxError(f'rect_matrix: missing must be None or "pairwise", got {missing!r}')
     side_i, side_j = read_sides(vcf, chrom_i, rows_i, chrom_j, rows_j, sample_names)
     pi, pj = PackedPanel.from_codes(side_i.codes), PackedPanel.from_codes(side_j.codes)
-    r = ld_rect(pi, pj, dosage=dosage)
+    r = ld_rect(pi, pj, dosage=dosage, missing=missing)
     side_i.alt_freqs = pi.alt_freq4().cpu().numpy().tolist()
     side_j.alt_freqs = pj.alt_freq4().cpu().numpy().tolist()
-    return RectMatrix(side_i, side_j, bool(dosage), r)
+    return RectMatrix(side_i, side_j, bool(dosage), r, missing)
 
 
 def write_variants(path: str, side: RectSide) -> None:

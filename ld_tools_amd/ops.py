@@ -2270,8 +2270,23 @@ def _rect_side(panel: PackedPanel, dosage: bool) -> tuple:
     return panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), panel.n_snps
 
 
+def _rect_missing(what: str, missing) -> bool:
+    """The rectangle's ``missing`` argument: None (the operator's own rule) or "pairwise" (pairwise-complete); True for the
+    latter.  Anything else is refused before the device is touched."""
+    if missing is None:
+        return False
+    if isinstance(missing, str) and missing == "pairwise":
+        return True
+    raise _lib.LdxError(f'{what}: missing must be None or "pairwise", got {missing!r}')
+
+
+def _pw_side(panel: PackedPanel) -> tuple:
+    """One side's arguments of the pairwise-complete entries: alt, ref, acnt, rcnt, n."""
+    return panel.alt.data_ptr(), panel.ref.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), panel.n_snps
+
+
 def ld_rect(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, dosage: bool = False,
-            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+            out: Optional[torch.Tensor] = None, missing: Optional[str] = None) -> torch.Tensor:
     """Signed r of every SNP of ``panel_i`` against every SNP of ``panel_j`` (None: ``panel_i`` itself, the full square) over
     the same haplotypes: float32 [n_i, n_j] on the device (include/ldx.h, ldx_ld_rect_dev).  Cell (i, j) is the r32 cell of
     ld_triangle(fmt="r32") for those two SNPs bit for bit -- -0.0f on a degenerate pair, +0.0f iff the covariance is 0 --
@@ -2280,7 +2295,13 @@ def ld_rect(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, dosage:
 
     ``dosage=True``: the genotype-dosage r of ld_triangle(fmt="r32", dosage=True) (even n_hap).  ``out``: a float32 device
     tensor [n_i, >= n_j] with unit column stride to write into; its row stride is taken as it is and the columns beyond n_j
-    are left untouched.  The view out[:, :n_j] is returned."""
+    are left untouched.  The view out[:, :n_j] is returned.
+
+    ``missing="pairwise"``: pairwise-complete r (include/ldx.h, "pairwise-complete LD"; ldx_ld_rect_pw_dev) -- every pair over
+    the haplotypes (``dosage``: the individuals, a half-missing genotype being missing) called at both SNPs, as PLINK --r2
+    does.  A pair of rows without missing codes gives the ``missing=None`` cell bit for bit.  None: the call as it always was
+    (n is every haplotype and the allele counts leave a hole out; ``dosage`` counts it as REF)."""
+    pairwise = _rect_missing("ld_rect", missing)
     pj = _rect_panels("ld_rect", panel_i, panel_j, dosage)
     n_i, n_j = panel_i.n_snps, pj.n_snps
     if out is not None:
@@ -2289,6 +2310,10 @@ def ld_rect(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, dosage:
     if out is None:
         out = torch.empty((n_i, n_j), dtype=torch.float32, device=panel_i.device)
         ld_out = n_j
+    if pairwise:
+        check(lib.ldx_ld_rect_pw_dev(*_pw_side(panel_i), *_pw_side(pj), panel_i.n_hap, int(bool(dosage)), out.data_ptr(),
+                                     ld_out, _stream_ptr()), "ldx_ld_rect_pw_dev")
+        return out[:, :n_j]
     entry = "ldx_ld_rect_dosage_dev" if dosage else "ldx_ld_rect_dev"
     check(getattr(lib, entry)(*_rect_side(panel_i, dosage), *_rect_side(pj, dosage), panel_i.n_hap, out.data_ptr(), ld_out,
                               _stream_ptr()), entry)
@@ -2322,6 +2347,7 @@ class LDRectHits:
     bound: np.float32       # the float32 bound on s (r2_bound)
     dosage: bool = False
     em: bool = False        # ld_em_hits: r is the EM r and column 3 of ``hits`` the D' cell instead of s
+    missing: Optional[str] = None   # "pairwise": the cells are ld_rect(missing="pairwise")'s
 
     @property
     def j(self) -> torch.Tensor:
@@ -2350,14 +2376,15 @@ class LDRectHits:
 
 
 def ld_rect_hits(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, r2: float = 0.2, strict: bool = False,
-                 dosage: bool = False, hit_capacity: Optional[int] = None) -> LDRectHits:
+                 dosage: bool = False, hit_capacity: Optional[int] = None, missing: Optional[str] = None) -> LDRectHits:
     """The pairs (row i of ``panel_i``, row j of ``panel_j``) with r^2 >= ``r2`` (``strict``: r^2 > r2), where r is the
     ld_rect cell bit for bit and r^2 one float32 multiply -- ld_neighbors' rule without a window, once per (i, j)
     (include/ldx.h, ldx_ld_rect_hits_dev + ldx_area_finish_ex_dev).  Degenerate pairs are never hits.
 
     ``hit_capacity``: record slots to start with (16 bytes each; default max(2^20, 32 (n_i + n_j))); a call that needs more
     runs again at the count the first run reserved plus ld_neighbors' margin, at most four times.  The host reads the
-    record count once per run."""
+    record count once per run.  ``missing="pairwise"``: r is the ld_rect(missing="pairwise") cell (ldx_ld_rect_pw_hits_dev)."""
+    pairwise = _rect_missing("ld_rect_hits", missing)
     pj = _rect_panels("ld_rect_hits", panel_i, panel_j, dosage)
     bound = r2_bound(r2, strict)
     require_gpu()
@@ -2366,11 +2393,81 @@ def ld_rect_hits(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, r2
     entry = "ldx_ld_rect_hits_dosage_dev" if dosage else "ldx_ld_rect_hits_dev"
 
     def launch(raw, cap, n_hits):
+        if pairwise:
+            check(lib.ldx_ld_rect_pw_hits_dev(*_pw_side(panel_i), *_pw_side(pj), panel_i.n_hap, int(bool(dosage)), float(bound),
+                                              raw.data_ptr(), cap, n_hits.data_ptr(), _stream_ptr()), "ldx_ld_rect_pw_hits_dev")
+            return
         check(getattr(lib, entry)(*_rect_side(panel_i, dosage), *_rect_side(pj, dosage), panel_i.n_hap, float(bound),
                                   raw.data_ptr(), cap, n_hits.data_ptr(), _stream_ptr()), entry)
 
     offsets, hits = _rect_hits_run("ld_rect_hits", launch, n_i, n_j, panel_i.device, hit_capacity)
-    return LDRectHits(offsets, hits, n_i, n_j, bound, bool(dosage))
+    return LDRectHits(offsets, hits, n_i, n_j, bound, bool(dosage), missing=missing)
+
+
+PAIRWISE_COUNTS = {False: ("n", "a", "b", "c"), True: ("N", "A", "B", "HA", "HB", "S")}   # the order of include/ldx.h
+
+
+def ld_rect_counts(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, dosage: bool = False) -> torch.Tensor:
+    """The integers of every pair of pairwise-complete LD as the kernel's K loop produced them, before any float: uint32
+    [4, n_i, n_j] (n, a, b, c) or, ``dosage``, [6, n_i, n_j] (N, A, B, HA, HB, S) on the device (include/ldx.h,
+    ldx_ld_rect_pw_counts_dev)."""
+    pj = _rect_panels("ld_rect_counts", panel_i, panel_j, dosage)
+    require_gpu()
+    n_i, n_j = panel_i.n_snps, pj.n_snps
+    out = torch.empty((len(PAIRWISE_COUNTS[bool(dosage)]), n_i, n_j), dtype=torch.int32, device=panel_i.device)
+    check(lib.ldx_ld_rect_pw_counts_dev(*_pw_side(panel_i), *_pw_side(pj), panel_i.n_hap, int(bool(dosage)), out.data_ptr(), n_j,
+                                        _stream_ptr()), "ldx_ld_rect_pw_counts_dev")
+    return out.view(torch.uint32)
+
+
+def pairwise_counts_host(codes_i, codes_j, dosage: bool = False) -> np.ndarray:
+    """Host mirror of the pairwise-complete counts (include/ldx.h, "pairwise-complete LD") in pure numpy: int64 [4, n_i, n_j]
+    (n, a, b, c) over the jointly called haplotypes or, ``dosage``, [6, n_i, n_j] (N, A, B, HA, HB, S) over the individuals
+    called at both SNPs (both codes of haplotypes 2k and 2k + 1 in {0, 1}).  float64 GEMMs of 0/1/2 matrices: exact."""
+    ci, cj = np.asarray(codes_i), np.asarray(codes_j)
+    if ci.ndim != 2 or cj.ndim != 2 or ci.shape[1] != cj.shape[1]:
+        raise _lib.LdxError(f"pairwise_counts_host: two code matrices over the same haplotypes needed, got shapes {ci.shape} "
+                            f"and {cj.shape}")
+    if dosage and ci.shape[1] % 2:
+        raise _lib.LdxError(f"pairwise_counts_host: dosage=True needs an even n_hap (got {ci.shape[1]})")
+
+    def planes(c):
+        alt, called = c == 1, (c == 0) | (c == 1)
+        if not dosage:
+            return called.astype(np.float64), alt.astype(np.float64), None
+        q = called[:, 0::2] & called[:, 1::2]
+        g = (alt[:, 0::2].astype(np.int64) + alt[:, 1::2].astype(np.int64)) * q
+        return q.astype(np.float64), g.astype(np.float64), (g == 2).astype(np.float64)
+
+    (qi, gi, hi), (qj, gj, hj) = planes(ci), planes(cj)
+    if dosage:
+        sets = [qi @ qj.T, gi @ qj.T, qi @ gj.T, hi @ qj.T, qi @ hj.T, gi @ gj.T]
+    else:
+        sets = [qi @ qj.T, gi @ qj.T, qi @ gj.T, gi @ gj.T]
+    return np.stack(sets).astype(np.int64)
+
+
+def pairwise_cell_host(counts, dosage: bool = False) -> np.ndarray:
+    """Host mirror of the pairwise-complete cell (include/ldx.h): float32, the shape of one set, from the integers ``counts``
+    [4 or 6, ...] in float64 with every operation rounded once -- -0.0f where either variance is 0, +0.0f where num = 0."""
+    k = np.asarray(counts)
+    want = len(PAIRWISE_COUNTS[bool(dosage)])
+    if k.shape[0] != want:
+        raise _lib.LdxError(f"pairwise_cell_host: {want} count sets needed (dosage={bool(dosage)}), got {k.shape[0]}")
+    k = k.astype(np.float64)
+    if dosage:
+        N, A, B, HA, HB, S = k
+        num = S * N - A * B                  # every product and the difference are integers below 2^53: exact, as the fma is
+        vx, vy = N * (A + 2.0 * HA) - A * A, N * (B + 2.0 * HB) - B * B
+    else:
+        n, a, b, c = k
+        num = c * n - a * b
+        vx, vy = a * (n - a), b * (n - b)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rsx = np.where(vx > 0.0, 1.0 / np.sqrt(np.where(vx > 0.0, vx, 1.0)), 0.0)
+        rsy = np.where(vy > 0.0, 1.0 / np.sqrt(np.where(vy > 0.0, vy, 1.0)), 0.0)
+    s = rsx * rsy
+    return np.where(s == 0.0, np.float32(-0.0), (num * s).astype(np.float32)).astype(np.float32)
 
 
 def _rect_hits_run(what: str, launch, n_i: int, n_j: int, dev, hit_capacity: Optional[int]):
