@@ -765,6 +765,59 @@ int ldx_ld_rect_pw_counts_dev(const void *alt_i, const void *ref_i, const uint32
                               const void *alt_j, const void *ref_j, const uint32_t *acnt_j, const uint32_t *rcnt_j, uint32_t n_j,
                               uint32_t n_hap, int dosage, uint32_t *counts, size_t ld, void *stream);
 
+/* ---- pairwise-complete bands: the band operators over the observations called at BOTH SNPs ---------------------------------
+ * The windowed operators above (ldx_ld_band_dev, ldx_ld_score_dev, ldx_ld_neighbors_dev and their dosage forms) keep every
+ * haplotype in n, or count a missing call as REF.  These three are their pairwise-complete forms: for every pair i > j of ONE
+ * panel with pos_i - pos_j <= window the cell is the cell of ldx_ld_rect_pw_dev for that panel against itself at (i, j), bit for
+ * bit -- the same integers (n a b c / N A B HA HB S), the same cell functions, -0.0f on a degenerate pair, +0.0f iff num = 0,
+ * within 4 float32 ulps of the exact r of its counts, symmetric in its two SNPs.  A kernel of its own on the FP4 matrix cores
+ * (ldx_pwband.hip), which walks the 256 x 128 tiles of the lower band only.
+ *
+ * Every entry takes both bit planes of the panel, its acnt / rcnt tables, `dosage` (0: haplotype form; else the dosage form,
+ * n_hap even), `hom` -- the uint32 table of ldx_dosage_stats_dev, read for rows without a missing code only, where it IS HA;
+ * NULL unless dosage --, positions (int64 [n_snps], NON-DECREASING, duplicates allowed) and window >= 0 in their units (values
+ * above 2^52 act as 2^52; the comparison is (double)pos_i - (double)pos_j <= window, ldx_ld_band_layout_dev's).
+ *
+ * ldx_pw_snp_stats_dev: the diagonal such a band goes with, over each SNP's OWN called set (it takes no window).  Haplotype
+ *   form: live iff acnt rcnt > 0.  Dosage form: over the individuals with both codes called -- N of them, A the sum of their
+ *   dosages, HA homozygous ALT -- live iff N (A + 2 HA) - A^2 > 0.  diag[i] (float32 [n_snps]) = +1.0f if live, else -0.0f;
+ *   live (uint8 [n_snps], or NULL) = 1 / 0.  On a panel without missing codes diag is the diagonal of ldx_ld_band_dev.
+ * ldx_ld_pw_band_dev: values[offsets[i] + j - lo[i]] = the cell, in the layout of ldx_ld_band_layout_dev for the same positions
+ *   and window.  The guard is ldx_ld_band_dev's -- a store only where lo[i] <= j < i and the index is < n_cells -- so every one of
+ *   the offsets[n_snps] cells is written (no memset) and nothing else.  values may be NULL when n_cells is 0.  The stored band
+ *   is a band like any other: ldx_band_score_dev and ldx_band_matvec_dev take it with the diagonal above.
+ * ldx_ld_pw_score_dev: ldx_ld_score_dev's sums over these cells: term = rint(2^32 (c *f32 c)) added to sums[i][0] and sums[j][0],
+ *   to sums[i][1 + k] where annot[j] has bit k and to sums[j][1 + k] where annot[i] has it (n_annot <= 8; annot NULL iff
+ *   n_annot = 0), as 64-bit integer atomics.  SNP i's own term, rint(2^32 diag[i]^2) -- 2^32 where it is live, else 0 --,
+ *   initialises sums[i][0] and the words 1 + k whose bit annot[i] has: sums (uint64 [n_snps][1 + n_annot]) needs no memset.
+ *   diag: ldx_pw_snp_stats_dev's.  The band is walked once per word: 1 + n_annot passes.
+ * ldx_ld_pw_neighbors_dev: every pair with s = c *f32 c >= r2_bound (ONE float32 multiply; r2_bound a float32 > 0) as the
+ *   records {i, j, c, s} and {j, i, c, s}, in the slots of ldx_ld_rect_pw_hits_dev (*n_hits is zeroed by the call and receives
+ *   the slots reserved; beyond hit_cap nothing is stored).  ldx_area_finish_ex_dev(counts_ready = 0) turns the slots into the
+ *   per-SNP neighbour CSR of ldx_ld_neighbors_dev.
+ *
+ * workspace: ldx_ld_pw_band_workspace_bytes(n_snps) bytes, 256-byte aligned, no initialisation needed (the call's first kernels
+ * write what the band kernel reads: each row's first in-window column and the tiles in front of each block of 256 rows): ONE
+ * workspace per launch that may be in flight.  Argument rules, checked before any HIP call (ldx_last_error() names the
+ * argument): a null pointer, n_snps or n_hap = 0, a negative window, r2_bound not > 0, an odd n_hap with dosage, n_annot > 8, a
+ * workspace too small = LDX_E_ARG; n_hap > LDX_MAX_HAPS or a bit plane of 4 GiB or more = LDX_E_UNSUPPORTED.  All calls only
+ * enqueue work on `stream`: no allocation, no synchronisation, no library state. */
+size_t ldx_ld_pw_band_workspace_bytes(uint32_t n_snps);
+int ldx_pw_snp_stats_dev(const void *alt, const void *ref, const uint32_t *acnt, const uint32_t *rcnt, uint32_t n_snps,
+                         uint32_t n_hap, int dosage, float *diag, uint8_t *live, void *stream);
+int ldx_ld_pw_band_dev(const void *alt, const void *ref, const uint32_t *acnt, const uint32_t *rcnt, const uint32_t *hom,
+                       uint32_t n_snps, uint32_t n_hap, int dosage, const int64_t *positions, int64_t window,
+                       const uint32_t *lo, const uint64_t *offsets, float *values, uint64_t n_cells, void *workspace,
+                       size_t workspace_bytes, void *stream);
+int ldx_ld_pw_score_dev(const void *alt, const void *ref, const uint32_t *acnt, const uint32_t *rcnt, const uint32_t *hom,
+                        uint32_t n_snps, uint32_t n_hap, int dosage, const int64_t *positions, int64_t window,
+                        const uint8_t *annot, uint32_t n_annot, const float *diag, uint64_t *sums, void *workspace,
+                        size_t workspace_bytes, void *stream);
+int ldx_ld_pw_neighbors_dev(const void *alt, const void *ref, const uint32_t *acnt, const uint32_t *rcnt, const uint32_t *hom,
+                            uint32_t n_snps, uint32_t n_hap, int dosage, const int64_t *positions, int64_t window,
+                            float r2_bound, ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits, void *workspace,
+                            size_t workspace_bytes, void *stream);
+
 /* ---- unphased LD by EM: maximum-likelihood r and D' of every row of one SNP set against every row of another ---------------
  * The dosage entries above give Weir's composite r of the genotypes.  These give what PLINK --r2 dprime / --ld and Haploview
  * compute from unphased genotypes: the maximum-likelihood two-locus haplotype frequency, the double heterozygotes resolved by

@@ -18,7 +18,7 @@ from .ops import LDCross, LDRegions, cross_host, ld_cross, ld_regions, region_po
 from .ops import dosage_host  # noqa: F401
 from .ops import LDBand, band_layout_host, cross_terms, ld_band, ld_cross_score  # noqa: F401
 from .ops import LDRectHits, ld_rect, ld_rect_hits, rect_hits_host  # noqa: F401
-from .ops import ld_rect_counts, pairwise_cell_host, pairwise_counts_host  # noqa: F401
+from .ops import ld_rect_counts, pairwise_cell_host, pairwise_counts_host, pw_snp_stats  # noqa: F401
 from .ops import LDEm, em_host, ld_em, ld_em_counts, ld_em_from_counts, ld_em_hits  # noqa: F401
 from .panel import PackedPanel, encode_codes, select_index  # noqa: F401
 
@@ -26,6 +26,6 @@ __all__ = ["PackedPanel", "encode_codes", "select_index", "ld_triangle", "ld_are
            "TriangleResult", "AreaHits", "ld_score", "LDScores", "ld_neighbors", "LDNeighbors", "ld_clump", "Clumps",
            "ld_prune", "Pruned", "ld_decay", "LDDecay", "ld_blocks", "LDBlocks", "blocks_host", "ld_cross", "LDCross", "ld_regions", "LDRegions", "cross_host", "split_host",
            "region_positions", "ld_matvec", "LDProduct", "ld_ridge", "RidgeResult", "prod_terms", "dosage_host", "ld_band", "LDBand",
-           "ld_cross_score", "band_layout_host", "cross_terms", "ld_rect", "ld_rect_hits", "LDRectHits", "rect_hits_host", "ld_rect_counts", "pairwise_counts_host", "pairwise_cell_host", "ld_em", "LDEm",
+           "ld_cross_score", "band_layout_host", "cross_terms", "ld_rect", "ld_rect_hits", "LDRectHits", "rect_hits_host", "ld_rect_counts", "pairwise_counts_host", "pairwise_cell_host", "pw_snp_stats", "ld_em", "LDEm",
            "ld_em_hits", "ld_em_counts", "ld_em_from_counts", "em_host", "LdxError",
            "version"]

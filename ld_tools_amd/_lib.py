@@ -171,6 +171,12 @@ SIGNATURES = {
     "ldx_ld_rect_pw_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _int, _vp, _sz, _vp]),
     "ldx_ld_rect_pw_hits_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _int, C.c_float, _vp, _u64,
                                        _vp, _vp]),
+    "ldx_ld_pw_band_workspace_bytes": (_sz, [_u32]),
+    "ldx_pw_snp_stats_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _int, _vp, _vp, _vp]),
+    "ldx_ld_pw_band_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _int, _vp, _i64, _vp, _vp, _vp, _u64, _vp, _sz, _vp]),
+    "ldx_ld_pw_score_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _int, _vp, _i64, _vp, _u32, _vp, _vp, _vp, _sz, _vp]),
+    "ldx_ld_pw_neighbors_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _int, _vp, _i64, C.c_float, _vp, _u64, _vp, _vp, _sz,
+                                       _vp]),
     "ldx_ld_rect_pw_counts_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _int, _vp, _sz, _vp]),
     "ldx_ld_em_rect_dev": (_int, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _sz, _vp]),
     "ldx_ld_em_rect_hits_dev": (_int, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, C.c_float, _vp, _u64, _vp, _vp]),

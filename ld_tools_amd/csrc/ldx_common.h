@@ -123,7 +123,7 @@ __host__ __device__ inline uint64_t tile_base(uint64_t t, uint64_t G) { return t
 // back with a larger buffer.  So every slot below min(*n_hits, hit_cap) holds a record or the mark, which is exactly what the
 // consumer, ldx_area_finish_ex_dev (ldx_area.hip), relies on.  `counts`, where given, receives the STORED records per query
 // row: what the consumer's scatter will place.
-// Users: area_scan_kernel, rect_kernel, em_kernel, pwc_kernel.  The band epilogues of triangle_mfma_kernel keep the same protocol as the
+// Users: area_scan_kernel, rect_kernel, em_kernel, pwc_kernel, pwband_kernel.  The band epilogues of triangle_mfma_kernel keep the same protocol as the
 // text of a macro (LDX_HIT_APPENDER, ldx_mfma.hip), because that kernel's instruction stream must not move.
 constexpr uint32_t kHitBatch = 256;              // slots a wave reserves per atomic
 constexpr uint32_t kHitInvalid = 0xFFFFFFFFu;    // `query` of an unused slot
@@ -161,6 +161,35 @@ struct HitAppender {
             if (sl < hit_cap) {
                 hits[sl] = ldx_hit{i, j, a, b};
                 if (counts) atomicAdd(&counts[i], 1u);
+            }
+        }
+        slot += cnt;
+    }
+    // the same for a symmetric pair: two records per lane with `keep`, {i, j, a, b} and {j, i, a, b}, in adjacent slots of one
+    // batch (at most 128 of its 256)
+    __device__ __forceinline__ void append_both(bool keep, uint32_t i, uint32_t j, float a, float b)
+    {
+        const unsigned long long mask = __ballot(keep);
+        if (!mask) return;   // wave-uniform
+        const uint32_t cnt = 2u * __builtin_popcountll(mask);
+        if (slot + cnt > slot_end) {
+            close();
+            unsigned long long base = 0;
+            if (lane == 0) base = atomicAdd(n_hits, (unsigned long long)kHitBatch);
+            base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
+                   __builtin_amdgcn_readfirstlane((uint32_t)base);
+            slot = base;
+            slot_end = base + kHitBatch;
+        }
+        if (keep) {
+            const uint64_t sl = slot + 2u * __builtin_popcountll(mask & ((1ull << lane) - 1ull));
+            if (sl < hit_cap) {
+                hits[sl] = ldx_hit{i, j, a, b};
+                if (counts) atomicAdd(&counts[i], 1u);
+            }
+            if (sl + 1u < hit_cap) {
+                hits[sl + 1u] = ldx_hit{j, i, a, b};
+                if (counts) atomicAdd(&counts[j], 1u);
             }
         }
         slot += cnt;

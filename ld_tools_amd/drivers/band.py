@@ -19,7 +19,7 @@ import numpy as np
 from .._lib import LdxError
 from ..ops import LDBand, ld_band, ld_cross_score
 from .ingest import haplotype_columns
-from .ldscore import _check_complete, _check_missing_arg, _fetch_panel
+from .ldscore import _check_complete, _check_missing_arg, _fetch_panel, _pairwise
 from .rmatrix import VARIANTS_HEADER
 
 
@@ -51,7 +51,7 @@ def band_matrix(vcf, chrom, chrom_rows: Sequence[Sequence], sample_names: Sequen
     if dosage:
         _check_complete("band_matrix", panel, chrom, missing)
     poss = [cv.poss[k] for k in keep]
-    band = ld_band(panel, np.asarray(poss, dtype=np.int64), window_bp=window_bp, dosage=dosage)
+    band = ld_band(panel, np.asarray(poss, dtype=np.int64), window_bp=window_bp, dosage=dosage, missing=_pairwise(missing))
     return BandMatrix(str(chrom), [cv.rs_ids[k] for k in keep], poss, [cv.recs[k].ref for k in keep],
                       [cv.recs[k].alts[0] for k in keep], panel.alt_freq4().cpu().numpy().tolist(), band)
 
@@ -131,7 +131,7 @@ def cross_scores_by_group(vcf, chrom, chrom_rows: Sequence[Sequence], groups: Ma
         if cols.size == 0:
             raise LdxError(f"{what}: no sample of group {label!r} is carried by the records of chromosome {chrom}")
         sub = panel.select(haplotypes=cols)
-        bands[label] = ld_band(sub, pos, window_bp=window_bp, dosage=dosage)
+        bands[label] = ld_band(sub, pos, window_bp=window_bp, dosage=dosage, missing=_pairwise(missing))
         lives[label] = sub.dosage_live() if dosage else \
             (sub.alt_counts().astype(np.int64) * sub.ref_counts().astype(np.int64)) > 0
     labels = list(groups)

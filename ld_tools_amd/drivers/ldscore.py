@@ -9,6 +9,8 @@ LDX_OUT_R32), and the unbiased estimate (``adjust``) uses n_obs = n_hap: the rig
 over the N = n_hap / 2 samples (include/ldx.h, ldx_ld_score_dosage_dev) -- phase-free, so it also suits unphased calls -- with
 n_obs = N and ``M_5_50`` from the dosage allele frequency a / (2 N): the quantities ``ldsc.py --l2`` computes.  LDSC has no
 missing genotypes; here a missing call would count as REF, so a panel with one is refused unless ``missing="ref"`` says so.
+``missing="pairwise"`` (either mode) takes every pair's r over the calls present at both variants instead, as PLINK --r2 does
+(ops.ld_score(missing="pairwise")); n_obs stays n_hap, or N with ``dosage``.
 """
 from __future__ import annotations
 
@@ -80,15 +82,20 @@ def _fetch_panel(what, vcf, chrom, chrom_rows, sample_names, annot, annot_names)
 
 
 def _check_missing_arg(what: str, dosage: bool, missing: Optional[str]) -> None:
-    if missing not in (None, "ref"):
-        raise LdxError(f"{what}: missing must be None or 'ref' (got {missing!r})")
-    if missing is not None and not dosage:
-        raise LdxError(f"{what}: missing= belongs to dosage=True (the haplotype r leaves such calls out of both counts)")
+    if missing not in (None, "ref", "pairwise"):
+        raise LdxError(f"{what}: missing must be None, 'ref' or 'pairwise' (got {missing!r})")
+    if missing == "ref" and not dosage:
+        raise LdxError(f"{what}: missing='ref' belongs to dosage=True (the haplotype r leaves such calls out of both counts)")
+
+
+def _pairwise(missing: Optional[str]) -> Optional[str]:
+    """The ``missing`` argument of the operators: "pairwise" or None ("ref" is this module's acceptance of their own rule)."""
+    return "pairwise" if missing == "pairwise" else None
 
 
 def _check_complete(what: str, panel: PackedPanel, chrom, missing: Optional[str]) -> None:
     """dosage mode: every call must be REF or the first ALT allele unless the caller accepted the REF imputation."""
-    if missing == "ref":
+    if missing in ("ref", "pairwise"):
         return
     short = panel.alt_counts().astype(np.int64) + panel.ref_counts().astype(np.int64) < panel.n_hap
     if short.any():
@@ -105,13 +112,13 @@ def ld_scores(vcf, chrom, chrom_rows: Sequence[Sequence], sample_names: Sequence
     (default A0, A1, ...).  ``adjust``: write LDSC's unbiased r^2 (LDScores.adjusted) rather than r^2.  Mixed-ploidy panels
     (genotype lists of different lengths) are out of scope: LdxError.  ``dosage``: genotype-dosage r over the samples, n_obs =
     N (the module docstring); a kept variant with a call that is neither REF nor the first ALT allele (a + r < n) then raises
-    LdxError unless ``missing="ref"`` accepts that such calls count as REF."""
+    LdxError unless ``missing="ref"`` accepts that such calls count as REF.  ``missing="pairwise"``: pairwise-complete r."""
     _check_missing_arg("ld_scores", dosage, missing)
     cv, keep, ann, names, panel = _fetch_panel("ld_scores", vcf, chrom, chrom_rows, sample_names, annot, annot_names)
     poss = [cv.poss[k] for k in keep]
     if dosage:
         _check_complete("ld_scores", panel, chrom, missing)
-    res = ld_score(panel, np.asarray(poss, dtype=np.int64), window_bp=window_bp, annot=ann, dosage=dosage)
+    res = ld_score(panel, np.asarray(poss, dtype=np.int64), window_bp=window_bp, annot=ann, dosage=dosage, missing=_pairwise(missing))
     fa = panel.alt_counts().astype(np.float64) / panel.n_hap
     return LDScoreTable(str(chrom), [cv.rs_ids[k] for k in keep], poss, fa, ann, names, res, adjust)
 
@@ -149,7 +156,7 @@ def ld_scores_by_group(vcf, chrom, chrom_rows: Sequence[Sequence], groups: Mappi
         if cols.size == 0:
             raise LdxError(f"{what}: no sample of group {label!r} is carried by the records of chromosome {chrom}")
         sub = panel.select(haplotypes=cols)
-        res = ld_score(sub, pos, window_bp=window_bp, annot=ann, dosage=dosage)
+        res = ld_score(sub, pos, window_bp=window_bp, annot=ann, dosage=dosage, missing=_pairwise(missing))
         fa = sub.alt_counts().astype(np.float64) / sub.n_hap
         tables[label] = LDScoreTable(str(chrom), list(rs_ids), list(poss), fa, ann, list(names), res, adjust)
     return tables

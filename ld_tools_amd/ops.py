@@ -704,11 +704,14 @@ class LDScores:
     _m: Optional[np.ndarray] = None
     _live: Optional[np.ndarray] = None
     dosage: bool = False                     # the sums are over genotype-dosage r (ld_score(dosage=True))
+    missing: Optional[str] = None            # "pairwise": the sums are over pairwise-complete r (ld_score(missing="pairwise"))
 
     @property
     def live(self) -> np.ndarray:
         """bool [n]: the SNP is not degenerate (a r > 0: it has ALT and REF codes; a dosage result: v > 0, the dosage varies
-        among the individuals)."""
+        among the individuals; a pairwise-complete dosage result: it varies among the individuals called at the SNP)."""
+        if self._live is None and self.missing is not None:
+            self._live = pw_snp_stats(self.panel, self.dosage)[1].cpu().numpy().astype(bool)
         if self._live is None and self.dosage:
             self._live = self.panel.dosage_live()
         if self._live is None:
@@ -769,7 +772,7 @@ def _band_positions(panel: PackedPanel, positions, window_bp, window_snps, check
 
 def ld_score(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, window_snps: Optional[int] = None,
              annot=None, path: Optional[str] = None, workspace: Optional[torch.Tensor] = None,
-             check_positions: bool = True, regions=None, dosage: bool = False) -> LDScores:
+             check_positions: bool = True, regions=None, dosage: bool = False, missing: Optional[str] = None) -> LDScores:
     """LD scores on the matrix-pipe band: for every SNP i, the sum of r^2 over the SNPs j with |pos_i - pos_j| <= window
     (i itself included), and with ``annot`` (bool / 0-1 [n, K], K <= 8) the same sum per category over the j that carry it
     (include/ldx.h, ldx_ld_score_dev).  r is the signed r of ld_triangle(fmt="r32"), bit for bit; the sums are exact
@@ -788,7 +791,17 @@ def ld_score(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, win
     ``dosage=True``: r is the genotype-dosage r of ld_triangle(fmt="r32", dosage=True), bit for bit -- what ldsc.py --l2 sums
     (include/ldx.h, ldx_ld_score_dosage_dev; the FP4 band only, not together with ``regions``).  ``LDScores.live`` is then
     v > 0 and ``adjusted()`` defaults to n_obs = n_hap / 2.
+
+    ``missing="pairwise"``: r is the pairwise-complete r of ld_rect(missing="pairwise") -- every pair over the haplotypes
+    (``dosage``: the individuals) called at both SNPs, as PLINK --r2 does (include/ldx.h, "pairwise-complete bands";
+    ldx_ld_pw_score_dev: the FP4 band only, not together with ``regions``; ``workspace`` of ldx_ld_pw_band_workspace_bytes()
+    bytes; with ``annot`` the band is walked once per column of the result).  A SNP's own term is 1 where it is polymorphic
+    among its own called observations.  None: the call as it always was.
     """
+    pairwise = _band_missing("ld_score", missing, path)
+    if pairwise and regions is not None:
+        raise _lib.LdxError('ld_score: regions= together with missing="pairwise" is not available: store the band with '
+                            'ld_band(missing="pairwise") and sum its cells per region')
     if dosage:
         _dosage_check("ld_score", panel, regions)
     require_gpu()
@@ -796,6 +809,18 @@ def ld_score(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, win
     pos, pos_h, window = _region_band(panel, positions, window_bp, window_snps, regions, check_positions, "ld_score")
     bits, k = (None, 0) if annot is None else pack_annot(annot, n)
     annot_d = torch.as_tensor(bits).to(panel.device) if k else None
+    if pairwise:
+        workspace = _pw_workspace(panel, workspace)
+        sums = torch.empty((n, 1 + k), dtype=torch.uint64, device=panel.device)
+        diag, _ = pw_snp_stats(panel, dosage)
+        check(lib.ldx_ld_pw_score_dev(*_pw_panel(panel, dosage), n, panel.n_hap, int(bool(dosage)), pos.data_ptr(),
+                                      min(window, BAND_WINDOW_MAX), _ptr(annot_d), k, diag.data_ptr(), sums.data_ptr(),
+                                      workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr()),
+              "ldx_ld_pw_score_dev")
+        res = LDScores(sums, pos_h if pos_h is not None else pos, window, panel.n_hap, bits, k, panel, dosage=bool(dosage),
+                       missing=missing)
+        res._keep = (pos, annot_d, workspace, diag)
+        return res
     pcode = _band_path(path)
     workspace = _band_workspace(lib.ldx_ld_score_workspace_bytes, panel, workspace)
     sums = torch.empty((n, 1 + k), dtype=torch.uint64, device=panel.device)
@@ -1671,7 +1696,10 @@ def ld_ridge(panel: PackedPanel, z, positions=None, window_bp: int = 1_000_000, 
     ``band`` (an LDBand of this panel from ld_band; default None: no change): every product is read from the stored band
     (LDBand.matvec: a sweep over the stored cells, the same int64 sums as ld_matvec on the band's window, hence the same iterates)
     instead of re-deriving every r cell on the matrix cores; positions and window are then the band's, and ``positions``,
-    the window arguments, ``path`` and ``regions`` are not read."""
+    the window arguments, ``path`` and ``regions`` are not read.  A pairwise-complete haplotype band
+    (ld_band(missing="pairwise")) is taken as it is -- the layout and the terms are the same -- and is the route to a ridge solve
+    on a panel with missing calls; its matrix is estimated pair by pair over different observations, so it need not be
+    positive semidefinite even on whole regions, and ``indefinite`` can be reported."""
     if band is not None:
         if band.dosage:
             raise _lib.LdxError("ld_ridge: band= needs a haplotype band (ld_matvec has no genotype-dosage form)")
@@ -1759,7 +1787,9 @@ class LDBand:
     cells bit for bit (its ``dosage=True`` cells for a dosage band); ``lo`` (int32 bit pattern of uint32 [n]) and
     ``offsets`` (int64 bit pattern of uint64 [n + 1]): cell (i, j), lo[i] <= j < i, is ``values[offsets[i] + j - lo[i]]``;
     ``diag``: float32 [n], r_matrix()'s diagonal (not part of ``values``).  ``positions``: what ld_band was given (numpy, or
-    the device tensor); ``window``: the window in their units."""
+    the device tensor); ``window``: the window in their units.  A pairwise-complete band (``missing == "pairwise"``) has the
+    same layout with ld_rect(missing="pairwise")'s cells and a +1 / -0.0 diagonal, so ``to_csr``, ``to_dense``, ``matvec``,
+    ld_ridge(band=) and ld_cross_score work on it as they are."""
 
     values: torch.Tensor
     lo: torch.Tensor
@@ -1770,6 +1800,7 @@ class LDBand:
     dosage: bool = False
     n_hap: int = 0
     _host: Optional[tuple] = None
+    missing: Optional[str] = None   # "pairwise": the cells are ld_rect(missing="pairwise")'s (ld_band(missing="pairwise"))
 
     @property
     def n_snps(self) -> int:
@@ -1845,7 +1876,9 @@ class LDBand:
         """ld_matvec from the stored band (include/ldx.h, ldx_band_matvec_dev): the same right-hand-side scaling, terms and
         int64 sums -- bit for bit ld_matvec's on the band's window for a haplotype band -- as one sweep over ``values``
         instead of a pass over the panel on the matrix cores (about three times faster than ld_matvec with
-        one right-hand side; with eight it is currently slower, so keep ld_matvec for wide batches)."""
+        one right-hand side; with eight it is currently slower, so keep ld_matvec for wide batches).  On a
+        pairwise-complete band the terms are those of its cells and its diagonal: the product with the windowed
+        pairwise-complete matrix, which ld_matvec itself does not offer."""
         x32, e, squeeze = matvec_rhs(x, self.n_snps, power, check_finite, self.values.device)
         require_gpu()
         return LDProduct(self._matvec_launch(x32, power), e, x32, self.window, power, squeeze)
@@ -1853,7 +1886,7 @@ class LDBand:
 
 def ld_band(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, window_snps: Optional[int] = None,
             path: Optional[str] = None, workspace: Optional[torch.Tensor] = None, check_positions: bool = True,
-            dosage: bool = False) -> LDBand:
+            dosage: bool = False, missing: Optional[str] = None) -> LDBand:
     """The windowed (band) LD matrix, kept: the signed r of every pair i > j with pos_i - pos_j <= window, 4 bytes per
     unordered pair, no threshold and no sort (include/ldx.h, ldx_ld_band_dev) -- ld_triangle(fmt="r32")'s cells bit for bit,
     written by the band kernel as it computes them.  Positions and window as for ld_score.  ``path``: 'fp4' (default) or
@@ -1861,13 +1894,22 @@ def ld_band(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, wind
     reuse.  ``dosage=True``: genotype-dosage r (ld_triangle(fmt="r32", dosage=True)'s cells; the FP4 band, an even n_hap).
 
     The layout is computed on the device; its total, offsets[n], is read back once to size ``values`` -- the call's only
-    synchronisation (besides the check of a device tensor of positions, unless ``check_positions`` is False)."""
+    synchronisation (besides the check of a device tensor of positions, unless ``check_positions`` is False).
+
+    ``missing="pairwise"``: the cells are the pairwise-complete r of ld_rect(panel, panel, missing="pairwise") at (i, j), bit
+    for bit -- every pair over the haplotypes (``dosage``: the individuals) called at both SNPs -- at the cost of the band
+    instead of the square (include/ldx.h, "pairwise-complete bands"; ldx_ld_pw_band_dev: the FP4 band only; ``workspace`` of
+    ldx_ld_pw_band_workspace_bytes() bytes).  ``diag`` is +1 where the SNP is polymorphic among its own called observations,
+    else -0.0.  A panel without missing codes gives the ``missing=None`` band bit for bit.  None: the call as it always was."""
+    pairwise = _band_missing("ld_band", missing, path)
     if dosage:
         _dosage_check("ld_band", panel)
     require_gpu()
     n = panel.n_snps
     pos, pos_h, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_band")
     window = min(window, BAND_WINDOW_MAX)
+    if pairwise:
+        return _pw_band(panel, pos, pos_h, window, workspace, bool(dosage), missing)
     pcode = _band_path(path)
     workspace = _band_workspace(lib.ldx_ld_band_workspace_bytes, panel, workspace)
     dev = panel.device
@@ -1914,7 +1956,9 @@ def ld_cross_score(band_a: LDBand, band_b: LDBand) -> np.ndarray:
     included (include/ldx.h, ldx_band_score_dev).  Every term is rint(2^32 (r1 *f32 r2)), added as a 64-bit integer: the
     result is reproducible and symmetric in its arguments.  Returns the scores as float64 [n] (sums 2^-32); the exact int64
     sums are its ``.sums``.  ``ld_cross_score(b, b)`` is ld_score's column 0, bit for bit.  Raises LdxError when the layouts
-    differ."""
+    differ.  Pairwise-complete bands (ld_band(missing="pairwise")) are bands like any other here: with two of them the
+    result is the cross score of the pairwise-complete r, and ``ld_cross_score(b, b)`` is ld_score(missing="pairwise")'s
+    column 0."""
     if not isinstance(band_a, LDBand) or not isinstance(band_b, LDBand):
         raise _lib.LdxError("ld_cross_score takes two LDBand results of ld_band")
     if not _same_layout(band_a, band_b):
@@ -2030,6 +2074,7 @@ class LDNeighbors:
     window: int
     bound: np.float32       # the float32 bound on s = r *f32 r (r2_bound)
     dosage: bool = False    # r is the genotype-dosage r (ld_neighbors(dosage=True))
+    missing: Optional[str] = None   # "pairwise": r is the pairwise-complete r (ld_neighbors(missing="pairwise"))
 
     @property
     def nbr(self) -> torch.Tensor:
@@ -2054,7 +2099,8 @@ class LDNeighbors:
 
 def ld_neighbors(panel: PackedPanel, positions=None, window_bp: int = 250_000, window_snps: Optional[int] = None,
                  r2: float = 0.2, strict: bool = False, path: Optional[str] = None, hit_capacity: Optional[int] = None,
-                 workspace: Optional[torch.Tensor] = None, check_positions: bool = True, dosage: bool = False) -> LDNeighbors:
+                 workspace: Optional[torch.Tensor] = None, check_positions: bool = True, dosage: bool = False,
+                 missing: Optional[str] = None) -> LDNeighbors:
     """Neighbour lists on the matrix-pipe band (include/ldx.h, ldx_ld_neighbors_dev + ldx_area_finish_ex_dev): for every SNP
     the SNPs j with |pos_i - pos_j| <= window, j != i, and r^2 >= ``r2`` (``strict``: r^2 > r2), where r is the r32 cell of
     ld_triangle(fmt="r32") bit for bit and r^2 one float32 multiply.  Degenerate SNPs have no neighbours.
@@ -2065,13 +2111,32 @@ def ld_neighbors(panel: PackedPanel, positions=None, window_bp: int = 250_000, w
     bytes to reuse.  The host reads the record count once.
 
     ``dosage=True``: r is the genotype-dosage r of ld_triangle(fmt="r32", dosage=True), bit for bit (include/ldx.h,
-    ldx_ld_neighbors_dosage_dev; the FP4 band only); SNPs whose dosage does not vary (v == 0) have no neighbours."""
+    ldx_ld_neighbors_dosage_dev; the FP4 band only); SNPs whose dosage does not vary (v == 0) have no neighbours.
+
+    ``missing="pairwise"``: r is the pairwise-complete r of ld_rect(missing="pairwise"), bit for bit -- what PLINK --r2 /
+    --indep-pairwise compare with the threshold on a panel with missing calls (include/ldx.h, "pairwise-complete bands";
+    ldx_ld_pw_neighbors_dev: the FP4 band only; ``workspace`` of ldx_ld_pw_band_workspace_bytes() bytes).  None: the call as
+    it always was."""
+    pairwise = _band_missing("ld_neighbors", missing, path)
     if dosage:
         _dosage_check("ld_neighbors", panel)
     require_gpu()
     n = panel.n_snps
     bound = r2_bound(r2, strict)
     pos, _, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_neighbors")
+    if pairwise:
+        workspace = _pw_workspace(panel, workspace)
+        side = _pw_panel(panel, dosage)
+
+        def launch(raw, cap, n_hits):
+            check(lib.ldx_ld_pw_neighbors_dev(*side, n, panel.n_hap, int(bool(dosage)), pos.data_ptr(),
+                                              min(window, BAND_WINDOW_MAX), float(bound), raw.data_ptr(), cap, n_hits.data_ptr(),
+                                              workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr()),
+                  "ldx_ld_pw_neighbors_dev")
+
+        cap = int(hit_capacity) if hit_capacity is not None else max(1 << 20, 32 * n)
+        offsets, hits = _rect_hits_run("ld_neighbors", launch, n, 0, panel.device, cap)
+        return LDNeighbors(offsets, hits, n, window, bound, bool(dosage), missing)
     pcode = _band_path(path)
     dev = panel.device
     workspace = _band_workspace(lib.ldx_ld_neighbors_workspace_bytes, panel, workspace)
@@ -2183,24 +2248,29 @@ class Pruned:
     rounds: int
 
 
-def _panel_live(panel: PackedPanel, dosage: bool = False) -> np.ndarray:
-    """The SNPs that can have a neighbour: a r > 0, or for the dosage lists v > 0."""
+def _panel_live(panel: PackedPanel, dosage: bool = False, pairwise: bool = False) -> np.ndarray:
+    """The SNPs that can have a neighbour: a r > 0, or for the dosage lists v > 0 (pairwise-complete: v over the individuals
+    called at the SNP)."""
+    if pairwise and dosage:
+        return pw_snp_stats(panel, True)[1].cpu().numpy().astype(bool)
     return panel.dosage_live() if dosage else live_snps(panel.alt_counts(), panel.ref_counts())
 
 
 def ld_clump(panel: PackedPanel, positions, pvalues, p1: float = 1e-4, p2: float = 1e-2, r2: float = 0.5,
              window_bp: int = 250_000, window_snps: Optional[int] = None, path: Optional[str] = None,
-             hit_capacity: Optional[int] = None, dosage: bool = False) -> Clumps:
+             hit_capacity: Optional[int] = None, dosage: bool = False, missing: Optional[str] = None) -> Clumps:
     """Clumping (PLINK --clump's rule): take the SNPs with p <= p1 in increasing (p, row); one not yet in a clump becomes an
     index and takes every SNP not yet in a clump with p <= p2 and r^2 >= r2 within the window.  r^2 is that of ld_neighbors
     (the haplotype r of the ALT indicators, unrounded; ``dosage=True``: the genotype-dosage r, PLINK's own).  SNPs with a
-    NaN p and degenerate SNPs (dosage: v == 0) take no part."""
+    NaN p and degenerate SNPs (dosage: v == 0) take no part.  ``missing="pairwise"``: ld_neighbors(missing="pairwise")'s
+    lists -- r^2 over the observations called at both SNPs."""
+    pairwise = _band_missing("ld_clump", missing, path)
     if dosage:
         _dosage_check("ld_clump", panel)
-    live = _panel_live(panel, dosage)
+    live = _panel_live(panel, dosage, pairwise)
     rank, member_ok = clump_ranks(pvalues, p1, p2, live)
     nb = ld_neighbors(panel, positions, window_bp=window_bp, window_snps=window_snps, r2=r2, strict=False, path=path,
-                      hit_capacity=hit_capacity, dosage=dosage)
+                      hit_capacity=hit_capacity, dosage=dosage, missing=missing)
     state, owner, rounds = select_dev(nb, rank, member_ok)
     idx = np.flatnonzero(state == SEL_INDEX)
     idx = idx[np.argsort(rank[idx], kind="stable")]
@@ -2210,16 +2280,18 @@ def ld_clump(panel: PackedPanel, positions, pvalues, p1: float = 1e-4, p2: float
 
 def ld_prune(panel: PackedPanel, positions=None, r2: float = 0.2, window_bp: Optional[int] = None,
              window_snps: Optional[int] = None, priority=None, path: Optional[str] = None,
-             hit_capacity: Optional[int] = None, dosage: bool = False) -> Pruned:
+             hit_capacity: Optional[int] = None, dosage: bool = False, missing: Optional[str] = None) -> Pruned:
     """Priority pruning: take the SNPs in decreasing priority (default: the MAF min(fa, fr) of the panel), ties by row; one
     with no kept neighbour is kept.  Neighbours are the SNPs within the window with r^2 > r2 (strict), as in ld_neighbors.
     The kept set has no pair above the threshold inside the window.  Degenerate SNPs are never kept.  The window is
     ``window_snps`` SNPs or ``window_bp`` in the units of ``positions`` (default 250 000 when positions are given).
     ``dosage=True``: the neighbours are those of the genotype-dosage r (PLINK --indep-pairwise's r), SNPs with v == 0 are
-    never kept, and the default priority is the dosage MAF min(f, 1 - f), f = a / n_hap."""
+    never kept, and the default priority is the dosage MAF min(f, 1 - f), f = a / n_hap.  ``missing="pairwise"``:
+    ld_neighbors(missing="pairwise")'s lists -- PLINK --indep-pairwise's r^2 on a panel with missing calls."""
+    pairwise = _band_missing("ld_prune", missing, path)
     if dosage:
         _dosage_check("ld_prune", panel)
-    live = _panel_live(panel, dosage)
+    live = _panel_live(panel, dosage, pairwise)
     if priority is None and dosage:
         f = panel.fa.cpu().numpy()[:panel.n_snps]
         priority = np.minimum(f, 1.0 - f)
@@ -2229,7 +2301,7 @@ def ld_prune(panel: PackedPanel, positions=None, r2: float = 0.2, window_bp: Opt
     if window_snps is None and window_bp is None:
         window_bp = 250_000
     nb = ld_neighbors(panel, positions, window_bp=0 if window_bp is None else window_bp, window_snps=window_snps, r2=r2,
-                      strict=True, path=path, hit_capacity=hit_capacity, dosage=dosage)
+                      strict=True, path=path, hit_capacity=hit_capacity, dosage=dosage, missing=missing)
     state, _, rounds = select_dev(nb, rank, live.astype(np.uint8))
     return Pruned(state == SEL_INDEX, rank, nb, rounds)
 
@@ -2283,6 +2355,59 @@ def _rect_missing(what: str, missing) -> bool:
 def _pw_side(panel: PackedPanel) -> tuple:
     """One side's arguments of the pairwise-complete entries: alt, ref, acnt, rcnt, n."""
     return panel.alt.data_ptr(), panel.ref.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), panel.n_snps
+
+
+# ---- pairwise-complete bands (include/ldx.h, "pairwise-complete bands")
+def _band_missing(what: str, missing, path) -> bool:
+    """The band operators' ``missing`` argument (_rect_missing's rule); "pairwise" runs on the FP4 band only.  Checked before
+    anything touches the device."""
+    pairwise = _rect_missing(what, missing)
+    if pairwise and path not in (None, "fp4"):
+        raise _lib.LdxError(f'{what}: missing="pairwise" runs on the FP4 band only (path must be None or \'fp4\', got {path!r})')
+    return pairwise
+
+
+def _pw_panel(panel: PackedPanel, dosage: bool) -> tuple:
+    """The panel's arguments of the pairwise-complete band entries: alt, ref, acnt, rcnt, hom (None unless ``dosage``)."""
+    hom = panel.dosage_stats()[0].data_ptr() if dosage else None
+    return panel.alt.data_ptr(), panel.ref.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), hom
+
+
+def _pw_workspace(panel: PackedPanel, workspace: Optional[torch.Tensor]) -> torch.Tensor:
+    return _band_workspace(lambda n, _h: lib.ldx_ld_pw_band_workspace_bytes(n), panel, workspace)
+
+
+def pw_snp_stats(panel: PackedPanel, dosage: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(diag float32 [n], live uint8 [n])`` on the device: the diagonal of a pairwise-complete band and what it stands on
+    (include/ldx.h, ldx_pw_snp_stats_dev) -- the SNP is polymorphic over its OWN called set: a r > 0, or with ``dosage``
+    N (A + 2 HA) - A^2 > 0 over the individuals with both codes called; diag is +1.0 where live, else -0.0."""
+    require_gpu()
+    n = panel.n_snps
+    diag = torch.empty(n, dtype=torch.float32, device=panel.device)
+    live = torch.empty(n, dtype=torch.uint8, device=panel.device)
+    check(lib.ldx_pw_snp_stats_dev(panel.alt.data_ptr(), panel.ref.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), n,
+                                   panel.n_hap, int(bool(dosage)), diag.data_ptr(), live.data_ptr(), _stream_ptr()),
+          "ldx_pw_snp_stats_dev")
+    return diag, live
+
+
+def _pw_band(panel: PackedPanel, pos, pos_h, window: int, workspace, dosage: bool, missing) -> "LDBand":
+    """ld_band(missing="pairwise") after the argument checks: ld_band's layout, ldx_ld_pw_band_dev's cells."""
+    n, dev = panel.n_snps, panel.device
+    workspace = _pw_workspace(panel, workspace)
+    lo = torch.empty(n, dtype=torch.int32, device=dev)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    check(lib.ldx_ld_band_layout_dev(pos.data_ptr(), n, window, lo.data_ptr(), offsets.data_ptr(), _stream_ptr()),
+          "ldx_ld_band_layout_dev")
+    n_cells = int(offsets[n].item())
+    values = torch.empty(n_cells, dtype=torch.float32, device=dev)
+    check(lib.ldx_ld_pw_band_dev(*_pw_panel(panel, dosage), n, panel.n_hap, int(dosage), pos.data_ptr(), window, lo.data_ptr(),
+                                 offsets.data_ptr(), _ptr(values) if n_cells else None, n_cells, workspace.data_ptr(),
+                                 workspace.numel() * workspace.element_size(), _stream_ptr()), "ldx_ld_pw_band_dev")
+    diag, _ = pw_snp_stats(panel, dosage)
+    res = LDBand(values, lo, offsets, diag, pos if pos_h is None else pos_h, window, dosage, panel.n_hap, missing=missing)
+    res._keep = (pos, workspace)   # alive until the launch is done
+    return res
 
 
 def ld_rect(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, dosage: bool = False,
