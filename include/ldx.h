@@ -874,6 +874,53 @@ int ldx_ld_em_counts_dev(const void *alt_i, uint32_t n_i, const void *alt_j, uin
 int ldx_ld_em_from_counts_dev(uint32_t n_ind, size_t m, const uint32_t *a1, const uint32_t *a2, const uint32_t *S,
                               const uint32_t *H, float *r, float *dprime, double *x, void *stream);
 
+/* ---- pairwise-complete EM: unphased LD by EM over the individuals called at BOTH SNPs -----------------------------------------
+ * The EM entries above count a missing code as REF, which biases r and D' on the data they are meant for: unphased call sets
+ * are the ones that carry missing calls.  PLINK --r2 dprime / --ld and Haploview estimate each pair's haplotype frequencies
+ * over the individuals called at both variants; these entries do that.  Panels and individuals are those of the dosage form of
+ * the pairwise-complete entries: both bit planes and the acnt / rcnt tables of each panel, n_hap even, individual k owns
+ * haplotypes 2k and 2k + 1 and is CALLED at a SNP when BOTH of its codes are 0 or 1 -- a half-missing genotype is missing, a
+ * second-ALT code is missing -- and g is the ALT dosage of a called individual.  For row x of I and row y of J, over the
+ * individuals called at both:
+ *     N    A = sum g_x    B = sum g_y    S = sum g_x g_y    H = #{g_x = 1 and g_y = 1}        (N, H <= 5120; A, B <= 10 240; S <= 20 480)
+ * and the two cells are those of the section above with the pair's OWN N, A and B in the place of n_hap / 2, acnt[i] and
+ * acnt[j]: T = 2 N, a_i = A, a_j = B, the same table n1 .. n4, the same x*, r and D' -- one device function, em_cell
+ * (ldx_em_tile.h), shared by both kernels, so a cell cannot depend on the kernel or the tile it came from.  Consequences:
+ *   a pair of rows without a missing code gives the ldx_ld_em_rect_dev cell bit for bit;
+ *   both cells are -0.0f when N = 0, or when A or B is 0 or 2 N within the joint set -- a SNP that is polymorphic overall but
+ *     monomorphic among the jointly called individuals included;
+ *   accuracy is the section above's: each cell within 2 float32 ulps of the exact value of its integers plus 2^-40 absolute;
+ *   a cell is a function of (N, A, B, S, H) alone, symmetric in the two SNPs: swapped sides give the transpose, permuted
+ *     individuals and rephased genotypes identical bits.
+ * The integers come from the FP4 matrix cores (ldx_em_pw.hip), five exact fp32 accumulator sets from three per-individual
+ * operands on each side; a 128 x 128 tile none of whose SNPs has acnt + rcnt != n_hap runs the two-set loop of the section
+ * above and reads N, A and B from n_hap / 2 and acnt.  No workspace, no library state.
+ *
+ * ldx_ld_em_rect_pw_dev: ldx_ld_em_rect_dev's outputs and output rules (either of out_r, out_dprime may be NULL, not both;
+ *   exactly the n_i x n_j words of each given output are written).
+ * ldx_ld_em_rect_pw_hits_dev: ldx_ld_em_rect_hits_dev's records {i, j, the r cell, the D' cell}, rule (ONE float32 multiply
+ *   against r2_bound > 0; -0.0f never a hit), slots and overflow; ldx_area_finish_ex_dev(n_snps = n_i, counts_ready = 0) finishes.
+ * ldx_ld_em_pw_counts_dev: counts[(s * n_i + i) * ld + j] = integer s of the pair as uint32, s in the order N A B S H: what
+ *   the K loop produced (the shortcut: what it read from the tables), before any float.
+ * ldx_ld_em_from_counts_pw_dev: the epilogue alone on m tuples (N[k], a1[k], a2[k], S[k], H[k]) -- ldx_ld_em_from_counts_dev with
+ *   a per-tuple N.  A tuple that is no genotype table (or has N > LDX_MAX_HAPS / 2) gives NaN in every output; N = 0 with every
+ *   other integer 0 is the degenerate pair: -0.0f, x = 0.  Any output may be NULL.
+ *
+ * Argument rules and codes are those of the EM and pairwise-complete entries, checked before any HIP call (ldx_last_error()
+ * names the argument): a null pointer, n_i, n_j or m = 0, ld < n_j, r2_bound not > 0, an odd n_hap = LDX_E_ARG; n_hap >
+ * LDX_MAX_HAPS or a bit plane of 4 GiB or more on either side = LDX_E_UNSUPPORTED.  All calls only enqueue work on `stream`. */
+int ldx_ld_em_rect_pw_dev(const void *alt_i, const void *ref_i, const uint32_t *acnt_i, const uint32_t *rcnt_i, uint32_t n_i,
+                          const void *alt_j, const void *ref_j, const uint32_t *acnt_j, const uint32_t *rcnt_j, uint32_t n_j,
+                          uint32_t n_hap, float *out_r, float *out_dprime, size_t ld_out, void *stream);
+int ldx_ld_em_rect_pw_hits_dev(const void *alt_i, const void *ref_i, const uint32_t *acnt_i, const uint32_t *rcnt_i, uint32_t n_i,
+                               const void *alt_j, const void *ref_j, const uint32_t *acnt_j, const uint32_t *rcnt_j, uint32_t n_j,
+                               uint32_t n_hap, float r2_bound, ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits, void *stream);
+int ldx_ld_em_pw_counts_dev(const void *alt_i, const void *ref_i, const uint32_t *acnt_i, const uint32_t *rcnt_i, uint32_t n_i,
+                            const void *alt_j, const void *ref_j, const uint32_t *acnt_j, const uint32_t *rcnt_j, uint32_t n_j,
+                            uint32_t n_hap, uint32_t *counts, size_t ld, void *stream);
+int ldx_ld_em_from_counts_pw_dev(size_t m, const uint32_t *N, const uint32_t *a1, const uint32_t *a2, const uint32_t *S,
+                                 const uint32_t *H, float *r, float *dprime, double *x, void *stream);
+
 /* ---- synthetic panels: deterministic, identical on host and device ------ */
 /* codes int8 [n_snps][ld_codes] receive global SNPs [snp_offset, snp_offset + n_snps) (a rank's
  * shard).  thresholds: per-SNP ALT probability * 2^64 (computed on the host, see

@@ -1,5 +1,5 @@
 // What the FP4 counting kernels share (triangle_mfma_kernel of ldx_mfma.hip, rect_kernel of ldx_rect.hip, em_kernel of
-// ldx_em.hip, pwc_kernel of ldx_pwc.hip and pwband_kernel of ldx_pwband.hip through ldx_pwc_tile.h): the operand encoding -- the exactness argument of the whole library, written once -- and the rectangle walk.
+// ldx_em.hip, em_pw_kernel of ldx_em_pw.hip, pwc_kernel of ldx_pwc.hip and pwband_kernel of ldx_pwband.hip through ldx_pwc_tile.h): the operand encoding -- the exactness argument of the whole library, written once -- and the rectangle walk.
 #pragma once
 
 #include "ldx_common.h"

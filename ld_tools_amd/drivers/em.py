@@ -2,11 +2,12 @@
 one list against every variant of another (what PLINK --r2 dprime reports for unphased genotype calls), as two dense float32
 matrices with the two variant lists that fix their rows and columns, and as a PLINK-style ``.ld`` table of the pairs above an
 r^2 threshold.  The inputs are those of ``drivers/rect.py``; the work is ``ops.ld_em`` / ``ops.ld_em_hits`` (include/ldx.h,
-"unphased LD by EM")."""
+"unphased LD by EM").  ``missing="pairwise"`` estimates every pair over the samples called at both variants, as PLINK and
+Haploview do with ``./.`` calls (include/ldx.h, "pairwise-complete EM")."""
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
 import numpy as np
 
@@ -39,11 +40,14 @@ def em_panels(vcf, chrom_i, rows_i, chrom_j, rows_j, sample_names: Sequence[str]
 
 
 def em_matrix(vcf, chrom_i, rows_i: Sequence[Sequence], chrom_j, rows_j: Sequence[Sequence],
-              sample_names: Sequence[str]) -> EmMatrix:
+              sample_names: Sequence[str], missing: Optional[str] = None) -> EmMatrix:
     """EM r and D' of the variants ``rows_i`` of chromosome ``chrom_i`` against the variants ``rows_j`` of ``chrom_j`` (VCF
-    rows [pos, rsID], as for ``rect_matrix``).  A missing call counts as REF."""
+    rows [pos, rsID], as for ``rect_matrix``).  ``missing=None``: a missing call counts as REF.  ``missing="pairwise"``: a
+    sample takes part in a pair only where it is called at both variants -- a ``./.`` call, a half-missing call (``0/.``)
+    and a call with a second ALT allele are all missing at that variant -- and a pair whose jointly called samples are none,
+    or monomorphic at either variant, is -0.0 in both matrices."""
     side_i, side_j, pi, pj = em_panels(vcf, chrom_i, rows_i, chrom_j, rows_j, sample_names)
-    out = ld_em(pi, pj)
+    out = ld_em(pi, pj, missing=missing)
     return EmMatrix(side_i, side_j, out.r, out.dprime)
 
 
@@ -67,10 +71,12 @@ def write_em_matrix(base: str, m: EmMatrix, rows_per_block: int = 1024) -> List[
     return paths
 
 
-def em_hits(vcf, chrom_i, rows_i, chrom_j, rows_j, sample_names: Sequence[str], r2: float = 0.2):
-    """The pairs with EM r^2 >= ``r2``: (rows' RectSide, columns' RectSide, LDRectHits of ops.ld_em_hits)."""
+def em_hits(vcf, chrom_i, rows_i, chrom_j, rows_j, sample_names: Sequence[str], r2: float = 0.2,
+            missing: Optional[str] = None):
+    """The pairs with EM r^2 >= ``r2``: (rows' RectSide, columns' RectSide, LDRectHits of ops.ld_em_hits).  ``missing``:
+    em_matrix's."""
     side_i, side_j, pi, pj = em_panels(vcf, chrom_i, rows_i, chrom_j, rows_j, sample_names)
-    return side_i, side_j, ld_em_hits(pi, pj, r2=r2)
+    return side_i, side_j, ld_em_hits(pi, pj, r2=r2, missing=missing)
 
 
 def write_ld_table(path: str, rows: RectSide, cols: RectSide, hits: LDRectHits) -> int:

@@ -14,6 +14,7 @@
     ld_rect_hits(panel_i, panel_j, r2=...)  the pairs of that rectangle with r^2 above a threshold, as a CSR
     ld_em(panel_i, panel_j)                 unphased LD by maximum likelihood: EM r and D' of two SNP sets (dense float32)
     ld_em_hits(panel_i, panel_j, r2=...)    the pairs of that rectangle whose EM r^2 reaches a threshold, with their D'
+                                            (both: missing="pairwise" = over the individuals called at both SNPs)
     pair_counts(panel_i, panel_j)           <- calc_ld.py:32           (bit-exact n11 block)
     ld_from_counts(n, n11, a1, r1, a2, r2)  <- calc_ld.py:33-97        (the epilogue alone)
 
@@ -2472,7 +2473,7 @@ class LDRectHits:
     bound: np.float32       # the float32 bound on s (r2_bound)
     dosage: bool = False
     em: bool = False        # ld_em_hits: r is the EM r and column 3 of ``hits`` the D' cell instead of s
-    missing: Optional[str] = None   # "pairwise": the cells are ld_rect(missing="pairwise")'s
+    missing: Optional[str] = None   # "pairwise": the cells are ld_rect(missing="pairwise")'s (``em``: ld_em(missing="pairwise")'s)
 
     @property
     def j(self) -> torch.Tensor:
@@ -2635,7 +2636,7 @@ class LDEm:
 
 
 def ld_em(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, out_r=None, out_dprime=None,
-          want_r: bool = True, want_dprime: bool = True) -> LDEm:
+          want_r: bool = True, want_dprime: bool = True, missing: Optional[str] = None) -> LDEm:
     """Unphased LD by maximum likelihood of every SNP of ``panel_i`` against every SNP of ``panel_j`` (None: ``panel_i``
     itself) over the same individuals (even n_hap; individual k owns haplotypes 2k and 2k + 1): the EM haplotype frequency of
     the genotype table, and from it ``.r`` and ``.dprime``, float32 [n_i, n_j] on the device (include/ldx.h, "unphased LD by
@@ -2644,7 +2645,14 @@ def ld_em(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, out_r=Non
 
     ``out_r`` / ``out_dprime``: float32 device tensors [n_i, >= n_j] with unit column stride and one row stride to write into;
     the columns beyond n_j are left untouched.  ``want_r`` / ``want_dprime`` = False leaves that matrix out (None in the
-    result); not both."""
+    result); not both.
+
+    ``missing="pairwise"``: every pair over the individuals called at BOTH SNPs (both codes of the individual 0 or 1: a
+    half-missing genotype is missing), as PLINK --r2 dprime and Haploview treat missing calls -- the pair's own N, A = sum g_x,
+    B = sum g_y, S and H through the same epilogue (include/ldx.h, "pairwise-complete EM"; ldx_ld_em_rect_pw_dev).  A pair of
+    rows without missing codes gives the ``missing=None`` cell bit for bit; -0.0f in both where the joint set is empty or
+    either SNP is monomorphic within it.  None: the call as it always was (a missing code counts as REF)."""
+    pairwise = _rect_missing("ld_em", missing)
     pj = _rect_panels("ld_em", panel_i, panel_j, True)
     n_i, n_j, dev = panel_i.n_snps, pj.n_snps, panel_i.device
     if not ((want_r or out_r is not None) or (want_dprime or out_dprime is not None)):
@@ -2664,39 +2672,59 @@ def ld_em(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, out_r=Non
         out_r = torch.empty((n_i, ld), dtype=torch.float32, device=dev)
     if out_dprime is None and want_dprime:
         out_dprime = torch.empty((n_i, ld), dtype=torch.float32, device=dev)
-    check(lib.ldx_ld_em_rect_dev(panel_i.alt.data_ptr(), panel_i.acnt.data_ptr(), n_i, pj.alt.data_ptr(), pj.acnt.data_ptr(),
-                                 n_j, panel_i.n_hap, out_r.data_ptr() if out_r is not None else None,
-                                 out_dprime.data_ptr() if out_dprime is not None else None, ld, _stream_ptr()),
-          "ldx_ld_em_rect_dev")
+    outs = (out_r.data_ptr() if out_r is not None else None, out_dprime.data_ptr() if out_dprime is not None else None)
+    if pairwise:
+        check(lib.ldx_ld_em_rect_pw_dev(*_pw_side(panel_i), *_pw_side(pj), panel_i.n_hap, *outs, ld, _stream_ptr()),
+              "ldx_ld_em_rect_pw_dev")
+    else:
+        check(lib.ldx_ld_em_rect_dev(panel_i.alt.data_ptr(), panel_i.acnt.data_ptr(), n_i, pj.alt.data_ptr(), pj.acnt.data_ptr(),
+                                     n_j, panel_i.n_hap, *outs, ld, _stream_ptr()), "ldx_ld_em_rect_dev")
     return LDEm(out_r[:, :n_j] if out_r is not None else None, out_dprime[:, :n_j] if out_dprime is not None else None)
 
 
 def ld_em_hits(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, r2: float = 0.2, strict: bool = False,
-               hit_capacity: Optional[int] = None) -> LDRectHits:
+               hit_capacity: Optional[int] = None, missing: Optional[str] = None) -> LDRectHits:
     """The pairs (row i of ``panel_i``, row j of ``panel_j``) whose EM r has r^2 >= ``r2`` (``strict``: r^2 > r2): r the ld_em
     cell bit for bit, r^2 one float32 multiply (include/ldx.h, ldx_ld_em_rect_hits_dev + ldx_area_finish_ex_dev).  The result
     is ld_rect_hits' CSR with ``em`` set: column 3 of ``hits`` holds the D' cell (``.dprime``).  Buffers and retries are
-    ld_rect_hits'."""
+    ld_rect_hits'.  ``missing="pairwise"``: the cells are ld_em(missing="pairwise")'s (ldx_ld_em_rect_pw_hits_dev)."""
+    pairwise = _rect_missing("ld_em_hits", missing)
     pj = _rect_panels("ld_em_hits", panel_i, panel_j, True)
     bound = r2_bound(r2, strict)
     require_gpu()
     n_i, n_j = panel_i.n_snps, pj.n_snps
 
     def launch(raw, cap, n_hits):
+        if pairwise:
+            check(lib.ldx_ld_em_rect_pw_hits_dev(*_pw_side(panel_i), *_pw_side(pj), panel_i.n_hap, float(bound), raw.data_ptr(),
+                                                 cap, n_hits.data_ptr(), _stream_ptr()), "ldx_ld_em_rect_pw_hits_dev")
+            return
         check(lib.ldx_ld_em_rect_hits_dev(panel_i.alt.data_ptr(), panel_i.acnt.data_ptr(), n_i, pj.alt.data_ptr(),
                                           pj.acnt.data_ptr(), n_j, panel_i.n_hap, float(bound), raw.data_ptr(), cap,
                                           n_hits.data_ptr(), _stream_ptr()), "ldx_ld_em_rect_hits_dev")
 
     offsets, hits = _rect_hits_run("ld_em_hits", launch, n_i, n_j, panel_i.device, hit_capacity)
-    return LDRectHits(offsets, hits, n_i, n_j, bound, False, True)
+    return LDRectHits(offsets, hits, n_i, n_j, bound, False, True, missing=missing)
 
 
-def ld_em_counts(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+EM_PAIRWISE_COUNTS = ("N", "A", "B", "S", "H")   # the order of include/ldx.h, "pairwise-complete EM"
+
+
+def ld_em_counts(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, missing: Optional[str] = None):
     """The two pair counts the EM starts from, as the kernel's K loop produced them: (S, H), int32 [n_i, n_j] each on the
-    device -- S = sum_k g_ik g_jk, H = the number of individuals heterozygous at both SNPs (ldx_ld_em_counts_dev)."""
+    device -- S = sum_k g_ik g_jk, H = the number of individuals heterozygous at both SNPs (ldx_ld_em_counts_dev).
+
+    ``missing="pairwise"``: the five integers of ld_em(missing="pairwise") over the individuals called at both SNPs, before
+    any float: one int32 [5, n_i, n_j] device tensor in the order N A B S H (ldx_ld_em_pw_counts_dev)."""
+    pairwise = _rect_missing("ld_em_counts", missing)
     pj = _rect_panels("ld_em_counts", panel_i, panel_j, True)
     require_gpu()
     n_i, n_j, dev = panel_i.n_snps, pj.n_snps, panel_i.device
+    if pairwise:
+        out = torch.empty((len(EM_PAIRWISE_COUNTS), n_i, n_j), dtype=torch.int32, device=dev)
+        check(lib.ldx_ld_em_pw_counts_dev(*_pw_side(panel_i), *_pw_side(pj), panel_i.n_hap, out.data_ptr(), n_j, _stream_ptr()),
+              "ldx_ld_em_pw_counts_dev")
+        return out
     S = torch.empty((n_i, n_j), dtype=torch.int32, device=dev)
     H = torch.empty((n_i, n_j), dtype=torch.int32, device=dev)
     check(lib.ldx_ld_em_counts_dev(panel_i.alt.data_ptr(), n_i, pj.alt.data_ptr(), n_j, panel_i.n_hap, S.data_ptr(),
@@ -2704,24 +2732,30 @@ def ld_em_counts(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None) ->
     return S, H
 
 
-def ld_em_from_counts(n_ind: int, a_i, a_j, S, H, device: Optional[torch.device] = None):
-    """The EM epilogue alone on a list of count tuples of ``n_ind`` individuals -- the device function of ld_em's kernel
+def ld_em_from_counts(n_ind, a_i, a_j, S, H, device: Optional[torch.device] = None):
+    """The EM epilogue alone on a list of count tuples of ``n_ind`` individuals -- the device function of ld_em's kernels
     (ldx_ld_em_from_counts_dev).  Returns (r float32, dprime float32, x float64) device tensors [m]; a tuple that is no
-    genotype table gives NaN in all three."""
+    genotype table gives NaN in all three.  ``n_ind`` may be an array, one N per tuple -- the pairwise-complete form, whose N
+    is the pair's own (ldx_ld_em_from_counts_pw_dev): N = 0 with every other integer 0 is a degenerate pair (-0.0f)."""
     require_gpu()
     dev = device or torch.device("cuda", torch.cuda.current_device())
+    per_tuple = hasattr(n_ind, "cpu") or np.ndim(n_ind) > 0
     cols = []
-    for name, v in (("a_i", a_i), ("a_j", a_j), ("S", S), ("H", H)):
+    for name, v in ((("n_ind", n_ind),) if per_tuple else ()) + (("a_i", a_i), ("a_j", a_j), ("S", S), ("H", H)):
         v = np.ascontiguousarray(v.cpu().numpy() if hasattr(v, "cpu") else v).reshape(-1)
         if v.size and (int(v.min()) < 0 or int(v.max()) >= (1 << 32)):
             raise _lib.LdxError(f"ld_em_from_counts: {name} must hold uint32 values")
         cols.append(torch.from_numpy(v.astype(np.int64).astype(np.uint32).view(np.int32)).to(dev))
     m = int(cols[0].numel())
     if any(int(c.numel()) != m for c in cols):
-        raise _lib.LdxError("ld_em_from_counts: a_i, a_j, S and H differ in length")
+        raise _lib.LdxError("ld_em_from_counts: " + ("n_ind, " if per_tuple else "") + "a_i, a_j, S and H differ in length")
     r = torch.empty(m, dtype=torch.float32, device=dev)
     dprime = torch.empty(m, dtype=torch.float32, device=dev)
     x = torch.empty(m, dtype=torch.float64, device=dev)
+    if per_tuple:
+        check(lib.ldx_ld_em_from_counts_pw_dev(m, *(c.data_ptr() for c in cols), r.data_ptr(), dprime.data_ptr(), x.data_ptr(),
+                                               _stream_ptr()), "ldx_ld_em_from_counts_pw_dev")
+        return r, dprime, x
     check(lib.ldx_ld_em_from_counts_dev(int(n_ind), m, cols[0].data_ptr(), cols[1].data_ptr(), cols[2].data_ptr(),
                                         cols[3].data_ptr(), r.data_ptr(), dprime.data_ptr(), x.data_ptr(), _stream_ptr()),
           "ldx_ld_em_from_counts_dev")
@@ -2729,7 +2763,7 @@ def ld_em_from_counts(n_ind: int, a_i, a_j, S, H, device: Optional[torch.device]
 
 
 def _em_root_host(g, dg, lo, hi, glo, ghi):
-    """em_root of ldx_em.hip: Newton steps kept inside [lo, hi] (g(lo) <= 0 <= g(hi)), bisection otherwise."""
+    """em_root of ldx_em_tile.h: Newton steps kept inside [lo, hi] (g(lo) <= 0 <= g(hi)), bisection otherwise."""
     if glo == 0.0:
         return lo
     if ghi == 0.0:
@@ -2761,7 +2795,8 @@ def _em_root_host(g, dg, lo, hi, glo, ghi):
 
 def em_host(n_ind: int, a_i: int, a_j: int, S: int, H: int) -> Tuple[float, float, float]:
     """The kernel's epilogue restated in Python floats (fp64): (x*, r, D') of one count tuple (include/ldx.h, "unphased LD
-    by EM"; ldx_em.hip, em_cell).  Documentation and a CPU reference: it follows the device path for path -- H = 0 closed
+    by EM"; ldx_em_tile.h, em_cell).  The integers are per pair: with the pair's own (N, A, B, S, H) over the individuals
+    called at both SNPs this is the pairwise-complete cell (N = 0 is a degenerate pair).  Documentation and a CPU reference: it follows the device path for path -- H = 0 closed
     form; g monotone or one rising branch with a sign change: one bracketed Newton root, no logarithm; two candidates: the
     larger l, the smaller x on a tie -- but is not promised to match it bit for bit.  A degenerate pair gives (0, -0.0, -0.0),
     a tuple that is no genotype table three NaNs."""
