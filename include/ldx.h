@@ -921,6 +921,53 @@ int ldx_ld_em_pw_counts_dev(const void *alt_i, const void *ref_i, const uint32_t
 int ldx_ld_em_from_counts_pw_dev(size_t m, const uint32_t *N, const uint32_t *a1, const uint32_t *a2, const uint32_t *S,
                                  const uint32_t *H, float *r, float *dprime, double *x, void *stream);
 
+/* ---- EM on the band: the EM r and D' of the in-window pairs of one panel, stored or as neighbour lists -----------------------
+ * The EM entries above give a rectangle; the standard request -- PLINK --r2 dprime --ld-window-kb over a chromosome -- is the
+ * band of ONE panel.  For every pair i > j with pos_i - pos_j <= window the two cells are those of ldx_ld_em_rect_dev
+ * (pairwise != 0: ldx_ld_em_rect_pw_dev) for that panel against itself at (i, j), bit for bit: the same integers through the
+ * same device function em_cell.  A kernel of its own on the FP4 matrix cores (ldx_emband.hip), which walks the 128 x 128
+ * tiles of the lower band only and runs the fp64 root search for the cells inside the window only.
+ *
+ * Every entry takes the panel's ALT plane and acnt table; `pairwise` (0: a missing code counts as REF, N = n_hap / 2; else
+ * every pair over the individuals called at both SNPs) and then also the REF plane and the rcnt table, which may be NULL
+ * only when pairwise is 0; n_hap even; positions (int64 [n_snps], NON-DECREASING, duplicates allowed) and window >= 0 in
+ * their units (values above 2^52 act as 2^52; the comparison is (double)pos_i - (double)pos_j <= window).
+ *
+ * ldx_em_snp_stats_dev: per SNP, over its OWN called individuals (it takes no window): N[i] of them and A[i] the sum of their
+ *   dosages (pairwise = 0: n_hap / 2 and acnt[i]); live iff 0 < A < 2 N -- the SNP has both alleles among them.  This is not
+ *   ldx_pw_snp_stats_dev's dosage `live`: an all-heterozygous SNP has no dosage variance but is a live EM SNP.  diag[i]
+ *   (float32 [n_snps]) = +1.0f if live, else -0.0f: the band's diagonal is DEFINED, not computed by em_cell (whose tie rule
+ *   gives -1 for an all-heterozygous SNP against itself).  N, A uint32 [n_snps]; live uint8 [n_snps] or NULL.
+ * ldx_ld_em_band_dev: values_r[offsets[i] + j - lo[i]] = r, values_dprime[the same] = D', in the layout of
+ *   ldx_ld_band_layout_dev for the same positions and window.  Either output may be NULL, not both (both only when n_cells is
+ *   0, which returns LDX_OK and launches nothing).  The guard is ldx_ld_pw_band_dev's -- a store only where lo[i] <= j < i and
+ *   the index is < n_cells -- so every one of the offsets[n_snps] cells is written (no memset) and nothing else.  values_r with
+ *   the diagonal above is a band like any other: ldx_band_score_dev and ldx_band_matvec_dev take it.
+ * ldx_ld_em_neighbors_dev: every pair with r *f32 r >= r2_bound (ONE float32 multiply; r2_bound a float32 > 0, so -0.0f is
+ *   never kept) as the records {i, j, r, D'} and {j, i, r, D'} -- the fourth word carries the D' cell, as in
+ *   ldx_ld_em_rect_hits_dev, not r^2 -- in the slots of ldx_ld_rect_hits_dev (*n_hits is zeroed by the call and receives the slots
+ *   reserved; beyond hit_cap nothing is stored).  ldx_area_finish_ex_dev(counts_ready = 0) turns the slots into the per-SNP
+ *   neighbour CSR of ldx_ld_neighbors_dev.
+ *
+ * workspace: ldx_ld_em_band_workspace_bytes(n_snps) bytes, 256-byte aligned, no initialisation needed (the call's first
+ * kernels write what the band kernel reads: each row's first in-window column and the tiles in front of each block of 128
+ * rows): ONE workspace per launch that may be in flight.  Argument rules, checked before any HIP call (ldx_last_error() names
+ * the argument): a null pointer (ref, rcnt: only with pairwise), n_snps or n_hap = 0, an odd n_hap, a negative window, r2_bound
+ * not > 0, both value pointers NULL with n_cells > 0, a workspace too small = LDX_E_ARG; n_hap > LDX_MAX_HAPS or a bit plane of
+ * 4 GiB or more = LDX_E_UNSUPPORTED.  All calls only enqueue work on `stream`: no allocation, no synchronisation, no library
+ * state. */
+size_t ldx_ld_em_band_workspace_bytes(uint32_t n_snps);
+int ldx_em_snp_stats_dev(const void *alt, const void *ref, const uint32_t *acnt, const uint32_t *rcnt, uint32_t n_snps,
+                         uint32_t n_hap, int pairwise, uint32_t *N, uint32_t *A, float *diag, uint8_t *live, void *stream);
+int ldx_ld_em_band_dev(const void *alt, const void *ref, const uint32_t *acnt, const uint32_t *rcnt, uint32_t n_snps,
+                       uint32_t n_hap, int pairwise, const int64_t *positions, int64_t window, const uint32_t *lo,
+                       const uint64_t *offsets, float *values_r, float *values_dprime, uint64_t n_cells, void *workspace,
+                       size_t workspace_bytes, void *stream);
+int ldx_ld_em_neighbors_dev(const void *alt, const void *ref, const uint32_t *acnt, const uint32_t *rcnt, uint32_t n_snps,
+                            uint32_t n_hap, int pairwise, const int64_t *positions, int64_t window, float r2_bound,
+                            ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits, void *workspace, size_t workspace_bytes,
+                            void *stream);
+
 /* ---- synthetic panels: deterministic, identical on host and device ------ */
 /* codes int8 [n_snps][ld_codes] receive global SNPs [snp_offset, snp_offset + n_snps) (a rank's
  * shard).  thresholds: per-SNP ALT probability * 2^64 (computed on the host, see

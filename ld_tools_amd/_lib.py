@@ -187,6 +187,10 @@ SIGNATURES = {
                                           _vp]),
     "ldx_ld_em_pw_counts_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _sz, _vp]),
     "ldx_ld_em_from_counts_pw_dev": (_int, [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ldx_ld_em_band_workspace_bytes": (_sz, [_u32]),
+    "ldx_em_snp_stats_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _int, _vp, _vp, _vp, _vp, _vp]),
+    "ldx_ld_em_band_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _int, _vp, _i64, _vp, _vp, _vp, _vp, _u64, _vp, _sz, _vp]),
+    "ldx_ld_em_neighbors_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _int, _vp, _i64, C.c_float, _vp, _u64, _vp, _vp, _sz, _vp]),
     "ldx_ld_select_workspace_bytes": (_sz, [_u32]),
     "ldx_ld_select_dev": (_int, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ldx_set_area_path": (_int, [_int]),

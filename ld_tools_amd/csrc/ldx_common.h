@@ -123,7 +123,7 @@ __host__ __device__ inline uint64_t tile_base(uint64_t t, uint64_t G) { return t
 // back with a larger buffer.  So every slot below min(*n_hits, hit_cap) holds a record or the mark, which is exactly what the
 // consumer, ldx_area_finish_ex_dev (ldx_area.hip), relies on.  `counts`, where given, receives the STORED records per query
 // row: what the consumer's scatter will place.
-// Users: area_scan_kernel, rect_kernel, em_kernel, em_pw_kernel, pwc_kernel, pwband_kernel.  The band epilogues of triangle_mfma_kernel keep the same protocol as the
+// Users: area_scan_kernel, rect_kernel, em_kernel, em_pw_kernel, pwc_kernel, pwband_kernel, emband_kernel.  The band epilogues of triangle_mfma_kernel keep the same protocol as the
 // text of a macro (LDX_HIT_APPENDER, ldx_mfma.hip), because that kernel's instruction stream must not move.
 constexpr uint32_t kHitBatch = 256;              // slots a wave reserves per atomic
 constexpr uint32_t kHitInvalid = 0xFFFFFFFFu;    // `query` of an unused slot

@@ -9,7 +9,8 @@
 //     (band_layout_kernel's comparison).  Positions are non-decreasing, so the band kernel's per-cell predicate -- j < i and
 //     pos_i - pos_j <= window -- IS low[i] <= j < i: a cell needs one table word of its row, not two positions.
 //   * walk: only the lower band.  I block ti (rows [256 ti, r1), r1 = min(256 (ti + 1), n)) meets the slabs low[256 ti] / 128 ..
-//     (r1 - 1) / 128: low is non-decreasing, so these cover every in-window j < i of the block.  The plan kernel writes the
+//     (r1 - 1) / 128: low is non-decreasing, so these cover every in-window j < i of the block.  The plan kernel (ldx_band_plan.h,
+//     shared with emband_kernel) writes the
 //     exclusive prefix of those counts, and their total, into the workspace; tile t is (ti, tj) with prefix[ti] <= t <
 //     prefix[ti + 1] (a binary search) and tj = first slab + t - prefix[ti].  The grid is fixed -- two workgroups per CU -- and a
 //     workgroup strides over the tile numbers: no host read of the total.  Consecutive tile numbers, which run side by side,
@@ -21,6 +22,7 @@
 //     is reduced over the 32 lanes of the half-wave, a column's when the pass ends and is reduced over the two half-waves; then
 //     ONE 64-bit integer atomic per row / column and wave.  A launch adds to ONE word of every SNP (Args::word); the
 //     annotation words take further launches.
+#include "ldx_band_plan.h"
 #include "ldx_pwc_tile.h"
 
 namespace ldx {
@@ -29,7 +31,7 @@ namespace pwband {
 using namespace pwc;
 
 enum Op : int { kStore = 0, kScore = 1, kNbr = 2 };
-constexpr uint32_t kNoRow = 0xFFFFFFFFu;   // `low` of a row beyond the panel: no column reaches it
+using bandplan::kNoRow;
 
 struct Args {
     Side s;                    // the panel: both sides of every tile
@@ -127,12 +129,8 @@ __global__ void __launch_bounds__(kThreads, 2) pwband_kernel(Args p)
     const uint64_t total = p.prefix[Ti];
     BandEpi<kOp, kDosage> epi{p, bl, HitAppender{p.hits, p.hit_cap, p.n_hits, threadIdx.x & 63u}};
     for (uint64_t t = blockIdx.x; t < total; t += gridDim.x) {   // workgroup-uniform
-        uint32_t a = 0, b = Ti - 1u;   // the last I block with prefix[ti] <= t: prefix[a] <= t < prefix[b + 1]
-        while (a < b) {
-            const uint32_t mid = a + (b - a + 1u) / 2u;
-            if (p.prefix[mid] <= t) a = mid; else b = mid - 1u;
-        }
-        const uint32_t ti = a, tj = p.low[ti * kTileRows] / kSlab + (uint32_t)(t - p.prefix[ti]);
+        uint32_t ti, tj;
+        bandplan::tile_at<kTileRows>(p.prefix, p.low, Ti, t, ti, tj);
         if (t != blockIdx.x) block_sync();   // the last tile's tables and image are free
         // (the thread's number as a value of THIS trip: what tile_body derives from it -- a few dozen lane offsets -- would
         // otherwise be made once in front of the loop and held in registers across every K loop, which no longer fits)
@@ -152,55 +150,6 @@ __global__ void __launch_bounds__(kThreads, 2) pwband_kernel(Args p)
         tile_body<kDosage, true>(sm, p.s, p.s, p.nblocks, p.n_hap, ti, tj, tid, epi);   // (its first barrier publishes the tables)
     }
     if constexpr (kOp == kNbr) epi.hit.close();   // what is left of the wave's last batch
-}
-
-// low[m]: band_layout_kernel's search (ldx_band.hip), one thread per SNP
-__global__ void __launch_bounds__(256) low_kernel(const int64_t *__restrict__ pos, uint32_t n_snps, double window,
-                                                  uint32_t *__restrict__ low)
-{
-    const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= n_snps) return;
-    const double pi = (double)pos[m];
-    uint32_t a = 0, b = m;   // the first j in [0, m] inside the window (j = m always is)
-    while (a < b) {
-        const uint32_t mid = a + (b - a) / 2u;
-        if (pi - (double)pos[mid] <= window) b = mid; else a = mid + 1u;
-    }
-    low[m] = a;
-}
-
-// prefix[ti] = tiles of the I blocks in front of ti, prefix[Ti] = all: one workgroup, 256 I blocks per trip, the running
-// total carried in a register every thread holds
-__global__ void __launch_bounds__(256) plan_kernel(const uint32_t *__restrict__ low, uint32_t n_snps, uint64_t *__restrict__ prefix)
-{
-    __shared__ uint32_t cnt[256];
-    __shared__ uint64_t pre[257];
-    const uint32_t tid = threadIdx.x, Ti = (n_snps + kTileRows - 1u) / kTileRows;
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < Ti; base += 256u) {
-        const uint32_t ti = base + tid;
-        uint32_t c = 0;
-        if (ti < Ti) {
-            const uint32_t r1 = n_snps - ti * kTileRows < kTileRows ? n_snps : (ti + 1u) * kTileRows;
-            const uint32_t first = low[ti * kTileRows] / kSlab, last = (r1 - 1u) / kSlab;
-            c = last >= first ? last - first + 1u : 0u;
-        }
-        cnt[tid] = c;
-        block_sync();
-        if (tid == 0u) {
-            uint64_t s = carry;
-            for (uint32_t k = 0; k < 256u; ++k) {
-                pre[k] = s;
-                s += cnt[k];
-            }
-            pre[256] = s;
-        }
-        block_sync();
-        if (ti < Ti) prefix[ti] = pre[tid];
-        carry = pre[256];
-        block_sync();   // cnt and pre are free again
-    }
-    if (tid == 0u) prefix[Ti] = carry;
 }
 
 // diag / live of one SNP over its OWN called set: one wavefront per row.  Haplotype form: a r > 0, from the tables.  Dosage
@@ -251,26 +200,17 @@ __global__ void score_init_kernel(const float *__restrict__ diag, const uint8_t 
     for (uint32_t c = 0; c < st; ++c) sums[(size_t)i * st + c] = ((m >> c) & 1u) ? t : 0u;
 }
 
-// the workspace: prefix [Ti + 1] uint64, then low [n] uint32, each part a multiple of 256 bytes
-static size_t prefix_bytes(uint32_t n_snps)
-{
-    return (((size_t)(n_snps + kTileRows - 1u) / kTileRows + 1u) * sizeof(uint64_t) + 255u) / 256u * 256u;
-}
-static size_t workspace_bytes(uint32_t n_snps) { return prefix_bytes(n_snps) + ((size_t)n_snps * sizeof(uint32_t) + 255u) / 256u * 256u; }
+// the workspace: the plan's (ldx_band_plan.h) for I blocks of kTileRows rows
+static size_t workspace_bytes(uint32_t n_snps) { return bandplan::workspace_bytes<kTileRows>(n_snps); }
 
 // low, the plan, then the band: everything in stream order, nothing read back
 template <int kOp>
 static int launch(Args &p, bool dosage, const int64_t *positions, int64_t window, void *workspace, hipStream_t s)
 {
     const uint32_t n = p.s.n;
-    uint64_t *const prefix = (uint64_t *)workspace;
-    uint32_t *const low = (uint32_t *)((char *)workspace + prefix_bytes(n));
-    const int64_t wmax = (int64_t)1 << 52;   // positions and window travel as doubles
-    low_kernel<<<(n + 255u) / 256u, 256, 0, s>>>(positions, n, (double)(window > wmax ? wmax : window), low);
-    LDX_HIP(hipGetLastError());
-    plan_kernel<<<1, 256, 0, s>>>(low, n, prefix);
-    LDX_HIP(hipGetLastError());
-    p.prefix = prefix, p.low = low;
+    bandplan::Plan plan;
+    if (const int rc = bandplan::make_plan<kTileRows>(positions, n, window, workspace, s, plan)) return rc;
+    p.prefix = plan.prefix, p.low = plan.low;
     const uint64_t tiles = (uint64_t)((n + kTileRows - 1u) / kTileRows) * n_slabs(n);   // (an upper bound of the plan's total)
     const uint64_t cap = 2u * (uint64_t)device_cus();                                    // two workgroups per CU are resident
     const uint32_t grid = (uint32_t)(tiles < cap ? tiles : cap);

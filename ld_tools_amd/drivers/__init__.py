@@ -18,7 +18,8 @@ from .ingest import RaggedGenotypesError, codes_matrix, find_record, haplotype_c
 from .ldscore import LDScoreTable, ld_scores, ld_scores_by_group, write_ldscore  # noqa: F401
 from .rmatrix import RMatrix, r_matrix, write_r_matrix  # noqa: F401
 from .rect import RectMatrix, RectSide, rect_matrix, write_rect_matrix  # noqa: F401
-from .em import EmMatrix, em_hits, em_matrix, write_em_matrix, write_ld_table  # noqa: F401
+from .em import (EmBand, EmMatrix, em_band, em_hits, em_matrix, em_window_hits, write_em_band,  # noqa: F401
+                 write_em_matrix, write_ld_table)
 from .prune import PruneTable, prune, write_prune  # noqa: F401
 from .regions import write_regions  # noqa: F401
 from .lite import DifChrsError, NotInIntgenConvDbError, NotRsIdError, check_rs_id, ld_lite_table  # noqa: F401

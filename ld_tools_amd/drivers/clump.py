@@ -11,7 +11,7 @@ the ALT dosages over the samples instead (ldx_ld_neighbors_dosage_dev; a missing
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
 import numpy as np
 
@@ -60,15 +60,19 @@ def chrom_panel(vcf, chrom, chrom_rows: Sequence[Sequence], sample_names: Sequen
 
 
 def clump(vcf, chrom, chrom_rows: Sequence[Sequence], sample_names: Sequence[str], pvalues: Sequence[float],
-          p1: float = 1e-4, p2: float = 1e-2, r2: float = 0.5, window_bp: int = 250_000, dosage: bool = False) -> ClumpTable:
+          p1: float = 1e-4, p2: float = 1e-2, r2: float = 0.5, window_bp: int = 250_000, dosage: bool = False,
+          em: bool = False, missing: Optional[str] = None) -> ClumpTable:
     """Clumps of one chromosome's variants (VCF rows [pos, rsID], one p-value per input row).  ``dosage``: genotype-dosage
-    r (ops.ld_clump)."""
+    r (ops.ld_clump).  ``em``: the EM r of the unphased genotypes; with ``missing="pairwise"`` -- every pair over the samples
+    called at both variants -- PLINK --clump's own r^2.  ``missing`` is passed through only where it is given."""
     p_in = np.asarray(pvalues, dtype=np.float64)
     if p_in.shape != (len(chrom_rows),):
         raise LdxError("clump: one p-value per input row is needed")
     panel, rows, rs_ids, poss = chrom_panel(vcf, chrom, chrom_rows, sample_names, "clump")
     p = p_in[rows]
-    res = ld_clump(panel, np.asarray(poss, dtype=np.int64), p, p1=p1, p2=p2, r2=r2, window_bp=window_bp, dosage=dosage)
+    more = {} if missing is None else {"missing": missing}
+    res = ld_clump(panel, np.asarray(poss, dtype=np.int64), p, p1=p1, p2=p2, r2=r2, window_bp=window_bp, dosage=dosage, em=em,
+                   **more)
     return ClumpTable(str(chrom), rs_ids, poss, p, res)
 
 

@@ -3,7 +3,12 @@ one list against every variant of another (what PLINK --r2 dprime reports for un
 matrices with the two variant lists that fix their rows and columns, and as a PLINK-style ``.ld`` table of the pairs above an
 r^2 threshold.  The inputs are those of ``drivers/rect.py``; the work is ``ops.ld_em`` / ``ops.ld_em_hits`` (include/ldx.h,
 "unphased LD by EM").  ``missing="pairwise"`` estimates every pair over the samples called at both variants, as PLINK and
-Haploview do with ``./.`` calls (include/ldx.h, "pairwise-complete EM")."""
+Haploview do with ``./.`` calls (include/ldx.h, "pairwise-complete EM").
+
+``em_band`` / ``write_em_band`` / ``em_window_hits`` are the one-chromosome forms -- PLINK ``--r2 dprime --ld-window-kb
+--ld-window-r2``: the EM r and D' of every pair of variants within ``window_bp`` of each other in drivers/band.py's layout, and
+the ``.ld`` table of the in-window pairs above the threshold, each pair once (ops.ld_em_band / ops.ld_neighbors(em=True);
+include/ldx.h, "EM on the band")."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -12,9 +17,11 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from .._lib import LdxError
-from ..ops import LDRectHits, ld_em, ld_em_hits
+from ..ops import LDEmBand, LDRectHits, ld_em, ld_em_band, ld_em_hits, ld_neighbors
 from ..panel import PackedPanel
+from .clump import chrom_panel
 from .rect import RectSide, read_sides, write_variants
+from .rmatrix import VARIANTS_HEADER
 
 LD_HEADER = "SNP_A\tSNP_B\tR2\tDP\n"
 
@@ -89,3 +96,76 @@ def write_ld_table(path: str, rows: RectSide, cols: RectSide, hits: LDRectHits) 
         for a, b, rv, dv in zip(i.tolist(), j.tolist(), r.astype(np.float64).tolist(), dp.astype(np.float64).tolist()):
             out.write(f"{rows.rs_ids[a]}\t{cols.rs_ids[b]}\t{rv * rv:.6f}\t{dv:.6f}\n")
     return int(i.size)
+
+
+@dataclass
+class EmBand:
+    """Row k of the two bands is variant k of these lists (position-sorted; variants without a matching record are left out)."""
+
+    chrom: str
+    rs_ids: List[str]
+    poss: List[int]
+    alt_freqs: List[float]            # round(a / n, 4) of code 1 over all haplotypes, as the reference reports it
+    bands: LDEmBand
+
+    @property
+    def n(self) -> int:
+        return len(self.rs_ids)
+
+
+def _chrom_em_panel(what: str, vcf, chrom, chrom_rows, sample_names):
+    panel, _, rs_ids, poss = chrom_panel(vcf, chrom, chrom_rows, sample_names, what)
+    if panel.n_hap % 2:
+        raise LdxError(f"{what}: {panel.n_hap} haplotypes: unphased LD needs diploid calls (an even count)")
+    return panel, rs_ids, poss
+
+
+def em_band(vcf, chrom, chrom_rows: Sequence[Sequence], sample_names: Sequence[str], window_bp: int = 1_000_000,
+            missing: Optional[str] = None) -> EmBand:
+    """The stored EM r and D' bands of one chromosome's variants (VCF rows [pos, rsID]; each record fetched once).
+    ``missing``: em_matrix's."""
+    panel, rs_ids, poss = _chrom_em_panel("em_band", vcf, chrom, chrom_rows, sample_names)
+    bands = ld_em_band(panel, np.asarray(poss, dtype=np.int64), window_bp=window_bp, missing=missing)
+    return EmBand(str(chrom), rs_ids, poss, panel.alt_freq4().cpu().numpy().tolist(), bands)
+
+
+def write_em_band(base: str, m: EmBand, cells_per_block: int = 1 << 26) -> List[str]:
+    """``{base}.band.r.npy`` and ``{base}.band.dprime.npy`` (float32 [n_cells] each, written in blocks through a memory map),
+    ``{base}.band.offsets.npy`` (uint64 [n + 1]), ``{base}.band.lo.npy`` (uint32 [n]) -- cell (i, j), lo[i] <= j < i, is word
+    offsets[i] + j - lo[i] of both --, ``{base}.band.diag.npy`` (float32 [n]: +1 where the variant has both alleles among its
+    called samples, else -0.0) and ``{base}.variants.tsv`` (index, rsID, position, ALT frequency).  Returns the six paths."""
+    b = m.bands.r
+    paths = [base + ".band.r.npy", base + ".band.dprime.npy", base + ".band.offsets.npy", base + ".band.lo.npy",
+             base + ".band.diag.npy", base + ".variants.tsv"]
+    for path, band in zip(paths, (m.bands.r, m.bands.dprime)):
+        mm = np.lib.format.open_memmap(path, mode="w+", dtype=np.float32, shape=(band.n_cells,))
+        try:
+            for c0 in range(0, band.n_cells, cells_per_block):
+                c1 = min(band.n_cells, c0 + cells_per_block)
+                mm[c0:c1] = band.values[c0:c1].cpu().numpy()
+            mm.flush()
+        finally:
+            del mm
+    np.save(paths[2], b.offsets.cpu().numpy().view(np.uint64))
+    np.save(paths[3], b.lo.cpu().numpy().view(np.uint32))
+    np.save(paths[4], b.diag.cpu().numpy())
+    with open(paths[5], "w") as out:
+        out.write("\t".join(VARIANTS_HEADER.rstrip("\n").split("\t")[:3] + ["alt_freq"]) + "\n")
+        for k in range(m.n):
+            out.write(f"{k}\t{m.rs_ids[k]}\t{m.poss[k]}\t{m.alt_freqs[k]}\n")
+    return paths
+
+
+def em_window_hits(vcf, chrom, chrom_rows: Sequence[Sequence], sample_names: Sequence[str], r2: float = 0.2,
+                   window_bp: int = 1_000_000, missing: Optional[str] = None):
+    """The pairs of one chromosome's variants within ``window_bp`` of each other with EM r^2 >= ``r2``, each pair ONCE, the
+    variant earlier in position order first: (RectSide of the variants -- both sides of ``write_ld_table`` --, LDRectHits
+    with ``em`` set, built from ops.ld_neighbors(em=True)'s records with i < j)."""
+    import torch
+    panel, rs_ids, poss = _chrom_em_panel("em_window_hits", vcf, chrom, chrom_rows, sample_names)
+    nb = ld_neighbors(panel, np.asarray(poss, dtype=np.int64), window_bp=window_bp, r2=r2, missing=missing, em=True)
+    once = nb.hits[nb.hits[:, 0] < nb.hits[:, 1]].contiguous()   # (sorted by (i, j) already)
+    offsets = torch.zeros(nb.n_snps + 1, dtype=torch.int32, device=once.device)
+    offsets[1:] = torch.cumsum(torch.bincount(once[:, 0].to(torch.int64), minlength=nb.n_snps), 0).to(torch.int32)
+    side = RectSide(str(chrom), rs_ids, poss, [], [], panel.alt_freq4().cpu().numpy().tolist(), None)
+    return side, LDRectHits(offsets, once, nb.n_snps, nb.n_snps, nb.bound, False, True, missing=missing)

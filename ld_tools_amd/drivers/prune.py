@@ -31,12 +31,17 @@ class PruneTable:
 
 
 def prune(vcf, chrom, chrom_rows: Sequence[Sequence], sample_names: Sequence[str], r2: float = 0.2,
-          window_bp: int = 250_000, priority: Optional[Sequence[float]] = None, dosage: bool = False) -> PruneTable:
+          window_bp: int = 250_000, priority: Optional[Sequence[float]] = None, dosage: bool = False, em: bool = False,
+          missing: Optional[str] = None) -> PruneTable:
     """Pruning of one chromosome's variants (VCF rows [pos, rsID]); ``priority``: one value per input row (higher first),
-    default the minor allele frequency.  ``dosage``: genotype-dosage r (ops.ld_prune)."""
+    default the minor allele frequency.  ``dosage``: genotype-dosage r (ops.ld_prune).  ``em``: the EM r of the unphased
+    genotypes (``missing="pairwise"``: every pair over the samples called at both variants); ``missing`` is passed through
+    only where it is given."""
     panel, rows, rs_ids, poss = chrom_panel(vcf, chrom, chrom_rows, sample_names, "prune")
     pr = None if priority is None else np.asarray(priority, dtype=np.float64)[rows]
-    res = ld_prune(panel, np.asarray(poss, dtype=np.int64), r2=r2, window_bp=window_bp, priority=pr, dosage=dosage)
+    more = {} if missing is None else {"missing": missing}
+    res = ld_prune(panel, np.asarray(poss, dtype=np.int64), r2=r2, window_bp=window_bp, priority=pr, dosage=dosage, em=em,
+                   **more)
     return PruneTable(str(chrom), rs_ids, poss, res)
 
 

@@ -15,6 +15,8 @@
     ld_em(panel_i, panel_j)                 unphased LD by maximum likelihood: EM r and D' of two SNP sets (dense float32)
     ld_em_hits(panel_i, panel_j, r2=...)    the pairs of that rectangle whose EM r^2 reaches a threshold, with their D'
                                             (both: missing="pairwise" = over the individuals called at both SNPs)
+    ld_em_band(panel, positions, ...)       the EM r and D' of every in-window pair of ONE panel, kept in ld_band's layout;
+                                            ld_neighbors / ld_clump / ld_prune(em=True) are the lists and selections on them
     pair_counts(panel_i, panel_j)           <- calc_ld.py:32           (bit-exact n11 block)
     ld_from_counts(n, n11, a1, r1, a2, r2)  <- calc_ld.py:33-97        (the epilogue alone)
 
@@ -1802,6 +1804,7 @@ class LDBand:
     n_hap: int = 0
     _host: Optional[tuple] = None
     missing: Optional[str] = None   # "pairwise": the cells are ld_rect(missing="pairwise")'s (ld_band(missing="pairwise"))
+    em: bool = False                # the cells are ld_em's r or D' (ld_em_band): ``missing`` is then ld_em's
 
     @property
     def n_snps(self) -> int:
@@ -2076,6 +2079,14 @@ class LDNeighbors:
     bound: np.float32       # the float32 bound on s = r *f32 r (r2_bound)
     dosage: bool = False    # r is the genotype-dosage r (ld_neighbors(dosage=True))
     missing: Optional[str] = None   # "pairwise": r is the pairwise-complete r (ld_neighbors(missing="pairwise"))
+    em: bool = False        # r is ld_em's r and column 3 of ``hits`` its D' cell, not s (ld_neighbors(em=True))
+
+    @property
+    def dprime(self) -> torch.Tensor:
+        """float32 [m]: the D' cell of each pair of an EM list (a view of ``hits``)."""
+        if not self.em:
+            raise _lib.LdxError("these neighbour lists carry s = r *f32 r, not D': D' comes with ld_neighbors(em=True)")
+        return self.hits[:, 3].view(torch.float32)
 
     @property
     def nbr(self) -> torch.Tensor:
@@ -2101,7 +2112,7 @@ class LDNeighbors:
 def ld_neighbors(panel: PackedPanel, positions=None, window_bp: int = 250_000, window_snps: Optional[int] = None,
                  r2: float = 0.2, strict: bool = False, path: Optional[str] = None, hit_capacity: Optional[int] = None,
                  workspace: Optional[torch.Tensor] = None, check_positions: bool = True, dosage: bool = False,
-                 missing: Optional[str] = None) -> LDNeighbors:
+                 missing: Optional[str] = None, em: bool = False) -> LDNeighbors:
     """Neighbour lists on the matrix-pipe band (include/ldx.h, ldx_ld_neighbors_dev + ldx_area_finish_ex_dev): for every SNP
     the SNPs j with |pos_i - pos_j| <= window, j != i, and r^2 >= ``r2`` (``strict``: r^2 > r2), where r is the r32 cell of
     ld_triangle(fmt="r32") bit for bit and r^2 one float32 multiply.  Degenerate SNPs have no neighbours.
@@ -2117,7 +2128,16 @@ def ld_neighbors(panel: PackedPanel, positions=None, window_bp: int = 250_000, w
     ``missing="pairwise"``: r is the pairwise-complete r of ld_rect(missing="pairwise"), bit for bit -- what PLINK --r2 /
     --indep-pairwise compare with the threshold on a panel with missing calls (include/ldx.h, "pairwise-complete bands";
     ldx_ld_pw_neighbors_dev: the FP4 band only; ``workspace`` of ldx_ld_pw_band_workspace_bytes() bytes).  None: the call as
-    it always was."""
+    it always was.
+
+    ``em=True``: r is the EM r of ld_em(panel, panel, missing=missing), bit for bit -- the maximum-likelihood r of the unphased
+    genotypes, PLINK --r2 / --clump's own; column 3 of the records is the D' cell (``.dprime``), not r^2 (include/ldx.h, "EM on
+    the band"; ldx_ld_em_neighbors_dev: the FP4 band only, an even n_hap, not with ``dosage``; ``workspace`` of
+    ldx_ld_em_band_workspace_bytes() bytes).  SNPs monomorphic among their called individuals have no neighbours; an
+    all-heterozygous SNP can have some."""
+    if em:
+        return _em_neighbors(panel, positions, window_bp, window_snps, r2, strict, path, hit_capacity, workspace, check_positions,
+                             dosage, missing)
     pairwise = _band_missing("ld_neighbors", missing, path)
     if dosage:
         _dosage_check("ld_neighbors", panel)
@@ -2249,9 +2269,11 @@ class Pruned:
     rounds: int
 
 
-def _panel_live(panel: PackedPanel, dosage: bool = False, pairwise: bool = False) -> np.ndarray:
+def _panel_live(panel: PackedPanel, dosage: bool = False, pairwise: bool = False, em: bool = False) -> np.ndarray:
     """The SNPs that can have a neighbour: a r > 0, or for the dosage lists v > 0 (pairwise-complete: v over the individuals
-    called at the SNP)."""
+    called at the SNP); for the EM lists 0 < A < 2 N over the SNP's called individuals (em_snp_stats)."""
+    if em:
+        return em_snp_stats(panel, pairwise)[3].cpu().numpy().astype(bool)
     if pairwise and dosage:
         return pw_snp_stats(panel, True)[1].cpu().numpy().astype(bool)
     return panel.dosage_live() if dosage else live_snps(panel.alt_counts(), panel.ref_counts())
@@ -2259,19 +2281,22 @@ def _panel_live(panel: PackedPanel, dosage: bool = False, pairwise: bool = False
 
 def ld_clump(panel: PackedPanel, positions, pvalues, p1: float = 1e-4, p2: float = 1e-2, r2: float = 0.5,
              window_bp: int = 250_000, window_snps: Optional[int] = None, path: Optional[str] = None,
-             hit_capacity: Optional[int] = None, dosage: bool = False, missing: Optional[str] = None) -> Clumps:
+             hit_capacity: Optional[int] = None, dosage: bool = False, missing: Optional[str] = None,
+             em: bool = False) -> Clumps:
     """Clumping (PLINK --clump's rule): take the SNPs with p <= p1 in increasing (p, row); one not yet in a clump becomes an
     index and takes every SNP not yet in a clump with p <= p2 and r^2 >= r2 within the window.  r^2 is that of ld_neighbors
     (the haplotype r of the ALT indicators, unrounded; ``dosage=True``: the genotype-dosage r, PLINK's own).  SNPs with a
     NaN p and degenerate SNPs (dosage: v == 0) take no part.  ``missing="pairwise"``: ld_neighbors(missing="pairwise")'s
-    lists -- r^2 over the observations called at both SNPs."""
-    pairwise = _band_missing("ld_clump", missing, path)
+    lists -- r^2 over the observations called at both SNPs.  ``em=True``: ld_neighbors(em=True)'s lists -- the EM r^2 of the
+    unphased genotypes; with ``missing="pairwise"`` PLINK --clump's own r^2.  SNPs monomorphic among their called individuals
+    take no part; an all-heterozygous SNP does."""
+    pairwise = _em_args("ld_clump", panel, missing, path, dosage) if em else _band_missing("ld_clump", missing, path)
     if dosage:
         _dosage_check("ld_clump", panel)
-    live = _panel_live(panel, dosage, pairwise)
+    live = _panel_live(panel, dosage, pairwise, em)
     rank, member_ok = clump_ranks(pvalues, p1, p2, live)
     nb = ld_neighbors(panel, positions, window_bp=window_bp, window_snps=window_snps, r2=r2, strict=False, path=path,
-                      hit_capacity=hit_capacity, dosage=dosage, missing=missing)
+                      hit_capacity=hit_capacity, dosage=dosage, missing=missing, em=em)
     state, owner, rounds = select_dev(nb, rank, member_ok)
     idx = np.flatnonzero(state == SEL_INDEX)
     idx = idx[np.argsort(rank[idx], kind="stable")]
@@ -2281,18 +2306,25 @@ def ld_clump(panel: PackedPanel, positions, pvalues, p1: float = 1e-4, p2: float
 
 def ld_prune(panel: PackedPanel, positions=None, r2: float = 0.2, window_bp: Optional[int] = None,
              window_snps: Optional[int] = None, priority=None, path: Optional[str] = None,
-             hit_capacity: Optional[int] = None, dosage: bool = False, missing: Optional[str] = None) -> Pruned:
+             hit_capacity: Optional[int] = None, dosage: bool = False, missing: Optional[str] = None,
+             em: bool = False) -> Pruned:
     """Priority pruning: take the SNPs in decreasing priority (default: the MAF min(fa, fr) of the panel), ties by row; one
     with no kept neighbour is kept.  Neighbours are the SNPs within the window with r^2 > r2 (strict), as in ld_neighbors.
     The kept set has no pair above the threshold inside the window.  Degenerate SNPs are never kept.  The window is
     ``window_snps`` SNPs or ``window_bp`` in the units of ``positions`` (default 250 000 when positions are given).
     ``dosage=True``: the neighbours are those of the genotype-dosage r (PLINK --indep-pairwise's r), SNPs with v == 0 are
     never kept, and the default priority is the dosage MAF min(f, 1 - f), f = a / n_hap.  ``missing="pairwise"``:
-    ld_neighbors(missing="pairwise")'s lists -- PLINK --indep-pairwise's r^2 on a panel with missing calls."""
-    pairwise = _band_missing("ld_prune", missing, path)
+    ld_neighbors(missing="pairwise")'s lists -- PLINK --indep-pairwise's r^2 on a panel with missing calls.  ``em=True``:
+    ld_neighbors(em=True)'s lists; SNPs monomorphic among their called individuals are never kept, and the default priority is
+    min(f, 1 - f) with f = A / (2 N) over the SNP's called individuals (em_snp_stats)."""
+    pairwise = _em_args("ld_prune", panel, missing, path, dosage) if em else _band_missing("ld_prune", missing, path)
     if dosage:
         _dosage_check("ld_prune", panel)
-    live = _panel_live(panel, dosage, pairwise)
+    live = _panel_live(panel, dosage, pairwise, em)
+    if priority is None and em:
+        n_called, a_sum = (t.cpu().numpy().astype(np.float64) for t in em_snp_stats(panel, pairwise)[:2])
+        f = a_sum / np.maximum(2.0 * n_called, 1.0)
+        priority = np.minimum(f, 1.0 - f)
     if priority is None and dosage:
         f = panel.fa.cpu().numpy()[:panel.n_snps]
         priority = np.minimum(f, 1.0 - f)
@@ -2302,7 +2334,7 @@ def ld_prune(panel: PackedPanel, positions=None, r2: float = 0.2, window_bp: Opt
     if window_snps is None and window_bp is None:
         window_bp = 250_000
     nb = ld_neighbors(panel, positions, window_bp=0 if window_bp is None else window_bp, window_snps=window_snps, r2=r2,
-                      strict=True, path=path, hit_capacity=hit_capacity, dosage=dosage, missing=missing)
+                      strict=True, path=path, hit_capacity=hit_capacity, dosage=dosage, missing=missing, em=em)
     state, _, rounds = select_dev(nb, rank, live.astype(np.uint8))
     return Pruned(state == SEL_INDEX, rank, nb, rounds)
 
@@ -2705,6 +2737,123 @@ def ld_em_hits(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, r2: 
 
     offsets, hits = _rect_hits_run("ld_em_hits", launch, n_i, n_j, panel_i.device, hit_capacity)
     return LDRectHits(offsets, hits, n_i, n_j, bound, False, True, missing=missing)
+
+
+# ---- EM on the band (include/ldx.h, "EM on the band")
+def _em_args(what: str, panel: PackedPanel, missing, path=None, dosage: bool = False) -> bool:
+    """The EM band operators' argument rules, checked before anything touches the device; True for missing="pairwise"."""
+    pairwise = _rect_missing(what, missing)
+    if dosage:
+        raise _lib.LdxError(f"{what}: em=True and dosage=True exclude each other (the EM r is its own estimate from the genotypes)")
+    if path not in (None, "fp4"):
+        raise _lib.LdxError(f"{what}: em=True runs on the FP4 band only (path must be None or 'fp4', got {path!r})")
+    if panel.n_hap % 2:
+        raise _lib.LdxError(f"{what}: the EM needs an even n_hap (got {panel.n_hap}): individual k owns haplotypes 2k and 2k + 1")
+    return pairwise
+
+
+def _em_panel(panel: PackedPanel, pairwise: bool) -> tuple:
+    """The panel's arguments of the EM band entries: alt, ref, acnt, rcnt (ref and rcnt None unless ``pairwise``)."""
+    if pairwise:
+        return panel.alt.data_ptr(), panel.ref.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr()
+    return panel.alt.data_ptr(), None, panel.acnt.data_ptr(), None
+
+
+def _em_workspace(panel: PackedPanel, workspace: Optional[torch.Tensor]) -> torch.Tensor:
+    return _band_workspace(lambda n, _h: lib.ldx_ld_em_band_workspace_bytes(n), panel, workspace)
+
+
+def em_snp_stats(panel: PackedPanel, pairwise: bool = False):
+    """``(N int32 [n], A int32 [n], diag float32 [n], live uint8 [n])`` on the device (include/ldx.h, ldx_em_snp_stats_dev):
+    per SNP the individuals called at it and the sum of their dosages (``pairwise`` False: n_hap / 2 and the ALT count),
+    live = 0 < A < 2 N, diag = +1.0 where live, else -0.0: the diagonal of an EM band.  An all-heterozygous SNP is live."""
+    if panel.n_hap % 2:
+        raise _lib.LdxError(f"em_snp_stats: the EM needs an even n_hap (got {panel.n_hap}): individual k owns haplotypes 2k and "
+                            "2k + 1")
+    require_gpu()
+    n, dev = panel.n_snps, panel.device
+    n_called = torch.empty(n, dtype=torch.int32, device=dev)
+    a_sum = torch.empty(n, dtype=torch.int32, device=dev)
+    diag = torch.empty(n, dtype=torch.float32, device=dev)
+    live = torch.empty(n, dtype=torch.uint8, device=dev)
+    check(lib.ldx_em_snp_stats_dev(*_em_panel(panel, pairwise), n, panel.n_hap, int(bool(pairwise)), n_called.data_ptr(),
+                                   a_sum.data_ptr(), diag.data_ptr(), live.data_ptr(), _stream_ptr()), "ldx_em_snp_stats_dev")
+    return n_called, a_sum, diag, live
+
+
+@dataclass
+class LDEmBand:
+    """ld_em_band's two bands (None where only the other was asked for): ``r`` and ``dprime`` are LDBands with ``em`` set that
+    share the layout tensors and the diagonal -- +1.0 where the SNP has both alleles among its called individuals, else -0.0
+    -- so everything an LDBand offers works on ``.r`` as it is.  ``live``: uint8 [n] on the device, the diagonal's rule."""
+
+    r: Optional[LDBand]
+    dprime: Optional[LDBand]
+    live: torch.Tensor
+
+    @property
+    def n_cells(self) -> int:
+        return (self.r if self.r is not None else self.dprime).n_cells
+
+
+def ld_em_band(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, window_snps: Optional[int] = None,
+               want_r: bool = True, want_dprime: bool = True, missing: Optional[str] = None,
+               workspace: Optional[torch.Tensor] = None, check_positions: bool = True) -> LDEmBand:
+    """The windowed EM LD of one panel, kept: for every pair i > j with pos_i - pos_j <= window the r and D' cells of
+    ld_em(panel, panel, missing=missing) at (i, j), bit for bit, in ld_band's layout -- what PLINK --r2 dprime --ld-window-kb
+    computes, at the cost of the band instead of the square (include/ldx.h, "EM on the band"; ldx_ld_em_band_dev).  Positions
+    and window as for ld_band; an even n_hap.  ``want_r`` / ``want_dprime`` = False leaves that band out (None in the result);
+    not both.  ``missing``: None (a missing code counts as REF) or "pairwise" (every pair over the individuals called at both
+    SNPs); a panel without missing codes gives the same bytes either way.  ``workspace``: a uint8 device tensor of
+    ldx_ld_em_band_workspace_bytes() bytes to reuse.  The layout's total is read back once to size the values."""
+    pairwise = _em_args("ld_em_band", panel, missing)
+    if not (want_r or want_dprime):
+        raise _lib.LdxError("ld_em_band: neither r nor D' was asked for")
+    require_gpu()
+    n, dev = panel.n_snps, panel.device
+    pos, pos_h, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_em_band")
+    window = min(window, BAND_WINDOW_MAX)
+    workspace = _em_workspace(panel, workspace)
+    lo = torch.empty(n, dtype=torch.int32, device=dev)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    check(lib.ldx_ld_band_layout_dev(pos.data_ptr(), n, window, lo.data_ptr(), offsets.data_ptr(), _stream_ptr()),
+          "ldx_ld_band_layout_dev")
+    n_cells = int(offsets[n].item())
+    vals = [torch.empty(n_cells, dtype=torch.float32, device=dev) if want else None for want in (want_r, want_dprime)]
+    check(lib.ldx_ld_em_band_dev(*_em_panel(panel, pairwise), n, panel.n_hap, int(pairwise), pos.data_ptr(), window, lo.data_ptr(),
+                                 offsets.data_ptr(), *(_ptr(v) if v is not None and n_cells else None for v in vals), n_cells,
+                                 workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr()),
+          "ldx_ld_em_band_dev")
+    _, _, diag, live = em_snp_stats(panel, pairwise)
+    bands = []
+    for v in vals:
+        band = None
+        if v is not None:
+            band = LDBand(v, lo, offsets, diag, pos if pos_h is None else pos_h, window, False, panel.n_hap, missing=missing, em=True)
+            band._keep = (pos, workspace)   # alive until the launch is done
+        bands.append(band)
+    return LDEmBand(bands[0], bands[1], live)
+
+
+def _em_neighbors(panel: PackedPanel, positions, window_bp, window_snps, r2, strict, path, hit_capacity, workspace,
+                  check_positions, dosage, missing) -> "LDNeighbors":
+    """ld_neighbors(em=True): the pairwise path's buffers and retries around ldx_ld_em_neighbors_dev."""
+    pairwise = _em_args("ld_neighbors", panel, missing, path, dosage)
+    require_gpu()
+    n = panel.n_snps
+    bound = r2_bound(r2, strict)
+    pos, _, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_neighbors")
+    workspace = _em_workspace(panel, workspace)
+    side = _em_panel(panel, pairwise)
+
+    def launch(raw, cap, n_hits):
+        check(lib.ldx_ld_em_neighbors_dev(*side, n, panel.n_hap, int(pairwise), pos.data_ptr(), min(window, BAND_WINDOW_MAX),
+                                          float(bound), raw.data_ptr(), cap, n_hits.data_ptr(), workspace.data_ptr(),
+                                          workspace.numel() * workspace.element_size(), _stream_ptr()), "ldx_ld_em_neighbors_dev")
+
+    cap = int(hit_capacity) if hit_capacity is not None else max(1 << 20, 32 * n)
+    offsets, hits = _rect_hits_run("ld_neighbors", launch, n, 0, panel.device, cap)
+    return LDNeighbors(offsets, hits, n, window, bound, False, missing, em=True)
 
 
 EM_PAIRWISE_COUNTS = ("N", "A", "B", "S", "H")   # the order of include/ldx.h, "pairwise-complete EM"
