@@ -892,7 +892,7 @@ int ldx_ld_em_from_counts_dev(uint32_t n_ind, size_t m, const uint32_t *a1, cons
  *   accuracy is the section above's: each cell within 2 float32 ulps of the exact value of its integers plus 2^-40 absolute;
  *   a cell is a function of (N, A, B, S, H) alone, symmetric in the two SNPs: swapped sides give the transpose, permuted
  *     individuals and rephased genotypes identical bits.
- * The integers come from the FP4 matrix cores (ldx_em_pw.hip), five exact fp32 accumulator sets from three per-individual
+ * The integers come from the FP4 matrix cores (ldx_em.hip, the same kernel template), five exact fp32 accumulator sets from three per-individual
  * operands on each side; a 128 x 128 tile none of whose SNPs has acnt + rcnt != n_hap runs the two-set loop of the section
  * above and reads N, A and B from n_hap / 2 and acnt.  No workspace, no library state.
  *

@@ -100,7 +100,7 @@ int area_mfma(const void *alt, const double *fa, const double *fr, const double 
 // plane_check: the matrix kernels address a bit plane with 32-bit lane offsets, so one of 4 GiB or more is LDX_E_UNSUPPORTED;
 // `arg` names the plane in the message ("alt_i is a bit plane ..."), null where the entry has only one.
 int plane_check(const char *who, const char *arg, uint32_t n_snps, uint32_t n_hap);
-// The rectangle entries' shape rules (ldx_rect.hip, ldx_em.hip, ldx_em_pw.hip, ldx_pwc.hip), in this order: n_i, n_j, n_hap non-zero; n_hap even where
+// The rectangle entries' shape rules (ldx_rect.hip, ldx_em.hip, ldx_pwc.hip), in this order: n_i, n_j, n_hap non-zero; n_hap even where
 // `odd_reason` (the words in the message's brackets) is non-null; n_hap within LDX_MAX_HAPS; both planes; fewer than 2^31
 // tiles of tile_rows x 128.  Each entry has checked its own pointers before; everything returns before any HIP call.
 int rect_args_ok(const char *who, uint32_t n_i, uint32_t n_j, uint32_t n_hap, const char *odd_reason, uint32_t tile_rows);
@@ -123,7 +123,7 @@ __host__ __device__ inline uint64_t tile_base(uint64_t t, uint64_t G) { return t
 // back with a larger buffer.  So every slot below min(*n_hits, hit_cap) holds a record or the mark, which is exactly what the
 // consumer, ldx_area_finish_ex_dev (ldx_area.hip), relies on.  `counts`, where given, receives the STORED records per query
 // row: what the consumer's scatter will place.
-// Users: area_scan_kernel, rect_kernel, em_kernel, em_pw_kernel, pwc_kernel, pwband_kernel, emband_kernel.  The band epilogues of triangle_mfma_kernel keep the same protocol as the
+// Users: area_scan_kernel, rect_kernel, em_rect_kernel, pwc_kernel, pwband_kernel, emband_kernel.  The band epilogues of triangle_mfma_kernel keep the same protocol as the
 // text of a macro (LDX_HIT_APPENDER, ldx_mfma.hip), because that kernel's instruction stream must not move.
 constexpr uint32_t kHitBatch = 256;              // slots a wave reserves per atomic
 constexpr uint32_t kHitInvalid = 0xFFFFFFFFu;    // `query` of an unused slot

@@ -1,11 +1,12 @@
-// The tile of the pairwise-complete EM kernels (em_pw_kernel of ldx_em_pw.hip, emband_kernel of ldx_emband.hip; DESIGN.md 3.10
-// and 3.11): the five integers N A B S H of every cell of I slab ti x J slab tj, handed one cell per lane to the caller's emit
-// functor -- the way tile_body of ldx_pwc_tile.h serves pwc_kernel and pwband_kernel.  ldx_em_pw.hip's header describes the
-// operands, the two K loops and the staging; here is only what a caller needs:
+// The tile of the EM kernels (em_rect_kernel of ldx_em.hip, emband_kernel of ldx_emband.hip): the
+// five integers N A B S H of every cell of I slab ti x J slab tj, handed one cell per lane to the caller's emit functor -- the
+// way tile_body of ldx_pwc_tile.h serves pwc_kernel and pwband_kernel.  ldx_em.hip's header describes the operands, the two K
+// loops and the staging; here is only what a caller needs:
 //   * tile_body<kPairwise> is called by the whole workgroup (256 threads, 2 x 2 waves of 64 x 64 cells).
 //     kPairwise: the hole test on the tile's 128 rows and 128 columns (acnt + rcnt != n_hap) picks, workgroup-uniformly, the
-//     two-set shortcut (em_kernel's K loop: N = n_hap / 2, A and B from acnt) or the four-pass five-set general loop.
-//     !kPairwise: always the shortcut -- em_kernel's cells; ref and rcnt are not read.
+//     two-set shortcut (N = n_hap / 2, A and B from acnt) or the four-pass five-set general loop.
+//     !kPairwise: always the shortcut -- the plain form's cells; ref and rcnt are not read, and a null acnt (a caller that
+//     wants S and H alone) gives A = B = 0.
 //   * its first barrier publishes what the caller wrote to LDS of its own before the call; between two calls of one workgroup
 //     the caller puts a block_sync() (tables, images and staged words are rewritten).
 //   * emit(i, j, N, A, B, S, H) is called by EVERY lane of a wave at once (a hit appender may ballot), with 128 ti <= i <
@@ -28,11 +29,11 @@ constexpr uint32_t kImage = 3u * kOpBytes;            // one buffer of the gener
 constexpr uint32_t kPlane = 32u * 32u;                // words of one plane of a wave's staged 32 x 32 tile
 constexpr uint32_t kStage = em::kWaves * 3u * kPlane * 4u;   // the general epilogue's staged integers: 48 KiB
 constexpr uint32_t kShiftA = 14;                      // staged word 1 = A << 14 | B  (A, B <= 10 240 < 2^14)
-static_assert(kImage == em::kImage && 2u * kImage <= em::kLdsBytes && kStage <= em::kLdsBytes, "the general loop lives in em_kernel's LDS");
+static_assert(kImage == em::kImage && 2u * kImage <= em::kLdsBytes && kStage <= em::kLdsBytes, "the general loop lives in the two-set loop's LDS");
 
 struct Side {
     const uint4 *alt, *ref;   // tiled bit planes (ldx_plane_bytes)
-    const uint32_t *acnt;     // [n] ALT counts
+    const uint32_t *acnt;     // [n] ALT counts (null: the plain counts form)
     const uint32_t *rcnt;     // [n] REF counts
     uint32_t n;               // SNPs
 };
@@ -70,7 +71,7 @@ __device__ __forceinline__ void tile_body(Smem &sm, const Side &si, const Side &
         const uint32_t *const acnt = is_col ? sj.acnt : si.acnt;
         const uint32_t x = (is_col ? tj : ti) * kSlab + (tid & (kSlab - 1u));
         const bool live = x < (is_col ? sj.n : si.n);
-        const uint32_t a = live ? acnt[x] : 0u;
+        const uint32_t a = live && acnt ? acnt[x] : 0u;   // (a null table reads as zeros)
         (is_col ? sm.cstat : sm.rstat)[tid & (kSlab - 1u)] = a;
         if constexpr (kPairwise) {
             const uint32_t *const rcnt = is_col ? sj.rcnt : si.rcnt;
@@ -83,7 +84,7 @@ __device__ __forceinline__ void tile_body(Smem &sm, const Side &si, const Side &
     }
 
     if (!general) {
-        // ---- the shortcut: em_kernel's K loop and epilogue; N, A and B from the launch and the tables
+        // ---- the shortcut: the two-set K loop and epilogue; N, A and B from the launch and the tables
         v16f acc_s[2][2], acc_h[2][2];
         em::count_two_sets(lds, si.alt, sj.alt, ti, tj, nblocks, tid, acc_s, acc_h);
         const uint32_t *const stage = em::stage_two_sets(lds, tid, acc_s, acc_h);
@@ -92,6 +93,7 @@ __device__ __forceinline__ void tile_body(Smem &sm, const Side &si, const Side &
         const uint32_t row0 = ti * kSlab + wr * kWaveRows;
         const uint32_t rows = row0 < si.n ? (si.n - row0 < kWaveRows ? si.n - row0 : kWaveRows) : 0u;   // wave-uniform
         for (uint32_t rr = 0; rr < rows; ++rr) {
+            __builtin_assume(row0 + rr < si.n);   // (a functor's own row test folds: its column test leaves the loop)
             const uint32_t packed = stage[rr * kWaveCols + lane];
             const uint32_t a_i = sm.rstat[wr * kWaveRows + rr];   // one address per wave: broadcast
             emit(row0 + rr, j, n_hap / 2u, a_i, a_j, packed >> em::kPackShift, packed & ((1u << em::kPackShift) - 1u));

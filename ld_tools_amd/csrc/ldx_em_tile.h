@@ -1,4 +1,4 @@
-// What the EM kernels share (em_kernel of ldx_em.hip, em_pw_kernel of ldx_em_pw.hip and emband_kernel of ldx_emband.hip through
+// What the EM kernels share (em_rect_kernel of ldx_em.hip and emband_kernel of ldx_emband.hip, both through tile_body of
 // ldx_em_pw_tile.h): the tile's
 // geometry, the het operands, the two-set K loop (S and H of a 128 x 128 tile without missing codes) with its packed LDS
 // staging, and the epilogue em_cell -- ONE function of (N, a_i, a_j, S, H), so that a cell cannot depend on the kernel, the

@@ -1,5 +1,5 @@
-// What the FP4 counting kernels share (triangle_mfma_kernel of ldx_mfma.hip, rect_kernel of ldx_rect.hip, em_kernel of
-// ldx_em.hip, em_pw_kernel of ldx_em_pw.hip, pwc_kernel of ldx_pwc.hip and pwband_kernel of ldx_pwband.hip through ldx_pwc_tile.h): the operand encoding -- the exactness argument of the whole library, written once -- and the rectangle walk.
+// What the FP4 counting kernels share (triangle_mfma_kernel of ldx_mfma.hip, rect_kernel of ldx_rect.hip, em_rect_kernel of
+// ldx_em.hip, pwc_kernel of ldx_pwc.hip and pwband_kernel of ldx_pwband.hip through ldx_pwc_tile.h): the operand encoding -- the exactness argument of the whole library, written once -- and the rectangle walk.
 #pragma once
 
 #include "ldx_common.h"
@@ -50,7 +50,7 @@ __device__ __forceinline__ v4i expand32_b4_dosage(uint32_t w)
 // haplotype slot, which is registers 0 and 2 of an operand (slots 4k and 4k + 2 of the word); registers 1 and 3, the odd
 // slots, are then free and carry a second per-individual bit that only meets a partner parked on the odd slots too.
 //   A side (0.5 / 1):  expand32_a4_dosage  g / 2 on the even slot (het 0001 = 0.5, hom 0010 = 1);
-//                      even_a4(z)          0.5 where z has the individual's bit (em_kernel's het_a4, as four registers);
+//                      even_a4(z)          0.5 where z has the individual's bit (the EM tile's het_a4, as four registers);
 //                      odd_a4(z)           1 on the ODD slot of the individual (0010), nothing on the even one.
 //   B side (2 / 4 / 1): expand32_b4_dosage  2 g on the even slot (and g on the odd one, which the three A operands above
 //                                          multiply by 0);

@@ -9,13 +9,13 @@
 //     (band_layout_kernel's comparison).  Positions are non-decreasing, so the band kernel's per-cell predicate -- j < i and
 //     pos_i - pos_j <= window -- IS low[i] <= j < i: a cell needs one table word of its row, not two positions.
 //   * walk: only the lower band.  I block ti (rows [256 ti, r1), r1 = min(256 (ti + 1), n)) meets the slabs low[256 ti] / 128 ..
-//     (r1 - 1) / 128: low is non-decreasing, so these cover every in-window j < i of the block.  The plan kernel (ldx_band_plan.h,
-//     shared with emband_kernel) writes the
+//     (r1 - 1) / 128: low is non-decreasing, so these cover every in-window j < i of the block.  The plan kernel writes the
 //     exclusive prefix of those counts, and their total, into the workspace; tile t is (ti, tj) with prefix[ti] <= t <
 //     prefix[ti + 1] (a binary search) and tj = first slab + t - prefix[ti].  The grid is fixed -- two workgroups per CU -- and a
 //     workgroup strides over the tile numbers: no host read of the total.  Consecutive tile numbers, which run side by side,
 //     share the 256 rows of one I block and walk its slabs; the next I block starts at most two slabs later, so the slabs are
-//     shared between neighbouring blocks through the L2 as well.
+//     shared between neighbouring blocks through the L2 as well.  Plan, tile loop, row tables, predicates, launch and argument
+//     rules are ldx_band_plan.h's, shared with emband_kernel.
 //   * epilogues: Store writes values[offsets[i] + j - lo[i]] under ldx_ld_band_dev's guard; Nbr appends both orientations of a
 //     pair in one HitAppender call; Score adds the cell's term to its row's and its column's sum as the cells go by, in doubles
 //     (integers <= 2^32, at most 256 of them: exact): a row's sum is complete when the lane has met the row's column tiles and
@@ -31,14 +31,13 @@ namespace pwband {
 using namespace pwc;
 
 enum Op : int { kStore = 0, kScore = 1, kNbr = 2 };
-using bandplan::kNoRow;
+static_assert(kThreads == bandplan::kBandThreads, "the walk's workgroup");
 
 struct Args {
     Side s;                    // the panel: both sides of every tile
     uint32_t nblocks;          // K-blocks of 256 haplotypes
     uint32_t n_hap;
-    const uint64_t *prefix;    // [Ti + 1] tiles in front of each I block, the total last (workspace)
-    const uint32_t *low;       // [n] the window's first column per row (workspace)
+    bandplan::Plan plan;
     const uint32_t *lo;        // store: the caller's layout
     const uint64_t *offsets;
     float *values;
@@ -54,10 +53,7 @@ struct Args {
 };
 
 // the band's own per-tile tables, beside tile_body's: 4 480 bytes
-struct BandLds {
-    uint64_t r_off[kTileRows];   // store: offsets[i]
-    uint32_t r_low[kTileRows];   // the window's first column of row i (kNoRow beyond the panel)
-    uint32_t r_lo[kTileRows];    // store: the caller's lo[i]
+struct BandLds : bandplan::RowTables<kTileRows> {
     uint8_t r_sel[kTileRows], c_sel[kSlab];   // score: does the row's / the column's mask select this launch's word
 };
 
@@ -75,11 +71,10 @@ struct BandEpi {
     {
         const uint32_t li = i - ti * kTileRows;
         const float c = r32_cell(k[kLast], k[0], k[1], rs_x, k[2], rs_y).r;
-        const bool inside = j < i && j >= bl.r_low[li];   // (i < n: r_low is kNoRow otherwise; j < i < n)
+        const bool inside = bandplan::inside(bl, li, i, j);
         if constexpr (kOp == kStore) {
-            const uint32_t lo_i = bl.r_lo[li];
-            const uint64_t idx = bl.r_off[li] + (uint64_t)(j - lo_i);
-            if (inside && j >= lo_i && idx < p.n_cells) p.values[idx] = c;   // ldx_ld_band_dev's guard
+            uint64_t idx;
+            if (bandplan::store_at(bl, li, j, inside, p.n_cells, idx)) p.values[idx] = c;
         } else if constexpr (kOp == kNbr) {
             const float s2 = c * c;   // ONE float32 multiply; -0.0f (degenerate) and +0.0f give 0 < bound
             hit.append_both(inside && s2 >= p.bound, i, j, c, s2);
@@ -125,36 +120,23 @@ __global__ void __launch_bounds__(kThreads, 2) pwband_kernel(Args p)
     __shared__ Smem sm;
     __shared__ BandLds bl;
     const uint32_t n = p.s.n;
-    const uint32_t Ti = (n + kTileRows - 1u) / kTileRows;
-    const uint64_t total = p.prefix[Ti];
     BandEpi<kOp, kDosage> epi{p, bl, HitAppender{p.hits, p.hit_cap, p.n_hits, threadIdx.x & 63u}};
-    for (uint64_t t = blockIdx.x; t < total; t += gridDim.x) {   // workgroup-uniform
-        uint32_t ti, tj;
-        bandplan::tile_at<kTileRows>(p.prefix, p.low, Ti, t, ti, tj);
-        if (t != blockIdx.x) block_sync();   // the last tile's tables and image are free
-        // (the thread's number as a value of THIS trip: what tile_body derives from it -- a few dozen lane offsets -- would
-        // otherwise be made once in front of the loop and held in registers across every K loop, which no longer fits)
-        uint32_t tid = threadIdx.x;
-        asm volatile("" : "+v"(tid));
-        const uint32_t x_r = ti * kTileRows + tid, x_c = tj * kSlab + tid;
-        bl.r_low[tid] = x_r < n ? p.low[x_r] : kNoRow;
-        if constexpr (kOp == kStore) {
-            bl.r_lo[tid] = x_r < n ? p.lo[x_r] : kNoRow;
-            bl.r_off[tid] = x_r < n ? p.offsets[x_r] : 0u;
-        }
+    bandplan::walk<kTileRows>(p.plan, n, [&](uint32_t ti, uint32_t tj, uint32_t tid) {
+        bandplan::fill_rows<kOp == kStore>(bl, p.plan, p.lo, p.offsets, n, ti, tid);
         if constexpr (kOp == kScore) {   // bit c of (mask << 1) | 1 selects word c
+            const uint32_t x_r = ti * kTileRows + tid, x_c = tj * kSlab + tid;
             bl.r_sel[tid] = (uint8_t)(((((p.annot && x_r < n) ? (uint32_t)p.annot[x_r] << 1 : 0u) | 1u) >> p.word) & 1u);
             if (tid < kSlab) bl.c_sel[tid] = (uint8_t)(((((p.annot && x_c < n) ? (uint32_t)p.annot[x_c] << 1 : 0u) | 1u) >> p.word) & 1u);
         }
         epi.ti = ti, epi.tj = tj;
         tile_body<kDosage, true>(sm, p.s, p.s, p.nblocks, p.n_hap, ti, tj, tid, epi);   // (its first barrier publishes the tables)
-    }
+    });
     if constexpr (kOp == kNbr) epi.hit.close();   // what is left of the wave's last batch
 }
 
 // diag / live of one SNP over its OWN called set: one wavefront per row.  Haplotype form: a r > 0, from the tables.  Dosage
 // form: the individuals with both codes called -- N of them, A = the sum of their dosages, HA homozygous ALT -- from both
-// planes (a lane per 32-bit word, as dosage_stats_kernel reads them); live iff N (A + 2 HA) - A^2 > 0.
+// planes (called_sums, ldx_band_plan.h); live iff N (A + 2 HA) - A^2 > 0.
 __global__ void __launch_bounds__(256) snp_stats_kernel(const uint32_t *__restrict__ alt, const uint32_t *__restrict__ ref,
                                                         const uint32_t *__restrict__ acnt, const uint32_t *__restrict__ rcnt,
                                                         uint32_t n_snps, uint32_t nchunks, bool dosage, float *__restrict__ diag,
@@ -167,22 +149,8 @@ __global__ void __launch_bounds__(256) snp_stats_kernel(const uint32_t *__restri
     if (!dosage) {
         lv = acnt[row] != 0u && rcnt[row] != 0u;
     } else {
-        const uint32_t slab = row / kSlab, rin = row % kSlab;
-        uint32_t N = 0, A = 0, HA = 0;
-        for (uint32_t w = lane; w < nchunks * 4u; w += 64u) {
-            const size_t at = (((size_t)slab * nchunks + (w >> 2)) * kSlab + rin) * 4u + (w & 3u);
-            const uint32_t wa = alt[at], q = ind_called(wa, ref[at]), g = wa & (q | (q << 1));
-            N += __builtin_popcount(q);
-            A += __builtin_popcount(g);
-            HA += __builtin_popcount(g & (g >> 1) & 0x55555555u);
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            N += __shfl_xor(N, off);
-            A += __shfl_xor(A, off);
-            HA += __shfl_xor(HA, off);
-        }
-        lv = (uint64_t)N * (A + 2u * (uint64_t)HA) > (uint64_t)A * A;   // (Cauchy-Schwarz: never below)
+        const bandplan::CalledSums c = bandplan::called_sums<true>(alt, ref, row, nchunks, lane);
+        lv = (uint64_t)c.N * (c.A + 2u * (uint64_t)c.HA) > (uint64_t)c.A * c.A;   // (Cauchy-Schwarz: never below)
     }
     if (lane != 0u) return;
     diag[row] = lv ? 1.0f : -0.0f;
@@ -200,29 +168,25 @@ __global__ void score_init_kernel(const float *__restrict__ diag, const uint8_t 
     for (uint32_t c = 0; c < st; ++c) sums[(size_t)i * st + c] = ((m >> c) & 1u) ? t : 0u;
 }
 
-// the workspace: the plan's (ldx_band_plan.h) for I blocks of kTileRows rows
-static size_t workspace_bytes(uint32_t n_snps) { return bandplan::workspace_bytes<kTileRows>(n_snps); }
-
-// low, the plan, then the band: everything in stream order, nothing read back
+// low, the plan, then the band (bandplan::launch); the tile bound is I blocks x slabs
 template <int kOp>
 static int launch(Args &p, bool dosage, const int64_t *positions, int64_t window, void *workspace, hipStream_t s)
 {
     const uint32_t n = p.s.n;
-    bandplan::Plan plan;
-    if (const int rc = bandplan::make_plan<kTileRows>(positions, n, window, workspace, s, plan)) return rc;
-    p.prefix = plan.prefix, p.low = plan.low;
-    const uint64_t tiles = (uint64_t)((n + kTileRows - 1u) / kTileRows) * n_slabs(n);   // (an upper bound of the plan's total)
-    const uint64_t cap = 2u * (uint64_t)device_cus();                                    // two workgroups per CU are resident
-    const uint32_t grid = (uint32_t)(tiles < cap ? tiles : cap);
-    // (Score: one pass over the band per word -- the sums of one word are what fits the registers beside the accumulators --
-    // so K annotation categories cost 1 + K passes)
-    for (uint32_t word = 0; word < (kOp == kScore ? p.st : 1u); ++word) {
-        p.word = word;
-        if (dosage) pwband_kernel<kOp, true><<<grid, kThreads, 0, s>>>(p);
-        else pwband_kernel<kOp, false><<<grid, kThreads, 0, s>>>(p);
-        LDX_HIP(hipGetLastError());
-    }
-    return LDX_OK;
+    const uint64_t tiles = (uint64_t)((n + kTileRows - 1u) / kTileRows) * n_slabs(n);
+    auto go = [&](const bandplan::Plan &plan, uint32_t grid) {
+        p.plan = plan;
+        // (Score: one pass over the band per word -- the sums of one word are what fits the registers beside the accumulators --
+        // so K annotation categories cost 1 + K passes)
+        for (uint32_t word = 0; word < (kOp == kScore ? p.st : 1u); ++word) {
+            p.word = word;
+            if (dosage) pwband_kernel<kOp, true><<<grid, kThreads, 0, s>>>(p);
+            else pwband_kernel<kOp, false><<<grid, kThreads, 0, s>>>(p);
+            LDX_HIP(hipGetLastError());
+        }
+        return (int)LDX_OK;
+    };
+    return bandplan::launch<kTileRows>(positions, n, window, workspace, s, tiles, go);
 }
 
 }  // namespace pwband
@@ -235,29 +199,10 @@ using namespace ldx;
     LDX_ARG_PTR(who, alt); LDX_ARG_PTR(who, ref); LDX_ARG_PTR(who, acnt); LDX_ARG_PTR(who, rcnt); \
     LDX_ARG_REQUIRE(hom != nullptr || !dosage, "%s: hom is a null pointer (the dosage form reads ldx_dosage_stats_dev's table)", who)
 
-static int shape_ok(const char *who, uint32_t n_snps, uint32_t n_hap, bool dosage)
+// only the dosage form pairs haplotypes
+static const char *odd_reason(bool dosage)
 {
-    LDX_ARG_REQUIRE(n_snps != 0u, "%s: n_snps is 0", who);
-    LDX_ARG_REQUIRE(n_hap != 0u, "%s: n_hap is 0", who);
-    LDX_ARG_REQUIRE(!dosage || n_hap % 2u == 0u, "%s: n_hap %u is odd (dosage pairs haplotypes 2k and 2k + 1 into individuals)", who,
-                    n_hap);
-    if (n_hap > LDX_MAX_HAPS) {
-        set_error("%s: n_hap %u > LDX_MAX_HAPS %u", who, n_hap, LDX_MAX_HAPS);
-        return LDX_E_UNSUPPORTED;
-    }
-    return plane_check(who, "alt", n_snps, n_hap);
-}
-
-static int band_ok(const char *who, uint32_t n_snps, uint32_t n_hap, bool dosage, const int64_t *positions, int64_t window,
-                   const void *workspace, size_t workspace_bytes)
-{
-    LDX_ARG_PTR(who, positions);
-    LDX_ARG_PTR(who, workspace);
-    LDX_ARG_REQUIRE(window >= 0, "%s: window %lld is negative", who, (long long)window);
-    if (const int rc = shape_ok(who, n_snps, n_hap, dosage)) return rc;
-    LDX_ARG_REQUIRE(workspace_bytes >= pwband::workspace_bytes(n_snps), "%s: workspace_bytes %zu < %zu", who, workspace_bytes,
-                    pwband::workspace_bytes(n_snps));
-    return LDX_OK;
+    return dosage ? "dosage pairs haplotypes 2k and 2k + 1 into individuals" : nullptr;
 }
 
 static pwband::Args make_args(const void *alt, const void *ref, const uint32_t *acnt, const uint32_t *rcnt, const uint32_t *hom,
@@ -271,7 +216,7 @@ static pwband::Args make_args(const void *alt, const void *ref, const uint32_t *
     return p;
 }
 
-extern "C" size_t ldx_ld_pw_band_workspace_bytes(uint32_t n_snps) { return pwband::workspace_bytes(n_snps); }
+extern "C" size_t ldx_ld_pw_band_workspace_bytes(uint32_t n_snps) { return bandplan::workspace_bytes<pwc::kTileRows>(n_snps); }
 
 extern "C" int ldx_pw_snp_stats_dev(const void *alt, const void *ref, const uint32_t *acnt, const uint32_t *rcnt, uint32_t n_snps,
                                     uint32_t n_hap, int dosage, float *diag, uint8_t *live, void *stream)
@@ -279,7 +224,7 @@ extern "C" int ldx_pw_snp_stats_dev(const void *alt, const void *ref, const uint
     const char *const who = "ldx_pw_snp_stats_dev";
     LDX_ARG_PTR(who, alt); LDX_ARG_PTR(who, ref); LDX_ARG_PTR(who, acnt); LDX_ARG_PTR(who, rcnt);
     LDX_ARG_PTR(who, diag);
-    if (const int rc = shape_ok(who, n_snps, n_hap, dosage != 0)) return rc;
+    if (const int rc = bandplan::shape_ok(who, n_snps, n_hap, odd_reason(dosage != 0))) return rc;
     pwband::snp_stats_kernel<<<(n_snps + 3u) / 4u, 256, 0, (hipStream_t)stream>>>(
         (const uint32_t *)alt, (const uint32_t *)ref, acnt, rcnt, n_snps, n_chunks(n_hap), dosage != 0, diag, live);
     LDX_HIP(hipGetLastError());
@@ -297,7 +242,9 @@ extern "C" int ldx_ld_pw_band_dev(const void *alt, const void *ref, const uint32
     LDX_ARG_PTR(who, offsets);
     LDX_ARG_REQUIRE(values != nullptr || n_cells == 0u, "%s: values is a null pointer but n_cells is %llu", who,
                     (unsigned long long)n_cells);
-    if (const int rc = band_ok(who, n_snps, n_hap, dosage != 0, positions, window, workspace, workspace_bytes)) return rc;
+    if (const int rc = bandplan::band_args_ok<pwc::kTileRows>(who, n_snps, n_hap, odd_reason(dosage != 0), positions, window,
+                                                              workspace, workspace_bytes))
+        return rc;
     if (n_cells == 0u) return LDX_OK;   // no pair in any window: nothing to write
     pwband::Args p = make_args(alt, ref, acnt, rcnt, hom, n_snps, n_hap);
     p.lo = lo, p.offsets = offsets, p.values = values, p.n_cells = n_cells;
@@ -315,7 +262,9 @@ extern "C" int ldx_ld_pw_score_dev(const void *alt, const void *ref, const uint3
     LDX_ARG_PTR(who, sums);
     LDX_ARG_REQUIRE(n_annot <= 8u, "%s: n_annot %u > 8", who, n_annot);
     LDX_ARG_REQUIRE(annot != nullptr || n_annot == 0u, "%s: annot is a null pointer but n_annot is %u", who, n_annot);
-    if (const int rc = band_ok(who, n_snps, n_hap, dosage != 0, positions, window, workspace, workspace_bytes)) return rc;
+    if (const int rc = bandplan::band_args_ok<pwc::kTileRows>(who, n_snps, n_hap, odd_reason(dosage != 0), positions, window,
+                                                              workspace, workspace_bytes))
+        return rc;
     pwband::Args p = make_args(alt, ref, acnt, rcnt, hom, n_snps, n_hap);
     p.annot = n_annot ? annot : nullptr, p.st = 1u + n_annot, p.sums = (unsigned long long *)sums;
     pwband::score_init_kernel<<<(n_snps + 255u) / 256u, 256, 0, (hipStream_t)stream>>>(diag, p.annot, p.st, n_snps, sums);
@@ -331,7 +280,9 @@ extern "C" int ldx_ld_pw_neighbors_dev(const void *alt, const void *ref, const u
     const char *const who = "ldx_ld_pw_neighbors_dev";
     LDX_PWB_PANEL(who);
     if (const int rc = hit_args_ok(who, r2_bound, hits, hit_cap, n_hits)) return rc;
-    if (const int rc = band_ok(who, n_snps, n_hap, dosage != 0, positions, window, workspace, workspace_bytes)) return rc;
+    if (const int rc = bandplan::band_args_ok<pwc::kTileRows>(who, n_snps, n_hap, odd_reason(dosage != 0), positions, window,
+                                                              workspace, workspace_bytes))
+        return rc;
     pwband::Args p = make_args(alt, ref, acnt, rcnt, hom, n_snps, n_hap);
     p.bound = r2_bound, p.hits = hits, p.hit_cap = hit_cap, p.n_hits = (unsigned long long *)n_hits;
     LDX_HIP(hipMemsetAsync(n_hits, 0, sizeof(uint64_t), (hipStream_t)stream));   // the slot counter starts at 0

@@ -76,6 +76,21 @@ def _band_workspace(size_fn, panel: PackedPanel, workspace: Optional[torch.Tenso
     return workspace
 
 
+def _plan_workspace(size_fn, panel: PackedPanel, workspace: Optional[torch.Tensor]) -> torch.Tensor:
+    """_band_workspace for the plan bands (pairwise-complete and EM), whose ``size_fn`` takes the SNP count alone."""
+    return _band_workspace(lambda n, _h: size_fn(n), panel, workspace)
+
+
+def _band_layout(pos: torch.Tensor, n: int, window: int, dev) -> Tuple[torch.Tensor, torch.Tensor, int]:
+    """A stored band's layout on the device (ldx_ld_band_layout_dev): ``(lo int32 [n], offsets int64 [n + 1], n_cells)``; the
+    total, offsets[n], is read back -- the one synchronisation of the band calls."""
+    lo = torch.empty(n, dtype=torch.int32, device=dev)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    check(lib.ldx_ld_band_layout_dev(pos.data_ptr(), n, window, lo.data_ptr(), offsets.data_ptr(), _stream_ptr()),
+          "ldx_ld_band_layout_dev")
+    return lo, offsets, int(offsets[n].item())
+
+
 # --------------------------------------------------------------------------- triangle
 @dataclass
 class TriangleResult:
@@ -813,7 +828,7 @@ def ld_score(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, win
     bits, k = (None, 0) if annot is None else pack_annot(annot, n)
     annot_d = torch.as_tensor(bits).to(panel.device) if k else None
     if pairwise:
-        workspace = _pw_workspace(panel, workspace)
+        workspace = _plan_workspace(lib.ldx_ld_pw_band_workspace_bytes, panel, workspace)
         sums = torch.empty((n, 1 + k), dtype=torch.uint64, device=panel.device)
         diag, _ = pw_snp_stats(panel, dosage)
         check(lib.ldx_ld_pw_score_dev(*_pw_panel(panel, dosage), n, panel.n_hap, int(bool(dosage)), pos.data_ptr(),
@@ -1917,11 +1932,7 @@ def ld_band(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, wind
     pcode = _band_path(path)
     workspace = _band_workspace(lib.ldx_ld_band_workspace_bytes, panel, workspace)
     dev = panel.device
-    lo = torch.empty(n, dtype=torch.int32, device=dev)
-    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    check(lib.ldx_ld_band_layout_dev(pos.data_ptr(), n, window, lo.data_ptr(), offsets.data_ptr(), _stream_ptr()),
-          "ldx_ld_band_layout_dev")
-    n_cells = int(offsets[n].item())
+    lo, offsets, n_cells = _band_layout(pos, n, window, dev)
     values = torch.empty(n_cells, dtype=torch.float32, device=dev)
     ws_bytes = workspace.numel() * workspace.element_size()
     if dosage:
@@ -2146,17 +2157,9 @@ def ld_neighbors(panel: PackedPanel, positions=None, window_bp: int = 250_000, w
     bound = r2_bound(r2, strict)
     pos, _, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_neighbors")
     if pairwise:
-        workspace = _pw_workspace(panel, workspace)
-        side = _pw_panel(panel, dosage)
-
-        def launch(raw, cap, n_hits):
-            check(lib.ldx_ld_pw_neighbors_dev(*side, n, panel.n_hap, int(bool(dosage)), pos.data_ptr(),
-                                              min(window, BAND_WINDOW_MAX), float(bound), raw.data_ptr(), cap, n_hits.data_ptr(),
-                                              workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr()),
-                  "ldx_ld_pw_neighbors_dev")
-
-        cap = int(hit_capacity) if hit_capacity is not None else max(1 << 20, 32 * n)
-        offsets, hits = _rect_hits_run("ld_neighbors", launch, n, 0, panel.device, cap)
+        offsets, hits = _plan_neighbors("ldx_ld_pw_neighbors_dev", lib.ldx_ld_pw_band_workspace_bytes, panel,
+                                        (*_pw_panel(panel, dosage), n, panel.n_hap, int(bool(dosage))), pos, window, bound,
+                                        hit_capacity, workspace)
         return LDNeighbors(offsets, hits, n, window, bound, bool(dosage), missing)
     pcode = _band_path(path)
     dev = panel.device
@@ -2406,10 +2409,6 @@ def _pw_panel(panel: PackedPanel, dosage: bool) -> tuple:
     return panel.alt.data_ptr(), panel.ref.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), hom
 
 
-def _pw_workspace(panel: PackedPanel, workspace: Optional[torch.Tensor]) -> torch.Tensor:
-    return _band_workspace(lambda n, _h: lib.ldx_ld_pw_band_workspace_bytes(n), panel, workspace)
-
-
 def pw_snp_stats(panel: PackedPanel, dosage: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """``(diag float32 [n], live uint8 [n])`` on the device: the diagonal of a pairwise-complete band and what it stands on
     (include/ldx.h, ldx_pw_snp_stats_dev) -- the SNP is polymorphic over its OWN called set: a r > 0, or with ``dosage``
@@ -2427,12 +2426,8 @@ def pw_snp_stats(panel: PackedPanel, dosage: bool = False) -> Tuple[torch.Tensor
 def _pw_band(panel: PackedPanel, pos, pos_h, window: int, workspace, dosage: bool, missing) -> "LDBand":
     """ld_band(missing="pairwise") after the argument checks: ld_band's layout, ldx_ld_pw_band_dev's cells."""
     n, dev = panel.n_snps, panel.device
-    workspace = _pw_workspace(panel, workspace)
-    lo = torch.empty(n, dtype=torch.int32, device=dev)
-    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    check(lib.ldx_ld_band_layout_dev(pos.data_ptr(), n, window, lo.data_ptr(), offsets.data_ptr(), _stream_ptr()),
-          "ldx_ld_band_layout_dev")
-    n_cells = int(offsets[n].item())
+    workspace = _plan_workspace(lib.ldx_ld_pw_band_workspace_bytes, panel, workspace)
+    lo, offsets, n_cells = _band_layout(pos, n, window, dev)
     values = torch.empty(n_cells, dtype=torch.float32, device=dev)
     check(lib.ldx_ld_pw_band_dev(*_pw_panel(panel, dosage), n, panel.n_hap, int(dosage), pos.data_ptr(), window, lo.data_ptr(),
                                  offsets.data_ptr(), _ptr(values) if n_cells else None, n_cells, workspace.data_ptr(),
@@ -2658,6 +2653,21 @@ def _rect_hits_run(what: str, launch, n_i: int, n_j: int, dev, hit_capacity: Opt
     return offsets, hits[:total]
 
 
+def _plan_neighbors(entry: str, size_fn, panel: PackedPanel, head: tuple, pos, window: int, bound, hit_capacity, workspace):
+    """A plan band's neighbours entry (``entry``: ldx_ld_pw_neighbors_dev or ldx_ld_em_neighbors_dev, ``head`` its arguments in
+    front of the positions) through _rect_hits_run, with ld_neighbors' default capacity.  Returns (offsets, sorted records)."""
+    n = panel.n_snps
+    workspace = _plan_workspace(size_fn, panel, workspace)
+
+    def launch(raw, cap, n_hits):
+        check(getattr(lib, entry)(*head, pos.data_ptr(), min(window, BAND_WINDOW_MAX), float(bound), raw.data_ptr(), cap,
+                                  n_hits.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                  _stream_ptr()), entry)
+
+    cap = int(hit_capacity) if hit_capacity is not None else max(1 << 20, 32 * n)
+    return _rect_hits_run("ld_neighbors", launch, n, 0, panel.device, cap)
+
+
 # --------------------------------------------------------------------------- unphased LD by EM (two SNP sets)
 @dataclass
 class LDEm:
@@ -2759,10 +2769,6 @@ def _em_panel(panel: PackedPanel, pairwise: bool) -> tuple:
     return panel.alt.data_ptr(), None, panel.acnt.data_ptr(), None
 
 
-def _em_workspace(panel: PackedPanel, workspace: Optional[torch.Tensor]) -> torch.Tensor:
-    return _band_workspace(lambda n, _h: lib.ldx_ld_em_band_workspace_bytes(n), panel, workspace)
-
-
 def em_snp_stats(panel: PackedPanel, pairwise: bool = False):
     """``(N int32 [n], A int32 [n], diag float32 [n], live uint8 [n])`` on the device (include/ldx.h, ldx_em_snp_stats_dev):
     per SNP the individuals called at it and the sum of their dosages (``pairwise`` False: n_hap / 2 and the ALT count),
@@ -2813,12 +2819,8 @@ def ld_em_band(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, w
     n, dev = panel.n_snps, panel.device
     pos, pos_h, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_em_band")
     window = min(window, BAND_WINDOW_MAX)
-    workspace = _em_workspace(panel, workspace)
-    lo = torch.empty(n, dtype=torch.int32, device=dev)
-    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    check(lib.ldx_ld_band_layout_dev(pos.data_ptr(), n, window, lo.data_ptr(), offsets.data_ptr(), _stream_ptr()),
-          "ldx_ld_band_layout_dev")
-    n_cells = int(offsets[n].item())
+    workspace = _plan_workspace(lib.ldx_ld_em_band_workspace_bytes, panel, workspace)
+    lo, offsets, n_cells = _band_layout(pos, n, window, dev)
     vals = [torch.empty(n_cells, dtype=torch.float32, device=dev) if want else None for want in (want_r, want_dprime)]
     check(lib.ldx_ld_em_band_dev(*_em_panel(panel, pairwise), n, panel.n_hap, int(pairwise), pos.data_ptr(), window, lo.data_ptr(),
                                  offsets.data_ptr(), *(_ptr(v) if v is not None and n_cells else None for v in vals), n_cells,
@@ -2843,16 +2845,9 @@ def _em_neighbors(panel: PackedPanel, positions, window_bp, window_snps, r2, str
     n = panel.n_snps
     bound = r2_bound(r2, strict)
     pos, _, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_neighbors")
-    workspace = _em_workspace(panel, workspace)
-    side = _em_panel(panel, pairwise)
-
-    def launch(raw, cap, n_hits):
-        check(lib.ldx_ld_em_neighbors_dev(*side, n, panel.n_hap, int(pairwise), pos.data_ptr(), min(window, BAND_WINDOW_MAX),
-                                          float(bound), raw.data_ptr(), cap, n_hits.data_ptr(), workspace.data_ptr(),
-                                          workspace.numel() * workspace.element_size(), _stream_ptr()), "ldx_ld_em_neighbors_dev")
-
-    cap = int(hit_capacity) if hit_capacity is not None else max(1 << 20, 32 * n)
-    offsets, hits = _rect_hits_run("ld_neighbors", launch, n, 0, panel.device, cap)
+    offsets, hits = _plan_neighbors("ldx_ld_em_neighbors_dev", lib.ldx_ld_em_band_workspace_bytes, panel,
+                                    (*_em_panel(panel, pairwise), n, panel.n_hap, int(pairwise)), pos, window, bound, hit_capacity,
+                                    workspace)
     return LDNeighbors(offsets, hits, n, window, bound, False, missing, em=True)
 
 

@@ -246,6 +246,62 @@ def test_hits_are_the_host_mirror_of_the_dense_cells(gpu):
     check(ops.ld_em_hits(pi, pj, r2=0.2, hit_capacity=256), "r2 >= 0.2 from a 256-slot buffer")
 
 
+# ---- 6b. panels WITH missing codes: the plain form counts a missing call as REF -----------------------------------------------
+# The plain and the pairwise entries run one kernel template, so comparing them no longer guards the plain form where codes
+# are missing.  By definition the plain cells of such a panel are those of the panel with every missing code replaced by REF
+# on the host: same bytes from ld_em, ld_em_hits, ld_em_counts and ld_em_band.  A plain form that consulted the hole test, ref
+# or rcnt would fail here.  Shapes: ragged rows and columns, more than one tile per side, a K tail.
+REF_CASES = tuple((kind, shape, n_hap) for kind in ("holed", "mixed") for shape, n_hap in (((129, 257), 254), ((300, 130), 1008)))
+_REF_PANELS = {}
+
+
+def ref_case(kind, shape, n_hap):
+    """(panel_i, panel_j) of the codes as they are and of the codes with every missing code set to REF, built once."""
+    import ld_em_pairwise_exact as epx
+    from ld_tools_amd import PackedPanel
+    key = (kind, shape, n_hap)
+    if key not in _REF_PANELS:
+        ci, cj, _ = epx.panel(kind, shape, n_hap)
+        assert ((ci > 1).any() or (ci < 0).any()) and ((cj > 1).any() or (cj < 0).any()), "the panel holds missing codes"
+        as_ref = [np.where((c == 0) | (c == 1), c, 0).astype(c.dtype) for c in (ci, cj)]
+        _REF_PANELS[key] = tuple(PackedPanel.from_codes(c) for c in (ci, cj, *as_ref))
+    return _REF_PANELS[key]
+
+
+def sorted_hits(h):
+    i, j, r = h.pairs()
+    order = np.lexsort((j, i))
+    return i[order], j[order], np.asarray(r).view(np.uint32)[order], bits(h.dprime)[order]
+
+
+@pytest.mark.parametrize("kind,shape,n_hap", REF_CASES, ids=[f"{k}-{s[0]}x{s[1]}x{h}" for k, s, h in REF_CASES])
+def test_plain_forms_count_a_missing_code_as_ref(gpu, kind, shape, n_hap):
+    from ld_tools_amd import ops
+    pi, pj, qi, qj = ref_case(kind, shape, n_hap)
+    got, want = ops.ld_em(pi, pj), ops.ld_em(qi, qj)
+    assert got.r.shape == shape
+    assert np.array_equal(bits(got.r), bits(want.r)) and np.array_equal(bits(got.dprime), bits(want.dprime))
+    for g, w in zip(ops.ld_em_counts(pi, pj), ops.ld_em_counts(qi, qj)):
+        assert g.shape == shape and np.array_equal(g.cpu().numpy(), w.cpu().numpy())
+    hg, hw = ops.ld_em_hits(pi, pj, r2=0.2), ops.ld_em_hits(qi, qj, r2=0.2)
+    assert len(hw) > 0 and len(hg) == len(hw)
+    assert np.array_equal(hg.offsets.cpu().numpy(), hw.offsets.cpu().numpy())
+    for g, w in zip(sorted_hits(hg), sorted_hits(hw)):
+        assert np.array_equal(g, w)
+
+
+def test_plain_band_counts_a_missing_code_as_ref(gpu):
+    from ld_tools_amd import ops
+    p, _, q, _ = ref_case("mixed", (300, 130), 1008)
+    got, want = ops.ld_em_band(p, window_snps=40), ops.ld_em_band(q, window_snps=40)
+    assert got.n_cells == want.n_cells > 0
+    for g, w in ((got.r, want.r), (got.dprime, want.dprime)):
+        assert np.array_equal(g.lo.cpu().numpy(), w.lo.cpu().numpy())
+        assert np.array_equal(g.offsets.cpu().numpy(), w.offsets.cpu().numpy())
+        assert np.array_equal(bits(g.values), bits(w.values)) and np.array_equal(bits(g.diag), bits(w.diag))
+    assert np.array_equal(got.live.cpu().numpy(), want.live.cpu().numpy())
+
+
 # ---- 7. outputs ------------------------------------------------------------------------------------------------------------
 def test_outputs_keep_their_surroundings_and_one_may_be_left_out(gpu):
     import torch

@@ -14,7 +14,7 @@ that clock drift hits all alike; every call sits between two device events of it
     dosage     ld_rect(I, J, dosage=True) into a preallocated [n_i, n_j] tensor
 
 Epilogue paths, classified on the host from the kernel's own counts on a sample of rows (the decision sequence of em_cell,
-ldx_em.hip, in numpy): degenerate; H = 0 (closed form); g monotone on [0, H]; one rising branch with a sign change (one
+ldx_em_tile.h, in numpy): degenerate; H = 0 (closed form); g monotone on [0, H]; one rising branch with a sign change (one
 root, no logarithm); two candidates (two roots and the likelihood comparison).  No time or ratio is promised: the JSON
 object that is printed (and written to --out) is the record.
 """
