@@ -192,6 +192,43 @@ int ldx_panel_select_dev(const void *alt_src, const void *ref_src, uint32_t n_sn
                          const uint32_t *snp_idx, uint32_t n_snps_dst, const uint32_t *hap_idx, uint32_t n_hap_dst,
                          void *alt_dst, void *ref_dst, uint32_t *acnt_dst, uint32_t *rcnt_dst, void *stream);
 
+/* ---- PLINK .bed ingest and export: genotype calls straight from / to the file's own bytes ---- */
+/* A SNP-major .bed row holds individual k as the 2-bit field at bits 2 (k % 4), 2 (k % 4) + 1 of byte k / 4, low bit first:
+ * 00 = homozygous A1, 01 (low bit set) = missing, 10 = heterozygous, 11 = homozygous A2.  In the panel individual k owns
+ * haplotypes 2k and 2k + 1.  With alt_is_a2 = 0 (ALT = A1, what PLINK and LDSC count) the codes are hom A1 -> (1, 1), het ->
+ * (1, 0), hom A2 -> (0, 0), missing -> (2, 2): a het always puts the ALT allele on haplotype 2k (a .bed carries no phase);
+ * alt_is_a2 = 1 swaps the two homozygotes.  ld_tools_amd/plink.py states the same on the host (bed_codes_host /
+ * codes_bed_host), and both entries match it byte for byte.
+ *
+ * ldx_bed_unpack_dev: rows row0 .. row0 + n_rows - 1 of a panel of n_snps_panel x 2 n_ind_dst, both planes and both counts,
+ * from n_rows .bed rows -- what ldx_pack_codes_dev makes of bed_codes_host(rows, n_ind_src, keep = ind_idx), without the codes.
+ *   bed: device pointer to the rows, row_bytes >= ceil(n_ind_src / 4) apart (else LDX_E_ARG), at ANY alignment (a whole file
+ *        copied to the device is read at base + 3); bits past n_ind_src in a row's last byte are ignored.  n_ind_src has no
+ *        upper limit.
+ *   ind_idx: uint32 [n_ind_dst] device array of source individuals, any order, repeats allowed, or NULL = identity (then
+ *        n_ind_dst == n_ind_src, else LDX_E_ARG).  An index >= n_ind_src has a meaning, as in ldx_panel_select_dev (a _dev
+ *        entry cannot report from inside the launch), and is never a stray read: a MISSING CALL at that individual.
+ *        2 n_ind_dst <= LDX_MAX_HAPS, else LDX_E_UNSUPPORTED.
+ *   row0: a multiple of 128; n_rows: a multiple of 128 unless row0 + n_rows == n_snps_panel; row0 + n_rows <= n_snps_panel
+ *        (else LDX_E_ARG).  So a file streams into one panel chunk by chunk, and each call owns whole slabs.
+ *   alt / ref / acnt / rcnt: the panel's (ldx_plane_bytes(n_snps_panel, 2 n_ind_dst), uint32 [padded_snps]), all required.
+ * EVERY byte of the slabs a call owns is written: both planes, pad haplotypes and the pad rows of the last slab as zero
+ * bits, acnt / rcnt including the pad rows' zeros.  The counts are plain stores by the workgroup that owns the rows: no
+ * memset, no atomics, nothing read from the destination -- a call into a used or poisoned panel gives the same bytes.
+ * A source of up to 7648 individuals is staged in LDS (the identity form always is); a wider one is gathered from global
+ * memory through the index.  The call only enqueues ONE kernel on `stream`: no allocation, no synchronisation, no state. */
+int ldx_bed_unpack_dev(const uint8_t *bed, size_t row_bytes, uint32_t n_ind_src, uint32_t n_rows,
+                       const uint32_t *ind_idx, uint32_t n_ind_dst, int alt_is_a2, uint32_t row0, uint32_t n_snps_panel,
+                       void *alt, void *ref, uint32_t *acnt, uint32_t *rcnt, void *stream);
+/* ldx_bed_pack_dev: rows row0 .. row0 + n_rows - 1 (any range inside the panel, else LDX_E_ARG) of a panel of n_snps x n_hap
+ * as n_rows .bed rows, row_bytes >= ceil(n_ind / 4) apart, at any alignment.  Per individual: both haplotypes ALT -> hom ALT,
+ * both REF -> hom REF, one of each in either order -> het, anything else (a bit missing from both planes) -> missing.  n_hap
+ * must be even (else LDX_E_ARG) and within LDX_MAX_HAPS (else LDX_E_UNSUPPORTED); ref is required.  Every byte of the
+ * ceil(n_ind / 4) of each row is written, pad bits zero; the bytes between that and row_bytes are left alone.  One kernel on
+ * `stream`. */
+int ldx_bed_pack_dev(const void *alt, const void *ref, uint32_t n_snps, uint32_t n_hap, uint32_t row0, uint32_t n_rows,
+                     uint8_t *bed, size_t row_bytes, int alt_is_a2, void *stream);
+
 /* ---- bit-exact contract: the alt/alt haplotype count of calc_ld.py:32 ------------------ */
 /* n11[i][j] = popcount(alt_i[row i] & alt_j[row j]) for all rows of panel I against all rows of
  * panel J (may be the same plane).  n11 is dense row-major uint32 [n_i][ld]. */

@@ -22,6 +22,8 @@ from .ops import ld_rect_counts, pairwise_cell_host, pairwise_counts_host, pw_sn
 from .ops import LDEm, em_host, ld_em, ld_em_counts, ld_em_from_counts, ld_em_hits  # noqa: F401
 from .ops import LDEmBand, em_snp_stats, ld_em_band  # noqa: F401
 from .panel import PackedPanel, encode_codes, select_index  # noqa: F401
+from . import plink  # noqa: F401
+from .plink import BedFile, bed_codes_host, codes_bed_host, write_bfile  # noqa: F401
 
 __all__ = ["PackedPanel", "encode_codes", "select_index", "ld_triangle", "ld_area", "pair_counts", "ld_from_counts",
            "TriangleResult", "AreaHits", "ld_score", "LDScores", "ld_neighbors", "LDNeighbors", "ld_clump", "Clumps",
@@ -29,4 +31,4 @@ __all__ = ["PackedPanel", "encode_codes", "select_index", "ld_triangle", "ld_are
            "region_positions", "ld_matvec", "LDProduct", "ld_ridge", "RidgeResult", "prod_terms", "dosage_host", "ld_band", "LDBand",
            "ld_cross_score", "band_layout_host", "cross_terms", "ld_rect", "ld_rect_hits", "LDRectHits", "rect_hits_host", "ld_rect_counts", "pairwise_counts_host", "pairwise_cell_host", "pw_snp_stats", "ld_em", "LDEm",
            "ld_em_hits", "ld_em_counts", "ld_em_from_counts", "em_host", "ld_em_band", "LDEmBand", "em_snp_stats", "LdxError",
-           "version"]
+           "version", "plink", "BedFile", "bed_codes_host", "codes_bed_host", "write_bfile"]

@@ -109,6 +109,8 @@ SIGNATURES = {
     "ldx_snp_stats_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
     "ldx_alt_freq4_dev": (_int, [_vp, _u32, _u32, _vp, _vp]),
     "ldx_panel_select_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "ldx_bed_unpack_dev": (_int, [_vp, _sz, _u32, _u32, _vp, _u32, _int, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "ldx_bed_pack_dev": (_int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _sz, _int, _vp]),
     "ldx_pair_counts_dev": (_int, [_vp, _u32, _vp, _u32, _u32, _vp, _sz, _vp]),
     "ldx_ld_from_counts_dev": (_int, [_u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ldx_triangle_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _vp, _vp, _vp, _vp]),

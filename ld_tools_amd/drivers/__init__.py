@@ -25,3 +25,16 @@ from .regions import write_regions  # noqa: F401
 from .lite import DifChrsError, NotInIntgenConvDbError, NotRsIdError, check_rs_id, ld_lite_table  # noqa: F401
 from .triangle import (TriangleMatrix, create_matrix, stream_triangle_table, triangle_matrix,  # noqa: F401
                        write_triangle_table)
+
+# drivers/plink.py is also a command (python -m ld_tools_amd.drivers.plink), so its names are bound on first use rather than
+# imported here: runpy would otherwise find the module loaded before it runs it
+_PLINK_NAMES = ("Bfile", "load_bfile", "bfile_ld_table", "bfile_clump", "bfile_prune", "bfile_ld_scores", "bfile_band",
+                "bfile_em_band", "make_bed")
+
+
+def __getattr__(name):
+    if name in _PLINK_NAMES:
+        from . import plink as _plink
+
+        return getattr(_plink, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,0 +1,425 @@
+"""PLINK binary filesets as a source and a sink: ``load_bfile`` opens ``prefix.bed/.bim/.fam`` and unpacks the genotype rows
+on the device (PackedPanel.from_bed: the file's own bytes, no per-allele codes), and the ``bfile_*`` drivers fill the table
+dataclasses of the VCF drivers from it, so that their writers write them unchanged:
+
+    bfile_ld_table   -> (RectSide, LDRectHits) for write_ld_table          PLINK --r2 dprime --ld-window-kb --ld-window-r2
+    bfile_clump      -> ClumpTable for write_clumped                       PLINK --clump
+    bfile_prune      -> PruneTable for write_prune                         (priority pruning; cf. --indep-pairwise)
+    bfile_ld_scores  -> LDScoreTable for write_ldscore                     ldsc.py --l2
+    bfile_band       -> BandMatrix for write_band
+    bfile_em_band    -> EmBand for write_em_band
+
+A ``.bed`` holds unphased genotype calls: a het is written (ALT, REF) whatever the truth, so the haplotype r of the phased
+operators means nothing here.  Every driver defaults to an unphased form (EM or genotype dosage) and refuses
+``dosage=False, em=False``.  ``make_bed`` writes a panel, or a subset of a loaded fileset, back as a fileset.
+
+    python -m ld_tools_amd.drivers.plink {ld,clump,prune,l2,make-bed} --bfile P --out O ...
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+from dataclasses import dataclass
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from .. import plink
+from .._lib import LdxError
+from ..ops import ld_band, ld_clump, ld_em_band, ld_neighbors, ld_prune, ld_score
+from ..panel import PackedPanel, select_index
+from .band import BandMatrix
+from .clump import ClumpTable
+from .em import EmBand
+from .ldscore import LDScoreTable, _check_complete, _check_missing_arg, _pairwise
+from .prune import PruneTable
+from .rect import RectSide
+
+
+@dataclass
+class Bfile:
+    """A loaded fileset: the panel, the ``.bim`` columns of its variants (row k of the panel is entry k) and the ``.fam``
+    columns of its individuals (individual k owns haplotypes 2k and 2k + 1).  ``alt``: which allele is code 1."""
+
+    prefix: str
+    panel: PackedPanel
+    alt: str
+    chrom: List[str]
+    ids: List[str]
+    cm: np.ndarray
+    pos: np.ndarray
+    a1: List[str]
+    a2: List[str]
+    fid: List[str]
+    iid: List[str]
+    father: List[str]
+    mother: List[str]
+    sex: List[str]
+    pheno: List[str]
+
+    @property
+    def n(self) -> int:
+        return len(self.ids)
+
+    @property
+    def alts(self) -> List[str]:
+        """The allele that code 1 stands for, per variant."""
+        return self.a1 if self.alt == "a1" else self.a2
+
+    @property
+    def refs(self) -> List[str]:
+        return self.a2 if self.alt == "a1" else self.a1
+
+    def bim(self, snps=None) -> dict:
+        k = list(range(self.n)) if snps is None else [int(i) for i in snps]
+        return {"chrom": [self.chrom[i] for i in k], "ids": [self.ids[i] for i in k], "cm": self.cm[k], "pos": self.pos[k],
+                "a1": [self.a1[i] for i in k], "a2": [self.a2[i] for i in k]}
+
+    def fam(self, individuals=None) -> dict:
+        k = list(range(len(self.iid))) if individuals is None else [int(i) for i in individuals]
+        return {name: [getattr(self, name)[i] for i in k] for name in ("fid", "iid", "father", "mother", "sex", "pheno")}
+
+
+def _is_names(x, pairs: bool) -> bool:
+    """A selection given by name: a non-empty list of strings (variant IDs) or of (FID, IID) pairs."""
+    if isinstance(x, np.ndarray) and x.dtype.kind not in "USO":
+        return False
+    try:
+        first = next(iter(x))
+    except (TypeError, StopIteration):
+        return False
+    if pairs:
+        return isinstance(first, (tuple, list)) and len(first) == 2 and all(isinstance(v, str) for v in first)
+    return isinstance(first, str)
+
+
+def _by_name(wanted, have: Sequence, what: str) -> np.ndarray:
+    where = {}
+    for k, name in enumerate(have):
+        where.setdefault(name, k)          # a repeated name means its first entry
+    wanted = [tuple(w) if isinstance(w, (tuple, list)) else w for w in wanted]
+    unknown = [w for w in wanted if w not in where]
+    if unknown:
+        raise LdxError(f"load_bfile: {len(unknown)} unknown {what}(s), the first: {unknown[0]!r}")
+    return np.asarray([where[w] for w in wanted], dtype=np.int64)
+
+
+def load_bfile(prefix, chrom=None, keep=None, extract=None, maf_min: Optional[float] = None,
+               geno_max: Optional[float] = None, alt: str = "a1") -> Bfile:
+    """Open ``prefix.bed/.bim/.fam`` (or a ``plink.BedFile``) and unpack it on the device.
+    ``chrom``: keep the variants with this ``.bim`` chromosome; their positions must be non-decreasing.
+    ``extract``: variants as an index array / mask over the ``.bim`` lines or a list of variant IDs; ``keep``: individuals as
+    an index array / mask over the ``.fam`` lines or a list of (FID, IID) pairs; an unknown name raises.  With ``chrom``,
+    ``extract`` is applied first and must name variants of that chromosome only.
+    ``maf_min`` / ``geno_max``: PLINK's --maf / --geno, from the kept individuals' counts after the unpack: a variant stays
+    when min(a, r) / (a + r) >= maf_min and 1 - (a + r) / n_hap <= geno_max (an all-missing variant has no MAF and goes with
+    --maf).  ``alt``: the allele that becomes code 1, "a1" (PLINK's and LDSC's counted allele) or "a2"."""
+    bed = prefix if isinstance(prefix, plink.BedFile) else plink.BedFile(prefix)
+    snps = None
+    if extract is not None:
+        snps = _by_name(extract, bed.ids, "variant ID") if _is_names(extract, False) else \
+            select_index(extract, bed.n_snps, "SNP").astype(np.int64)
+    if chrom is not None:
+        on = np.asarray([c == str(chrom) for c in bed.chrom])
+        if snps is None:
+            snps = np.flatnonzero(on)
+        elif not on[snps].all():
+            raise LdxError(f"load_bfile: extract names variants outside chromosome {chrom}")
+        if snps.size == 0:
+            raise LdxError(f"load_bfile: no variant of chromosome {chrom} in {bed.prefix}.bim")
+        if snps.size > 1 and (np.diff(bed.pos[snps]) < 0).any():
+            raise LdxError(f"load_bfile: the positions of chromosome {chrom} are not in non-decreasing order")
+    inds = None
+    if keep is not None:
+        inds = _by_name(keep, list(zip(bed.fid, bed.iid)), "(FID, IID) pair") if _is_names(keep, True) else \
+            select_index(keep, bed.n_ind, "individual").astype(np.int64)
+    panel = PackedPanel.from_bed(bed, keep=inds, extract=snps, alt=alt)
+    snps = np.arange(bed.n_snps) if snps is None else snps
+    if maf_min is not None or geno_max is not None:
+        a, r = panel.alt_counts().astype(np.int64), panel.ref_counts().astype(np.int64)
+        ok = np.ones(a.size, dtype=bool)
+        if maf_min is not None:
+            ok &= np.minimum(a, r) >= float(maf_min) * (a + r)
+            ok &= (a + r) > 0
+        if geno_max is not None:
+            ok &= (panel.n_hap - a - r) <= float(geno_max) * panel.n_hap
+        if not ok.any():
+            raise LdxError("load_bfile: no variant passes maf_min / geno_max")
+        if not ok.all():
+            panel = panel.select(snps=ok)
+            snps = snps[ok]
+    b, f = bed.bim(snps), bed.fam(inds)
+    return Bfile(bed.prefix, panel, alt, b["chrom"], b["ids"], np.asarray(b["cm"]), np.asarray(b["pos"], dtype=np.int64),
+                 b["a1"], b["a2"], f["fid"], f["iid"], f["father"], f["mother"], f["sex"], f["pheno"])
+
+
+def _unphased(what: str, dosage: Optional[bool], em: Optional[bool], default: str):
+    """(dosage, em) of a driver call: None, None -> the driver's default form; one given -> the other off; both off -> the
+    haplotype r, which a .bed cannot give."""
+    if dosage is None and em is None:
+        return default == "dosage", default == "em"
+    dosage, em = bool(dosage), bool(em)
+    if not dosage and not em:
+        raise LdxError(f"{what}: dosage=False, em=False asks for the haplotype r, and a .bed carries no phase (a het is "
+                       "stored without an order); use em=True or dosage=True")
+    if dosage and em:
+        raise LdxError(f"{what}: dosage and em are two different estimates; choose one")
+    return dosage, em
+
+
+def _one_chrom(what: str, bf: Bfile) -> str:
+    chroms = list(dict.fromkeys(bf.chrom))
+    if len(chroms) != 1:
+        raise LdxError(f"{what}: the fileset holds chromosomes {chroms[:4]}...; load one with load_bfile(chrom=)")
+    if bf.n > 1 and (np.diff(bf.pos) < 0).any():
+        raise LdxError(f"{what}: the positions of chromosome {chroms[0]} are not in non-decreasing order")
+    return chroms[0]
+
+
+def _loaded(src, **load) -> Bfile:
+    return src if isinstance(src, Bfile) else load_bfile(src, **load)
+
+
+def _poss(bf: Bfile) -> List[int]:
+    return [int(p) for p in bf.pos]
+
+
+def bfile_ld_table(src, r2: float = 0.2, window_bp: int = 1_000_000, missing: Optional[str] = None,
+                   em: Optional[bool] = None, dosage: Optional[bool] = None, **load):
+    """drivers/em.py's ``em_window_hits`` from a fileset: the in-window pairs with EM r^2 >= ``r2``, each once, as
+    (RectSide, LDRectHits) for ``write_ld_table``.  The table holds D', so the EM form is the only one."""
+    import torch
+
+    bf = _loaded(src, **load)
+    dosage, em = _unphased("bfile_ld_table", dosage, em, "em")
+    if not em:
+        raise LdxError("bfile_ld_table: the .ld table holds D', which only the EM form (em=True) estimates")
+    chrom = _one_chrom("bfile_ld_table", bf)
+    nb = ld_neighbors(bf.panel, bf.pos, window_bp=window_bp, r2=r2, missing=missing, em=True)
+    once = nb.hits[nb.hits[:, 0] < nb.hits[:, 1]].contiguous()
+    offsets = torch.zeros(nb.n_snps + 1, dtype=torch.int32, device=once.device)
+    offsets[1:] = torch.cumsum(torch.bincount(once[:, 0].to(torch.int64), minlength=nb.n_snps), 0).to(torch.int32)
+    from ..ops import LDRectHits
+
+    side = RectSide(chrom, list(bf.ids), _poss(bf), [], [], bf.panel.alt_freq4().cpu().numpy().tolist(), None)
+    return side, LDRectHits(offsets, once, nb.n_snps, nb.n_snps, nb.bound, False, True, missing=missing)
+
+
+def bfile_clump(src, pvalues: Sequence[float], p1: float = 1e-4, p2: float = 1e-2, r2: float = 0.5,
+                window_bp: int = 250_000, dosage: Optional[bool] = None, em: Optional[bool] = None,
+                missing: Optional[str] = None, **load) -> ClumpTable:
+    """drivers/clump.py's ``clump`` from a fileset; one p-value per variant of the loaded fileset.  Default: the EM r
+    (``missing="pairwise"`` makes it PLINK --clump's own r^2)."""
+    bf = _loaded(src, **load)
+    dosage, em = _unphased("bfile_clump", dosage, em, "em")
+    chrom = _one_chrom("bfile_clump", bf)
+    p = np.asarray(pvalues, dtype=np.float64)
+    if p.shape != (bf.n,):
+        raise LdxError("bfile_clump: one p-value per variant is needed")
+    more = {} if missing is None else {"missing": missing}
+    res = ld_clump(bf.panel, bf.pos, p, p1=p1, p2=p2, r2=r2, window_bp=window_bp, dosage=dosage, em=em, **more)
+    return ClumpTable(chrom, list(bf.ids), _poss(bf), p, res)
+
+
+def bfile_prune(src, r2: float = 0.2, window_bp: int = 250_000, priority: Optional[Sequence[float]] = None,
+                dosage: Optional[bool] = None, em: Optional[bool] = None, missing: Optional[str] = None, **load) -> PruneTable:
+    """drivers/prune.py's ``prune`` from a fileset.  Default: the genotype-dosage r, PLINK's own."""
+    bf = _loaded(src, **load)
+    dosage, em = _unphased("bfile_prune", dosage, em, "dosage")
+    chrom = _one_chrom("bfile_prune", bf)
+    pr = None if priority is None else np.asarray(priority, dtype=np.float64)
+    if pr is not None and pr.shape != (bf.n,):
+        raise LdxError("bfile_prune: one priority per variant is needed")
+    more = {} if missing is None else {"missing": missing}
+    res = ld_prune(bf.panel, bf.pos, r2=r2, window_bp=window_bp, priority=pr, dosage=dosage, em=em, **more)
+    return PruneTable(chrom, list(bf.ids), _poss(bf), res)
+
+
+def _dosage_only(what: str, dosage, em) -> None:
+    dosage, em = _unphased(what, dosage, em, "dosage")
+    if em:
+        raise LdxError(f"{what}: this operator has no EM form; use dosage=True")
+
+
+def bfile_ld_scores(src, window_bp: int = 1_000_000, annot=None, annot_names: Optional[Sequence[str]] = None,
+                    adjust: bool = True, dosage: Optional[bool] = None, em: Optional[bool] = None,
+                    missing: Optional[str] = None, **load) -> LDScoreTable:
+    """drivers/ldscore.py's ``ld_scores`` from a fileset (dosage form: ldsc.py --l2's quantities).  ``annot``: bool / 0-1
+    [n, K], one row per variant of the loaded fileset.  A missing call needs ``missing="ref"`` or ``"pairwise"``."""
+    bf = _loaded(src, **load)
+    _dosage_only("bfile_ld_scores", dosage, em)
+    _check_missing_arg("bfile_ld_scores", True, missing)
+    chrom = _one_chrom("bfile_ld_scores", bf)
+    ann, names = None, []
+    if annot is not None:
+        a = np.asarray(annot)
+        a = a[:, None] if a.ndim == 1 else a
+        if a.shape[0] != bf.n:
+            raise LdxError("bfile_ld_scores: annot needs one row per variant")
+        if a.dtype != bool and not np.isin(a, (0, 1)).all():
+            raise LdxError("bfile_ld_scores: annot must be boolean or 0/1")
+        ann = a.astype(bool)
+        names = list(annot_names) if annot_names is not None else [f"A{k}" for k in range(ann.shape[1])]
+        if len(names) != ann.shape[1]:
+            raise LdxError("bfile_ld_scores: one name per annotation column")
+    _check_complete("bfile_ld_scores", bf.panel, chrom, missing)
+    res = ld_score(bf.panel, bf.pos, window_bp=window_bp, annot=ann, dosage=True, missing=_pairwise(missing))
+    fa = bf.panel.alt_counts().astype(np.float64) / bf.panel.n_hap
+    return LDScoreTable(chrom, list(bf.ids), _poss(bf), fa, ann, names, res, adjust)
+
+
+def bfile_band(src, window_bp: int = 1_000_000, dosage: Optional[bool] = None, em: Optional[bool] = None,
+               missing: Optional[str] = None, **load) -> BandMatrix:
+    """drivers/band.py's ``band_matrix`` from a fileset: the stored band of the genotype-dosage r."""
+    bf = _loaded(src, **load)
+    _dosage_only("bfile_band", dosage, em)
+    _check_missing_arg("bfile_band", True, missing)
+    chrom = _one_chrom("bfile_band", bf)
+    _check_complete("bfile_band", bf.panel, chrom, missing)
+    band = ld_band(bf.panel, bf.pos, window_bp=window_bp, dosage=True, missing=_pairwise(missing))
+    return BandMatrix(chrom, list(bf.ids), _poss(bf), list(bf.refs), list(bf.alts),
+                      bf.panel.alt_freq4().cpu().numpy().tolist(), band)
+
+
+def bfile_em_band(src, window_bp: int = 1_000_000, missing: Optional[str] = None, em: Optional[bool] = None,
+                  dosage: Optional[bool] = None, **load) -> EmBand:
+    """drivers/em.py's ``em_band`` from a fileset: the stored EM r and D' bands."""
+    bf = _loaded(src, **load)
+    dosage, em = _unphased("bfile_em_band", dosage, em, "em")
+    if not em:
+        raise LdxError("bfile_em_band: the EM band is em=True by definition; bfile_band stores the dosage r")
+    chrom = _one_chrom("bfile_em_band", bf)
+    bands = ld_em_band(bf.panel, bf.pos, window_bp=window_bp, missing=missing)
+    return EmBand(chrom, list(bf.ids), _poss(bf), bf.panel.alt_freq4().cpu().numpy().tolist(), bands)
+
+
+def make_bed(prefix_out, src, snps=None, individuals=None, bim: Optional[dict] = None, fam: Optional[dict] = None,
+             alt: Optional[str] = None) -> List[str]:
+    """Write a fileset.  ``src``: a ``Bfile`` -- ``snps`` / ``individuals`` (index arrays or masks over ITS variants and
+    individuals, e.g. a PruneTable's ``pruned.keep``) choose a subset, taken on the device (PackedPanel.select), and the
+    ``.bim`` / ``.fam`` columns follow -- or a bare ``PackedPanel`` with its ``bim`` / ``fam`` columns (plink.write_bfile's).
+    ``alt``: which allele code 1 is written as (default: the Bfile's own, "a1" for a panel).  Returns the three paths."""
+    if isinstance(src, Bfile):
+        panel, alt = src.panel, alt or src.alt
+        si = None if snps is None else select_index(snps, src.n, "SNP")
+        ii = None if individuals is None else select_index(individuals, panel.n_ind, "individual")
+        if si is not None or ii is not None:
+            cols = None if ii is None else np.stack([2 * ii, 2 * ii + 1], axis=1).reshape(-1)
+            panel = panel.select(snps=si, haplotypes=cols)
+        bim, fam = src.bim(si), src.fam(ii)
+    elif isinstance(src, PackedPanel):
+        if bim is None or fam is None or snps is not None or individuals is not None:
+            raise LdxError("make_bed: a bare panel needs its bim and fam columns (and takes no subset)")
+        panel, alt = src, alt or "a1"
+    else:
+        raise LdxError("make_bed: src must be a Bfile or a PackedPanel")
+    return plink.write_bfile(prefix_out, panel.to_bed(alt=alt), bim, fam)
+
+
+# ---------------------------------------------------------------------------------------------- command line
+def _read_names(path: str, n_cols: int) -> list:
+    out = []
+    with open(path) as f:
+        for line in f:
+            parts = line.split()
+            if not parts:
+                continue
+            if len(parts) < n_cols:
+                raise LdxError(f"{path}: a line with fewer than {n_cols} field(s)")
+            out.append(parts[0] if n_cols == 1 else (parts[0], parts[1]))
+    return out
+
+
+def _read_pvalues(path: str, ids: Sequence[str], snp_col: str, p_col: str) -> np.ndarray:
+    """One p per variant of ``ids`` from a whitespace table with a header (PLINK's --clump file); absent variants get NaN."""
+    with open(path) as f:
+        head = f.readline().split()
+        if snp_col not in head or p_col not in head:
+            raise LdxError(f"{path}: no {snp_col} / {p_col} column")
+        a, b = head.index(snp_col), head.index(p_col)
+        got = {}
+        for line in f:
+            parts = line.split()
+            if len(parts) > max(a, b):
+                try:
+                    got[parts[a]] = float(parts[b])
+                except ValueError:
+                    got[parts[a]] = float("nan")
+    return np.asarray([got.get(i, float("nan")) for i in ids], dtype=np.float64)
+
+
+def parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(prog="python -m ld_tools_amd.drivers.plink",
+                                 description="LD tables, clumps, pruned sets and LD scores from a PLINK binary fileset.")
+    sub = ap.add_subparsers(dest="command", required=True)
+
+    def common(name, text):
+        p = sub.add_parser(name, help=text, description=text)
+        p.add_argument("--bfile", required=True, help="prefix of the .bed/.bim/.fam fileset")
+        p.add_argument("--out", required=True, help="prefix of the files written")
+        p.add_argument("--chr", default=None, help="keep this chromosome (needed when the fileset holds several)")
+        p.add_argument("--keep", default=None, help="file of FID IID lines: the individuals to keep")
+        p.add_argument("--extract", default=None, help="file of variant IDs: the variants to keep")
+        p.add_argument("--maf", type=float, default=None, help="minor allele frequency bound")
+        p.add_argument("--geno", type=float, default=None, help="largest missing-call rate of a variant")
+        p.add_argument("--alt", choices=plink.ALTS, default="a1", help="the allele counted as ALT (code 1)")
+        return p
+
+    p = common("ld", "pairs within a window with EM r^2 above a bound (.ld: SNP_A SNP_B R2 DP)")
+    p.add_argument("--ld-window-kb", type=float, default=1000.0)
+    p.add_argument("--ld-window-r2", type=float, default=0.2)
+    p.add_argument("--missing", choices=("pairwise",), default=None)
+    p = common("clump", "PLINK --clump (.clumped)")
+    p.add_argument("--clump", required=True, help="association results with a header")
+    p.add_argument("--clump-snp-field", default="SNP")
+    p.add_argument("--clump-field", default="P")
+    p.add_argument("--clump-p1", type=float, default=1e-4)
+    p.add_argument("--clump-p2", type=float, default=1e-2)
+    p.add_argument("--clump-r2", type=float, default=0.5)
+    p.add_argument("--clump-kb", type=float, default=250.0)
+    p.add_argument("--dosage", action="store_true", help="the genotype-dosage r instead of the EM r")
+    p.add_argument("--missing", choices=("pairwise",), default=None)
+    p = common("prune", "priority pruning (.prune.in / .prune.out)")
+    p.add_argument("--r2", type=float, default=0.2)
+    p.add_argument("--window-kb", type=float, default=250.0)
+    p.add_argument("--em", action="store_true", help="the EM r instead of the genotype-dosage r")
+    p.add_argument("--missing", choices=("pairwise",), default=None)
+    p = common("l2", "LD scores in LDSC's layout (.l2.ldscore.gz, .l2.M, .l2.M_5_50)")
+    p.add_argument("--ld-wind-kb", type=float, default=1000.0)
+    p.add_argument("--missing", choices=("ref", "pairwise"), default=None)
+    p.add_argument("--no-adjust", action="store_true", help="write r^2 sums, not LDSC's unbiased estimate")
+    common("make-bed", "write the selected variants and individuals as a new fileset")
+    return ap
+
+
+def main(argv=None) -> int:
+    from .clump import write_clumped
+    from .em import write_ld_table
+    from .ldscore import write_ldscore
+    from .prune import write_prune
+
+    a = parser().parse_args(argv)
+    keep = None if a.keep is None else _read_names(a.keep, 2)
+    extract = None if a.extract is None else _read_names(a.extract, 1)
+    bf = load_bfile(a.bfile, chrom=a.chr, keep=keep, extract=extract, maf_min=a.maf, geno_max=a.geno, alt=a.alt)
+    if a.command == "ld":
+        side, hits = bfile_ld_table(bf, r2=a.ld_window_r2, window_bp=int(a.ld_window_kb * 1000), missing=a.missing)
+        print(write_ld_table(a.out + ".ld", side, side, hits), "pairs ->", a.out + ".ld")
+    elif a.command == "clump":
+        p = _read_pvalues(a.clump, bf.ids, a.clump_snp_field, a.clump_field)
+        table = bfile_clump(bf, p, p1=a.clump_p1, p2=a.clump_p2, r2=a.clump_r2, window_bp=int(a.clump_kb * 1000),
+                            dosage=a.dosage or None, missing=a.missing)
+        print(write_clumped(a.out + ".clumped", table))
+    elif a.command == "prune":
+        table = bfile_prune(bf, r2=a.r2, window_bp=int(a.window_kb * 1000), em=a.em or None, missing=a.missing)
+        print(*write_prune(a.out, table))
+    elif a.command == "l2":
+        table = bfile_ld_scores(bf, window_bp=int(a.ld_wind_kb * 1000), adjust=not a.no_adjust, missing=a.missing)
+        print(*write_ldscore(a.out, table))
+    else:
+        print(*make_bed(a.out, bf))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

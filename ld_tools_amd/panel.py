@@ -153,6 +153,111 @@ class PackedPanel:
             codes[k, :len(r)] = encode_codes(list(r))
         return PackedPanel.from_codes(codes, device)
 
+    @staticmethod
+    def from_bed(source, keep=None, extract=None, alt: str = "a1", chunk_snps: int = 65536,
+                 out: Optional["PackedPanel"] = None, device: Optional[torch.device] = None) -> "PackedPanel":
+        """The panel of a PLINK SNP-major ``.bed``, unpacked on the device from the file's own bytes (include/ldx.h,
+        ldx_bed_unpack_dev): what ``from_codes(plink.bed_codes_host(rows, n_ind, keep, alt))`` gives, byte for byte, without
+        the codes.  ``source``: a ``plink.BedFile``, or ``(rows, n_ind)`` with the rows a uint8 [n_snps][>= ceil(n_ind / 4)]
+        host array or device tensor (unit stride along a row; any alignment, any row stride).  ``extract``: a SNP index array
+        or mask (``select_index`` rules); those rows' bytes are gathered before the unpack.  ``keep``: an individual index
+        array (any order, repeats allowed) or mask over the file's individuals, applied inside the kernel -- the file may hold
+        far more individuals than a panel can.  ``alt``: which allele is code 1, "a1" (PLINK's and LDSC's counted allele) or
+        "a2".  A host source moves in chunks of ``chunk_snps`` rows (rounded down to a multiple of 128) through pinned
+        staging and is unpacked chunk by chunk; ``out``: a panel of the result's shape to write into (every byte of it is
+        written)."""
+        from . import plink
+
+        dev = device or (out.device if out is not None else require_gpu())
+        a2 = plink._alt_is_a2(alt)
+        if isinstance(source, plink.BedFile):
+            rows, n_ind = source.rows, source.n_ind
+        else:
+            try:
+                rows, n_ind = source
+                n_ind = int(n_ind)
+            except (TypeError, ValueError) as exc:
+                raise _lib.LdxError("from_bed: source must be a BedFile or (rows, n_ind)") from exc
+        on_dev = isinstance(rows, torch.Tensor) and rows.is_cuda
+        if isinstance(rows, torch.Tensor) and not on_dev:
+            rows = rows.numpy()
+        nb = plink.row_bytes(n_ind)
+        if not on_dev:
+            rows = rows if isinstance(rows, np.ndarray) else np.asarray(rows)
+        is_u8 = rows.dtype == (torch.uint8 if on_dev else np.uint8)
+        if n_ind < 1 or rows.ndim != 2 or not is_u8 or rows.shape[1] < nb or rows.shape[0] < 1:
+            raise _lib.LdxError(f"from_bed: rows must be a uint8 matrix [n_snps][>= {nb}] for {n_ind} individuals")
+        if extract is not None:
+            ei = select_index(extract, rows.shape[0], "SNP")
+            rows = rows[torch.from_numpy(ei.astype(np.int64)).to(rows.device)] if on_dev else np.asarray(rows)[ei]
+        ki = None if keep is None else select_index(keep, n_ind, "individual")
+        n_snps, n_dst = int(rows.shape[0]), n_ind if ki is None else int(ki.size)
+        if 2 * n_dst > _lib.MAX_HAPS:
+            raise _lib.LdxError(f"from_bed: {n_dst} individuals are {2 * n_dst} haplotypes, more than {_lib.MAX_HAPS} "
+                                "(LDX_MAX_HAPS); pass keep= to take a subset")
+        if out is None:
+            pb, npad = lib.ldx_plane_bytes(n_snps, 2 * n_dst), lib.ldx_padded_snps(n_snps)
+            e = lambda n, dt: torch.empty(n, dtype=dt, device=dev)  # noqa: E731  (the calls write every byte)
+            out = PackedPanel(n_snps, 2 * n_dst, e(pb, torch.uint8), e(pb, torch.uint8), e(npad, torch.int32),
+                              e(npad, torch.int32), e(npad, torch.float64), e(npad, torch.float64), e(npad, torch.float64))
+        elif (out.n_snps, out.n_hap) != (n_snps, 2 * n_dst) or out.device != dev:
+            raise _lib.LdxError(f"from_bed: out is a {out.n_snps} x {out.n_hap} panel on {out.device}, the file gives "
+                                f"{n_snps} x {2 * n_dst} on {dev}")
+        kd = None if ki is None else torch.from_numpy(ki.view(np.int32)).to(dev)
+        chunk = max(_lib.SLAB_ROWS, int(chunk_snps) // _lib.SLAB_ROWS * _lib.SLAB_ROWS)
+
+        def unpack(block: torch.Tensor, row0: int) -> None:
+            ld = block.stride(0) if block.shape[0] > 1 else max(block.stride(0), nb)
+            check(lib.ldx_bed_unpack_dev(block.data_ptr(), ld, n_ind, block.shape[0], _ptr(kd), n_dst, int(a2), row0, n_snps,
+                                         out.alt.data_ptr(), out.ref.data_ptr(), out.acnt.data_ptr(), out.rcnt.data_ptr(),
+                                         _stream_ptr()), "ldx_bed_unpack_dev")
+
+        if on_dev:
+            if rows.device != dev:
+                raise _lib.LdxError(f"from_bed: the rows are on {rows.device}, the panel on {dev}")
+            if rows.stride(1) != 1:
+                rows = rows.contiguous()
+            for r0 in range(0, n_snps, chunk):
+                unpack(rows[r0:r0 + chunk], r0)
+        else:
+            # two pinned buffers and two device buffers in turn: chunk k + 1 is copied in while chunk k unpacks
+            width = int(rows.shape[1])
+            pinned = [torch.empty((min(chunk, n_snps), width), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+            staged = [torch.empty((min(chunk, n_snps), width), dtype=torch.uint8, device=dev) for _ in range(2)]
+            done = [None, None]
+            for k, r0 in enumerate(range(0, n_snps, chunk)):
+                b, m = k & 1, min(chunk, n_snps - r0)
+                if done[b] is not None:
+                    done[b].synchronize()           # the copy out of this pinned buffer has finished
+                np.copyto(pinned[b][:m].numpy(), rows[r0:r0 + m])
+                staged[b][:m].copy_(pinned[b][:m], non_blocking=True)
+                done[b] = torch.cuda.Event()
+                done[b].record()
+                unpack(staged[b][:m], r0)
+        out.refresh_stats()
+        return out
+
+    def to_bed(self, alt: str = "a1", block_snps: int = 65536) -> np.ndarray:
+        """The panel as PLINK SNP-major ``.bed`` rows, uint8 [n_snps][ceil(n_ind / 4)] on the host: ``plink.codes_bed_host`` of
+        the panel's codes, byte for byte (include/ldx.h, ldx_bed_pack_dev) -- per individual both haplotypes ALT, both REF,
+        one of each (a het, in either order), anything else a missing call.  Packed on the device and moved in blocks of
+        ``block_snps`` rows."""
+        from . import plink
+
+        a2 = plink._alt_is_a2(alt)
+        if self.n_hap % 2:
+            raise _lib.LdxError(f"to_bed: n_hap={self.n_hap} is odd (individual k owns haplotypes 2k and 2k + 1)")
+        nb = plink.row_bytes(self.n_ind)
+        host = np.empty((self.n_snps, nb), dtype=np.uint8)
+        block = max(1, min(int(block_snps), self.n_snps))
+        buf = torch.empty((block, nb), dtype=torch.uint8, device=self.device)
+        for r0 in range(0, self.n_snps, block):
+            m = min(block, self.n_snps - r0)
+            check(lib.ldx_bed_pack_dev(self.alt.data_ptr(), self.ref.data_ptr(), self.n_snps, self.n_hap, r0, m,
+                                       buf.data_ptr(), nb, int(a2), _stream_ptr()), "ldx_bed_pack_dev")
+            host[r0:r0 + m] = buf[:m].cpu().numpy()
+        return host
+
     def pack_from(self, codes: torch.Tensor) -> None:
         """(Re)pack this panel from a device int8 matrix of its shape, on the current stream."""
         s = _stream_ptr()
