@@ -474,7 +474,9 @@ int ldx_ld_decay_dev(const void *alt, const uint32_t *acnt, const uint32_t *rcnt
  *     n_out[0]: the number of blocks;  n_out[1]: the block starts caused by the `left` rule (it outranks the window rule) --
  *               Hudson & Kaplan's lower bound Rm on the number of recombination events, restricted to the window.
  * One wave walks the SNPs (the scan is sequential in the number of blocks); the result stays on the device, so the two
- * calls can be captured together.  Gabriel's D' confidence-interval blocks are not offered: the band carries no D'. */
+ * calls can be captured together.  Gabriel's D' confidence-interval blocks -- the definition for unphased genotypes, a PLINK
+ * fileset among them -- are the "Gabriel blocks" entries below (ldx_ld_em_ci_band_dev, ldx_gabriel_candidates_dev,
+ * ldx_gabriel_pick_dev). */
 size_t ldx_ld_fgt_workspace_bytes(uint32_t n_snps, uint32_t n_hap);
 int ldx_ld_fgt_dev(const void *alt, const uint32_t *acnt, uint32_t n_snps, uint32_t n_hap, const int64_t *positions,
                    int64_t window, uint32_t min_count, const uint8_t *keep, int path,
@@ -1004,6 +1006,72 @@ int ldx_ld_em_neighbors_dev(const void *alt, const void *ref, const uint32_t *ac
                             uint32_t n_hap, int pairwise, const int64_t *positions, int64_t window, float r2_bound,
                             ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits, void *workspace, size_t workspace_bytes,
                             void *stream);
+
+/* ---- Gabriel blocks: D' confidence bounds on the EM band, candidates and block picking ----------------------------------------
+ * This project's own definition, written after Gabriel et al. 2002 and Haploview's defaults; NOT validated against PLINK
+ * --blocks or Haploview.  All thresholds are integers in percent, so everything behind the two bounds is integer logic.
+ *
+ * The bounds of a pair (device function ci_cell, ONE function of N, a_i, a_j, S, H; T, n1..n4, H as in the EM section):
+ *   no genotype table, or a_i or a_j in {0, T}: lo = hi = 0xFF, "no interval" (neither strong nor recombinant).
+ *   s = -1 iff the pair's em_cell r cell is < 0, else +1; Dm = min(a_i (T - a_j), (T - a_i) a_j) for s = +1,
+ *   min(a_i a_j, (T - a_i)(T - a_j)) for s = -1.  For k = 0 .. 100: h1 = (a_i a_j + s k Dm / 100) / T, h2 = a_i - h1,
+ *   h3 = a_j - h1, h4 = T - a_i - a_j + h1, each clamped below at 2^-20;
+ *   L_k = n1 ln h1 + n2 ln h2 + n3 ln h3 + n4 ln h4 + H ln(h1 h4 + h2 h3), a term with count 0 skipped;
+ *   w_k = exp(L_k - max L), W = sum w_k ascending.  lo = (the smallest k with sum_{m <= k} w_m > 0.05 W) - 1, floored at 0;
+ *   hi = (the largest k with sum_{m >= k} w_m > 0.05 W) + 1, capped at 100; the sums run from their own end.  fp64.
+ * ldx_ld_ci_from_counts_dev: that function alone on m tuples (N per tuple, as ldx_ld_em_from_counts_pw_dev).
+ * ldx_ld_em_ci_band_dev: ldx_ld_em_band_dev's arguments and rules, with `keep` (uint8 [n_snps], NULL = all) and the two bound
+ *   arrays (uint8 [n_cells]) in place of the float values: ci_lo / ci_hi[offsets[i] + j - lo[i]] for every in-window pair
+ *   i > j of kept SNPs; every other cell of the layout is 0xFF and runs no likelihood surface.  Every one of the n_cells cells
+ *   is written by the call (a fill in front of the band): no memset by the caller.
+ *
+ * Candidates (ldx_gabriel_candidates_dev), on the stored bounds and `keep` -- the caller folds MAF and `live` into it:
+ *   a pair of kept SNPs is strong at cut c iff lo != 0xFF, lo >= c and hi >= strong_hi (98); recombinant iff hi < recomb_hi (90).
+ *   A candidate is first < last, both kept, in each other's window (a cell of the layout), the pair strong at cand_cut (70).
+ *   m = the kept SNPs in [first, last], span = pos_last - pos_first, row = m - 2 capped at 3:
+ *       m      cut[row]   max_span[row]      min_informative[row]
+ *       2      80         20 000             1
+ *       3      50         30 000             3
+ *       4      50         window (-1)        6
+ *       >= 5   70         window (-1)        6
+ *   nS = the strong pairs at cut[row], nR = the recombinant pairs, over all pairs of kept SNPs inside [first, last].  Valid iff
+ *   span <= max_span[row], nS + nR >= min_informative[row] and frac_den nS > frac_num (nS + nR) (20, 19: more than 95 %).
+ *   The list has one slot per cell of the layout, column-major (first ascending, then last): cand_span[slot] = the span of a
+ *   valid candidate, -1 otherwise; cand_first / cand_last[slot] always.  params NULL = the defaults above
+ *   (ldx_gabriel_default_params writes them).
+ * Pick (ldx_gabriel_pick_dev): the caller sorts cand_span descending with a STABLE sort -- ties stay ordered by smaller first,
+ *   then smaller last -- and passes the sorted spans and the permutation (order[k] = the slot at rank k).  Going down the valid
+ *   candidates, one is accepted iff no SNP in [first, last] lies in an accepted block.
+ *     block_of[i] (uint32 [n_snps]): the 0-based block, in position order, of SNP i; 0xFFFFFFFF for a SNP not kept (it may lie
+ *                 between a block's ends and is no member); 0xFFFFFFFE for a kept SNP in no block;
+ *     n_out[0]: the blocks;  n_out[1]: the valid candidates.
+ * Workspaces (256-byte aligned, no initialisation needed, one per launch in flight): ldx_gabriel_candidates_workspace_bytes
+ * (16 bytes per cell and 12 per SNP) and ldx_gabriel_pick_workspace_bytes.  n_cells = 0 (no pair in any window) is valid: the
+ * candidates call does nothing and the pick call marks every kept SNP 0xFFFFFFFE.  Argument rules as for the EM band, checked
+ * before any HIP call; the calls only enqueue work on `stream`. */
+typedef struct ldx_gabriel_params {
+    uint32_t cand_cut, strong_hi, recomb_hi;
+    uint32_t cut[4];
+    int64_t max_span[4];           /* negative: the window */
+    uint32_t min_informative[4];
+    uint32_t frac_num, frac_den;
+} ldx_gabriel_params;
+void ldx_gabriel_default_params(ldx_gabriel_params *params);
+int ldx_ld_ci_from_counts_dev(size_t m, const uint32_t *N, const uint32_t *a1, const uint32_t *a2, const uint32_t *S,
+                              const uint32_t *H, uint8_t *lo, uint8_t *hi, void *stream);
+int ldx_ld_em_ci_band_dev(const void *alt, const void *ref, const uint32_t *acnt, const uint32_t *rcnt, uint32_t n_snps,
+                          uint32_t n_hap, int pairwise, const int64_t *positions, int64_t window, const uint8_t *keep,
+                          const uint32_t *lo, const uint64_t *offsets, uint8_t *ci_lo, uint8_t *ci_hi, uint64_t n_cells,
+                          void *workspace, size_t workspace_bytes, void *stream);
+size_t ldx_gabriel_candidates_workspace_bytes(uint32_t n_snps, uint64_t n_cells);
+size_t ldx_gabriel_pick_workspace_bytes(uint32_t n_snps);
+int ldx_gabriel_candidates_dev(const uint8_t *ci_lo, const uint8_t *ci_hi, const uint32_t *lo, const uint64_t *offsets,
+                               uint64_t n_cells, const int64_t *positions, const uint8_t *keep, uint32_t n_snps, int64_t window,
+                               const ldx_gabriel_params *params, int64_t *cand_span, uint32_t *cand_first, uint32_t *cand_last,
+                               void *workspace, size_t workspace_bytes, void *stream);
+int ldx_gabriel_pick_dev(const int64_t *sorted_span, const int64_t *order, const uint32_t *cand_first, const uint32_t *cand_last,
+                         uint64_t n_cells, const uint8_t *keep, uint32_t n_snps, uint32_t *block_of, uint32_t *n_out,
+                         void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- synthetic panels: deterministic, identical on host and device ------ */
 /* codes int8 [n_snps][ld_codes] receive global SNPs [snp_offset, snp_offset + n_snps) (a rank's

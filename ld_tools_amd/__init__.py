@@ -21,6 +21,8 @@ from .ops import LDRectHits, ld_rect, ld_rect_hits, rect_hits_host  # noqa: F401
 from .ops import ld_rect_counts, pairwise_cell_host, pairwise_counts_host, pw_snp_stats  # noqa: F401
 from .ops import LDEm, em_host, ld_em, ld_em_counts, ld_em_from_counts, ld_em_hits  # noqa: F401
 from .ops import LDEmBand, em_snp_stats, ld_em_band  # noqa: F401
+from .ops import (GabrielBlocks, LDCiBand, dprime_ci_host, gabriel_candidates_host, gabriel_kept_host,  # noqa: F401
+                  gabriel_pick_host, ld_ci_from_counts, ld_dprime_ci, ld_gabriel_blocks)
 from .panel import PackedPanel, encode_codes, select_index  # noqa: F401
 from . import plink  # noqa: F401
 from .plink import BedFile, bed_codes_host, codes_bed_host, write_bfile  # noqa: F401
@@ -30,5 +32,7 @@ __all__ = ["PackedPanel", "encode_codes", "select_index", "ld_triangle", "ld_are
            "ld_prune", "Pruned", "ld_decay", "LDDecay", "ld_blocks", "LDBlocks", "blocks_host", "ld_cross", "LDCross", "ld_regions", "LDRegions", "cross_host", "split_host",
            "region_positions", "ld_matvec", "LDProduct", "ld_ridge", "RidgeResult", "prod_terms", "dosage_host", "ld_band", "LDBand",
            "ld_cross_score", "band_layout_host", "cross_terms", "ld_rect", "ld_rect_hits", "LDRectHits", "rect_hits_host", "ld_rect_counts", "pairwise_counts_host", "pairwise_cell_host", "pw_snp_stats", "ld_em", "LDEm",
-           "ld_em_hits", "ld_em_counts", "ld_em_from_counts", "em_host", "ld_em_band", "LDEmBand", "em_snp_stats", "LdxError",
+           "ld_em_hits", "ld_em_counts", "ld_em_from_counts", "em_host", "ld_em_band", "LDEmBand", "em_snp_stats", "ld_dprime_ci",
+           "LDCiBand", "ld_gabriel_blocks", "GabrielBlocks", "ld_ci_from_counts", "dprime_ci_host", "gabriel_candidates_host",
+           "gabriel_pick_host", "gabriel_kept_host", "LdxError",
            "version", "plink", "BedFile", "bed_codes_host", "codes_bed_host", "write_bfile"]

@@ -193,6 +193,13 @@ SIGNATURES = {
     "ldx_em_snp_stats_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _int, _vp, _vp, _vp, _vp, _vp]),
     "ldx_ld_em_band_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _int, _vp, _i64, _vp, _vp, _vp, _vp, _u64, _vp, _sz, _vp]),
     "ldx_ld_em_neighbors_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _int, _vp, _i64, C.c_float, _vp, _u64, _vp, _vp, _sz, _vp]),
+    "ldx_gabriel_default_params": (None, [_vp]),
+    "ldx_ld_ci_from_counts_dev": (_int, [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ldx_ld_em_ci_band_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _sz, _vp]),
+    "ldx_gabriel_candidates_workspace_bytes": (_sz, [_u32, _u64]),
+    "ldx_gabriel_pick_workspace_bytes": (_sz, [_u32]),
+    "ldx_gabriel_candidates_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _u32, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ldx_gabriel_pick_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _sz, _vp]),
     "ldx_ld_select_workspace_bytes": (_sz, [_u32]),
     "ldx_ld_select_dev": (_int, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ldx_set_area_path": (_int, [_int]),
@@ -208,6 +215,13 @@ for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)          # AttributeError here == header and library out of sync
     _fn.restype = _res
     _fn.argtypes = _args
+
+
+class GabrielParams(C.Structure):
+    """ldx_gabriel_params of include/ldx.h ("Gabriel blocks")."""
+
+    _fields_ = [("cand_cut", _u32), ("strong_hi", _u32), ("recomb_hi", _u32), ("cut", _u32 * 4), ("max_span", _i64 * 4),
+                ("min_informative", _u32 * 4), ("frac_num", _u32), ("frac_den", _u32)]
 
 
 def check(rc: int, what: str = "") -> None:

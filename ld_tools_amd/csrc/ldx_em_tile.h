@@ -151,6 +151,68 @@ __device__ __forceinline__ Cell em_cell(uint32_t n_ind, uint32_t a_i, uint32_t a
     return Cell{(float)r, (float)(__builtin_fabs(dn) / dmax), x};
 }
 
+// ---- the D' confidence bounds of a pair (include/ldx.h, "Gabriel blocks"): (N, a_i, a_j, S, H) -> lo, hi in percent -----------
+// ONE function of the five integers, like em_cell, which it calls for the sign: the likelihood of the table on the 101 grid
+// points D' = k / 100 of the sign's side, L_k = em_loglik's function at h1 = (a_i a_j + s k Dm / 100) / T (every h clamped below
+// at 2^-20; a term with count 0 skipped), the weights exp(L_k - max L) summed ascending, and the two 5 % tails.  The 101
+// values live in a per-lane array (scratch): one pass of logarithms, one of exponentials, two of sums.
+constexpr int kCiGrid = 100;
+constexpr uint8_t kNoCi = 0xFF;       // no interval: no genotype table, or a degenerate pair
+struct Ci {
+    uint8_t lo, hi;
+};
+__device__ __forceinline__ Ci ci_cell(uint32_t n_ind, uint32_t a_i, uint32_t a_j, uint32_t S, uint32_t H)
+{
+    const Cell c = em_cell(n_ind, a_i, a_j, S, H);
+    const int64_t T = 2 * (int64_t)n_ind, ai = a_i, aj = a_j, h = H;
+    if (c.r != c.r || ai == 0 || ai == T || aj == 0 || aj == T) return Ci{kNoCi, kNoCi};
+    const int64_t n1 = ((int64_t)S - h) / 2, n2 = ai - n1 - h, n3 = aj - n1 - h, n4 = T - ai - aj + n1;
+    const bool neg = c.r < 0.0f;   // the r CELL decides the side, its tie rule included
+    const int64_t u = ai * (T - aj), v = (T - ai) * aj, p = ai * aj, q = (T - ai) * (T - aj);
+    const int64_t dm = neg ? (p < q ? p : q) : (u < v ? u : v);
+    const double Td = (double)T, base = (double)p, eps = 0x1p-20;
+    const double f1 = (double)n1, f2 = (double)n2, f3 = (double)n3, f4 = (double)n4, fh = (double)h;
+    const double di = (double)ai, dj = (double)aj, d4 = (double)(T - ai - aj);
+    double w[kCiGrid + 1];
+    double top = -__builtin_inf();
+    for (int k = 0; k <= kCiGrid; ++k) {
+        const double step = (double)((int64_t)k * dm) / 100.0;   // k Dm < 2^36: exact before the division
+        double h1 = (neg ? base - step : base + step) / Td;
+        double h2 = di - h1, h3 = dj - h1, h4 = d4 + h1;
+        h1 = h1 < eps ? eps : h1, h2 = h2 < eps ? eps : h2, h3 = h3 < eps ? eps : h3, h4 = h4 < eps ? eps : h4;
+        const double l14 = (n1 > 0 ? f1 * log(h1) : 0.0) + (n4 > 0 ? f4 * log(h4) : 0.0);
+        const double l23 = (n2 > 0 ? f2 * log(h2) : 0.0) + (n3 > 0 ? f3 * log(h3) : 0.0);
+        const double l = (l14 + l23) + (h > 0 ? fh * log(h1 * h4 + h2 * h3) : 0.0);
+        w[k] = l;
+        top = l > top ? l : top;
+    }
+    double W = 0.0;
+    for (int k = 0; k <= kCiGrid; ++k) {
+        const double e = exp(w[k] - top);
+        w[k] = e;
+        W += e;
+    }
+    const double tail = 0.05 * W;
+    int klo = kCiGrid, khi = 0;   // (the whole sum is W > tail: both loops stop)
+    double cum = 0.0;
+    for (int k = 0; k <= kCiGrid; ++k) {
+        cum += w[k];
+        if (cum > tail) {
+            klo = k;
+            break;
+        }
+    }
+    cum = 0.0;
+    for (int k = kCiGrid; k >= 0; --k) {
+        cum += w[k];
+        if (cum > tail) {
+            khi = k;
+            break;
+        }
+    }
+    return Ci{(uint8_t)(klo > 0 ? klo - 1 : 0), (uint8_t)(khi < kCiGrid ? khi + 1 : kCiGrid)};
+}
+
 // ---- the two-set K loop: S and H of I slab ti x J slab tj, no missing code read --------------------------------------------------
 // Called by the whole workgroup.  `lds` holds two {S image, H image} buffers (2 x kImage); the first barrier inside also
 // publishes what the caller wrote to LDS of its own before the call.  On return every wave is past the last block's barrier:

@@ -14,7 +14,8 @@
 //   * per-tile tables: r_low, r_lo, r_off of the tile's 128 rows, 2 KiB of LDS beside tile_body's 65 KiB; tile_body's first
 //     barrier publishes them.  A cell is inside iff r_low[li] <= j < i; em_cell -- the fp64 root search -- runs for the cells
 //     inside only, so a tile that the window cuts pays for its share.
-//   * epilogues: Store writes values_r / values_d[offsets[i] + j - lo[i]] under ldx_ld_band_dev's guard; Nbr appends both
+//   * epilogues: Ci (ldx_ld_em_ci_band_dev) writes the D' confidence bounds of ci_cell for the pairs of kept SNPs into a layout
+//     that fill_no_ci_kernel set to 0xFF in front of the band; Store writes values_r / values_d[offsets[i] + j - lo[i]] under ldx_ld_band_dev's guard; Nbr appends both
 //     orientations of a pair in one HitAppender call, D' in the record's fourth word (as ldx_ld_em_rect_hits_dev).
 #include "ldx_band_plan.h"
 #include "ldx_em_pw_tile.h"
@@ -26,7 +27,7 @@ using em::kThreads;
 static_assert(kThreads == bandplan::kBandThreads, "the walk's workgroup");
 using BandLds = bandplan::RowTables<kSlab>;   // the band's own per-tile tables, beside tile_body's: 2 KiB
 
-enum Op : int { kStore = 0, kNbr = 1 };
+enum Op : int { kStore = 0, kNbr = 1, kCi = 2 };
 
 struct Args {
     em_pw::Side s;             // the panel: both sides of every tile
@@ -41,6 +42,8 @@ struct Args {
     ldx_hit *hits;
     uint64_t hit_cap;
     unsigned long long *n_hits;
+    const uint8_t *keep;       // bounds: the SNPs whose pairs get an interval (null: all)
+    uint8_t *ci_lo, *ci_hi;    // bounds: the caller's layout, filled with kNoCi in front of the band
 };
 
 template <int kOp>
@@ -54,6 +57,16 @@ struct BandEmit {
     {
         const uint32_t li = i - ti * kSlab;
         const bool inside = bandplan::inside(bl, li, i, j);
+        if constexpr (kOp == kCi) {
+            // the likelihood surface runs for the pairs of kept SNPs inside only; every other cell keeps the fill's kNoCi
+            uint64_t idx;
+            if (bandplan::store_at(bl, li, j, inside && (!p.keep || (p.keep[i] != 0u && p.keep[j] != 0u)), p.n_cells, idx)) {
+                const em::Ci ci = em::ci_cell(N, A, B, S, H);
+                p.ci_lo[idx] = ci.lo;
+                p.ci_hi[idx] = ci.hi;
+            }
+            return;
+        }
         em::Cell c{-0.0f, -0.0f, 0.0};
         if (inside) c = em::em_cell(N, A, B, S, H);
         if constexpr (kOp == kStore) {
@@ -75,7 +88,7 @@ __global__ void __launch_bounds__(kThreads, 2) emband_kernel(Args p)
     __shared__ BandLds bl;
     BandEmit<kOp> emit{p, bl, HitAppender{p.hits, p.hit_cap, p.n_hits, threadIdx.x & 63u}};
     bandplan::walk<kSlab>(p.plan, p.s.n, [&](uint32_t ti, uint32_t tj, uint32_t tid) {
-        bandplan::fill_rows<kOp == kStore>(bl, p.plan, p.lo, p.offsets, p.s.n, ti, tid);
+        bandplan::fill_rows<kOp != kNbr>(bl, p.plan, p.lo, p.offsets, p.s.n, ti, tid);
         emit.ti = ti;
         em_pw::tile_body<kPairwise>(sm, p.s, p.s, p.nblocks, p.n_hap, ti, tj, tid, emit);   // (its first barrier publishes the tables)
     });
@@ -109,6 +122,23 @@ __global__ void __launch_bounds__(256) snp_stats_kernel(const uint32_t *__restri
     out_a[row] = A;
     diag[row] = lv ? 1.0f : -0.0f;
     if (live) live[row] = lv ? 1u : 0u;
+}
+
+// kNoCi into every cell of both bound arrays: four cells per thread, one 32-bit store where the array allows it
+__global__ void __launch_bounds__(256) fill_no_ci_kernel(uint8_t *__restrict__ a, uint8_t *__restrict__ b, uint64_t n_cells)
+{
+    const uint64_t at = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 4u;
+    if (at >= n_cells) return;
+    uint8_t *const both[2] = {a, b};
+#pragma unroll
+    for (int w = 0; w < 2; ++w) {
+        uint8_t *const dst = both[w] + at;
+        if (((uintptr_t)dst & 3u) == 0u && at + 4u <= n_cells) {
+            *reinterpret_cast<uint32_t *>(dst) = 0xFFFFFFFFu;
+        } else {
+            for (uint64_t q = 0; q < 4u && at + q < n_cells; ++q) dst[q] = em::kNoCi;
+        }
+    }
 }
 
 // low, the plan, then the band (bandplan::launch); the tile bound is the lower triangle of I blocks x slabs
@@ -202,4 +232,30 @@ extern "C" int ldx_ld_em_neighbors_dev(const void *alt, const void *ref, const u
     p.bound = r2_bound, p.hits = hits, p.hit_cap = hit_cap, p.n_hits = (unsigned long long *)n_hits;
     LDX_HIP(hipMemsetAsync(n_hits, 0, sizeof(uint64_t), (hipStream_t)stream));   // the slot counter starts at 0
     return emband::launch<emband::kNbr>(p, pairwise != 0, positions, window, workspace, (hipStream_t)stream);
+}
+
+extern "C" int ldx_ld_em_ci_band_dev(const void *alt, const void *ref, const uint32_t *acnt, const uint32_t *rcnt, uint32_t n_snps,
+                                     uint32_t n_hap, int pairwise, const int64_t *positions, int64_t window, const uint8_t *keep,
+                                     const uint32_t *lo, const uint64_t *offsets, uint8_t *ci_lo, uint8_t *ci_hi, uint64_t n_cells,
+                                     void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *const who = "ldx_ld_em_ci_band_dev";
+    LDX_EMB_PANEL(who);
+    LDX_ARG_PTR(who, lo);
+    LDX_ARG_PTR(who, offsets);
+    LDX_ARG_REQUIRE((ci_lo != nullptr && ci_hi != nullptr) || n_cells == 0u,
+                    "%s: ci_lo or ci_hi is a null pointer but n_cells is %llu", who, (unsigned long long)n_cells);
+    if (const int rc = bandplan::band_args_ok<kSlab>(who, n_snps, n_hap, kOddReason, positions, window, workspace, workspace_bytes))
+        return rc;
+    if (n_cells == 0u) return LDX_OK;   // no pair in any window: nothing to write
+    const uint64_t fill_grid = (n_cells + 1023u) / 1024u;
+    if (fill_grid >= (1ull << 31)) {
+        set_error("%s: n_cells = %llu needs 2^31 or more workgroups", who, (unsigned long long)n_cells);
+        return LDX_E_UNSUPPORTED;
+    }
+    emband::fill_no_ci_kernel<<<(uint32_t)fill_grid, 256, 0, (hipStream_t)stream>>>(ci_lo, ci_hi, n_cells);
+    LDX_HIP(hipGetLastError());
+    emband::Args p = make_args(alt, ref, acnt, rcnt, n_snps, n_hap);
+    p.lo = lo, p.offsets = offsets, p.n_cells = n_cells, p.keep = keep, p.ci_lo = ci_lo, p.ci_hi = ci_hi;
+    return emband::launch<emband::kCi>(p, pairwise != 0, positions, window, workspace, (hipStream_t)stream);
 }

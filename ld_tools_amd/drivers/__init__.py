@@ -11,7 +11,7 @@ as the VCF source; pysam itself is only imported by the command-line shells.
 from .area import AreaQueryResult, area_scan, get_inld_vars, write_area_file  # noqa: F401
 from .band import (BandMatrix, CrossScoreTable, band_matrix, cross_scores_by_group, write_band,  # noqa: F401
                    write_cross_score)
-from .blocks import write_blocks  # noqa: F401
+from .blocks import GabrielTable, gabriel_blocks, write_blocks, write_gabriel_blocks  # noqa: F401
 from .clump import ClumpTable, clump, write_clumped  # noqa: F401
 from .decay import write_decay  # noqa: F401
 from .ingest import RaggedGenotypesError, codes_matrix, find_record, haplotype_columns, sample_genotypes  # noqa: F401
@@ -29,7 +29,7 @@ from .triangle import (TriangleMatrix, create_matrix, stream_triangle_table, tri
 # drivers/plink.py is also a command (python -m ld_tools_amd.drivers.plink), so its names are bound on first use rather than
 # imported here: runpy would otherwise find the module loaded before it runs it
 _PLINK_NAMES = ("Bfile", "load_bfile", "bfile_ld_table", "bfile_clump", "bfile_prune", "bfile_ld_scores", "bfile_band",
-                "bfile_em_band", "make_bed")
+                "bfile_em_band", "bfile_blocks", "make_bed")
 
 
 def __getattr__(name):

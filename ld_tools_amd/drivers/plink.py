@@ -8,12 +8,13 @@ dataclasses of the VCF drivers from it, so that their writers write them unchang
     bfile_ld_scores  -> LDScoreTable for write_ldscore                     ldsc.py --l2
     bfile_band       -> BandMatrix for write_band
     bfile_em_band    -> EmBand for write_em_band
+    bfile_blocks     -> GabrielTable for write_gabriel_blocks              PLINK --blocks (Gabriel et al.'s D' interval rule)
 
 A ``.bed`` holds unphased genotype calls: a het is written (ALT, REF) whatever the truth, so the haplotype r of the phased
 operators means nothing here.  Every driver defaults to an unphased form (EM or genotype dosage) and refuses
 ``dosage=False, em=False``.  ``make_bed`` writes a panel, or a subset of a loaded fileset, back as a fileset.
 
-    python -m ld_tools_amd.drivers.plink {ld,clump,prune,l2,make-bed} --bfile P --out O ...
+    python -m ld_tools_amd.drivers.plink {ld,clump,prune,l2,blocks,make-bed} --bfile P --out O ...
 """
 from __future__ import annotations
 
@@ -26,9 +27,10 @@ import numpy as np
 
 from .. import plink
 from .._lib import LdxError
-from ..ops import ld_band, ld_clump, ld_em_band, ld_neighbors, ld_prune, ld_score
+from ..ops import ld_band, ld_clump, ld_em_band, ld_gabriel_blocks, ld_neighbors, ld_prune, ld_score
 from ..panel import PackedPanel, select_index
 from .band import BandMatrix
+from .blocks import GabrielTable
 from .clump import ClumpTable
 from .em import EmBand
 from .ldscore import LDScoreTable, _check_complete, _check_missing_arg, _pairwise
@@ -293,6 +295,22 @@ def bfile_em_band(src, window_bp: int = 1_000_000, missing: Optional[str] = None
     return EmBand(chrom, list(bf.ids), _poss(bf), bf.panel.alt_freq4().cpu().numpy().tolist(), bands)
 
 
+def bfile_blocks(src, window_bp: int = 500_000, missing: Optional[str] = "pairwise", maf_min: float = 0.05, keep_snps=None,
+                 **more) -> GabrielTable:
+    """Gabriel's D' confidence-interval blocks of a fileset, for ``write_gabriel_blocks``: ops.ld_gabriel_blocks on the genotype
+    calls -- the operator is unphased by definition, so a .bed is its natural input.  ``missing``: "pairwise" (the default:
+    every pair over the individuals called at both variants, as PLINK treats missing calls) or None (a missing call counts as
+    REF).  ``keep_snps``: bool [n] over the loaded variants; ``more``: load_bfile's arguments and the block parameters
+    (ops.GABRIEL_DEFAULTS)."""
+    from ..ops import GABRIEL_DEFAULTS
+
+    params = {k: more.pop(k) for k in list(more) if k in GABRIEL_DEFAULTS}
+    bf = _loaded(src, **more)
+    chrom = _one_chrom("bfile_blocks", bf)
+    res = ld_gabriel_blocks(bf.panel, bf.pos, window_bp=window_bp, missing=missing, keep=keep_snps, maf_min=maf_min, **params)
+    return GabrielTable(chrom, list(bf.ids), _poss(bf), res)
+
+
 def make_bed(prefix_out, src, snps=None, individuals=None, bim: Optional[dict] = None, fam: Optional[dict] = None,
              alt: Optional[str] = None) -> List[str]:
     """Write a fileset.  ``src``: a ``Bfile`` -- ``snps`` / ``individuals`` (index arrays or masks over ITS variants and
@@ -388,11 +406,16 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--ld-wind-kb", type=float, default=1000.0)
     p.add_argument("--missing", choices=("ref", "pairwise"), default=None)
     p.add_argument("--no-adjust", action="store_true", help="write r^2 sums, not LDSC's unbiased estimate")
+    p = common("blocks", "haplotype blocks by Gabriel et al.'s D' confidence-interval rule (.blocks, .blocks.det)")
+    p.add_argument("--blocks-max-kb", type=float, default=500.0, help="the window: the largest distance of a block's ends")
+    p.add_argument("--blocks-min-maf", type=float, default=0.05)
+    p.add_argument("--missing", choices=("pairwise", "ref"), default="pairwise")
     common("make-bed", "write the selected variants and individuals as a new fileset")
     return ap
 
 
 def main(argv=None) -> int:
+    from .blocks import write_gabriel_blocks
     from .clump import write_clumped
     from .em import write_ld_table
     from .ldscore import write_ldscore
@@ -416,6 +439,10 @@ def main(argv=None) -> int:
     elif a.command == "l2":
         table = bfile_ld_scores(bf, window_bp=int(a.ld_wind_kb * 1000), adjust=not a.no_adjust, missing=a.missing)
         print(*write_ldscore(a.out, table))
+    elif a.command == "blocks":
+        table = bfile_blocks(bf, window_bp=int(a.blocks_max_kb * 1000), missing=None if a.missing == "ref" else a.missing,
+                             maf_min=a.blocks_min_maf)
+        print(table.result.n_blocks, "blocks ->", *write_gabriel_blocks(a.out, table.result, table.rs_ids, table.chrom))
     else:
         print(*make_bed(a.out, bf))
     return 0

@@ -25,6 +25,7 @@ tensors; nothing here computes LD on the host.
 """
 from __future__ import annotations
 
+import ctypes
 from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
@@ -3001,6 +3002,398 @@ def em_host(n_ind: int, a_i: int, a_j: int, S: int, H: int) -> Tuple[float, floa
     r = dn / math.sqrt(float(ai * (T - ai)) * float(aj * (T - aj)))
     dmax = min(ai * (T - aj), (T - ai) * aj) if dn >= 0.0 else min(ai * aj, (T - ai) * (T - aj))
     return x, r, abs(dn) / float(dmax)
+
+
+# ---- Gabriel blocks: D' confidence bounds on the EM band (include/ldx.h, "Gabriel blocks")
+NO_BLOCK = 0xFFFFFFFE            # block_of of a kept SNP that lies in no block (ldx_gabriel_pick_dev)
+NO_CI = 0xFF                     # both bounds of a pair without an interval
+CI_TAIL = 0.05
+GABRIEL_DEFAULTS = dict(cand_cut=70, strong_hi=98, recomb_hi=90, cuts=(80, 50, 50, 70), max_spans=(20_000, 30_000, None, None),
+                        min_informative=(1, 3, 6, 6), strong_share=(19, 20))
+
+
+def gabriel_params(**kw) -> dict:
+    """The section-3 parameters with their defaults (GABRIEL_DEFAULTS), checked: cuts / max_spans / min_informative have one
+    entry per row m = 2, 3, 4, >= 5 (a max span of None is the window); strong_share = (19, 20) means more than 95 %."""
+    unknown = set(kw) - set(GABRIEL_DEFAULTS)
+    if unknown:
+        raise _lib.LdxError(f"unknown Gabriel parameter(s): {sorted(unknown)}")
+    p = {k: kw[k] if kw.get(k) is not None else v for k, v in GABRIEL_DEFAULTS.items()}
+    for k in ("cuts", "max_spans", "min_informative"):
+        p[k] = tuple(p[k])
+        if len(p[k]) != 4:
+            raise _lib.LdxError(f"{k} needs four entries (m = 2, 3, 4, >= 5)")
+    p["max_spans"] = tuple(-1 if s is None or int(s) < 0 else int(s) for s in p["max_spans"])
+    num, den = (int(v) for v in p["strong_share"])
+    if den <= 0 or not 0 <= num <= den:
+        raise _lib.LdxError("strong_share must be (num, den) with 0 <= num <= den, den > 0")
+    p["strong_share"] = (num, den)
+    for k in ("cand_cut", "strong_hi", "recomb_hi"):
+        p[k] = int(p[k])
+    for v in (p["cand_cut"], p["strong_hi"], p["recomb_hi"], *p["cuts"], *p["min_informative"]):
+        if not 0 <= int(v) < (1 << 32):
+            raise _lib.LdxError("Gabriel parameters must be non-negative 32-bit integers")
+    return p
+
+
+def _gabriel_struct(p: dict) -> "_lib.GabrielParams":
+    s = _lib.GabrielParams()
+    s.cand_cut, s.strong_hi, s.recomb_hi = p["cand_cut"], p["strong_hi"], p["recomb_hi"]
+    for k in range(4):
+        s.cut[k], s.max_span[k], s.min_informative[k] = int(p["cuts"][k]), p["max_spans"][k], int(p["min_informative"][k])
+    s.frac_num, s.frac_den = p["strong_share"]
+    return s
+
+
+def dprime_ci_host(n_ind, a_i, a_j, S, H):
+    """Host mirror (numpy, fp64) of ci_cell (ldx_em_tile.h): the D' confidence bounds (lo, hi) in percent of a count tuple,
+    (NO_CI, NO_CI) for a tuple that is no genotype table or a degenerate pair.  Scalars give two ints, arrays (``n_ind`` may
+    stay a scalar) two uint8 arrays.  The sign is em_host's r as a float32 cell; a reference, not promised to match the
+    device where a cumulative sum grazes the 5 % line."""
+    scalar = np.ndim(a_i) == 0
+    A, B, S, H = (np.atleast_1d(np.asarray(v, dtype=np.int64)).reshape(-1) for v in (a_i, a_j, S, H))
+    N = np.broadcast_to(np.asarray(n_ind, dtype=np.int64).reshape(-1), A.shape)
+    m = A.shape[0]
+    T = 2 * N
+    neg = np.zeros(m, dtype=bool)
+    ok = np.zeros(m, dtype=bool)
+    for k in range(m):
+        r = em_host(int(N[k]), int(A[k]), int(B[k]), int(S[k]), int(H[k]))[1]
+        ok[k] = r == r and 0 < A[k] < T[k] and 0 < B[k] < T[k]
+        neg[k] = ok[k] and bool(np.float32(r) < 0)
+    lo = np.full(m, NO_CI, dtype=np.uint8)
+    hi = np.full(m, NO_CI, dtype=np.uint8)
+    if ok.any():
+        N, T, A, B, S, H, neg_ = N[ok], T[ok], A[ok], B[ok], S[ok], H[ok], neg[ok]
+        n1 = (S - H) // 2
+        n2, n3, n4 = A - n1 - H, B - n1 - H, T - A - B + n1
+        dm = np.where(neg_, np.minimum(A * B, (T - A) * (T - B)), np.minimum(A * (T - B), (T - A) * B))
+        step = (np.arange(101, dtype=np.int64)[None, :] * dm[:, None]).astype(np.float64) / 100.0
+        base = (A * B).astype(np.float64)[:, None]
+        h1 = np.where(neg_[:, None], base - step, base + step) / T.astype(np.float64)[:, None]
+        h2 = A.astype(np.float64)[:, None] - h1
+        h3 = B.astype(np.float64)[:, None] - h1
+        h4 = (T - A - B).astype(np.float64)[:, None] + h1
+        h1, h2, h3, h4 = (np.maximum(h, 2.0 ** -20) for h in (h1, h2, h3, h4))
+
+        def term(cnt, h):
+            return np.where(cnt[:, None] > 0, cnt.astype(np.float64)[:, None] * np.log(h), 0.0)
+
+        ell = ((term(n1, h1) + term(n4, h4)) + (term(n2, h2) + term(n3, h3))) + term(H, h1 * h4 + h2 * h3)
+        w = np.exp(ell - ell.max(axis=1, keepdims=True))
+        up = np.cumsum(w, axis=1)                     # ascending sums; W is the last
+        down = np.cumsum(w[:, ::-1], axis=1)          # descending sums, from k = 100
+        tail = CI_TAIL * up[:, -1:]
+        klo = np.argmax(up > tail, axis=1)
+        khi = 100 - np.argmax(down > tail, axis=1)
+        lo[ok] = np.maximum(klo - 1, 0).astype(np.uint8)
+        hi[ok] = np.minimum(khi + 1, 100).astype(np.uint8)
+    return (int(lo[0]), int(hi[0])) if scalar else (lo, hi)
+
+
+def gabriel_kept_host(n_called, a_sum, keep=None, maf_min: float = 0.05) -> np.ndarray:
+    """bool [n]: keep & live & (MAF over the SNP's own called individuals >= maf_min), from em_snp_stats' N and A: live iff
+    0 < A < 2 N, MAF = min(A, 2 N - A) / (2 N), compared as min(A, 2 N - A) >= maf_min * 2 N in fp64."""
+    t = 2 * np.asarray(n_called, dtype=np.int64)
+    a = np.asarray(a_sum, dtype=np.int64)
+    kept = (a > 0) & (a < t) & (np.minimum(a, t - a).astype(np.float64) >= float(maf_min) * t.astype(np.float64))
+    return kept if keep is None else kept & np.asarray(keep).astype(bool)
+
+
+def gabriel_candidates_host(lo, hi, positions, kept, window: int, **params) -> np.ndarray:
+    """Host mirror of ldx_gabriel_candidates_dev: the VALID candidates as int64 [k, 3] rows (first, last, span), ordered by
+    first, then last.  ``lo`` / ``hi``: the two bound bands (uint8 [n_cells]) in the layout of band_layout_host(positions,
+    window); ``kept`` bool [n]; ``params``: the section-3 parameters (gabriel_params)."""
+    p = gabriel_params(**params)
+    lo = np.asarray(lo).astype(np.int64)
+    hi = np.asarray(hi).astype(np.int64)
+    pos = np.asarray(positions, dtype=np.int64)
+    kept = np.asarray(kept).astype(bool)
+    n = pos.shape[0]
+    band_lo, off = band_layout_host(pos, int(window))
+    band_lo = np.asarray(band_lo).astype(np.int64)
+    off = np.asarray(off).astype(np.int64)
+    has = lo != NO_CI
+    strong_hi = has & (hi >= p["strong_hi"])
+    recomb = hi < p["recomb_hi"]
+    # per-row suffix counts over the kept columns, as the device builds them: S at the cuts of rows 1..3, and R
+    suf = np.zeros((4, lo.shape[0]), dtype=np.int64)
+    for i in range(n):
+        a, b = off[i], off[i + 1]
+        if b == a or not kept[i]:
+            continue
+        kj = kept[band_lo[i]:i]
+        preds = [strong_hi[a:b] & (lo[a:b] >= p["cuts"][r]) & kj for r in (1, 2, 3)] + [recomb[a:b] & kj]
+        for q, pr in enumerate(preds):
+            suf[q, a:b] = np.cumsum(pr[::-1])[::-1]
+    out = []
+    for f in range(n):
+        if not kept[f]:
+            continue
+        tri = np.zeros(4, dtype=np.int64)
+        m = 1
+        for l in range(f + 1, n):
+            if band_lo[l] > f:
+                break
+            at = off[l] + f - band_lo[l]
+            tri += suf[:, at]
+            if not kept[l]:
+                continue
+            m += 1
+            if not (strong_hi[at] and lo[at] >= p["cand_cut"]):
+                continue
+            row = min(m, 5) - 2
+            if row == 0:
+                n_s, n_r = int(strong_hi[at] and lo[at] >= p["cuts"][0]), int(recomb[at])
+            else:
+                n_s, n_r = int(tri[row - 1]), int(tri[3])
+            span = int(pos[l] - pos[f])
+            cap = int(window) if p["max_spans"][row] < 0 else p["max_spans"][row]
+            if span <= int(window) and span <= cap and n_s + n_r >= p["min_informative"][row] and \
+                    p["strong_share"][1] * n_s > p["strong_share"][0] * (n_s + n_r):
+                out.append((f, l, span))
+    return np.asarray(out, dtype=np.int64).reshape(-1, 3)
+
+
+def gabriel_pick_host(cands, n: int, kept=None) -> Tuple[np.ndarray, int]:
+    """Host mirror of ldx_gabriel_pick_dev: (block_of uint32 [n], n_blocks) from the valid candidates (rows first, last, span):
+    by span descending, ties by smaller first, then smaller last, a candidate is accepted iff no SNP of [first, last] lies in
+    an accepted block; blocks are numbered in position order.  ``kept`` (bool [n], default all): NOT_KEPT for the others."""
+    cands = np.asarray(cands, dtype=np.int64).reshape(-1, 3)
+    kept = np.ones(n, dtype=bool) if kept is None else np.asarray(kept).astype(bool)
+    used = np.zeros(n, dtype=bool)
+    starts = []
+    for k in np.lexsort((cands[:, 1], cands[:, 0], -cands[:, 2])):
+        f, l = int(cands[k, 0]), int(cands[k, 1])
+        if not used[f:l + 1].any():
+            used[f:l + 1] = True
+            starts.append(f)
+    block_of = np.full(n, NOT_KEPT, dtype=np.uint32)
+    block_of[kept] = NO_BLOCK
+    flag = np.zeros(n, dtype=np.int64)
+    flag[starts] = 1
+    number = np.cumsum(flag) - 1
+    member = used & kept
+    block_of[member] = number[member].astype(np.uint32)
+    return block_of, len(starts)
+
+
+def ld_ci_from_counts(n_ind, a_i, a_j, S, H, device: Optional[torch.device] = None):
+    """The D' confidence bounds alone on a list of count tuples -- the device function of ld_dprime_ci's kernel
+    (ldx_ld_ci_from_counts_dev).  Returns (lo uint8, hi uint8) device tensors [m]; ``n_ind`` a scalar or one N per tuple."""
+    require_gpu()
+    dev = device or torch.device("cuda", torch.cuda.current_device())
+    m = int(np.size(a_i.cpu().numpy() if hasattr(a_i, "cpu") else a_i))
+    if not (hasattr(n_ind, "cpu") or np.ndim(n_ind) > 0):
+        n_ind = np.full(m, int(n_ind), dtype=np.int64)
+    cols = []
+    for name, v in (("n_ind", n_ind), ("a_i", a_i), ("a_j", a_j), ("S", S), ("H", H)):
+        v = np.ascontiguousarray(v.cpu().numpy() if hasattr(v, "cpu") else v).reshape(-1)
+        if v.size and (int(v.min()) < 0 or int(v.max()) >= (1 << 32)):
+            raise _lib.LdxError(f"ld_ci_from_counts: {name} must hold uint32 values")
+        if v.size != m:
+            raise _lib.LdxError("ld_ci_from_counts: n_ind, a_i, a_j, S and H differ in length")
+        cols.append(torch.from_numpy(v.astype(np.int64).astype(np.uint32).view(np.int32)).to(dev))
+    lo = torch.empty(m, dtype=torch.uint8, device=dev)
+    hi = torch.empty(m, dtype=torch.uint8, device=dev)
+    if m:
+        check(lib.ldx_ld_ci_from_counts_dev(m, *(c.data_ptr() for c in cols), lo.data_ptr(), hi.data_ptr(), _stream_ptr()),
+              "ldx_ld_ci_from_counts_dev")
+    return lo, hi
+
+
+@dataclass
+class LDCiBand:
+    """ld_dprime_ci's two bands: ``lo`` / ``hi`` uint8 [n_cells] on the device, the D' confidence bounds in percent of every
+    in-window pair i > j at ``offsets[i] + j - band_lo[i]`` (ld_band's layout); NO_CI in both for a pair without an interval
+    or with a SNP that is not kept.  ``kept``: uint8 [n] on the device -- keep & MAF & live."""
+
+    lo: torch.Tensor
+    hi: torch.Tensor
+    band_lo: torch.Tensor
+    offsets: torch.Tensor
+    kept: torch.Tensor
+    positions: object
+    window: int
+    n_cells: int
+    missing: Optional[str] = None
+
+    @property
+    def n_snps(self) -> int:
+        return int(self.band_lo.numel())
+
+    def layout(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(lo int64 [n], offsets int64 [n + 1]) on the host."""
+        return self.band_lo.cpu().numpy().astype(np.int64), self.offsets.cpu().numpy().astype(np.int64)
+
+    def strong(self, cut: int = 70, strong_hi: int = 98) -> torch.Tensor:
+        """bool [n_cells] on the device: lo != NO_CI, lo >= cut and hi >= strong_hi."""
+        return (self.lo != NO_CI) & (self.lo >= int(cut)) & (self.hi >= int(strong_hi))
+
+    def recombinant(self, recomb_hi: int = 90) -> torch.Tensor:
+        """bool [n_cells] on the device: hi < recomb_hi (a pair without an interval never is)."""
+        return self.hi < int(recomb_hi)
+
+    def to_dense(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(lo, hi) as symmetric uint8 [n, n] host arrays, NO_CI on the diagonal and outside the band."""
+        n = self.n_snps
+        band_lo, off = self.layout()
+        lo_h, hi_h = self.lo.cpu().numpy(), self.hi.cpu().numpy()
+        out = [np.full((n, n), NO_CI, dtype=np.uint8) for _ in range(2)]
+        rows = np.repeat(np.arange(n), np.diff(off))
+        cols = np.arange(off[-1]) - off[rows] + band_lo[rows]
+        for d, v in zip(out, (lo_h, hi_h)):
+            d[rows, cols] = v
+            d[cols, rows] = v
+        return out[0], out[1]
+
+
+def _keep_mask(keep, n: int) -> Optional[np.ndarray]:
+    if keep is None:
+        return None
+    k = keep.cpu().numpy() if isinstance(keep, torch.Tensor) else np.asarray(keep)
+    if k.shape != (n,) or (k.dtype != bool and not np.isin(k, (0, 1)).all()):
+        raise _lib.LdxError(f"keep must be a boolean array of shape [{n}]")
+    return k.astype(bool)
+
+
+def ld_dprime_ci(panel: PackedPanel, positions=None, window_bp: int = 500_000, window_snps: Optional[int] = None,
+                 missing: Optional[str] = None, keep=None, maf_min: float = 0.05, workspace: Optional[torch.Tensor] = None,
+                 check_positions: bool = True) -> LDCiBand:
+    """Gabriel's D' confidence bounds of every in-window pair, on the EM band (include/ldx.h, "Gabriel blocks";
+    ldx_ld_em_ci_band_dev): for i > j with pos_i - pos_j <= window, both SNPs kept, the 5 % tails of the likelihood of the
+    pair's genotype table over D' = 0 .. 100 % on the side of the EM estimate's sign, as two bytes in ld_band's layout.  A SNP
+    is kept iff ``keep`` (bool [n], default all) and its MAF over its own called individuals is >= ``maf_min`` and it has both
+    alleles among them; a cell with a SNP not kept holds NO_CI.  Positions, window, ``missing`` and ``workspace`` as for
+    ld_em_band.  This project's own definition after Gabriel et al. 2002, not validated against PLINK or Haploview."""
+    pairwise = _em_args("ld_dprime_ci", panel, missing)
+    if not 0.0 <= float(maf_min) <= 0.5:
+        raise _lib.LdxError("maf_min must lie in [0, 0.5]")
+    n = panel.n_snps
+    kmask = _keep_mask(keep, n)
+    require_gpu()
+    dev = panel.device
+    pos, pos_h, window = _band_positions(panel, positions, window_bp, window_snps, check_positions, "ld_dprime_ci")
+    window = min(window, BAND_WINDOW_MAX)
+    workspace = _plan_workspace(lib.ldx_ld_em_band_workspace_bytes, panel, workspace)
+    n_called, a_sum, _, live = em_snp_stats(panel, pairwise)
+    t = 2 * n_called.to(torch.int64)
+    a = a_sum.to(torch.int64)
+    kept = live.bool() & (torch.minimum(a, t - a).to(torch.float64) >= float(maf_min) * t.to(torch.float64))
+    if kmask is not None:
+        kept = kept & torch.as_tensor(kmask).to(dev)
+    kept = kept.to(torch.uint8).contiguous()
+    lo, offsets, n_cells = _band_layout(pos, n, window, dev)
+    ci_lo = torch.empty(n_cells, dtype=torch.uint8, device=dev)
+    ci_hi = torch.empty(n_cells, dtype=torch.uint8, device=dev)
+    check(lib.ldx_ld_em_ci_band_dev(*_em_panel(panel, pairwise), n, panel.n_hap, int(pairwise), pos.data_ptr(), window,
+                                    kept.data_ptr(), lo.data_ptr(), offsets.data_ptr(), _ptr(ci_lo) if n_cells else None,
+                                    _ptr(ci_hi) if n_cells else None, n_cells, workspace.data_ptr(),
+                                    workspace.numel() * workspace.element_size(), _stream_ptr()), "ldx_ld_em_ci_band_dev")
+    res = LDCiBand(ci_lo, ci_hi, lo, offsets, kept, pos if pos_h is None else pos_h, window, n_cells, missing)
+    res._keep = (pos, workspace)   # alive until the launch is done
+    return res
+
+
+@dataclass
+class GabrielBlocks:
+    """Haplotype blocks by Gabriel's rule (ld_gabriel_blocks).  ``block_of_dev`` / ``n_out`` are the device tensors the pick
+    wrote (int32 views of the uint32 words); the host arrays are fetched when first asked for.  ``ci``: the bounds' band."""
+
+    block_of_dev: torch.Tensor
+    n_out: torch.Tensor
+    ci: LDCiBand
+    params: dict
+    _host: Optional[tuple] = None
+
+    def _fetch(self) -> tuple:
+        if self._host is None:
+            block_of = self.block_of_dev.cpu().numpy().view(np.uint32)
+            n_out = self.n_out.cpu().numpy().view(np.uint32)
+            pos = self.ci.positions
+            pos = np.asarray(pos.cpu().numpy() if isinstance(pos, torch.Tensor) else pos, dtype=np.int64)
+            nb = int(n_out[0])
+            members = np.flatnonzero(block_of < NO_BLOCK)
+            b = block_of[members].astype(np.int64)
+            starts = np.full(nb, -1, dtype=np.int64)
+            ends = np.full(nb, -1, dtype=np.int64)
+            starts[b[::-1]] = members[::-1]   # the first member wins
+            ends[b] = members                 # the last member wins
+            self._host = (block_of, nb, int(n_out[1]), starts, ends, np.bincount(b, minlength=nb).astype(np.int64), pos)
+        return self._host
+
+    @property
+    def block_of(self) -> np.ndarray:
+        """uint32 [n]: the 0-based block (in position order) of every member, NO_BLOCK for a kept SNP in no block, NOT_KEPT
+        for a SNP that is not kept."""
+        return self._fetch()[0]
+
+    @property
+    def n_blocks(self) -> int:
+        return self._fetch()[1]
+
+    @property
+    def n_candidates(self) -> int:
+        """The valid candidates the pick went through."""
+        return self._fetch()[2]
+
+    @property
+    def starts(self) -> np.ndarray:
+        """int64 [n_blocks]: the first SNP of every block."""
+        return self._fetch()[3]
+
+    @property
+    def ends(self) -> np.ndarray:
+        """int64 [n_blocks]: the last SNP of every block (inclusive)."""
+        return self._fetch()[4]
+
+    @property
+    def sizes(self) -> np.ndarray:
+        """int64 [n_blocks]: members (kept SNPs) per block."""
+        return self._fetch()[5]
+
+    @property
+    def spans_bp(self) -> np.ndarray:
+        pos = self._fetch()[6]
+        return pos[self.ends] - pos[self.starts]
+
+
+def ld_gabriel_blocks(panel: PackedPanel, positions=None, window_bp: int = 500_000, window_snps: Optional[int] = None,
+                      missing: Optional[str] = None, keep=None, maf_min: float = 0.05, workspace: Optional[torch.Tensor] = None,
+                      check_positions: bool = True, dosage: bool = False, path: Optional[str] = None, **params) -> GabrielBlocks:
+    """Haplotype blocks by Gabriel et al.'s D' confidence-interval rule -- what PLINK --blocks and Haploview pick by default --
+    from unphased genotypes (include/ldx.h, "Gabriel blocks"): ld_dprime_ci's bounds, then the candidates (first, last) whose
+    end pair is strong and whose inside pairs are more than 95 % strong among the informative ones, then the greedy pick by
+    span.  ``params``: cand_cut, strong_hi, recomb_hi, cuts, max_spans, min_informative, strong_share (GABRIEL_DEFAULTS).
+    Everything is stream-ordered; beyond the layout's total the host reads nothing until a result property is asked for.
+    ``dosage=True`` and a haplotype ``path`` are refused, as the EM operators refuse them."""
+    _em_args("ld_gabriel_blocks", panel, missing, path, dosage)
+    p = gabriel_params(**params)
+    ci = ld_dprime_ci(panel, positions, window_bp, window_snps, missing, keep, maf_min, workspace, check_positions)
+    n, dev, n_cells = panel.n_snps, panel.device, ci.n_cells
+    pos = ci._keep[0]
+    span = torch.empty(n_cells, dtype=torch.int64, device=dev)
+    first = torch.empty(n_cells, dtype=torch.int32, device=dev)
+    last = torch.empty(n_cells, dtype=torch.int32, device=dev)
+    ws = torch.empty(lib.ldx_gabriel_candidates_workspace_bytes(n, n_cells) + lib.ldx_gabriel_pick_workspace_bytes(n),
+                     dtype=torch.uint8, device=dev)
+    pick_ws = ws[lib.ldx_gabriel_candidates_workspace_bytes(n, n_cells):]
+    prm = _gabriel_struct(p)
+    nz = bool(n_cells)
+    check(lib.ldx_gabriel_candidates_dev(_ptr(ci.lo) if nz else None, _ptr(ci.hi) if nz else None, ci.band_lo.data_ptr(),
+                                         ci.offsets.data_ptr(), n_cells, pos.data_ptr(), ci.kept.data_ptr(), n, ci.window,
+                                         ctypes.addressof(prm), _ptr(span) if nz else None, _ptr(first) if nz else None,
+                                         _ptr(last) if nz else None, ws.data_ptr(), ws.numel(), _stream_ptr()),
+          "ldx_gabriel_candidates_dev")
+    sorted_span, order = torch.sort(span, descending=True, stable=True)
+    block_of = torch.empty(n, dtype=torch.int32, device=dev)
+    n_out = torch.empty(2, dtype=torch.int32, device=dev)
+    check(lib.ldx_gabriel_pick_dev(_ptr(sorted_span) if nz else None, _ptr(order) if nz else None, _ptr(first) if nz else None,
+                                   _ptr(last) if nz else None, n_cells, ci.kept.data_ptr(), n, block_of.data_ptr(),
+                                   n_out.data_ptr(), pick_ws.data_ptr(), pick_ws.numel(), _stream_ptr()), "ldx_gabriel_pick_dev")
+    res = GabrielBlocks(block_of, n_out, ci, p)
+    res._keep = (ws, sorted_span, order, first, last, span)   # alive until the launches are done
+    return res
 
 
 # --------------------------------------------------------------------------- instrumentation
