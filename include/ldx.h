@@ -1073,6 +1073,56 @@ int ldx_gabriel_pick_dev(const int64_t *sorted_span, const int64_t *order, const
                          uint64_t n_cells, const uint8_t *keep, uint32_t n_snps, uint32_t *block_of, uint32_t *n_out,
                          void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- sample relatedness: IBS counts and KING-robust kinship between the INDIVIDUALS of a panel -------------------------------
+ * This project's own definitions, written after Manichaikul et al. 2010 (the between-family estimator); NOT validated against
+ * PLINK 2 (--make-king-table, --king-cutoff, --distance ibs) or KING.
+ *
+ * Individual a owns haplotypes 2a and 2a + 1 (n_hap even).  At a SNP it is CALLED when both codes are 0 or 1 -- a half-missing
+ * or second-ALT genotype is missing -- and then has the ALT dosage g in {0, 1, 2}.  A SNP is KEPT when it passes the optional
+ * mask keep (uint8 [n_snps] of the panel, NULL = all); a SNP that is not kept counts as missing for everybody.
+ * Counts of individuals a, b over the kept SNPs called in both, uint32:
+ *     N[a][b]     SNPs jointly called                 HH[a][b]    #{g_a = 1 and g_b = 1}
+ *     IBS0[a][b]  #{(g_a, g_b) = (0, 2) or (2, 0)}    HET[a][b]   #{g_a = 1 and b called}   (not symmetric: HET[b][a] is the partner's)
+ * Derived, exact:  IBS1 = HET[a][b] + HET[b][a] - 2 HH,  IBS2 = N - IBS1 - IBS0,  sum (g_a - g_b)^2 = 4 IBS0 + IBS1.
+ * Cells, each operation in fp64 rounded once, then one conversion (numpy reproduces them bit for bit), m = min(HET[a][b], HET[b][a]):
+ *     kin = (float)(0.5 - (double)(4 IBS0 + IBS1) / (double)(4 m));    -0.0f where m == 0
+ *     ibs = (float)((double)(2 IBS2 + IBS1) / (double)(2 N));          -0.0f where N == 0
+ * On the diagonal kin[a][a] is 0.5f when a has a heterozygous kept call, else -0.0f.  Both are functions of the integers alone:
+ * symmetric, and identical under permuted SNPs, rephased genotypes and a split of the SNPs over several calls.
+ *
+ * The transposed store (ldx_sample_planes_dev): three bit planes, in this order -- called, heterozygous, homozygous ALT -- each
+ * a tiled plane as above with the axes exchanged: rows = individuals in slabs of 128, bits = the SNPs snp_begin .. snp_begin +
+ * snp_count - 1 of the panel in chunks of 128 (16 bytes), n_chunks = 2 * ceil(snp_count / 256); element (slab s, chunk c, row r)
+ * of a plane is the 16-byte group at ((s * n_chunks + c) * 128 + r) * 16, bit k % 128 of it SNP snp_begin + 128 c + k % 128 of
+ * individual 128 s + r: a row's consecutive SNPs are 16-byte loads that consecutive rows coalesce.  A bit of a SNP that is not
+ * kept, of a pad SNP or of a pad row is 0.  ldx_sample_planes_bytes(n_ind, snp_count) is the size of the three planes; the call
+ * writes every byte of it and the tables: no memset by the caller.  tables (ldx_sample_tables_bytes, uint32): the called, the
+ * heterozygous and the homozygous-ALT kept calls per individual -- [3][128 * ceil(n_ind / 128)] -- then the number of kept SNPs.
+ * At most LDX_KING_MAX_STORE_SNPS SNPs per store; a longer panel is counted in several calls (accumulate).
+ *
+ * ldx_sample_counts_dev: counts[(k * n_ind + a) * ld + b], k in the order N, HH, IBS0, HET, the full square, from a store and its
+ * tables.  accumulate = 0: the call first defines every word [a][b < n_ind]; accumulate = 1: it adds to what is there (chromosomes,
+ * .bed chunks), n_prior being the SNPs already counted into `counts`: n_prior + n_snps may not pass 2^32 - 1 (LDX_E_ARG).
+ * Work: (lower tile of 128 x 128 individuals) x (K slice); a slice's sums are exact fp32 integers -- every FP4 product is 1, so
+ * slice SNPs <= LDX_KING_MAX_SLICE_SNPS < 2^24 -- converted to uint32 once and added with 32-bit integer atomics: bit-reproducible.
+ * n_slices = 0 lets the library choose (about four rounds of workgroups, no slice under LDX_KING_MIN_SLICE_SNPS); a value of the
+ * caller's is used as given (capped at the K-blocks of 256 SNPs) and refused with LDX_E_ARG when a slice would pass the bound.
+ * A tile none of whose individuals misses a kept call takes N and HET from the tables; both paths end in the same integers.
+ * ldx_king_from_counts_dev: the two cells on m tuples; ldx_sample_cells_dev: dense float32 [n_ind][ld_out] from the four count
+ * planes.  Either of kin, ibs may be NULL, not both.  n_ind <= LDX_MAX_HAPS / 2.  Argument rules are checked before any HIP call. */
+#define LDX_KING_MIN_SLICE_SNPS 65536u      /* the automatic choice makes no shorter slice: its atomics stay small beside its MFMAs */
+#define LDX_KING_MAX_SLICE_SNPS 8388608u    /* 2^23: (largest product, 1) x (slice SNPs) < 2^24 */
+#define LDX_KING_MAX_STORE_SNPS 134217728u  /* 2^27 SNPs in one store */
+size_t ldx_sample_planes_bytes(uint32_t n_ind, uint32_t n_snps);
+size_t ldx_sample_tables_bytes(uint32_t n_ind);
+int ldx_sample_planes_dev(const void *alt, const void *ref, uint32_t n_snps, uint32_t n_hap, const uint8_t *keep,
+                          uint32_t snp_begin, uint32_t snp_count, void *store, uint32_t *tables, void *stream);
+int ldx_sample_counts_dev(const void *store, const uint32_t *tables, uint32_t n_ind, uint32_t n_snps, uint32_t *counts,
+                          size_t ld, int accumulate, uint64_t n_prior, uint32_t n_slices, void *stream);
+int ldx_king_from_counts_dev(size_t m, const uint32_t *N, const uint32_t *HH, const uint32_t *IBS0, const uint32_t *HETa,
+                             const uint32_t *HETb, float *kin, float *ibs, void *stream);
+int ldx_sample_cells_dev(const uint32_t *counts, uint32_t n_ind, size_t ld, float *kin, float *ibs, size_t ld_out, void *stream);
+
 /* ---- synthetic panels: deterministic, identical on host and device ------ */
 /* codes int8 [n_snps][ld_codes] receive global SNPs [snp_offset, snp_offset + n_snps) (a rank's
  * shard).  thresholds: per-SNP ALT probability * 2^64 (computed on the host, see

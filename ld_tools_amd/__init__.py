@@ -23,6 +23,8 @@ from .ops import LDEm, em_host, ld_em, ld_em_counts, ld_em_from_counts, ld_em_hi
 from .ops import LDEmBand, em_snp_stats, ld_em_band  # noqa: F401
 from .ops import (GabrielBlocks, LDCiBand, dprime_ci_host, gabriel_candidates_host, gabriel_kept_host,  # noqa: F401
                   gabriel_pick_host, ld_ci_from_counts, ld_dprime_ci, ld_gabriel_blocks)
+from .ops import (RelatedPairs, SampleCounts, ibs_cell_host, ibs_matrix, king_cell_host, king_cutoff,  # noqa: F401
+                  king_from_counts, king_kinship, sample_counts, sample_counts_host)
 from .panel import PackedPanel, encode_codes, select_index  # noqa: F401
 from . import plink  # noqa: F401
 from .plink import BedFile, bed_codes_host, codes_bed_host, write_bfile  # noqa: F401
@@ -34,5 +36,6 @@ __all__ = ["PackedPanel", "encode_codes", "select_index", "ld_triangle", "ld_are
            "ld_cross_score", "band_layout_host", "cross_terms", "ld_rect", "ld_rect_hits", "LDRectHits", "rect_hits_host", "ld_rect_counts", "pairwise_counts_host", "pairwise_cell_host", "pw_snp_stats", "ld_em", "LDEm",
            "ld_em_hits", "ld_em_counts", "ld_em_from_counts", "em_host", "ld_em_band", "LDEmBand", "em_snp_stats", "ld_dprime_ci",
            "LDCiBand", "ld_gabriel_blocks", "GabrielBlocks", "ld_ci_from_counts", "dprime_ci_host", "gabriel_candidates_host",
-           "gabriel_pick_host", "gabriel_kept_host", "LdxError",
+           "gabriel_pick_host", "gabriel_kept_host", "sample_counts", "SampleCounts", "RelatedPairs", "king_kinship", "ibs_matrix",
+           "sample_counts_host", "king_cell_host", "ibs_cell_host", "king_from_counts", "king_cutoff", "LdxError",
            "version", "plink", "BedFile", "bed_codes_host", "codes_bed_host", "write_bfile"]

@@ -9,12 +9,13 @@ dataclasses of the VCF drivers from it, so that their writers write them unchang
     bfile_band       -> BandMatrix for write_band
     bfile_em_band    -> EmBand for write_em_band
     bfile_blocks     -> GabrielTable for write_gabriel_blocks              PLINK --blocks (Gabriel et al.'s D' interval rule)
+    bfile_king       -> KingTable for write_kin0 / write_king_cutoff       PLINK 2 --make-king-table / --king-cutoff
 
 A ``.bed`` holds unphased genotype calls: a het is written (ALT, REF) whatever the truth, so the haplotype r of the phased
 operators means nothing here.  Every driver defaults to an unphased form (EM or genotype dosage) and refuses
 ``dosage=False, em=False``.  ``make_bed`` writes a panel, or a subset of a loaded fileset, back as a fileset.
 
-    python -m ld_tools_amd.drivers.plink {ld,clump,prune,l2,blocks,make-bed} --bfile P --out O ...
+    python -m ld_tools_amd.drivers.plink {ld,clump,prune,l2,blocks,king,make-bed} --bfile P --out O ...
 """
 from __future__ import annotations
 
@@ -311,6 +312,40 @@ def bfile_blocks(src, window_bp: int = 500_000, missing: Optional[str] = "pairwi
     return GabrielTable(chrom, list(bf.ids), _poss(bf), res)
 
 
+def bfile_king(src, out: Optional[str] = None, keep=None, extract=None, prune_r2: Optional[float] = None,
+               prune_window_bp: int = 250_000, prune_missing: Optional[str] = None, kin_min: Optional[float] = None,
+               cutoff: Optional[float] = None, matrix: bool = False, **load):
+    """drivers/king.py's ``king_table`` from a fileset: the pair counts between its individuals, IDs from the ``.fam``.
+    ``keep`` / ``extract``: load_bfile's selections of individuals and variants.  ``prune_r2``: count over the variants
+    ``ld_prune`` keeps at this r^2 (genotype-dosage r, ``prune_window_bp``; ``prune_missing="pairwise"`` for a fileset with
+    missing calls) -- the mask goes to the count as ``keep``, no panel is rebuilt; the fileset must then hold one chromosome.
+    ``out``: a prefix to write ``.kin0`` under (pairs with kinship >= ``kin_min``, all by default), ``.king`` / ``.king.id``
+    with ``matrix`` and ``.king.cutoff.in.id`` / ``.out.id`` with ``cutoff``.  Returns the KingTable."""
+    from .king import KingTable, write_kin0, write_king_cutoff, write_king_matrix
+    from ..ops import sample_counts
+
+    if isinstance(src, Bfile):
+        if keep is not None or extract is not None or load:
+            raise LdxError("bfile_king: a loaded fileset takes no keep / extract / load arguments")
+        bf = src
+    else:
+        bf = load_bfile(src, keep=keep, extract=extract, **load)
+    mask = None
+    if prune_r2 is not None:
+        _one_chrom("bfile_king", bf)
+        more = {} if prune_missing is None else {"missing": prune_missing}
+        mask = ld_prune(bf.panel, bf.pos, r2=prune_r2, window_bp=prune_window_bp, dosage=True, **more).keep
+    table = KingTable(list(bf.fid), list(bf.iid), sample_counts(bf.panel, keep=mask), kin_min, mask)
+    if out is not None:
+        write_kin0(out + ".kin0", table)
+        kin = table.counts.kinship() if (matrix or cutoff is not None) else None
+        if matrix:
+            write_king_matrix(out, table, kin.cpu().numpy())
+        if cutoff is not None:
+            write_king_cutoff(out, table, cutoff, kin)
+    return table
+
+
 def make_bed(prefix_out, src, snps=None, individuals=None, bim: Optional[dict] = None, fam: Optional[dict] = None,
              alt: Optional[str] = None) -> List[str]:
     """Write a fileset.  ``src``: a ``Bfile`` -- ``snps`` / ``individuals`` (index arrays or masks over ITS variants and
@@ -410,6 +445,13 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--blocks-max-kb", type=float, default=500.0, help="the window: the largest distance of a block's ends")
     p.add_argument("--blocks-min-maf", type=float, default=0.05)
     p.add_argument("--missing", choices=("pairwise", "ref"), default="pairwise")
+    p = common("king", "KING-robust kinship between the individuals (.kin0; --king-cutoff: .king.cutoff.in.id / .out.id)")
+    p.add_argument("--king-table-filter", type=float, default=None, help="write only the pairs with kinship >= this")
+    p.add_argument("--king-cutoff", type=float, default=None, help="keep a maximal set with no pair above this kinship")
+    p.add_argument("--make-king", action="store_true", help="also write the lower triangle (.king, .king.id)")
+    p.add_argument("--prune-r2", type=float, default=None, help="count over the variants LD pruning keeps at this r^2")
+    p.add_argument("--prune-window-kb", type=float, default=250.0)
+    p.add_argument("--missing", choices=("pairwise",), default=None, help="how the pruning treats missing calls")
     common("make-bed", "write the selected variants and individuals as a new fileset")
     return ap
 
@@ -443,6 +485,10 @@ def main(argv=None) -> int:
         table = bfile_blocks(bf, window_bp=int(a.blocks_max_kb * 1000), missing=None if a.missing == "ref" else a.missing,
                              maf_min=a.blocks_min_maf)
         print(table.result.n_blocks, "blocks ->", *write_gabriel_blocks(a.out, table.result, table.rs_ids, table.chrom))
+    elif a.command == "king":
+        table = bfile_king(bf, out=a.out, prune_r2=a.prune_r2, prune_window_bp=int(a.prune_window_kb * 1000),
+                           prune_missing=a.missing, kin_min=a.king_table_filter, cutoff=a.king_cutoff, matrix=a.make_king)
+        print(table.counts.n_ind, "individuals,", table.counts.n_snps, "variants ->", a.out + ".kin0")
     else:
         print(*make_bed(a.out, bf))
     return 0

@@ -3396,6 +3396,251 @@ def ld_gabriel_blocks(panel: PackedPanel, positions=None, window_bp: int = 500_0
     return res
 
 
+# --------------------------------------------------------------------------- sample relatedness (individual x individual)
+SAMPLE_COUNTS = ("N", "HH", "IBS0", "HET")     # the planes of ldx_sample_counts_dev, in its order
+SAMPLE_STORE_SNPS = 1 << 18                    # SNPs per transposed store of sample_counts: 96 KiB per individual
+
+
+def _u32_to_i64(t: torch.Tensor) -> torch.Tensor:
+    return t.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+
+
+def float32_bound(t: float, strict: bool = False) -> np.float32:
+    """The float32 b with ``x >= b`` equal to ``x >= t`` (``x > t`` when strict) for every float32 x: the smallest float32 not
+    below (strict: above) t."""
+    t = float(t)
+    if np.isnan(t):
+        raise _lib.LdxError("the bound must not be NaN")
+    with np.errstate(over="ignore"):
+        b = np.float32(t)
+    if float(b) < t or (strict and float(b) == t):
+        b = np.nextafter(b, np.float32(np.inf), dtype=np.float32)
+    return np.float32(b)
+
+
+@dataclass
+class RelatedPairs:
+    """The pairs a > b of SampleCounts.related, as numpy arrays of one length: the two individuals, the kinship cell and the
+    pair's counts."""
+
+    a: np.ndarray
+    b: np.ndarray
+    kin: np.ndarray
+    n: np.ndarray
+    hethet: np.ndarray
+    ibs0: np.ndarray
+
+    def __len__(self) -> int:
+        return int(self.a.size)
+
+
+@dataclass
+class SampleCounts:
+    """The integer co-occurrence counts between the individuals of a panel over its kept SNPs (include/ldx.h, "sample
+    relatedness"): ``counts`` int32 [4, n_ind, n_ind] on the device (uint32 bit patterns, planes N, HH, IBS0, HET), and
+    ``n_snps``, the SNPs walked so far (kept or not) by the calls that accumulated into it."""
+
+    counts: torch.Tensor
+    n_snps: int
+
+    @property
+    def n_ind(self) -> int:
+        return int(self.counts.shape[1])
+
+    @property
+    def n(self) -> torch.Tensor:
+        """uint32 [n_ind, n_ind]: SNPs called in both."""
+        return self.counts[0].view(torch.uint32)
+
+    @property
+    def hethet(self) -> torch.Tensor:
+        """uint32 [n_ind, n_ind]: SNPs heterozygous in both."""
+        return self.counts[1].view(torch.uint32)
+
+    @property
+    def ibs0(self) -> torch.Tensor:
+        """uint32 [n_ind, n_ind]: opposite homozygotes."""
+        return self.counts[2].view(torch.uint32)
+
+    @property
+    def het(self) -> torch.Tensor:
+        """uint32 [n_ind, n_ind]: het[a, b] = SNPs where a is heterozygous and b called (het[b, a] is the partner's)."""
+        return self.counts[3].view(torch.uint32)
+
+    @property
+    def ibs1(self) -> torch.Tensor:
+        """int64 [n_ind, n_ind]: HET[a][b] + HET[b][a] - 2 HH."""
+        het = _u32_to_i64(self.counts[3])
+        return het + het.T - 2 * _u32_to_i64(self.counts[1])
+
+    @property
+    def ibs2(self) -> torch.Tensor:
+        """int64 [n_ind, n_ind]: N - IBS1 - IBS0."""
+        return _u32_to_i64(self.counts[0]) - self.ibs1 - _u32_to_i64(self.counts[2])
+
+    def _cells(self, want_kin: bool, want_ibs: bool):
+        n = self.n_ind
+        dev = self.counts.device
+        kin = torch.empty((n, n), dtype=torch.float32, device=dev) if want_kin else None
+        ibs = torch.empty((n, n), dtype=torch.float32, device=dev) if want_ibs else None
+        check(lib.ldx_sample_cells_dev(self.counts.data_ptr(), n, n, _ptr(kin), _ptr(ibs), n, _stream_ptr()), "ldx_sample_cells_dev")
+        return kin, ibs
+
+    def kinship(self) -> torch.Tensor:
+        """float32 [n_ind, n_ind] on the device: the KING-robust kinship cell of every pair (-0.0f where the smaller HET is 0)."""
+        return self._cells(True, False)[0]
+
+    def ibs(self) -> torch.Tensor:
+        """float32 [n_ind, n_ind] on the device: the IBS similarity (2 IBS2 + IBS1) / (2 N) (-0.0f where N is 0)."""
+        return self._cells(False, True)[1]
+
+    def related(self, kin_min: float, strict: bool = False) -> RelatedPairs:
+        """The pairs a > b whose kinship cell is >= kin_min (strict: > kin_min), a float32 comparison, in row-major order."""
+        kin = self.kinship()
+        bound = torch.tensor(float(float32_bound(kin_min, strict)), dtype=torch.float32, device=kin.device)
+        lower = torch.ones_like(kin, dtype=torch.bool).tril(-1)
+        idx = torch.nonzero((kin >= bound) & lower)
+        a, b = idx[:, 0], idx[:, 1]
+        take = lambda k: _u32_to_i64(self.counts[k][a, b]).cpu().numpy()  # noqa: E731
+        return RelatedPairs(a.cpu().numpy(), b.cpu().numpy(), kin[a, b].cpu().numpy(), take(0), take(1), take(2))
+
+
+def sample_counts(panel: PackedPanel, keep=None, out: Optional[SampleCounts] = None, n_slices: Optional[int] = None,
+                  store_snps: int = SAMPLE_STORE_SNPS) -> SampleCounts:
+    """The counts N, HH, IBS0, HET between the individuals of ``panel`` (haplotypes 2a, 2a + 1 are individual a) over the SNPs
+    that pass ``keep`` (a boolean mask [n_snps]; None = all): the panel is transposed on the device into individual-major bit
+    planes, ``store_snps`` SNPs at a time (ldx_sample_planes_dev), and counted on the FP4 matrix cores (ldx_sample_counts_dev).
+    ``out``: an earlier result of the same individuals to add to -- chromosomes, or chunks of a fileset, sum into one result.
+    ``n_slices``: the K slices per tile (None: the library's choice).  Every cell is an exact integer; the result does not
+    depend on the order or the split of the SNPs."""
+    require_gpu()
+    if panel.n_hap % 2:
+        raise _lib.LdxError(f"sample_counts: n_hap must be even (haplotypes 2a and 2a + 1 are individual a), got {panel.n_hap}")
+    n_ind, n_snps, dev = panel.n_ind, panel.n_snps, panel.device
+    store_snps = int(store_snps)
+    if not (1 <= store_snps <= _lib.KING_MAX_STORE_SNPS):
+        raise _lib.LdxError(f"sample_counts: store_snps must lie in 1..{_lib.KING_MAX_STORE_SNPS}")
+    k = _keep_mask(keep, n_snps)
+    keep_d = None if k is None else torch.from_numpy(k.astype(np.uint8)).to(dev)
+    if out is None:
+        res = SampleCounts(torch.empty((len(SAMPLE_COUNTS), n_ind, n_ind), dtype=torch.int32, device=dev), 0)
+        accumulate = 0
+    else:
+        if out.n_ind != n_ind or out.counts.device != dev:
+            raise _lib.LdxError(f"sample_counts: out holds {out.n_ind} individuals on {out.counts.device}, the panel {n_ind} on {dev}")
+        res, accumulate = out, 1
+    width = min(store_snps, n_snps)
+    store = torch.empty(lib.ldx_sample_planes_bytes(n_ind, width), dtype=torch.uint8, device=dev)
+    tables = torch.empty(lib.ldx_sample_tables_bytes(n_ind) // 4, dtype=torch.int32, device=dev)
+    for begin in range(0, n_snps, store_snps):
+        count = min(store_snps, n_snps - begin)
+        check(lib.ldx_sample_planes_dev(panel.alt.data_ptr(), panel.ref.data_ptr(), n_snps, panel.n_hap, _ptr(keep_d), begin, count,
+                                        store.data_ptr(), tables.data_ptr(), _stream_ptr()), "ldx_sample_planes_dev")
+        check(lib.ldx_sample_counts_dev(store.data_ptr(), tables.data_ptr(), n_ind, count, res.counts.data_ptr(), n_ind, accumulate,
+                                        res.n_snps if accumulate else 0, int(n_slices or 0), _stream_ptr()), "ldx_sample_counts_dev")
+        res.n_snps += count
+        accumulate = 1
+    res._keep = (store, tables, keep_d)   # alive until the launches are done
+    return res
+
+
+def king_kinship(panel: PackedPanel, keep=None) -> torch.Tensor:
+    """float32 [n_ind, n_ind] on the device: ``sample_counts(panel, keep).kinship()``."""
+    return sample_counts(panel, keep).kinship()
+
+
+def ibs_matrix(panel: PackedPanel, keep=None) -> torch.Tensor:
+    """float32 [n_ind, n_ind] on the device: ``sample_counts(panel, keep).ibs()``."""
+    return sample_counts(panel, keep).ibs()
+
+
+def sample_counts_host(codes, keep=None) -> np.ndarray:
+    """Host mirror of sample_counts in pure numpy: int64 [4, n_ind, n_ind] (N, HH, IBS0, HET) from the allele codes [n_snps,
+    n_hap] (1 = ALT, 0 = REF, anything else = missing).  float64 GEMMs of 0/1 matrices: exact below 2^53."""
+    c = np.asarray(codes)
+    if c.ndim != 2 or c.shape[1] % 2 or c.shape[1] == 0:
+        raise _lib.LdxError(f"sample_counts_host: codes [n_snps, n_hap] with an even n_hap needed, got shape {c.shape}")
+    k = _keep_mask(keep, c.shape[0])
+    if k is not None:
+        c = c[k]
+    h0, h1 = c[:, 0::2], c[:, 1::2]
+    called = ((h0 == 0) | (h0 == 1)) & ((h1 == 0) | (h1 == 1))
+    g = ((h0 == 1).astype(np.int8) + (h1 == 1).astype(np.int8)) * called
+    q = called.T.astype(np.float64)
+    t = ((g == 1) & called).T.astype(np.float64)
+    z = ((g == 2) & called).T.astype(np.float64)
+    r = ((g == 0) & called).T.astype(np.float64)
+    sets = [q @ q.T, t @ t.T, r @ z.T + z @ r.T, t @ q.T]
+    return np.stack(sets).astype(np.int64)
+
+
+def _cell_ints(N, HH, IBS0, HETa, HETb):
+    N, HH, IBS0, HETa, HETb = (np.asarray(x).astype(np.int64) for x in (N, HH, IBS0, HETa, HETb))
+    ibs1 = HETa + HETb - 2 * HH
+    return N, IBS0, ibs1, np.minimum(HETa, HETb)
+
+
+def king_cell_host(N, HH, IBS0, HETa, HETb) -> np.ndarray:
+    """Host mirror of the kinship cell (include/ldx.h, "sample relatedness"): float32, -0.0f where min(HETa, HETb) is 0."""
+    N, IBS0, ibs1, m = _cell_ints(N, HH, IBS0, HETa, HETb)
+    num, den = (4 * IBS0 + ibs1).astype(np.float64), (4 * m).astype(np.float64)
+    val = (0.5 - num / np.where(m > 0, den, 1.0)).astype(np.float32)
+    return np.where(m > 0, val, np.float32(-0.0)).astype(np.float32)
+
+
+def ibs_cell_host(N, HH, IBS0, HETa, HETb) -> np.ndarray:
+    """Host mirror of the IBS cell: float32 (2 IBS2 + IBS1) / (2 N), -0.0f where N is 0."""
+    N, IBS0, ibs1, _ = _cell_ints(N, HH, IBS0, HETa, HETb)
+    ibs2 = N - ibs1 - IBS0
+    val = ((2 * ibs2 + ibs1).astype(np.float64) / np.where(N > 0, (2 * N).astype(np.float64), 1.0)).astype(np.float32)
+    return np.where(N > 0, val, np.float32(-0.0)).astype(np.float32)
+
+
+def king_from_counts(N, HH, IBS0, HETa, HETb, device: Optional[torch.device] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The two cells alone on a list of count tuples -- the device functions of the dense cells (ldx_king_from_counts_dev).
+    Returns (kin, ibs), float32 device tensors [m]."""
+    require_gpu()
+    dev = device or torch.device("cuda", torch.cuda.current_device())
+    cols = []
+    for name, v in (("N", N), ("HH", HH), ("IBS0", IBS0), ("HETa", HETa), ("HETb", HETb)):
+        v = np.ascontiguousarray(v.cpu().numpy() if hasattr(v, "cpu") else v).reshape(-1)
+        if v.size and (int(v.min()) < 0 or int(v.max()) >= (1 << 32)):
+            raise _lib.LdxError(f"king_from_counts: {name} must hold uint32 values")
+        cols.append(torch.from_numpy(v.astype(np.int64).astype(np.uint32).view(np.int32)).to(dev))
+    m = int(cols[0].numel())
+    if any(int(c.numel()) != m for c in cols):
+        raise _lib.LdxError("king_from_counts: N, HH, IBS0, HETa and HETb differ in length")
+    kin = torch.empty(m, dtype=torch.float32, device=dev)
+    ibs = torch.empty(m, dtype=torch.float32, device=dev)
+    check(lib.ldx_king_from_counts_dev(m, *(c.data_ptr() for c in cols), kin.data_ptr(), ibs.data_ptr(), _stream_ptr()),
+          "ldx_king_from_counts_dev")
+    return kin, ibs
+
+
+def king_cutoff(kin, cutoff: float) -> Tuple[np.ndarray, np.ndarray]:
+    """A maximal set of individuals no two of which are related above ``cutoff``: edges are the pairs with kin > cutoff (a
+    float32 comparison); the individuals are ranked by (number of edges ascending, index ascending) and the kept set is the
+    lexicographically first maximal independent set in that rank (select_host on the CSR of the edges).  Returns (keep bool
+    [n_ind], removed_because_of int64 [n_ind]: the kept individual that removed this one, -1 for a kept one)."""
+    k = kin.cpu().numpy() if isinstance(kin, torch.Tensor) else np.asarray(kin)
+    if k.ndim != 2 or k.shape[0] != k.shape[1]:
+        raise _lib.LdxError(f"king_cutoff: a square kinship matrix is needed, got shape {k.shape}")
+    n = k.shape[0]
+    edge = k.astype(np.float32) >= float32_bound(cutoff, strict=True)
+    edge = edge | edge.T
+    np.fill_diagonal(edge, False)
+    degree = edge.sum(axis=1)
+    order = np.lexsort((np.arange(n), degree))
+    rank = np.empty(n, dtype=np.uint32)
+    rank[order] = np.arange(n, dtype=np.uint32)
+    rows, nbr = np.nonzero(edge)
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(rows, minlength=n), out=offsets[1:])
+    state, owner = select_host(offsets, nbr, rank, np.ones(n, dtype=np.uint8))
+    keep = state == SEL_INDEX
+    return keep, np.where(keep, -1, owner).astype(np.int64)
+
+
 # --------------------------------------------------------------------------- instrumentation
 def probe_andpop(blocks: int, threads: int, iters: int) -> torch.Tensor:
     sink = torch.empty(blocks * threads, dtype=torch.int32, device=torch.device("cuda", torch.cuda.current_device()))
