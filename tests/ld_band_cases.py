@@ -117,6 +117,27 @@ def cell_rows_cols(lo, offsets):
     return rows, cols
 
 
+CHUNK_ROWS = 4096                    # band_chunks' default height
+
+
+def band_chunks(lo, offsets, height: int = CHUNK_ROWS):
+    """The band in chunks of ``height`` rows, for a reference that is computed on sub-rectangles: yields
+    ((a, b), (c0, b), cells, li, lj) -- the rows [a, b), the columns [c0, b) with c0 = lo[a] (lo is non-decreasing and a cell's
+    column is below its row, so they hold every cell of those rows), the cell numbers of those rows in layout order (int64,
+    consecutive) and the cells' (row - a, column - c0).  Nothing of size n x n is built."""
+    lo = np.asarray(lo).astype(np.int64)
+    off = np.asarray(offsets).astype(np.int64)
+    n = lo.size
+    for a in range(0, n, height):
+        b = min(a + height, n)
+        c0 = int(lo[a])
+        length = np.arange(a, b, dtype=np.int64) - lo[a:b]
+        cells = np.arange(off[a], off[b], dtype=np.int64)
+        li = np.repeat(np.arange(b - a, dtype=np.int64), length)
+        lj = cells - np.repeat(off[a:b] - lo[a:b], length) - c0
+        yield (a, b), (c0, b), cells, li, lj
+
+
 def pair_sums(n: int, rows, cols, terms, own=None) -> np.ndarray:
     """int64 [n]: every cell's term added to both of its SNPs, plus the SNPs' own terms; int64 addition wraps, as the
     kernels' 64-bit words do."""

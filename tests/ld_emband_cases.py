@@ -30,6 +30,15 @@ GRID_CASE = (4100, 62)            # the everything window: 33 I blocks, 561 tile
 GRID_TILES = 561
 GRID_HOLE_ROWS = (4099, 77)       # one hole-carrying row past row 4096, one inside column slab 0
 SMALL_SIZES = (1, 129)
+# past the first trip of the plan (ldx_band_plan.h: plan_kernel prefix-sums 256 I blocks per trip and carries the total on):
+# 258 I blocks of 128 rows, blocks 256 (full) and 257 (77 rows) in the second trip; pb.ragged_positions, pb.PLAN_WINDOW
+PLAN_TRIP = pb.PLAN_TRIP
+PLAN_CASE = (128 * 257 + 77, 62)  # 32 973 SNPs
+PLAN_WINDOW = pb.PLAN_WINDOW
+PLAN_CELLS, PLAN_REACH, PLAN_TILES, PLAN_TILES_PAST = 836_438, 38, 515, 4   # pinned by tests/test_ld_emband_host.py
+PLAN_HOLE_ROWS = slice(128 * 256, 128 * 257)   # plan_panel's only rows with holes: I block 256 = slab 256
+PLAN_SAMPLED_FROM = 128 * 255     # the oracle's sample: rows of I blocks 255 and above
+PLAN_SAMPLED_CELLS = 200
 
 _CACHE = {}
 
@@ -79,21 +88,33 @@ def grid_panel() -> np.ndarray:
     return _keep(("grid",), build)
 
 
-def tile_kinds(codes, lo) -> set:
-    """{(holes in the I block, holes in the slab)} over the 128 x 128 tiles the band kernel walks for this layout."""
+def plan_panel() -> np.ndarray:
+    """complete_panel at PLAN_CASE with holes (MISS) in the rows PLAN_HOLE_ROWS only: with PLAN_WINDOW the I blocks of
+    plan_kernel's second trip hold clean x clean, holes x clean, clean x holes and holes x holes tiles."""
+    def build():
+        codes = plant_het(pb.complete_panel(*PLAN_CASE))
+        px.add_holes(codes, np.random.default_rng(4245), rows=PLAN_HOLE_ROWS)
+        return codes
+    return _keep(("plan",), build)
+
+
+def tile_kinds(codes, lo, first_block: int = 0) -> set:
+    """{(holes in the I block, holes in the slab)} over the 128 x 128 tiles the band kernel walks for this layout, from I
+    block ``first_block`` on."""
     holes = ~px.complete_rows(codes)
     n = codes.shape[0]
     kinds = set()
-    for ti in range((n + 127) // 128):
+    for ti in range(first_block, (n + 127) // 128):
         r0, r1 = 128 * ti, min(128 * (ti + 1), n)
         for tj in range(int(lo[r0]) // 128, (r1 - 1) // 128 + 1):
             kinds.add((bool(holes[r0:r1].any()), bool(holes[128 * tj: 128 * (tj + 1)].any())))
     return kinds
 
 
-def tiles_walked(lo, n: int) -> int:
-    """Tiles of the band kernel's walk: the sum over I blocks of 128 rows of the slabs lo[128 ti] / 128 .. (r1 - 1) / 128."""
-    return sum((min(128 * (ti + 1), n) - 1) // 128 - int(lo[128 * ti]) // 128 + 1 for ti in range((n + 127) // 128))
+def tiles_walked(lo, n: int, first_block: int = 0) -> int:
+    """Tiles of the band kernel's walk: the sum over I blocks of 128 rows (from ``first_block`` on) of the slabs lo[128 ti] / 128
+    .. (r1 - 1) / 128."""
+    return sum((min(128 * (ti + 1), n) - 1) // 128 - int(lo[128 * ti]) // 128 + 1 for ti in range(first_block, (n + 127) // 128))
 
 
 def own_counts(codes, pairwise: bool):

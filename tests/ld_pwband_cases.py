@@ -28,6 +28,16 @@ BIG_CASE = (130, 10240)           # an all-ALT row: the largest counts
 GRID_CASE = (8269, 62)            # the everything window: 33 I blocks, 1 105 tiles -- more than a grid of two workgroups per CU
 WALK_SIZES = (1, 257, 4096 + 130)
 N_ANNOT = 3
+# past the first trip of the plan (ldx_band_plan.h: plan_kernel prefix-sums 256 I blocks per trip and carries the total on):
+# 258 I blocks, blocks 256 (full) and 257 (77 rows) in the second trip; ragged positions, about 25 SNPs each side
+PLAN_TRIP = 256                   # I blocks per trip of plan_kernel
+PLAN_CASE = (256 * 257 + 77, 62)  # 65 869 SNPs
+PLAN_WINDOW = 500
+PLAN_CELLS, PLAN_REACH, PLAN_TILES, PLAN_TILES_PAST = 1_669_273, 41, 772, 5   # pinned by tests/test_ld_pwband_host.py
+# plan_panel's only rows with holes: the second slab of I block 256.  I block 257 starts at row 65 792, whose window reaches
+# back to slab 513 and no further, so slab 513 is the one slab a hole-free I block of the second trip meets with holes in it
+# (the block's first slab, 512, is met by block 256 alone: no clean x holes tile)
+PLAN_HOLE_ROWS = slice(256 * 256 + 128, 256 * 256 + 256)
 
 _CACHE = {}
 
@@ -96,21 +106,35 @@ def tiles_panel(n: int = N_MAIN, n_hap: int = 1008) -> np.ndarray:
     return _CACHE[key]
 
 
-def tile_kinds(codes, lo) -> set:
-    """{(holes in the I block, holes in the slab)} over the tiles the band kernel walks for this layout."""
+def plan_panel() -> np.ndarray:
+    """complete_panel at PLAN_CASE with holes (MISS) in the rows PLAN_HOLE_ROWS only: with PLAN_WINDOW the I blocks of
+    plan_kernel's second trip hold clean x clean, holes x clean, clean x holes and holes x holes tiles."""
+    key = ("plan",)
+    if key not in _CACHE:
+        codes = np.array(complete_panel(*PLAN_CASE))
+        px.add_holes(codes, np.random.default_rng(4244), rows=PLAN_HOLE_ROWS)
+        codes.setflags(write=False)
+        _CACHE[key] = codes
+    return _CACHE[key]
+
+
+def tile_kinds(codes, lo, first_block: int = 0) -> set:
+    """{(holes in the I block, holes in the slab)} over the tiles the band kernel walks for this layout, from I block
+    ``first_block`` on."""
     holes = ~px.complete_rows(codes)
     n = codes.shape[0]
     kinds = set()
-    for ti in range((n + 255) // 256):
+    for ti in range(first_block, (n + 255) // 256):
         r0, r1 = 256 * ti, min(256 * (ti + 1), n)
         for tj in range(int(lo[r0]) // 128, (r1 - 1) // 128 + 1):
             kinds.add((bool(holes[r0:r1].any()), bool(holes[128 * tj: 128 * (tj + 1)].any())))
     return kinds
 
 
-def tiles_walked(lo, n: int) -> int:
-    """Tiles of the band kernel's walk: the sum over I blocks of the slabs lo[256 ti] / 128 .. (r1 - 1) / 128."""
-    return sum((min(256 * (ti + 1), n) - 1) // 128 - int(lo[256 * ti]) // 128 + 1 for ti in range((n + 255) // 256))
+def tiles_walked(lo, n: int, first_block: int = 0) -> int:
+    """Tiles of the band kernel's walk: the sum over I blocks (from ``first_block`` on) of the slabs lo[256 ti] / 128 ..
+    (r1 - 1) / 128."""
+    return sum((min(256 * (ti + 1), n) - 1) // 128 - int(lo[256 * ti]) // 128 + 1 for ti in range(first_block, (n + 255) // 256))
 
 
 def annot_matrix(n: int) -> np.ndarray:

@@ -92,6 +92,49 @@ def test_medium_panel(gpu):
     assert np.array_equal(ints(sample_counts(PackedPanel.from_codes(codes, gpu), store_snps=3001)), want)   # seven stores, accumulated
 
 
+MOST_IND = 39 * 128 + 1   # 4993 individuals: T = 40 tile rows, 820 lower tiles, the most LDX_MAX_HAPS allows
+_MOST = {}
+
+
+def most_individuals(holes, gpu):
+    """(codes, host counts as int32 [4, n_ind, n_ind], the same on the device) of the 4993-individual panel, once per ``holes``."""
+    from ld_tools_amd import sample_counts_host
+
+    if holes not in _MOST:
+        codes = panel_codes(MOST_IND, 130, seed=4993 + len(holes), holes=holes)
+        want = sample_counts_host(codes).astype(np.int32)      # counts <= 130; the int64 copy would be 800 MB
+        _MOST[holes] = (codes, want, torch.from_numpy(want).to(gpu))
+    return _MOST[holes]
+
+
+@pytest.mark.parametrize("n_slices", [None, 2])
+@pytest.mark.parametrize("holes", ["single", "3%"])
+def test_every_tile_number_the_counts_kernel_can_be_given(gpu, holes, n_slices):
+    """counts_kernel turns a workgroup number into a lower tile (ti, tj) with a square root and two correcting loops; the other
+    cases reach 6 tiles.  Here all 820 of the largest panel, every count compared on the device.  With "single" the one
+    missing genotype (individual 2496) makes tile row and column 19 general tiles amid shortcut tiles across the triangle."""
+    from ld_tools_amd import PackedPanel, _lib, ibs_cell_host, king_cell_host, sample_counts
+
+    assert (MOST_IND + 127) // 128 == (_lib.MAX_HAPS // 2 + 127) // 128 == 40 and 40 * 41 // 2 == 820   # no panel has more tiles
+    codes, want, want_dev = most_individuals(holes, gpu)
+    sc = sample_counts(PackedPanel.from_codes(codes, gpu), n_slices=n_slices)
+    assert sc.n_ind == MOST_IND and sc.n_snps == 130
+    if not torch.equal(sc.counts, want_dev):
+        plane, a, b = (int(x) for x in torch.nonzero(sc.counts != want_dev)[0])
+        raise AssertionError(f"plane {plane}, individuals ({a}, {b}), tile ({a // 128}, {b // 128}): {sc.counts[plane, a, b].item()} "
+                             f"!= {want[plane, a, b]}")
+    if holes == "single":
+        assert 0 < (MOST_IND // 2) // 128 < 39 and int((want[0] != 130).sum()) == 2 * MOST_IND - 1
+    # the cells: the last tile row (one individual) against every partner, and 10 000 seeded cells
+    rng = np.random.default_rng(820)
+    a = np.concatenate([np.full(MOST_IND, MOST_IND - 1), rng.integers(0, MOST_IND, size=10_000)])
+    b = np.concatenate([np.arange(MOST_IND), rng.integers(0, MOST_IND, size=10_000)])
+    tup = (want[0][a, b], want[1][a, b], want[2][a, b], want[3][a, b], want[3][b, a])
+    ai, bi = torch.from_numpy(a).to(gpu), torch.from_numpy(b).to(gpu)
+    assert np.array_equal(bits(sc.kinship()[ai, bi].cpu().numpy()), bits(king_cell_host(*tup)))
+    assert np.array_equal(bits(sc.ibs()[ai, bi].cpu().numpy()), bits(ibs_cell_host(*tup)))
+
+
 def test_special_panels(gpu):
     from ld_tools_amd import PackedPanel, sample_counts, sample_counts_host
 

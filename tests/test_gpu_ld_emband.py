@@ -545,3 +545,92 @@ def test_drivers_on_a_chromosome_with_missing_calls(gpu, tmp_path):
     assert ct.clumps.neighbors.em and ct.clumps.neighbors.missing == PW and pt.pruned.neighbors.em
     direct = ops.ld_prune(panel, pos, r2=r2, window_bp=window, em=True, missing=PW)
     assert np.array_equal(pt.pruned.keep, direct.keep)
+
+
+# ---- 12. past the first trip of the plan --------------------------------------------------------------------------------------
+# eb.PLAN_CASE: 258 I blocks of 128 rows, two of them in plan_kernel's second trip (ldx_band_plan.h): the carry between trips,
+# prefix[Ti] after the loop, tile_at's search over 259 entries, rows up to 32 972.  The reference of every cell is the EM
+# rectangle of a SELECTED panel, whose rows start at 0; sampled cells of the last I blocks go to the 60-digit oracle.
+PLAN_PANELS = ("plan", "mixed")
+PLAN_FILL = 0x7FC12345   # a quiet NaN with a payload no kernel produces
+_PLAN = {}
+
+
+def plan_case(kind):
+    n, n_hap = eb.PLAN_CASE
+    codes = eb.plan_panel() if kind == "plan" else eb.mixed_panel(n, n_hap)
+    return ("plan", kind), codes, pb.ragged_positions(n)
+
+
+def plan_layout():
+    """(lo, offsets, rows, cols) of the plan case on the host, int64, from band_layout_host; once per process."""
+    if "layout" not in _PLAN:
+        lo, off, rows, cols = eb.band_cells(pb.ragged_positions(eb.PLAN_CASE[0]), eb.PLAN_WINDOW)
+        _PLAN["layout"] = (lo.astype(np.int64), off.astype(np.int64), rows, cols)
+    return _PLAN["layout"]
+
+
+def plan_bands(gpu, kind, missing):
+    """ld_em_band of the plan case, once per panel and form (the store test checks every cell of it)."""
+    import torch
+    from ld_tools_amd import ops
+    if (kind, missing) not in _PLAN:
+        key, codes, pos = plan_case(kind)
+        # two freed blocks of the values' size full of the fill pattern: the allocator hands them to the next requests of that
+        # size, so a cell the kernel leaves out is likely to show as the pattern and not as an earlier run's bytes
+        filled = [torch.full((eb.PLAN_CELLS,), PLAN_FILL, dtype=torch.int32, device=gpu) for _ in range(2)]
+        del filled
+        _PLAN[(kind, missing)] = ops.ld_em_band(packed(key, codes), pos, window_bp=eb.PLAN_WINDOW, missing=missing)
+    return _PLAN[(kind, missing)]
+
+
+@pytest.mark.parametrize("missing", MISSING)
+@pytest.mark.parametrize("kind", PLAN_PANELS)
+def test_past_the_first_trip_the_store_is_the_rectangle_and_the_oracle(gpu, kind, missing):
+    import torch
+    from ld_tools_amd import ops
+    key, codes, pos = plan_case(kind)
+    n = codes.shape[0]
+    p = packed(key, codes)
+    lo, off, rows, cols = plan_layout()
+    what = f"plan case, {kind} panel, missing={missing}"
+    res = plan_bands(gpu, kind, missing)
+    assert res.r.n_snps == n and res.n_cells == eb.PLAN_CELLS
+    assert np.array_equal(res.r.layout()[0], lo) and np.array_equal(res.r.layout()[1], off)
+    got = {"r": res.r.values.view(torch.int32), "D'": res.dprime.values.view(torch.int32)}
+    for name, g in got.items():
+        assert not bool((g == PLAN_FILL).any().item()), f"{what}: a cell of {name} was not written"
+    for (a, b), (c0, c1), cells, li, lj in bc.band_chunks(lo, off):
+        sq = ops.ld_em(p.select(snps=np.arange(a, b)), p.select(snps=np.arange(c0, c1)), missing=missing)
+        at = torch.from_numpy(li * (c1 - c0) + lj).to(gpu)
+        for name, m in (("r", sq.r), ("D'", sq.dprime)):
+            want = m.reshape(-1).view(torch.int32)[at]
+            mine = got[name][int(cells[0]): int(cells[-1]) + 1]
+            if not torch.equal(mine, want):
+                k = int(torch.nonzero(mine != want)[0].item())
+                raise AssertionError(f"{what}: {name} cell {cells[k]} = ({a + li[k]}, {c0 + lj[k]}) has the bits {mine[k].item():#x}, "
+                                     f"the rectangle of rows {a} .. {b - 1} has {want[k].item():#x}")
+    live = assert_diag(res, codes, missing, what)
+    # the 60-digit oracle on seeded cells of I blocks 255 and above, on their own five integers (a tie passes either way)
+    cand = np.flatnonzero(live[rows] & live[cols] & (rows >= eb.PLAN_SAMPLED_FROM))
+    pick = np.sort(np.random.default_rng(255).choice(cand, size=eb.PLAN_SAMPLED_CELLS, replace=False))
+    assert (rows[pick] >= 128 * eb.PLAN_TRIP).sum() >= 50                      # in the second trip's own rows too
+    counts = eb.pair_counts(codes, rows[pick], cols[pick], missing == PW)
+    r, d = res.r.values.cpu().numpy()[pick], res.dprime.values.cpu().numpy()[pick]
+    bad = eb.cells_pass_the_oracle(counts, r, d)
+    assert not bad, f"{what}: {len(bad)} of {pick.size} sampled cells miss the oracle, the first {bad[0]}"
+
+
+@pytest.mark.parametrize("missing", MISSING)
+@pytest.mark.parametrize("kind", PLAN_PANELS)
+def test_past_the_first_trip_neighbours_are_the_host_filter_of_the_band_cells(gpu, kind, missing):
+    from ld_tools_amd import ops
+    key, codes, pos = plan_case(kind)
+    n = codes.shape[0]
+    lo, off, rows, cols = plan_layout()
+    res = plan_bands(gpu, kind, missing)
+    want = eb.expected_neighbors(n, rows, cols, res.r.values.cpu().numpy(), res.dprime.values.cpu().numpy(),
+                                 ops.r2_bound(eb.NBR_R2))
+    nb = ops.ld_neighbors(packed(key, codes), pos, window_bp=eb.PLAN_WINDOW, r2=eb.NBR_R2, em=True, missing=missing)
+    assert_neighbors(nb, want, f"plan case, {kind} panel, missing={missing}")
+    assert int((want[1] >= 128 * eb.PLAN_TRIP).sum()) >= 1                     # a hit in a row of the second trip

@@ -308,3 +308,44 @@ def test_the_operators_refuse_dosage_and_haplotype_paths(gpu):
             ops.ld_gabriel_blocks(panel, pos, window_bp=gc.WINDOW, **kw)
     with pytest.raises(LdxError):
         ops.ld_gabriel_blocks(panel, pos, window_bp=gc.WINDOW, cuts=(1, 2))
+
+
+# ---- 5. past the first trip of the plan -----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("missing", MISSING)
+@pytest.mark.parametrize("kind", ["plan", "mixed"])
+def test_past_the_first_trip_every_byte_is_the_list_epilogue_on_the_cpu_counts(gpu, kind, missing):
+    """eb.PLAN_CASE: 258 I blocks, two of them in plan_kernel's second trip (ldx_band_plan.h).  Every byte of both bands against
+    the list epilogue on the CPU's five integers, which are counted block by block of 512 rows.  (No sample goes to the
+    60-digit definition here: at 31 individuals small tables tie too often for the 0.5 % cap, as the grid case notes, and the
+    list epilogue is held to the definition by test 1.)"""
+    import ld_band_cases as bc
+    import ld_pwband_cases as pb
+    from ld_tools_amd import ops
+    n, n_hap = eb.PLAN_CASE
+    codes = eb.plan_panel() if kind == "plan" else eb.mixed_panel(n, n_hap)
+    pos = pb.ragged_positions(n)
+    what = f"plan case, {kind} panel, missing={missing}"
+    panel = packed(("plan", kind), codes)
+    ci = ops.ld_dprime_ci(panel, pos, window_bp=eb.PLAN_WINDOW, missing=missing)
+    band_lo, off, rows, cols = eb.band_cells(pos, eb.PLAN_WINDOW)
+    assert ci.n_cells == rows.size == eb.PLAN_CELLS and ci.n_snps == n
+    assert np.array_equal(ci.layout()[0], band_lo.astype(np.int64)) and np.array_equal(ci.layout()[1], off.astype(np.int64))
+    kept = host_kept(codes, missing)
+    assert np.array_equal(ci.kept.cpu().numpy().astype(bool), kept) and kept.sum() > n // 4 and not kept.all()
+    got_lo, got_hi = ci.lo.cpu().numpy(), ci.hi.cpu().numpy()
+    run = kept[rows] & kept[cols]
+    assert (run & (rows >= 128 * eb.PLAN_TRIP)).sum() >= 100 and (~run & (rows >= 128 * eb.PLAN_TRIP)).sum() >= 100
+    assert ((got_lo[~run] == ops.NO_CI) & (got_hi[~run] == ops.NO_CI)).all(), what
+    f = form(codes, missing)
+    counts = np.empty((5, eb.PLAN_CELLS), dtype=np.int64)
+    for (a, b), (c0, c1), cells, li, lj in bc.band_chunks(band_lo, off, 512):
+        counts[:, cells] = epx.pair_counts(f[a:b], f[c0:c1])[:, li, lj]
+    want_lo, want_hi = (t.cpu().numpy() for t in ops.ld_ci_from_counts(*counts[:, run]))
+    bad = np.flatnonzero((got_lo[run] != want_lo) | (got_hi[run] != want_hi))
+    assert bad.size == 0, (f"{what}: {bad.size} cells differ from the list epilogue, the first ({rows[run][bad[0]]}, "
+                           f"{cols[run][bad[0]]}): {(got_lo[run][bad[0]], got_hi[run][bad[0]])} != {(want_lo[bad[0]], want_hi[bad[0]])}")
+    has = want_lo != ops.NO_CI                                                # (a kept pair may be monomorphic within its joint set)
+    assert has.mean() > 0.9 and np.array_equal(has, want_hi != ops.NO_CI) and (want_lo[has] <= want_hi[has]).all()
+    # a relaunch into dirty buffers gives the same bytes: every cell of the layout is written
+    again_lo, again_hi = raw_ci_band(panel, pos, eb.PLAN_WINDOW, kept, ci.band_lo, ci.offsets, ci.n_cells, missing == PW, 0x5A)
+    assert np.array_equal(again_lo, got_lo) and np.array_equal(again_hi, got_hi), what

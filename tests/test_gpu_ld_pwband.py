@@ -450,3 +450,112 @@ def test_drivers_pass_missing_through(gpu, dosage):
     else:
         plain = band_matrix(vcf, "6", rows, names, window_bp=2_000)
         assert plain.band.missing is None and not np.array_equal(bits(plain.band.values), bits(m.band.values))
+
+
+# ---- 10. past the first trip of the plan ---------------------------------------------------------------------------------------
+# pb.PLAN_CASE: 258 I blocks, two of them in plan_kernel's second trip (ldx_band_plan.h): the carry between trips, prefix[Ti]
+# after the loop, tile_at's search over 259 entries, rows up to 65 868.  The reference of every cell is the rectangle of a
+# SELECTED panel, whose rows start at 0; three row blocks go to the exact oracle, one of them across the trip boundary.
+PLAN_PANELS = ("plan", "mixed")
+PLAN_FILL = 0x7FC12345   # walk_case's quiet NaN: a payload no kernel produces
+_PLAN_BAND = {}
+
+
+def plan_case(kind):
+    n, n_hap = pb.PLAN_CASE
+    codes = pb.plan_panel() if kind == "plan" else pb.mixed_panel(n, n_hap)[0]
+    return ("plan", kind), codes, pb.ragged_positions(n)
+
+
+def plan_layout():
+    """(lo, offsets, rows, cols) of the plan case on the host, from band_layout_host; once per process."""
+    from ld_tools_amd import ops
+    if "layout" not in _PLAN_BAND:
+        lo, off = ops.band_layout_host(pb.ragged_positions(pb.PLAN_CASE[0]), pb.PLAN_WINDOW)
+        _PLAN_BAND["layout"] = (lo.astype(np.int64), off.astype(np.int64)) + bc.cell_rows_cols(lo, off)
+    return _PLAN_BAND["layout"]
+
+
+def plan_band(gpu, kind, dosage):
+    """The stored band of the plan case, once per panel and form (the store test checks every cell of it)."""
+    import torch
+    from ld_tools_amd import ops
+    if (kind, dosage) not in _PLAN_BAND:
+        key, codes, pos = plan_case(kind)
+        # a freed block of the values' size full of the fill pattern: the allocator hands it to the next request of that size,
+        # so a cell the kernel leaves out is likely to show as the pattern and not as an earlier run's bytes
+        filled = torch.full((pb.PLAN_CELLS,), PLAN_FILL, dtype=torch.int32, device=gpu)
+        del filled
+        _PLAN_BAND[(kind, dosage)] = ops.ld_band(packed(key, codes), pos, window_bp=pb.PLAN_WINDOW, dosage=dosage, missing=PW)
+    return _PLAN_BAND[(kind, dosage)]
+
+
+@pytest.mark.parametrize("dosage", FORMS)
+@pytest.mark.parametrize("kind", PLAN_PANELS)
+def test_past_the_first_trip_the_stored_band_is_the_rectangle_and_the_oracle(gpu, kind, dosage):
+    import torch
+    from ld_tools_amd import ops
+    key, codes, pos = plan_case(kind)
+    n = codes.shape[0]
+    p = packed(key, codes)
+    lo, off, rows, cols = plan_layout()
+    what = f"plan case, {kind} panel, dosage={dosage}"
+    band = plan_band(gpu, kind, dosage)
+    assert band.n_snps == n and band.n_cells == pb.PLAN_CELLS
+    assert np.array_equal(band.layout()[0], lo) and np.array_equal(band.layout()[1], off)
+    got = band.values.view(torch.int32)
+    assert not bool((got == PLAN_FILL).any().item()), f"{what}: a cell was not written"
+    for (a, b), (c0, c1), cells, li, lj in bc.band_chunks(lo, off):
+        sq = ops.ld_rect(p.select(snps=np.arange(a, b)), p.select(snps=np.arange(c0, c1)), dosage=dosage, missing=PW)
+        want = sq.reshape(-1).view(torch.int32)[torch.from_numpy(li * (c1 - c0) + lj).to(gpu)]
+        mine = got[int(cells[0]): int(cells[-1]) + 1]
+        if not torch.equal(mine, want):
+            k = int(torch.nonzero(mine != want)[0].item())
+            raise AssertionError(f"{what}: cell {cells[k]} = ({a + li[k]}, {c0 + lj[k]}) is {band.values[int(cells[k])].item()!r}, "
+                                 f"the rectangle of rows {a} .. {b - 1} has {sq[int(li[k]), int(lj[k])].item()!r}")
+    # the exact oracle on three row blocks: the first rows, across the trip boundary (I blocks 255 | 256), the ragged last block
+    values, diag = band.values.cpu().numpy(), bits(band.diag)
+    edge = 256 * pb.PLAN_TRIP
+    for a, b in ((0, 512), (edge - 256, edge + 256), (n - 333, n)):
+        c0 = int(lo[a])
+        ex = px.PairwiseExactBlock(codes[a:b], codes[c0:b], dosage)
+        at = np.arange(off[a], off[b])
+        check_cells(values[at], ex, rows[at] - a, cols[at] - c0, f"{what}, rows {a} .. {b - 1}")
+        own = np.arange(b - a)
+        live = ex.v_x[own, own + a - c0] > 0                                   # check_diag's rule on the block's own rows
+        assert np.array_equal(diag[a:b] == ONE, live) and np.array_equal(diag[a:b] == NEG0, ~live), f"{what}: diag of rows {a} .."
+
+
+@pytest.mark.parametrize("dosage", FORMS)
+@pytest.mark.parametrize("kind", PLAN_PANELS)
+def test_past_the_first_trip_scores_are_the_host_sums_of_the_band_cells(gpu, kind, dosage):
+    from ld_tools_amd import ops
+    key, codes, pos = plan_case(kind)
+    n = codes.shape[0]
+    lo, off, rows, cols = plan_layout()
+    band = plan_band(gpu, kind, dosage)
+    values, live = band.values.cpu().numpy(), bits(band.diag) == ONE
+    bits_a, k = ops.pack_annot(pb.annot_matrix(n), n)
+    sc = ops.ld_score(packed(key, codes), pos, window_bp=pb.PLAN_WINDOW, annot=pb.annot_matrix(n), dosage=dosage, missing=PW)
+    got = sc.sums.cpu().numpy().view(np.uint64)
+    want = pb.expected_sums(n, rows, cols, values, live, bits_a, k)
+    assert got.shape == want.shape == (n, 1 + pb.N_ANNOT)
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, f"{kind}, dosage={dosage}: {bad.shape[0]} sums differ, the first at {bad[0].tolist()}: " \
+                          f"{got[tuple(bad[0])]} != {want[tuple(bad[0])]}"
+    assert np.array_equal(sc.live, live)
+    assert np.array_equal(sc.m, ops.window_counts(pos, pb.PLAN_WINDOW, live, bits_a, k))
+
+
+@pytest.mark.parametrize("dosage", FORMS)
+@pytest.mark.parametrize("kind", PLAN_PANELS)
+def test_past_the_first_trip_neighbours_are_the_host_filter_of_the_band_cells(gpu, kind, dosage):
+    from ld_tools_amd import ops
+    key, codes, pos = plan_case(kind)
+    n = codes.shape[0]
+    lo, off, rows, cols = plan_layout()
+    band = plan_band(gpu, kind, dosage)
+    want = pb.expected_neighbors(n, rows, cols, band.values.cpu().numpy(), ops.r2_bound(pb.NBR_R2))
+    nb = ops.ld_neighbors(packed(key, codes), pos, window_bp=pb.PLAN_WINDOW, r2=pb.NBR_R2, dosage=dosage, missing=PW)
+    assert_neighbors(nb, want, f"plan case, {kind} panel, dosage={dosage}")
+    assert int((want[1] >= 256 * pb.PLAN_TRIP).sum()) >= 1                     # a hit in a row of the second trip

@@ -13,6 +13,7 @@ import pytest
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "tests"))
 
+import ld_band_cases as bc  # noqa: E402
 import ld_em_exact as emx  # noqa: E402
 import ld_em_pairwise_exact as epx  # noqa: E402
 import ld_emband_cases as eb  # noqa: E402
@@ -62,6 +63,41 @@ def test_the_grid_case_has_561_tiles_and_two_hole_rows():
     holes = np.flatnonzero(~px.complete_rows(codes))
     assert sorted(holes.tolist()) == sorted(eb.GRID_HOLE_ROWS) and max(eb.GRID_HOLE_ROWS) > 4096 and min(eb.GRID_HOLE_ROWS) < 128
     assert eb.own_live(codes, True)[list(eb.GRID_HOLE_ROWS)].all()
+
+
+def test_the_plan_case_lies_past_the_first_trip_of_the_plan():
+    """PLAN_CASE from band_layout_host alone: 258 I blocks of 128 rows, so two of them in plan_kernel's second trip, with the
+    four tile kinds among their tiles; and band_chunks covers the band once."""
+    from ld_tools_amd import ops
+    n, n_hap = eb.PLAN_CASE
+    assert n == 32_973 and n_hap == 62
+    pos = pb.ragged_positions(n)
+    lo, off = ops.band_layout_host(pos, eb.PLAN_WINDOW)
+    lo = lo.astype(np.int64)
+    blocks = (n + 127) // 128
+    assert blocks == 258 > eb.PLAN_TRIP and n - 128 * 257 == 77                # one full and one ragged block past the trip
+    assert int(off[n]) == eb.PLAN_CELLS == 836_438 and int((np.arange(n) - lo).max()) == eb.PLAN_REACH == 38
+    assert eb.tiles_walked(lo, n) == eb.PLAN_TILES == 515 > 2 * 256            # more than two workgroups on each of 256 CUs
+    assert eb.tiles_walked(lo, n, eb.PLAN_TRIP) == eb.PLAN_TILES_PAST == 4
+    assert any(lo[128 * ti] // 128 < ti for ti in range(eb.PLAN_TRIP, blocks))   # a first slab that is not the block's own
+    codes = eb.plan_panel()
+    assert codes.shape == eb.PLAN_CASE
+    holes = ~px.complete_rows(codes)
+    assert holes[eb.PLAN_HOLE_ROWS].any() and int(holes.sum()) == int(holes[eb.PLAN_HOLE_ROWS].sum())   # one slab, nothing else
+    assert (eb.PLAN_HOLE_ROWS.start, eb.PLAN_HOLE_ROWS.stop) == (128 * eb.PLAN_TRIP, 128 * eb.PLAN_TRIP + 128)
+    assert eb.tile_kinds(codes, lo, eb.PLAN_TRIP) == {(False, False), (True, False), (False, True), (True, True)}
+    assert eb.tile_kinds(eb.mixed_panel(n, n_hap), lo, eb.PLAN_TRIP) == {(True, True)}
+    live = eb.own_live(codes, True)
+    rows, cols = bc.cell_rows_cols(lo, off)
+    assert int((live[rows] & live[cols] & (rows >= eb.PLAN_SAMPLED_FROM)).sum()) > eb.PLAN_SAMPLED_CELLS
+    # the chunks: every cell once, in layout order, inside its chunk's rectangle, at its own (row, column)
+    seen = []
+    for (a, b), (c0, c1), cells, li, lj in bc.band_chunks(lo, off):
+        assert 0 < b - a <= bc.CHUNK_ROWS and c1 == b and c0 == lo[a] and c1 - c0 <= bc.CHUNK_ROWS + eb.PLAN_REACH
+        assert np.array_equal(rows[cells], a + li) and np.array_equal(cols[cells], c0 + lj)
+        assert (li < b - a).all() and (lj >= 0).all() and (lj < c1 - c0).all()
+        seen.append(cells)
+    assert len(seen) == 9 and np.array_equal(np.concatenate(seen), np.arange(eb.PLAN_CELLS))
 
 
 @pytest.mark.parametrize("kind", ["mixed", "complete"])

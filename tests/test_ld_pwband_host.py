@@ -156,6 +156,40 @@ def test_the_panels_hold_what_the_gpu_tests_rely_on():
     assert int(px.PairwiseExactBlock(big[60:70], big[60:70], True).S.max()) == 2 * pb.BIG_CASE[1]
 
 
+def test_the_plan_case_lies_past_the_first_trip_of_the_plan():
+    """PLAN_CASE from band_layout_host alone: 258 I blocks of 256 rows, so two of them in plan_kernel's second trip, with the
+    four tile kinds among their tiles; and band_chunks covers the band once."""
+    from ld_tools_amd import ops
+    n, n_hap = pb.PLAN_CASE
+    assert n == 65_869 and n_hap == 62
+    pos = pb.ragged_positions(n)
+    lo, off = ops.band_layout_host(pos, pb.PLAN_WINDOW)
+    lo = lo.astype(np.int64)
+    blocks = (n + 255) // 256
+    assert blocks == 258 > pb.PLAN_TRIP and n - 256 * 257 == 77                # one full and one ragged block past the trip
+    assert int(off[n]) == pb.PLAN_CELLS == 1_669_273 and int((np.arange(n) - lo).max()) == pb.PLAN_REACH == 41
+    assert pb.tiles_walked(lo, n) == pb.PLAN_TILES == 772 > 2 * 256            # more than two workgroups on each of 256 CUs
+    assert pb.tiles_walked(lo, n, pb.PLAN_TRIP) == pb.PLAN_TILES_PAST == 5 >= 4
+    assert any(lo[256 * ti] // 128 < (256 * ti) // 128 for ti in range(pb.PLAN_TRIP, blocks))   # a first slab that is not its own
+    codes = pb.plan_panel()
+    assert codes.shape == pb.PLAN_CASE
+    holes = ~px.complete_rows(codes)
+    assert holes[pb.PLAN_HOLE_ROWS].any() and int(holes.sum()) == int(holes[pb.PLAN_HOLE_ROWS].sum())   # one slab, nothing else
+    assert pb.PLAN_HOLE_ROWS.start % 128 == 0 and pb.PLAN_HOLE_ROWS.stop - pb.PLAN_HOLE_ROWS.start == 128
+    assert pb.PLAN_HOLE_ROWS.start // 256 == pb.PLAN_TRIP
+    assert pb.tile_kinds(codes, lo, pb.PLAN_TRIP) == {(False, False), (True, False), (False, True), (True, True)}
+    assert pb.tile_kinds(pb.mixed_panel(n, n_hap)[0], lo, pb.PLAN_TRIP) == {(True, True)}
+    # the chunks: every cell once, in layout order, inside its chunk's rectangle, at its own (row, column)
+    rows, cols = bc.cell_rows_cols(lo, off)
+    seen = []
+    for (a, b), (c0, c1), cells, li, lj in bc.band_chunks(lo, off):
+        assert 0 < b - a <= bc.CHUNK_ROWS and c1 == b and c0 == lo[a] and c1 - c0 <= bc.CHUNK_ROWS + pb.PLAN_REACH
+        assert np.array_equal(rows[cells], a + li) and np.array_equal(cols[cells], c0 + lj)
+        assert (li < b - a).all() and (lj >= 0).all() and (lj < c1 - c0).all()
+        seen.append(cells)
+    assert len(seen) == 17 and np.array_equal(np.concatenate(seen), np.arange(pb.PLAN_CELLS))
+
+
 # ---- 3. the ABI and the argument rules --------------------------------------------------------------------------------------------
 def test_new_symbols_are_declared_bound_and_exported():
     from ld_tools_amd import _lib
