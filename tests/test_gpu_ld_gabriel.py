@@ -6,6 +6,11 @@ pair's five integers from the CPU (ld_em_pairwise_exact.pair_counts), 0xFF where
 window; sampled cells equal the 60-digit definition (tests/ld_ci_exact.py) unless that calls the tuple fragile, and at most 0.5 %
 of a sample may be fragile; blocks, block count and candidate count are the host mirrors' on the DEVICE's own bytes, exactly --
 it is integer logic from there on.  Sizes sit on the band kernel's loops: 128 x 128 tiles, 256-haplotype K-blocks.
+
+Section 6 drives the integer kernels of csrc/ldx_gabriel.hip directly, on made-up bound bytes (tests/ld_gabriel_kernel_cases.py):
+the candidate list slot by slot against the layout and the host mirror, the pick against the host mirror, both against the plain
+loops of tests/ld_gabriel_cases.py where those are cheap.  tests/test_ld_gabriel_host.py proves without a GPU that each input
+reaches the depth it is there for.
 """
 import ctypes as C
 import sys
@@ -349,3 +354,161 @@ def test_past_the_first_trip_every_byte_is_the_list_epilogue_on_the_cpu_counts(g
     # a relaunch into dirty buffers gives the same bytes: every cell of the layout is written
     again_lo, again_hi = raw_ci_band(panel, pos, eb.PLAN_WINDOW, kept, ci.band_lo, ci.offsets, ci.n_cells, missing == PW, 0x5A)
     assert np.array_equal(again_lo, got_lo) and np.array_equal(again_hi, got_hi), what
+
+
+# ---- 6. the candidate and pick kernels, directly (tests/ld_gabriel_kernel_cases.py) ---------------------------------------------
+# No panel and no EM: made-up bound bytes, so that the chunks of pick_kernel settle at depth, the lists run over many chunks and
+# the trips of the scans over several multiples of 256.  Every device array is a view of one poisoned allocation with gaps
+# between the views (kc.Kernels): a stray write fails an assertion there.
+import ld_gabriel_kernel_cases as kc  # noqa: E402
+
+_KERNELS = {}
+
+
+def kernels(gpu, name, keep="case", layout=None):
+    """The carve of a case, made once (its outputs and workspaces stay dirty from launch to launch)."""
+    key = (name, keep if isinstance(keep, str) else "none" if keep is None else "all", layout is not None)
+    if key not in _KERNELS:
+        _KERNELS[key] = kc.Kernels(gpu, kc.case(name), keep=keep, layout=layout)
+    return _KERNELS[key]
+
+
+def assert_the_list_and_the_pick(res, name, what, params=None, all_kept=False, brute=False):
+    """The three comparisons of every direct case.  ``params``: what the kernels were given (None: the defaults);
+    the mirrors get the same."""
+    c = kc.case(name)
+    first, last, _ = kc.column_major(c["band_lo"], c["off"])
+    # the list in full: one slot per cell, column-major, every slot written
+    assert res.cand_span.shape == res.cand_first.shape == res.cand_last.shape == (c["n_cells"],) == first.shape, what
+    assert not (res.cand_first == 0xA5A5A5A5).any() and not (res.cand_last == 0xA5A5A5A5).any(), what
+    assert not (res.cand_span.view(np.uint64) == 0xA5A5A5A5A5A5A5A5).any(), what
+    assert np.array_equal(res.cand_first, first) and np.array_equal(res.cand_last, last), what
+    cands, block_of, n_blocks = kc.mirrors(name, params, all_kept)
+    live = res.cand_span >= 0
+    got = np.stack([res.cand_first[live].astype(np.int64), res.cand_last[live].astype(np.int64), res.cand_span[live]], axis=1)
+    assert np.array_equal(got, cands), (what, got.shape, cands.shape)
+    assert (res.cand_span[~live] == -1).all(), what
+    # the pick
+    assert np.array_equal(res.block_of, block_of), (what, np.flatnonzero(res.block_of != block_of)[:8])
+    assert res.n_out.tolist() == [n_blocks, cands.shape[0]], (what, res.n_out, n_blocks, cands.shape[0])
+    if brute:
+        valid, _, brute_blocks, accepted, _ = kc.brute(name, params, all_kept)
+        assert [tuple(v) for v in got.tolist()] == valid and np.array_equal(res.block_of, brute_blocks), what
+        assert int(res.n_out[0]) == len(accepted), what
+    return cands, block_of, n_blocks
+
+
+@pytest.mark.parametrize("params", [None, kc.OTHER], ids=["default", "other"])
+@pytest.mark.parametrize("name", ["random257", "random513"])
+def test_kernels_on_random_bounds_equal_the_mirrors_and_the_plain_loops(gpu, name, params):
+    res = kernels(gpu, name).run(params or {})
+    cands, _, n_blocks = assert_the_list_and_the_pick(res, name, f"{name}, {params}", params, brute=True)
+    assert cands.shape[0] >= 100 and n_blocks >= 15
+
+
+@pytest.mark.parametrize("name", ["long3000", "wide600"])
+def test_kernels_over_many_chunks_of_candidates(gpu, name):
+    """Blocks accepted in one chunk kill candidates many chunks later (tests/test_ld_gabriel_host.py shows that they do)."""
+    res = kernels(gpu, name).run({})
+    cands, _, _ = assert_the_list_and_the_pick(res, name, name)
+    assert cands.shape[0] > 10 * kc.CHUNK
+
+
+@pytest.mark.parametrize("n,window", kc.CHAINS)
+def test_kernels_on_chains_of_tied_candidates(gpu, n, window):
+    """Every span ties and every candidate overlaps the next: up to 256 rounds per chunk, and the order is the slot order under
+    the caller's stable sort alone."""
+    from ld_tools_amd import ops
+    name = f"chain{n}w{window}"
+    res = kernels(gpu, name).run({})
+    assert_the_list_and_the_pick(res, name, name, brute=n <= 601)
+    if window == 1:                                           # without any mirror: (0, 1), (2, 3), ...
+        even = n - n % 2
+        assert np.array_equal(res.block_of[:even], np.arange(even) // 2) and res.n_out.tolist() == [n // 2, n - 1]
+        assert n % 2 == 0 or res.block_of[n - 1] == ops.NO_BLOCK
+
+
+@pytest.mark.parametrize("name", [f"trip{n}" for n in kc.TRIP_SIZES] + ["valid256of512", "valid512of699", "full256", "full512"])
+def test_kernels_at_trip_and_chunk_boundaries(gpu, name):
+    res = kernels(gpu, name).run({})
+    assert_the_list_and_the_pick(res, name, name, brute=True)
+
+
+@pytest.mark.parametrize("name", ["random257", "random513"])
+def test_a_null_keep_is_every_snp_kept_and_null_params_are_the_defaults(gpu, name):
+    n = kc.case(name)["n"]
+    both = kernels(gpu, name, keep=None).run({})
+    assert_the_list_and_the_pick(both, name, f"{name}, no keep", all_kept=True, brute=True)
+    ones = kernels(gpu, name, keep=np.ones(n, dtype=bool))
+    want = ones.run({})
+    for r in (ones.run({}, cand_keep=False), ones.run({}, pick_keep=False), both):      # one call with a null keep, the other without
+        assert all(np.array_equal(a, b) for a, b in zip(r, want))
+    assert not np.array_equal(want.block_of, kc.mirrors(name)[1])
+    # the candidates ignore a keep they do not get; the pick then only marks the SNPs that ITS keep drops
+    mixed = kernels(gpu, name).run({}, cand_keep=False)
+    dropped = ~kc.case(name)["kept"]
+    assert np.array_equal(mixed.cand_span, want.cand_span) and (mixed.block_of[dropped] == 0xFFFFFFFF).all()
+    assert np.array_equal(mixed.block_of[~dropped], want.block_of[~dropped]) and np.array_equal(mixed.n_out, want.n_out)
+    # a null parameter pointer
+    null = kernels(gpu, name).run(None)
+    assert_the_list_and_the_pick(null, name, f"{name}, null params")
+    assert all(np.array_equal(a, b) for a, b in zip(null, kernels(gpu, name).run({})))
+
+
+def test_kernels_with_spans_above_32_bits(gpu):
+    res = kernels(gpu, "scaled513").run(kc.SCALED)
+    cands, _, _ = assert_the_list_and_the_pick(res, "scaled513", "scaled", kc.SCALED, brute=True)
+    base = kernels(gpu, "random513").run({})
+    live = base.cand_span >= 0
+    assert np.array_equal(res.cand_first, base.cand_first) and np.array_equal(res.cand_last, base.cand_last)
+    assert np.array_equal(res.cand_span >= 0, live) and np.array_equal(res.cand_span[live], base.cand_span[live] << 33)
+    assert np.array_equal(res.block_of, base.block_of) and np.array_equal(res.n_out, base.n_out)
+    assert res.cand_span.max() > 1 << 32
+
+
+@pytest.mark.parametrize("name", ["long3000", "wide600"])
+def test_a_relaunch_into_dirty_buffers_changes_nothing(gpu, name):
+    """`used`, `start`, the suffix counts, the column offsets and the list hold the run before, then 0x00, then 0xFF."""
+    k = kc.Kernels(gpu, kc.case(name))
+    first = k.run({})
+    assert_the_list_and_the_pick(first, name, f"{name}, poisoned")
+    fills = [None, 0x00, 0xFF]
+    for fill in fills:
+        if fill is not None:
+            k.refill(fill)
+        again = k.run({})
+        assert all(np.array_equal(a, b) for a, b in zip(again, first)), fill
+    # and after another parameter set's run
+    k.run(kc.OTHER)
+    assert all(np.array_equal(a, b) for a, b in zip(k.run({}), first))
+
+
+def test_no_pair_in_any_window_at_size(gpu):
+    from ld_tools_amd import ops
+    c = kc.case("empty700")
+    res = kernels(gpu, "empty700").run({})
+    assert res.cand_span.size == res.cand_first.size == res.cand_last.size == 0
+    assert np.array_equal(res.block_of, np.where(c["kept"], ops.NO_BLOCK, ops.NOT_KEPT).astype(np.uint32))
+    assert res.n_out.tolist() == [0, 0]
+    assert_the_list_and_the_pick(res, "empty700", "empty")
+
+
+def test_a_foreign_layout_writes_nothing_beyond_the_list(gpu):
+    """The layout of a wider window with bands, list and n_cells of the narrow one: the guards `at >= n_cells` and
+    `slot >= n_cells` of the kernels.  Values are unspecified; nothing past slot n_cells - 1 -- a gap of the carve -- is written."""
+    from ld_tools_amd import ops
+    c = kc.case("random513")
+    wide = ops.band_layout_host(c["pos"], 3 * c["window"])
+    assert int(wide[1][-1]) > 2 * c["n_cells"] and (wide[0] <= c["band_lo"]).all()
+    res = kc.Kernels(gpu, c, layout=wide).run({}, pick=False)      # (run asserts the gaps)
+    assert res.cand_span.shape == (c["n_cells"],) and res.block_of is None
+
+
+def test_the_pick_alone_scans_the_inside_of_a_candidate(gpu):
+    """A list of the caller's: a candidate whose ends are free and whose inside is blocks of the chunk before (kc.nested_list)."""
+    span, first, last, block_of, n_out = kc.nested_list()
+    k = kernels(gpu, "chain600w1")
+    for keep in (True, False):
+        res = k.pick_list(span, first, last, keep=keep)
+        assert np.array_equal(res.block_of, block_of) and res.n_out.tolist() == n_out
+        assert np.array_equal(res.cand_span, span) and np.array_equal(res.cand_first, first) and np.array_equal(res.cand_last, last)

@@ -15,6 +15,7 @@ import pytest
 import ld_ci_exact as cx
 import ld_em_exact as emx
 import ld_gabriel_cases as gc
+import ld_gabriel_kernel_cases as kc
 from ld_tools_amd import _lib, ops
 
 FRAGILE_CAP = 0.005
@@ -155,19 +156,11 @@ def test_candidates_and_pick_equal_the_plain_loops(planted):
 def test_mirrors_on_random_bounds_and_other_parameters(seed):
     """Integer logic only: random bytes for the bounds (strong, recombinant, uninformative and missing pairs in every mix),
     duplicate positions, SNPs not kept, and parameters away from the defaults."""
-    rng = np.random.default_rng(seed)
     n, window = 40, 9000
-    pos = np.cumsum(rng.choice([0, 300, 700, 2500], size=n)).astype(np.int64)
-    kept = rng.random(n) > 0.15
-    band_lo, off = ops.band_layout_host(pos, window)
-    m = int(off[-1])
-    kind = rng.choice(4, size=m, p=[0.55, 0.15, 0.2, 0.1])
-    lo = np.select([kind == 0, kind == 1, kind == 2], [rng.integers(45, 100, m), rng.integers(0, 40, m), rng.integers(0, 70, m)],
-                   ops.NO_CI).astype(np.uint8)
-    hi = np.select([kind == 0, kind == 1, kind == 2], [rng.integers(96, 101, m), rng.integers(40, 90, m), rng.integers(90, 101, m)],
-                   ops.NO_CI).astype(np.uint8)
-    for params in ({}, dict(cuts=(75, 60, 55, 65), max_spans=(1500, 4000, 6000, None), min_informative=(1, 2, 4, 5),
-                            strong_share=(3, 4), cand_cut=60, strong_hi=97, recomb_hi=85)):
+    c = kc.random_bounds(n, window, seed)                  # (the generator of the kernel cases, at its defaults)
+    pos, kept, lo, hi, band_lo, off = (c[k] for k in ("pos", "kept", "lo", "hi", "band_lo", "off"))
+    assert (np.diff(pos) == 0).any() and not kept.all() and (lo == ops.NO_CI).any()
+    for params in ({}, kc.OTHER):
         lo_d, hi_d = gc.dense_from_band(lo, band_lo, off, n), gc.dense_from_band(hi, band_lo, off, n)
         valid, _ = gc.brute_candidates(lo_d, hi_d, pos, kept, window, **params)
         cands = ops.gabriel_candidates_host(lo, hi, pos, kept, window, **params)
@@ -277,3 +270,108 @@ def test_the_operators_refuse_what_the_em_refuses():
         ops.ld_dprime_ci(Panel(), window_snps=2, maf_min=0.7)
     with pytest.raises(_lib.LdxError):
         ops.ld_dprime_ci(Panel(), window_snps=2, keep=[1, 0])
+
+
+# ---- the inputs of the direct kernel tests (tests/ld_gabriel_kernel_cases.py): each must stay in the regime it is there for ------
+def test_settle_profile_on_hand_worked_chunks():
+    """Rounds are counted as the kernel runs them: everybody reads the states of the round before."""
+    # a chain: (0, 1) is accepted in round 1, (1, 2) sees that in round 2 and dies, (2, 3) sees THAT in round 3 ...
+    assert kc.settle_profile([(0, 1, 1), (1, 2, 1), (2, 3, 1), (3, 4, 1)], 5) == (1, 4)
+    # round 1: (0, 5) and (6, 7) have nobody in front that overlaps them; round 2: (1, 2) and (7, 8) die with them
+    assert kc.settle_profile([(0, 5, 9), (1, 2, 3), (6, 7, 3), (7, 8, 3)], 9) == (1, 2)
+    assert kc.settle_profile([(2 * k, 2 * k + 1, 1) for k in range(257)], 514) == (2, 1)
+    assert kc.settle_profile([], 3) == (0, 0)
+    # two chunks: a wide block and the chain (k, k + 1), k < 255, then k = 255, 256, 257.  Chunk 1: the chain's k is settled in
+    # round k + 1, 255 rounds.  Chunk 2: (255, 256) is dead on entry -- (254, 255) was accepted --, (256, 257) is accepted in
+    # round 1 and (257, 258) dies in round 2.
+    cands = [(500, 503, 5)] + [(k, k + 1, 1) for k in range(258)]
+    assert kc.settle_profile(cands, 504) == (2, 255)
+    assert kc.late_rejections(cands, 504) == [(256, 255, 256, 0)]
+    assert kc.pick_order([(1, 2, 5), (0, 3, 5), (4, 9, 7), (0, 2, 5)]).tolist() == [[4, 9, 7], [0, 2, 5], [0, 3, 5], [1, 2, 5]]
+    first, last, cell = kc.column_major(*ops.band_layout_host([0, 1, 2, 3], 2))       # rows 1: (0); 2: (0, 1); 3: (1, 2)
+    assert (first.tolist(), last.tolist(), cell.tolist()) == ([0, 0, 1, 1, 2], [1, 2, 2, 3, 3], [0, 1, 2, 3, 4])
+
+
+@pytest.mark.parametrize("name", ["random257", "random513"])
+def test_the_random_kernel_cases_reach_every_rule(name):
+    c = kc.case(name)
+    assert (np.diff(c["pos"]) == 0).sum() > 20 and 0.75 < c["kept"].mean() < 0.95
+    reasons = set()
+    for params in (None, kc.OTHER):
+        valid, lost, block_of, accepted, overlapped = kc.brute(name, params)
+        cands, mirror_blocks, n_blocks = kc.mirrors(name, params)
+        assert [tuple(v) for v in cands.tolist()] == valid and np.array_equal(mirror_blocks, block_of) and n_blocks == len(accepted)
+        rows = [min(int(c["kept"][f:l + 1].sum()), 5) for f, l, _ in valid]
+        print(f"{name}, {'other' if params else 'default'} parameters: {c['n_cells']} cells, {len(valid)} valid candidates "
+              f"(m = 2, 3, 4, >= 5: {[rows.count(m) for m in (2, 3, 4, 5)]}), {len(accepted)} blocks, {len(overlapped)} overlapped, "
+              f"lost {({k: len(v) for k, v in lost.items()})}")
+        assert set(rows) == {2, 3, 4, 5} and len(valid) >= 100 and len(accepted) >= 15 and overlapped
+        reasons |= {k for k, v in lost.items() if v}
+    assert reasons == {"span", "informative", "share"}
+    if name == "random257":                                 # the window passes 20 kb: the default cap of a two-SNP block bites
+        assert kc.brute(name)[1]["span"] and c["window"] > 20_000
+
+
+def test_the_many_chunk_cases_carry_blocks_from_chunk_to_chunk():
+    for name, least in (("long3000", 10), ("wide600", 20)):
+        c = kc.case(name)
+        cands, _, n_blocks = kc.mirrors(name)
+        order = kc.pick_order(cands)
+        chunks, rounds = kc.settle_profile(order, c["n"])
+        late = kc.late_rejections(order, c["n"])
+        print(f"{name}: {c['n_cells']} cells, {len(cands)} valid candidates in {chunks} chunks, at most {rounds} rounds, "
+              f"{n_blocks} blocks, {len(late)} candidates lost to a block of an earlier chunk")
+        assert chunks >= least and chunks == -(-len(cands) // kc.CHUNK) and n_blocks >= 10
+        assert late and max(rank // kc.CHUNK - was for rank, _, _, was in late) >= least // 2    # ... of many chunks earlier
+    assert kc.case("long3000")["n"] > 11 * kc.CHUNK and kc.case("wide600")["n_cells"] > 30_000
+
+
+@pytest.mark.parametrize("n,window,rounds", [(600, 1, 256), (600, 2, 150), (1500, 3, 100), (601, 1, 256)])
+def test_the_chains_need_deep_settles(n, window, rounds):
+    c = kc.case(f"chain{n}w{window}")
+    cands, block_of, n_blocks = kc.mirrors(f"chain{n}w{window}")
+    assert cands.shape[0] == c["n_cells"] and np.unique(cands[:, 2]).size == window     # every slot valid, spans tie
+    chunks, deepest = kc.settle_profile(kc.pick_order(cands), n)
+    print(f"chain n = {n}, window {window}: {chunks} chunks, {deepest} rounds in the deepest")
+    assert (deepest == 256 if rounds == 256 else rounds <= deepest <= 256) and chunks >= 3
+    if window == 1:                                           # written out without any mirror: the pairs (0, 1), (2, 3), ...
+        want = np.arange(n) // 2
+        assert n_blocks == n // 2 and np.array_equal(block_of[:n - n % 2], want[:n - n % 2])
+        assert n % 2 == 0 or block_of[n - 1] == ops.NO_BLOCK
+
+
+def test_the_trip_cases_sit_on_the_boundaries():
+    assert kc.TRIP_SIZES == (1, 2, 255, 256, 257, 512, 513) and kc.CHUNK == 256
+    for n in kc.TRIP_SIZES:
+        c = kc.case(f"trip{n}")
+        cands, block_of, n_blocks = kc.mirrors(f"trip{n}")
+        assert c["n_cells"] == n - 1 and cands.shape[0] == int((c["kept"][1:] & c["kept"][:-1]).sum())
+        assert n < 255 or (not c["kept"].all() and n_blocks > 50 and (block_of == ops.NO_BLOCK).any())
+    for name, n_cells, n_valid in (("valid256of512", 512, 256), ("valid512of699", 699, 512), ("full256", 256, 256), ("full512", 512, 512)):
+        assert kc.case(name)["n_cells"] == n_cells and kc.mirrors(name)[0].shape[0] == n_valid and kc.case(name)["kept"].all()
+    empty = kc.case("empty700")
+    assert empty["n_cells"] == 0 and (np.diff(empty["pos"]) > 0).all() and not empty["kept"].all() and kc.mirrors("empty700")[2] == 0
+
+
+def test_the_scaled_case_has_spans_above_32_bits():
+    base, scaled = kc.case("random513"), kc.case("scaled513")
+    assert np.array_equal(scaled["band_lo"], base["band_lo"]) and np.array_equal(scaled["off"], base["off"])
+    assert scaled["window"] == base["window"] << 33 < ops.BAND_WINDOW_MAX
+    cands, block_of, n_blocks = kc.mirrors("scaled513", kc.SCALED)
+    want, want_blocks, want_n = kc.mirrors("random513")
+    assert np.array_equal(cands[:, :2], want[:, :2]) and np.array_equal(cands[:, 2], want[:, 2] << 33)
+    assert np.array_equal(block_of, want_blocks) and n_blocks == want_n
+    assert cands[:, 2].max() > 1 << 32 and (cands[:, 2] % (1 << 32) == 0).all()    # the low word says nothing about a span
+    assert (want[:, 2] == 0).any() and np.unique(want[:, 2]).size > 20
+
+
+def test_the_nested_list_needs_the_scan_inside_a_candidate():
+    span, first, last, block_of, n_out = kc.nested_list()
+    live = span >= 0
+    cands = np.stack([first[live], last[live], span[live]], axis=1).astype(np.int64)
+    got, n_blocks = ops.gabriel_pick_host(cands, 600)
+    assert np.array_equal(got, block_of) and [n_blocks, cands.shape[0]] == n_out == [258, 259]
+    order = kc.pick_order(cands)
+    assert kc.late_rejections(order, 600) == [(256, 1, 514, 0)] and kc.settle_profile(order, 600) == (2, 1)
+    assert block_of[1] == 0 and block_of[514] == 257            # both ends of (1, 514) are free when its chunk begins
+    assert live.sum() < live.size and not live[:3].all() and kc.case("chain600w1")["n_cells"] == live.size
