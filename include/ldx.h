@@ -1123,6 +1123,42 @@ int ldx_king_from_counts_dev(size_t m, const uint32_t *N, const uint32_t *HH, co
                              const uint32_t *HETb, float *kin, float *ibs, void *stream);
 int ldx_sample_cells_dev(const uint32_t *counts, uint32_t n_ind, size_t ld, float *kin, float *ibs, size_t ld_out, void *stream);
 
+/* ---- genotype products: the genotype matrix times a narrow dense matrix, both ways, from the bit planes ----------------------
+ * This project's own definition, NOT validated against PLINK 2, GCTA or FastPCA.
+ *
+ * Individuals, called genotypes and kept SNPs are those of "sample relatedness" above.  g_ia in {0, 1, 2} is the ALT dosage of
+ * individual a at SNP i (0 when missing), c_ia in {0, 1} says whether a is called at i; a SNP that is not kept is missing for
+ * everybody.  The operator is A = [G | C]; all arithmetic is on integers:
+ *     forward   y[a][c]  = sum_i ( g_ia w[i][c] + c_ia wc[i][c] )                          int64 [n_ind][k]
+ *     reverse   z[i][c]  = sum_a g_ia u[a][c]      zc[i][c] = sum_a c_ia u[a][c]           int64 [n_snps][k] each
+ * w, wc, u: int32 fixed-point values with |.| <= 2^30 (rows ld_w / ld_u apart), k in 1 .. LDX_GENO_MAX_COLS; wc may be NULL = 0.
+ * The two are adjoint: sum u y == sum (w z + wc zc) exactly.  The sums do not depend on order or slicing: bit-reproducible.
+ *
+ * ldx_geno_matmul_dev: store and tables are what ldx_sample_planes_dev wrote for the same n_snps; row i of w belongs to SNP
+ * snp_begin + i of that store.  accumulate = 0: the call first defines every word y[a][c < k]; accumulate = 1: it adds to what is
+ * there (the stores of a long panel, chunks of a fileset).  Work: (slab of 128 individuals) x (32 columns) x (K slice of SNPs) on
+ * the int8 matrix instruction: the genotype is the A operand, each weight four balanced base-256 digits in [-128, 127] (four
+ * int8 columns), the int32 accumulators of the digits are recombined as sum_l 2^(8 l) acc_l in int64 at the end of the slice
+ * and added to y with 64-bit integer atomics.  An accumulator takes at most 3 x 128 per SNP (g w and c wc), so slice SNPs <=
+ * LDX_GENO_MAX_SLICE_SNPS.  n_slices = 0 lets the library choose; a value of the caller's is used as given (capped at the
+ * K-blocks of 256 SNPs) and refused with LDX_E_ARG when a slice would pass the bound.  `tables` is part of the contract for a
+ * shortcut on slabs without missing calls; the present kernel takes the general path everywhere and does not read it.
+ *
+ * ldx_geno_rmatmul_dev: alt, ref, keep as for ldx_sample_planes_dev.  Work: (slab of 128 SNPs) x (32 columns), K = all
+ * individuals (2 x 128 x LDX_MAX_HAPS / 2 < 2^31), plain stores: every word z[i][c < k], zc[i][c < k] of every SNP is written
+ * (0 for a SNP that is not kept), no memset by the caller.
+ *
+ * Argument rules, checked before any HIP call: a null pointer, an odd n_hap, k outside 1 .. LDX_GENO_MAX_COLS, a leading
+ * dimension below k, n_ind or n_snps = 0, more than LDX_KING_MAX_STORE_SNPS SNPs in a store, an n_slices past the slice bound =
+ * LDX_E_ARG; n_hap > LDX_MAX_HAPS (n_ind > LDX_MAX_HAPS / 2) or a bit plane of 4 GiB or more = LDX_E_UNSUPPORTED. */
+#define LDX_GENO_MAX_COLS 64u
+#define LDX_GENO_MAX_SLICE_SNPS 4194304u    /* 2^22: 3 x 128 x (slice SNPs) < 2^31 */
+int ldx_geno_matmul_dev(const void *store, const uint32_t *tables, uint32_t n_ind, uint32_t n_snps, const int32_t *w,
+                        const int32_t *wc, size_t ld_w, uint32_t k, int64_t *y, size_t ld_y, int accumulate, uint32_t n_slices,
+                        void *stream);
+int ldx_geno_rmatmul_dev(const void *alt, const void *ref, uint32_t n_snps, uint32_t n_hap, const uint8_t *keep,
+                         const int32_t *u, size_t ld_u, uint32_t k, int64_t *z, int64_t *zc, size_t ld_z, void *stream);
+
 /* ---- synthetic panels: deterministic, identical on host and device ------ */
 /* codes int8 [n_snps][ld_codes] receive global SNPs [snp_offset, snp_offset + n_snps) (a rank's
  * shard).  thresholds: per-SNP ALT probability * 2^64 (computed on the host, see

@@ -25,6 +25,8 @@ from .ops import (GabrielBlocks, LDCiBand, dprime_ci_host, gabriel_candidates_ho
                   gabriel_pick_host, ld_ci_from_counts, ld_dprime_ci, ld_gabriel_blocks)
 from .ops import (RelatedPairs, SampleCounts, ibs_cell_host, ibs_matrix, king_cell_host, king_cutoff,  # noqa: F401
                   king_from_counts, king_kinship, sample_counts, sample_counts_host)
+from .ops import (GenoOperator, GenoProduct, SamplePCA, Scores, geno_matmul, geno_matmul_host, geno_quantize,  # noqa: F401
+                  geno_rmatmul, geno_rmatmul_host, polygenic_score, polygenic_score_host, sample_pca, sample_pca_host)
 from .panel import PackedPanel, encode_codes, select_index  # noqa: F401
 from . import plink  # noqa: F401
 from .plink import BedFile, bed_codes_host, codes_bed_host, write_bfile  # noqa: F401
@@ -37,5 +39,7 @@ __all__ = ["PackedPanel", "encode_codes", "select_index", "ld_triangle", "ld_are
            "ld_em_hits", "ld_em_counts", "ld_em_from_counts", "em_host", "ld_em_band", "LDEmBand", "em_snp_stats", "ld_dprime_ci",
            "LDCiBand", "ld_gabriel_blocks", "GabrielBlocks", "ld_ci_from_counts", "dprime_ci_host", "gabriel_candidates_host",
            "gabriel_pick_host", "gabriel_kept_host", "sample_counts", "SampleCounts", "RelatedPairs", "king_kinship", "ibs_matrix",
-           "sample_counts_host", "king_cell_host", "ibs_cell_host", "king_from_counts", "king_cutoff", "LdxError",
+           "sample_counts_host", "king_cell_host", "ibs_cell_host", "king_from_counts", "king_cutoff", "GenoOperator", "GenoProduct",
+           "geno_quantize", "geno_matmul", "geno_rmatmul", "geno_matmul_host", "geno_rmatmul_host", "polygenic_score",
+           "polygenic_score_host", "Scores", "sample_pca", "sample_pca_host", "SamplePCA", "LdxError",
            "version", "plink", "BedFile", "bed_codes_host", "codes_bed_host", "write_bfile"]

@@ -36,6 +36,8 @@ DECAY_MAX_BINS = 1024                    # LDX_DECAY_MAX_BINS
 KING_MIN_SLICE_SNPS = 65536              # LDX_KING_MIN_SLICE_SNPS
 KING_MAX_SLICE_SNPS = 1 << 23            # LDX_KING_MAX_SLICE_SNPS
 KING_MAX_STORE_SNPS = 1 << 27            # LDX_KING_MAX_STORE_SNPS
+GENO_MAX_COLS = 64                       # LDX_GENO_MAX_COLS
+GENO_MAX_SLICE_SNPS = 1 << 22            # LDX_GENO_MAX_SLICE_SNPS
 FLAG_DPRIME_INT0 = 1
 FLAG_RSQ_INT0 = 2
 MEASURES = {"r_square": 0, "d_prime": 1}
@@ -209,6 +211,8 @@ SIGNATURES = {
     "ldx_sample_counts_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _sz, _int, _u64, _u32, _vp]),
     "ldx_king_from_counts_dev": (_int, [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ldx_sample_cells_dev": (_int, [_vp, _u32, _sz, _vp, _vp, _sz, _vp]),
+    "ldx_geno_matmul_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _sz, _u32, _vp, _sz, _int, _u32, _vp]),
+    "ldx_geno_rmatmul_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _sz, _u32, _vp, _vp, _sz, _vp]),
     "ldx_ld_select_workspace_bytes": (_sz, [_u32]),
     "ldx_ld_select_dev": (_int, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ldx_set_area_path": (_int, [_int]),

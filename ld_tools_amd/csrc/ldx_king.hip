@@ -18,6 +18,7 @@
 //     contiguous bytes per half-wave.
 //   * cells_kernel / tuples_kernel: king_cell and ibs_cell, one function each, dense or on a list of tuples.
 #include "ldx_fp4.h"
+#include "ldx_sample_store.h"   // pad_ind, snp_chunks, plane_vecs
 
 namespace ldx {
 namespace king {
@@ -34,13 +35,6 @@ constexpr uint32_t kMaxSliceBlocks = LDX_KING_MAX_SLICE_SNPS / kBlockSnps;
 // every product is 1 (0.5 x 2 or 1 x 1) and of n.z and z.n at most one is set per SNP: an accumulator is at most the slice's SNPs
 static_assert(1ull * LDX_KING_MAX_SLICE_SNPS < (1ull << 24), "a slice's counts must stay exact in fp32");
 static_assert(LDX_KING_MIN_SLICE_SNPS % kBlockSnps == 0 && LDX_KING_MAX_SLICE_SNPS % kBlockSnps == 0, "slices are whole K-blocks");
-
-__host__ __device__ inline uint32_t pad_ind(uint32_t n_ind) { return n_slabs(n_ind) * kSlab; }
-__host__ __device__ inline uint32_t snp_chunks(uint32_t n_snps) { return (uint32_t)(((uint64_t)n_snps + 255u) / 256u * 2u); }
-__host__ __device__ inline size_t plane_vecs(uint32_t n_ind, uint32_t n_snps)
-{
-    return (size_t)n_slabs(n_ind) * snp_chunks(n_snps) * kSlab;
-}
 
 // ---- the cells: functions of the pair's integers alone ----------------------------------------------------------------------
 __device__ __forceinline__ float king_cell(uint32_t, uint32_t HH, uint32_t IBS0, uint32_t HETa, uint32_t HETb)

@@ -10,12 +10,14 @@ dataclasses of the VCF drivers from it, so that their writers write them unchang
     bfile_em_band    -> EmBand for write_em_band
     bfile_blocks     -> GabrielTable for write_gabriel_blocks              PLINK --blocks (Gabriel et al.'s D' interval rule)
     bfile_king       -> KingTable for write_kin0 / write_king_cutoff       PLINK 2 --make-king-table / --king-cutoff
+    bfile_pca        -> PcaTable for write_eigenvec / write_eigenval       PLINK 2 --pca approx
+    bfile_score      -> ScoreTable for write_sscore                        PLINK --score (sums)
 
 A ``.bed`` holds unphased genotype calls: a het is written (ALT, REF) whatever the truth, so the haplotype r of the phased
 operators means nothing here.  Every driver defaults to an unphased form (EM or genotype dosage) and refuses
 ``dosage=False, em=False``.  ``make_bed`` writes a panel, or a subset of a loaded fileset, back as a fileset.
 
-    python -m ld_tools_amd.drivers.plink {ld,clump,prune,l2,blocks,king,make-bed} --bfile P --out O ...
+    python -m ld_tools_amd.drivers.plink {ld,clump,prune,l2,blocks,king,pca,score,make-bed} --bfile P --out O ...
 """
 from __future__ import annotations
 
@@ -346,6 +348,109 @@ def bfile_king(src, out: Optional[str] = None, keep=None, extract=None, prune_r2
     return table
 
 
+def _bfile_and_mask(what: str, src, keep, extract, prune_r2, prune_window_bp, prune_missing, load):
+    if isinstance(src, Bfile):
+        if keep is not None or extract is not None or load:
+            raise LdxError(f"{what}: a loaded fileset takes no keep / extract / load arguments")
+        bf = src
+    else:
+        bf = load_bfile(src, keep=keep, extract=extract, **load)
+    mask = None
+    if prune_r2 is not None:
+        _one_chrom(what, bf)
+        more = {} if prune_missing is None else {"missing": prune_missing}
+        mask = ld_prune(bf.panel, bf.pos, r2=prune_r2, window_bp=prune_window_bp, dosage=True, **more).keep
+    return bf, mask
+
+
+def bfile_pca(src, out: Optional[str] = None, n_pcs: int = 10, keep=None, extract=None, prune_r2: Optional[float] = None,
+              prune_window_bp: int = 250_000, prune_missing: Optional[str] = None, king_cutoff: Optional[float] = None,
+              oversample: int = 10, n_iter: int = 10, seed: int = 0, **load):
+    """drivers/pca.py's ``pca_table`` from a fileset (PLINK 2's --pca approx): the principal components of its individuals, IDs
+    from the ``.fam``.  ``keep`` / ``extract`` / ``prune_r2`` ...: as for bfile_king.  ``king_cutoff``: first drop relatives --
+    ops.king_cutoff on the KING-robust kinship over the same variants -- decompose the unrelated individuals and project the
+    others on their components.  ``out``: a prefix to write ``.eigenvec`` and ``.eigenval`` under.  Returns the PcaTable."""
+    from .pca import pca_table, write_eigenval, write_eigenvec
+    from ..ops import king_cutoff as cutoff_set, sample_counts
+
+    bf, mask = _bfile_and_mask("bfile_pca", src, keep, extract, prune_r2, prune_window_bp, prune_missing, load)
+    unrelated = None
+    if king_cutoff is not None:
+        unrelated, _ = cutoff_set(sample_counts(bf.panel, keep=mask).kinship(), king_cutoff)
+    table = pca_table(bf.panel, list(zip(bf.fid, bf.iid)), n_pcs=min(int(n_pcs), int(bf.panel.n_ind if unrelated is None else
+                                                                                     unrelated.sum())),
+                      keep=mask, unrelated=unrelated, oversample=oversample, n_iter=n_iter, seed=seed)
+    if out is not None:
+        write_eigenvec(out + ".eigenvec", table)
+        write_eigenval(out + ".eigenval", table)
+    return table
+
+
+def read_score_file(path: str) -> tuple:
+    """(ids, alleles, weights float64 [lines, k]) of a whitespace table: variant ID, allele, one or more weights per line; a first
+    line whose third field is no number is a header."""
+    ids, alleles, rows = [], [], []
+    with open(path) as f:
+        for no, line in enumerate(f):
+            parts = line.split()
+            if not parts:
+                continue
+            if len(parts) < 3:
+                raise LdxError(f"{path}: a line with fewer than 3 fields")
+            try:
+                vals = [float(v) for v in parts[2:]]
+            except ValueError:
+                if no == 0:
+                    continue
+                raise LdxError(f"{path}: line {no + 1}: a weight that is no number") from None
+            if rows and len(vals) != len(rows[0]):
+                raise LdxError(f"{path}: line {no + 1}: {len(vals)} weights beside {len(rows[0])}")
+            ids.append(parts[0])
+            alleles.append(parts[1])
+            rows.append(vals)
+    if not rows:
+        raise LdxError(f"{path}: no weight line")
+    return ids, alleles, np.asarray(rows, dtype=np.float64)
+
+
+def bfile_score(src, weights, out: Optional[str] = None, impute: str = "mean", keep=None, extract=None, **load):
+    """drivers/pca.py's ``score_table`` from a fileset (PLINK's --score sums): ``weights`` is the path of a score file
+    (read_score_file) or its (ids, alleles, weights) triple.  A line counts when its ID is a variant of the fileset (the first of a
+    repeated ID) and its allele one of the variant's two; a later line of the same variant replaces an earlier one.  A weight w
+    for the allele that is code 1 is beta = w; for the other allele beta = -w with the constant 2 w per counted genotype
+    (its dosage is 2 - g).  Only matched variants are scored (ALLELE_CT counts them).  ``out``: a prefix to write ``.sscore``
+    under.  Returns the ScoreTable, ``n_matched`` / ``n_lines`` set."""
+    from .pca import score_table, write_sscore
+
+    bf, _ = _bfile_and_mask("bfile_score", src, keep, extract, None, 0, None, load)
+    ids, alleles, w = read_score_file(weights) if isinstance(weights, str) else weights
+    w = np.asarray(w, dtype=np.float64)
+    w = w[:, None] if w.ndim == 1 else w
+    if not (len(ids) == len(alleles) == w.shape[0]):
+        raise LdxError("bfile_score: ids, alleles and weights differ in length")
+    where = {}
+    for k, name in enumerate(bf.ids):
+        where.setdefault(name, k)
+    beta, offset = np.zeros((bf.n, w.shape[1])), np.zeros((bf.n, w.shape[1]))
+    matched, n_matched = np.zeros(bf.n, dtype=bool), 0
+    alts, refs = bf.alts, bf.refs
+    for name, allele, row in zip(ids, alleles, w):
+        k = where.get(name)
+        if k is None or allele not in (alts[k], refs[k]):
+            continue
+        n_matched += 1
+        matched[k] = True
+        beta[k], offset[k] = (row, 0.0) if allele == alts[k] else (-row, 2.0 * row)
+    if not n_matched:
+        raise LdxError("bfile_score: no weight line names a variant of the fileset and one of its alleles")
+    table = score_table(bf.panel, list(zip(bf.fid, bf.iid)), beta, keep=matched, impute=impute,
+                        offset=offset if offset.any() else None)
+    table.n_matched, table.n_lines = n_matched, len(ids)
+    if out is not None:
+        write_sscore(out + ".sscore", table)
+    return table
+
+
 def make_bed(prefix_out, src, snps=None, individuals=None, bim: Optional[dict] = None, fam: Optional[dict] = None,
              alt: Optional[str] = None) -> List[str]:
     """Write a fileset.  ``src``: a ``Bfile`` -- ``snps`` / ``individuals`` (index arrays or masks over ITS variants and
@@ -452,6 +557,16 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--prune-r2", type=float, default=None, help="count over the variants LD pruning keeps at this r^2")
     p.add_argument("--prune-window-kb", type=float, default=250.0)
     p.add_argument("--missing", choices=("pairwise",), default=None, help="how the pruning treats missing calls")
+    p = common("pca", "principal components of the individuals (.eigenvec, .eigenval)")
+    p.add_argument("--pca", type=int, default=10, dest="n_pcs", help="the number of components")
+    p.add_argument("--king-cutoff", type=float, default=None, help="decompose a maximal unrelated set, project the others")
+    p.add_argument("--prune-r2", type=float, default=None, help="use the variants LD pruning keeps at this r^2")
+    p.add_argument("--prune-window-kb", type=float, default=250.0)
+    p.add_argument("--missing", choices=("pairwise",), default=None, help="how the pruning treats missing calls")
+    p.add_argument("--seed", type=int, default=0)
+    p = common("score", "polygenic score sums of the individuals (.sscore)")
+    p.add_argument("--score", required=True, help="weights: variant ID, allele, weight per line")
+    p.add_argument("--no-mean-imputation", action="store_true", help="a missing genotype adds nothing (default: 2 x frequency)")
     common("make-bed", "write the selected variants and individuals as a new fileset")
     return ap
 
@@ -489,6 +604,14 @@ def main(argv=None) -> int:
         table = bfile_king(bf, out=a.out, prune_r2=a.prune_r2, prune_window_bp=int(a.prune_window_kb * 1000),
                            prune_missing=a.missing, kin_min=a.king_table_filter, cutoff=a.king_cutoff, matrix=a.make_king)
         print(table.counts.n_ind, "individuals,", table.counts.n_snps, "variants ->", a.out + ".kin0")
+    elif a.command == "pca":
+        table = bfile_pca(bf, out=a.out, n_pcs=a.n_pcs, prune_r2=a.prune_r2, prune_window_bp=int(a.prune_window_kb * 1000),
+                          prune_missing=a.missing, king_cutoff=a.king_cutoff, seed=a.seed)
+        print(int(table.in_pca.sum()), "of", len(table.iid), "individuals decomposed,", table.pca.n_used, "variants ->",
+              a.out + ".eigenvec", a.out + ".eigenval")
+    elif a.command == "score":
+        table = bfile_score(bf, a.score, out=a.out, impute="zero" if a.no_mean_imputation else "mean")
+        print(table.n_matched, "of", table.n_lines, "weight lines matched ->", a.out + ".sscore")
     else:
         print(*make_bed(a.out, bf))
     return 0

@@ -3641,6 +3641,426 @@ def king_cutoff(kin, cutoff: float) -> Tuple[np.ndarray, np.ndarray]:
     return keep, np.where(keep, -1, owner).astype(np.int64)
 
 
+# --------------------------------------------------------------------------- genotype products, sample PCA, polygenic scores
+GENO_SCALE_BITS = 30                           # a quantised weight is rint(2^30 x 2^-e): |q| <= 2^30
+
+
+def _as_f64_2d(x, what: str) -> torch.Tensor:
+    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+    if t.is_complex() or t.dtype == torch.bool:
+        raise _lib.LdxError(f"{what} must be real (got {t.dtype})")
+    if t.ndim != 2:
+        raise _lib.LdxError(f"{what} must have shape [n, k], got {tuple(t.shape)}")
+    return t
+
+
+def geno_quantize(*mats, device=None):
+    """Float matrices [n, k] that share column exponents, as the fixed-point weights of the genotype products: e_c is the
+    smallest integer with max |x[:, c]| 2^-e_c <= 1 over all matrices given (matvec_rhs's rule; an all-zero column keeps e = 0)
+    and q = rint(2^30 x 2^-e) as int32, round-half-even, every step in fp64 (the scaling by a power of two is exact).  Returns
+    (list of int32 tensors, e int64 [k]) on ``device`` (default: where the first matrix is; numpy input stays on the host)."""
+    if not mats:
+        raise _lib.LdxError("geno_quantize: no matrix given")
+    ts = [_as_f64_2d(m, "geno_quantize: a matrix") for m in mats]
+    dev = torch.device(device) if device is not None else ts[0].device
+    ts = [t.to(dev).to(torch.float64) for t in ts]
+    n, k = ts[0].shape
+    if any(t.shape[1] != k for t in ts):
+        raise _lib.LdxError("geno_quantize: the matrices differ in their number of columns")
+    if not 1 <= k <= _lib.GENO_MAX_COLS:
+        raise _lib.LdxError(f"geno_quantize: 1 to {_lib.GENO_MAX_COLS} columns per call (got {k})")
+    big = torch.zeros(k, dtype=torch.float64, device=dev)
+    for t in ts:
+        if not bool(torch.isfinite(t).all().item()):
+            raise _lib.LdxError("geno_quantize: the matrices must be finite")
+        if t.shape[0]:
+            big = torch.maximum(big, t.abs().amax(dim=0))
+    mant, e = torch.frexp(big)                              # big = mant 2^e, mant in [0.5, 1)
+    e = e.to(torch.int64) - (mant == 0.5).to(torch.int64)   # the smallest e with big 2^-e <= 1
+    e = torch.where(big > 0, e, torch.zeros_like(e)).clamp(-990, 1000)
+    scale = _pow2(GENO_SCALE_BITS - e)
+    return [torch.round(t * scale).to(torch.int32).contiguous() for t in ts], e
+
+
+@dataclass
+class GenoProduct:
+    """A genotype product (GenoOperator): ``sums``, the int64 device tensor the kernel wrote, in units of 2^(e_c - 30), and
+    ``exps``, device int64 [k], the columns' exponents."""
+
+    sums: torch.Tensor
+    exps: torch.Tensor
+
+    def values(self) -> torch.Tensor:
+        """float64 device tensor shaped like ``sums``: sums 2^(e - 30)."""
+        return self.sums.to(torch.float64) * _pow2(self.exps - GENO_SCALE_BITS)
+
+
+def _geno_weights(what: str, q, rows: int, dev, k: Optional[int] = None) -> torch.Tensor:
+    t = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q))
+    if t.dtype != torch.int32 or t.ndim != 2 or t.shape[0] != rows or not 1 <= t.shape[1] <= _lib.GENO_MAX_COLS:
+        raise _lib.LdxError(f"{what}: int32 weights [{rows}, k], k in 1..{_lib.GENO_MAX_COLS}, needed; got {t.dtype} {tuple(t.shape)}")
+    if k is not None and t.shape[1] != k:
+        raise _lib.LdxError(f"{what}: {t.shape[1]} columns beside {k}")
+    t = t.to(dev).contiguous()
+    lo, hi = torch.aminmax(t)
+    if int(lo.item()) < -(1 << GENO_SCALE_BITS) or int(hi.item()) > (1 << GENO_SCALE_BITS):
+        raise _lib.LdxError(f"{what}: the weights must lie in -2^30 .. 2^30")
+    return t
+
+
+class GenoOperator:
+    """The operator A = [G | C] of a panel over the SNPs that pass ``keep`` (include/ldx.h, "genotype products"): G the ALT
+    dosages of the individuals (0 where missing), C the called flags.  The individual-major store(s) of the forward product are
+    built once here, ``store_snps`` SNPs each (ldx_sample_planes_dev), and kept, so that an iteration does not transpose the
+    panel again; the reverse product reads the panel's own planes.  All sums are exact integers."""
+
+    def __init__(self, panel: PackedPanel, keep=None, store_snps: int = SAMPLE_STORE_SNPS):
+        require_gpu()
+        if panel.n_hap % 2:
+            raise _lib.LdxError(f"GenoOperator: n_hap must be even (haplotypes 2a and 2a + 1 are individual a), got {panel.n_hap}")
+        store_snps = int(store_snps)
+        if not (1 <= store_snps <= _lib.KING_MAX_STORE_SNPS):
+            raise _lib.LdxError(f"GenoOperator: store_snps must lie in 1..{_lib.KING_MAX_STORE_SNPS}")
+        self.panel, self.n_ind, self.n_snps, self.device = panel, panel.n_ind, panel.n_snps, panel.device
+        k = _keep_mask(keep, panel.n_snps)
+        self._keep_d = None if k is None else torch.from_numpy(k.astype(np.uint8)).to(self.device)
+        self._stores = []
+        for begin in range(0, self.n_snps, store_snps):
+            count = min(store_snps, self.n_snps - begin)
+            store = torch.empty(lib.ldx_sample_planes_bytes(self.n_ind, count), dtype=torch.uint8, device=self.device)
+            tables = torch.empty(lib.ldx_sample_tables_bytes(self.n_ind) // 4, dtype=torch.int32, device=self.device)
+            check(lib.ldx_sample_planes_dev(panel.alt.data_ptr(), panel.ref.data_ptr(), self.n_snps, panel.n_hap, _ptr(self._keep_d),
+                                            begin, count, store.data_ptr(), tables.data_ptr(), _stream_ptr()), "ldx_sample_planes_dev")
+            self._stores.append((begin, count, store, tables))
+
+    def called_counts(self) -> torch.Tensor:
+        """int64 device tensor [n_ind]: the kept SNPs at which each individual is called (the stores' tables)."""
+        total = torch.zeros(self.n_ind, dtype=torch.int64, device=self.device)
+        for _, _, _, tables in self._stores:
+            total += _u32_to_i64(tables[:self.n_ind])
+        return total
+
+    def matmul_q(self, q_w, q_wc=None, n_slices: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """y = G q_w + C q_wc on raw int32 weights [n_snps, k]: int64 device tensor [n_ind, k].  ``out``: an earlier result to
+        add to.  ``n_slices``: the K slices per store (None: the library's choice)."""
+        w = _geno_weights("matmul_q", q_w, self.n_snps, self.device)
+        k = int(w.shape[1])
+        wc = None if q_wc is None else _geno_weights("matmul_q", q_wc, self.n_snps, self.device, k)
+        if out is None:
+            y, accumulate = torch.empty((self.n_ind, k), dtype=torch.int64, device=self.device), 0
+        else:
+            if out.dtype != torch.int64 or tuple(out.shape) != (self.n_ind, k) or not out.is_contiguous() or out.device != self.device:
+                raise _lib.LdxError(f"matmul_q: out must be a contiguous int64 [{self.n_ind}, {k}] tensor on {self.device}")
+            y, accumulate = out, 1
+        for begin, count, store, tables in self._stores:
+            off = begin * k * 4
+            check(lib.ldx_geno_matmul_dev(store.data_ptr(), tables.data_ptr(), self.n_ind, count, w.data_ptr() + off,
+                                          None if wc is None else wc.data_ptr() + off, k, k, y.data_ptr(), k, accumulate,
+                                          int(n_slices or 0), _stream_ptr()), "ldx_geno_matmul_dev")
+            accumulate = 1
+        return y
+
+    def rmatmul_q(self, q_u) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(z, zc) = (G^T q_u, C^T q_u) on raw int32 weights [n_ind, k]: two int64 device tensors [n_snps, k]; the rows of SNPs
+        that are not kept are 0."""
+        u = _geno_weights("rmatmul_q", q_u, self.n_ind, self.device)
+        k = int(u.shape[1])
+        z = torch.empty((self.n_snps, k), dtype=torch.int64, device=self.device)
+        zc = torch.empty((self.n_snps, k), dtype=torch.int64, device=self.device)
+        p = self.panel
+        check(lib.ldx_geno_rmatmul_dev(p.alt.data_ptr(), p.ref.data_ptr(), self.n_snps, p.n_hap, _ptr(self._keep_d), u.data_ptr(), k, k,
+                                       z.data_ptr(), zc.data_ptr(), k, _stream_ptr()), "ldx_geno_rmatmul_dev")
+        return z, zc
+
+    def matmul(self, W, Wc=None, n_slices: Optional[int] = None) -> GenoProduct:
+        """G W + C Wc for float matrices [n_snps, k] (geno_quantize: they share the column exponents)."""
+        qs, e = geno_quantize(*([W] if Wc is None else [W, Wc]), device=self.device)
+        return GenoProduct(self.matmul_q(qs[0], None if Wc is None else qs[1], n_slices), e)
+
+    def rmatmul(self, U) -> Tuple[GenoProduct, GenoProduct]:
+        """(G^T U, C^T U) for a float matrix [n_ind, k]."""
+        (q,), e = geno_quantize(U, device=self.device)
+        z, zc = self.rmatmul_q(q)
+        return GenoProduct(z, e), GenoProduct(zc, e)
+
+    def stats(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(n, a): per SNP the called individuals and the ALT allele sum over them, exact int64 device tensors [n_snps] (0 for
+        a SNP that is not kept): the reverse product of a column of ones."""
+        z, zc = self.rmatmul_q(torch.ones((self.n_ind, 1), dtype=torch.int32, device=self.device))
+        return zc[:, 0].contiguous(), z[:, 0].contiguous()
+
+
+def geno_matmul(panel: PackedPanel, W, Wc=None, keep=None) -> GenoProduct:
+    """One-shot ``GenoOperator(panel, keep).matmul(W, Wc)``."""
+    return GenoOperator(panel, keep).matmul(W, Wc)
+
+
+def geno_rmatmul(panel: PackedPanel, U, keep=None) -> Tuple[GenoProduct, GenoProduct]:
+    """One-shot ``GenoOperator(panel, keep).rmatmul(U)``."""
+    return GenoOperator(panel, keep).rmatmul(U)
+
+
+def geno_planes_host(codes, keep=None) -> Tuple[np.ndarray, np.ndarray]:
+    """(g, c) int64 [n_snps, n_ind] from the allele codes [n_snps, n_hap] (1 = ALT, 0 = REF, anything else = missing): the
+    dosage of the called genotypes and the called flag; both 0 at a SNP that ``keep`` drops."""
+    x = np.asarray(codes)
+    if x.ndim != 2 or x.shape[1] % 2 or x.shape[1] == 0:
+        raise _lib.LdxError(f"codes [n_snps, n_hap] with an even n_hap needed, got shape {x.shape}")
+    h0, h1 = x[:, 0::2], x[:, 1::2]
+    called = ((h0 == 0) | (h0 == 1)) & ((h1 == 0) | (h1 == 1))
+    k = _keep_mask(keep, x.shape[0])
+    if k is not None:
+        called = called & k[:, None]
+    g = ((h0 == 1).astype(np.int64) + (h1 == 1).astype(np.int64)) * called
+    return g, called.astype(np.int64)
+
+
+def _host_weights(what: str, q, rows: int) -> np.ndarray:
+    q = q.cpu().numpy() if isinstance(q, torch.Tensor) else np.asarray(q)
+    if q.ndim != 2 or q.shape[0] != rows or q.dtype.kind not in "iu":
+        raise _lib.LdxError(f"{what}: integer weights [{rows}, k] needed, got {q.dtype} {q.shape}")
+    # 3 x 2^30 per SNP or individual: int64 sums are exact below 2^63 / (3 x 2^30) rows; Python ints beyond
+    return q.astype(np.int64) if rows < (1 << 63) // (3 << GENO_SCALE_BITS) else q.astype(object)
+
+
+def geno_matmul_host(codes, q_w, q_wc=None, keep=None) -> np.ndarray:
+    """Host mirror of GenoOperator.matmul_q in numpy integers: [n_ind, k]."""
+    g, c = geno_planes_host(codes, keep)
+    y = g.T @ _host_weights("geno_matmul_host", q_w, g.shape[0])
+    if q_wc is not None:
+        y = y + c.T @ _host_weights("geno_matmul_host", q_wc, g.shape[0])
+    return y
+
+
+def geno_rmatmul_host(codes, q_u, keep=None) -> Tuple[np.ndarray, np.ndarray]:
+    """Host mirror of GenoOperator.rmatmul_q in numpy integers: (z, zc), [n_snps, k] each."""
+    g, c = geno_planes_host(codes, keep)
+    u = _host_weights("geno_rmatmul_host", q_u, g.shape[1])
+    return g @ u, c @ u
+
+
+class _GenoEngine:
+    """What polygenic_score and sample_pca need of a panel: the two integer products and the torch device of the elementwise
+    steps between them.  The device and the host form differ in nothing else, which is what makes them agree bit for bit."""
+
+    device: torch.device
+    n_ind: int
+    n_snps: int
+
+    def stats(self) -> Tuple[np.ndarray, np.ndarray]:
+        z, zc = self.rmatmul_q(torch.ones((self.n_ind, 1), dtype=torch.int32, device=self.device))
+        return zc[:, 0].cpu().numpy(), z[:, 0].cpu().numpy()
+
+
+class _DeviceEngine(_GenoEngine):
+    def __init__(self, panel: PackedPanel, keep=None):
+        self.op = GenoOperator(panel, keep)
+        self.device, self.n_ind, self.n_snps = panel.device, panel.n_ind, panel.n_snps
+        self.matmul_q, self.rmatmul_q = self.op.matmul_q, self.op.rmatmul_q
+
+    def called(self) -> np.ndarray:
+        return self.op.called_counts().cpu().numpy()
+
+
+class _HostEngine(_GenoEngine):
+    def __init__(self, codes, keep=None):
+        self.g, self.c = geno_planes_host(codes, keep)
+        self.device, (self.n_snps, self.n_ind) = torch.device("cpu"), self.g.shape
+
+    def matmul_q(self, q_w, q_wc=None):
+        y = self.g.T @ _host_weights("matmul_q", q_w, self.n_snps)
+        if q_wc is not None:
+            y = y + self.c.T @ _host_weights("matmul_q", q_wc, self.n_snps)
+        return torch.from_numpy(np.ascontiguousarray(y.astype(np.int64)))
+
+    def rmatmul_q(self, q_u):
+        u = _host_weights("rmatmul_q", q_u, self.n_ind)
+        return tuple(torch.from_numpy(np.ascontiguousarray((m @ u).astype(np.int64))) for m in (self.g, self.c))
+
+    def called(self) -> np.ndarray:
+        return self.c.sum(axis=0)
+
+
+def _engine(what: str, source, keep) -> _GenoEngine:
+    if isinstance(source, PackedPanel):
+        require_gpu()
+        if source.n_hap % 2:
+            raise _lib.LdxError(f"{what}: n_hap must be even (haplotypes 2a and 2a + 1 are individual a), got {source.n_hap}")
+        return _DeviceEngine(source, keep)
+    return _HostEngine(source, keep)
+
+
+def _scale_sums(y: np.ndarray, e: np.ndarray) -> np.ndarray:
+    """float64(y) 2^(e - 30) on the host: one conversion, one exact scaling."""
+    return y.astype(np.float64) * np.ldexp(1.0, (e - GENO_SCALE_BITS).astype(np.int64))[None, :]
+
+
+def _allele_freq(n: np.ndarray, a: np.ndarray) -> np.ndarray:
+    """p = a / (2 n) in fp64 where n > 0, else 0: one division."""
+    return np.where(n > 0, a.astype(np.float64) / np.where(n > 0, 2.0 * n.astype(np.float64), 1.0), 0.0)
+
+
+@dataclass
+class Scores:
+    """polygenic_score's result: ``sum`` float64 [n_ind, k], the score sums; ``allele_ct`` int64 [n_ind], twice the kept SNPs
+    the individual is called at; ``sums`` / ``exps``: the integers behind ``sum`` (sum = sums 2^(exps - 30))."""
+
+    sum: np.ndarray
+    allele_ct: np.ndarray
+    sums: np.ndarray
+    exps: np.ndarray
+
+    @property
+    def avg(self) -> np.ndarray:
+        """float64 [n_ind, k]: sum / allele_ct (NaN for an individual without a call)."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return self.sum / self.allele_ct[:, None].astype(np.float64)
+
+
+def _score(eng: _GenoEngine, beta, impute: str, offset=None) -> Scores:
+    if impute not in ("mean", "zero"):
+        raise _lib.LdxError(f"polygenic_score: impute must be 'mean' or 'zero' (got {impute!r})")
+
+    def weights(x, what):
+        x = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        x = np.asarray(x, dtype=np.float64)
+        x = x[:, None] if x.ndim == 1 else x
+        if x.ndim != 2 or x.shape[0] != eng.n_snps:
+            raise _lib.LdxError(f"polygenic_score: {what} must have shape [n_snps] or [n_snps, k] (n_snps = {eng.n_snps}), got {x.shape}")
+        return x
+
+    b = weights(beta, "beta")
+    o = None if offset is None else weights(offset, "offset")
+    if o is not None and o.shape != b.shape:
+        raise _lib.LdxError(f"polygenic_score: offset {o.shape} beside beta {b.shape}")
+    if impute == "zero":   # sum_i c (g b + o)
+        qs, e = geno_quantize(*([b] if o is None else [b, o]), device=eng.device)
+        y = eng.matmul_q(qs[0], None if o is None else qs[1]).cpu().numpy()
+    else:
+        n, a = eng.stats()
+        tp = 2.0 * _allele_freq(n, a)
+        m = tp[:, None] * b
+        # sum_i c (g b + o) + (1 - c) (2p b + o)  =  G b - C (2p b) + sum_i (2p b + o), i over the kept SNPs with calls (p = 0 elsewhere)
+        qs, e = geno_quantize(*([b, m] if o is None else [b, m, np.where((n > 0)[:, None], o, 0.0)]), device=eng.device)
+        const = qs[1].to(torch.int64).sum(dim=0) if o is None else (qs[1].to(torch.int64) + qs[2].to(torch.int64)).sum(dim=0)
+        y = (eng.matmul_q(qs[0], -qs[1]) + const[None, :]).cpu().numpy()
+    e = e.cpu().numpy()
+    return Scores(_scale_sums(y, e), 2 * eng.called().astype(np.int64), y, e)
+
+
+def polygenic_score(panel: PackedPanel, beta, keep=None, impute: str = "mean", offset=None) -> Scores:
+    """Per-SNP weights applied to the individuals of ``panel`` over the SNPs that pass ``keep`` (PLINK's --score sums; this
+    project's own definition).  ``beta``: [n_snps] or [n_snps, k], k <= 64.  ``impute="zero"``: sum = G beta, a missing genotype
+    adds nothing; ``"mean"``: a missing genotype of a kept SNP with calls counts as 2 p_i, p_i = a_i / (2 n_i) from
+    GenoOperator.stats().  ``offset`` (shaped like beta; default none): a constant per SNP that every genotype counted at it adds --
+    a weight given for the REF allele is beta = -w, offset = 2 w.  Everything is summed on integers (geno_quantize, the forward
+    product on the matrix cores) and scaled once; polygenic_score_host gives the same bits."""
+    return _score(_engine("polygenic_score", panel, keep), beta, impute, offset)
+
+
+def polygenic_score_host(codes, beta, keep=None, impute: str = "mean", offset=None) -> Scores:
+    """Host mirror of polygenic_score on the allele codes [n_snps, n_hap]: the same integers from numpy products."""
+    return _score(_HostEngine(codes, keep), beta, impute, offset)
+
+
+@dataclass
+class SamplePCA:
+    """sample_pca's result: ``eigenvalues`` float64 [n_pcs] (descending) and ``eigenvectors`` float64 [n_ind, n_pcs] of the
+    GRM X X^T / M, each vector with its largest-magnitude entry positive; ``n_used`` = M, the SNPs with a finite weight;
+    ``loadings`` float64 [n_snps, n_pcs] = X^T u_j / sqrt(M lambda_j), or None; ``two_p`` and ``inv_sd``: 2 p_i and
+    1 / sqrt(v_i) per SNP (0 for a SNP outside the M), which ``project`` applies to other individuals."""
+
+    eigenvalues: np.ndarray
+    eigenvectors: np.ndarray
+    n_used: int
+    loadings: Optional[np.ndarray]
+    two_p: np.ndarray
+    inv_sd: np.ndarray
+
+    def project(self, other, keep=None) -> np.ndarray:
+        """float64 [n_other, n_pcs]: the coordinates of the individuals of ``other`` -- a PackedPanel (device product) or allele
+        codes [n_snps, n_hap] (host product), over the same SNPs -- on the components, with this result's p and v: one forward
+        product of the scaled loadings; a training individual gets back its eigenvector entries up to the method's error."""
+        if self.loadings is None:
+            raise _lib.LdxError("SamplePCA.project needs the loadings: run sample_pca(..., loadings=True)")
+        eng = _engine("SamplePCA.project", other, keep)
+        if eng.n_snps != self.loadings.shape[0]:
+            raise _lib.LdxError(f"SamplePCA.project: {eng.n_snps} SNPs beside the loadings' {self.loadings.shape[0]}")
+        lam = np.where(self.eigenvalues > 0, self.eigenvalues, np.inf)
+        w = (self.loadings * self.inv_sd[:, None]) / np.sqrt(self.n_used * lam)[None, :]
+        (q_w, q_c), e = geno_quantize(w, -(self.two_p[:, None] * w), device=eng.device)
+        return _scale_sums(eng.matmul_q(q_w, q_c).cpu().numpy(), e.cpu().numpy())
+
+
+def _pca(eng: _GenoEngine, n_pcs: int, oversample: int, n_iter: int, seed: int, loadings: bool) -> SamplePCA:
+    n_ind = eng.n_ind
+    if not 1 <= n_pcs <= n_ind:
+        raise _lib.LdxError(f"sample_pca: n_pcs must lie in 1..n_ind = {n_ind} (got {n_pcs})")
+    L = min(n_ind, n_pcs + int(oversample))
+    if oversample < 0 or n_iter < 0 or not 1 <= L <= _lib.GENO_MAX_COLS:
+        raise _lib.LdxError(f"sample_pca: n_pcs + oversample must lie in 1..{_lib.GENO_MAX_COLS} and n_iter be >= 0")
+    # 1. the SNP weights, in numpy fp64
+    n, a = eng.stats()
+    p = _allele_freq(n, a)
+    v = 2.0 * p * (1.0 - p)
+    ok = (n > 0) & (v > 0)
+    w = np.where(ok, 1.0 / np.where(ok, v, 1.0), 0.0)
+    M = int(np.count_nonzero(w > 0))
+    if M == 0:
+        raise _lib.LdxError("sample_pca: no polymorphic SNP with calls")
+    tp = 2.0 * p
+    tp_d = torch.from_numpy(tp).to(eng.device)[:, None]
+    w_d = torch.from_numpy(w).to(eng.device)[:, None]
+
+    def reverse(Q):   # Zs - tp o Zcs, every operation rounded once
+        (q,), e = geno_quantize(Q, device=eng.device)
+        Z, Zc = eng.rmatmul_q(q)
+        s = _pow2(e - GENO_SCALE_BITS)[None, :]
+        Zs, Zcs = Z.to(torch.float64) * s, Zc.to(torch.float64) * s
+        return Zs - tp_d * Zcs
+
+    def apply(Q):     # 3. H = K Q
+        T = reverse(Q) * w_d
+        (q_t, q_c), e2 = geno_quantize(T, -(tp_d * T), device=eng.device)
+        Y = eng.matmul_q(q_t, q_c).cpu().numpy()
+        return _scale_sums(Y, e2.cpu().numpy()) / M
+
+    # 2. the start
+    Q = np.linalg.qr(np.random.default_rng(seed).standard_normal((n_ind, L)))[0]
+    for _ in range(n_iter):                                   # 4.
+        Q = np.linalg.qr(apply(Q))[0]
+    H = apply(Q)                                              # 5.
+    QtH = Q.T @ H
+    lam, S = np.linalg.eigh((QtH + QtH.T) / 2.0)
+    top = np.argsort(-lam, kind="stable")[:n_pcs]
+    lam, U = lam[top], Q @ S[:, top]
+    big = np.argmax(np.abs(U), axis=0)                        # the first largest-magnitude entry of each vector
+    U = U * np.where(U[big, np.arange(U.shape[1])] < 0, -1.0, 1.0)[None, :]
+    rsv = np.sqrt(w)
+    load = None
+    if loadings:                                              # 6.
+        D = reverse(U).cpu().numpy()
+        load = (D * rsv[:, None]) / np.sqrt(M * np.where(lam > 0, lam, np.inf))[None, :]
+    return SamplePCA(lam, U, M, load, tp, rsv)
+
+
+def sample_pca(panel: PackedPanel, n_pcs: int = 10, keep=None, oversample: int = 10, n_iter: int = 10, seed: int = 0,
+               loadings: bool = False) -> SamplePCA:
+    """The top ``n_pcs`` principal components of the individuals of ``panel`` by randomised subspace iteration on the GRM
+    K = X X^T / M, X_ia = c_ia (g_ia - 2 p_i) / sqrt(2 p_i (1 - p_i)) over the M kept SNPs with calls and 0 < p < 1 (this
+    project's own definition; FastPCA's scheme).  K is never formed: one application is a reverse and a forward genotype
+    product on the matrix cores, both on integers, with one elementwise fp64 step on the device between them; the
+    n_ind x (n_pcs + oversample) algebra (QR, the small eigenproblem) is numpy on the host.  sample_pca_host runs the same
+    steps with host products and gives the same bits."""
+    return _pca(_engine("sample_pca", panel, keep), int(n_pcs), int(oversample), int(n_iter), seed, loadings)
+
+
+def sample_pca_host(codes, n_pcs: int = 10, keep=None, oversample: int = 10, n_iter: int = 10, seed: int = 0,
+                    loadings: bool = False) -> SamplePCA:
+    """Host mirror of sample_pca on the allele codes [n_snps, n_hap]."""
+    return _pca(_HostEngine(codes, keep), int(n_pcs), int(oversample), int(n_iter), seed, loadings)
+
+
 # --------------------------------------------------------------------------- instrumentation
 def probe_andpop(blocks: int, threads: int, iters: int) -> torch.Tensor:
     sink = torch.empty(blocks * threads, dtype=torch.int32, device=torch.device("cuda", torch.cuda.current_device()))
