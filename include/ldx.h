@@ -1159,6 +1159,54 @@ int ldx_geno_matmul_dev(const void *store, const uint32_t *tables, uint32_t n_in
 int ldx_geno_rmatmul_dev(const void *alt, const void *ref, uint32_t n_snps, uint32_t n_hap, const uint8_t *keep,
                          const int32_t *u, size_t ld_u, uint32_t k, int64_t *z, int64_t *zc, size_t ld_z, void *stream);
 
+/* ---- association scan: per SNP the least-squares fit of quantitative phenotypes on the genotype, an intercept and covariates --
+ * This project's own definition (what PLINK 2 --glm reports for a quantitative trait: BETA, SE, T_STAT, P), NOT validated
+ * against PLINK 2.  It differs from PLINK wherever a call is missing: a missing genotype is set to the SNP's MEAN over its
+ * called individuals (as regenie, BOLT-LMM and fastGWA do), PLINK refits each SNP over its called individuals.
+ *
+ * Individuals, called genotypes and kept SNPs are those of "genotype products" above (a half-missing genotype is missing); the
+ * scan sees all N = n_ind individuals of the panel (a subset is taken first, with ldx_panel_select_dev).
+ * Design (the host's part, numpy fp64: ops.glm_design): D = [1 | X] with n_cov columns, thin QR D = Q R (refused when
+ * |R_aa| <= 2^-20 max |R| on R's diagonal, when df = N - n_cov - 1 < 1, or on a non-finite value), Y~ = Y - Q (Q^T Y); a column
+ * of Y~ whose largest |entry| is <= 2^-40 times the largest |entry| of its phenotype AS GIVEN (not centred) is set to 0: a
+ * phenotype in the span of D leaves only the rounding of the projection, which the quantiser would scale to 30 bits (so does a
+ * spread below about 1e-12 of a large offset: centre such a phenotype first); U = [Q | Y~],
+ * k = n_cov + n_pheno <= LDX_GENO_MAX_COLS columns, is quantised as ONE matrix by the weights' rule (q int32, exponents e:
+ * u^ = q 2^(e - 30)).  From here on everything is a function of integers: yy_j = (double)(sum_a q_aj^2) 2^(2 (e_j - 30)), the
+ * integer sum exact and rounded once; the quantised Q^ is TREATED as orthonormal -- part of the definition.
+ * Per SNP, from counts {n called, het, hom} and the rows z, zc of the reverse product of q: s = het + 2 hom, e2 = het + 4 hom,
+ *     mu = (double)s / (double)n            gg = (double)(n e2 - s^2) / (double)n         (the numerator an exact int64)
+ *     h_a = ((double)z_a - mu (double)zc_a) 2^(e_a - 30),  a < n_cov       d = gg - (((h_0^2 + h_1^2) + h_2^2) + ...)
+ * per cell (SNP, phenotype j), column c = n_cov + j:  b = ((double)z_c - mu (double)zc_c) 2^(e_c - 30),
+ *     beta = b / d     s2 = (yy_j - (b b) / d) / df     se = sqrt(s2 / d)     t = beta / se
+ *     p = 2 P(T_df <= -|t|) = I_x(df / 2, 1 / 2),  x = df / (df + t^2)      neglog10_p = -log10 p, evaluated from ln p
+ * every operation in fp64 rounded once, in this order: beta, se, t and the flags are reproduced bit for bit by numpy
+ * (ops.glm_linear_host).  The tail is a continued fraction (modified Lentz) with the front factor in log space, so neglog10_p is
+ * finite where p underflows to 0; for x >= (a + 1) / (a + b + 2) the complement 1 - I_{1-x}(1 / 2, df / 2) is taken, 1 - x formed
+ * as t^2 / (df + t^2); ln B(df / 2, 1 / 2) is one difference of lgamma values per call.  |ln p| is within 2^-30 max(1, |ln p|) of
+ * the exact value.  t = 0 gives p = 1, neglog10_p = 0 exactly.
+ * flags, uint8 per cell, the first that applies; 0 and 5 are finite results, every other flag is NaN in all five outputs:
+ *     0 OK      1 SNP not kept, or n = 0      2 genotype constant among the called (n e2 = s^2)      3 d max_vif < gg
+ *     4 yy_j = 0 (the phenotype is constant after the covariates)
+ *     5 s2 <= 0, a perfect fit: beta as computed, se = 0, t = +-inf (beta's sign), p = 0, neglog10_p = +inf
+ *     6 the tail's continued fraction passed 512 steps
+ *
+ * ldx_geno_snp_counts_dev: counts[i] = {called, het, hom ALT, 0} over the individuals of SNP i, from the panel's tiled planes
+ * with the reverse product's own genotype words, so that they agree with z, zc by construction.  Work: a workgroup per slab of
+ * 128 SNPs, popcounts, the two halves of a row meet in LDS; plain 16-byte stores: every word of every row is written (0 for a SNP
+ * that is not kept).  counts must be 16-byte aligned; the other argument rules are ldx_geno_rmatmul_dev's.
+ * ldx_glm_linear_dev: z, zc int64 [n_snps][ld_z] (columns 0 .. n_cov - 1 of Q, then the phenotypes), counts as above, exps int64
+ * [n_cov + n_pheno], yy double [n_pheno]; beta, se, t, p, neglog10_p double [n_snps][ld_out] and flags uint8 [n_snps][ld_out]: the
+ * words [i][j < n_pheno] are written, the padding is not touched.  Work: a workgroup per 128 SNPs; mu, gg, h, d and flags 1 - 3
+ * once per SNP (a wave per SNP, lane a on column a), then a thread per cell.  A null pointer, n_snps, n_cov or n_pheno = 0, n_cov +
+ * n_pheno > LDX_GENO_MAX_COLS, a leading dimension below its width, n_ind <= n_cov + 1, or a max_vif that is not > 1 = LDX_E_ARG,
+ * checked before any HIP call. */
+int ldx_geno_snp_counts_dev(const void *alt, const void *ref, uint32_t n_snps, uint32_t n_hap, const uint8_t *keep,
+                            uint32_t *counts, void *stream);
+int ldx_glm_linear_dev(const int64_t *z, const int64_t *zc, size_t ld_z, const uint32_t *counts, uint32_t n_snps, uint32_t n_ind,
+                       uint32_t n_cov, uint32_t n_pheno, const int64_t *exps, const double *yy, double max_vif, double *beta,
+                       double *se, double *t, double *p, double *neglog10_p, uint8_t *flags, size_t ld_out, void *stream);
+
 /* ---- synthetic panels: deterministic, identical on host and device ------ */
 /* codes int8 [n_snps][ld_codes] receive global SNPs [snp_offset, snp_offset + n_snps) (a rank's
  * shard).  thresholds: per-SNP ALT probability * 2^64 (computed on the host, see

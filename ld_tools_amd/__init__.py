@@ -27,9 +27,11 @@ from .ops import (RelatedPairs, SampleCounts, ibs_cell_host, ibs_matrix, king_ce
                   king_from_counts, king_kinship, sample_counts, sample_counts_host)
 from .ops import (GenoOperator, GenoProduct, SamplePCA, Scores, geno_matmul, geno_matmul_host, geno_quantize,  # noqa: F401
                   geno_rmatmul, geno_rmatmul_host, polygenic_score, polygenic_score_host, sample_pca, sample_pca_host)
+from .ops import (GLM_FLAGS, GlmDesign, GlmResult, geno_counts_host, geno_snp_counts, glm_design, glm_linear_host,  # noqa: F401
+                  glm_tail_host, ld_glm, ld_glm_host)
 from .panel import PackedPanel, encode_codes, select_index  # noqa: F401
 from . import plink  # noqa: F401
-from .plink import BedFile, bed_codes_host, codes_bed_host, write_bfile  # noqa: F401
+from .plink import BedFile, bed_codes_host, codes_bed_host, read_covar, read_pheno, write_bfile  # noqa: F401
 
 __all__ = ["PackedPanel", "encode_codes", "select_index", "ld_triangle", "ld_area", "pair_counts", "ld_from_counts",
            "TriangleResult", "AreaHits", "ld_score", "LDScores", "ld_neighbors", "LDNeighbors", "ld_clump", "Clumps",
@@ -41,5 +43,6 @@ __all__ = ["PackedPanel", "encode_codes", "select_index", "ld_triangle", "ld_are
            "gabriel_pick_host", "gabriel_kept_host", "sample_counts", "SampleCounts", "RelatedPairs", "king_kinship", "ibs_matrix",
            "sample_counts_host", "king_cell_host", "ibs_cell_host", "king_from_counts", "king_cutoff", "GenoOperator", "GenoProduct",
            "geno_quantize", "geno_matmul", "geno_rmatmul", "geno_matmul_host", "geno_rmatmul_host", "polygenic_score",
-           "polygenic_score_host", "Scores", "sample_pca", "sample_pca_host", "SamplePCA", "LdxError",
-           "version", "plink", "BedFile", "bed_codes_host", "codes_bed_host", "write_bfile"]
+           "polygenic_score_host", "Scores", "sample_pca", "sample_pca_host", "SamplePCA", "geno_snp_counts", "geno_counts_host",
+           "glm_design", "GlmDesign", "ld_glm", "ld_glm_host", "glm_linear_host", "glm_tail_host", "GlmResult", "GLM_FLAGS", "LdxError",
+           "version", "plink", "BedFile", "bed_codes_host", "codes_bed_host", "write_bfile", "read_pheno", "read_covar"]

@@ -213,6 +213,8 @@ SIGNATURES = {
     "ldx_sample_cells_dev": (_int, [_vp, _u32, _sz, _vp, _vp, _sz, _vp]),
     "ldx_geno_matmul_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _sz, _u32, _vp, _sz, _int, _u32, _vp]),
     "ldx_geno_rmatmul_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _sz, _u32, _vp, _vp, _sz, _vp]),
+    "ldx_geno_snp_counts_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "ldx_glm_linear_dev": (_int, [_vp, _vp, _sz, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ldx_ld_select_workspace_bytes": (_sz, [_u32]),
     "ldx_ld_select_dev": (_int, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ldx_set_area_path": (_int, [_int]),

@@ -62,6 +62,18 @@ __device__ __forceinline__ uint32_t ind_called(uint32_t alt, uint32_t ref)
     const uint32_t c = alt | ref;
     return c & (c >> 1) & 0x55555555u;
 }
+// The genotype words of one 32-bit word of a panel row (16 individuals, each on the even slot of its two haplotypes): q called,
+// z homozygous ALT, t heterozygous.  The reverse genotype product (ldx_geno.hip) and the per-SNP genotype counts (ldx_glm.hip)
+// both take their words from here, so the counts agree with the products by construction.
+struct GenoWords {
+    uint32_t q, z, t;
+};
+__device__ __forceinline__ GenoWords geno_words(uint32_t wa, uint32_t wr)
+{
+    const uint32_t q = ind_called(wa, wr);
+    const uint32_t a = wa & (q | (q << 1));   // a half-missing genotype is missing
+    return GenoWords{q, a & (a >> 1) & 0x55555555u, (a ^ (a >> 1)) & q};
+}
 __device__ __forceinline__ v4i even_a4(uint32_t z)
 {
     return v4i{(int)(z & 0x11111111u), 0, (int)((z >> 2) & 0x11111111u), 0};   // 0.5, -, 0.5, -

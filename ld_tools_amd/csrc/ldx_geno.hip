@@ -268,9 +268,8 @@ __global__ void __launch_bounds__(kThreads) rmatmul_kernel(RevArgs p)
 #pragma unroll
         for (int wd = 0; wd < 4; ++wd) {
             const uint32_t wa = word_of(va, wd), wr = word_of(vr, wd);
-            const uint32_t q = ind_called(wa, wr);
-            const uint32_t a = wa & (q | (q << 1));   // a half-missing genotype is missing
-            const uint32_t z = a & (a >> 1) & 0x55555555u, t = (a ^ (a >> 1)) & q;
+            const GenoWords g = geno_words(wa, wr);   // a half-missing genotype is missing
+            const uint32_t q = g.q, z = g.z, t = g.t;
             v4i ag, ac;
 #pragma unroll
             for (int dd = 0; dd < 4; ++dd) {

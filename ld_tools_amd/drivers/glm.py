@@ -1,0 +1,88 @@
+"""Linear association scans of the variants of a panel, in the layout of PLINK 2's ``.glm.linear`` (--glm on a quantitative
+trait).  Not a reference workflow: ops.ld_glm is this project's own definition (include/ldx.h, "association scan"), NOT
+validated against PLINK 2 -- a missing genotype counts as the variant's mean, where PLINK refits over the called individuals, so
+the numbers differ wherever a call is missing; the file follows PLINK's layout.  Numbers are written with the shortest text that
+reads back to the same float64; a P below the float64 range is written from its -log10, so it keeps its exponent.
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from .._lib import LdxError
+from ..ops import GlmResult, ld_glm
+
+GLM_COLUMNS = ("#CHROM", "POS", "ID", "REF", "ALT", "A1", "TEST", "OBS_CT", "BETA", "SE", "T_STAT", "P")
+
+
+@dataclass
+class GlmTable:
+    """Variant k is (chrom[k], pos[k], ids[k]) with the alleles ref[k], alt[k]; ``alt`` is the counted allele (A1: the sign of
+    BETA).  ``names``: one per phenotype column of ``result`` (ops.ld_glm's)."""
+
+    chrom: List[str]
+    pos: List[int]
+    ids: List[str]
+    ref: List[str]
+    alt: List[str]
+    names: List[str]
+    result: GlmResult
+
+
+def glm_table(panel, variants: dict, Y, covar=None, names: Optional[Sequence[str]] = None, **more) -> GlmTable:
+    """ops.ld_glm of ``panel`` with the columns of its variants: ``variants`` holds ``chrom``, ``pos``, ``ids``, ``ref`` and
+    ``alt`` (the allele that is code 1), one entry per SNP of the panel.  ``names``: the phenotypes' names (default PHENO1 ...);
+    ``more``: ld_glm's individuals, keep and max_vif."""
+    cols = {}
+    for key in ("chrom", "pos", "ids", "ref", "alt"):
+        if key not in variants or len(variants[key]) != panel.n_snps:
+            raise LdxError(f"glm_table: variants[{key!r}] needs one entry per SNP of the panel ({panel.n_snps})")
+        cols[key] = list(variants[key])
+    res = ld_glm(panel, Y, covar, **more)
+    n_pheno = res.design.n_pheno
+    names = [f"PHENO{j + 1}" for j in range(n_pheno)] if names is None else [str(n) for n in names]
+    if len(names) != n_pheno:
+        raise LdxError(f"glm_table: {len(names)} names for {n_pheno} phenotypes")
+    return GlmTable([str(c) for c in cols["chrom"]], [int(p) for p in cols["pos"]], [str(i) for i in cols["ids"]],
+                    [str(a) for a in cols["ref"]], [str(a) for a in cols["alt"]], names, res)
+
+
+def _txt(x: float) -> str:
+    return repr(float(x))
+
+
+def p_text(p: float, neglog10_p: float) -> str:
+    """The text of a p-value: the shortest that reads back to ``p`` while p is a normal float64; below that m e-X from
+    ``neglog10_p`` (six digits of m), "0" where that is infinite."""
+    if p >= 2.2250738585072014e-308:
+        return _txt(p)
+    if math.isinf(neglog10_p):
+        return "0"
+    ex = math.floor(-neglog10_p)
+    m = f"{10.0 ** (-neglog10_p - ex):.6g}"
+    if m == "10":            # the mantissa rounded up to the next decade
+        m, ex = "1", ex + 1
+    return f"{m}e{ex}"
+
+
+def write_glm_linear(path: str, table: GlmTable, pheno=0) -> int:
+    """``path``: the ``.glm.linear`` lines of one phenotype of ``table`` (its name or column number), tab-separated:
+    ``#CHROM POS ID REF ALT A1 TEST OBS_CT BETA SE T_STAT P``, TEST = ADD, one line per variant; the cells of a flagged variant
+    (ops.GLM_FLAGS other than 0 and 5) are NA.  Returns the number of lines."""
+    j = table.names.index(pheno) if isinstance(pheno, str) else int(pheno)
+    r = table.result
+    beta, se, t, p, nlp = (x[:, j].cpu().numpy() for x in (r.beta, r.se, r.t, r.p, r.neglog10_p))
+    flags, n_obs = r.flags[:, j].cpu().numpy(), r.n_obs
+    with open(path, "w") as f:
+        f.write("\t".join(GLM_COLUMNS) + "\n")
+        for k in range(len(table.ids)):
+            head = "\t".join((table.chrom[k], str(table.pos[k]), table.ids[k], table.ref[k], table.alt[k], table.alt[k], "ADD",
+                              str(int(n_obs[k])))) + "\t"
+            if flags[k] not in (0, 5):
+                f.write(head + "NA\tNA\tNA\tNA\n")
+            else:
+                f.write(head + f"{_txt(beta[k])}\t{_txt(se[k])}\t{_txt(t[k])}\t{p_text(float(p[k]), float(nlp[k]))}\n")
+    return len(table.ids)

@@ -12,12 +12,13 @@ dataclasses of the VCF drivers from it, so that their writers write them unchang
     bfile_king       -> KingTable for write_kin0 / write_king_cutoff       PLINK 2 --make-king-table / --king-cutoff
     bfile_pca        -> PcaTable for write_eigenvec / write_eigenval       PLINK 2 --pca approx
     bfile_score      -> ScoreTable for write_sscore                        PLINK --score (sums)
+    bfile_glm        -> GlmTables for write_glm_linear                     PLINK 2 --glm (quantitative traits, mean imputation)
 
 A ``.bed`` holds unphased genotype calls: a het is written (ALT, REF) whatever the truth, so the haplotype r of the phased
 operators means nothing here.  Every driver defaults to an unphased form (EM or genotype dosage) and refuses
 ``dosage=False, em=False``.  ``make_bed`` writes a panel, or a subset of a loaded fileset, back as a fileset.
 
-    python -m ld_tools_amd.drivers.plink {ld,clump,prune,l2,blocks,king,pca,score,make-bed} --bfile P --out O ...
+    python -m ld_tools_amd.drivers.plink {ld,clump,prune,l2,blocks,king,pca,score,glm,make-bed} --bfile P --out O ...
 """
 from __future__ import annotations
 
@@ -451,6 +452,84 @@ def bfile_score(src, weights, out: Optional[str] = None, impute: str = "mean", k
     return table
 
 
+def _sample_rows(what: str, table, bf: Bfile, names) -> tuple:
+    """(names, values float64 [individuals of ``bf``, names], NaN where the table has no line for an individual) of a phenotype or
+    covariate table -- a path or plink.read_pheno's (fid, iid, names, values) -- restricted to ``names`` when given.  A line is
+    matched by (FID, IID); a table without a FID column (``fid`` None) by IID alone, which must then name one individual of the
+    fileset only.  An individual on two lines is refused."""
+    if isinstance(table, str):
+        table = plink.read_covar(table) if what == "covariate" else plink.read_pheno(table)
+    fid, iid, have, values = table
+    values = np.asarray(values, dtype=np.float64).reshape(len(iid), len(have))
+    if names is not None:
+        unknown = [n for n in names if n not in have]
+        if unknown:
+            raise LdxError(f"bfile_glm: no {what} named {unknown[0]!r} (the table has {', '.join(have[:8])} ...)")
+        values, have = values[:, [list(have).index(n) for n in names]], list(names)
+    where: dict = {}
+    for k, key in enumerate(zip(bf.fid, bf.iid) if fid is not None else bf.iid):
+        if key in where:
+            raise LdxError(f"bfile_glm: the fileset holds {key!r} twice: the {what} table cannot tell its individuals apart"
+                           + ("" if fid is not None else " by IID alone; give it a FID column"))
+        where[key] = k
+    out = np.full((len(bf.iid), len(have)), np.nan)
+    filled = np.zeros(len(bf.iid), dtype=bool)
+    for key, row in zip(zip(fid, iid) if fid is not None else iid, values):
+        k = where.get(key)
+        if k is not None:
+            if filled[k]:
+                raise LdxError(f"bfile_glm: the {what} table names {key!r} on two lines")
+            out[k], filled[k] = row, True
+    return list(have), out
+
+
+def bfile_glm(src, pheno, covar=None, out: Optional[str] = None, pheno_names: Optional[Sequence[str]] = None,
+              covar_names: Optional[Sequence[str]] = None, max_vif: float = 50.0, allow_binary: bool = False, **load) -> list:
+    """drivers/glm.py's ``glm_table`` from a fileset (PLINK 2's --glm for quantitative traits; ops.ld_glm's definition: a missing
+    genotype counts as the variant's mean).  ``pheno`` / ``covar``: the path of a phenotype / covariate table (plink.read_pheno,
+    plink.read_covar; an ``.eigenvec`` is a covariate table) or its (fid, iid, names, values); ``pheno_names`` / ``covar_names``
+    choose columns.  A row is complete for a phenotype when the phenotype and every covariate are finite and the individual is
+    in the fileset; the phenotypes are grouped by their set of complete rows, and each group is scanned over its own individuals
+    (ld_glm's ``individuals``), at most 64 columns a sweep.  A phenotype whose values all lie in {1, 2} or {0, 1} is a
+    case/control trait, which belongs to a logistic model: refused unless ``allow_binary``.  ``out``: a prefix to write one
+    ``<out>.<phenotype>.glm.linear`` per phenotype under.  Returns the GlmTables, one per sweep."""
+    from .glm import GlmTable, write_glm_linear
+    from .._lib import GENO_MAX_COLS
+    from ..ops import ld_glm
+
+    bf = _loaded(src, **load)
+    names, Y = _sample_rows("phenotype", pheno, bf, pheno_names)
+    C = np.empty((len(bf.iid), 0)) if covar is None else _sample_rows("covariate", covar, bf, covar_names)[1]
+    for j, name in enumerate(names):
+        seen = set(np.unique(Y[np.isfinite(Y[:, j]), j]).tolist())
+        if not seen:
+            raise LdxError(f"bfile_glm: phenotype {name} has no value for an individual of the fileset")
+        if (seen <= {1.0, 2.0} or seen <= {0.0, 1.0}) and not allow_binary:
+            raise LdxError(f"bfile_glm: phenotype {name} takes the values {sorted(seen)} only: a case/control trait belongs to a "
+                           "logistic model, which is not implemented (allow_binary=True fits the line anyway)")
+    complete = np.isfinite(Y) & np.isfinite(C).all(axis=1)[:, None]
+    groups: dict = {}
+    for j in range(len(names)):
+        groups.setdefault(complete[:, j].tobytes(), []).append(j)
+    width = GENO_MAX_COLS - (C.shape[1] + 1)
+    if width < 1:
+        raise LdxError(f"bfile_glm: {C.shape[1]} covariates leave no column for a phenotype ({GENO_MAX_COLS} a sweep)")
+    tables = []
+    for cols in groups.values():
+        rows = np.flatnonzero(complete[:, cols[0]])
+        for at in range(0, len(cols), width):
+            batch = cols[at:at + width]
+            res = ld_glm(bf.panel, Y[np.ix_(rows, batch)], C[rows] if C.shape[1] else None,
+                         individuals=None if rows.size == len(bf.iid) else rows, max_vif=max_vif)   # everybody: no copy of the panel
+            tables.append(GlmTable(list(bf.chrom), _poss(bf), list(bf.ids), list(bf.refs), list(bf.alts),
+                                   [names[j] for j in batch], res))
+    if out is not None:
+        for table in tables:
+            for name in table.names:
+                write_glm_linear(f"{out}.{name}.glm.linear", table, name)
+    return tables
+
+
 def make_bed(prefix_out, src, snps=None, individuals=None, bim: Optional[dict] = None, fam: Optional[dict] = None,
              alt: Optional[str] = None) -> List[str]:
     """Write a fileset.  ``src``: a ``Bfile`` -- ``snps`` / ``individuals`` (index arrays or masks over ITS variants and
@@ -567,6 +646,12 @@ def parser() -> argparse.ArgumentParser:
     p = common("score", "polygenic score sums of the individuals (.sscore)")
     p.add_argument("--score", required=True, help="weights: variant ID, allele, weight per line")
     p.add_argument("--no-mean-imputation", action="store_true", help="a missing genotype adds nothing (default: 2 x frequency)")
+    p = common("glm", "linear association scan of quantitative phenotypes (.<phenotype>.glm.linear)")
+    p.add_argument("--pheno", required=True, help="phenotype table: '#FID IID', 'FID IID' or '#IID', then one column per phenotype")
+    p.add_argument("--pheno-name", nargs="+", default=None, help="the phenotypes to scan (default: every column)")
+    p.add_argument("--covar", default=None, help="covariate table in the same layout (an .eigenvec is one)")
+    p.add_argument("--covar-name", nargs="+", default=None, help="the covariates to use (default: every column)")
+    p.add_argument("--vif", type=float, default=50.0, help="largest variance inflation factor of a variant")
     common("make-bed", "write the selected variants and individuals as a new fileset")
     return ap
 
@@ -609,6 +694,11 @@ def main(argv=None) -> int:
                           prune_missing=a.missing, king_cutoff=a.king_cutoff, seed=a.seed)
         print(int(table.in_pca.sum()), "of", len(table.iid), "individuals decomposed,", table.pca.n_used, "variants ->",
               a.out + ".eigenvec", a.out + ".eigenval")
+    elif a.command == "glm":
+        split = lambda v: None if v is None else [n for part in v for n in part.split(",") if n]  # noqa: E731
+        tables = bfile_glm(bf, a.pheno, covar=a.covar, out=a.out, pheno_names=split(a.pheno_name), covar_names=split(a.covar_name),
+                           max_vif=a.vif)
+        print(*(f"{a.out}.{name}.glm.linear" for t in tables for name in t.names))
     elif a.command == "score":
         table = bfile_score(bf, a.score, out=a.out, impute="zero" if a.no_mean_imputation else "mean")
         print(table.n_matched, "of", table.n_lines, "weight lines matched ->", a.out + ".sscore")

@@ -26,6 +26,7 @@ tensors; nothing here computes LD on the host.
 from __future__ import annotations
 
 import ctypes
+import math
 from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
@@ -34,7 +35,7 @@ import torch
 
 from . import _lib
 from ._lib import MEASURES, UNIT_PAIRS, check, lib
-from .panel import PackedPanel, _ptr, _stream_ptr, require_gpu
+from .panel import PackedPanel, _ptr, _stream_ptr, require_gpu, select_index
 
 
 PATHS = {"auto": 0, "popcount": 1, "mfma": 2, "fp4": 3}
@@ -4059,6 +4060,314 @@ def sample_pca_host(codes, n_pcs: int = 10, keep=None, oversample: int = 10, n_i
                     loadings: bool = False) -> SamplePCA:
     """Host mirror of sample_pca on the allele codes [n_snps, n_hap]."""
     return _pca(_HostEngine(codes, keep), int(n_pcs), int(oversample), int(n_iter), seed, loadings)
+
+
+# --------------------------------------------------------------------------- linear association scan
+GLM_MAX_STEPS = 512                            # passes of the tail's continued fraction before flag 6
+GLM_EPS = 2.0 ** -50
+GLM_FLAGS = {0: "ok", 1: "no call", 2: "constant genotype", 3: "vif", 4: "constant phenotype", 5: "perfect fit",
+             6: "iteration cap"}
+
+
+@dataclass
+class GlmDesign:
+    """glm_design's result: ``q`` int32 [N, k] and ``exps`` int64 [k], the quantised U = [Q | Y~] (the first ``n_cov`` columns are
+    the orthonormal basis of [1 | X], the other ``n_pheno`` the residual phenotypes); ``yy`` float64 [n_pheno], the residual sums
+    of squares from the integers; ``df`` = N - n_cov - 1.  All numpy, on the host."""
+
+    q: np.ndarray
+    exps: np.ndarray
+    yy: np.ndarray
+    n_ind: int
+    n_cov: int
+    n_pheno: int
+    df: int
+
+
+def _glm_matrix(x, what: str, rows: Optional[int] = None) -> np.ndarray:
+    x = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    if x.dtype.kind not in "fiub":
+        raise _lib.LdxError(f"{what} must be real numbers (got {x.dtype})")
+    x = np.asarray(x, dtype=np.float64)
+    x = x[:, None] if x.ndim == 1 else x
+    if x.ndim != 2 or (rows is not None and x.shape[0] != rows):
+        raise _lib.LdxError(f"{what} must have shape [{'N' if rows is None else rows}] or [{'N' if rows is None else rows}, k], "
+                            f"got {x.shape}")
+    if not np.isfinite(x).all():
+        raise _lib.LdxError(f"{what} holds a value that is not finite (take the complete rows first: ld_glm(individuals=))")
+    return x
+
+
+def glm_design(Y, covar=None) -> GlmDesign:
+    """The design step of the association scan (include/ldx.h, "association scan"), numpy fp64 on the host: D = [1 | covar],
+    thin QR, Y~ = Y - Q (Q^T Y), U = [Q | Y~] quantised as one matrix (geno_quantize), yy from the integers.  ``Y``: [N] or
+    [N, p]; ``covar``: [N, c'] without an intercept, or None.  Refused: a rank-deficient D (|R_aa| <= 2^-20 max |R|),
+    df = N - n_cov - 1 < 1, a non-finite value, more than 64 columns in U."""
+    y = _glm_matrix(Y, "glm_design: Y")
+    n, p = y.shape
+    if p < 1:
+        raise _lib.LdxError("glm_design: Y has no column")
+    x = np.empty((n, 0)) if covar is None else _glm_matrix(covar, "glm_design: covar", n)
+    D = np.concatenate([np.ones((n, 1)), x], axis=1)
+    n_cov = D.shape[1]
+    if n_cov + p > _lib.GENO_MAX_COLS:
+        raise _lib.LdxError(f"glm_design: {n_cov} covariate columns (with the intercept) and {p} phenotypes are more than "
+                            f"{_lib.GENO_MAX_COLS} columns in one sweep; batch the phenotypes")
+    df = n - n_cov - 1
+    if df < 1:
+        raise _lib.LdxError(f"glm_design: {n} individuals leave df = N - {n_cov} - 1 = {df} < 1")
+    Q, R = np.linalg.qr(D)
+    diag = np.abs(np.diag(R))
+    if not np.isfinite(R).all() or (diag <= 2.0 ** -20 * np.abs(R).max()).any():
+        raise _lib.LdxError("glm_design: the covariates (with the intercept) are rank-deficient: a column is constant or a "
+                            "combination of the others")
+    yt = y - Q @ (Q.T @ y)
+    # a phenotype in the span of [1 | X] leaves only the rounding of the projection, which the quantiser would blow up to full
+    # scale: below 2^-40 of the largest |entry| of the phenotype AS GIVEN (not centred) the residual column is zero (flag 4)
+    yt[:, np.abs(yt).max(axis=0) <= 2.0 ** -40 * np.abs(y).max(axis=0)] = 0.0
+    (q,), e = geno_quantize(np.concatenate([Q, yt], axis=1))
+    q, e = q.numpy(), e.numpy()
+    # sum_a q^2 exactly, in two limbs: q^2 <= 2^60, so the sums of its low 30 bits and of the rest both fit an int64 for any N here;
+    # joined as Python ints and rounded to fp64 once
+    sq = q[:, n_cov:].astype(np.int64) ** 2
+    lo, hi = (sq & ((1 << 30) - 1)).sum(axis=0), (sq >> 30).sum(axis=0)
+    yy = np.asarray([math.ldexp(float((int(hi[j]) << 30) + int(lo[j])), 2 * (int(e[n_cov + j]) - GENO_SCALE_BITS)) for j in range(p)],
+                    dtype=np.float64)
+    return GlmDesign(q, e, yy, n, n_cov, p, df)
+
+
+def _glm_cf(a, b, x):
+    """The continued fraction of I_x(a, b) by the modified Lentz method, on arrays: (h, converged) -- glm_linear_kernel's steps."""
+    tiny = 1e-300
+    fix = lambda v: np.where(np.abs(v) < tiny, tiny, v)  # noqa: E731
+    qab, qap, qam = a + b, a + 1.0, a - 1.0
+    c = np.ones_like(x)
+    d = 1.0 / fix(1.0 - qab * x / qap)
+    h = d.copy()
+    done = np.zeros(x.shape, dtype=bool)
+    for m in range(1, GLM_MAX_STEPS + 1):
+        m2 = 2.0 * m
+        aa = m * (b - m) * x / ((qam + m2) * (a + m2))
+        d = 1.0 / fix(1.0 + aa * d)
+        c = fix(1.0 + aa / c)
+        h1 = h * (d * c)
+        aa = -(a + m) * (qab + m) * x / ((a + m2) * (qap + m2))
+        d = 1.0 / fix(1.0 + aa * d)
+        c = fix(1.0 + aa / c)
+        dl = d * c
+        h = np.where(done, h, h1 * dl)
+        done = done | (np.abs(dl - 1.0) <= GLM_EPS)
+        if done.all():
+            break
+    return h, done
+
+
+def glm_tail_host(t, df: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(p, neglog10_p, converged) of two-sided Student-t statistics ``t`` (finite or +-inf) with ``df`` degrees of freedom: the
+    numpy mirror of the kernel's tail (same branches and steps; numpy's log / exp, so equal within rounding, not bit for bit)."""
+    t = np.asarray(t, dtype=np.float64)
+    a, b = 0.5 * df, 0.5
+    ln_beta = math.lgamma(a) + math.lgamma(0.5) - math.lgamma(a + 0.5)
+    p, nlp, ok = np.ones(t.shape), np.zeros(t.shape), np.ones(t.shape, dtype=bool)
+    with np.errstate(all="ignore"):
+        t2 = t * t
+        far = np.isinf(t2)
+        p[far], nlp[far] = 0.0, np.inf
+        go = (t2 > 0.0) & ~far
+        if go.any():
+            t2 = t2[go]
+            den = df + t2
+            x, omx = df / den, t2 / den
+            front = a * -np.log1p(t2 / df) + b * np.log(omx) - ln_beta
+            direct = x < (a + 1.0) / (a + b + 2.0)
+            hd, okd = _glm_cf(a, b, np.where(direct, x, 0.0))
+            hc, okc = _glm_cf(b, a, np.where(direct, 0.0, omx))
+            lnp_d = front - math.log(a) + np.log(hd)
+            comp = np.exp(front - math.log(b)) * hc
+            lnp = np.where(direct, lnp_d, np.log1p(-comp))
+            p[go] = np.where(direct, np.exp(lnp_d), 1.0 - comp)
+            nlp[go] = -lnp / 2.302585092994046
+            ok[go] = np.where(direct, okd, okc)
+    return p, nlp, ok
+
+
+def glm_linear_host(z, zc, counts, exps, yy, n_ind: int, n_cov: int, max_vif: float = 50.0):
+    """The numpy mirror of ldx_glm_linear_dev: (beta, se, t, p, neglog10_p float64 [n_snps, n_pheno], flags uint8) from the int64
+    products ``z``, ``zc`` [n_snps, k], the per-SNP ``counts`` [n_snps, 4], the exponents [k] and ``yy`` [n_pheno].  Every
+    operation of beta, se, t and the flags is the kernel's, in its order (the h^2 are summed one after the other, not with
+    np.sum): those four agree with the device bit for bit."""
+    z, zc = np.asarray(z, dtype=np.int64), np.asarray(zc, dtype=np.int64)
+    counts = np.asarray(counts).astype(np.int64)
+    e, yy = np.asarray(exps, dtype=np.int64), np.asarray(yy, dtype=np.float64)
+    n_snps, k = z.shape
+    n_pheno = k - n_cov
+    df = int(n_ind) - n_cov - 1
+    if not (n_cov >= 1 and n_pheno >= 1 and df >= 1 and max_vif > 1.0 and yy.shape == (n_pheno,) and e.shape == (k,)
+            and zc.shape == z.shape and counts.shape == (n_snps, 4)):
+        raise _lib.LdxError("glm_linear_host: shapes, df or max_vif outside the rules of ldx_glm_linear_dev")
+    scale = np.ldexp(1.0, (e - GENO_SCALE_BITS).astype(np.int64))
+    n, het, hom = counts[:, 0], counts[:, 1], counts[:, 2]
+    s, e2 = het + 2 * hom, het + 4 * hom
+    num = n * e2 - s * s
+    flag = np.where(n == 0, 1, np.where(num == 0, 2, 0)).astype(np.uint8)
+    with np.errstate(all="ignore"):
+        nd = np.where(n > 0, n, 1).astype(np.float64)
+        mu = s.astype(np.float64) / nd
+        gg = num.astype(np.float64) / nd
+        acc = np.zeros(n_snps)
+        for a in range(n_cov):
+            h = (z[:, a].astype(np.float64) - mu * zc[:, a].astype(np.float64)) * scale[a]
+            acc = acc + h * h
+        d = gg - acc
+        flag[(flag == 0) & (d * float(max_vif) < gg)] = 3
+        flags = np.repeat(flag[:, None], n_pheno, axis=1)
+        flags[(flags == 0) & (yy == 0.0)[None, :]] = 4
+        b = (z[:, n_cov:].astype(np.float64) - mu[:, None] * zc[:, n_cov:].astype(np.float64)) * scale[None, n_cov:]
+        beta = b / d[:, None]
+        s2 = (yy[None, :] - (b * b) / d[:, None]) / float(df)
+        flags[(flags == 0) & (s2 <= 0.0)] = 5
+        se = np.sqrt(s2 / d[:, None])
+        t = beta / se
+        fit = flags == 5
+        se[fit], t[fit] = 0.0, np.copysign(np.inf, beta[fit])
+        live = flags == 0
+        p, nlp = np.zeros(t.shape), np.full(t.shape, np.inf)
+        p[live], nlp[live], ok = glm_tail_host(t[live], df)
+        capped = np.zeros(t.shape, dtype=bool)
+        capped[live] = ~ok
+        flags[capped] = 6
+    dead = (flags != 0) & (flags != 5)
+    for out in (beta, se, t, p, nlp):
+        out[dead] = np.nan
+    return beta, se, t, p, nlp, flags
+
+
+def geno_counts_host(codes, keep=None) -> np.ndarray:
+    """Host mirror of geno_snp_counts on the allele codes: uint32 [n_snps, 4] = {called, het, hom ALT, 0}."""
+    g, c = geno_planes_host(codes, keep)
+    return np.stack([c.sum(axis=1), (g == 1).sum(axis=1), (g == 2).sum(axis=1), np.zeros(g.shape[0], dtype=np.int64)],
+                    axis=1).astype(np.uint32)
+
+
+def geno_snp_counts(panel: PackedPanel, keep=None) -> torch.Tensor:
+    """int32 device tensor [n_snps, 4] (the words are uint32): per SNP the called, heterozygous and homozygous-ALT individuals
+    and a zero, from the panel's planes with the reverse genotype product's own words (ldx_geno_snp_counts_dev); the rows of SNPs
+    that ``keep`` drops are 0."""
+    require_gpu()
+    if panel.n_hap % 2:
+        raise _lib.LdxError(f"geno_snp_counts: n_hap must be even (haplotypes 2a and 2a + 1 are individual a), got {panel.n_hap}")
+    k = _keep_mask(keep, panel.n_snps)
+    keep_d = None if k is None else torch.from_numpy(k.astype(np.uint8)).to(panel.device)
+    return _snp_counts(panel, keep_d)
+
+
+def _snp_counts(panel: PackedPanel, keep_d: Optional[torch.Tensor]) -> torch.Tensor:
+    counts = torch.empty((panel.n_snps, 4), dtype=torch.int32, device=panel.device)
+    check(lib.ldx_geno_snp_counts_dev(panel.alt.data_ptr(), panel.ref.data_ptr(), panel.n_snps, panel.n_hap, _ptr(keep_d),
+                                      counts.data_ptr(), _stream_ptr()), "ldx_geno_snp_counts_dev")
+    return counts
+
+
+@dataclass
+class GlmResult:
+    """ld_glm's result.  ``beta``, ``se``, ``t``, ``p``, ``neglog10_p``: float64 tensors [n_snps, n_pheno] and ``flags`` uint8
+    (GLM_FLAGS; 0 and 5 are finite results, the others NaN) -- on the panel's device, nothing read back until asked for (host
+    tensors from ld_glm_host); ``counts`` [n_snps, 4]: called, het, hom ALT per SNP; ``design``: the integers of the design
+    step; ``df`` = N - n_cov - 1."""
+
+    beta: torch.Tensor
+    se: torch.Tensor
+    t: torch.Tensor
+    p: torch.Tensor
+    neglog10_p: torch.Tensor
+    flags: torch.Tensor
+    counts: torch.Tensor
+    design: GlmDesign
+    df: int
+
+    @property
+    def n_obs(self) -> np.ndarray:
+        """int64 [n_snps]: the individuals called at each SNP (0 for a SNP that is not kept)."""
+        return self.counts[:, 0].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+
+    @property
+    def a1_freq(self) -> np.ndarray:
+        """float64 [n_snps]: the frequency of the counted allele among the called, (het + 2 hom) / (2 n); 0 without a call."""
+        c = self.counts.cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+        return _allele_freq(c[:, 0], c[:, 1] + 2 * c[:, 2])
+
+
+def _glm_missing(what: str, missing) -> None:
+    if missing == "pairwise":
+        raise _lib.LdxError(f"{what}: missing='pairwise' (PLINK's complete-case fit, a refit of every SNP over its called "
+                            "individuals) is not implemented; the scan sets a missing genotype to the SNP's mean (missing=None)")
+    if missing is not None:
+        raise _lib.LdxError(f"{what}: missing must be None (mean imputation), got {missing!r}")
+
+
+def _glm_columns(individuals, n_ind: int) -> Optional[np.ndarray]:
+    if individuals is None:
+        return None
+    ii = select_index(individuals, n_ind, "individual").astype(np.int64)
+    return np.stack([2 * ii, 2 * ii + 1], axis=1).reshape(-1)
+
+
+def ld_glm(panel: PackedPanel, Y, covar=None, individuals=None, keep=None, max_vif: float = 50.0,
+           missing: Optional[str] = None) -> GlmResult:
+    """Linear association scan (include/ldx.h, "association scan"; this project's own definition, what PLINK 2 --glm reports for
+    a quantitative trait): per SNP that passes ``keep`` the least-squares fit of every column of ``Y`` [N] / [N, p] on the
+    genotype, an intercept and ``covar`` [N, c'].  ``individuals`` (index array or mask over the panel's individuals, any order):
+    the N individuals the rows of ``Y`` and ``covar`` belong to, taken with PackedPanel.select; default: all, in the panel's
+    order.  A missing genotype counts as the SNP's mean over its called individuals -- PLINK refits over the called, so the two
+    differ wherever a call is missing; ``missing="pairwise"`` is refused.  One reverse genotype product of the quantised design
+    (glm_design; ldx_geno_rmatmul_dev, the launch of GenoOperator.rmatmul_q), one counts launch, one statistics launch;
+    ld_glm_host gives beta, se, t and the flags bit for bit."""
+    require_gpu()
+    _glm_missing("ld_glm", missing)
+    if panel.n_hap % 2:
+        raise _lib.LdxError(f"ld_glm: n_hap must be even (haplotypes 2a and 2a + 1 are individual a), got {panel.n_hap}")
+    if not float(max_vif) > 1.0:
+        raise _lib.LdxError("ld_glm: max_vif must be > 1")
+    cols = _glm_columns(individuals, panel.n_ind)
+    if cols is not None:
+        panel = panel.select(haplotypes=cols)
+    des = glm_design(_glm_matrix(Y, "ld_glm: Y", panel.n_ind), None if covar is None else _glm_matrix(covar, "ld_glm: covar", panel.n_ind))
+    mask = _keep_mask(keep, panel.n_snps)
+    keep_d = None if mask is None else torch.from_numpy(mask.astype(np.uint8)).to(panel.device)
+    dev, k, p = panel.device, des.n_cov + des.n_pheno, des.n_pheno
+    # the reverse product alone (GenoOperator.rmatmul_q's launch): the operator would first build the individual-major stores of
+    # the forward product, which a scan never reads
+    q = _geno_weights("ld_glm", des.q, panel.n_ind, dev)
+    z, zc = (torch.empty((panel.n_snps, k), dtype=torch.int64, device=dev) for _ in range(2))
+    check(lib.ldx_geno_rmatmul_dev(panel.alt.data_ptr(), panel.ref.data_ptr(), panel.n_snps, panel.n_hap, _ptr(keep_d), q.data_ptr(),
+                                   k, k, z.data_ptr(), zc.data_ptr(), k, _stream_ptr()), "ldx_geno_rmatmul_dev")
+    counts = _snp_counts(panel, keep_d)
+    exps, yy = torch.from_numpy(des.exps).to(dev), torch.from_numpy(des.yy).to(dev)
+    outs = [torch.empty((panel.n_snps, p), dtype=torch.float64, device=dev) for _ in range(5)]
+    flags = torch.empty((panel.n_snps, p), dtype=torch.uint8, device=dev)
+    check(lib.ldx_glm_linear_dev(z.data_ptr(), zc.data_ptr(), k, counts.data_ptr(), panel.n_snps, panel.n_ind, des.n_cov, p,
+                                 exps.data_ptr(), yy.data_ptr(), float(max_vif), *(o.data_ptr() for o in outs), flags.data_ptr(), p,
+                                 _stream_ptr()), "ldx_glm_linear_dev")
+    return GlmResult(*outs, flags, counts, des, des.df)
+
+
+def ld_glm_host(codes, Y, covar=None, individuals=None, keep=None, max_vif: float = 50.0) -> GlmResult:
+    """Host mirror of ld_glm on the allele codes [n_snps, n_hap]: the same design, the integer products of geno_rmatmul_host,
+    glm_linear_host.  The tensors of the result are on the host."""
+    x = np.asarray(codes)
+    if x.ndim != 2 or x.shape[1] % 2 or x.shape[1] == 0:
+        raise _lib.LdxError(f"ld_glm_host: codes [n_snps, n_hap] with an even n_hap needed, got shape {x.shape}")
+    if not float(max_vif) > 1.0:
+        raise _lib.LdxError("ld_glm_host: max_vif must be > 1")
+    cols = _glm_columns(individuals, x.shape[1] // 2)
+    if cols is not None:
+        x = x[:, cols]
+    n_ind = x.shape[1] // 2
+    des = glm_design(_glm_matrix(Y, "ld_glm_host: Y", n_ind), None if covar is None else _glm_matrix(covar, "ld_glm_host: covar", n_ind))
+    z, zc = geno_rmatmul_host(x, des.q, keep)
+    counts = geno_counts_host(x, keep)
+    outs = glm_linear_host(z, zc, counts, des.exps, des.yy, n_ind, des.n_cov, max_vif)
+    return GlmResult(*(torch.from_numpy(np.ascontiguousarray(o)) for o in outs), torch.from_numpy(counts.astype(np.int64)), des, des.df)
 
 
 # --------------------------------------------------------------------------- instrumentation

@@ -234,3 +234,58 @@ def write_bfile(prefix, rows_u8, bim: dict, fam: dict) -> List[str]:
         f.writelines(" ".join(str(c[k]) for c in fam_cols) + "\n" for k in range(n_ind))
     return paths
 
+
+# ---------------------------------------------------------------------------------------------- phenotype and covariate tables
+PHENO_MISSING = ("NA", "nan", "-9")
+
+
+def _sample_table(path: str, what: str, missing: Sequence[str]):
+    """(fid, iid, names, values float64 [lines, len(names)]) of a whitespace table whose header is ``#FID IID ...``,
+    ``FID IID ...`` or ``#IID ...`` (``fid`` is None then: the table names its individuals by IID alone); a field in ``missing``
+    reads as NaN.  An individual named on two lines is refused."""
+    try:
+        with open(path) as f:
+            lines = [ln.split() for ln in f if ln.split()]
+    except OSError as exc:
+        raise LdxError(f"cannot read {path}: {exc}") from exc
+    if not lines:
+        raise LdxError(f"{path}: empty {what} table")
+    head = lines[0]
+    if head[0] in ("#FID", "FID") and len(head) >= 2 and head[1] == "IID":
+        n_id = 2
+    elif head[0] in ("#IID", "IID"):
+        n_id = 1
+    else:
+        raise LdxError(f"{path}: the header of a {what} table starts with '#FID IID', 'FID IID' or '#IID', not {head[0]!r}")
+    names = head[n_id:]
+    if not names:
+        raise LdxError(f"{path}: no {what} column")
+    if len(set(names)) != len(names):
+        raise LdxError(f"{path}: a {what} name is repeated")
+    fid, iid, rows, seen = [], [], [], set()
+    for no, parts in enumerate(lines[1:], 2):
+        if len(parts) != len(head):
+            raise LdxError(f"{path}: line {no}: {len(parts)} fields beside the header's {len(head)}")
+        iid.append(parts[n_id - 1])
+        fid.append(parts[0])
+        key = (fid[-1], iid[-1])
+        if key in seen:
+            raise LdxError(f"{path}: line {no}: individual {' '.join(key[2 - n_id:])} has a line already")
+        seen.add(key)
+        try:
+            rows.append([float("nan") if v in missing else float(v) for v in parts[n_id:]])
+        except ValueError:
+            raise LdxError(f"{path}: line {no}: a {what} value that is no number") from None
+    return (fid if n_id == 2 else None), iid, names, np.asarray(rows, dtype=np.float64).reshape(len(rows), len(names))
+
+
+def read_pheno(path) -> tuple:
+    """(fid, iid, names, values) of a phenotype table (PLINK 2's --pheno): ``NA``, ``nan`` and ``-9`` are missing (NaN);
+    ``fid`` is None when the table has no FID column."""
+    return _sample_table(os.fspath(path), "phenotype", PHENO_MISSING)
+
+
+def read_covar(path) -> tuple:
+    """(fid, iid, names, values) of a covariate table (PLINK 2's --covar; an ``.eigenvec`` is one): ``NA`` and ``nan`` are
+    missing (NaN); -9 is a value."""
+    return _sample_table(os.fspath(path), "covariate", PHENO_MISSING[:2])
