@@ -17,11 +17,17 @@
                                             (both: missing="pairwise" = over the individuals called at both SNPs)
     ld_em_band(panel, positions, ...)       the EM r and D' of every in-window pair of ONE panel, kept in ld_band's layout;
                                             ld_neighbors / ld_clump / ld_prune(em=True) are the lists and selections on them
+    ld_decay / ld_blocks                    LD decay curves per distance bin; haplotype blocks by the four-gamete test
+    ld_dprime_ci / ld_gabriel_blocks        D' confidence bounds on the EM band and Gabriel's haplotype blocks
+    sample_counts / king_kinship / ibs_matrix   IBS counts and KING-robust kinship between the individuals
+    GenoOperator / geno_matmul / geno_rmatmul   genotype products on the matrix cores, exact integers
+    sample_pca / polygenic_score            sample PCA and per-SNP weights applied to the individuals, on those products
+    ld_glm(panel, Y, covar, ...)            linear association scan on the reverse genotype product
     pair_counts(panel_i, panel_j)           <- calc_ld.py:32           (bit-exact n11 block)
     ld_from_counts(n, n11, a1, r1, a2, r2)  <- calc_ld.py:33-97        (the epilogue alone)
 
-Every function enqueues HIP kernels of libldx.so on torch's current stream and returns device
-tensors; nothing here computes LD on the host.
+Every device function enqueues HIP kernels of libldx.so on torch's current stream and returns device tensors.  The
+``*_host`` functions are the numpy mirrors the tests compare against; each stands next to the call it mirrors.
 """
 from __future__ import annotations
 
@@ -67,15 +73,52 @@ def _band_path(path: Optional[str]) -> int:
     return PATHS["fp4" if path is None else path]
 
 
+def _ws(workspace: torch.Tensor) -> Tuple[int, int]:
+    """A workspace's two arguments of a library entry: its address and its size in bytes."""
+    return workspace.data_ptr(), workspace.numel() * workspace.element_size()
+
+
 def _band_workspace(size_fn, panel: PackedPanel, workspace: Optional[torch.Tensor]) -> torch.Tensor:
     """A band operator's workspace: the caller's, checked against ``size_fn`` (its ldx_ld_*_workspace_bytes), or a new one
     (the call's first kernels set what they read: no initialisation)."""
     need = size_fn(panel.n_snps, panel.n_hap)
     if workspace is None:
         return torch.empty(need, dtype=torch.uint8, device=panel.device)
-    if workspace.numel() * workspace.element_size() < need:
+    if _ws(workspace)[1] < need:
         raise _lib.LdxError(f"workspace too small: {need} bytes needed")
     return workspace
+
+
+def _phased_panel(panel: PackedPanel) -> tuple:
+    """The panel's arguments of the phased band entries: alt, acnt, rcnt, fa, fr."""
+    return (panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), panel.fa.data_ptr(),
+            panel.fr.data_ptr())
+
+
+def _dosage_panel(panel: PackedPanel) -> tuple:
+    """The panel's arguments of the genotype-dosage entries: alt, gstat (PackedPanel.dosage_stats, cached on the panel)."""
+    return panel.alt.data_ptr(), panel.dosage_stats()[1].data_ptr()
+
+
+def _keep_mask(keep, n: int) -> Optional[np.ndarray]:
+    if keep is None:
+        return None
+    k = keep.cpu().numpy() if isinstance(keep, torch.Tensor) else np.asarray(keep)
+    if k.shape != (n,) or (k.dtype != bool and not np.isin(k, (0, 1)).all()):
+        raise _lib.LdxError(f"keep must be a boolean array of shape [{n}]")
+    return k.astype(bool)
+
+
+def _keep_dev(keep, n: int, dev) -> Optional[torch.Tensor]:
+    """_keep_mask as the entries take it: a contiguous uint8 tensor [n] on ``dev``, None for no mask."""
+    k = _keep_mask(keep, n)
+    return None if k is None else torch.from_numpy(k.astype(np.uint8)).to(dev)
+
+
+def _even_n_hap(what: str, panel: PackedPanel) -> None:
+    """The operators over individuals need both haplotypes of each one."""
+    if panel.n_hap % 2:
+        raise _lib.LdxError(f"{what}: n_hap must be even (haplotypes 2a and 2a + 1 are individual a), got {panel.n_hap}")
 
 
 def _plan_workspace(size_fn, panel: PackedPanel, workspace: Optional[torch.Tensor]) -> torch.Tensor:
@@ -308,9 +351,9 @@ def ld_triangle(panel: PackedPanel, unit_range: Optional[Tuple[int, int]] = None
         if out.ws is None and pcode != PATHS["popcount"]:
             out.ws = torch.zeros(lib.ldx_triangle_workspace_bytes(), dtype=torch.uint8, device=dev)
         if dosage:
-            check(lib.ldx_triangle_dosage_dev(panel.alt.data_ptr(), panel.dosage_stats()[1].data_ptr(), panel.n_snps, panel.n_hap,
-                                              u0, u1, pcode, out.r32.data_ptr(), _ptr(out.ws),
-                                              0 if out.ws is None else out.ws.numel(), _stream_ptr()), "ldx_triangle_dosage_dev")
+            check(lib.ldx_triangle_dosage_dev(*_dosage_panel(panel), panel.n_snps, panel.n_hap, u0, u1, pcode,
+                                              out.r32.data_ptr(), _ptr(out.ws), 0 if out.ws is None else out.ws.numel(),
+                                              _stream_ptr()), "ldx_triangle_dosage_dev")
             return out
         check(lib.ldx_triangle_ex_dev(panel.alt.data_ptr(), panel.fa.data_ptr(), panel.fr.data_ptr(),
                                       panel.q.data_ptr(), panel.n_snps, panel.n_hap, u0, u1, pcode,
@@ -835,8 +878,7 @@ def ld_score(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, win
         diag, _ = pw_snp_stats(panel, dosage)
         check(lib.ldx_ld_pw_score_dev(*_pw_panel(panel, dosage), n, panel.n_hap, int(bool(dosage)), pos.data_ptr(),
                                       min(window, BAND_WINDOW_MAX), _ptr(annot_d), k, diag.data_ptr(), sums.data_ptr(),
-                                      workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr()),
-              "ldx_ld_pw_score_dev")
+                                      *_ws(workspace), _stream_ptr()), "ldx_ld_pw_score_dev")
         res = LDScores(sums, pos_h if pos_h is not None else pos, window, panel.n_hap, bits, k, panel, dosage=bool(dosage),
                        missing=missing)
         res._keep = (pos, annot_d, workspace, diag)
@@ -845,15 +887,11 @@ def ld_score(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, win
     workspace = _band_workspace(lib.ldx_ld_score_workspace_bytes, panel, workspace)
     sums = torch.empty((n, 1 + k), dtype=torch.uint64, device=panel.device)
     if dosage:
-        check(lib.ldx_ld_score_dosage_dev(panel.alt.data_ptr(), panel.dosage_stats()[1].data_ptr(), n, panel.n_hap,
-                                          pos.data_ptr(), window, _ptr(annot_d), k, pcode, sums.data_ptr(),
-                                          workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr()),
-              "ldx_ld_score_dosage_dev")
+        check(lib.ldx_ld_score_dosage_dev(*_dosage_panel(panel), n, panel.n_hap, pos.data_ptr(), window, _ptr(annot_d), k,
+                                          pcode, sums.data_ptr(), *_ws(workspace), _stream_ptr()), "ldx_ld_score_dosage_dev")
     else:
-        check(lib.ldx_ld_score_dev(panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), panel.fa.data_ptr(),
-                                   panel.fr.data_ptr(), n, panel.n_hap, pos.data_ptr(), window, _ptr(annot_d), k, pcode,
-                                   sums.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                   _stream_ptr()), "ldx_ld_score_dev")
+        check(lib.ldx_ld_score_dev(*_phased_panel(panel), n, panel.n_hap, pos.data_ptr(), window, _ptr(annot_d), k, pcode,
+                                   sums.data_ptr(), *_ws(workspace), _stream_ptr()), "ldx_ld_score_dev")
     res = LDScores(sums, pos_h, window, panel.n_hap, bits, k, panel, dosage=bool(dosage))
     if pos_h is None:   # positions stayed on the device: fetched with m
         res.positions = pos      # type: ignore[assignment]
@@ -984,12 +1022,7 @@ def ld_decay(panel: PackedPanel, positions=None, window_bp: int = 250_000, windo
         least = min(window, DECAY_WINDOW_MAX) // _lib.DECAY_MAX_BINS + 1
         raise _lib.LdxError(f"{n_bins} bins > DECAY_MAX_BINS {_lib.DECAY_MAX_BINS}: the smallest admissible bin_bp for this "
                             f"window is {least}")
-    keep_d = None
-    if keep is not None:
-        k = keep.cpu().numpy() if isinstance(keep, torch.Tensor) else np.asarray(keep)
-        if k.shape != (n,) or (k.dtype != bool and not np.isin(k, (0, 1)).all()):
-            raise _lib.LdxError(f"keep must be a boolean array of shape [{n}]")
-        keep_d = torch.as_tensor(np.ascontiguousarray(k.astype(np.uint8))).to(panel.device)
+    keep_d = _keep_dev(keep, n, panel.device)
     pcode = _band_path(path)
     workspace = _band_workspace(lib.ldx_ld_decay_workspace_bytes, panel, workspace)
     sums = torch.empty(n_bins, dtype=torch.uint64, device=panel.device)
@@ -1001,10 +1034,9 @@ def ld_decay(panel: PackedPanel, positions=None, window_bp: int = 250_000, windo
 
 
 def _decay_launch(panel, pos, window, width, keep_d, pcode, sums, counts, workspace) -> None:
-    check(lib.ldx_ld_decay_dev(panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), panel.fa.data_ptr(),
-                               panel.fr.data_ptr(), panel.n_snps, panel.n_hap, pos.data_ptr(), window, width, _ptr(keep_d),
-                               pcode, sums.data_ptr(), counts.data_ptr(), sums.numel(), workspace.data_ptr(),
-                               workspace.numel() * workspace.element_size(), _stream_ptr()), "ldx_ld_decay_dev")
+    check(lib.ldx_ld_decay_dev(*_phased_panel(panel), panel.n_snps, panel.n_hap, pos.data_ptr(), window, width, _ptr(keep_d),
+                               pcode, sums.data_ptr(), counts.data_ptr(), sums.numel(), *_ws(workspace), _stream_ptr()),
+          "ldx_ld_decay_dev")
 
 
 # --------------------------------------------------------------------------- haplotype blocks (four-gamete test)
@@ -1136,17 +1168,12 @@ def ld_blocks(panel: PackedPanel, positions=None, window_bp: int = 500_000, wind
     min_count = int(min_count)
     if not 1 <= min_count <= panel.n_hap:
         raise _lib.LdxError(f"min_count must be 1 .. n_hap ({panel.n_hap}), got {min_count}")
-    kept = None
-    if keep is not None:
-        k = keep.cpu().numpy() if isinstance(keep, torch.Tensor) else np.asarray(keep)
-        if k.shape != (n,) or (k.dtype != bool and not np.isin(k, (0, 1)).all()):
-            raise _lib.LdxError(f"keep must be a boolean array of shape [{n}]")
-        kept = k.astype(bool)
+    kept = _keep_mask(keep, n)
     if maf_min > 0.0:
         a = panel.alt_counts().astype(np.int64)
         common = np.minimum(a, panel.n_hap - a) >= float(maf_min) * panel.n_hap
         kept = common if kept is None else kept & common
-    keep_d = None if kept is None else torch.as_tensor(np.ascontiguousarray(kept.astype(np.uint8))).to(panel.device)
+    keep_d = None if kept is None else torch.from_numpy(kept.astype(np.uint8)).to(panel.device)
     pcode = _band_path(path)
     workspace = _band_workspace(lib.ldx_ld_fgt_workspace_bytes, panel, workspace)
     left = torch.empty(n, dtype=torch.int32, device=panel.device)
@@ -1161,8 +1188,7 @@ def ld_blocks(panel: PackedPanel, positions=None, window_bp: int = 500_000, wind
 
 def _fgt_launch(panel, pos, window, min_count, keep_d, pcode, left, workspace) -> None:
     check(lib.ldx_ld_fgt_dev(panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.n_snps, panel.n_hap, pos.data_ptr(), window,
-                             min_count, _ptr(keep_d), pcode, left.data_ptr(), workspace.data_ptr(),
-                             workspace.numel() * workspace.element_size(), _stream_ptr()), "ldx_ld_fgt_dev")
+                             min_count, _ptr(keep_d), pcode, left.data_ptr(), *_ws(workspace), _stream_ptr()), "ldx_ld_fgt_dev")
 
 
 def _blocks_launch(left, pos, keep_d, n, window, block_of, n_out) -> None:
@@ -1356,16 +1382,13 @@ class LDCross:
 
 
 def _cross_launch(panel, pos, window, pcode, sides, cross, workspace) -> None:
-    check(lib.ldx_ld_cross_dev(panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), panel.fa.data_ptr(),
-                               panel.fr.data_ptr(), panel.n_snps, panel.n_hap, pos.data_ptr(), window, pcode,
-                               sides.data_ptr(), cross.data_ptr(), workspace.data_ptr(),
-                               workspace.numel() * workspace.element_size(), _stream_ptr()), "ldx_ld_cross_dev")
+    check(lib.ldx_ld_cross_dev(*_phased_panel(panel), panel.n_snps, panel.n_hap, pos.data_ptr(), window, pcode,
+                               sides.data_ptr(), cross.data_ptr(), *_ws(workspace), _stream_ptr()), "ldx_ld_cross_dev")
 
 
 def _split_launch(cross, n, min_snps, max_snps, cuts, n_out, workspace) -> None:
     check(lib.ldx_ld_split_dev(cross.data_ptr(), n, min_snps, max_snps, cuts.data_ptr(), n_out.data_ptr(),
-                               workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr()),
-          "ldx_ld_split_dev")
+                               *_ws(workspace), _stream_ptr()), "ldx_ld_split_dev")
 
 
 def ld_cross(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, window_snps: Optional[int] = None,
@@ -1598,10 +1621,8 @@ def _matvec_launch(panel: PackedPanel, pos: torch.Tensor, window: int, x32: torc
     n, k = x32.shape
     workspace = _band_workspace(lib.ldx_ld_matvec_workspace_bytes, panel, workspace)
     sums = torch.empty((n, k), dtype=torch.int64, device=panel.device)
-    check(lib.ldx_ld_matvec_dev(panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), panel.fa.data_ptr(),
-                                panel.fr.data_ptr(), n, panel.n_hap, pos.data_ptr(), window, x32.data_ptr(), k, power, pcode,
-                                sums.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                _stream_ptr()), "ldx_ld_matvec_dev")
+    check(lib.ldx_ld_matvec_dev(*_phased_panel(panel), n, panel.n_hap, pos.data_ptr(), window, x32.data_ptr(), k, power, pcode,
+                                sums.data_ptr(), *_ws(workspace), _stream_ptr()), "ldx_ld_matvec_dev")
     return sums, workspace
 
 
@@ -1936,20 +1957,17 @@ def ld_band(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, wind
     dev = panel.device
     lo, offsets, n_cells = _band_layout(pos, n, window, dev)
     values = torch.empty(n_cells, dtype=torch.float32, device=dev)
-    ws_bytes = workspace.numel() * workspace.element_size()
     if dosage:
-        gstat = panel.dosage_stats()[1]
-        check(lib.ldx_ld_band_dosage_dev(panel.alt.data_ptr(), gstat.data_ptr(), n, panel.n_hap, pos.data_ptr(), window, pcode,
-                                         lo.data_ptr(), offsets.data_ptr(), _ptr(values) if n_cells else None, n_cells,
-                                         workspace.data_ptr(), ws_bytes, _stream_ptr()), "ldx_ld_band_dosage_dev")
-        live = gstat[:n, 1] > 0.0
+        check(lib.ldx_ld_band_dosage_dev(*_dosage_panel(panel), n, panel.n_hap, pos.data_ptr(), window, pcode, lo.data_ptr(),
+                                         offsets.data_ptr(), _ptr(values) if n_cells else None, n_cells, *_ws(workspace),
+                                         _stream_ptr()), "ldx_ld_band_dosage_dev")
+        live = panel.dosage_stats()[1][:n, 1] > 0.0
         diag = torch.where(live, torch.ones((), dtype=torch.float32, device=dev),
                            torch.full((), -0.0, dtype=torch.float32, device=dev))
     else:
-        check(lib.ldx_ld_band_dev(panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), panel.fa.data_ptr(),
-                                  panel.fr.data_ptr(), n, panel.n_hap, pos.data_ptr(), window, pcode, lo.data_ptr(),
-                                  offsets.data_ptr(), _ptr(values) if n_cells else None, n_cells, workspace.data_ptr(),
-                                  ws_bytes, _stream_ptr()), "ldx_ld_band_dev")
+        check(lib.ldx_ld_band_dev(*_phased_panel(panel), n, panel.n_hap, pos.data_ptr(), window, pcode, lo.data_ptr(),
+                                  offsets.data_ptr(), _ptr(values) if n_cells else None, n_cells, *_ws(workspace),
+                                  _stream_ptr()), "ldx_ld_band_dev")
         # r_matrix()'s diagonal (ldx_common.h, r32_diag): (n - a) / r in fp64, rounded to float32 once; -0.0f where a r == 0
         a, r = panel.acnt[:n].to(torch.float64), panel.rcnt[:n].to(torch.float64)
         live = (a * r) != 0
@@ -2164,45 +2182,17 @@ def ld_neighbors(panel: PackedPanel, positions=None, window_bp: int = 250_000, w
                                         hit_capacity, workspace)
         return LDNeighbors(offsets, hits, n, window, bound, bool(dosage), missing)
     pcode = _band_path(path)
-    dev = panel.device
     workspace = _band_workspace(lib.ldx_ld_neighbors_workspace_bytes, panel, workspace)
-    fin_bytes = lib.ldx_area_finish_workspace_bytes(n)
-    fin = torch.empty(fin_bytes, dtype=torch.uint8, device=dev)
-    counts = lib.ldx_area_finish_counts(fin.data_ptr())   # the band counts per row as it stores: no counting pass
-    cap = int(hit_capacity) if hit_capacity is not None else max(1 << 20, 32 * n)
-    n_hits = torch.zeros(1, dtype=torch.int64, device=dev)
-    summary = torch.zeros(2, dtype=torch.int64, device=dev)
-    offsets = torch.empty(n + 1, dtype=torch.int32, device=dev)
-    for attempt in range(4):
-        if not 0 <= cap < (1 << 32):
-            raise _lib.LdxError(f"ld_neighbors: {cap} record slots needed; the CSR's offsets are uint32 (at most 2^32 - 1)")
-        raw = torch.empty((cap, 4), dtype=torch.int32, device=dev)
-        hits = torch.empty((cap, 4), dtype=torch.int32, device=dev)
-        if dosage:
-            check(lib.ldx_ld_neighbors_dosage_dev(panel.alt.data_ptr(), panel.dosage_stats()[1].data_ptr(), n, panel.n_hap,
-                                                  pos.data_ptr(), window, float(bound), pcode, raw.data_ptr(), cap,
-                                                  n_hits.data_ptr(), counts, workspace.data_ptr(),
-                                                  workspace.numel() * workspace.element_size(), _stream_ptr()),
-                  "ldx_ld_neighbors_dosage_dev")
-        else:
-            check(lib.ldx_ld_neighbors_dev(panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(),
-                                           panel.fa.data_ptr(), panel.fr.data_ptr(), n, panel.n_hap, pos.data_ptr(), window,
-                                           float(bound), pcode, raw.data_ptr(), cap, n_hits.data_ptr(), counts,
-                                           workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr()),
-                  "ldx_ld_neighbors_dev")
-        check(lib.ldx_area_finish_ex_dev(raw.data_ptr(), n_hits.data_ptr(), cap, n, hits.data_ptr(), offsets.data_ptr(),
-                                         summary.data_ptr(), fin.data_ptr(), fin_bytes, 1, _stream_ptr()),
-              "ldx_area_finish_ex_dev")
-        total, reserved = (int(x) for x in summary.tolist())
-        if reserved <= cap:
-            break
-        # the slots the run reserved (records + the batches' unused tails): the count a re-run needs, give or take the tails
-        # of a different work order -- hence the margin and, in the worst case, another run
-        cap = reserved + reserved // 64 + (1 << 16)
-    else:
-        raise _lib.LdxError("ld_neighbors: the record count did not settle")
-    del raw
-    return LDNeighbors(offsets, hits[:total], n, window, bound, bool(dosage))
+    entry = "ldx_ld_neighbors_dosage_dev" if dosage else "ldx_ld_neighbors_dev"
+    head = _dosage_panel(panel) if dosage else _phased_panel(panel)
+
+    def launch(raw, cap, n_hits, counts):
+        check(getattr(lib, entry)(*head, n, panel.n_hap, pos.data_ptr(), window, float(bound), pcode, raw.data_ptr(), cap,
+                                  n_hits.data_ptr(), counts, *_ws(workspace), _stream_ptr()), entry)
+
+    # the default capacity is max(2^20, 32 n): _rect_hits_run's with no panel J
+    offsets, hits = _rect_hits_run("ld_neighbors", launch, n, 0, panel.device, hit_capacity, counts_ready=1)
+    return LDNeighbors(offsets, hits, n, window, bound, bool(dosage))
 
 
 def select_dev(nb: LDNeighbors, rank, member_ok, batch: int = SELECT_BATCH) -> Tuple[np.ndarray, np.ndarray, int]:
@@ -2376,7 +2366,7 @@ def _rect_out(what: str, name: str, out, n_i: int, n_j: int, dev):
 def _rect_side(panel: PackedPanel, dosage: bool) -> tuple:
     """One side's arguments of the rectangle entries: alt, gstat, n (dosage) or alt, acnt, rcnt, n."""
     if dosage:
-        return panel.alt.data_ptr(), panel.dosage_stats()[1].data_ptr(), panel.n_snps
+        return (*_dosage_panel(panel), panel.n_snps)
     return panel.alt.data_ptr(), panel.acnt.data_ptr(), panel.rcnt.data_ptr(), panel.n_snps
 
 
@@ -2432,8 +2422,8 @@ def _pw_band(panel: PackedPanel, pos, pos_h, window: int, workspace, dosage: boo
     lo, offsets, n_cells = _band_layout(pos, n, window, dev)
     values = torch.empty(n_cells, dtype=torch.float32, device=dev)
     check(lib.ldx_ld_pw_band_dev(*_pw_panel(panel, dosage), n, panel.n_hap, int(dosage), pos.data_ptr(), window, lo.data_ptr(),
-                                 offsets.data_ptr(), _ptr(values) if n_cells else None, n_cells, workspace.data_ptr(),
-                                 workspace.numel() * workspace.element_size(), _stream_ptr()), "ldx_ld_pw_band_dev")
+                                 offsets.data_ptr(), _ptr(values) if n_cells else None, n_cells, *_ws(workspace), _stream_ptr()),
+          "ldx_ld_pw_band_dev")
     diag, _ = pw_snp_stats(panel, dosage)
     res = LDBand(values, lo, offsets, diag, pos if pos_h is None else pos_h, window, dosage, panel.n_hap, missing=missing)
     res._keep = (pos, workspace)   # alive until the launch is done
@@ -2547,7 +2537,7 @@ def ld_rect_hits(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, r2
 
     entry = "ldx_ld_rect_hits_dosage_dev" if dosage else "ldx_ld_rect_hits_dev"
 
-    def launch(raw, cap, n_hits):
+    def launch(raw, cap, n_hits, _counts):
         if pairwise:
             check(lib.ldx_ld_rect_pw_hits_dev(*_pw_side(panel_i), *_pw_side(pj), panel_i.n_hap, int(bool(dosage)), float(bound),
                                               raw.data_ptr(), cap, n_hits.data_ptr(), _stream_ptr()), "ldx_ld_rect_pw_hits_dev")
@@ -2625,12 +2615,16 @@ def pairwise_cell_host(counts, dosage: bool = False) -> np.ndarray:
     return np.where(s == 0.0, np.float32(-0.0), (num * s).astype(np.float32)).astype(np.float32)
 
 
-def _rect_hits_run(what: str, launch, n_i: int, n_j: int, dev, hit_capacity: Optional[int]):
-    """The hit entries' buffers and retry loop: ``launch(raw, cap, n_hits)`` enqueues one run into ``cap`` record slots,
+def _rect_hits_run(what: str, launch, n_i: int, n_j: int, dev, hit_capacity: Optional[int], counts_ready: int = 0):
+    """The hit entries' buffers and retry loop: ``launch(raw, cap, n_hits, counts)`` enqueues one run into ``cap`` record slots,
     ldx_area_finish_ex_dev sorts what it stored into a CSR over the rows of panel I; a run that reserved more slots than it
-    had runs again at the reserved count plus ld_neighbors' margin, at most four times.  Returns (offsets, sorted records)."""
+    had runs again at the reserved count plus a margin, at most four times.  ``counts_ready`` = 1 (ld_neighbors' band, which
+    counts per row as it stores: no counting pass): ``counts`` is where the finishing step expects those counts
+    (ldx_area_finish_counts); 0: ``counts`` is None and the finishing step counts the stored records per row itself.
+    Returns (offsets, sorted records)."""
     fin_bytes = lib.ldx_area_finish_workspace_bytes(n_i)
     fin = torch.empty(fin_bytes, dtype=torch.uint8, device=dev)
+    counts = lib.ldx_area_finish_counts(fin.data_ptr()) if counts_ready else None
     cap = int(hit_capacity) if hit_capacity is not None else max(1 << 20, 32 * (n_i + n_j))
     n_hits = torch.zeros(1, dtype=torch.int64, device=dev)
     summary = torch.zeros(2, dtype=torch.int64, device=dev)
@@ -2640,15 +2634,16 @@ def _rect_hits_run(what: str, launch, n_i: int, n_j: int, dev, hit_capacity: Opt
             raise _lib.LdxError(f"{what}: {cap} record slots needed; the CSR's offsets are uint32 (at most 2^32 - 1)")
         raw = torch.empty((cap, 4), dtype=torch.int32, device=dev)
         hits = torch.empty((cap, 4), dtype=torch.int32, device=dev)
-        launch(raw, cap, n_hits)
-        # the finishing step counts the stored records per row itself (counts_ready = 0): rows are panel I's
+        launch(raw, cap, n_hits, counts)
         check(lib.ldx_area_finish_ex_dev(raw.data_ptr(), n_hits.data_ptr(), cap, n_i, hits.data_ptr(), offsets.data_ptr(),
-                                         summary.data_ptr(), fin.data_ptr(), fin_bytes, 0, _stream_ptr()),
+                                         summary.data_ptr(), fin.data_ptr(), fin_bytes, counts_ready, _stream_ptr()),
               "ldx_area_finish_ex_dev")
         total, reserved = (int(x) for x in summary.tolist())
         if reserved <= cap:
             break
-        cap = reserved + reserved // 64 + (1 << 16)   # ld_neighbors' margin: the batches' tails differ with the work order
+        # the slots the run reserved (records + the batches' unused tails): the count a re-run needs, give or take the tails
+        # of a different work order -- hence the margin and, in the worst case, another run
+        cap = reserved + reserved // 64 + (1 << 16)
     else:
         raise _lib.LdxError(f"{what}: the record count did not settle")
     del raw
@@ -2661,10 +2656,9 @@ def _plan_neighbors(entry: str, size_fn, panel: PackedPanel, head: tuple, pos, w
     n = panel.n_snps
     workspace = _plan_workspace(size_fn, panel, workspace)
 
-    def launch(raw, cap, n_hits):
+    def launch(raw, cap, n_hits, _counts):
         check(getattr(lib, entry)(*head, pos.data_ptr(), min(window, BAND_WINDOW_MAX), float(bound), raw.data_ptr(), cap,
-                                  n_hits.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                  _stream_ptr()), entry)
+                                  n_hits.data_ptr(), *_ws(workspace), _stream_ptr()), entry)
 
     cap = int(hit_capacity) if hit_capacity is not None else max(1 << 20, 32 * n)
     return _rect_hits_run("ld_neighbors", launch, n, 0, panel.device, cap)
@@ -2738,7 +2732,7 @@ def ld_em_hits(panel_i: PackedPanel, panel_j: Optional[PackedPanel] = None, r2: 
     require_gpu()
     n_i, n_j = panel_i.n_snps, pj.n_snps
 
-    def launch(raw, cap, n_hits):
+    def launch(raw, cap, n_hits, _counts):
         if pairwise:
             check(lib.ldx_ld_em_rect_pw_hits_dev(*_pw_side(panel_i), *_pw_side(pj), panel_i.n_hap, float(bound), raw.data_ptr(),
                                                  cap, n_hits.data_ptr(), _stream_ptr()), "ldx_ld_em_rect_pw_hits_dev")
@@ -2826,8 +2820,7 @@ def ld_em_band(panel: PackedPanel, positions=None, window_bp: int = 1_000_000, w
     vals = [torch.empty(n_cells, dtype=torch.float32, device=dev) if want else None for want in (want_r, want_dprime)]
     check(lib.ldx_ld_em_band_dev(*_em_panel(panel, pairwise), n, panel.n_hap, int(pairwise), pos.data_ptr(), window, lo.data_ptr(),
                                  offsets.data_ptr(), *(_ptr(v) if v is not None and n_cells else None for v in vals), n_cells,
-                                 workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr()),
-          "ldx_ld_em_band_dev")
+                                 *_ws(workspace), _stream_ptr()), "ldx_ld_em_band_dev")
     _, _, diag, live = em_snp_stats(panel, pairwise)
     bands = []
     for v in vals:
@@ -2946,7 +2939,6 @@ def em_host(n_ind: int, a_i: int, a_j: int, S: int, H: int) -> Tuple[float, floa
     form; g monotone or one rising branch with a sign change: one bracketed Newton root, no logarithm; two candidates: the
     larger l, the smaller x on a tie -- but is not promised to match it bit for bit.  A degenerate pair gives (0, -0.0, -0.0),
     a tuple that is no genotype table three NaNs."""
-    import math
     N, ai, aj, S, H = int(n_ind), int(a_i), int(a_j), int(S), int(H)
     T = 2 * N
     n1 = (S - H) // 2
@@ -3249,15 +3241,6 @@ class LDCiBand:
         return out[0], out[1]
 
 
-def _keep_mask(keep, n: int) -> Optional[np.ndarray]:
-    if keep is None:
-        return None
-    k = keep.cpu().numpy() if isinstance(keep, torch.Tensor) else np.asarray(keep)
-    if k.shape != (n,) or (k.dtype != bool and not np.isin(k, (0, 1)).all()):
-        raise _lib.LdxError(f"keep must be a boolean array of shape [{n}]")
-    return k.astype(bool)
-
-
 def ld_dprime_ci(panel: PackedPanel, positions=None, window_bp: int = 500_000, window_snps: Optional[int] = None,
                  missing: Optional[str] = None, keep=None, maf_min: float = 0.05, workspace: Optional[torch.Tensor] = None,
                  check_positions: bool = True) -> LDCiBand:
@@ -3289,8 +3272,8 @@ def ld_dprime_ci(panel: PackedPanel, positions=None, window_bp: int = 500_000, w
     ci_hi = torch.empty(n_cells, dtype=torch.uint8, device=dev)
     check(lib.ldx_ld_em_ci_band_dev(*_em_panel(panel, pairwise), n, panel.n_hap, int(pairwise), pos.data_ptr(), window,
                                     kept.data_ptr(), lo.data_ptr(), offsets.data_ptr(), _ptr(ci_lo) if n_cells else None,
-                                    _ptr(ci_hi) if n_cells else None, n_cells, workspace.data_ptr(),
-                                    workspace.numel() * workspace.element_size(), _stream_ptr()), "ldx_ld_em_ci_band_dev")
+                                    _ptr(ci_hi) if n_cells else None, n_cells, *_ws(workspace), _stream_ptr()),
+          "ldx_ld_em_ci_band_dev")
     res = LDCiBand(ci_lo, ci_hi, lo, offsets, kept, pos if pos_h is None else pos_h, window, n_cells, missing)
     res._keep = (pos, workspace)   # alive until the launch is done
     return res
@@ -3506,6 +3489,23 @@ class SampleCounts:
         return RelatedPairs(a.cpu().numpy(), b.cpu().numpy(), kin[a, b].cpu().numpy(), take(0), take(1), take(2))
 
 
+def _store_args(what: str, panel: PackedPanel, keep, store_snps) -> Tuple[int, Optional[torch.Tensor]]:
+    """The argument rules of the operators that build individual-major stores (sample_counts, GenoOperator), checked before
+    anything touches the device: an even n_hap, ``store_snps`` within the library's range, a boolean ``keep``.  Returns
+    (store_snps, the keep mask on the device or None)."""
+    _even_n_hap(what, panel)
+    store_snps = int(store_snps)
+    if not (1 <= store_snps <= _lib.KING_MAX_STORE_SNPS):
+        raise _lib.LdxError(f"{what}: store_snps must lie in 1..{_lib.KING_MAX_STORE_SNPS}")
+    return store_snps, _keep_dev(keep, panel.n_snps, panel.device)
+
+
+def _planes_launch(panel: PackedPanel, keep_d, begin: int, count: int, store, tables) -> None:
+    """Transpose the SNPs [begin, begin + count) of the panel into one individual-major store and its tables."""
+    check(lib.ldx_sample_planes_dev(panel.alt.data_ptr(), panel.ref.data_ptr(), panel.n_snps, panel.n_hap, _ptr(keep_d), begin,
+                                    count, store.data_ptr(), tables.data_ptr(), _stream_ptr()), "ldx_sample_planes_dev")
+
+
 def sample_counts(panel: PackedPanel, keep=None, out: Optional[SampleCounts] = None, n_slices: Optional[int] = None,
                   store_snps: int = SAMPLE_STORE_SNPS) -> SampleCounts:
     """The counts N, HH, IBS0, HET between the individuals of ``panel`` (haplotypes 2a, 2a + 1 are individual a) over the SNPs
@@ -3515,14 +3515,8 @@ def sample_counts(panel: PackedPanel, keep=None, out: Optional[SampleCounts] = N
     ``n_slices``: the K slices per tile (None: the library's choice).  Every cell is an exact integer; the result does not
     depend on the order or the split of the SNPs."""
     require_gpu()
-    if panel.n_hap % 2:
-        raise _lib.LdxError(f"sample_counts: n_hap must be even (haplotypes 2a and 2a + 1 are individual a), got {panel.n_hap}")
+    store_snps, keep_d = _store_args("sample_counts", panel, keep, store_snps)
     n_ind, n_snps, dev = panel.n_ind, panel.n_snps, panel.device
-    store_snps = int(store_snps)
-    if not (1 <= store_snps <= _lib.KING_MAX_STORE_SNPS):
-        raise _lib.LdxError(f"sample_counts: store_snps must lie in 1..{_lib.KING_MAX_STORE_SNPS}")
-    k = _keep_mask(keep, n_snps)
-    keep_d = None if k is None else torch.from_numpy(k.astype(np.uint8)).to(dev)
     if out is None:
         res = SampleCounts(torch.empty((len(SAMPLE_COUNTS), n_ind, n_ind), dtype=torch.int32, device=dev), 0)
         accumulate = 0
@@ -3535,8 +3529,7 @@ def sample_counts(panel: PackedPanel, keep=None, out: Optional[SampleCounts] = N
     tables = torch.empty(lib.ldx_sample_tables_bytes(n_ind) // 4, dtype=torch.int32, device=dev)
     for begin in range(0, n_snps, store_snps):
         count = min(store_snps, n_snps - begin)
-        check(lib.ldx_sample_planes_dev(panel.alt.data_ptr(), panel.ref.data_ptr(), n_snps, panel.n_hap, _ptr(keep_d), begin, count,
-                                        store.data_ptr(), tables.data_ptr(), _stream_ptr()), "ldx_sample_planes_dev")
+        _planes_launch(panel, keep_d, begin, count, store, tables)
         check(lib.ldx_sample_counts_dev(store.data_ptr(), tables.data_ptr(), n_ind, count, res.counts.data_ptr(), n_ind, accumulate,
                                         res.n_snps if accumulate else 0, int(n_slices or 0), _stream_ptr()), "ldx_sample_counts_dev")
         res.n_snps += count
@@ -3709,6 +3702,17 @@ def _geno_weights(what: str, q, rows: int, dev, k: Optional[int] = None) -> torc
     return t
 
 
+def _rmatmul_launch(panel: PackedPanel, keep_d: Optional[torch.Tensor], u: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The reverse product's launch on checked weights ``u`` (_geno_weights, [n_ind, k]): (z, zc), int64 [n_snps, k] each.  It reads
+    the panel's own planes, so a caller that needs no forward product (ld_glm) calls it without a GenoOperator and its stores."""
+    k = int(u.shape[1])
+    z = torch.empty((panel.n_snps, k), dtype=torch.int64, device=panel.device)
+    zc = torch.empty((panel.n_snps, k), dtype=torch.int64, device=panel.device)
+    check(lib.ldx_geno_rmatmul_dev(panel.alt.data_ptr(), panel.ref.data_ptr(), panel.n_snps, panel.n_hap, _ptr(keep_d), u.data_ptr(),
+                                   k, k, z.data_ptr(), zc.data_ptr(), k, _stream_ptr()), "ldx_geno_rmatmul_dev")
+    return z, zc
+
+
 class GenoOperator:
     """The operator A = [G | C] of a panel over the SNPs that pass ``keep`` (include/ldx.h, "genotype products"): G the ALT
     dosages of the individuals (0 where missing), C the called flags.  The individual-major store(s) of the forward product are
@@ -3717,21 +3721,14 @@ class GenoOperator:
 
     def __init__(self, panel: PackedPanel, keep=None, store_snps: int = SAMPLE_STORE_SNPS):
         require_gpu()
-        if panel.n_hap % 2:
-            raise _lib.LdxError(f"GenoOperator: n_hap must be even (haplotypes 2a and 2a + 1 are individual a), got {panel.n_hap}")
-        store_snps = int(store_snps)
-        if not (1 <= store_snps <= _lib.KING_MAX_STORE_SNPS):
-            raise _lib.LdxError(f"GenoOperator: store_snps must lie in 1..{_lib.KING_MAX_STORE_SNPS}")
+        store_snps, self._keep_d = _store_args("GenoOperator", panel, keep, store_snps)
         self.panel, self.n_ind, self.n_snps, self.device = panel, panel.n_ind, panel.n_snps, panel.device
-        k = _keep_mask(keep, panel.n_snps)
-        self._keep_d = None if k is None else torch.from_numpy(k.astype(np.uint8)).to(self.device)
         self._stores = []
         for begin in range(0, self.n_snps, store_snps):
             count = min(store_snps, self.n_snps - begin)
             store = torch.empty(lib.ldx_sample_planes_bytes(self.n_ind, count), dtype=torch.uint8, device=self.device)
             tables = torch.empty(lib.ldx_sample_tables_bytes(self.n_ind) // 4, dtype=torch.int32, device=self.device)
-            check(lib.ldx_sample_planes_dev(panel.alt.data_ptr(), panel.ref.data_ptr(), self.n_snps, panel.n_hap, _ptr(self._keep_d),
-                                            begin, count, store.data_ptr(), tables.data_ptr(), _stream_ptr()), "ldx_sample_planes_dev")
+            _planes_launch(panel, self._keep_d, begin, count, store, tables)
             self._stores.append((begin, count, store, tables))
 
     def called_counts(self) -> torch.Tensor:
@@ -3764,14 +3761,7 @@ class GenoOperator:
     def rmatmul_q(self, q_u) -> Tuple[torch.Tensor, torch.Tensor]:
         """(z, zc) = (G^T q_u, C^T q_u) on raw int32 weights [n_ind, k]: two int64 device tensors [n_snps, k]; the rows of SNPs
         that are not kept are 0."""
-        u = _geno_weights("rmatmul_q", q_u, self.n_ind, self.device)
-        k = int(u.shape[1])
-        z = torch.empty((self.n_snps, k), dtype=torch.int64, device=self.device)
-        zc = torch.empty((self.n_snps, k), dtype=torch.int64, device=self.device)
-        p = self.panel
-        check(lib.ldx_geno_rmatmul_dev(p.alt.data_ptr(), p.ref.data_ptr(), self.n_snps, p.n_hap, _ptr(self._keep_d), u.data_ptr(), k, k,
-                                       z.data_ptr(), zc.data_ptr(), k, _stream_ptr()), "ldx_geno_rmatmul_dev")
-        return z, zc
+        return _rmatmul_launch(self.panel, self._keep_d, _geno_weights("rmatmul_q", q_u, self.n_ind, self.device))
 
     def matmul(self, W, Wc=None, n_slices: Optional[int] = None) -> GenoProduct:
         """G W + C Wc for float matrices [n_snps, k] (geno_quantize: they share the column exponents)."""
@@ -3885,8 +3875,7 @@ class _HostEngine(_GenoEngine):
 def _engine(what: str, source, keep) -> _GenoEngine:
     if isinstance(source, PackedPanel):
         require_gpu()
-        if source.n_hap % 2:
-            raise _lib.LdxError(f"{what}: n_hap must be even (haplotypes 2a and 2a + 1 are individual a), got {source.n_hap}")
+        _even_n_hap(what, source)
         return _DeviceEngine(source, keep)
     return _HostEngine(source, keep)
 
@@ -4254,11 +4243,8 @@ def geno_snp_counts(panel: PackedPanel, keep=None) -> torch.Tensor:
     and a zero, from the panel's planes with the reverse genotype product's own words (ldx_geno_snp_counts_dev); the rows of SNPs
     that ``keep`` drops are 0."""
     require_gpu()
-    if panel.n_hap % 2:
-        raise _lib.LdxError(f"geno_snp_counts: n_hap must be even (haplotypes 2a and 2a + 1 are individual a), got {panel.n_hap}")
-    k = _keep_mask(keep, panel.n_snps)
-    keep_d = None if k is None else torch.from_numpy(k.astype(np.uint8)).to(panel.device)
-    return _snp_counts(panel, keep_d)
+    _even_n_hap("geno_snp_counts", panel)
+    return _snp_counts(panel, _keep_dev(keep, panel.n_snps, panel.device))
 
 
 def _snp_counts(panel: PackedPanel, keep_d: Optional[torch.Tensor]) -> torch.Tensor:
@@ -4324,23 +4310,18 @@ def ld_glm(panel: PackedPanel, Y, covar=None, individuals=None, keep=None, max_v
     ld_glm_host gives beta, se, t and the flags bit for bit."""
     require_gpu()
     _glm_missing("ld_glm", missing)
-    if panel.n_hap % 2:
-        raise _lib.LdxError(f"ld_glm: n_hap must be even (haplotypes 2a and 2a + 1 are individual a), got {panel.n_hap}")
+    _even_n_hap("ld_glm", panel)
     if not float(max_vif) > 1.0:
         raise _lib.LdxError("ld_glm: max_vif must be > 1")
     cols = _glm_columns(individuals, panel.n_ind)
     if cols is not None:
         panel = panel.select(haplotypes=cols)
     des = glm_design(_glm_matrix(Y, "ld_glm: Y", panel.n_ind), None if covar is None else _glm_matrix(covar, "ld_glm: covar", panel.n_ind))
-    mask = _keep_mask(keep, panel.n_snps)
-    keep_d = None if mask is None else torch.from_numpy(mask.astype(np.uint8)).to(panel.device)
+    keep_d = _keep_dev(keep, panel.n_snps, panel.device)
     dev, k, p = panel.device, des.n_cov + des.n_pheno, des.n_pheno
     # the reverse product alone (GenoOperator.rmatmul_q's launch): the operator would first build the individual-major stores of
     # the forward product, which a scan never reads
-    q = _geno_weights("ld_glm", des.q, panel.n_ind, dev)
-    z, zc = (torch.empty((panel.n_snps, k), dtype=torch.int64, device=dev) for _ in range(2))
-    check(lib.ldx_geno_rmatmul_dev(panel.alt.data_ptr(), panel.ref.data_ptr(), panel.n_snps, panel.n_hap, _ptr(keep_d), q.data_ptr(),
-                                   k, k, z.data_ptr(), zc.data_ptr(), k, _stream_ptr()), "ldx_geno_rmatmul_dev")
+    z, zc = _rmatmul_launch(panel, keep_d, _geno_weights("ld_glm", des.q, panel.n_ind, dev))
     counts = _snp_counts(panel, keep_d)
     exps, yy = torch.from_numpy(des.exps).to(dev), torch.from_numpy(des.yy).to(dev)
     outs = [torch.empty((panel.n_snps, p), dtype=torch.float64, device=dev) for _ in range(5)]
