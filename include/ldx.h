@@ -1207,6 +1207,60 @@ int ldx_glm_linear_dev(const int64_t *z, const int64_t *zc, size_t ld_z, const u
                        uint32_t n_cov, uint32_t n_pheno, const int64_t *exps, const double *yy, double max_vif, double *beta,
                        double *se, double *t, double *p, double *neglog10_p, uint8_t *flags, size_t ld_out, void *stream);
 
+/* ---- logistic association scan: per SNP the maximum-likelihood logistic fit of 0/1 phenotypes on the genotype, an intercept and
+ * covariates ----
+ * This project's own definition (what PLINK 2 --glm reports for a case/control trait without its Firth fallback: log odds ratio,
+ * SE, Z, P), NOT validated against PLINK 2.
+ *
+ * Individuals, called genotypes, kept SNPs and mean imputation are those of "association scan": the scan sees all N = n_ind
+ * individuals of the panel (a subset is taken first); the genotype column of SNP i is x_a = g_ia - mu_i for a called individual
+ * and 0 for a missing one, mu_i = s / n over the called.
+ * For a phenotype y in {0,1}^N and the design D = [1 | X], X with n_cov <= LDX_LOGIT_MAX_COV columns (intercept + 13 covariates +
+ * genotype = 15 parameters, one slot of a 16-wide tile left free):
+ *     theta^ = (gamma^, beta^) maximises l(theta) = sum_a [ y_a eta_a - log(1 + e^eta_a) ],  eta = D gamma + x beta
+ *     beta = beta^, the log odds ratio per ALT allele
+ *     se = sqrt([I(theta^)^-1]_bb),  I(theta) = sum_a w_a v_a v_a^T,  v_a = (d_a, x_a),  w_a = mu_a (1 - mu_a),
+ *          the information evaluated AT the reported theta^, not one step before it
+ *     z = beta / se          p = erfc(|z| / sqrt 2)
+ *     neglog10_p = -ln p / ln 10 with ln p formed in log space (ln erfcx(t) - t^2, t = |z| / sqrt 2, from t = 5 on): finite where
+ *          p underflows to 0; z = 0 gives p = 1, neglog10_p = 0 exactly.  |ln p| is within 2^-30 max(1, |ln p|) of the exact value.
+ * beta^ and se do not depend on the parametrisation of the span of D: they are functions of the codes, X and y.  The iteration
+ * path is not part of the definition.
+ * Design (the host's part, numpy fp64: ops.logit_design): thin QR of D with the refusals of "association scan"; B = sqrt(N) Q,
+ * stored column-major [n_cov + 1][N]; per phenotype the null fit gamma_0 on B by Newton from 0.  A phenotype with no case, no
+ * control, or a null fit that does not converge has a NaN row in theta0: every cell of it carries flag 4.
+ * Iteration (the device and its numpy mirror, ops.ld_glm_logistic_host): undamped Newton from (gamma_0, 0); an evaluation forms
+ * I and U = sum_a v_a (y_a - mu_a) at the current point and solves I delta = U by Cholesky; when the Newton decrement
+ * lambda^2 = U^T I^-1 U <= 2^-60 that step is applied and I evaluated once more at the new point for se; at most
+ * LDX_LOGIT_MAX_ITER evaluations.  mu and 1 - mu are formed from e^-|eta| without cancellation.
+ * flags, uint8 per cell, the first that applies; every flag other than 0 is NaN in all five outputs:
+ *     0 OK      1 SNP not kept, or n = 0      2 genotype constant among the called
+ *     3 collinear with the design: d max_vif < xx,  xx = sum_a x_a^2 (from the integer counts, as gg of "association scan"),
+ *       d = xx - sum_c (sum_a Q_ac x_a)^2;  max_vif > 1
+ *     4 phenotype unusable (a NaN in its row of theta0)
+ *     5 no finite maximiser found: the cap was reached, or I lost positive definiteness (a pivot that is not > 0, or not finite).
+ *       This covers complete and quasi-complete separation.  PLINK would fall back to Firth regression here; this scan does not.
+ * n_iter, uint8 per cell: the information evaluations made (0 for the flags 1 - 4).
+ * Reproducibility: no floating-point atomics; the individuals are walked in a fixed order (K-groups of 4, the last one padded with
+ * zeros).  A cell's bits depend on that cell's SNP, y and design alone -- not on the other SNPs or phenotypes of the call, on keep,
+ * or on the launch.  numpy does not reproduce beta^ bit for bit (the device's exp and the MFMA's internal order are its own);
+ * accuracy is stated against an exact oracle: |beta - beta_exact| <= 2^-40 se_exact, |se / se_exact - 1| <= 2^-40.
+ *
+ * ldx_glm_logistic_dev: alt, ref, keep as ldx_geno_snp_counts_dev, counts its result for the same keep; design double
+ * [n_cov + 1][ld_design] (B above), y uint8 [n_pheno][ld_design], theta0 double [n_pheno][n_cov + 1]; beta, se, z, p, neglog10_p
+ * double [n_snps][ld_out] and flags, n_iter uint8 [n_snps][ld_out]: the words [i][j < n_pheno] are written with plain stores, the
+ * padding is not touched.  Work: one wave per cell, four cells per workgroup; per evaluation a pass over the individuals, 64 at
+ * a time -- a lane per individual for eta, mu, w, r, then I and U on v_mfma_f64_16x16x4_f64 (U in the 16th column) -- and a
+ * 15 x 15 Cholesky solve in the wave's registers.  A null pointer, an odd n_hap, n_snps or n_pheno = 0, n_pheno > 65535,
+ * n_cov > LDX_LOGIT_MAX_COV, a leading dimension below its width, n_ind <= n_cov + 2, or a max_vif that is not > 1 = LDX_E_ARG,
+ * checked before any HIP call. */
+#define LDX_LOGIT_MAX_COV 13u
+#define LDX_LOGIT_MAX_ITER 30u
+int ldx_glm_logistic_dev(const void *alt, const void *ref, uint32_t n_snps, uint32_t n_hap, const uint8_t *keep,
+                         const uint32_t *counts, const double *design, size_t ld_design, uint32_t n_cov, const uint8_t *y,
+                         const double *theta0, uint32_t n_pheno, double max_vif, double *beta, double *se, double *z, double *p,
+                         double *neglog10_p, uint8_t *flags, uint8_t *n_iter, size_t ld_out, void *stream);
+
 /* ---- synthetic panels: deterministic, identical on host and device ------ */
 /* codes int8 [n_snps][ld_codes] receive global SNPs [snp_offset, snp_offset + n_snps) (a rank's
  * shard).  thresholds: per-SNP ALT probability * 2^64 (computed on the host, see

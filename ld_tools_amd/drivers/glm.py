@@ -13,9 +13,11 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from .._lib import LdxError
-from ..ops import GlmResult, ld_glm
+from ..ops import LOGIT_FLAGS, GlmResult, LogitResult, ld_glm, ld_glm_logistic
 
 GLM_COLUMNS = ("#CHROM", "POS", "ID", "REF", "ALT", "A1", "TEST", "OBS_CT", "BETA", "SE", "T_STAT", "P")
+LOGISTIC_COLUMNS = ("#CHROM", "POS", "ID", "REF", "ALT", "A1", "TEST", "OBS_CT", "OR", "LOG(OR)_SE", "Z_STAT", "P", "ERRCODE")
+LOGISTIC_ERRCODES = {k: v.upper().replace(" ", "_") for k, v in LOGIT_FLAGS.items() if k}   # the name of a flag as one word
 
 
 @dataclass
@@ -30,6 +32,30 @@ class GlmTable:
     alt: List[str]
     names: List[str]
     result: GlmResult
+
+
+@dataclass
+class LogisticTable(GlmTable):
+    """A GlmTable whose ``result`` is the one of ops.ld_glm_logistic."""
+
+    result: LogitResult
+
+
+def logistic_table(panel, variants: dict, Y, covar=None, names: Optional[Sequence[str]] = None, **more) -> LogisticTable:
+    """ops.ld_glm_logistic of ``panel`` with the columns of its variants, as glm_table: ``Y`` holds 0 (control) and 1 (case);
+    ``more``: the individuals, keep and max_vif of ld_glm_logistic."""
+    cols = {}
+    for key in ("chrom", "pos", "ids", "ref", "alt"):
+        if key not in variants or len(variants[key]) != panel.n_snps:
+            raise LdxError(f"logistic_table: variants[{key!r}] needs one entry per SNP of the panel ({panel.n_snps})")
+        cols[key] = list(variants[key])
+    res = ld_glm_logistic(panel, Y, covar, **more)
+    n_pheno = res.design.n_pheno
+    names = [f"PHENO{j + 1}" for j in range(n_pheno)] if names is None else [str(n) for n in names]
+    if len(names) != n_pheno:
+        raise LdxError(f"logistic_table: {len(names)} names for {n_pheno} phenotypes")
+    return LogisticTable([str(c) for c in cols["chrom"]], [int(p) for p in cols["pos"]], [str(i) for i in cols["ids"]],
+                         [str(a) for a in cols["ref"]], [str(a) for a in cols["alt"]], names, res)
 
 
 def glm_table(panel, variants: dict, Y, covar=None, names: Optional[Sequence[str]] = None, **more) -> GlmTable:
@@ -85,4 +111,26 @@ def write_glm_linear(path: str, table: GlmTable, pheno=0) -> int:
                 f.write(head + "NA\tNA\tNA\tNA\n")
             else:
                 f.write(head + f"{_txt(beta[k])}\t{_txt(se[k])}\t{_txt(t[k])}\t{p_text(float(p[k]), float(nlp[k]))}\n")
+    return len(table.ids)
+
+
+def write_glm_logistic(path: str, table: LogisticTable, pheno=0) -> int:
+    """``path``: the ``.glm.logistic`` lines of one phenotype of ``table`` (its name or column number), tab-separated, in the
+    columns of PLINK 2: ``#CHROM POS ID REF ALT A1 TEST OBS_CT OR LOG(OR)_SE Z_STAT P ERRCODE``, TEST = ADD, OR = exp(beta),
+    ERRCODE "." for a fitted variant; a flagged variant (ops.LOGIT_FLAGS other than 0) has NA in the four numbers and the name of
+    its flag (LOGISTIC_ERRCODES) as ERRCODE -- flag 5, NO_FINITE_MAXIMISER, is where PLINK would have refitted by Firth
+    regression.  Returns the number of lines."""
+    j = table.names.index(pheno) if isinstance(pheno, str) else int(pheno)
+    r = table.result
+    beta, se, z, p, nlp = (x[:, j].cpu().numpy() for x in (r.beta, r.se, r.z, r.p, r.neglog10_p))
+    flags, n_obs = r.flags[:, j].cpu().numpy(), r.n_obs
+    with open(path, "w") as f:
+        f.write("\t".join(LOGISTIC_COLUMNS) + "\n")
+        for k in range(len(table.ids)):
+            head = "\t".join((table.chrom[k], str(table.pos[k]), table.ids[k], table.ref[k], table.alt[k], table.alt[k], "ADD",
+                              str(int(n_obs[k])))) + "\t"
+            if flags[k] != 0:
+                f.write(head + f"NA\tNA\tNA\tNA\t{LOGISTIC_ERRCODES[int(flags[k])]}\n")
+            else:
+                f.write(head + f"{_txt(math.exp(beta[k]))}\t{_txt(se[k])}\t{_txt(z[k])}\t{p_text(float(p[k]), float(nlp[k]))}\t.\n")
     return len(table.ids)

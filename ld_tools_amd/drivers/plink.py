@@ -13,12 +13,13 @@ dataclasses of the VCF drivers from it, so that their writers write them unchang
     bfile_pca        -> PcaTable for write_eigenvec / write_eigenval       PLINK 2 --pca approx
     bfile_score      -> ScoreTable for write_sscore                        PLINK --score (sums)
     bfile_glm        -> GlmTables for write_glm_linear                     PLINK 2 --glm (quantitative traits, mean imputation)
+    bfile_logistic   -> LogisticTables for write_glm_logistic              PLINK 2 --glm (case/control traits, no Firth fallback)
 
 A ``.bed`` holds unphased genotype calls: a het is written (ALT, REF) whatever the truth, so the haplotype r of the phased
 operators means nothing here.  Every driver defaults to an unphased form (EM or genotype dosage) and refuses
 ``dosage=False, em=False``.  ``make_bed`` writes a panel, or a subset of a loaded fileset, back as a fileset.
 
-    python -m ld_tools_amd.drivers.plink {ld,clump,prune,l2,blocks,king,pca,score,glm,make-bed} --bfile P --out O ...
+    python -m ld_tools_amd.drivers.plink {ld,clump,prune,l2,blocks,king,pca,score,glm,logistic,make-bed} --bfile P --out O ...
 """
 from __future__ import annotations
 
@@ -506,7 +507,7 @@ def bfile_glm(src, pheno, covar=None, out: Optional[str] = None, pheno_names: Op
             raise LdxError(f"bfile_glm: phenotype {name} has no value for an individual of the fileset")
         if (seen <= {1.0, 2.0} or seen <= {0.0, 1.0}) and not allow_binary:
             raise LdxError(f"bfile_glm: phenotype {name} takes the values {sorted(seen)} only: a case/control trait belongs to a "
-                           "logistic model, which is not implemented (allow_binary=True fits the line anyway)")
+                           "logistic model: bfile_logistic (allow_binary=True fits the line anyway)")
     complete = np.isfinite(Y) & np.isfinite(C).all(axis=1)[:, None]
     groups: dict = {}
     for j in range(len(names)):
@@ -527,6 +528,56 @@ def bfile_glm(src, pheno, covar=None, out: Optional[str] = None, pheno_names: Op
         for table in tables:
             for name in table.names:
                 write_glm_linear(f"{out}.{name}.glm.linear", table, name)
+    return tables
+
+
+def case_control(name: str, values) -> np.ndarray:
+    """A case/control phenotype column as 0 (control) / 1 (case), NaN kept: its finite values must all lie in {1, 2} (PLINK's
+    control / case; a column of 1s alone is all controls) or in {0, 1}.  Anything else is refused."""
+    v = np.asarray(values, dtype=np.float64)
+    seen = set(np.unique(v[np.isfinite(v)]).tolist())
+    if not seen:
+        raise LdxError(f"bfile_logistic: phenotype {name} has no value for an individual of the fileset")
+    if seen <= {1.0, 2.0}:
+        return v - 1.0
+    if seen <= {0.0, 1.0}:
+        return v.copy()
+    raise LdxError(f"bfile_logistic: phenotype {name} takes the values {sorted(seen)[:6]}: a case/control trait is coded 1 / 2 "
+                   "(control / case) or 0 / 1; a quantitative trait belongs to bfile_glm")
+
+
+def bfile_logistic(src, pheno, covar=None, out: Optional[str] = None, pheno_names: Optional[Sequence[str]] = None,
+                   covar_names: Optional[Sequence[str]] = None, max_vif: float = 50.0, **load) -> list:
+    """drivers/glm.py's ``logistic_table`` from a fileset (PLINK 2's --glm for case/control traits without its Firth fallback;
+    ops.ld_glm_logistic's definition: a missing genotype counts as the variant's mean).  ``pheno`` / ``covar``, their names and
+    the grouping of the phenotypes by their complete rows are bfile_glm's; a phenotype's finite values must lie in {1, 2}
+    (control / case) or {0, 1} (case_control); at most 13 covariates.  ``out``: a prefix to write one
+    ``<out>.<phenotype>.glm.logistic`` per phenotype under.  Returns the LogisticTables, one per group."""
+    from .glm import LogisticTable, write_glm_logistic
+    from .._lib import LOGIT_MAX_COV
+    from ..ops import ld_glm_logistic
+
+    bf = _loaded(src, **load)
+    names, Y = _sample_rows("phenotype", pheno, bf, pheno_names)
+    C = np.empty((len(bf.iid), 0)) if covar is None else _sample_rows("covariate", covar, bf, covar_names)[1]
+    if C.shape[1] > LOGIT_MAX_COV:
+        raise LdxError(f"bfile_logistic: {C.shape[1]} covariates are more than {LOGIT_MAX_COV}")
+    Y = np.stack([case_control(name, Y[:, j]) for j, name in enumerate(names)], axis=1)
+    complete = np.isfinite(Y) & np.isfinite(C).all(axis=1)[:, None]
+    groups: dict = {}
+    for j in range(len(names)):
+        groups.setdefault(complete[:, j].tobytes(), []).append(j)
+    tables = []
+    for cols in groups.values():
+        rows = np.flatnonzero(complete[:, cols[0]])
+        res = ld_glm_logistic(bf.panel, Y[np.ix_(rows, cols)], C[rows] if C.shape[1] else None,
+                              individuals=None if rows.size == len(bf.iid) else rows, max_vif=max_vif)
+        tables.append(LogisticTable(list(bf.chrom), _poss(bf), list(bf.ids), list(bf.refs), list(bf.alts),
+                                    [names[j] for j in cols], res))
+    if out is not None:
+        for table in tables:
+            for name in table.names:
+                write_glm_logistic(f"{out}.{name}.glm.logistic", table, name)
     return tables
 
 
@@ -652,6 +703,12 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--covar", default=None, help="covariate table in the same layout (an .eigenvec is one)")
     p.add_argument("--covar-name", nargs="+", default=None, help="the covariates to use (default: every column)")
     p.add_argument("--vif", type=float, default=50.0, help="largest variance inflation factor of a variant")
+    p = common("logistic", "logistic association scan of case/control phenotypes (.<phenotype>.glm.logistic)")
+    p.add_argument("--pheno", required=True, help="phenotype table as for glm; values 1 / 2 (control / case) or 0 / 1")
+    p.add_argument("--pheno-name", nargs="+", default=None, help="the phenotypes to scan (default: every column)")
+    p.add_argument("--covar", default=None, help="covariate table in the same layout (an .eigenvec is one); at most 13 columns")
+    p.add_argument("--covar-name", nargs="+", default=None, help="the covariates to use (default: every column)")
+    p.add_argument("--vif", type=float, default=50.0, help="largest variance inflation factor of a variant")
     common("make-bed", "write the selected variants and individuals as a new fileset")
     return ap
 
@@ -699,6 +756,11 @@ def main(argv=None) -> int:
         tables = bfile_glm(bf, a.pheno, covar=a.covar, out=a.out, pheno_names=split(a.pheno_name), covar_names=split(a.covar_name),
                            max_vif=a.vif)
         print(*(f"{a.out}.{name}.glm.linear" for t in tables for name in t.names))
+    elif a.command == "logistic":
+        split = lambda v: None if v is None else [n for part in v for n in part.split(",") if n]  # noqa: E731
+        tables = bfile_logistic(bf, a.pheno, covar=a.covar, out=a.out, pheno_names=split(a.pheno_name),
+                                covar_names=split(a.covar_name), max_vif=a.vif)
+        print(*(f"{a.out}.{name}.glm.logistic" for t in tables for name in t.names))
     elif a.command == "score":
         table = bfile_score(bf, a.score, out=a.out, impute="zero" if a.no_mean_imputation else "mean")
         print(table.n_matched, "of", table.n_lines, "weight lines matched ->", a.out + ".sscore")

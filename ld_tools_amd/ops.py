@@ -23,6 +23,7 @@
     GenoOperator / geno_matmul / geno_rmatmul   genotype products on the matrix cores, exact integers
     sample_pca / polygenic_score            sample PCA and per-SNP weights applied to the individuals, on those products
     ld_glm(panel, Y, covar, ...)            linear association scan on the reverse genotype product
+    ld_glm_logistic(panel, Y, covar, ...)   logistic association scan for 0/1 traits: a Newton fit per cell on the fp64 matrix cores
     pair_counts(panel_i, panel_j)           <- calc_ld.py:32           (bit-exact n11 block)
     ld_from_counts(n, n11, a1, r1, a2, r2)  <- calc_ld.py:33-97        (the epilogue alone)
 
@@ -4349,6 +4350,232 @@ def ld_glm_host(codes, Y, covar=None, individuals=None, keep=None, max_vif: floa
     counts = geno_counts_host(x, keep)
     outs = glm_linear_host(z, zc, counts, des.exps, des.yy, n_ind, des.n_cov, max_vif)
     return GlmResult(*(torch.from_numpy(np.ascontiguousarray(o)) for o in outs), torch.from_numpy(counts.astype(np.int64)), des, des.df)
+
+
+# --------------------------------------------------------------------------- logistic association scan
+LOGIT_DECREMENT = 2.0 ** -60                   # the Newton decrement at which the step applied is the last
+LOGIT_FLAGS = {0: "ok", 1: "no call", 2: "constant genotype", 3: "vif", 4: "unusable phenotype", 5: "no finite maximiser"}
+
+
+@dataclass
+class LogitDesign:
+    """logit_design's result, numpy on the host: ``basis`` float64 [n_cov + 1, N], the rows of B = sqrt(N) Q of D = [1 | covar]
+    (column-major B); ``y`` uint8 [n_pheno, N]; ``theta0`` float64 [n_pheno, n_cov + 1], the null fit of each phenotype on B, a
+    NaN row for a phenotype without a case, without a control or whose null fit did not converge; ``n_cov`` counts the
+    covariates WITHOUT the intercept."""
+
+    basis: np.ndarray
+    y: np.ndarray
+    theta0: np.ndarray
+    n_ind: int
+    n_cov: int
+    n_pheno: int
+
+
+def _logit_mu(eta):
+    """(mu, 1 - mu, w = mu (1 - mu)) of the linear predictor, from e^-|eta|: no cancellation at either end (the kernel's steps)."""
+    e = np.exp(-np.abs(eta))
+    den = 1.0 + e
+    hi, lo = 1.0 / den, e / den
+    pos = eta >= 0.0
+    return np.where(pos, hi, lo), np.where(pos, lo, hi), hi * lo
+
+
+def _logit_newton(V, y, theta, last_index: int):
+    """Undamped Newton on the rows of ``V`` [m, N] from ``theta`` (include/ldx.h, "logistic association scan", Iteration):
+    (theta, se of parameter ``last_index``, evaluations, ok)."""
+    yes = y != 0
+    done = False
+    for it in range(1, _lib.LOGIT_MAX_ITER + 1):
+        with np.errstate(all="ignore"):
+            mu, om, w = _logit_mu(theta @ V)
+            r = np.where(yes, om, -mu)
+            info = (V * w) @ V.T
+            grad = V @ r
+        if not (np.isfinite(info).all() and np.isfinite(grad).all()):
+            return theta, np.nan, it, False
+        try:
+            L = np.linalg.cholesky(info)
+        except np.linalg.LinAlgError:
+            return theta, np.nan, it, False
+        if done:
+            return theta, 1.0 / L[last_index, last_index], it, True
+        zf = np.linalg.solve(L, grad)
+        theta = theta + np.linalg.solve(L.T, zf)
+        dec = float(zf @ zf)
+        if not np.isfinite(dec):
+            return theta, np.nan, it, False
+        done = dec <= LOGIT_DECREMENT
+    return theta, np.nan, _lib.LOGIT_MAX_ITER, False
+
+
+def logit_design(Y, covar=None) -> LogitDesign:
+    """The design step of the logistic scan (include/ldx.h, "logistic association scan"), numpy fp64 on the host: D = [1 | covar],
+    thin QR with glm_design's refusals, B = sqrt(N) Q, and per phenotype the null fit on B by Newton from 0.  ``Y``: [N] or [N, p]
+    of 0 / 1; ``covar``: [N, c'] without an intercept, c' <= 13, or None."""
+    y = _glm_matrix(Y, "logit_design: Y")
+    n, p = y.shape
+    if p < 1:
+        raise _lib.LdxError("logit_design: Y has no column")
+    if not np.isin(y, (0.0, 1.0)).all():
+        raise _lib.LdxError("logit_design: Y must hold 0 (control) and 1 (case) only")
+    x = np.empty((n, 0)) if covar is None else _glm_matrix(covar, "logit_design: covar", n)
+    n_cov = x.shape[1]
+    if n_cov > _lib.LOGIT_MAX_COV:
+        raise _lib.LdxError(f"logit_design: {n_cov} covariates are more than LDX_LOGIT_MAX_COV = {_lib.LOGIT_MAX_COV}")
+    if n <= n_cov + 2:
+        raise _lib.LdxError(f"logit_design: {n} individuals leave no degree of freedom beside the intercept, {n_cov} covariates "
+                            "and the genotype")
+    Q, R = np.linalg.qr(np.concatenate([np.ones((n, 1)), x], axis=1))
+    diag = np.abs(np.diag(R))
+    if not np.isfinite(R).all() or (diag <= 2.0 ** -20 * np.abs(R).max()).any():
+        raise _lib.LdxError("logit_design: the covariates (with the intercept) are rank-deficient: a column is constant or a "
+                            "combination of the others")
+    basis = np.ascontiguousarray((math.sqrt(n) * Q).T)
+    y8 = np.ascontiguousarray(y.T.astype(np.uint8))
+    theta0 = np.full((p, n_cov + 1), np.nan)
+    for j in range(p):
+        cases = int(y8[j].sum())
+        if cases == 0 or cases == n:
+            continue
+        th, _se, _it, ok = _logit_newton(basis, y8[j], np.zeros(n_cov + 1), n_cov)
+        if ok:
+            theta0[j] = th
+    return LogitDesign(basis, y8, theta0, n, n_cov, p)
+
+
+def _erfcx_cf(t):
+    """erfcx(t) = e^(t^2) erfc(t) for t >= 5 by its continued fraction, 60 terms from the bottom (past full fp64 there)."""
+    f = np.zeros_like(t)
+    for k in range(60, 0, -1):
+        f = (0.5 * k) / (t + f)
+    return 0.5641895835477563 / (t + f)
+
+
+def logit_tail_host(z) -> Tuple[np.ndarray, np.ndarray]:
+    """(p, neglog10_p) of the two-sided normal tail of ``z``: p = erfc(|z| / sqrt 2), ln p in log space from |z| / sqrt 2 = 5 on
+    -- the numpy mirror of the kernel's tail (math.erfc, and a continued fraction for erfcx)."""
+    z = np.asarray(z, dtype=np.float64)
+    t = np.abs(z) * 0.7071067811865476
+    p = np.vectorize(math.erfc, otypes=[np.float64])(t)
+    with np.errstate(all="ignore"):
+        far = t >= 5.0
+        lnp = np.where(far, np.log(_erfcx_cf(np.where(far, t, 5.0))) - t * t, np.log(p))
+        nlp = np.where(t == 0.0, 0.0, -lnp / 2.302585092994046)
+    return p, nlp
+
+
+@dataclass
+class LogitResult:
+    """ld_glm_logistic's result.  ``beta`` (log odds ratio per ALT allele), ``se``, ``z``, ``p``, ``neglog10_p``: float64 tensors
+    [n_snps, n_pheno]; ``flags`` uint8 (LOGIT_FLAGS; every flag but 0 is NaN in all five) and ``n_iter`` uint8, the information
+    evaluations -- on the panel's device, nothing read back until asked for (host tensors from ld_glm_logistic_host); ``counts``
+    [n_snps, 4]: called, het, hom ALT per SNP; ``design``: the design step's result."""
+
+    beta: torch.Tensor
+    se: torch.Tensor
+    z: torch.Tensor
+    p: torch.Tensor
+    neglog10_p: torch.Tensor
+    flags: torch.Tensor
+    n_iter: torch.Tensor
+    counts: torch.Tensor
+    design: LogitDesign
+
+    n_obs = GlmResult.n_obs
+    a1_freq = GlmResult.a1_freq
+
+
+def _logit_y(what: str, Y, n_ind: int) -> np.ndarray:
+    y = _glm_matrix(Y, f"{what}: Y", n_ind)
+    if not np.isin(y, (0.0, 1.0)).all():
+        raise _lib.LdxError(f"{what}: Y must hold 0 (control) and 1 (case) only")
+    return y
+
+
+def ld_glm_logistic(panel: PackedPanel, Y, covar=None, individuals=None, keep=None, max_vif: float = 50.0,
+                    missing: Optional[str] = None) -> LogitResult:
+    """Logistic association scan (include/ldx.h, "logistic association scan"; this project's own definition, what PLINK 2 --glm
+    reports for a case/control trait, without its Firth fallback): per SNP that passes ``keep`` the maximum-likelihood logistic
+    fit of every 0/1 column of ``Y`` [N] / [N, p] on the genotype, an intercept and ``covar`` [N, c' <= 13].  ``individuals``,
+    ``keep``, ``max_vif`` and the mean imputation of missing genotypes are ld_glm's; ``missing="pairwise"`` is refused.  One counts
+    launch and one launch of the scan (ldx_glm_logistic_dev: a wave per cell, Newton from the null fit of logit_design, the
+    information matrices on the fp64 matrix cores); ld_glm_logistic_host is the same algorithm in numpy."""
+    require_gpu()
+    _glm_missing("ld_glm_logistic", missing)
+    _even_n_hap("ld_glm_logistic", panel)
+    if not float(max_vif) > 1.0:
+        raise _lib.LdxError("ld_glm_logistic: max_vif must be > 1")
+    cols = _glm_columns(individuals, panel.n_ind)
+    if cols is not None:
+        panel = panel.select(haplotypes=cols)
+    des = logit_design(_logit_y("ld_glm_logistic", Y, panel.n_ind),
+                       None if covar is None else _glm_matrix(covar, "ld_glm_logistic: covar", panel.n_ind))
+    keep_d = _keep_dev(keep, panel.n_snps, panel.device)
+    dev, p = panel.device, des.n_pheno
+    counts = _snp_counts(panel, keep_d)
+    basis, y8, theta0 = (torch.from_numpy(a).to(dev) for a in (des.basis, des.y, des.theta0))
+    outs = [torch.empty((panel.n_snps, p), dtype=torch.float64, device=dev) for _ in range(5)]
+    flags, n_iter = (torch.empty((panel.n_snps, p), dtype=torch.uint8, device=dev) for _ in range(2))
+    check(lib.ldx_glm_logistic_dev(panel.alt.data_ptr(), panel.ref.data_ptr(), panel.n_snps, panel.n_hap, _ptr(keep_d),
+                                   counts.data_ptr(), basis.data_ptr(), des.n_ind, des.n_cov, y8.data_ptr(), theta0.data_ptr(), p,
+                                   float(max_vif), *(o.data_ptr() for o in outs), flags.data_ptr(), n_iter.data_ptr(), p,
+                                   _stream_ptr()), "ldx_glm_logistic_dev")
+    return LogitResult(*outs, flags, n_iter, counts, des)
+
+
+def ld_glm_logistic_host(codes, Y, covar=None, individuals=None, keep=None, max_vif: float = 50.0) -> LogitResult:
+    """Host mirror of ld_glm_logistic on the allele codes [n_snps, n_hap]: the same design step, flags and Newton iteration in
+    numpy fp64 (equal within rounding, not bit for bit: numpy's exp and summation order are its own).  The tensors of the result
+    are on the host."""
+    x = np.asarray(codes)
+    if x.ndim != 2 or x.shape[1] % 2 or x.shape[1] == 0:
+        raise _lib.LdxError(f"ld_glm_logistic_host: codes [n_snps, n_hap] with an even n_hap needed, got shape {x.shape}")
+    if not float(max_vif) > 1.0:
+        raise _lib.LdxError("ld_glm_logistic_host: max_vif must be > 1")
+    cols = _glm_columns(individuals, x.shape[1] // 2)
+    if cols is not None:
+        x = x[:, cols]
+    n_ind = x.shape[1] // 2
+    des = logit_design(_logit_y("ld_glm_logistic_host", Y, n_ind),
+                       None if covar is None else _glm_matrix(covar, "ld_glm_logistic_host: covar", n_ind))
+    g, called = geno_planes_host(x, keep)
+    counts = geno_counts_host(x, keep)
+    n_snps, p, P = x.shape[0], des.n_pheno, des.n_cov + 1
+    c64 = counts.astype(np.int64)
+    n, s, e2 = c64[:, 0], c64[:, 1] + 2 * c64[:, 2], c64[:, 1] + 4 * c64[:, 2]
+    num = n * e2 - s * s
+    outs = [np.full((n_snps, p), np.nan) for _ in range(5)]
+    flags, n_iter = np.zeros((n_snps, p), dtype=np.uint8), np.zeros((n_snps, p), dtype=np.uint8)
+    usable = ~np.isnan(des.theta0).any(axis=1)
+    V = np.zeros((P + 1, n_ind))
+    V[:P] = des.basis
+    for i in range(n_snps):
+        if n[i] == 0 or num[i] == 0:
+            flags[i] = 1 if n[i] == 0 else 2
+            continue
+        xi = np.where(called[i] != 0, g[i] - float(s[i]) / float(n[i]), 0.0)
+        xx = float(num[i]) / float(n[i])
+        h = des.basis @ xi
+        d = xx - float(((h * h) / float(n_ind)).sum())
+        if d * float(max_vif) < xx:
+            flags[i] = 3
+            continue
+        V[P] = xi
+        for j in range(p):
+            if not usable[j]:
+                flags[i, j] = 4
+                continue
+            th, se, it, ok = _logit_newton(V, des.y[j], np.concatenate([des.theta0[j], [0.0]]), P)
+            n_iter[i, j] = it
+            if not ok or not (np.isfinite(th[P]) and np.isfinite(se)):
+                flags[i, j] = 5
+                continue
+            outs[0][i, j], outs[1][i, j], outs[2][i, j] = th[P], se, th[P] / se
+    live = flags == 0
+    outs[3][live], outs[4][live] = logit_tail_host(outs[2][live])
+    return LogitResult(*(torch.from_numpy(o) for o in outs), torch.from_numpy(flags), torch.from_numpy(n_iter),
+                       torch.from_numpy(counts.astype(np.int64)), des)
 
 
 # --------------------------------------------------------------------------- instrumentation
