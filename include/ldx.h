@@ -1261,6 +1261,57 @@ int ldx_glm_logistic_dev(const void *alt, const void *ref, uint32_t n_snps, uint
                          const double *theta0, uint32_t n_pheno, double max_vif, double *beta, double *se, double *z, double *p,
                          double *neglog10_p, uint8_t *flags, uint8_t *n_iter, size_t ld_out, void *stream);
 
+/* ---- Firth logistic association scan: the penalised-likelihood fit of the same model, as a fallback for the cells the
+ * maximum-likelihood scan flags 5, or for every cell ----
+ * This project's own definition (the estimate PLINK 2 --glm firth-fallback / firth and logistf aim at), NOT validated against
+ * PLINK 2 or logistf.
+ *
+ * The individuals, called genotypes, keep, mean imputation, design B = sqrt(N) Q, theta0 and the flags 1 - 4 are those of
+ * "logistic association scan"; so are v_a, w_a, mu_a and I(theta).  The estimate is
+ *     theta^ maximises  l*(theta) = l(theta) + 1/2 ln det I(theta)                                   (Firth 1993)
+ *     modified score  U*(theta) = sum_a v_a [ y_a - mu_a + h_a (1/2 - mu_a) ],   h_a = w_a v_a^T I(theta)^-1 v_a
+ *     beta = theta^_b,  se = sqrt([I(theta^)^-1]_bb)  (the UNPENALISED information at theta^),  z, p, neglog10_p as in the ML scan
+ * theta^ is finite for every full-rank cell (Kosmidis & Firth 2021), separated ones included.  For the saturated 2 x 2 table
+ * without covariates, a, b cases and c, d controls at genotype high, low, it is the Haldane-Anscombe estimate:
+ *     beta = ln[(a + 1/2)(d + 1/2) / ((b + 1/2)(c + 1/2))]
+ *     se^2 = 1 / (n_h mu_h (1 - mu_h)) + 1 / (n_l mu_l (1 - mu_l)),  mu_h = (a + 1/2) / (a + c + 1),  mu_l = (b + 1/2) / (b + d + 1),
+ *            n_h = a + c,  n_l = b + d
+ * beta^ and se do not depend on the parametrisation of the span of D (ln det I changes by a constant).  The iteration path is not
+ * part of the definition.
+ * Iteration (the device and its numpy mirror, ops.ld_glm_logistic_host(firth=)): Fisher scoring theta <- theta + I(theta)^-1 U*(theta)
+ * from (theta0_j, 0) -- the start of the ML scan, whether the cell is reached by the fallback or not.  An evaluation forms I, its
+ * Cholesky factor L and M = L^-1, then h_a = w_a |M v_a|^2 and U* in a second pass over the individuals, and solves I delta = U*;
+ * when lambda*^2 = U*^T I^-1 U* <= 2^-88 that step is applied and I evaluated once more at the new point for se; at most
+ * LDX_FIRTH_MAX_ITER information evaluations.  Scoring with I (not with the Hessian of l*) converges linearly: the stop constant
+ * is chosen so that the steps not taken sum to less than 2^-40 se.  Safeguard: an evaluation whose lambda*^2
+ * is not below that of the point before gives its point up for the one half as far along the step before, and the step length
+ * stays halved for the rest of the fit (a variant with a single carrier has a hat value near 1 and the plain step overshoots
+ * about twofold: without the safeguard such cells end in a 2-cycle).  A cell that never triggers it is not touched by it.
+ * flags: 0 - 4 as in the ML scan; 5 = the cap was reached, or a pivot was lost (not > 0, or not finite).  n_iter: the information
+ * evaluations of the Firth fit.  Accuracy, against an exact oracle of this definition: |beta - beta_exact| <= 2^-40 se_exact,
+ * |se / se_exact - 1| <= 2^-40; the tail as in the ML scan.
+ * Out of scope: a phenotype whose NULL maximum-likelihood fit fails keeps flag 4 (no null Firth fit is made);
+ * profile-likelihood p-values (logistf's) are not computed, the test is Wald; pairwise-complete missing data is refused upstream.
+ * Reproducibility: as the ML scan -- no floating-point atomics, every sum in a fixed order; a cell's bits depend on its SNP, y and
+ * design alone, not on mode, the other cells, keep or the launch.
+ *
+ * ldx_glm_firth_dev: the arguments of ldx_glm_logistic_dev, then mode and firth uint8 [n_snps][ld_out].
+ *     mode 0  fits every cell and derives the flags 1 - 4 itself by the ML scan's rules; firth = 1 where a fit was made (the flag
+ *             is 0 or 5), 0 under the flags 1 - 4.
+ *     mode 1  flags is input and output: a cell whose flag is not 5 on entry gets firth = 0 and nothing else of it is touched; a
+ *             cell with flag 5 is refitted: the five outputs, flags (0 or 5), n_iter and firth = 1 are written.  Stream-ordered
+ *             after the ML launch that wrote flags; nothing is read back and nothing is compacted on the host.
+ * Work: one wave per cell, four cells per workgroup, no barrier; per evaluation pass A of the ML scan, the Cholesky and the
+ * triangular inverse in the wave's registers, and pass B: T = M V on v_mfma_f64_16x16x4_f64, 16 individuals x 4 K-groups of
+ * parameters x 4 column blocks = 16 instructions per 64 individuals, as many as pass A.  mode > 1, a null firth and every refusal
+ * of ldx_glm_logistic_dev = LDX_E_ARG, checked before any HIP call. */
+#define LDX_FIRTH_MAX_ITER 200u
+int ldx_glm_firth_dev(const void *alt, const void *ref, uint32_t n_snps, uint32_t n_hap, const uint8_t *keep,
+                      const uint32_t *counts, const double *design, size_t ld_design, uint32_t n_cov, const uint8_t *y,
+                      const double *theta0, uint32_t n_pheno, double max_vif, double *beta, double *se, double *z, double *p,
+                      double *neglog10_p, uint8_t *flags, uint8_t *n_iter, size_t ld_out, uint32_t mode, uint8_t *firth,
+                      void *stream);
+
 /* ---- synthetic panels: deterministic, identical on host and device ------ */
 /* codes int8 [n_snps][ld_codes] receive global SNPs [snp_offset, snp_offset + n_snps) (a rank's
  * shard).  thresholds: per-SNP ALT probability * 2^64 (computed on the host, see

@@ -29,8 +29,8 @@ from .ops import (GenoOperator, GenoProduct, SamplePCA, Scores, geno_matmul, gen
                   geno_rmatmul, geno_rmatmul_host, polygenic_score, polygenic_score_host, sample_pca, sample_pca_host)
 from .ops import (GLM_FLAGS, GlmDesign, GlmResult, geno_counts_host, geno_snp_counts, glm_design, glm_linear_host,  # noqa: F401
                   glm_tail_host, ld_glm, ld_glm_host)
-from .ops import (LOGIT_FLAGS, LogitDesign, LogitResult, ld_glm_logistic, ld_glm_logistic_host, logit_design,  # noqa: F401
-                  logit_tail_host)
+from .ops import (FIRTH_MODES, FIRTH_STOP, LOGIT_FLAGS, LogitDesign, LogitResult, ld_glm_logistic,  # noqa: F401
+                  ld_glm_logistic_host, logit_design, logit_tail_host)
 from .panel import PackedPanel, encode_codes, select_index  # noqa: F401
 from . import plink  # noqa: F401
 from .plink import BedFile, bed_codes_host, codes_bed_host, read_covar, read_pheno, write_bfile  # noqa: F401
@@ -48,4 +48,5 @@ __all__ = ["PackedPanel", "encode_codes", "select_index", "ld_triangle", "ld_are
            "polygenic_score_host", "Scores", "sample_pca", "sample_pca_host", "SamplePCA", "geno_snp_counts", "geno_counts_host",
            "glm_design", "GlmDesign", "ld_glm", "ld_glm_host", "glm_linear_host", "glm_tail_host", "GlmResult", "GLM_FLAGS", "LdxError",
            "logit_design", "LogitDesign", "ld_glm_logistic", "ld_glm_logistic_host", "logit_tail_host", "LogitResult", "LOGIT_FLAGS",
+           "FIRTH_MODES", "FIRTH_STOP",
            "version", "plink", "BedFile", "bed_codes_host", "codes_bed_host", "write_bfile", "read_pheno", "read_covar"]

@@ -40,6 +40,7 @@ GENO_MAX_COLS = 64                       # LDX_GENO_MAX_COLS
 GENO_MAX_SLICE_SNPS = 1 << 22            # LDX_GENO_MAX_SLICE_SNPS
 LOGIT_MAX_COV = 13                       # LDX_LOGIT_MAX_COV
 LOGIT_MAX_ITER = 30                      # LDX_LOGIT_MAX_ITER
+FIRTH_MAX_ITER = 200                     # LDX_FIRTH_MAX_ITER
 FLAG_DPRIME_INT0 = 1
 FLAG_RSQ_INT0 = 2
 MEASURES = {"r_square": 0, "d_prime": 1}
@@ -219,6 +220,8 @@ SIGNATURES = {
     "ldx_glm_linear_dev": (_int, [_vp, _vp, _sz, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ldx_glm_logistic_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _sz, _u32, _vp, _vp, _u32, _dbl, _vp, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _sz, _vp]),
+    "ldx_glm_firth_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _sz, _u32, _vp, _vp, _u32, _dbl, _vp, _vp, _vp, _vp, _vp,
+                                 _vp, _vp, _sz, _u32, _vp, _vp]),
     "ldx_ld_select_workspace_bytes": (_sz, [_u32]),
     "ldx_ld_select_dev": (_int, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ldx_set_area_path": (_int, [_int]),

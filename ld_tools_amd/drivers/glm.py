@@ -17,6 +17,7 @@ from ..ops import LOGIT_FLAGS, GlmResult, LogitResult, ld_glm, ld_glm_logistic
 
 GLM_COLUMNS = ("#CHROM", "POS", "ID", "REF", "ALT", "A1", "TEST", "OBS_CT", "BETA", "SE", "T_STAT", "P")
 LOGISTIC_COLUMNS = ("#CHROM", "POS", "ID", "REF", "ALT", "A1", "TEST", "OBS_CT", "OR", "LOG(OR)_SE", "Z_STAT", "P", "ERRCODE")
+HYBRID_COLUMNS = LOGISTIC_COLUMNS[:6] + ("FIRTH?",) + LOGISTIC_COLUMNS[6:]   # PLINK 2's .glm.logistic.hybrid
 LOGISTIC_ERRCODES = {k: v.upper().replace(" ", "_") for k, v in LOGIT_FLAGS.items() if k}   # the name of a flag as one word
 
 
@@ -43,7 +44,7 @@ class LogisticTable(GlmTable):
 
 def logistic_table(panel, variants: dict, Y, covar=None, names: Optional[Sequence[str]] = None, **more) -> LogisticTable:
     """ops.ld_glm_logistic of ``panel`` with the columns of its variants, as glm_table: ``Y`` holds 0 (control) and 1 (case);
-    ``more``: the individuals, keep and max_vif of ld_glm_logistic."""
+    ``more``: the individuals, keep, max_vif and firth (None, "fallback" or "always") of ld_glm_logistic."""
     cols = {}
     for key in ("chrom", "pos", "ids", "ref", "alt"):
         if key not in variants or len(variants[key]) != panel.n_snps:
@@ -134,3 +135,37 @@ def write_glm_logistic(path: str, table: LogisticTable, pheno=0) -> int:
             else:
                 f.write(head + f"{_txt(math.exp(beta[k]))}\t{_txt(se[k])}\t{_txt(z[k])}\t{p_text(float(p[k]), float(nlp[k]))}\t.\n")
     return len(table.ids)
+
+
+def _write_firth(path: str, table: LogisticTable, pheno, hybrid: bool) -> int:
+    j = table.names.index(pheno) if isinstance(pheno, str) else int(pheno)
+    r = table.result
+    if r.firth is None:
+        raise LdxError(f"{'write_glm_hybrid' if hybrid else 'write_glm_firth'}: the table holds a scan without firth=")
+    beta, se, z, p, nlp = (x[:, j].cpu().numpy() for x in (r.beta, r.se, r.z, r.p, r.neglog10_p))
+    flags, mark, n_obs = r.flags[:, j].cpu().numpy(), r.firth[:, j].cpu().numpy(), r.n_obs
+    with open(path, "w") as f:
+        f.write("\t".join(HYBRID_COLUMNS if hybrid else LOGISTIC_COLUMNS) + "\n")
+        for k in range(len(table.ids)):
+            head = (table.chrom[k], str(table.pos[k]), table.ids[k], table.ref[k], table.alt[k], table.alt[k])
+            if hybrid:
+                head += ("Y" if mark[k] else "N",)
+            head = "\t".join(head + ("ADD", str(int(n_obs[k])))) + "\t"
+            if flags[k] != 0:
+                f.write(head + f"NA\tNA\tNA\tNA\t{LOGISTIC_ERRCODES[int(flags[k])]}\n")
+            else:
+                f.write(head + f"{_txt(math.exp(beta[k]))}\t{_txt(se[k])}\t{_txt(z[k])}\t{p_text(float(p[k]), float(nlp[k]))}\t.\n")
+    return len(table.ids)
+
+
+def write_glm_hybrid(path: str, table: LogisticTable, pheno=0) -> int:
+    """``path``: the ``.glm.logistic.hybrid`` lines of one phenotype of a ``table`` scanned with ``firth=`` (PLINK 2's file of
+    --glm firth-fallback): the columns of write_glm_logistic with ``FIRTH?`` in front of TEST -- Y where the line holds a Firth fit
+    (the result's ``firth``), N elsewhere; a flagged variant as in write_glm_logistic.  Returns the number of lines."""
+    return _write_firth(path, table, pheno, True)
+
+
+def write_glm_firth(path: str, table: LogisticTable, pheno=0) -> int:
+    """``path``: the ``.glm.firth`` lines of one phenotype of a ``table`` scanned with ``firth="always"`` (PLINK 2's file of
+    --glm firth): the columns of write_glm_logistic, every fitted line a Firth fit.  Returns the number of lines."""
+    return _write_firth(path, table, pheno, False)

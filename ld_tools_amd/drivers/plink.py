@@ -14,6 +14,7 @@ dataclasses of the VCF drivers from it, so that their writers write them unchang
     bfile_score      -> ScoreTable for write_sscore                        PLINK --score (sums)
     bfile_glm        -> GlmTables for write_glm_linear                     PLINK 2 --glm (quantitative traits, mean imputation)
     bfile_logistic   -> LogisticTables for write_glm_logistic              PLINK 2 --glm (case/control traits, no Firth fallback)
+                        (firth=: write_glm_hybrid / write_glm_firth         PLINK 2 --glm firth-fallback / firth)
 
 A ``.bed`` holds unphased genotype calls: a het is written (ALT, REF) whatever the truth, so the haplotype r of the phased
 operators means nothing here.  Every driver defaults to an unphased form (EM or genotype dosage) and refuses
@@ -547,13 +548,17 @@ def case_control(name: str, values) -> np.ndarray:
 
 
 def bfile_logistic(src, pheno, covar=None, out: Optional[str] = None, pheno_names: Optional[Sequence[str]] = None,
-                   covar_names: Optional[Sequence[str]] = None, max_vif: float = 50.0, **load) -> list:
+                   covar_names: Optional[Sequence[str]] = None, max_vif: float = 50.0, firth: Optional[str] = None,
+                   **load) -> list:
     """drivers/glm.py's ``logistic_table`` from a fileset (PLINK 2's --glm for case/control traits without its Firth fallback;
     ops.ld_glm_logistic's definition: a missing genotype counts as the variant's mean).  ``pheno`` / ``covar``, their names and
     the grouping of the phenotypes by their complete rows are bfile_glm's; a phenotype's finite values must lie in {1, 2}
     (control / case) or {0, 1} (case_control); at most 13 covariates.  ``out``: a prefix to write one
-    ``<out>.<phenotype>.glm.logistic`` per phenotype under.  Returns the LogisticTables, one per group."""
-    from .glm import LogisticTable, write_glm_logistic
+    ``<out>.<phenotype>.glm.logistic`` per phenotype under.  ``firth`` (ops.ld_glm_logistic's): "fallback" refits the variants
+    without a finite maximiser by Firth's penalised likelihood and writes ``<out>.<phenotype>.glm.logistic.hybrid`` (PLINK 2's
+    firth-fallback, its default), "always" fits every variant that way and writes ``<out>.<phenotype>.glm.firth``.  Returns the
+    LogisticTables, one per group."""
+    from .glm import LogisticTable, write_glm_firth, write_glm_hybrid, write_glm_logistic
     from .._lib import LOGIT_MAX_COV
     from ..ops import ld_glm_logistic
 
@@ -571,13 +576,18 @@ def bfile_logistic(src, pheno, covar=None, out: Optional[str] = None, pheno_name
     for cols in groups.values():
         rows = np.flatnonzero(complete[:, cols[0]])
         res = ld_glm_logistic(bf.panel, Y[np.ix_(rows, cols)], C[rows] if C.shape[1] else None,
-                              individuals=None if rows.size == len(bf.iid) else rows, max_vif=max_vif)
+                              individuals=None if rows.size == len(bf.iid) else rows, max_vif=max_vif, firth=firth)
         tables.append(LogisticTable(list(bf.chrom), _poss(bf), list(bf.ids), list(bf.refs), list(bf.alts),
                                     [names[j] for j in cols], res))
     if out is not None:
         for table in tables:
             for name in table.names:
-                write_glm_logistic(f"{out}.{name}.glm.logistic", table, name)
+                if firth is None:
+                    write_glm_logistic(f"{out}.{name}.glm.logistic", table, name)
+                elif firth == "fallback":
+                    write_glm_hybrid(f"{out}.{name}.glm.logistic.hybrid", table, name)
+                else:
+                    write_glm_firth(f"{out}.{name}.glm.firth", table, name)
     return tables
 
 
@@ -709,6 +719,9 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--covar", default=None, help="covariate table in the same layout (an .eigenvec is one); at most 13 columns")
     p.add_argument("--covar-name", nargs="+", default=None, help="the covariates to use (default: every column)")
     p.add_argument("--vif", type=float, default=50.0, help="largest variance inflation factor of a variant")
+    p.add_argument("--firth", choices=("fallback", "always"), default=None,
+                   help="Firth's penalised fit where the likelihood has no finite maximiser (.glm.logistic.hybrid) or for every "
+                        "variant (.glm.firth); default: off")
     common("make-bed", "write the selected variants and individuals as a new fileset")
     return ap
 
@@ -759,8 +772,9 @@ def main(argv=None) -> int:
     elif a.command == "logistic":
         split = lambda v: None if v is None else [n for part in v for n in part.split(",") if n]  # noqa: E731
         tables = bfile_logistic(bf, a.pheno, covar=a.covar, out=a.out, pheno_names=split(a.pheno_name),
-                                covar_names=split(a.covar_name), max_vif=a.vif)
-        print(*(f"{a.out}.{name}.glm.logistic" for t in tables for name in t.names))
+                                covar_names=split(a.covar_name), max_vif=a.vif, firth=a.firth)
+        ext = {None: "glm.logistic", "fallback": "glm.logistic.hybrid", "always": "glm.firth"}[a.firth]
+        print(*(f"{a.out}.{name}.{ext}" for t in tables for name in t.names))
     elif a.command == "score":
         table = bfile_score(bf, a.score, out=a.out, impute="zero" if a.no_mean_imputation else "mean")
         print(table.n_matched, "of", table.n_lines, "weight lines matched ->", a.out + ".sscore")

@@ -23,7 +23,8 @@
     GenoOperator / geno_matmul / geno_rmatmul   genotype products on the matrix cores, exact integers
     sample_pca / polygenic_score            sample PCA and per-SNP weights applied to the individuals, on those products
     ld_glm(panel, Y, covar, ...)            linear association scan on the reverse genotype product
-    ld_glm_logistic(panel, Y, covar, ...)   logistic association scan for 0/1 traits: a Newton fit per cell on the fp64 matrix cores
+    ld_glm_logistic(panel, Y, covar, ...)   logistic association scan for 0/1 traits: a Newton fit per cell on the fp64 matrix cores;
+                                            firth="fallback" / "always": Firth's penalised fit where that has no finite maximiser / everywhere
     pair_counts(panel_i, panel_j)           <- calc_ld.py:32           (bit-exact n11 block)
     ld_from_counts(n, n11, a1, r1, a2, r2)  <- calc_ld.py:33-97        (the epilogue alone)
 
@@ -4354,6 +4355,8 @@ def ld_glm_host(codes, Y, covar=None, individuals=None, keep=None, max_vif: floa
 
 # --------------------------------------------------------------------------- logistic association scan
 LOGIT_DECREMENT = 2.0 ** -60                   # the Newton decrement at which the step applied is the last
+FIRTH_STOP = 2.0 ** -88                        # lambda*^2 of the Firth scoring step at which the step applied is the last
+FIRTH_MODES = (None, "fallback", "always")
 LOGIT_FLAGS = {0: "ok", 1: "no call", 2: "constant genotype", 3: "vif", 4: "unusable phenotype", 5: "no finite maximiser"}
 
 
@@ -4407,6 +4410,51 @@ def _logit_newton(V, y, theta, last_index: int):
             return theta, np.nan, it, False
         done = dec <= LOGIT_DECREMENT
     return theta, np.nan, _lib.LOGIT_MAX_ITER, False
+
+
+def _firth_scoring(V, y, theta, last_index: int, decs: Optional[list] = None):
+    """Fisher scoring on Firth's modified score over the rows of ``V`` [m, N] from ``theta`` (include/ldx.h, "Firth logistic
+    association scan", Iteration): (theta, se of parameter ``last_index``, evaluations, ok).  ``decs`` collects lambda*^2 of every
+    evaluation that takes a step."""
+    yes = y != 0
+    done = False
+    eye = np.eye(V.shape[0])
+    # the safeguard: a point whose lambda*^2 is not below that of the point before is given up for one half as far along the same
+    # step, and the step length stays halved for the rest of the fit
+    length, before, start, step = 1.0, np.inf, theta, None
+    for it in range(1, _lib.FIRTH_MAX_ITER + 1):
+        with np.errstate(all="ignore"):
+            mu, om, w = _logit_mu(theta @ V)
+            r = np.where(yes, om, -mu)
+            info = (V * w) @ V.T
+        if not np.isfinite(info).all():
+            return theta, np.nan, it, False
+        try:
+            L = np.linalg.cholesky(info)
+        except np.linalg.LinAlgError:
+            return theta, np.nan, it, False
+        if done:
+            return theta, 1.0 / L[last_index, last_index], it, True
+        with np.errstate(all="ignore"):
+            T = np.linalg.solve(L, eye) @ V                     # M V, M = L^-1: h_a = w_a |M v_a|^2
+            h = w * (T * T).sum(axis=0)
+            # summed pairwise, as the device sums per lane and then across the lanes: a running sum over thousands of individuals
+            # leaves a rounding error in U* that keeps lambda*^2 above the stop constant
+            score = (V * (r + h * (0.5 - mu))).sum(axis=1)
+            zf = np.linalg.solve(L, score)
+            dec = float(zf @ zf)
+        if not np.isfinite(dec):
+            return theta, np.nan, it, False
+        if decs is not None:
+            decs.append(dec)
+        if dec >= before:                                       # rejected: back to the point before, half as far along its step
+            length *= 0.5
+        else:
+            with np.errstate(all="ignore"):
+                start, step, before = theta, np.linalg.solve(L.T, zf), dec
+            done = dec <= FIRTH_STOP
+        theta = start + length * step
+    return theta, np.nan, _lib.FIRTH_MAX_ITER, False
 
 
 def logit_design(Y, covar=None) -> LogitDesign:
@@ -4470,7 +4518,8 @@ class LogitResult:
     """ld_glm_logistic's result.  ``beta`` (log odds ratio per ALT allele), ``se``, ``z``, ``p``, ``neglog10_p``: float64 tensors
     [n_snps, n_pheno]; ``flags`` uint8 (LOGIT_FLAGS; every flag but 0 is NaN in all five) and ``n_iter`` uint8, the information
     evaluations -- on the panel's device, nothing read back until asked for (host tensors from ld_glm_logistic_host); ``counts``
-    [n_snps, 4]: called, het, hom ALT per SNP; ``design``: the design step's result."""
+    [n_snps, 4]: called, het, hom ALT per SNP; ``design``: the design step's result; ``firth`` uint8, 1 where the cell holds a
+    Firth fit (include/ldx.h, "Firth logistic association scan"), None for a scan without ``firth=``."""
 
     beta: torch.Tensor
     se: torch.Tensor
@@ -4481,9 +4530,16 @@ class LogitResult:
     n_iter: torch.Tensor
     counts: torch.Tensor
     design: LogitDesign
+    firth: Optional[torch.Tensor] = None
 
     n_obs = GlmResult.n_obs
     a1_freq = GlmResult.a1_freq
+
+
+def _firth_mode(what: str, firth):
+    if firth not in FIRTH_MODES:
+        raise _lib.LdxError(f"{what}: firth must be None, 'fallback' or 'always', got {firth!r}")
+    return firth
 
 
 def _logit_y(what: str, Y, n_ind: int) -> np.ndarray:
@@ -4494,14 +4550,18 @@ def _logit_y(what: str, Y, n_ind: int) -> np.ndarray:
 
 
 def ld_glm_logistic(panel: PackedPanel, Y, covar=None, individuals=None, keep=None, max_vif: float = 50.0,
-                    missing: Optional[str] = None) -> LogitResult:
+                    missing: Optional[str] = None, firth: Optional[str] = None) -> LogitResult:
     """Logistic association scan (include/ldx.h, "logistic association scan"; this project's own definition, what PLINK 2 --glm
     reports for a case/control trait, without its Firth fallback): per SNP that passes ``keep`` the maximum-likelihood logistic
     fit of every 0/1 column of ``Y`` [N] / [N, p] on the genotype, an intercept and ``covar`` [N, c' <= 13].  ``individuals``,
     ``keep``, ``max_vif`` and the mean imputation of missing genotypes are ld_glm's; ``missing="pairwise"`` is refused.  One counts
     launch and one launch of the scan (ldx_glm_logistic_dev: a wave per cell, Newton from the null fit of logit_design, the
-    information matrices on the fp64 matrix cores); ld_glm_logistic_host is the same algorithm in numpy."""
+    information matrices on the fp64 matrix cores); ld_glm_logistic_host is the same algorithm in numpy.
+    ``firth`` (include/ldx.h, "Firth logistic association scan"): "fallback" refits the cells the scan flags 5 by Firth's
+    penalised likelihood, a second launch (ldx_glm_firth_dev, mode 1) in stream order behind the first with nothing read back in
+    between; "always" fits every cell that way (mode 0 alone).  The result's ``firth`` marks the penalised cells."""
     require_gpu()
+    _firth_mode("ld_glm_logistic", firth)
     _glm_missing("ld_glm_logistic", missing)
     _even_n_hap("ld_glm_logistic", panel)
     if not float(max_vif) > 1.0:
@@ -4517,17 +4577,24 @@ def ld_glm_logistic(panel: PackedPanel, Y, covar=None, individuals=None, keep=No
     basis, y8, theta0 = (torch.from_numpy(a).to(dev) for a in (des.basis, des.y, des.theta0))
     outs = [torch.empty((panel.n_snps, p), dtype=torch.float64, device=dev) for _ in range(5)]
     flags, n_iter = (torch.empty((panel.n_snps, p), dtype=torch.uint8, device=dev) for _ in range(2))
-    check(lib.ldx_glm_logistic_dev(panel.alt.data_ptr(), panel.ref.data_ptr(), panel.n_snps, panel.n_hap, _ptr(keep_d),
-                                   counts.data_ptr(), basis.data_ptr(), des.n_ind, des.n_cov, y8.data_ptr(), theta0.data_ptr(), p,
-                                   float(max_vif), *(o.data_ptr() for o in outs), flags.data_ptr(), n_iter.data_ptr(), p,
-                                   _stream_ptr()), "ldx_glm_logistic_dev")
-    return LogitResult(*outs, flags, n_iter, counts, des)
+    args = (panel.alt.data_ptr(), panel.ref.data_ptr(), panel.n_snps, panel.n_hap, _ptr(keep_d), counts.data_ptr(),
+            basis.data_ptr(), des.n_ind, des.n_cov, y8.data_ptr(), theta0.data_ptr(), p, float(max_vif),
+            *(o.data_ptr() for o in outs), flags.data_ptr(), n_iter.data_ptr(), p)
+    if firth != "always":
+        check(lib.ldx_glm_logistic_dev(*args, _stream_ptr()), "ldx_glm_logistic_dev")
+        if firth is None:
+            return LogitResult(*outs, flags, n_iter, counts, des)
+    mark = torch.empty((panel.n_snps, p), dtype=torch.uint8, device=dev)
+    check(lib.ldx_glm_firth_dev(*args, 1 if firth == "fallback" else 0, mark.data_ptr(), _stream_ptr()), "ldx_glm_firth_dev")
+    return LogitResult(*outs, flags, n_iter, counts, des, mark)
 
 
-def ld_glm_logistic_host(codes, Y, covar=None, individuals=None, keep=None, max_vif: float = 50.0) -> LogitResult:
+def ld_glm_logistic_host(codes, Y, covar=None, individuals=None, keep=None, max_vif: float = 50.0,
+                         firth: Optional[str] = None) -> LogitResult:
     """Host mirror of ld_glm_logistic on the allele codes [n_snps, n_hap]: the same design step, flags and Newton iteration in
-    numpy fp64 (equal within rounding, not bit for bit: numpy's exp and summation order are its own).  The tensors of the result
-    are on the host."""
+    numpy fp64 (equal within rounding, not bit for bit: numpy's exp and summation order are its own), and for ``firth`` the same
+    Fisher scoring on the modified score.  The tensors of the result are on the host."""
+    _firth_mode("ld_glm_logistic_host", firth)
     x = np.asarray(codes)
     if x.ndim != 2 or x.shape[1] % 2 or x.shape[1] == 0:
         raise _lib.LdxError(f"ld_glm_logistic_host: codes [n_snps, n_hap] with an even n_hap needed, got shape {x.shape}")
@@ -4546,7 +4613,7 @@ def ld_glm_logistic_host(codes, Y, covar=None, individuals=None, keep=None, max_
     n, s, e2 = c64[:, 0], c64[:, 1] + 2 * c64[:, 2], c64[:, 1] + 4 * c64[:, 2]
     num = n * e2 - s * s
     outs = [np.full((n_snps, p), np.nan) for _ in range(5)]
-    flags, n_iter = np.zeros((n_snps, p), dtype=np.uint8), np.zeros((n_snps, p), dtype=np.uint8)
+    flags, n_iter, mark = (np.zeros((n_snps, p), dtype=np.uint8) for _ in range(3))
     usable = ~np.isnan(des.theta0).any(axis=1)
     V = np.zeros((P + 1, n_ind))
     V[:P] = des.basis
@@ -4566,7 +4633,13 @@ def ld_glm_logistic_host(codes, Y, covar=None, individuals=None, keep=None, max_
             if not usable[j]:
                 flags[i, j] = 4
                 continue
-            th, se, it, ok = _logit_newton(V, des.y[j], np.concatenate([des.theta0[j], [0.0]]), P)
+            start = np.concatenate([des.theta0[j], [0.0]])
+            if firth != "always":
+                th, se, it, ok = _logit_newton(V, des.y[j], start, P)
+                ok = ok and bool(np.isfinite(th[P]) and np.isfinite(se))
+            if firth == "always" or (firth == "fallback" and not ok):
+                th, se, it, ok = _firth_scoring(V, des.y[j], start, P)
+                mark[i, j] = 1
             n_iter[i, j] = it
             if not ok or not (np.isfinite(th[P]) and np.isfinite(se)):
                 flags[i, j] = 5
@@ -4575,7 +4648,7 @@ def ld_glm_logistic_host(codes, Y, covar=None, individuals=None, keep=None, max_
     live = flags == 0
     outs[3][live], outs[4][live] = logit_tail_host(outs[2][live])
     return LogitResult(*(torch.from_numpy(o) for o in outs), torch.from_numpy(flags), torch.from_numpy(n_iter),
-                       torch.from_numpy(counts.astype(np.int64)), des)
+                       torch.from_numpy(counts.astype(np.int64)), des, None if firth is None else torch.from_numpy(mark))
 
 
 # --------------------------------------------------------------------------- instrumentation
