@@ -1312,6 +1312,80 @@ int ldx_glm_firth_dev(const void *alt, const void *ref, uint32_t n_snps, uint32_
                       double *neglog10_p, uint8_t *flags, uint8_t *n_iter, size_t ld_out, uint32_t mode, uint8_t *firth,
                       void *stream);
 
+/* ---- genotype QC and table tests: per-group genotype counts, exact HWE and Fisher tests, the chi-square tests of --model -----
+ * This project's own definition (what PLINK --hardy, --missing, --het, --test-missing, --assoc fisher and --model report), NOT
+ * validated against PLINK: no PLINK binary was available to compare with.
+ *
+ * Individuals, called genotypes (a half-missing genotype is missing) and keep are those of "genotype products" above.
+ *
+ * ldx_geno_group_counts_dev: member uint32 [n_ind]; bit g of member[a] set = individual a belongs to group g, g < n_groups <=
+ * LDX_QC_MAX_GROUPS (higher bits are ignored).  Groups may overlap, be empty, or hold everybody.  counts uint32
+ * [n_snps][n_groups][4] = {called, het, hom ALT, 0} over the group's individuals.  Every word is written with plain stores (no
+ * memset by the caller), each 16-byte row as one group; a SNP that is not kept gets zeros.  The panel's two planes are read ONCE
+ * for all groups: a workgroup per slab of 128 SNPs; the groups' bit words (16 individuals per 32-bit word on the even slots) are
+ * made from member in LDS; the genotype words are the reverse product's own, so a group that holds every individual reproduces
+ * ldx_geno_snp_counts_dev bit for bit; per word and group three AND + popcount.  Pad haplotypes count as not called.
+ * A null pointer (keep may be NULL), an odd or zero n_hap, n_snps = 0, n_groups outside 1 .. LDX_QC_MAX_GROUPS or counts not
+ * 16-byte aligned = LDX_E_ARG; n_hap > LDX_MAX_HAPS or a bit plane of 4 GiB or more = LDX_E_UNSUPPORTED; checked before any HIP call.
+ *
+ * The exact tests work on m tuples in contiguous device arrays (uint32), one thread per tuple; a tuple's bits depend on the
+ * tuple alone; no floating-point atomics.  Outputs p, neglog10_p (double [m]) and flags (uint8 [m]).
+ * THE TWO-SIDED TAIL RULE, shared by both: with the distribution's terms P(k), p = the sum of the terms no more probable than
+ * the observed one, where term k is included iff P(k) / P(obs) <= 1 + 2^-30.  Exact ties occur (n = 6 with 4 ALT alleles:
+ * P(2 het) = P(4 het)) and are the observed term's equals: they are included.  The device forms every term relative to the
+ * observed one by the term ratio, from the observed term outwards; at most LDX_QC_MAX_N steps of three roundings each keep the
+ * relative error below 2^-35 (2^-39 for n <= 5120), so the rule is decided correctly wherever no exact ratio lies in
+ * [1 + 2^-31, 1 + 2^-29] -- a condition on the tuple that the test oracle asserts for every tuple it uses.
+ * midp = 1 gives p - P(obs) / 2 (Lancaster: only the observed term is halved; PLINK also halves the ties).
+ * Scaled sums: a term and the total are carried as v 2^(256 e), v in [2^-256, 2^256), the tail (terms <= 1 + 2^-30 of the
+ * observed one, which is 1) in a plain double; ln p = ln(tail) - ln(total), neglog10_p = -ln p / ln 10: finite where p
+ * underflows to 0 (all-heterozygous n = 2560: p about 1e-769).  When every term is in the tail p = 1 and neglog10_p = 0 exactly
+ * (midp: p = 1 - P(obs) / 2).  Terms past the mode that fall below 2^-1280 of the observed one are dropped.  |ln p| is within
+ * 2^-30 max(1, |ln p|) of the exact value.
+ *
+ * ldx_hwe_exact_dev: the exact test of Hardy-Weinberg proportions (Wigginton, Cutler, Abecasis 2005) on (n called, het, hom
+ * ALT): given n and n_A = het + 2 hom ALT alleles, the heterozygote count k has the parity of n_A and runs to min(n_A, 2n - n_A);
+ * P(k) ~ 2^k n! / (((n_A - k) / 2)! k! ((2n - n_A - k) / 2)!), P(k + 2) / P(k) = 4 n_AA n_BB / ((k + 2)(k + 1)).
+ *     flags, the first that applies: 3 not a genotype table (het + hom > n) or n > LDX_QC_MAX_N: NaN      1 n = 0: NaN
+ *                                    2 monomorphic: p = 1, neglog10_p = 0 exactly (midp or not)           0 OK
+ * ldx_fisher_exact_dev: Fisher's exact test on the 2 x 2 table [[a, b], [c, d]]: the first cell x of the tables with these
+ * margins, P(x + 1) / P(x) = (r1 - x)(c1 - x) / ((x + 1)(r2 - c1 + x + 1)), r1 = a + b, r2 = c + d, c1 = a + c.
+ *     flags: 3 a + b + c + d > 2 LDX_QC_MAX_N: NaN      1 empty table: NaN      2 a zero row or column margin: p = 1, neglog10_p = 0      0 OK
+ * A tuple outside the rules cannot be refused by these entries, which do not read device memory before the launch: it carries
+ * flag 3 and NaN, and the host layer (ops.ld_hwe_from_counts, ops.ld_fisher_from_counts), which holds the integers, refuses it
+ * as LDX_E_ARG before the call.
+ *
+ * ldx_model_tests_dev: the five tests of plink --model on (case n, het, hom; control n, het, hom), in this order: allelic,
+ * Cochran-Armitage trend, genotypic, dominant, recessive.  chisq, p, neglog10_p double [m][5], flags uint8 [m][5], odds double [m].
+ * R cases, S controls, N = R + S <= LDX_MAX_HAPS / 2; r0 r1 r2 / s0 s1 s2 the genotype counts, n_g = r_g + s_g.  Every integer is
+ * exact in int64; the fp64 operations, each rounded once, are exactly these (ops.model_tests_host repeats chisq and odds bit
+ * for bit):
+ *     2 x 2 table [[a, b], [c, d]] with total T:  chisq = ((double)T (double)((ad - bc)^2)) / (double)((a + b)(c + d)(a + c)(b + d))
+ *     allelic    T = 2N on allele counts a = r1 + 2 r2, b = 2R - a, c = s1 + 2 s2, d = 2S - c;  odds = (double)(ad) / (double)(bc)
+ *     trend      U = N (r1 + 2 r2) - R (n1 + 2 n2),  D = N (n1 + 4 n2) - (n1 + 2 n2)^2,  chisq = ((double)N (double)(U^2)) / (double)(R S D)
+ *     genotypic  chisq = sum over the cells in the order r0 r1 r2 s0 s1 s2, added one after the other from 0, of
+ *                (double)((O N - row col)^2) / (double)(N row col);  2 df
+ *     dominant   T = N on individuals: a = r1 + r2, b = r0, c = s1 + s2, d = s0          recessive  a = r2, b = r0 + r1, c = s2, d = s0 + s1
+ * Dominant and recessive are with respect to ALT (code 1), NOT to the minor allele.
+ * Tails: 1 df: the two-sided normal tail of sqrt(chisq), the function of "logistic association scan"; 2 df: ln p = -chisq / 2
+ * exactly, p = exp(-chisq / 2).  |ln p| is within 2^-30 max(1, |ln p|) of the exact value.
+ *     flags per test, the first that applies; every flag but 0 is NaN in chisq, p, neglog10_p (odds is NaN unless the allelic flag is 0):
+ *     4 not two genotype tables (het + hom > n) or N > LDX_MAX_HAPS / 2 (refused by the host layer, as above)
+ *     1 no called case or no called control      2 a zero margin: the statistic is undefined
+ *     3 genotypic only: a cell below min_cell (PLINK's --cell, default 5)      0 OK
+ * A null pointer, m = 0 or m > 2^38, a midp other than 0 or 1 = LDX_E_ARG, checked before any HIP call. */
+#define LDX_QC_MAX_GROUPS 32u
+#define LDX_QC_MAX_N 65536u                 /* individuals of an exact-test tuple (a Fisher table: 2 LDX_QC_MAX_N alleles) */
+int ldx_geno_group_counts_dev(const void *alt, const void *ref, uint32_t n_snps, uint32_t n_hap, const uint8_t *keep,
+                              const uint32_t *member, uint32_t n_groups, uint32_t *counts, void *stream);
+int ldx_hwe_exact_dev(size_t m, const uint32_t *n, const uint32_t *het, const uint32_t *hom, int midp, double *p,
+                      double *neglog10_p, uint8_t *flags, void *stream);
+int ldx_fisher_exact_dev(size_t m, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d, int midp,
+                         double *p, double *neglog10_p, uint8_t *flags, void *stream);
+int ldx_model_tests_dev(size_t m, const uint32_t *case_n, const uint32_t *case_het, const uint32_t *case_hom,
+                        const uint32_t *ctrl_n, const uint32_t *ctrl_het, const uint32_t *ctrl_hom, uint32_t min_cell,
+                        double *chisq, double *p, double *neglog10_p, double *odds, uint8_t *flags, void *stream);
+
 /* ---- synthetic panels: deterministic, identical on host and device ------ */
 /* codes int8 [n_snps][ld_codes] receive global SNPs [snp_offset, snp_offset + n_snps) (a rank's
  * shard).  thresholds: per-SNP ALT probability * 2^64 (computed on the host, see

@@ -31,6 +31,10 @@ from .ops import (GLM_FLAGS, GlmDesign, GlmResult, geno_counts_host, geno_snp_co
                   glm_tail_host, ld_glm, ld_glm_host)
 from .ops import (FIRTH_MODES, FIRTH_STOP, LOGIT_FLAGS, LogitDesign, LogitResult, ld_glm_logistic,  # noqa: F401
                   ld_glm_logistic_host, logit_design, logit_tail_host)
+from .ops import (MODEL_FLAGS, MODEL_TESTS, QC_FLAGS, HardyResult, MissingResult, ModelResult, SampleQC,  # noqa: F401
+                  fisher_exact_host, geno_group_counts, geno_group_counts_host, hwe_exact_host, ld_fisher_from_counts, ld_hardy,
+                  ld_hwe_from_counts, ld_model, ld_model_from_counts, ld_test_missing, model_tests_host, sample_qc,
+                  sample_qc_host, sample_qc_mask, snp_qc_mask)
 from .panel import PackedPanel, encode_codes, select_index  # noqa: F401
 from . import plink  # noqa: F401
 from .plink import BedFile, bed_codes_host, codes_bed_host, read_covar, read_pheno, write_bfile  # noqa: F401
@@ -49,4 +53,8 @@ __all__ = ["PackedPanel", "encode_codes", "select_index", "ld_triangle", "ld_are
            "glm_design", "GlmDesign", "ld_glm", "ld_glm_host", "glm_linear_host", "glm_tail_host", "GlmResult", "GLM_FLAGS", "LdxError",
            "logit_design", "LogitDesign", "ld_glm_logistic", "ld_glm_logistic_host", "logit_tail_host", "LogitResult", "LOGIT_FLAGS",
            "FIRTH_MODES", "FIRTH_STOP",
+           "geno_group_counts", "geno_group_counts_host", "ld_hwe_from_counts", "ld_fisher_from_counts", "ld_model_from_counts",
+           "hwe_exact_host", "fisher_exact_host", "model_tests_host", "ld_hardy", "HardyResult", "ld_model", "ModelResult",
+           "ld_test_missing", "MissingResult", "sample_qc", "sample_qc_host", "SampleQC", "snp_qc_mask", "sample_qc_mask",
+           "QC_FLAGS", "MODEL_TESTS", "MODEL_FLAGS",
            "version", "plink", "BedFile", "bed_codes_host", "codes_bed_host", "write_bfile", "read_pheno", "read_covar"]

@@ -41,6 +41,8 @@ GENO_MAX_SLICE_SNPS = 1 << 22            # LDX_GENO_MAX_SLICE_SNPS
 LOGIT_MAX_COV = 13                       # LDX_LOGIT_MAX_COV
 LOGIT_MAX_ITER = 30                      # LDX_LOGIT_MAX_ITER
 FIRTH_MAX_ITER = 200                     # LDX_FIRTH_MAX_ITER
+QC_MAX_GROUPS = 32                       # LDX_QC_MAX_GROUPS
+QC_MAX_N = 65536                         # LDX_QC_MAX_N
 FLAG_DPRIME_INT0 = 1
 FLAG_RSQ_INT0 = 2
 MEASURES = {"r_square": 0, "d_prime": 1}
@@ -222,6 +224,10 @@ SIGNATURES = {
                                     _vp, _vp, _sz, _vp]),
     "ldx_glm_firth_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _sz, _u32, _vp, _vp, _u32, _dbl, _vp, _vp, _vp, _vp, _vp,
                                  _vp, _vp, _sz, _u32, _vp, _vp]),
+    "ldx_geno_group_counts_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp]),
+    "ldx_hwe_exact_dev": (_int, [_sz, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp]),
+    "ldx_fisher_exact_dev": (_int, [_sz, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp]),
+    "ldx_model_tests_dev": (_int, [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ldx_ld_select_workspace_bytes": (_sz, [_u32]),
     "ldx_ld_select_dev": (_int, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ldx_set_area_path": (_int, [_int]),

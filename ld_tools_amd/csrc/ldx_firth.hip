@@ -21,6 +21,7 @@
 #include <math.h>
 
 #include "ldx_fp4.h"
+#include "ldx_tail.h"   // normal_tail
 
 namespace ldx {
 namespace firth {
@@ -37,8 +38,6 @@ constexpr uint32_t kRowW = 16;                 // row of the LDS tile that holds
 constexpr uint32_t kStride = 68;               // doubles per row of the tile: rows i and i + 1 start 8 banks apart
 constexpr uint32_t kTile = 17u * kStride;      // doubles of a wave's tile
 constexpr double kStop = 0x1p-88;
-constexpr double kLn10 = 2.302585092994046;
-constexpr double kSqrtHalf = 0.7071067811865476;
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 
@@ -76,15 +75,6 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// ln p and p of the two-sided normal tail of z: p = erfc(|z| / sqrt 2); ln p from erfcx where erfc loses its range
-__device__ __forceinline__ void normal_tail(double z, double &pv, double &nlp)
-{
-    const double t = fabs(z) * kSqrtHalf;
-    pv = erfc(t);
-    const double lnp = t < 5.0 ? log(pv) : log(erfcx(t)) - t * t;
-    nlp = t == 0.0 ? 0.0 : -lnp / kLn10;
 }
 
 __global__ void __launch_bounds__(kThreads, kMinWaves) firth_kernel(Args p)

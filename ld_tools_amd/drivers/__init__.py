@@ -24,6 +24,8 @@ from .glm import GlmTable, glm_table, write_glm_linear  # noqa: F401
 from .king import KingTable, king_table, write_kin0, write_king_cutoff, write_king_matrix  # noqa: F401
 from .pca import PcaTable, ScoreTable, pca_table, score_table, write_eigenval, write_eigenvec, write_sscore  # noqa: F401
 from .prune import PruneTable, prune, write_prune  # noqa: F401
+from .qc import (QcVariants, write_assoc_fisher, write_hardy, write_het, write_model, write_smiss,  # noqa: F401
+                 write_test_missing, write_vmiss)
 from .regions import write_regions  # noqa: F401
 from .lite import DifChrsError, NotInIntgenConvDbError, NotRsIdError, check_rs_id, ld_lite_table  # noqa: F401
 from .triangle import (TriangleMatrix, create_matrix, stream_triangle_table, triangle_matrix,  # noqa: F401
@@ -32,7 +34,8 @@ from .triangle import (TriangleMatrix, create_matrix, stream_triangle_table, tri
 # drivers/plink.py is also a command (python -m ld_tools_amd.drivers.plink), so its names are bound on first use rather than
 # imported here: runpy would otherwise find the module loaded before it runs it
 _PLINK_NAMES = ("Bfile", "load_bfile", "bfile_ld_table", "bfile_clump", "bfile_prune", "bfile_ld_scores", "bfile_band",
-                "bfile_em_band", "bfile_blocks", "bfile_king", "bfile_pca", "bfile_score", "bfile_glm", "read_score_file", "make_bed")
+                "bfile_em_band", "bfile_blocks", "bfile_king", "bfile_pca", "bfile_score", "bfile_glm", "read_score_file", "make_bed",
+                "bfile_hardy", "bfile_missing", "bfile_het", "bfile_model", "bfile_qc")
 
 
 def __getattr__(name):

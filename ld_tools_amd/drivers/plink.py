@@ -15,12 +15,18 @@ dataclasses of the VCF drivers from it, so that their writers write them unchang
     bfile_glm        -> GlmTables for write_glm_linear                     PLINK 2 --glm (quantitative traits, mean imputation)
     bfile_logistic   -> LogisticTables for write_glm_logistic              PLINK 2 --glm (case/control traits, no Firth fallback)
                         (firth=: write_glm_hybrid / write_glm_firth         PLINK 2 --glm firth-fallback / firth)
+    bfile_hardy      -> HardyResult for write_hardy                        PLINK --hardy (exact test, per group)
+    bfile_missing    -> write_vmiss / write_smiss / write_test_missing     PLINK 2 --missing, PLINK --test-missing
+    bfile_het        -> SampleQC for write_het                             PLINK --het
+    bfile_model      -> ModelResult for write_model / write_assoc_fisher   PLINK --model, --assoc fisher
+    bfile_qc         -> QcMasks (.qc.in / .qc.out / .qc.keep)              PLINK --mind --geno --maf --hwe
 
 A ``.bed`` holds unphased genotype calls: a het is written (ALT, REF) whatever the truth, so the haplotype r of the phased
 operators means nothing here.  Every driver defaults to an unphased form (EM or genotype dosage) and refuses
 ``dosage=False, em=False``.  ``make_bed`` writes a panel, or a subset of a loaded fileset, back as a fileset.
 
-    python -m ld_tools_amd.drivers.plink {ld,clump,prune,l2,blocks,king,pca,score,glm,logistic,make-bed} --bfile P --out O ...
+    python -m ld_tools_amd.drivers.plink {ld,clump,prune,l2,blocks,king,pca,score,glm,logistic,hardy,missing,het,model,qc,make-bed}
+        --bfile P --out O ...
 """
 from __future__ import annotations
 
@@ -591,6 +597,143 @@ def bfile_logistic(src, pheno, covar=None, out: Optional[str] = None, pheno_name
     return tables
 
 
+def _qc_variants(bf: Bfile):
+    from .qc import QcVariants
+
+    return QcVariants(list(bf.chrom), _poss(bf), list(bf.ids), list(bf.alts), list(bf.refs))
+
+
+def _case_vector(what: str, bf: Bfile, pheno, pheno_name: Optional[str]) -> np.ndarray:
+    """0 / 1 / NaN per individual of ``bf`` from a phenotype table (one column: ``pheno_name``, default the first) through
+    case_control; None: the ``.fam``'s own phenotype column (1 / 2; 0, -9 and anything else = NaN).  A quantitative column is
+    refused."""
+    if pheno is None:
+        v = np.full(len(bf.iid), np.nan)
+        for k, x in enumerate(bf.pheno):
+            if x in ("1", "2"):
+                v[k] = float(x)
+        name = "of the .fam"
+    else:
+        names, Y = _sample_rows("phenotype", pheno, bf, None if pheno_name is None else [pheno_name])
+        v, name = Y[:, 0], names[0]
+    try:
+        return case_control(name, v)
+    except LdxError as exc:
+        raise LdxError(f"{what}: {str(exc).replace('bfile_logistic: ', '')}") from None
+
+
+def bfile_hardy(src, out: Optional[str] = None, groups=None, midp: bool = False, **load):
+    """ops.ld_hardy from a fileset (PLINK --hardy): genotype counts and the exact HWE test of every variant, within each group
+    of ``groups`` (ops.geno_group_counts'; None: everybody).  ``out``: a prefix to write ``.hardy`` under (one group), or
+    ``.<label>.hardy`` per group.  Returns (QcVariants, HardyResult)."""
+    from ..ops import ld_hardy
+    from .qc import write_hardy
+
+    bf = _loaded(src, **load)
+    res, variants = ld_hardy(bf.panel, groups, midp=midp), _qc_variants(bf)
+    if out is not None:
+        for g, label in enumerate(res.labels):
+            write_hardy(f"{out}.hardy" if len(res.labels) == 1 else f"{out}.{label}.hardy", variants, res, g)
+    return variants, res
+
+
+def bfile_missing(src, out: Optional[str] = None, pheno=None, pheno_name: Optional[str] = None, midp: bool = False, **load):
+    """Missing-call reports of a fileset (PLINK 2 --missing): ``.vmiss`` per variant and ``.smiss`` per individual; with a
+    case/control phenotype (``pheno``: a table or its (fid, iid, names, values), ``pheno_name`` its column) also PLINK's
+    --test-missing as ``.missing``.  Returns (QcVariants, called per variant, SampleQC, MissingResult or None)."""
+    from ..ops import geno_snp_counts, ld_test_missing, sample_qc
+    from .qc import write_smiss, write_test_missing, write_vmiss
+
+    bf = _loaded(src, **load)
+    variants = _qc_variants(bf)
+    called, qc = geno_snp_counts(bf.panel)[:, 0], sample_qc(bf.panel)
+    tm = None if pheno is None else ld_test_missing(bf.panel, _case_vector("bfile_missing", bf, pheno, pheno_name), midp=midp)
+    if out is not None:
+        write_vmiss(out + ".vmiss", variants, called, bf.panel.n_ind)
+        write_smiss(out + ".smiss", bf.fid, bf.iid, qc)
+        if tm is not None:
+            write_test_missing(out + ".missing", variants, tm)
+    return variants, called, qc, tm
+
+
+def bfile_het(src, out: Optional[str] = None, **load):
+    """ops.sample_qc from a fileset (PLINK --het): per individual the observed and expected homozygous calls and the inbreeding
+    coefficient F.  ``out``: a prefix to write ``.het`` under.  Returns the SampleQC."""
+    from ..ops import sample_qc
+    from .qc import write_het
+
+    bf = _loaded(src, **load)
+    qc = sample_qc(bf.panel)
+    if out is not None:
+        write_het(out + ".het", bf.fid, bf.iid, qc)
+    return qc
+
+
+def bfile_model(src, pheno=None, out: Optional[str] = None, pheno_name: Optional[str] = None, midp: bool = False,
+                min_cell: int = 5, **load):
+    """ops.ld_model from a fileset (PLINK --model and --assoc fisher): the five chi-square table tests and Fisher's exact test on
+    the allele counts.  ``pheno``: a case/control phenotype table (case_control: 1 / 2 or 0 / 1; None: the ``.fam``'s column);
+    a quantitative trait is refused -- it belongs to bfile_glm.  ``out``: a prefix to write ``.model`` and ``.assoc.fisher``
+    under.  Returns (QcVariants, ModelResult)."""
+    from ..ops import ld_model
+    from .qc import write_assoc_fisher, write_model
+
+    bf = _loaded(src, **load)
+    res = ld_model(bf.panel, _case_vector("bfile_model", bf, pheno, pheno_name), midp=midp, min_cell=min_cell)
+    variants = _qc_variants(bf)
+    if out is not None:
+        write_model(out + ".model", variants, res)
+        write_assoc_fisher(out + ".assoc.fisher", variants, res)
+    return variants, res
+
+
+@dataclass
+class QcMasks:
+    """bfile_qc's result: ``snps`` uint8 device tensor [variants] (an operator's ``keep=``), ``individuals`` bool [individuals]."""
+
+    snps: object
+    individuals: np.ndarray
+
+    @property
+    def extract(self) -> np.ndarray:
+        """The variant mask as bool [variants] on the host: load_bfile's ``extract`` (``individuals`` is its ``keep``)."""
+        return self.snps.cpu().numpy().astype(bool)
+
+
+def bfile_qc(src, out: Optional[str] = None, geno: Optional[float] = None, maf: Optional[float] = None,
+             hwe: Optional[float] = None, mind: Optional[float] = None, pheno=None, pheno_name: Optional[str] = None,
+             midp: bool = False, **load) -> QcMasks:
+    """PLINK's --mind, then --geno --maf --hwe, on a fileset: individuals with a missing-call rate above ``mind`` go first, and
+    the variant filters (ops.snp_qc_mask) see the remaining individuals; HWE is tested on the controls when a phenotype is given
+    (``pheno`` / ``pheno_name`` as bfile_model; the ``.fam``'s own column is not used), on everybody otherwise.  ``out``: a prefix
+    to write the variant lists ``.qc.in`` / ``.qc.out`` and the individual list ``.qc.keep`` (FID IID) under.  The masks go to
+    bfile_prune / bfile_king and to every operator's ``keep=`` as they stand."""
+    from ..ops import sample_qc_mask, snp_qc_mask
+
+    bf = _loaded(src, **load)
+    panel = bf.panel
+    ind = sample_qc_mask(panel, mind_max=mind) if mind is not None else np.ones(panel.n_ind, dtype=bool)
+    if not ind.any():
+        raise LdxError("bfile_qc: no individual passes mind")
+    if not ind.all():
+        rows = np.flatnonzero(ind)
+        panel = panel.select(haplotypes=np.stack([2 * rows, 2 * rows + 1], axis=1).reshape(-1))
+    hwe_group = None
+    if pheno is not None and hwe is not None:
+        hwe_group = _case_vector("bfile_qc", bf, pheno, pheno_name)[ind] == 0.0
+        if not hwe_group.any():
+            raise LdxError("bfile_qc: the phenotype leaves no control to test HWE on")
+    snps = snp_qc_mask(panel, maf_min=maf, geno_max=geno, hwe_min=hwe, hwe_group=hwe_group, midp=midp)
+    if out is not None:
+        ok = snps.cpu().numpy().astype(bool)
+        for ext, want in ((".qc.in", True), (".qc.out", False)):
+            with open(out + ext, "w") as f:
+                f.writelines(f"{name}\n" for name, o in zip(bf.ids, ok) if o == want)
+        with open(out + ".qc.keep", "w") as f:
+            f.writelines(f"{a}\t{b}\n" for a, b, o in zip(bf.fid, bf.iid, ind) if o)
+    return QcMasks(snps, ind)
+
+
 def make_bed(prefix_out, src, snps=None, individuals=None, bim: Optional[dict] = None, fam: Optional[dict] = None,
              alt: Optional[str] = None) -> List[str]:
     """Write a fileset.  ``src``: a ``Bfile`` -- ``snps`` / ``individuals`` (index arrays or masks over ITS variants and
@@ -722,6 +865,24 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--firth", choices=("fallback", "always"), default=None,
                    help="Firth's penalised fit where the likelihood has no finite maximiser (.glm.logistic.hybrid) or for every "
                         "variant (.glm.firth); default: off")
+    p = common("hardy", "genotype counts and the exact Hardy-Weinberg test per variant (.hardy)")
+    p.add_argument("--midp", action="store_true", help="the mid-p: half of the observed term is taken off")
+    p = common("missing", "missing-call rates per variant and individual (.vmiss, .smiss; with --pheno: .missing)")
+    p.add_argument("--pheno", default=None, help="case/control phenotype table: adds the test of missingness by status")
+    p.add_argument("--pheno-name", default=None, help="its column (default: the first)")
+    p.add_argument("--midp", action="store_true")
+    common("het", "observed and expected homozygous calls and the inbreeding coefficient per individual (.het)")
+    p = common("model", "case/control table tests per variant (.model, .assoc.fisher)")
+    p.add_argument("--pheno", default=None, help="case/control phenotype table, 1 / 2 or 0 / 1 (default: the .fam's column)")
+    p.add_argument("--pheno-name", default=None, help="its column (default: the first)")
+    p.add_argument("--cell", type=int, default=5, help="smallest cell of the genotypic test")
+    p.add_argument("--midp", action="store_true", help="the mid-p of Fisher's exact test")
+    p = common("qc", "variant and individual filters (.qc.in, .qc.out, .qc.keep); --maf and --geno are applied here, after --mind")
+    p.add_argument("--hwe", type=float, default=None, help="smallest exact HWE p of a variant (on the controls with --pheno)")
+    p.add_argument("--mind", type=float, default=None, help="largest missing-call rate of an individual")
+    p.add_argument("--pheno", default=None, help="case/control phenotype table: HWE is tested on its controls")
+    p.add_argument("--pheno-name", default=None, help="its column (default: the first)")
+    p.add_argument("--midp", action="store_true")
     common("make-bed", "write the selected variants and individuals as a new fileset")
     return ap
 
@@ -736,8 +897,27 @@ def main(argv=None) -> int:
     a = parser().parse_args(argv)
     keep = None if a.keep is None else _read_names(a.keep, 2)
     extract = None if a.extract is None else _read_names(a.extract, 1)
-    bf = load_bfile(a.bfile, chrom=a.chr, keep=keep, extract=extract, maf_min=a.maf, geno_max=a.geno, alt=a.alt)
-    if a.command == "ld":
+    own_filters = a.command == "qc"      # qc applies --maf / --geno itself, after --mind
+    bf = load_bfile(a.bfile, chrom=a.chr, keep=keep, extract=extract, maf_min=None if own_filters else a.maf,
+                    geno_max=None if own_filters else a.geno, alt=a.alt)
+    if a.command == "hardy":
+        variants, _ = bfile_hardy(bf, out=a.out, midp=a.midp)
+        print(len(variants), "variants ->", a.out + ".hardy")
+    elif a.command == "missing":
+        variants, _, qc, tm = bfile_missing(bf, out=a.out, pheno=a.pheno, pheno_name=a.pheno_name, midp=a.midp)
+        print(len(variants), "variants,", qc.called.size, "individuals ->", a.out + ".vmiss", a.out + ".smiss",
+              *([] if tm is None else [a.out + ".missing"]))
+    elif a.command == "het":
+        print(bfile_het(bf, out=a.out).called.size, "individuals ->", a.out + ".het")
+    elif a.command == "model":
+        variants, _ = bfile_model(bf, a.pheno, out=a.out, pheno_name=a.pheno_name, midp=a.midp, min_cell=a.cell)
+        print(len(variants), "variants ->", a.out + ".model", a.out + ".assoc.fisher")
+    elif a.command == "qc":
+        masks = bfile_qc(bf, out=a.out, geno=a.geno, maf=a.maf, hwe=a.hwe, mind=a.mind, pheno=a.pheno, pheno_name=a.pheno_name,
+                         midp=a.midp)
+        print(int(masks.extract.sum()), "of", bf.n, "variants,", int(masks.individuals.sum()), "of", len(bf.iid),
+              "individuals ->", a.out + ".qc.in", a.out + ".qc.out", a.out + ".qc.keep")
+    elif a.command == "ld":
         side, hits = bfile_ld_table(bf, r2=a.ld_window_r2, window_bp=int(a.ld_window_kb * 1000), missing=a.missing)
         print(write_ld_table(a.out + ".ld", side, side, hits), "pairs ->", a.out + ".ld")
     elif a.command == "clump":

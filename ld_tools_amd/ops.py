@@ -25,6 +25,9 @@
     ld_glm(panel, Y, covar, ...)            linear association scan on the reverse genotype product
     ld_glm_logistic(panel, Y, covar, ...)   logistic association scan for 0/1 traits: a Newton fit per cell on the fp64 matrix cores;
                                             firth="fallback" / "always": Firth's penalised fit where that has no finite maximiser / everywhere
+    geno_group_counts(panel, groups)        genotype counts of every SNP within each of up to 32 groups of individuals, one pass
+    ld_hardy / ld_model / ld_test_missing   exact HWE test per group; the table tests of --model and Fisher's test; missingness by status
+    sample_qc / snp_qc_mask / sample_qc_mask   per-individual call counts and F; the --maf / --geno / --hwe and --mind masks
     pair_counts(panel_i, panel_j)           <- calc_ld.py:32           (bit-exact n11 block)
     ld_from_counts(n, n11, a1, r1, a2, r2)  <- calc_ld.py:33-97        (the epilogue alone)
 
@@ -4649,6 +4652,555 @@ def ld_glm_logistic_host(codes, Y, covar=None, individuals=None, keep=None, max_
     outs[3][live], outs[4][live] = logit_tail_host(outs[2][live])
     return LogitResult(*(torch.from_numpy(o) for o in outs), torch.from_numpy(flags), torch.from_numpy(n_iter),
                        torch.from_numpy(counts.astype(np.int64)), des, None if firth is None else torch.from_numpy(mark))
+
+
+# --------------------------------------------------------------------------- genotype QC and table tests
+QC_FLAGS = {0: "ok", 1: "empty", 2: "degenerate", 3: "not a table"}          # ldx_hwe_exact_dev / ldx_fisher_exact_dev
+MODEL_TESTS = ("ALLELIC", "TREND", "GENO", "DOM", "REC")                      # the order of ldx_model_tests_dev
+MODEL_FLAGS = {0: "ok", 1: "no case or no control", 2: "zero margin", 3: "small cell", 4: "not a table"}
+MODEL_MAX_N = _lib.MAX_HAPS // 2                # cases + controls of a model tuple
+TIE_BITS = 30                                   # a term is in the tail iff P(k) / P(obs) <= 1 + 2^-30
+
+
+def _qc_missing(what: str, missing) -> None:
+    if missing is not None:
+        raise _lib.LdxError(f"{what}: missing={missing!r} has no meaning here: the counts are over each SNP's own called "
+                            "individuals (missing must be None)")
+
+
+def _groups_member(what: str, groups, n_ind: int) -> Tuple[np.ndarray, np.ndarray, list]:
+    """(member uint32 [n_ind], sizes int64 [n_groups], labels) of ``groups``: a bool / 0-1 matrix [n_groups, n_ind] (labels
+    0 .. n_groups - 1), or a vector [n_ind] of labels expanded to one group per distinct label in sorted order (a NaN label:
+    in no group).  None: one group of everybody."""
+    if groups is None:
+        return np.ones(n_ind, dtype=np.uint32), np.asarray([n_ind], dtype=np.int64), [0]
+    g = groups.cpu().numpy() if isinstance(groups, torch.Tensor) else np.asarray(groups)
+    if g.ndim == 1:
+        if g.shape != (n_ind,):
+            raise _lib.LdxError(f"{what}: a label vector needs one entry per individual ({n_ind}), got {g.shape}")
+        live = ~np.isnan(g) if g.dtype.kind == "f" else np.ones(n_ind, dtype=bool)
+        labels = sorted(set(g[live].tolist()))
+        g = np.stack([live & (g == lab) for lab in labels]) if labels else np.zeros((0, n_ind), dtype=bool)
+    else:
+        if g.ndim != 2 or g.shape[1] != n_ind or (g.dtype != bool and not np.isin(g, (0, 1)).all()):
+            raise _lib.LdxError(f"{what}: groups must be a bool / 0-1 matrix [n_groups, {n_ind}] or a label vector [{n_ind}]")
+        labels = list(range(g.shape[0]))
+    if not 1 <= g.shape[0] <= _lib.QC_MAX_GROUPS:
+        raise _lib.LdxError(f"{what}: 1 to {_lib.QC_MAX_GROUPS} groups per call (got {g.shape[0]})")
+    g = g.astype(bool)
+    member = np.zeros(n_ind, dtype=np.uint32)
+    for k in range(g.shape[0]):
+        member |= g[k].astype(np.uint32) << np.uint32(k)
+    return member, g.sum(axis=1).astype(np.int64), labels
+
+
+def _member_matrix(member: np.ndarray, n_groups: int) -> np.ndarray:
+    return ((member[None, :] >> np.arange(n_groups, dtype=np.uint32)[:, None]) & 1).astype(bool)
+
+
+def geno_group_counts_host(codes, groups, keep=None) -> Tuple[np.ndarray, np.ndarray]:
+    """Host mirror of geno_group_counts on the allele codes: (uint32 [n_snps, n_groups, 4] = {called, het, hom ALT, 0} over each
+    group's individuals, the group sizes int64 [n_groups])."""
+    g, c = geno_planes_host(codes, keep)
+    member, sizes, _ = _groups_member("geno_group_counts_host", groups, g.shape[1])
+    m = _member_matrix(member, sizes.size).astype(np.int64).T            # [n_ind, n_groups]
+    out = np.stack([c @ m, (g == 1).astype(np.int64) @ m, (g == 2).astype(np.int64) @ m, np.zeros((g.shape[0], sizes.size), dtype=np.int64)],
+                   axis=2)
+    return out.astype(np.uint32), sizes
+
+
+def _group_counts(panel: PackedPanel, keep_d: Optional[torch.Tensor], member: np.ndarray, n_groups: int) -> torch.Tensor:
+    mem = torch.from_numpy(member.view(np.int32)).to(panel.device)
+    counts = torch.empty((panel.n_snps, n_groups, 4), dtype=torch.int32, device=panel.device)
+    check(lib.ldx_geno_group_counts_dev(panel.alt.data_ptr(), panel.ref.data_ptr(), panel.n_snps, panel.n_hap, _ptr(keep_d),
+                                        mem.data_ptr(), n_groups, counts.data_ptr(), _stream_ptr()), "ldx_geno_group_counts_dev")
+    return counts
+
+
+def geno_group_counts(panel: PackedPanel, groups, keep=None) -> Tuple[torch.Tensor, np.ndarray]:
+    """(int32 device tensor [n_snps, n_groups, 4] (the words are uint32), the group sizes int64 [n_groups]): per SNP and group of
+    individuals the called, heterozygous and homozygous-ALT individuals and a zero, in ONE pass over the panel's planes
+    (ldx_geno_group_counts_dev).  ``groups``: a bool / 0-1 matrix [n_groups, n_ind] -- the groups may overlap, be empty or hold
+    everybody -- or a label vector [n_ind], one group per distinct label in sorted order; at most 32 groups.  The rows of SNPs
+    that ``keep`` drops are 0.  A group of everybody reproduces geno_snp_counts bit for bit."""
+    require_gpu()
+    _even_n_hap("geno_group_counts", panel)
+    member, sizes, _ = _groups_member("geno_group_counts", groups, panel.n_ind)
+    return _group_counts(panel, _keep_dev(keep, panel.n_snps, panel.device), member, int(sizes.size)), sizes
+
+
+def _int_cols(what: str, named) -> list:
+    """The integer arrays of a from_counts call as flat int64 numpy arrays of one length, uint32 values."""
+    cols = []
+    for name, v in named:
+        v = np.ascontiguousarray(v.cpu().numpy() if hasattr(v, "cpu") else v).reshape(-1)
+        if v.dtype.kind not in "iu":
+            raise _lib.LdxError(f"{what}: {name} must be an integer array, got {v.dtype}")
+        if v.size and (int(v.min()) < 0 or int(v.max()) >= (1 << 32)):
+            raise _lib.LdxError(f"{what}: {name} must hold uint32 values")
+        cols.append(v.astype(np.int64))
+    if any(c.size != cols[0].size for c in cols):
+        raise _lib.LdxError(f"{what}: {', '.join(n for n, _ in named)} differ in length")
+    if cols[0].size == 0:
+        raise _lib.LdxError(f"{what}: no tuple given")
+    return cols
+
+
+def _to_dev_u32(cols, dev) -> list:
+    return [torch.from_numpy(c.astype(np.uint32).view(np.int32)).to(dev) for c in cols]
+
+
+def _hwe_check(what: str, n, het, hom) -> None:
+    if (het + hom > n).any():
+        raise _lib.LdxError(f"{what}: LDX_E_ARG: het + hom > n in a tuple")
+    if (n > _lib.QC_MAX_N).any():
+        raise _lib.LdxError(f"{what}: LDX_E_ARG: n > LDX_QC_MAX_N = {_lib.QC_MAX_N} in a tuple")
+
+
+def _fisher_check(what: str, a, b, c, d) -> None:
+    if (a + b + c + d > 2 * _lib.QC_MAX_N).any():
+        raise _lib.LdxError(f"{what}: LDX_E_ARG: a table holds more than 2 LDX_QC_MAX_N = {2 * _lib.QC_MAX_N} counts")
+
+
+def _model_check(what: str, R, r1, r2, S, s1, s2) -> None:
+    if (r1 + r2 > R).any() or (s1 + s2 > S).any():
+        raise _lib.LdxError(f"{what}: LDX_E_ARG: het + hom > n in a tuple")
+    if (R + S > MODEL_MAX_N).any():
+        raise _lib.LdxError(f"{what}: LDX_E_ARG: more than {MODEL_MAX_N} cases and controls in a tuple")
+
+
+def _exact_launch(entry: str, cols: list, midp: bool):
+    m = int(cols[0].numel())
+    dev = cols[0].device
+    p = torch.empty(m, dtype=torch.float64, device=dev)
+    nlp = torch.empty(m, dtype=torch.float64, device=dev)
+    flags = torch.empty(m, dtype=torch.uint8, device=dev)
+    check(getattr(lib, entry)(m, *(c.data_ptr() for c in cols), int(bool(midp)), p.data_ptr(), nlp.data_ptr(), flags.data_ptr(),
+                              _stream_ptr()), entry)
+    return p, nlp, flags
+
+
+def ld_hwe_from_counts(n, het, hom, midp: bool = False, device: Optional[torch.device] = None):
+    """The exact test of Hardy-Weinberg proportions on integer tuples (n called, het, hom ALT) (ldx_hwe_exact_dev; include/ldx.h,
+    "genotype QC and table tests"): (p, neglog10_p float64, flags uint8) device tensors [m].  ``midp``: p - P(obs) / 2.  flags
+    (QC_FLAGS): 1 n = 0 (NaN), 2 monomorphic (p = 1).  A tuple with het + hom > n or n > 65536 is refused (LDX_E_ARG)."""
+    require_gpu()
+    dev = device or torch.device("cuda", torch.cuda.current_device())
+    cols = _int_cols("ld_hwe_from_counts", (("n", n), ("het", het), ("hom", hom)))
+    _hwe_check("ld_hwe_from_counts", *cols)
+    return _exact_launch("ldx_hwe_exact_dev", _to_dev_u32(cols, dev), midp)
+
+
+def ld_fisher_from_counts(a, b, c, d, midp: bool = False, device: Optional[torch.device] = None):
+    """Fisher's exact test on the 2 x 2 tables [[a, b], [c, d]] (ldx_fisher_exact_dev), the two-sided tail rule of the HWE test:
+    (p, neglog10_p, flags) device tensors [m].  flags: 1 empty table (NaN), 2 a zero row or column margin (p = 1).  A table of
+    more than 131072 counts is refused (LDX_E_ARG)."""
+    require_gpu()
+    dev = device or torch.device("cuda", torch.cuda.current_device())
+    cols = _int_cols("ld_fisher_from_counts", (("a", a), ("b", b), ("c", c), ("d", d)))
+    _fisher_check("ld_fisher_from_counts", *cols)
+    return _exact_launch("ldx_fisher_exact_dev", _to_dev_u32(cols, dev), midp)
+
+
+def _model_launch(cols: list, min_cell: int):
+    m, dev = int(cols[0].numel()), cols[0].device
+    chisq, p, nlp = (torch.empty((m, 5), dtype=torch.float64, device=dev) for _ in range(3))
+    odds = torch.empty(m, dtype=torch.float64, device=dev)
+    flags = torch.empty((m, 5), dtype=torch.uint8, device=dev)
+    check(lib.ldx_model_tests_dev(m, *(c.data_ptr() for c in cols), int(min_cell), chisq.data_ptr(), p.data_ptr(), nlp.data_ptr(),
+                                  odds.data_ptr(), flags.data_ptr(), _stream_ptr()), "ldx_model_tests_dev")
+    return chisq, p, nlp, odds, flags
+
+
+def _min_cell(what: str, min_cell) -> int:
+    if int(min_cell) != min_cell or not 0 <= int(min_cell) < (1 << 32):
+        raise _lib.LdxError(f"{what}: min_cell must be an integer in 0 .. 2^32 - 1")
+    return int(min_cell)
+
+
+def ld_model_from_counts(case_n, case_het, case_hom, ctrl_n, ctrl_het, ctrl_hom, min_cell: int = 5,
+                         device: Optional[torch.device] = None):
+    """The five chi-square tests of ``plink --model`` on integer tuples (ldx_model_tests_dev), MODEL_TESTS in this order: allelic,
+    Cochran-Armitage trend, genotypic (2 df), dominant, recessive -- the last two with respect to ALT, not to the minor allele.
+    Returns (chisq, p, neglog10_p float64 [m, 5], odds float64 [m] -- the allelic odds ratio --, flags uint8 [m, 5]:
+    MODEL_FLAGS) on the device.  model_tests_host gives chisq, odds and the flags bit for bit."""
+    require_gpu()
+    dev = device or torch.device("cuda", torch.cuda.current_device())
+    cols = _int_cols("ld_model_from_counts", (("case_n", case_n), ("case_het", case_het), ("case_hom", case_hom),
+                                              ("ctrl_n", ctrl_n), ("ctrl_het", ctrl_het), ("ctrl_hom", ctrl_hom)))
+    _model_check("ld_model_from_counts", *cols)
+    return _model_launch(_to_dev_u32(cols, dev), _min_cell("ld_model_from_counts", min_cell))
+
+
+def _tail_ints(weights: list, io: int, midp: bool) -> Tuple[float, float]:
+    """(p, neglog10_p) by the two-sided tail rule from the terms' exact integer weights: term k is in the tail iff
+    w_k / w_obs <= 1 + 2^-30.  ln p is the difference of two logarithms of Python integers: no range to leave."""
+    wo, one = weights[io], 1 << TIE_BITS
+    tail = sum(w for w in weights if w * one <= wo * (one + 1))
+    total = sum(weights)
+    num, den = (2 * tail - wo, 2 * total) if midp else (tail, total)
+    if num == den:
+        return 1.0, 0.0
+    lnp = math.log(num) - math.log(den)
+    try:
+        p = num / den                      # int / int: correctly rounded, 0.0 on underflow
+    except OverflowError:
+        p = math.exp(lnp)
+    return p, -lnp / 2.302585092994046
+
+
+def hwe_exact_host(n, het, hom, midp: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Host mirror of ld_hwe_from_counts in Python integers: P(k) ~ 2^k n! / (hA! k! hB!) is 2^k times a multinomial
+    coefficient, an exact integer; the first term from binomials, the others by the term ratio.  (p, neglog10_p float64 [m],
+    flags uint8 [m]); within the contract, not bit for bit."""
+    n, het, hom = _int_cols("hwe_exact_host", (("n", n), ("het", het), ("hom", hom)))
+    _hwe_check("hwe_exact_host", n, het, hom)
+    p, nlp, flags = np.full(n.size, np.nan), np.full(n.size, np.nan), np.zeros(n.size, dtype=np.uint8)
+    for i, (ni, hi, mi) in enumerate(zip(n.tolist(), het.tolist(), hom.tolist())):
+        nA = hi + 2 * mi
+        nB = 2 * ni - nA
+        if ni == 0:
+            flags[i] = 1
+        elif nA == 0 or nB == 0:
+            flags[i], p[i], nlp[i] = 2, 1.0, 0.0
+        else:
+            k0 = nA & 1
+            w = [(math.comb(ni, k0) * math.comb(ni - k0, (nA - k0) // 2)) << k0]
+            for k in range(k0, min(nA, nB), 2):      # w_{k+2} = w_k 4 hA hB / ((k + 2)(k + 1)): the division is exact
+                w.append(w[-1] * (4 * ((nA - k) // 2) * ((nB - k) // 2)) // ((k + 2) * (k + 1)))
+            p[i], nlp[i] = _tail_ints(w, (hi - k0) // 2, midp)
+    return p, nlp, flags
+
+
+def fisher_exact_host(a, b, c, d, midp: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Host mirror of ld_fisher_from_counts in Python integers: P(x) ~ C(r1, x) C(r2, c1 - x)."""
+    a, b, c, d = _int_cols("fisher_exact_host", (("a", a), ("b", b), ("c", c), ("d", d)))
+    _fisher_check("fisher_exact_host", a, b, c, d)
+    p, nlp, flags = np.full(a.size, np.nan), np.full(a.size, np.nan), np.zeros(a.size, dtype=np.uint8)
+    for i, (ai, bi, ci, di) in enumerate(zip(a.tolist(), b.tolist(), c.tolist(), d.tolist())):
+        r1, r2, c1, c2 = ai + bi, ci + di, ai + ci, bi + di
+        if r1 + r2 == 0:
+            flags[i] = 1
+        elif 0 in (r1, r2, c1, c2):
+            flags[i], p[i], nlp[i] = 2, 1.0, 0.0
+        else:
+            lo, hi = max(0, c1 - r2), min(r1, c1)
+            w = [math.comb(r1, lo) * math.comb(r2, c1 - lo)]
+            for x in range(lo, hi):                  # w_{x+1} = w_x (r1 - x)(c1 - x) / ((x + 1)(r2 - c1 + x + 1)), exactly
+                w.append(w[-1] * ((r1 - x) * (c1 - x)) // ((x + 1) * (r2 - c1 + x + 1)))
+            p[i], nlp[i] = _tail_ints(w, ai - lo, midp)
+    return p, nlp, flags
+
+
+def model_tests_host(case_n, case_het, case_hom, ctrl_n, ctrl_het, ctrl_hom, min_cell: int = 5):
+    """The numpy mirror of ldx_model_tests_dev: (chisq, p, neglog10_p float64 [m, 5], odds float64 [m], flags uint8 [m, 5]).
+    Every integer is exact in int64 and every fp64 operation is the kernel's, in its order: chisq, odds and the flags agree with
+    the device bit for bit; the tails are within the contract (logit_tail_host for 1 df)."""
+    R, r1, r2, S, s1, s2 = _int_cols("model_tests_host", (("case_n", case_n), ("case_het", case_het), ("case_hom", case_hom),
+                                                          ("ctrl_n", ctrl_n), ("ctrl_het", ctrl_het), ("ctrl_hom", ctrl_hom)))
+    _model_check("model_tests_host", R, r1, r2, S, s1, s2)
+    min_cell = _min_cell("model_tests_host", min_cell)
+    m = R.size
+    chisq, flags, odds = np.full((m, 5), np.nan), np.zeros((m, 5), dtype=np.uint8), np.full(m, np.nan)
+    flags[(R == 0) | (S == 0)] = 1
+    live = flags[:, 0] == 0
+    N, r0, s0 = R + S, R - r1 - r2, S - s1 - s2
+    n0, n1, n2 = r0 + s0, r1 + s1, r2 + s2
+    f64 = lambda x: x.astype(np.float64)  # noqa: E731
+
+    def table(t, T, a, b, c, d):
+        den = (a + b) * (c + d) * ((a + c) * (b + d))
+        ok = live & (den != 0)
+        det = a * d - b * c
+        with np.errstate(all="ignore"):
+            chisq[ok, t] = ((f64(T) * f64(det * det)) / f64(np.where(den != 0, den, 1)))[ok]
+        flags[live & (den == 0), t] = 2
+        return ok
+
+    a, c = r1 + 2 * r2, s1 + 2 * s2
+    b, d = 2 * R - a, 2 * S - c
+    ok = table(0, 2 * N, a, b, c, d)
+    with np.errstate(all="ignore"):
+        odds[ok] = (f64(a * d) / f64(b * c))[ok]
+    U = N * (r1 + 2 * r2) - R * (n1 + 2 * n2)
+    den = R * S * (N * (n1 + 4 * n2) - (n1 + 2 * n2) * (n1 + 2 * n2))
+    ok = live & (den != 0)
+    with np.errstate(all="ignore"):
+        chisq[ok, 1] = ((f64(N) * f64(U * U)) / f64(np.where(den != 0, den, 1)))[ok]
+    flags[live & (den == 0), 1] = 2
+    zero = (n0 == 0) | (n1 == 0) | (n2 == 0)
+    small = np.zeros(m, dtype=bool)
+    for o in (r0, r1, r2, s0, s1, s2):
+        small |= o < min_cell
+    flags[live & zero, 2] = 2
+    flags[live & ~zero & small, 2] = 3
+    ok = live & ~zero & ~small
+    total = np.zeros(m)
+    with np.errstate(all="ignore"):
+        for row, cells in ((R, (r0, r1, r2)), (S, (s0, s1, s2))):
+            for col, o in zip((n0, n1, n2), cells):
+                rc = row * col
+                dev = o * N - rc
+                total = total + f64(dev * dev) / f64(np.where(ok, N * rc, 1))
+    chisq[ok, 2] = total[ok]
+    table(3, N, r1 + r2, r0, s1 + s2, s0)
+    table(4, N, r2, r0 + r1, s2, s0 + s1)
+    p, nlp = np.full((m, 5), np.nan), np.full((m, 5), np.nan)
+    for t in (0, 1, 3, 4):
+        ok = flags[:, t] == 0
+        with np.errstate(all="ignore"):
+            p[ok, t], nlp[ok, t] = logit_tail_host(np.sqrt(chisq[ok, t]))
+    ok = flags[:, 2] == 0
+    p[ok, 2], nlp[ok, 2] = np.exp(-0.5 * chisq[ok, 2]), (0.5 * chisq[ok, 2]) / 2.302585092994046
+    return chisq, p, nlp, odds, flags
+
+
+def _count_cols(counts: torch.Tensor, g: int) -> list:
+    """The contiguous uint32 columns called, het, hom ALT of group g of a counts tensor [n_snps, n_groups, 4]."""
+    return [counts[:, g, k].contiguous() for k in range(3)]
+
+
+@dataclass
+class HardyResult:
+    """ld_hardy's result, per (SNP, group): ``counts`` int32 [n_snps, n_groups, 4] (called, het, hom ALT, 0), ``o_het`` = het / n
+    and ``e_het`` = 2 p q with p = (het + 2 hom) / (2 n) (float64, NaN where n = 0), ``p``, ``neglog10_p`` float64 and ``flags``
+    uint8 (QC_FLAGS) [n_snps, n_groups] -- on the panel's device; ``sizes``: the groups' individuals; ``labels``: their labels."""
+
+    counts: torch.Tensor
+    sizes: np.ndarray
+    labels: list
+    o_het: torch.Tensor
+    e_het: torch.Tensor
+    p: torch.Tensor
+    neglog10_p: torch.Tensor
+    flags: torch.Tensor
+
+
+def ld_hardy(panel: PackedPanel, groups=None, midp: bool = False, keep=None, missing: Optional[str] = None) -> HardyResult:
+    """Genotype counts and the exact Hardy-Weinberg test of every SNP within each group of individuals (PLINK --hardy; this
+    project's own definition: include/ldx.h, "genotype QC and table tests"): one geno_group_counts pass, then ld_hwe_from_counts'
+    launch on its n_snps x n_groups tuples.  ``groups``: as geno_group_counts (None: everybody).  A SNP that ``keep`` drops has
+    zero counts and flag 1."""
+    _qc_missing("ld_hardy", missing)
+    require_gpu()
+    _even_n_hap("ld_hardy", panel)
+    member, sizes, labels = _groups_member("ld_hardy", groups, panel.n_ind)
+    G = int(sizes.size)
+    counts = _group_counts(panel, _keep_dev(keep, panel.n_snps, panel.device), member, G)
+    flat = counts.view(-1, 4)
+    p, nlp, flags = _exact_launch("ldx_hwe_exact_dev", [flat[:, k].contiguous() for k in range(3)], midp)
+    n, het, hom = (flat[:, k].to(torch.float64) for k in range(3))
+    a = het + 2.0 * hom
+    shape = (panel.n_snps, G)
+    return HardyResult(counts, sizes, labels, (het / n).view(shape), ((a * (2.0 * n - a)) / (2.0 * n * n)).view(shape),
+                       p.view(shape), nlp.view(shape), flags.view(shape))
+
+
+def _case_groups(what: str, case, n_ind: int) -> np.ndarray:
+    """bool [2, n_ind]: the cases and the controls of a 0 / 1 / NaN vector (NaN: in neither)."""
+    v = case.cpu().numpy() if isinstance(case, torch.Tensor) else np.asarray(case)
+    v = v.astype(np.float64)
+    if v.shape != (n_ind,) or not np.isin(v[~np.isnan(v)], (0.0, 1.0)).all():
+        raise _lib.LdxError(f"{what}: case must be a vector [{n_ind}] of 0 (control), 1 (case) and NaN (left out)")
+    return np.stack([v == 1.0, v == 0.0])
+
+
+@dataclass
+class ModelResult:
+    """ld_model's result.  ``chisq``, ``p``, ``neglog10_p`` float64 [n_snps, 5] and ``flags`` uint8 [n_snps, 5] (MODEL_TESTS,
+    MODEL_FLAGS), ``odds`` float64 [n_snps] (allelic), ``fisher_p`` / ``fisher_neglog10_p`` / ``fisher_flags`` [n_snps]: Fisher's
+    exact test on the allele counts (None without ``fisher``), ``case_counts`` / ``ctrl_counts`` int32 [n_snps, 4] -- on the
+    panel's device; ``n_case``, ``n_ctrl``: the individuals of the two groups."""
+
+    chisq: torch.Tensor
+    p: torch.Tensor
+    neglog10_p: torch.Tensor
+    odds: torch.Tensor
+    flags: torch.Tensor
+    fisher_p: Optional[torch.Tensor]
+    fisher_neglog10_p: Optional[torch.Tensor]
+    fisher_flags: Optional[torch.Tensor]
+    case_counts: torch.Tensor
+    ctrl_counts: torch.Tensor
+    n_case: int
+    n_ctrl: int
+
+
+def allele_table(case_counts: torch.Tensor, ctrl_counts: torch.Tensor) -> list:
+    """The allelic 2 x 2 table [[a, b], [c, d]] of two counts tensors [n, 4]: ALT and REF alleles of the cases and of the
+    controls, four contiguous int32 tensors (uint32 words)."""
+    out = []
+    for t in (case_counts, ctrl_counts):
+        alt = t[:, 1] + 2 * t[:, 2]
+        out += [alt.contiguous(), (2 * t[:, 0] - alt).contiguous()]
+    return out
+
+
+def ld_model(panel: PackedPanel, case, midp: bool = False, min_cell: int = 5, fisher: bool = True, keep=None,
+             missing: Optional[str] = None) -> ModelResult:
+    """The single-SNP case/control table tests of ``plink --model`` and ``--assoc fisher`` (this project's own definition):
+    one geno_group_counts pass over cases and controls, ld_model_from_counts' launch on the counts and, with ``fisher``,
+    ld_fisher_from_counts' on the allele counts (``midp`` is its).  ``case``: 0 / 1 / NaN per individual, NaN = left out."""
+    _qc_missing("ld_model", missing)
+    require_gpu()
+    _even_n_hap("ld_model", panel)
+    groups = _case_groups("ld_model", case, panel.n_ind)
+    min_cell = _min_cell("ld_model", min_cell)
+    member, sizes, _ = _groups_member("ld_model", groups, panel.n_ind)
+    counts = _group_counts(panel, _keep_dev(keep, panel.n_snps, panel.device), member, 2)
+    cc, uc = counts[:, 0].contiguous(), counts[:, 1].contiguous()
+    outs = _model_launch(_count_cols(counts, 0) + _count_cols(counts, 1), min_cell)
+    fp = _exact_launch("ldx_fisher_exact_dev", allele_table(cc, uc), midp) if fisher else (None, None, None)
+    return ModelResult(*outs, *fp, cc, uc, int(sizes[0]), int(sizes[1]))
+
+
+@dataclass
+class MissingResult:
+    """ld_test_missing's result: ``f_miss_case`` / ``f_miss_ctrl`` float64 [n_snps], the missing-call rates of the two groups (NaN
+    for an empty group), ``p``, ``neglog10_p``, ``flags`` of Fisher's test on [[missing, called] cases, [missing, called]
+    controls], ``called`` int32 [n_snps, 2] -- on the panel's device; ``n_case``, ``n_ctrl``."""
+
+    f_miss_case: torch.Tensor
+    f_miss_ctrl: torch.Tensor
+    p: torch.Tensor
+    neglog10_p: torch.Tensor
+    flags: torch.Tensor
+    called: torch.Tensor
+    n_case: int
+    n_ctrl: int
+
+
+def ld_test_missing(panel: PackedPanel, case, midp: bool = False, missing: Optional[str] = None) -> MissingResult:
+    """Missingness by case/control status (PLINK --test-missing): per SNP Fisher's exact test on the called and missing
+    individuals of the cases and of the controls."""
+    _qc_missing("ld_test_missing", missing)
+    require_gpu()
+    _even_n_hap("ld_test_missing", panel)
+    member, sizes, _ = _groups_member("ld_test_missing", _case_groups("ld_test_missing", case, panel.n_ind), panel.n_ind)
+    counts = _group_counts(panel, None, member, 2)
+    called = counts[:, :, 0].contiguous()
+    nc, nu = int(sizes[0]), int(sizes[1])
+    cols = [(nc - called[:, 0]).contiguous(), called[:, 0].contiguous(), (nu - called[:, 1]).contiguous(), called[:, 1].contiguous()]
+    p, nlp, flags = _exact_launch("ldx_fisher_exact_dev", cols, midp)
+    with np.errstate(all="ignore"):
+        fc = cols[0].to(torch.float64) / float(nc) if nc else torch.full_like(p, float("nan"))
+        fu = cols[2].to(torch.float64) / float(nu) if nu else torch.full_like(p, float("nan"))
+    return MissingResult(fc, fu, p, nlp, flags, called, nc, nu)
+
+
+@dataclass
+class SampleQC:
+    """sample_qc's result, per individual over the kept SNPs: ``called``, ``het``, ``hom`` int64 [n_ind] (the integers
+    ldx_sample_planes_dev leaves in its tables), ``n_kept`` the kept SNPs, ``e_hom`` float64: the expected homozygous calls
+    sum_s called_is e_s, and ``f`` = (O_hom - E_hom) / (called - E_hom) with O_hom = called - het, the inbreeding coefficient of
+    ``plink --het`` (NaN where called = E_hom)."""
+
+    called: np.ndarray
+    het: np.ndarray
+    hom: np.ndarray
+    n_kept: int
+    e_hom: np.ndarray
+    f: np.ndarray
+
+    @property
+    def f_miss(self) -> np.ndarray:
+        """float64 [n_ind]: 1 - called / n_kept (NaN without a kept SNP)."""
+        with np.errstate(all="ignore"):
+            return 1.0 - self.called.astype(np.float64) / float(self.n_kept) if self.n_kept else np.full(self.called.size, np.nan)
+
+
+def het_weights(snp_counts) -> Tuple[np.ndarray, np.ndarray]:
+    """(q int32 [n_snps, 1], exps int64 [1]): the per-SNP expected homozygosity e_s = 1 - a (2n - a) / (n (2n - 1)), a = het +
+    2 hom over the n called (the unbiased estimate of PLINK --het; 0 where n = 0), as quantised weights of the genotype products
+    (geno_quantize's rule, on the host)."""
+    c = np.asarray(snp_counts).astype(np.int64) & 0xFFFFFFFF
+    n, a = c[:, 0], c[:, 1] + 2 * c[:, 2]
+    with np.errstate(all="ignore"):
+        e = np.where(n > 0, 1.0 - (a * (2 * n - a)).astype(np.float64) / np.where(n > 0, n * (2 * n - 1), 1).astype(np.float64), 0.0)
+    (q,), exps = geno_quantize(torch.from_numpy(e[:, None]), device="cpu")
+    return q.numpy(), exps.numpy()
+
+
+def _sample_f(called, het, y, exps) -> Tuple[np.ndarray, np.ndarray]:
+    e_hom = _scale_sums(np.asarray(y, dtype=np.int64).reshape(-1, 1), np.asarray(exps))[:, 0]
+    with np.errstate(all="ignore"):
+        f = ((called - het).astype(np.float64) - e_hom) / (called.astype(np.float64) - e_hom)
+    return e_hom, f
+
+
+def sample_qc(panel: PackedPanel, keep=None, missing: Optional[str] = None) -> SampleQC:
+    """Per individual the called, heterozygous and homozygous-ALT calls over the SNPs that pass ``keep`` (PLINK --missing's
+    sample file, --het): the tables of the individual-major stores (GenoOperator), not a recount; the expected homozygosity sum
+    is one forward product of the operator with het_weights as its ``wc`` column."""
+    _qc_missing("sample_qc", missing)
+    require_gpu()
+    op = GenoOperator(panel, keep)
+    n_ind = panel.n_ind
+    pad = (lib.ldx_sample_tables_bytes(n_ind) // 4 - 4) // 3    # the tables: [3][pad] counters, then the kept SNPs (16 bytes)
+    tot, n_kept = np.zeros((3, n_ind), dtype=np.int64), 0
+    for _, _, _, tables in op._stores:
+        t = tables.cpu().numpy().view(np.uint32).astype(np.int64)
+        tot += t[:3 * pad].reshape(3, pad)[:, :n_ind]
+        n_kept += int(t[3 * pad])
+    q, exps = het_weights(_snp_counts(panel, op._keep_d).cpu().numpy())
+    y = op.matmul_q(torch.zeros_like(torch.from_numpy(q)), torch.from_numpy(q)).cpu().numpy()
+    e_hom, f = _sample_f(tot[0], tot[1], y, exps)
+    return SampleQC(tot[0], tot[1], tot[2], n_kept, e_hom, f)
+
+
+def sample_qc_host(codes, keep=None) -> SampleQC:
+    """Host mirror of sample_qc on the allele codes: the same weights, the integer product of geno_matmul_host."""
+    g, c = geno_planes_host(codes, keep)
+    k = _keep_mask(keep, g.shape[0])
+    q, exps = het_weights(geno_counts_host(codes, keep))
+    y = geno_matmul_host(codes, np.zeros_like(q), q, keep)
+    called, het, hom = c.sum(axis=0), (g == 1).sum(axis=0), (g == 2).sum(axis=0)
+    e_hom, f = _sample_f(called, het, y, exps)
+    return SampleQC(called, het, hom, int(g.shape[0] if k is None else k.sum()), e_hom, f)
+
+
+def snp_qc_mask(panel: PackedPanel, maf_min: Optional[float] = None, geno_max: Optional[float] = None,
+                hwe_min: Optional[float] = None, hwe_group=None, midp: bool = False, missing: Optional[str] = None) -> torch.Tensor:
+    """The variant filters of PLINK --maf / --geno / --hwe as a device uint8 mask [n_snps] that every operator's ``keep=`` takes
+    as it stands.  Over all individuals: min(a, 2n - a) >= maf_min 2n with n > 0, and 1 - n / n_ind <= geno_max; over
+    ``hwe_group`` (a bool mask or index array over the individuals, e.g. the controls; None: all): the exact HWE p (``midp``:
+    its mid-p) >= hwe_min, a SNP without a call in the group failing."""
+    _qc_missing("snp_qc_mask", missing)
+    require_gpu()
+    _even_n_hap("snp_qc_mask", panel)
+    n_ind = panel.n_ind
+    groups = np.ones((2, n_ind), dtype=bool)
+    if hwe_group is not None:
+        groups[1] = False
+        groups[1, select_index(hwe_group, n_ind, "individual").astype(np.int64)] = True
+    member, _, _ = _groups_member("snp_qc_mask", groups, n_ind)
+    counts = _group_counts(panel, None, member, 2).to(torch.int64)
+    n, a = counts[:, 0, 0], counts[:, 0, 1] + 2 * counts[:, 0, 2]
+    ok = torch.ones(panel.n_snps, dtype=torch.bool, device=panel.device)
+    if maf_min is not None:
+        ok &= (n > 0) & (torch.minimum(a, 2 * n - a).to(torch.float64) >= float(maf_min) * (2 * n).to(torch.float64))
+    if geno_max is not None:
+        ok &= (n_ind - n).to(torch.float64) <= float(geno_max) * float(n_ind)
+    if hwe_min is not None:
+        p, _, flags = _exact_launch("ldx_hwe_exact_dev", [counts[:, 1, k].to(torch.int32).contiguous() for k in range(3)], midp)
+        ok &= (flags != 1) & (p >= float(hwe_min))
+    return ok.to(torch.uint8)
+
+
+def sample_qc_mask(panel: PackedPanel, mind_max: Optional[float] = None, het_sd: Optional[float] = None, keep=None) -> np.ndarray:
+    """The individual filters of PLINK --mind and of the usual heterozygosity check as a bool mask [n_ind] for
+    PackedPanel.select (through its haplotypes) and the drivers: 1 - called / kept SNPs <= mind_max, and |F - mean F| <= het_sd
+    standard deviations of F (mean and sample sd over the individuals with a finite F; one without fails)."""
+    qc = sample_qc(panel, keep)
+    ok = np.ones(qc.called.size, dtype=bool)
+    if mind_max is not None:
+        ok &= qc.f_miss <= float(mind_max)
+    if het_sd is not None:
+        fin = np.isfinite(qc.f)
+        mean, sd = (qc.f[fin].mean(), qc.f[fin].std(ddof=1)) if fin.sum() > 1 else (0.0, 0.0)
+        with np.errstate(all="ignore"):
+            ok &= fin & (np.abs(qc.f - mean) <= float(het_sd) * sd)
+    return ok
 
 
 # --------------------------------------------------------------------------- instrumentation
