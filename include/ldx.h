@@ -1386,6 +1386,106 @@ int ldx_model_tests_dev(size_t m, const uint32_t *case_n, const uint32_t *case_h
                         const uint32_t *ctrl_n, const uint32_t *ctrl_het, const uint32_t *ctrl_hom, uint32_t min_cell,
                         double *chisq, double *p, double *neglog10_p, double *odds, uint8_t *flags, void *stream);
 
+/* ---- epistasis scan: 3 x 3 x 2 genotype tables of SNP pairs in cases and controls, allelic and BOOST interaction tests -------
+ * This project's own definition (what PLINK --fast-epistasis and --fast-epistasis boost report), NOT validated against PLINK: no
+ * PLINK binary was available to compare with.
+ *
+ * Individuals, g in {0, 1, 2} and "called" are those of "pairwise-complete EM": a half-missing or second-ALT genotype is missing.
+ * The two groups, cases and controls, are given as two PANELS over the same SNPs (ops.py makes them with PackedPanel.select), each
+ * with its own even n_hap <= LDX_MAX_HAPS; an individual in neither panel is left out.
+ *
+ * THE TABLE of row i of SNP set I, row j of SNP set J and group c: n^c_ab, a, b in {0, 1, 2}, the individuals of group c called at
+ * both SNPs with g_i = a and g_j = b.  18 exact integers per pair in the order case n00 n01 n02 n10 ... n22, then control (index
+ * 9 c + 3 a + b with c = 0 for the cases).  The kernel forms, per group, the nine products of the three per-individual operands
+ * dosage g, het t and called q of each side (GG TT GT TG GQ QG TQ QT QQ) on the FP4 matrix pipe, every product and every sum exact, and
+ *     n11 = TT    n21 = (GT - TT) / 2    n12 = (TG - TT) / 2    n22 = (GG - n11 - 2 n12 - 2 n21) / 4
+ *     row margins r1 = TQ, r2 = (GQ - TQ) / 2, column margins c1 = QT, c2 = (QG - QT) / 2, the rest by subtraction.
+ *
+ * THE TESTS.  Each is a function of the 18 integers alone, in fp64 with every operation rounded once (-ffp-contract=off), in the
+ * order written here, and symmetric under swapping the two SNPs.  flags is the OR of the bits below.
+ * per group the 2 x 2 allele table  a = S, b = 2A - S, c = 2B - S, d = 4N - 2A - 2B + S  with N = sum n, A = sum a n_ab,
+ * B = sum b n_ab, S = sum ab n_ab (exact integers), L = ln((a d) / (b c)), V = (1/a + 1/d) + (1/b + 1/c).
+ *     dir = L_case - L_ctrl, the direction of the interaction, in both tests.
+ *     bit 2: a zero among the eight allele cells: dir is NaN (and so is the allelic chi-square).  No continuity correction.
+ * LDX_EPI_ALLELIC (the default of --fast-epistasis):  Z = dir / sqrt(V_case + V_ctrl), chisq = Z Z, 1 df.
+ * LDX_EPI_BOOST: the likelihood-ratio test of the saturated model against the log-linear model without the three-way term on the
+ * 3 x 3 x 2 table (BOOST's exact statistic, Wan et al. 2010), 4 df.  The table is fitted in the one of its two orientations (as
+ * given, or with the SNPs swapped: n^c_ab -> n^c_ba) whose 18 integers come first in lexicographic order; the statistic is thus a
+ * function of the unordered pair.  mu starts at 1 in all 18 cells.  A cycle of iterative proportional fitting scales, in this
+ * order, the margins SNP i x SNP j (s = mu^0_ab + mu^1_ab), SNP i x group (s = (mu^c_a0 + mu^c_a1) + mu^c_a2) and SNP j x group
+ * (s = (mu^c_0b + mu^c_1b) + mu^c_2b): f = observed margin / s, or 0 where s = 0, and every cell of the margin is multiplied by f.
+ * The iteration stops after the first cycle in which no cell moved by more than 2^-40 N_total (|mu after - mu before the cycle|),
+ * or after LDX_EPI_MAX_CYCLES cycles.
+ *     G2 = 2 sum over the cells with n > 0, in index order from 0, of n ln(n / mu);  chisq = G2 where G2 > 0, else 0.
+ *     bit 1: a group has no jointly called individual: NaN, no fit.
+ *     bit 4: the cycle cap was reached; the statistic is reported as it stands.
+ *     bit 8: one of the 21 two-way margins is 0: the cell is reported, the df are nominally 4, p is conservative.
+ * LDX_EPI_MAX_CYCLES is the smallest cap that no table without bit 8 among the test oracle's tuples (tests/ld_epistasis_exact.py)
+ * reaches: the slowest of them stops in its 55th cycle (a table of 44 individuals with six empty cells; the tables of 100 and
+ * more individuals stop within 24).  A table WITH bit 8 can crawl towards a boundary at the rate 1 / cycles: it is cut off here.
+ * Tails, from chisq alone: allelic ln p = the two-sided normal tail of sqrt(chisq), the function of "logistic association scan";
+ * boost ln p = -G2 / 2 + log1p(G2 / 2), the closed form of 4 df, so that neglog10_p stays finite where p is 0.
+ * Accuracy, against an exact oracle (rationals up to the logarithms, then 60 decimal digits; the IPF iterated until nothing moves
+ * above 1e-45), for every cell without bits 1, 2 (allelic) and 4: |chisq - exact| <= BOUND max(exact, 1), with BOUND =
+ * LDX_EPI_REL_BOUND_ALLELIC = 2^-46 and LDX_EPI_REL_BOUND_BOOST = 4.17e-12 (2^-37.8).  numpy repeats mu and the cycle count bit
+ * for bit (ops.epi_boost_host); the statistic itself goes through the device's own log.  Each bound is 8 x the worst error of the
+ * numpy mirror on the oracle's tuples (1.78e-15 and 5.22e-13, tests/test_epistasis_host.py measures them).  The boost bound is
+ * looser than the logistic scan's 2^-40 for a stated reason: the stop rule leaves mu within about 2^-40 N of the fit, and G2 is a
+ * sum of terms n ln(n / mu) of both signs, each up to N ln 2 in size, that cancels down to a statistic of order 1 -- the residue
+ * of the fit and the rounding of the terms do not shrink with it (the worst tuple has G2 = 1.17 at N = 3290).  Below 1 the
+ * bound is absolute for the same reason.
+ *
+ * CELLS are float32 chi-squares.  A NaN cell is never a hit.  A cell depends on its 18 integers only: not on the tile, the path
+ * (shortcut or nine-set loop), the other SNPs of the call, the phase or the order of the individuals; swapping the sides gives
+ * the transpose bit for bit.
+ *
+ * ldx_epi_side: one SNP set as its two group panels: the tiled planes (ldx_plane_bytes of the group's n_hap) and the group's
+ * per-SNP table cnt uint32 [n_snps][4] = {called, het, hom ALT, 0} (ldx_geno_snp_counts_dev of the group panel), 16-byte aligned.
+ * A 128 x 128 tile none of whose 256 SNPs has an uncalled individual of a group (called = n_hap / 2) forms four of the nine sets
+ * for that group and reads the margins from cnt; the integers are the same either way.
+ * ldx_epi_counts_dev: counts[(s n_i + i) ld + j], s = 0 .. 17, uint32: what the loops produced, before any float.
+ * ldx_epi_rect_dev: dense float32 chisq [n_i][ld]; dir (float32) and flags (uint8) in the same layout where not null.
+ * ldx_epi_hits_dev: one ldx_hit {query = i, oppos = j, r_square = chisq, d_prime = dir} for every pair whose cell is >= bound: ONE
+ * float32 compare, bound > 0.  Slots, batches, *n_hits and overflow are ldx_ld_rect_hits_dev's; ldx_area_finish_ex_dev finishes.
+ * With n_tot, n_sig and best (all three or none; the caller zeroes them, [n_i] each) it also fills the per-SNP summary of the rows
+ * of I: n_tot[x] the valid (non-NaN) tests of row x, n_sig[x] those with chisq >= bound_sig (> 0), both uint32 integer atomics,
+ * and best[x] a uint64 atomicMax of (float bits of chisq) << 32 | (0xFFFFFFFF - partner): the largest chi-square and, on ties, the
+ * smallest partner index, whatever the order of arrival; best[x] is 0 where n_tot[x] is.  The summary does not depend on hit_cap.
+ * self = 1 (side_j must be side_i's panels): only the tiles tj <= ti are walked and only the pairs i > j tested, once each; the
+ * summary credits both SNPs, each with the other as its partner.
+ * ldx_epi_from_counts_dev: the epilogue alone on m tuples of 18 uint32 (tuples[18 k + s]): chisq (double), chisq32 (the cell), dir,
+ * ln_p (double [m]), flags (uint8 [m]), mu (double [m][18], the fitted table in the tuple's orientation; NaN unless boost without
+ * bit 1) and cycles (uint32 [m]); every output may be null.  A tuple with a group total above LDX_MAX_HAPS / 2 is no table of this
+ * library: this entry does not read device memory before the launch, so the tuple carries flag 16 and NaN, and the host layer
+ * (ops.ld_epistasis_from_counts), which holds the integers, refuses it as LDX_E_ARG before the call.
+ * Work: a workgroup of 256 threads per tile, one per CU; four passes per tile, each the K loop over the cases' planes, then over
+ * the controls', with the epilogue staged through LDS; plain vector stores; no floating-point atomics.
+ * A null pointer (the optional outputs excepted), a test other than the two, n_i, n_j or a group's n_hap 0, an odd n_hap, ld below
+ * n_j, a cnt that is not 16-byte aligned, bound or bound_sig not > 0, self without identical sides, m = 0 = LDX_E_ARG; a group's
+ * n_hap > LDX_MAX_HAPS, a bit plane of 4 GiB or more, 2^31 or more tiles or workgroups = LDX_E_UNSUPPORTED; all checked before
+ * any HIP call. */
+#define LDX_EPI_ALLELIC 0
+#define LDX_EPI_BOOST 1
+#define LDX_EPI_MAX_CYCLES 55u
+#define LDX_EPI_REL_BOUND_ALLELIC 0x1p-46
+#define LDX_EPI_REL_BOUND_BOOST 4.17e-12
+typedef struct ldx_epi_side {
+    const void *alt_case, *ref_case;
+    const uint32_t *cnt_case;
+    const void *alt_ctrl, *ref_ctrl;
+    const uint32_t *cnt_ctrl;
+    uint32_t n_snps;
+} ldx_epi_side;
+int ldx_epi_counts_dev(const ldx_epi_side *side_i, const ldx_epi_side *side_j, uint32_t n_hap_case, uint32_t n_hap_ctrl,
+                       uint32_t *counts, size_t ld, void *stream);
+int ldx_epi_rect_dev(const ldx_epi_side *side_i, const ldx_epi_side *side_j, uint32_t n_hap_case, uint32_t n_hap_ctrl, int test,
+                     float *chisq, float *dir, uint8_t *flags, size_t ld, void *stream);
+int ldx_epi_hits_dev(const ldx_epi_side *side_i, const ldx_epi_side *side_j, uint32_t n_hap_case, uint32_t n_hap_ctrl, int test,
+                     int self, float bound, ldx_hit *hits, uint64_t hit_cap, uint64_t *n_hits, float bound_sig, uint32_t *n_tot,
+                     uint32_t *n_sig, uint64_t *best, void *stream);
+int ldx_epi_from_counts_dev(size_t m, int test, const uint32_t *tuples, double *chisq, float *chisq32, double *dir, double *ln_p,
+                            uint8_t *flags, double *mu, uint32_t *cycles, void *stream);
+
 /* ---- synthetic panels: deterministic, identical on host and device ------ */
 /* codes int8 [n_snps][ld_codes] receive global SNPs [snp_offset, snp_offset + n_snps) (a rank's
  * shard).  thresholds: per-SNP ALT probability * 2^64 (computed on the host, see

@@ -35,6 +35,9 @@ from .ops import (MODEL_FLAGS, MODEL_TESTS, QC_FLAGS, HardyResult, MissingResult
                   fisher_exact_host, geno_group_counts, geno_group_counts_host, hwe_exact_host, ld_fisher_from_counts, ld_hardy,
                   ld_hwe_from_counts, ld_model, ld_model_from_counts, ld_test_missing, model_tests_host, sample_qc,
                   sample_qc_host, sample_qc_mask, snp_qc_mask)
+from .ops import (EPI_DF, EPI_FLAGS, EPI_TESTS, EpiCells, EpiHits, EpiResult, EpiSummary, epi_allelic_host,  # noqa: F401
+                  epi_boost_host, epi_chisq_bound, epi_counts_host, epi_tail_host, ld_epistasis, ld_epistasis_counts,
+                  ld_epistasis_from_counts, ld_epistasis_hits)
 from .panel import PackedPanel, encode_codes, select_index  # noqa: F401
 from . import plink  # noqa: F401
 from .plink import BedFile, bed_codes_host, codes_bed_host, read_covar, read_pheno, write_bfile  # noqa: F401
@@ -57,4 +60,7 @@ __all__ = ["PackedPanel", "encode_codes", "select_index", "ld_triangle", "ld_are
            "hwe_exact_host", "fisher_exact_host", "model_tests_host", "ld_hardy", "HardyResult", "ld_model", "ModelResult",
            "ld_test_missing", "MissingResult", "sample_qc", "sample_qc_host", "SampleQC", "snp_qc_mask", "sample_qc_mask",
            "QC_FLAGS", "MODEL_TESTS", "MODEL_FLAGS",
+           "ld_epistasis", "ld_epistasis_hits", "ld_epistasis_counts", "ld_epistasis_from_counts", "EpiResult", "EpiHits",
+           "EpiSummary", "EpiCells", "epi_counts_host", "epi_allelic_host", "epi_boost_host", "epi_tail_host", "epi_chisq_bound",
+           "EPI_TESTS", "EPI_DF", "EPI_FLAGS",
            "version", "plink", "BedFile", "bed_codes_host", "codes_bed_host", "write_bfile", "read_pheno", "read_covar"]

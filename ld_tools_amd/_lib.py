@@ -43,6 +43,9 @@ LOGIT_MAX_ITER = 30                      # LDX_LOGIT_MAX_ITER
 FIRTH_MAX_ITER = 200                     # LDX_FIRTH_MAX_ITER
 QC_MAX_GROUPS = 32                       # LDX_QC_MAX_GROUPS
 QC_MAX_N = 65536                         # LDX_QC_MAX_N
+EPI_TESTS = {"allelic": 0, "boost": 1}   # LDX_EPI_ALLELIC / LDX_EPI_BOOST
+EPI_MAX_CYCLES = 55                      # LDX_EPI_MAX_CYCLES
+EPI_REL_BOUND = {"allelic": 2.0 ** -46, "boost": 4.17e-12}   # LDX_EPI_REL_BOUND_ALLELIC / _BOOST
 FLAG_DPRIME_INT0 = 1
 FLAG_RSQ_INT0 = 2
 MEASURES = {"r_square": 0, "d_prime": 1}
@@ -228,6 +231,10 @@ SIGNATURES = {
     "ldx_hwe_exact_dev": (_int, [_sz, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp]),
     "ldx_fisher_exact_dev": (_int, [_sz, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp]),
     "ldx_model_tests_dev": (_int, [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ldx_epi_counts_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _sz, _vp]),
+    "ldx_epi_rect_dev": (_int, [_vp, _vp, _u32, _u32, _int, _vp, _vp, _vp, _sz, _vp]),
+    "ldx_epi_hits_dev": (_int, [_vp, _vp, _u32, _u32, _int, _int, C.c_float, _vp, _u64, _vp, C.c_float, _vp, _vp, _vp, _vp]),
+    "ldx_epi_from_counts_dev": (_int, [_sz, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ldx_ld_select_workspace_bytes": (_sz, [_u32]),
     "ldx_ld_select_dev": (_int, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ldx_set_area_path": (_int, [_int]),
@@ -250,6 +257,13 @@ class GabrielParams(C.Structure):
 
     _fields_ = [("cand_cut", _u32), ("strong_hi", _u32), ("recomb_hi", _u32), ("cut", _u32 * 4), ("max_span", _i64 * 4),
                 ("min_informative", _u32 * 4), ("frac_num", _u32), ("frac_den", _u32)]
+
+
+class EpiSide(C.Structure):
+    """ldx_epi_side of include/ldx.h ("epistasis scan")."""
+
+    _fields_ = [("alt_case", _vp), ("ref_case", _vp), ("cnt_case", _vp), ("alt_ctrl", _vp), ("ref_ctrl", _vp), ("cnt_ctrl", _vp),
+                ("n_snps", _u32)]
 
 
 def check(rc: int, what: str = "") -> None:

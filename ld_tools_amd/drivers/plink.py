@@ -687,6 +687,39 @@ def bfile_model(src, pheno=None, out: Optional[str] = None, pheno_name: Optional
     return variants, res
 
 
+def bfile_epistasis(src, pheno=None, out: Optional[str] = None, test: str = "boost", p: float = 1e-4, p_sig: float = 1e-2,
+                    set_i: Optional[Sequence[str]] = None, set_j: Optional[Sequence[str]] = None,
+                    pheno_name: Optional[str] = None, hit_capacity: Optional[int] = None, **load):
+    """drivers/epistasis.py's ``epistasis_table`` from a fileset (PLINK --fast-epistasis, ``test`` "allelic", and
+    --fast-epistasis boost, "boost"): the SNP x SNP interaction test of every pair of variants once, or, with the variant ID
+    lists ``set_i`` and ``set_j`` (one alone is tested against all variants), of every variant of the first set against every
+    variant of the second.  ``pheno``: a case/control phenotype table (case_control: 1 / 2 or 0 / 1; None: the ``.fam``'s
+    column); a quantitative trait is refused -- it belongs to bfile_glm.  ``p``: the pairs written; ``p_sig``: the summary's
+    threshold.  ``out``: a prefix to write ``.epi.cc`` and ``.epi.cc.summary`` under.  Returns the EpiTable."""
+    from .epistasis import epistasis_table, write_epi_cc, write_epi_summary
+
+    bf = _loaded(src, **load)
+    case = _case_vector("bfile_epistasis", bf, pheno, pheno_name)
+    if set_i is None and set_j is None:
+        table = epistasis_table(bf.panel, case, bf.chrom, bf.ids, test=test, p=p, p_sig=p_sig, hit_capacity=hit_capacity)
+    else:
+        sides = []
+        for names in (set_i, set_j):
+            if names is None:
+                sides.append((bf.panel, list(bf.chrom), list(bf.ids)))
+                continue
+            if not _is_names(names, False):
+                raise LdxError("bfile_epistasis: set_i and set_j are non-empty lists of variant IDs")
+            k = _by_name(list(names), bf.ids, "variant")
+            sides.append((bf.panel.select(snps=k), [bf.chrom[x] for x in k], [bf.ids[x] for x in k]))
+        (pi, ci, ii), (pj, cj, ij) = sides
+        table = epistasis_table(pi, case, ci, ii, pj, cj, ij, test=test, p=p, p_sig=p_sig, hit_capacity=hit_capacity)
+    if out is not None:
+        write_epi_cc(out + ".epi.cc", table)
+        write_epi_summary(out + ".epi.cc.summary", table)
+    return table
+
+
 @dataclass
 class QcMasks:
     """bfile_qc's result: ``snps`` uint8 device tensor [variants] (an operator's ``keep=``), ``individuals`` bool [individuals]."""
@@ -883,6 +916,15 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--pheno", default=None, help="case/control phenotype table: HWE is tested on its controls")
     p.add_argument("--pheno-name", default=None, help="its column (default: the first)")
     p.add_argument("--midp", action="store_true")
+    p = common("epistasis", "SNP x SNP interaction scan of a case/control trait (.epi.cc, .epi.cc.summary)")
+    p.add_argument("--pheno", default=None, help="case/control phenotype table, 1 / 2 or 0 / 1 (default: the .fam's column)")
+    p.add_argument("--pheno-name", default=None, help="its column (default: the first)")
+    p.add_argument("--test", choices=("boost", "allelic"), default="boost",
+                   help="boost: the 4-df likelihood-ratio test (--fast-epistasis boost); allelic: the 1-df test of --fast-epistasis")
+    p.add_argument("--epi1", type=float, default=1e-4, help="write the pairs with p at or below this")
+    p.add_argument("--epi2", type=float, default=1e-2, help="the summary's threshold")
+    p.add_argument("--set-i", default=None, help="file of variant IDs: the first set of a set-by-set scan")
+    p.add_argument("--set-j", default=None, help="file of variant IDs: the second set")
     common("make-bed", "write the selected variants and individuals as a new fileset")
     return ap
 
@@ -912,6 +954,11 @@ def main(argv=None) -> int:
     elif a.command == "model":
         variants, _ = bfile_model(bf, a.pheno, out=a.out, pheno_name=a.pheno_name, midp=a.midp, min_cell=a.cell)
         print(len(variants), "variants ->", a.out + ".model", a.out + ".assoc.fisher")
+    elif a.command == "epistasis":
+        table = bfile_epistasis(bf, a.pheno, out=a.out, test=a.test, p=a.epi1, p_sig=a.epi2, pheno_name=a.pheno_name,
+                                set_i=None if a.set_i is None else _read_names(a.set_i, 1),
+                                set_j=None if a.set_j is None else _read_names(a.set_j, 1))
+        print(len(table.result), "pairs ->", a.out + ".epi.cc", a.out + ".epi.cc.summary")
     elif a.command == "qc":
         masks = bfile_qc(bf, out=a.out, geno=a.geno, maf=a.maf, hwe=a.hwe, mind=a.mind, pheno=a.pheno, pheno_name=a.pheno_name,
                          midp=a.midp)

@@ -5203,6 +5203,421 @@ def sample_qc_mask(panel: PackedPanel, mind_max: Optional[float] = None, het_sd:
     return ok
 
 
+# --------------------------------------------------------------------------- epistasis scan (include/ldx.h, "epistasis scan")
+EPI_TESTS = tuple(_lib.EPI_TESTS)                  # "allelic", "boost"
+EPI_DF = {"allelic": 1, "boost": 4}
+EPI_FLAGS = {1: "a group has no jointly called individual", 2: "a zero among the eight allele cells (dir is NaN)",
+             4: "the cycle cap was reached", 8: "a two-way margin is 0", 16: "a group total above LDX_MAX_HAPS / 2"}
+_EPI_TR = np.array([(k // 9) * 9 + (k % 3) * 3 + (k % 9) // 3 for k in range(18)])   # the table with the SNPs swapped
+
+
+def _epi_test(what: str, test) -> int:
+    if test not in _lib.EPI_TESTS:
+        raise _lib.LdxError(f"{what}: test must be one of {EPI_TESTS}, got {test!r}")
+    return _lib.EPI_TESTS[test]
+
+
+def _epi_missing(what: str, missing) -> None:
+    if missing is not None and not (isinstance(missing, str) and missing == "pairwise"):
+        raise _lib.LdxError(f'{what}: the scan is pairwise-complete; missing must be None or "pairwise", got {missing!r}')
+
+
+def _epi_tuples(what: str, counts) -> np.ndarray:
+    """int64 [18, ...] from the counts argument of the epilogue functions."""
+    k = counts.cpu().numpy() if hasattr(counts, "cpu") else np.asarray(counts)
+    if k.ndim < 1 or k.shape[0] != 18 or k.dtype.kind not in "iu":
+        raise _lib.LdxError(f"{what}: counts must be an integer array [18, ...], got {k.dtype} with shape {k.shape}")
+    k = k.astype(np.int64)
+    if k.size and int(k.min()) < 0:
+        raise _lib.LdxError(f"{what}: counts must not be negative")
+    return k
+
+
+def epi_counts_host(codes_i, codes_j, case) -> np.ndarray:
+    """Host mirror of ld_epistasis_counts on the allele codes: int64 [18, n_i, n_j], the 3 x 3 genotype table of every pair in the
+    cases (planes 0 .. 8, 3 a + b) and in the controls (9 .. 17) over the individuals called at both SNPs (both codes of
+    haplotypes 2k and 2k + 1 in {0, 1}).  float64 GEMMs of 0 / 1 matrices: exact."""
+    ci, cj = np.asarray(codes_i), np.asarray(codes_j)
+    if ci.ndim != 2 or cj.ndim != 2 or ci.shape[1] != cj.shape[1] or ci.shape[1] % 2:
+        raise _lib.LdxError(f"epi_counts_host: two code matrices over the same even number of haplotypes needed, got shapes "
+                            f"{ci.shape} and {cj.shape}")
+    groups = _case_groups("epi_counts_host", case, ci.shape[1] // 2)
+
+    def planes(c, member):
+        ok = (c >= 0) & (c <= 1)
+        q = ok[:, 0::2] & ok[:, 1::2] & member[None, :]
+        g = (c[:, 0::2] == 1).astype(np.int64) + (c[:, 1::2] == 1).astype(np.int64)
+        return [((g == a) & q).astype(np.float64) for a in range(3)]
+
+    out = []
+    for member in groups:
+        pi, pj = planes(ci, member), planes(cj, member)
+        out += [pi[a] @ pj[b].T for a in range(3) for b in range(3)]
+    return np.stack(out).astype(np.int64)
+
+
+def _epi_allele(k: np.ndarray):
+    """(L, V, ok) of one group's nine planes [9, ...]: the log odds ratio of the 2 x 2 allele table and its variance."""
+    w = np.arange(3)
+    n = k.reshape(3, 3, *k.shape[1:])
+    N = n.sum(axis=(0, 1))
+    A = np.tensordot(w, n.sum(axis=1), 1)
+    B = np.tensordot(w, n.sum(axis=0), 1)
+    S = np.tensordot(np.outer(w, w).reshape(-1), k, 1)
+    a, b, c, d = S, 2 * A - S, 2 * B - S, 4 * N - 2 * A - 2 * B + S
+    ok = (a != 0) & (b != 0) & (c != 0) & (d != 0)
+    fa, fb, fc, fd = (np.where(ok, x, 1).astype(np.float64) for x in (a, b, c, d))
+    L = np.log((fa * fd) / (fb * fc))
+    V = (1.0 / fa + 1.0 / fd) + (1.0 / fb + 1.0 / fc)
+    return L, V, ok
+
+
+def epi_allelic_host(counts) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Host mirror of the allelic test (include/ldx.h, LDX_EPI_ALLELIC) on counts [18, ...] in numpy fp64, every operation
+    rounded once in the kernel's order: (chisq float64, dir float64, flags uint8), NaN in both under flag 2."""
+    k = _epi_tuples("epi_allelic_host", counts)
+    (L1, V1, ok1), (L0, V0, ok0) = _epi_allele(k[:9]), _epi_allele(k[9:])
+    ok = ok1 & ok0
+    with np.errstate(all="ignore"):
+        d = np.where(ok, L1 - L0, np.nan)
+        z = d / np.sqrt(V1 + V0)
+    return z * z, d, np.where(ok, 0, 2).astype(np.uint8)
+
+
+def epi_boost_host(counts, max_cycles: int = _lib.EPI_MAX_CYCLES) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """Host mirror of the BOOST test (include/ldx.h, LDX_EPI_BOOST) on counts [18, ...]: ``(mu float64 [18, ...], cycles int64,
+    chisq float64, flags uint8)``.  The iterative proportional fitting uses + x / in the kernel's order on the kernel's
+    orientation of the table, so mu and cycles are the device's bit for bit; chisq goes through numpy's log."""
+    k = _epi_tuples("epi_boost_host", counts)
+    shape = k.shape[1:]
+    k = k.reshape(18, -1)
+    m = k.shape[1]
+    t = k[_EPI_TR]
+    differ = t != k
+    first = np.argmax(differ, axis=0)
+    cols = np.arange(m)
+    swap = differ.any(axis=0) & (t[first, cols] < k[first, cols])
+    o = np.where(swap[None, :], t, k).astype(np.float64)
+    m_ab = o[:9] + o[9:]
+    m_ac = np.stack([[(o[9 * g + 3 * x] + o[9 * g + 3 * x + 1]) + o[9 * g + 3 * x + 2] for x in range(3)] for g in range(2)])
+    m_bc = np.stack([[(o[9 * g + x] + o[9 * g + 3 + x]) + o[9 * g + 6 + x] for x in range(3)] for g in range(2)])
+    n_grp = (m_ac[:, 0] + m_ac[:, 1]) + m_ac[:, 2]
+    _, _, flags2 = epi_allelic_host(k)
+    flags = flags2.astype(np.uint8)
+    empty = (n_grp[0] == 0.0) | (n_grp[1] == 0.0)
+    flags = flags | np.where(empty, 1, 0).astype(np.uint8)
+    zero = (m_ab == 0.0).any(axis=0) | (m_ac == 0.0).any(axis=(0, 1)) | (m_bc == 0.0).any(axis=(0, 1))
+    flags = flags | np.where(zero & ~empty, 8, 0).astype(np.uint8)
+    tol = 2.0 ** -40 * (n_grp[0] + n_grp[1])
+    mu = np.ones((18, m))
+    cycles = np.zeros(m, dtype=np.int64)
+    conv = empty.copy()
+
+    def scale(v, rows, margin):
+        s = v[rows[0]] + v[rows[1]] if len(rows) == 2 else (v[rows[0]] + v[rows[1]]) + v[rows[2]]
+        nz = s != 0.0
+        f = np.where(nz, margin / np.where(nz, s, 1.0), 0.0)
+        for r in rows:
+            v[r] = v[r] * f
+
+    for _ in range(int(max_cycles)):
+        act = np.nonzero(~conv)[0]
+        if not act.size:
+            break
+        v = mu[:, act]
+        old = v.copy()
+        for c in range(9):
+            scale(v, (c, 9 + c), m_ab[c, act])
+        for g in range(2):
+            for x in range(3):
+                scale(v, (9 * g + 3 * x, 9 * g + 3 * x + 1, 9 * g + 3 * x + 2), m_ac[g, x, act])
+        for g in range(2):
+            for x in range(3):
+                scale(v, (9 * g + x, 9 * g + 3 + x, 9 * g + 6 + x), m_bc[g, x, act])
+        mu[:, act] = v
+        cycles[act] += 1
+        conv[act] = np.abs(v - old).max(axis=0) <= tol[act]
+    flags = flags | np.where(~conv, 4, 0).astype(np.uint8)
+    acc = np.zeros(m)
+    with np.errstate(all="ignore"):
+        for c in range(18):
+            pos = o[c] > 0.0
+            acc = acc + np.where(pos, o[c] * np.log(np.where(pos, o[c], 1.0) / np.where(pos, mu[c], 1.0)), 0.0)
+    g2 = 2.0 * acc
+    chisq = np.where(empty, np.nan, np.where(g2 > 0.0, g2, 0.0))
+    mu = np.where(swap[None, :], mu[_EPI_TR], mu)
+    mu[:, empty] = np.nan
+    return mu.reshape(18, *shape), cycles.reshape(shape), chisq.reshape(shape), flags.reshape(shape)
+
+
+def epi_tail_host(chisq, test: str = "boost") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``(ln_p, p, neglog10_p)`` of a chi-square of ``test``: 1 df through logit_tail_host(sqrt chisq), 4 df in the closed form
+    ln p = -x + log1p(x), x = chisq / 2 (include/ldx.h, "epistasis scan").  NaN stays NaN."""
+    _epi_test("epi_tail_host", test)
+    x = np.asarray(chisq, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        if test == "allelic":
+            _, nlp = logit_tail_host(np.sqrt(x))
+            ln_p = -(nlp * 2.302585092994046)
+        else:
+            h = 0.5 * x
+            ln_p = -h + np.log1p(h)
+        ln_p = np.where(np.isnan(x), np.nan, ln_p)
+        return ln_p, np.exp(ln_p), -ln_p / 2.302585092994046
+
+
+def epi_chisq_bound(p: float, test: str = "boost") -> np.float32:
+    """The float32 chi-square bound of a p threshold: the smallest float32 b > 0 with p(b) <= ``p`` under epi_tail_host, found
+    once on the host by bisection -- the scan then keeps a cell by ONE float32 compare, chisq >= b."""
+    _epi_test("epi_chisq_bound", test)
+    if not 0.0 < float(p) < 1.0:
+        raise _lib.LdxError(f"epi_chisq_bound: p must lie in (0, 1), got {p!r}")
+    target = math.log(float(p))
+    lo, hi = 0.0, 1.0
+    while float(epi_tail_host(hi, test)[0]) > target:
+        lo, hi = hi, 2.0 * hi
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if float(epi_tail_host(mid, test)[0]) > target:
+            lo = mid
+        else:
+            hi = mid
+    b = np.float32(hi)
+    while float(epi_tail_host(float(b), test)[0]) > target:
+        b = np.nextafter(b, np.float32(np.inf))
+    return b
+
+
+def _epi_tail_dev(chisq: torch.Tensor, test: str) -> torch.Tensor:
+    """ln p of a float chi-square tensor, float64 on its device (epi_tail_host's formulas)."""
+    x = chisq.to(torch.float64)
+    if test == "allelic":
+        t = torch.sqrt(x) * 0.7071067811865476
+        near = torch.log(torch.special.erfc(t))
+        far = torch.log(torch.special.erfcx(torch.clamp(t, min=5.0))) - t * t
+        return torch.where(t < 5.0, near, far)
+    h = 0.5 * x
+    return -h + torch.log1p(h)
+
+
+@dataclass
+class EpiResult:
+    """ld_epistasis' matrices on the device: ``chisq`` and ``dir`` float32 [n_i, n_j], ``flags`` uint8 [n_i, n_j] (EPI_FLAGS, the
+    OR of the bits); ``p`` / ``neglog10_p`` are computed from ``chisq`` when asked for (float64, epi_tail_host's formulas)."""
+
+    chisq: torch.Tensor
+    dir: torch.Tensor
+    flags: torch.Tensor
+    test: str
+    n_case: int
+    n_ctrl: int
+
+    @property
+    def df(self) -> int:
+        return EPI_DF[self.test]
+
+    @property
+    def ln_p(self) -> torch.Tensor:
+        return _epi_tail_dev(self.chisq, self.test)
+
+    @property
+    def p(self) -> torch.Tensor:
+        return torch.exp(self.ln_p)
+
+    @property
+    def neglog10_p(self) -> torch.Tensor:
+        return -self.ln_p / 2.302585092994046
+
+
+@dataclass
+class EpiSummary:
+    """The per-SNP summary of ld_epistasis_hits over the rows of panel I, on the device: ``n_tot`` the valid tests of the SNP,
+    ``n_sig`` those with chisq >= ``bound_sig``, ``best_chisq`` (float32, NaN where n_tot is 0) the largest chi-square and
+    ``best_partner`` (int64, -1 where n_tot is 0) its partner, the smallest index on ties."""
+
+    n_sig: torch.Tensor
+    n_tot: torch.Tensor
+    best_chisq: torch.Tensor
+    best_partner: torch.Tensor
+    bound_sig: np.float32
+
+
+@dataclass
+class EpiHits:
+    """The pairs of an epistasis scan at or above a chi-square bound (ld_epistasis_hits) as ld_rect_hits' CSR over the rows of
+    panel I: ``hits`` int32 [m, 4] = i, j, chisq bits, dir bits, sorted by (i, j).  The self scan holds every pair once, i > j."""
+
+    offsets: torch.Tensor
+    hits: torch.Tensor
+    n_i: int
+    n_j: int
+    bound: np.float32
+    test: str
+    self_scan: bool
+    summary: EpiSummary
+
+    @property
+    def j(self) -> torch.Tensor:
+        return self.hits[:, 1]
+
+    @property
+    def chisq(self) -> torch.Tensor:
+        return self.hits[:, 2].view(torch.float32)
+
+    @property
+    def dir(self) -> torch.Tensor:
+        return self.hits[:, 3].view(torch.float32)
+
+    def __len__(self) -> int:
+        return int(self.hits.shape[0])
+
+    def pairs(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """(i int64, j int64, chisq float32, dir float32) on the host, sorted by (i, j)."""
+        h = self.hits.cpu().numpy()
+        return (h[:, 0].astype(np.int64), h[:, 1].astype(np.int64), np.ascontiguousarray(h[:, 2]).view(np.float32),
+                np.ascontiguousarray(h[:, 3]).view(np.float32))
+
+
+class _EpiSide:
+    """One SNP set as the scan takes it (ldx_epi_side): the cases' and the controls' panels, made once with PackedPanel.select,
+    and their per-SNP count tables.  Holds the tensors alive."""
+
+    def __init__(self, what: str, panel: PackedPanel, groups: np.ndarray):
+        self.panels, self.counts = [], []
+        for member in groups:
+            ind = np.nonzero(member)[0].astype(np.int64)
+            sub = panel.select(haplotypes=np.stack([2 * ind, 2 * ind + 1], axis=1).reshape(-1))
+            self.panels.append(sub)
+            self.counts.append(_snp_counts(sub, None))
+        (pc, pu), (cc, cu) = self.panels, self.counts
+        self.struct = _lib.EpiSide(pc.alt.data_ptr(), pc.ref.data_ptr(), cc.data_ptr(), pu.alt.data_ptr(), pu.ref.data_ptr(),
+                                   cu.data_ptr(), panel.n_snps)
+
+    @property
+    def ref(self):
+        return ctypes.byref(self.struct)
+
+
+def _epi_sides(what: str, panel: PackedPanel, case, panel_j: Optional[PackedPanel], missing):
+    """The scan operators' argument rules, checked before anything touches the device, and the two sides: (side_i, side_j,
+    n_hap_case, n_hap_ctrl); side_j is side_i where ``panel_j`` is None."""
+    _epi_missing(what, missing)
+    pj = _rect_panels(what, panel, panel_j, True)
+    groups = _case_groups(what, case, panel.n_ind)
+    sizes = groups.sum(axis=1)
+    if not sizes.all():
+        raise _lib.LdxError(f"{what}: {int(sizes[0])} cases and {int(sizes[1])} controls: both groups must hold an individual")
+    require_gpu()
+    side_i = _EpiSide(what, panel, groups)
+    side_j = side_i if panel_j is None else _EpiSide(what, pj, groups)
+    return side_i, side_j, 2 * int(sizes[0]), 2 * int(sizes[1])
+
+
+def ld_epistasis(panel: PackedPanel, case, panel_j: Optional[PackedPanel] = None, test: str = "boost",
+                 missing: Optional[str] = None) -> EpiResult:
+    """The SNP x SNP interaction test of every SNP of ``panel`` against every SNP of ``panel_j`` (None: ``panel`` itself, the full
+    square) in a case/control sample: ``test`` "allelic" (plink --fast-epistasis, 1 df) or "boost" (--fast-epistasis boost, the
+    likelihood-ratio test of BOOST, 4 df) on the pair's 3 x 3 x 2 genotype table over the individuals called at both SNPs
+    (include/ldx.h, "epistasis scan"; ldx_epi_rect_dev; this project's own definition).  ``case``: ld_model's argument, 0 / 1 /
+    NaN per individual, NaN = left out.  ``missing``: None or "pairwise", the same thing: the scan is always pairwise-complete."""
+    code = _epi_test("ld_epistasis", test)
+    side_i, side_j, hc, hu = _epi_sides("ld_epistasis", panel, case, panel_j, missing)
+    n_i, n_j, dev = side_i.struct.n_snps, side_j.struct.n_snps, panel.device
+    chisq = torch.empty((n_i, n_j), dtype=torch.float32, device=dev)
+    dirn = torch.empty((n_i, n_j), dtype=torch.float32, device=dev)
+    flags = torch.empty((n_i, n_j), dtype=torch.uint8, device=dev)
+    check(lib.ldx_epi_rect_dev(side_i.ref, side_j.ref, hc, hu, code, chisq.data_ptr(), dirn.data_ptr(), flags.data_ptr(), n_j,
+                               _stream_ptr()), "ldx_epi_rect_dev")
+    return EpiResult(chisq, dirn, flags, test, hc // 2, hu // 2)
+
+
+def ld_epistasis_counts(panel: PackedPanel, case, panel_j: Optional[PackedPanel] = None,
+                        missing: Optional[str] = None) -> torch.Tensor:
+    """The 18 integers of every pair as the scan's K loops produced them, before any float: int32 [18, n_i, n_j] on the device,
+    cases then controls, 3 a + b within a group (ldx_epi_counts_dev; epi_counts_host is the numpy mirror)."""
+    side_i, side_j, hc, hu = _epi_sides("ld_epistasis_counts", panel, case, panel_j, missing)
+    n_i, n_j = side_i.struct.n_snps, side_j.struct.n_snps
+    out = torch.empty((18, n_i, n_j), dtype=torch.int32, device=panel.device)
+    check(lib.ldx_epi_counts_dev(side_i.ref, side_j.ref, hc, hu, out.data_ptr(), n_j, _stream_ptr()), "ldx_epi_counts_dev")
+    return out
+
+
+def ld_epistasis_hits(panel: PackedPanel, case, panel_j: Optional[PackedPanel] = None, test: str = "boost",
+                      chisq: Optional[float] = None, p: float = 1e-4, p_sig: float = 1e-2, hit_capacity: Optional[int] = None,
+                      missing: Optional[str] = None) -> EpiHits:
+    """The pairs of ld_epistasis whose cell is at or above a bound, and the per-SNP summary PLINK writes next to them
+    (ldx_epi_hits_dev + ldx_area_finish_ex_dev).  ``panel_j`` None is the SELF scan: every pair i > j once, and the summary
+    credits both SNPs of a pair.  The bound is ``chisq`` where given, else epi_chisq_bound(p): a float32 made once on the host
+    and returned as ``.bound``; a cell is kept by one float32 compare.  ``p_sig`` is the summary's threshold (``n_sig``), turned
+    into ``summary.bound_sig`` the same way.  Buffers and retries are ld_rect_hits'."""
+    code = _epi_test("ld_epistasis_hits", test)
+    bound = np.float32(chisq) if chisq is not None else epi_chisq_bound(p, test)
+    bound_sig = epi_chisq_bound(p_sig, test)
+    if not bound > 0.0:
+        raise _lib.LdxError(f"ld_epistasis_hits: the chi-square bound must be > 0, got {bound!r}")
+    side_i, side_j, hc, hu = _epi_sides("ld_epistasis_hits", panel, case, panel_j, missing)
+    n_i, n_j, dev = side_i.struct.n_snps, side_j.struct.n_snps, panel.device
+    self_scan = panel_j is None
+    n_tot = torch.zeros(n_i, dtype=torch.int32, device=dev)
+    n_sig = torch.zeros(n_i, dtype=torch.int32, device=dev)
+    best = torch.zeros(n_i, dtype=torch.int64, device=dev)
+
+    def launch(raw, cap, n_hits, _counts):
+        for t in (n_tot, n_sig, best):   # a retry starts the summary again
+            t.zero_()
+        check(lib.ldx_epi_hits_dev(side_i.ref, side_j.ref, hc, hu, code, int(self_scan), float(bound), raw.data_ptr(), cap,
+                                   n_hits.data_ptr(), float(bound_sig), n_tot.data_ptr(), n_sig.data_ptr(), best.data_ptr(),
+                                   _stream_ptr()), "ldx_epi_hits_dev")
+
+    offsets, hits = _rect_hits_run("ld_epistasis_hits", launch, n_i, n_j, dev, hit_capacity)
+    none = n_tot == 0
+    bits = (best >> 32).to(torch.int32)
+    best_chisq = torch.where(none, torch.full_like(bits, 0x7FC00000), bits).view(torch.float32)
+    partner = torch.where(none, torch.full_like(best, -1), 0xFFFFFFFF - (best & 0xFFFFFFFF))
+    return EpiHits(offsets, hits, n_i, n_j, bound, test, self_scan, EpiSummary(n_sig, n_tot, best_chisq, partner, bound_sig))
+
+
+@dataclass
+class EpiCells:
+    """ld_epistasis_from_counts' outputs on the device, shaped as the counts behind their first axis: ``chisq`` float64,
+    ``chisq32`` (the scan's cell), ``dir`` and ``ln_p`` float64, ``flags`` uint8, ``cycles`` int32 and ``mu`` float64 [18, ...]
+    (the fitted table; NaN unless boost without flag 1)."""
+
+    chisq: torch.Tensor
+    chisq32: torch.Tensor
+    dir: torch.Tensor
+    ln_p: torch.Tensor
+    flags: torch.Tensor
+    mu: torch.Tensor
+    cycles: torch.Tensor
+
+
+def ld_epistasis_from_counts(counts, test: str = "boost", device: Optional[torch.device] = None) -> EpiCells:
+    """The scan's epilogue alone on tables ``counts`` [18, ...] (ld_epistasis_counts' order) -- the device function of the scan's
+    kernel (ldx_epi_from_counts_dev).  A table with more than LDX_MAX_HAPS / 2 individuals in a group is refused."""
+    code = _epi_test("ld_epistasis_from_counts", test)
+    k = _epi_tuples("ld_epistasis_from_counts", counts)
+    shape = k.shape[1:]
+    k = k.reshape(18, -1)
+    if k.size and max(int(k[:9].sum(axis=0).max()), int(k[9:].sum(axis=0).max())) > _lib.MAX_HAPS // 2:
+        raise _lib.LdxError(f"ld_epistasis_from_counts: LDX_E_ARG: a group total above LDX_MAX_HAPS / 2 = {_lib.MAX_HAPS // 2}")
+    m = k.shape[1]
+    if m == 0:
+        raise _lib.LdxError("ld_epistasis_from_counts: no table given")
+    require_gpu()
+    dev = device or (counts.device if isinstance(counts, torch.Tensor) and counts.is_cuda else
+                     torch.device("cuda", torch.cuda.current_device()))
+    tuples = torch.from_numpy(np.ascontiguousarray(k.T).astype(np.uint32).view(np.int32)).to(dev)
+    e = lambda dt, *s: torch.empty((m, *s), dtype=dt, device=dev)  # noqa: E731
+    chisq, chisq32, dirn, ln_p = e(torch.float64), e(torch.float32), e(torch.float64), e(torch.float64)
+    flags, mu, cycles = e(torch.uint8), e(torch.float64, 18), e(torch.int32)
+    check(lib.ldx_epi_from_counts_dev(m, code, tuples.data_ptr(), chisq.data_ptr(), chisq32.data_ptr(), dirn.data_ptr(),
+                                      ln_p.data_ptr(), flags.data_ptr(), mu.data_ptr(), cycles.data_ptr(), _stream_ptr()),
+          "ldx_epi_from_counts_dev")
+    v = lambda t: t.view(shape)  # noqa: E731
+    return EpiCells(v(chisq), v(chisq32), v(dirn), v(ln_p), v(flags), mu.T.contiguous().view(18, *shape), v(cycles))
+
+
 # --------------------------------------------------------------------------- instrumentation
 def probe_andpop(blocks: int, threads: int, iters: int) -> torch.Tensor:
     sink = torch.empty(blocks * threads, dtype=torch.int32, device=torch.device("cuda", torch.cuda.current_device()))
