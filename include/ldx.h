@@ -1486,6 +1486,71 @@ int ldx_epi_hits_dev(const ldx_epi_side *side_i, const ldx_epi_side *side_j, uin
 int ldx_epi_from_counts_dev(size_t m, int test, const uint32_t *tuples, double *chisq, float *chisq32, double *dir, double *ln_p,
                             uint8_t *flags, double *mu, uint32_t *cycles, void *stream);
 
+/* ---- permutation tests: max(T) label permutation for the allelic and the trend test of a case/control scan -------------------
+ * This project's own definition (what PLINK --assoc mperm and --model mperm report as EMP1 and EMP2), NOT validated against
+ * PLINK: no PLINK binary was available to compare with.
+ *
+ * INDIVIDUALS.  The scan runs over the n individuals with a phenotype, in panel order, index k (ops.py takes them with
+ * PackedPanel.select, as the epistasis scan does); n_case of them are cases.  g in {0, 1, 2}, "called" and half-missing
+ * genotypes are those of "genotype products" above (geno_words).
+ *
+ * PERMUTATION p is a global 0-based index; a call covers [first, first + n_perm).  key(p, k) = the synthetic panels' key(seed,
+ * i = p, h = k) below (the mix64 finaliser).  Individual k is a case in permutation p iff fewer than n_case individuals k' have
+ * (key(p, k'), k') < (key(p, k), k) lexicographically.  So every permutation has exactly n_case cases, and a permutation depends
+ * on (seed, p, n, n_case) alone: not on n_perm, first or the chunking of a run.
+ *
+ * THE LABEL PLANE: a tiled bit plane of ldx_plane_bytes(n_perm, 2 n) with the permutations as rows; the bit of haplotype slot 2k
+ * is set iff k is a case, the odd slots are zero -- what ldx_pack_codes_dev makes as the alt plane of codes 1 on the even slot of
+ * a case and 0 elsewhere, so a caller's own label matrix is packed by the existing code.  Every row must hold n_case cases.
+ *
+ * Per SNP over the n individuals: N called, n1 heterozygous, n2 homozygous ALT (cnt: ldx_geno_snp_counts_dev's table of the
+ * panel), G = n1 + 2 n2, Q2 = n1 + 4 n2.  Per cell (SNP i, permutation p), with L_pk the label:
+ *     R = sum_k called_k L_pk     a = sum_k g_k L_pk     S = N - R
+ * THE STATISTIC.  Every integer is exact in int64; the fp64 operations are exactly these, each rounded once:
+ *     LDX_PERM_ALLELIC  b = 2R - a, c = G - a, d = 2S - c, det = ad - bc, den = (a + b)(c + d)((a + c)(b + d))
+ *                       chisq = ((double)(2N) (double)(det^2)) / (double)den
+ *     LDX_PERM_TREND    U = N a - R G, den = R S (N Q2 - G^2)
+ *                       chisq = ((double)N (double)(U^2)) / (double)den
+ * Both are, bit for bit, ldx_model_tests_dev's chisq of tests 0 and 1 on any genotype table with these margins.  det^2, U^2 and
+ * den are at most N^4 < 2^53 for N <= LDX_MAX_HAPS / 2: exact doubles.  A cell with den = 0 is INVALID (for a usable SNP: R = 0 or
+ * R = N): it is neither counted nor enters a maximum.
+ *
+ * SNP FLAGS, from the observed labels (the host layer, ops.ld_mperm, forms them with ldx_perm_from_counts_dev on the group counts
+ * of ldx_geno_group_counts_dev): 0 OK; 1 no called case or no called control; 2 den = 0; 3 dropped by keep.  A flagged SNP has NaN
+ * stat and n_ge = 0 and takes part in no maximum.
+ * RESULTS: stat[i] the observed chisq; n_ge[i] = #{p : cell (i, p) is valid and chisq >= stat[i]} (uint32); max[p] = the largest
+ * valid chisq over the flag-0 SNPs, +0.0 if there is none; EMP1 = (n_ge + 1) / (R + 1), EMP2 = (#{p : max[p] >= stat[i]} + 1) /
+ * (R + 1), each ONE fp64 division.
+ *
+ * ldx_perm_labels_dev: writes the label plane of permutations first .. first + n_perm - 1 of n = n_hap / 2 individuals, one
+ *   workgroup per permutation (a radix select on the composite (key, k) in LDS); plain stores, every byte of the plane written.
+ * ldx_perm_scan_dev: stat double [n_snps], the observed statistic of each SNP, NaN for a SNP that takes no part (flagged or not
+ *   kept).  Adds to n_ge[i] (uint32) the permutations p of this call whose cell (i, p) is valid with chisq >= stat[i], and raises
+ *   max[p] (uint64: the bits of a non-negative double, p local to the call) to the largest valid chisq over the SNPs of this call
+ *   that take part.  The caller zeroes both; passing the same buffers again accumulates -- max over further SNP chunks or
+ *   chromosomes (same labels), n_ge over further permutation chunks (same SNPs).  All compares are fp64 >= on the values above, so
+ *   exact ties count.  Integer atomics only: the result does not depend on the order of arrival, the tile or the path.
+ *   128 x 128 tiles of SNPs x permutations on the FP4 matrix pipe, a = (g / 2).(2 L) and R = (called / 2).(2 L); a tile none of
+ *   whose SNPs has an uncalled individual (cnt called = n) forms a alone, with R = n_case.
+ * ldx_perm_counts_dev: counts[(s n_snps + i) ld + p], s = 0 for a, 1 for R, uint32: what the loops produced, before any float.
+ * ldx_perm_from_counts_dev: the scan's epilogue alone on m tuples (n[k] called, het[k], hom[k], r[k], a[k]): chisq double [m], flags
+ *   uint8 [m], the first that applies: 4 no table has these margins (het + hom > n, r > n, a > 2r, a > G, G - a > 2(n - r)) or n >
+ *   LDX_MAX_HAPS / 2      1 r = 0 or r = n: no called case or no called control      2 den = 0      0 OK; chisq is NaN unless 0.
+ *   The entry does not read device memory before the launch, so a tuple that is no table carries flag 4 and NaN, and the host
+ *   layer (ops.ld_mperm_from_counts), which holds the integers, refuses it as LDX_E_ARG before the call.
+ * A null pointer, a test other than the two, n_snps, n_perm or m = 0, n_case outside 1 .. n - 1, an odd or zero n_hap, a cnt that is
+ * not 16-byte aligned, ld < n_perm = LDX_E_ARG; n_hap > LDX_MAX_HAPS, a bit plane (the panel's or the labels') of 4 GiB or more,
+ * 2^31 or more tiles = LDX_E_UNSUPPORTED; all checked before any HIP call. */
+#define LDX_PERM_ALLELIC 0
+#define LDX_PERM_TREND 1
+int ldx_perm_labels_dev(uint64_t seed, uint64_t first, uint32_t n_perm, uint32_t n_hap, uint32_t n_case, void *labels, void *stream);
+int ldx_perm_scan_dev(const void *alt, const void *ref, const uint32_t *cnt, uint32_t n_snps, uint32_t n_hap, const void *labels,
+                      uint32_t n_perm, uint32_t n_case, int test, const double *stat, uint32_t *n_ge, uint64_t *max, void *stream);
+int ldx_perm_counts_dev(const void *alt, const void *ref, const uint32_t *cnt, uint32_t n_snps, uint32_t n_hap, const void *labels,
+                        uint32_t n_perm, uint32_t n_case, uint32_t *counts, size_t ld, void *stream);
+int ldx_perm_from_counts_dev(size_t m, int test, const uint32_t *n, const uint32_t *het, const uint32_t *hom, const uint32_t *r,
+                             const uint32_t *a, double *chisq, uint8_t *flags, void *stream);
+
 /* ---- synthetic panels: deterministic, identical on host and device ------ */
 /* codes int8 [n_snps][ld_codes] receive global SNPs [snp_offset, snp_offset + n_snps) (a rank's
  * shard).  thresholds: per-SNP ALT probability * 2^64 (computed on the host, see

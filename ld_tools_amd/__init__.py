@@ -38,6 +38,8 @@ from .ops import (MODEL_FLAGS, MODEL_TESTS, QC_FLAGS, HardyResult, MissingResult
 from .ops import (EPI_DF, EPI_FLAGS, EPI_TESTS, EpiCells, EpiHits, EpiResult, EpiSummary, epi_allelic_host,  # noqa: F401
                   epi_boost_host, epi_chisq_bound, epi_counts_host, epi_tail_host, ld_epistasis, ld_epistasis_counts,
                   ld_epistasis_from_counts, ld_epistasis_hits)
+from .ops import (MPERM_FLAGS, MPERM_TESTS, MpermResult, PermLabels, ld_mperm, ld_mperm_counts, ld_mperm_from_counts,  # noqa: F401
+                  ld_mperm_host, mperm_emp2, mperm_stat_host, perm_labels, perm_labels_host)
 from .panel import PackedPanel, encode_codes, select_index  # noqa: F401
 from . import plink  # noqa: F401
 from .plink import BedFile, bed_codes_host, codes_bed_host, read_covar, read_pheno, write_bfile  # noqa: F401
@@ -63,4 +65,6 @@ __all__ = ["PackedPanel", "encode_codes", "select_index", "ld_triangle", "ld_are
            "ld_epistasis", "ld_epistasis_hits", "ld_epistasis_counts", "ld_epistasis_from_counts", "EpiResult", "EpiHits",
            "EpiSummary", "EpiCells", "epi_counts_host", "epi_allelic_host", "epi_boost_host", "epi_tail_host", "epi_chisq_bound",
            "EPI_TESTS", "EPI_DF", "EPI_FLAGS",
+           "ld_mperm", "ld_mperm_counts", "ld_mperm_from_counts", "ld_mperm_host", "mperm_stat_host", "mperm_emp2", "perm_labels",
+           "perm_labels_host", "PermLabels", "MpermResult", "MPERM_TESTS", "MPERM_FLAGS",
            "version", "plink", "BedFile", "bed_codes_host", "codes_bed_host", "write_bfile", "read_pheno", "read_covar"]

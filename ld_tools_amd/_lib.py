@@ -46,6 +46,7 @@ QC_MAX_N = 65536                         # LDX_QC_MAX_N
 EPI_TESTS = {"allelic": 0, "boost": 1}   # LDX_EPI_ALLELIC / LDX_EPI_BOOST
 EPI_MAX_CYCLES = 55                      # LDX_EPI_MAX_CYCLES
 EPI_REL_BOUND = {"allelic": 2.0 ** -46, "boost": 4.17e-12}   # LDX_EPI_REL_BOUND_ALLELIC / _BOOST
+PERM_TESTS = {"allelic": 0, "trend": 1}   # LDX_PERM_ALLELIC / LDX_PERM_TREND
 FLAG_DPRIME_INT0 = 1
 FLAG_RSQ_INT0 = 2
 MEASURES = {"r_square": 0, "d_prime": 1}
@@ -235,6 +236,10 @@ SIGNATURES = {
     "ldx_epi_rect_dev": (_int, [_vp, _vp, _u32, _u32, _int, _vp, _vp, _vp, _sz, _vp]),
     "ldx_epi_hits_dev": (_int, [_vp, _vp, _u32, _u32, _int, _int, C.c_float, _vp, _u64, _vp, C.c_float, _vp, _vp, _vp, _vp]),
     "ldx_epi_from_counts_dev": (_int, [_sz, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ldx_perm_labels_dev": (_int, [_u64, _u64, _u32, _u32, _u32, _vp, _vp]),
+    "ldx_perm_scan_dev": (_int, [_vp, _vp, _vp, _u32, _u32, _vp, _u32, _u32, _int, _vp, _vp, _vp, _vp]),
+    "ldx_perm_counts_dev": (_int, [_vp, _vp, _vp, _u32, _u32, _vp, _u32, _u32, _vp, _sz, _vp]),
+    "ldx_perm_from_counts_dev": (_int, [_sz, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ldx_ld_select_workspace_bytes": (_sz, [_u32]),
     "ldx_ld_select_dev": (_int, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ldx_set_area_path": (_int, [_int]),

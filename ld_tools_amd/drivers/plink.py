@@ -19,13 +19,14 @@ dataclasses of the VCF drivers from it, so that their writers write them unchang
     bfile_missing    -> write_vmiss / write_smiss / write_test_missing     PLINK 2 --missing, PLINK --test-missing
     bfile_het        -> SampleQC for write_het                             PLINK --het
     bfile_model      -> ModelResult for write_model / write_assoc_fisher   PLINK --model, --assoc fisher
+    bfile_mperm      -> MpermTable for write_assoc_mperm                   PLINK --assoc mperm=N, --model trend mperm=N (max(T))
     bfile_qc         -> QcMasks (.qc.in / .qc.out / .qc.keep)              PLINK --mind --geno --maf --hwe
 
 A ``.bed`` holds unphased genotype calls: a het is written (ALT, REF) whatever the truth, so the haplotype r of the phased
 operators means nothing here.  Every driver defaults to an unphased form (EM or genotype dosage) and refuses
 ``dosage=False, em=False``.  ``make_bed`` writes a panel, or a subset of a loaded fileset, back as a fileset.
 
-    python -m ld_tools_amd.drivers.plink {ld,clump,prune,l2,blocks,king,pca,score,glm,logistic,hardy,missing,het,model,qc,make-bed}
+    python -m ld_tools_amd.drivers.plink {ld,clump,prune,l2,blocks,king,pca,score,glm,logistic,hardy,missing,het,model,mperm,qc,make-bed}
         --bfile P --out O ...
 """
 from __future__ import annotations
@@ -720,6 +721,22 @@ def bfile_epistasis(src, pheno=None, out: Optional[str] = None, test: str = "boo
     return table
 
 
+def bfile_mperm(src, pheno=None, out: Optional[str] = None, test: str = "allelic", n_perm: int = 10000, seed: int = 0,
+                pheno_name: Optional[str] = None, **load):
+    """drivers/mperm.py's ``mperm_table`` from a fileset (PLINK --assoc mperm=N, ``test`` "allelic", and --model trend mperm=N,
+    "trend"): the max(T) permutation test of every variant, EMP1 and EMP2.  ``pheno``: a case/control phenotype table
+    (case_control: 1 / 2 or 0 / 1; None: the ``.fam``'s column); a quantitative trait is refused.  ``out``: a prefix to write
+    ``.assoc.mperm`` (allelic) or ``.model.trend.mperm`` under.  Returns the MpermTable."""
+    from .mperm import MPERM_SUFFIX, mperm_table, write_assoc_mperm
+
+    bf = _loaded(src, **load)
+    case = _case_vector("bfile_mperm", bf, pheno, pheno_name)
+    table = mperm_table(bf.panel, case, bf.chrom, bf.ids, test=test, n_perm=n_perm, seed=seed)
+    if out is not None:
+        write_assoc_mperm(out + MPERM_SUFFIX[test], table)
+    return table
+
+
 @dataclass
 class QcMasks:
     """bfile_qc's result: ``snps`` uint8 device tensor [variants] (an operator's ``keep=``), ``individuals`` bool [individuals]."""
@@ -925,6 +942,13 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--epi2", type=float, default=1e-2, help="the summary's threshold")
     p.add_argument("--set-i", default=None, help="file of variant IDs: the first set of a set-by-set scan")
     p.add_argument("--set-j", default=None, help="file of variant IDs: the second set")
+    p = common("mperm", "max(T) permutation test of a case/control trait: EMP1 and EMP2 (.assoc.mperm, .model.trend.mperm)")
+    p.add_argument("--pheno", default=None, help="case/control phenotype table, 1 / 2 or 0 / 1 (default: the .fam's column)")
+    p.add_argument("--pheno-name", default=None, help="its column (default: the first)")
+    p.add_argument("--test", choices=("allelic", "trend"), default="allelic",
+                   help="allelic: the 1-df allele test of --assoc; trend: the Cochran-Armitage test of --model")
+    p.add_argument("--mperm", type=int, default=10000, help="the number of label permutations")
+    p.add_argument("--seed", type=int, default=0, help="the permutations' seed")
     common("make-bed", "write the selected variants and individuals as a new fileset")
     return ap
 
@@ -959,6 +983,11 @@ def main(argv=None) -> int:
                                 set_i=None if a.set_i is None else _read_names(a.set_i, 1),
                                 set_j=None if a.set_j is None else _read_names(a.set_j, 1))
         print(len(table.result), "pairs ->", a.out + ".epi.cc", a.out + ".epi.cc.summary")
+    elif a.command == "mperm":
+        from .mperm import MPERM_SUFFIX
+
+        table = bfile_mperm(bf, a.pheno, out=a.out, test=a.test, n_perm=a.mperm, seed=a.seed, pheno_name=a.pheno_name)
+        print(len(table.ids), "variants,", table.result.n_perm, "permutations ->", a.out + MPERM_SUFFIX[a.test])
     elif a.command == "qc":
         masks = bfile_qc(bf, out=a.out, geno=a.geno, maf=a.maf, hwe=a.hwe, mind=a.mind, pheno=a.pheno, pheno_name=a.pheno_name,
                          midp=a.midp)

@@ -28,6 +28,8 @@
     geno_group_counts(panel, groups)        genotype counts of every SNP within each of up to 32 groups of individuals, one pass
     ld_hardy / ld_model / ld_test_missing   exact HWE test per group; the table tests of --model and Fisher's test; missingness by status
     sample_qc / snp_qc_mask / sample_qc_mask   per-individual call counts and F; the --maf / --geno / --hwe and --mind masks
+    ld_mperm(panel, case, n_perm=, seed=)   max(T) permutation test of the allelic / trend test: EMP1 and EMP2, the SNP x permutation
+                                            rectangle reduced on chip to n counters and R maxima
     pair_counts(panel_i, panel_j)           <- calc_ld.py:32           (bit-exact n11 block)
     ld_from_counts(n, n11, a1, r1, a2, r2)  <- calc_ld.py:33-97        (the epilogue alone)
 
@@ -5616,6 +5618,308 @@ def ld_epistasis_from_counts(counts, test: str = "boost", device: Optional[torch
           "ldx_epi_from_counts_dev")
     v = lambda t: t.view(shape)  # noqa: E731
     return EpiCells(v(chisq), v(chisq32), v(dirn), v(ln_p), v(flags), mu.T.contiguous().view(18, *shape), v(cycles))
+
+
+# --------------------------------------------------------------------------- permutation tests (include/ldx.h, "permutation tests")
+MPERM_TESTS = tuple(_lib.PERM_TESTS)             # "allelic", "trend"
+MPERM_FLAGS = {0: "ok", 1: "no called case or no called control", 2: "den = 0: the statistic is undefined", 3: "dropped by keep",
+               4: "no table has these margins"}
+MPERM_MAX_N = _lib.MAX_HAPS // 2                 # individuals with a phenotype
+
+
+def _mperm_test(what: str, test) -> int:
+    if test not in _lib.PERM_TESTS:
+        raise _lib.LdxError(f"{what}: test must be one of {MPERM_TESTS}, got {test!r}")
+    return _lib.PERM_TESTS[test]
+
+
+def _mperm_shape(what: str, n: int, n_case: int, n_perm: int, first: int = 0) -> None:
+    if int(n_perm) < 1 or int(first) < 0:
+        raise _lib.LdxError(f"{what}: n_perm must be >= 1 and first >= 0 (got {n_perm}, {first})")
+    if not 2 <= int(n) <= MPERM_MAX_N:
+        raise _lib.LdxError(f"{what}: {n} individuals with a phenotype, outside 2 .. {MPERM_MAX_N} (LDX_MAX_HAPS / 2)")
+    if not 1 <= int(n_case) <= int(n) - 1:
+        raise _lib.LdxError(f"{what}: n_case {n_case} outside 1 .. n - 1 = {int(n) - 1}: both groups must hold an individual")
+
+
+def perm_labels_host(n: int, n_case: int, n_perm: int, seed: int, first: int = 0) -> np.ndarray:
+    """The numpy mirror of perm_labels: bool [n_perm, n], row r the cases of permutation first + r -- the n_case individuals that
+    come first in the order of (key(p, k), k), key = synth.key64(seed, i = p, h = k): uint64 keys and a stable argsort."""
+    from . import synth
+
+    _mperm_shape("perm_labels_host", n, n_case, n_perm, first)
+    p = np.arange(first, first + n_perm, dtype=np.uint64)
+    keys = synth.key64(int(seed), p[:, None], np.arange(n, dtype=np.uint64)[None, :])
+    order = np.argsort(keys, axis=1, kind="stable")
+    out = np.zeros((n_perm, n), dtype=bool)
+    np.put_along_axis(out, order[:, :n_case], True, axis=1)
+    return out
+
+
+@dataclass
+class PermLabels:
+    """The label plane of a block of permutations (include/ldx.h, "permutation tests"): ``plane`` uint8 [ldx_plane_bytes(n_perm,
+    2 n)] on the device, permutations as rows, the bit of haplotype slot 2k set iff individual k is a case.  ``seed`` is None for
+    a caller's own labels (from_array)."""
+
+    plane: torch.Tensor
+    n: int
+    n_case: int
+    n_perm: int
+    seed: Optional[int] = None
+    first: int = 0
+
+    @staticmethod
+    def from_array(labels, device: Optional[torch.device] = None) -> "PermLabels":
+        """A caller's own labels, bool / 0-1 [n_perm, n]; every row must hold the same number of cases.  Packed by the panels' own
+        code: code 1 on the even haplotype slot of a case, 0 elsewhere, and the alt plane of that."""
+        x = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+        if x.ndim != 2 or (x.dtype != bool and not np.isin(x, (0, 1)).all()):
+            raise _lib.LdxError(f"PermLabels.from_array: a bool / 0-1 matrix [n_perm, n] needed, got {x.dtype} with shape {x.shape}")
+        x = x.astype(bool)
+        sizes = x.sum(axis=1)
+        if x.shape[0] < 1 or (sizes != sizes[0]).any():
+            raise _lib.LdxError("PermLabels.from_array: every permutation must hold the same number of cases")
+        _mperm_shape("PermLabels.from_array", x.shape[1], int(sizes[0]), x.shape[0])
+        codes = np.zeros((x.shape[0], 2 * x.shape[1]), dtype=np.int8)
+        codes[:, 0::2] = x
+        return PermLabels(PackedPanel.from_codes(codes, device).alt, x.shape[1], int(sizes[0]), x.shape[0])
+
+    def to_array(self) -> np.ndarray:
+        """bool [n_perm, n]: the plane unpacked on the host."""
+        nch = lib.ldx_n_chunks(2 * self.n)
+        words = self.plane.cpu().numpy().view(np.uint32).reshape(-1, nch, _lib.SLAB_ROWS, 4)
+        rows = words.transpose(0, 2, 1, 3).reshape(-1, nch * 4)[: self.n_perm]
+        bits = np.unpackbits(np.ascontiguousarray(rows).view(np.uint8), axis=1, bitorder="little")
+        if bits[:, 1::2].any() or bits[:, 2 * self.n:].any():
+            raise _lib.LdxError("PermLabels.to_array: a bit on an odd haplotype slot or beyond the individuals")
+        return bits[:, 0:2 * self.n:2].astype(bool)
+
+
+def perm_labels(n: int, n_case: int, n_perm: int, seed: int, first: int = 0, device: Optional[torch.device] = None) -> PermLabels:
+    """The labels of permutations first .. first + n_perm - 1 of ``n`` individuals, ``n_case`` of them cases, made on the device
+    (ldx_perm_labels_dev): a permutation depends on (seed, its index, n, n_case) alone.  perm_labels_host is the numpy mirror."""
+    _mperm_shape("perm_labels", n, n_case, n_perm, first)
+    dev = device or require_gpu()
+    plane = torch.empty(lib.ldx_plane_bytes(int(n_perm), 2 * int(n)), dtype=torch.uint8, device=dev)
+    check(lib.ldx_perm_labels_dev(int(seed) & ((1 << 64) - 1), int(first), int(n_perm), 2 * int(n), int(n_case), plane.data_ptr(),
+                                  _stream_ptr()), "ldx_perm_labels_dev")
+    return PermLabels(plane, int(n), int(n_case), int(n_perm), int(seed), int(first))
+
+
+def _mperm_tuples(what: str, n, het, hom, r, a) -> list:
+    cols = _int_cols(what, (("n", n), ("het", het), ("hom", hom), ("r", r), ("a", a)))
+    N, n1, n2, R, A = cols
+    G = n1 + 2 * n2
+    if ((N > MPERM_MAX_N) | (n1 + n2 > N) | (R > N) | (A > 2 * R) | (A > G) | (G - A > 2 * (N - R))).any():
+        raise _lib.LdxError(f"{what}: LDX_E_ARG: a tuple that no genotype table of at most {MPERM_MAX_N} individuals has as its margins")
+    return cols
+
+
+def mperm_stat_host(n, het, hom, r, a, test: str = "allelic") -> Tuple[np.ndarray, np.ndarray]:
+    """The numpy mirror of ld_mperm_from_counts: (chisq float64 [m], flags uint8 [m]: 1 r = 0 or r = n, 2 den = 0) of the tuples
+    (n called, het, hom ALT; r called cases, a their ALT alleles).  int64 integers and the kernel's fp64 operations in its order:
+    bit for bit the device's, and model_tests_host's chisq of tests 0 and 1 on any table with these margins."""
+    code = _mperm_test("mperm_stat_host", test)
+    N, n1, n2, R, A = _mperm_tuples("mperm_stat_host", n, het, hom, r, a)
+    G, Q2, S = n1 + 2 * n2, n1 + 4 * n2, N - R
+    if code == 0:
+        b, c = 2 * R - A, G - A
+        d = 2 * S - c
+        det = A * d - b * c
+        den = (A + b) * (c + d) * ((A + c) * (b + d))
+        num = (2 * N).astype(np.float64) * (det * det).astype(np.float64)
+    else:
+        U = N * A - R * G
+        den = R * S * (N * Q2 - G * G)
+        num = N.astype(np.float64) * (U * U).astype(np.float64)
+    flags = np.where((R == 0) | (S == 0), 1, np.where(den == 0, 2, 0)).astype(np.uint8)
+    chisq = np.full(N.size, np.nan)
+    ok = flags == 0
+    chisq[ok] = num[ok] / den[ok].astype(np.float64)
+    return chisq, flags
+
+
+def _mperm_launch(code: int, cols: list) -> Tuple[torch.Tensor, torch.Tensor]:
+    m, dev = int(cols[0].numel()), cols[0].device
+    chisq = torch.empty(m, dtype=torch.float64, device=dev)
+    flags = torch.empty(m, dtype=torch.uint8, device=dev)
+    check(lib.ldx_perm_from_counts_dev(m, code, *(c.data_ptr() for c in cols), chisq.data_ptr(), flags.data_ptr(), _stream_ptr()),
+          "ldx_perm_from_counts_dev")
+    return chisq, flags
+
+
+def ld_mperm_from_counts(n, het, hom, r, a, test: str = "allelic", device: Optional[torch.device] = None):
+    """The permutation scan's epilogue alone on integer tuples (ldx_perm_from_counts_dev): (chisq float64 [m], flags uint8 [m]) on
+    the device.  A tuple that no genotype table has as its margins is refused (LDX_E_ARG)."""
+    code = _mperm_test("ld_mperm_from_counts", test)
+    cols = _mperm_tuples("ld_mperm_from_counts", n, het, hom, r, a)
+    require_gpu()
+    dev = device or torch.device("cuda", torch.cuda.current_device())
+    return _mperm_launch(code, _to_dev_u32(cols, dev))
+
+
+def mperm_emp2(stat: torch.Tensor, maxima: torch.Tensor) -> torch.Tensor:
+    """EMP2 = (#{p : maxima[p] >= stat[i]} + 1) / (R + 1) by one sort and one searchsorted; NaN where stat is."""
+    srt = torch.sort(maxima.reshape(-1)).values
+    below = torch.searchsorted(srt, torch.nan_to_num(stat, nan=0.0).contiguous(), right=False)   # maxima < stat
+    num = (srt.numel() - below + 1).to(torch.float64)
+    emp = num / torch.full_like(num, float(srt.numel() + 1))   # tensor by tensor: ONE fp64 division on every device
+    return torch.where(torch.isnan(stat), torch.full_like(emp, float("nan")), emp)
+
+
+@dataclass
+class MpermResult:
+    """ld_mperm's result (tensors on the panel's device; ld_mperm_host: on the CPU).  ``stat`` float64 [n_snps], the observed
+    chi-square (NaN where flagged); ``flags`` uint8 [n_snps] (MPERM_FLAGS); ``n_ge`` int32 [n_snps], the permutations whose cell is
+    valid and >= stat, over ``n_perm_total`` permutations (this call's ``n_perm`` and those counted into a shared ``n_ge`` before);
+    ``maxima`` float64 [n_perm], the largest valid chi-square of each of THIS call's permutations over the unflagged SNPs seen so
+    far (+0.0: none).  ``emp1`` = (n_ge + 1) / (n_perm_total + 1), ``emp2`` = mperm_emp2(stat, maxima); NaN where flagged."""
+
+    stat: torch.Tensor
+    flags: torch.Tensor
+    n_ge: torch.Tensor
+    maxima: torch.Tensor
+    n_perm: int
+    n_case: int
+    n_ctrl: int
+    test: str = "allelic"
+    n_perm_total: int = 0
+
+    @property
+    def emp1(self) -> torch.Tensor:
+        num = self.n_ge.to(torch.float64) + 1.0
+        e = num / torch.full_like(num, float(self.n_perm_total + 1))   # tensor by tensor: ONE fp64 division on every device
+        return torch.where(self.flags == 0, e, torch.full_like(e, float("nan")))
+
+    @property
+    def emp2(self) -> torch.Tensor:
+        return mperm_emp2(self.stat, self.maxima)
+
+
+class _MpermRun:
+    """What the scan operators share: the argument rules, the sub-panel of the individuals with a phenotype (PackedPanel.select,
+    as the epistasis scan), its per-SNP table, the labels and the observed tuples.  Holds the tensors alive."""
+
+    def __init__(self, what: str, panel: PackedPanel, case, n_perm, seed, first, labels, keep, missing):
+        _qc_missing(what, missing)
+        _even_n_hap(what, panel)
+        groups = _case_groups(what, case, panel.n_ind)
+        sizes = groups.sum(axis=1)
+        self.n_case, self.n_ctrl = int(sizes[0]), int(sizes[1])
+        self.n = self.n_case + self.n_ctrl
+        if labels is not None:
+            if not isinstance(labels, PermLabels):
+                labels = PermLabels.from_array(labels, panel.device)
+            if (labels.n, labels.n_case) != (self.n, self.n_case) or (n_perm is not None and int(n_perm) != labels.n_perm):
+                raise _lib.LdxError(f"{what}: labels of {labels.n_perm} permutations of {labels.n} individuals with {labels.n_case} "
+                                    f"cases; the call has {self.n} individuals with a phenotype, {self.n_case} cases"
+                                    + ("" if n_perm is None else f", n_perm = {n_perm}"))
+        elif n_perm is None:
+            raise _lib.LdxError(f"{what}: give n_perm (and seed) or labels")
+        _mperm_shape(what, self.n, self.n_case, labels.n_perm if labels is not None else n_perm, first)
+        require_gpu()
+        self.keep = _keep_mask(keep, panel.n_snps)
+        keep_d = _keep_dev(keep, panel.n_snps, panel.device)
+        ind = np.nonzero(groups[0] | groups[1])[0].astype(np.int64)
+        self.sub = panel if self.n == panel.n_ind else panel.select(haplotypes=np.stack([2 * ind, 2 * ind + 1], axis=1).reshape(-1))
+        self.cnt = _snp_counts(self.sub, keep_d)
+        self.labels = labels if labels is not None else perm_labels(self.n, self.n_case, int(n_perm), seed, first, panel.device)
+        member, _, _ = _groups_member(what, groups, panel.n_ind)
+        self.groups = _group_counts(panel, keep_d, member, 2)      # the observed labels: [n_snps, 2, 4]
+
+    def observed(self, code: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(stat, flags) of the observed labels through the scan's own epilogue."""
+        g = self.groups
+        tot = g[:, 0] + g[:, 1]
+        cols = [tot[:, 0], tot[:, 1], tot[:, 2], g[:, 0, 0], g[:, 0, 1] + 2 * g[:, 0, 2]]
+        stat, flags = _mperm_launch(code, [c.contiguous() for c in cols])
+        if self.keep is not None:
+            flags[torch.from_numpy(~self.keep).to(flags.device)] = 3
+        return stat, flags
+
+    def head(self) -> tuple:
+        s = self.sub
+        return (s.alt.data_ptr(), s.ref.data_ptr(), self.cnt.data_ptr(), s.n_snps, s.n_hap, self.labels.plane.data_ptr(),
+                self.labels.n_perm, self.n_case)
+
+
+def ld_mperm(panel: PackedPanel, case, test: str = "allelic", n_perm: Optional[int] = None, seed: int = 0, first: int = 0,
+             labels=None, keep=None, maxima: Optional[torch.Tensor] = None, n_ge: Optional[torch.Tensor] = None,
+             n_perm_before: int = 0, missing: Optional[str] = None) -> MpermResult:
+    """The max(T) permutation test of ``plink --assoc mperm`` / ``--model mperm`` for the allelic or the trend test (this project's
+    own definition: include/ldx.h, "permutation tests"; ldx_perm_scan_dev).  ``case``: ld_model's argument, 0 / 1 / NaN per
+    individual, NaN = left out.  The labels of permutations ``first`` .. ``first + n_perm - 1`` come from ``seed`` (perm_labels),
+    or ``labels`` gives them: a PermLabels or a bool matrix [R, individuals with a phenotype], every row with as many cases as
+    ``case``.  Of the SNP x permutation rectangle only ``n_ge`` and ``maxima`` leave the chip.
+    ``maxima``: an earlier call's, over the SAME permutations and other SNPs (a chromosome at a time): this call raises it, and
+    its emp2 is then over all SNPs so far.  ``n_ge``: an earlier call's, over the SAME SNPs and other permutations, of which
+    ``n_perm_before`` were counted: this call adds to it.  Both are changed in place.  A SNP that ``keep`` drops has flag 3."""
+    what = "ld_mperm"
+    code = _mperm_test(what, test)
+    run = _MpermRun(what, panel, case, n_perm, seed, first, labels, keep, missing)
+    R, n, dev = run.labels.n_perm, panel.n_snps, panel.device
+    if maxima is None:
+        maxima = torch.zeros(R, dtype=torch.float64, device=dev)
+    elif maxima.dtype != torch.float64 or maxima.shape != (R,) or maxima.device != dev or not maxima.is_contiguous():
+        raise _lib.LdxError(f"{what}: maxima must be a contiguous float64 tensor [{R}] on {dev}")
+    if n_ge is None:
+        n_ge = torch.zeros(n, dtype=torch.int32, device=dev)
+    elif n_ge.dtype != torch.int32 or n_ge.shape != (n,) or n_ge.device != dev or not n_ge.is_contiguous():
+        raise _lib.LdxError(f"{what}: n_ge must be a contiguous int32 tensor [{n}] on {dev}")
+    stat, flags = run.observed(code)
+    check(lib.ldx_perm_scan_dev(*run.head(), code, stat.data_ptr(), n_ge.data_ptr(), maxima.data_ptr(), _stream_ptr()),
+          "ldx_perm_scan_dev")
+    return MpermResult(stat, flags, n_ge, maxima, R, run.n_case, run.n_ctrl, test, R + int(n_perm_before))
+
+
+def ld_mperm_counts(panel: PackedPanel, case, n_perm: Optional[int] = None, seed: int = 0, first: int = 0, labels=None,
+                    missing: Optional[str] = None) -> torch.Tensor:
+    """The two integers of every (SNP, permutation) cell as the scan's K loops produced them, before any float: int32 [2, n_snps,
+    R] on the device, a (ALT alleles among the permutation's cases) then R (its cases called at the SNP) (ldx_perm_counts_dev).
+    For tests and small R."""
+    run = _MpermRun("ld_mperm_counts", panel, case, n_perm, seed, first, labels, None, missing)
+    R = run.labels.n_perm
+    out = torch.empty((2, panel.n_snps, R), dtype=torch.int32, device=panel.device)
+    check(lib.ldx_perm_counts_dev(*run.head(), out.data_ptr(), R, _stream_ptr()), "ldx_perm_counts_dev")
+    return out
+
+
+def ld_mperm_host(codes, case, test: str = "allelic", n_perm: Optional[int] = None, seed: int = 0, first: int = 0, labels=None,
+                  keep=None) -> MpermResult:
+    """The numpy mirror of ld_mperm on the allele codes [n_snps, n_hap]: the same MpermResult with CPU tensors, bit for bit --
+    exact integer GEMMs for (a, R) of every cell, mperm_stat_host for the statistic."""
+    what = "ld_mperm_host"
+    _mperm_test(what, test)
+    g, c = geno_planes_host(codes, keep)
+    groups = _case_groups(what, case, g.shape[1])
+    ind = np.nonzero(groups[0] | groups[1])[0]
+    n, n_case = int(ind.size), int(groups[0].sum())
+    if labels is None:
+        if n_perm is None:
+            raise _lib.LdxError(f"{what}: give n_perm (and seed) or labels")
+        L = perm_labels_host(n, n_case, int(n_perm), seed, first)
+    else:
+        L = labels.to_array() if isinstance(labels, PermLabels) else np.asarray(labels).astype(bool)
+        if L.ndim != 2 or L.shape[1] != n or (L.sum(axis=1) != n_case).any():
+            raise _lib.LdxError(f"{what}: labels must be [R, {n}] with {n_case} cases in every row")
+    g, c = g[:, ind], c[:, ind]
+    obs = groups[0][ind]
+    N, n1, n2 = c.sum(axis=1), (g == 1).sum(axis=1), (g == 2).sum(axis=1)
+    stat, flags = mperm_stat_host(N, n1, n2, c[:, obs].sum(axis=1), g[:, obs].sum(axis=1), test)
+    k = _keep_mask(keep, g.shape[0])
+    if k is not None:
+        flags[~k] = 3
+    Lf = L.astype(np.float64).T                                   # sums <= 10 240: exact
+    a, R = (g.astype(np.float64) @ Lf).astype(np.int64), (c.astype(np.float64) @ Lf).astype(np.int64)
+    m, P = a.shape
+    rep = lambda v: np.repeat(v, P)  # noqa: E731
+    x, f = mperm_stat_host(rep(N), rep(n1), rep(n2), R.reshape(-1), a.reshape(-1), test)
+    x, valid = x.reshape(m, P), (f.reshape(m, P) == 0) & (flags == 0)[:, None]
+    n_ge = (valid & (x >= np.where(flags == 0, stat, np.inf)[:, None])).sum(axis=1).astype(np.int32)
+    maxima = np.where(valid, x, 0.0).max(axis=0) if m else np.zeros(P)
+    t = torch.from_numpy
+    return MpermResult(t(stat), t(flags), t(n_ge), t(np.ascontiguousarray(maxima, dtype=np.float64)), P, n_case, n - n_case, test, P)
 
 
 # --------------------------------------------------------------------------- instrumentation
