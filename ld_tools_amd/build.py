@@ -25,7 +25,7 @@ SOURCES = ["ldx_api.hip", "ldx_pack.hip", "ldx_pairs.hip", "ldx_mfma.hip", "ldx_
            "ldx_logit.hip", "ldx_firth.hip", "ldx_qc.hip", "ldx_epi.hip", "ldx_perm.hip"]
 HEADERS = [CSRC / "ldx_common.h", CSRC / "ldx_fp4.h", CSRC / "ldx_tile.h", CSRC / "ldx_pwc_tile.h", CSRC / "ldx_em_tile.h",
            CSRC / "ldx_em_pw_tile.h", CSRC / "ldx_band_plan.h", CSRC / "ldx_sample_store.h", CSRC / "ldx_tail.h",
-           PKG.parent / "include" / "ldx.h"]
+           CSRC / "ldx_logit_fit.h", PKG.parent / "include" / "ldx.h"]
 
 # -ffp-contract=off: the epilogue must round every product and sum separately (calc_ld.py:50);
 # hipcc's default for device code is fp-contract=fast.

@@ -112,6 +112,20 @@ __host__ __device__ inline uint32_t n_slabs(uint32_t n_snps) { return (n_snps + 
 // per K-block (one per lane half), so a row always holds an even number of chunks; pad chunks are zero bits
 __host__ __device__ inline uint32_t n_chunks(uint32_t n_hap) { return (n_hap + 255u) / 256u * 2u; }
 
+// key(seed, i, h) of the synthetic panels (ldx_synth.hip, ld_tools_amd/synth.py) and of the permutations' labels (ldx_perm.hip):
+// the splitmix64 finaliser of seed ^ i*0x9E3779B97F4A7C15 ^ h*0xBF58476D1CE4E5B9
+__device__ __forceinline__ uint64_t mix64(uint64_t x)
+{
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+__device__ __forceinline__ uint64_t key64(uint64_t seed, uint64_t i, uint64_t h)
+{
+    return mix64(seed ^ (i * 0x9E3779B97F4A7C15ull) ^ (h * 0xBF58476D1CE4E5B9ull));
+}
+
 // first unit of j-tile t: t*G - 8*t*(t-1), G = groups in the padded panel
 __host__ __device__ inline uint64_t tile_base(uint64_t t, uint64_t G) { return t * G - 8u * t * (t - 1u); }
 

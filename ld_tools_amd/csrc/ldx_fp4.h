@@ -74,6 +74,14 @@ __device__ __forceinline__ GenoWords geno_words(uint32_t wa, uint32_t wr)
     const uint32_t a = wa & (q | (q << 1));   // a half-missing genotype is missing
     return GenoWords{q, a & (a >> 1) & 0x55555555u, (a ^ (a >> 1)) & q};
 }
+// 16 bits to the even slots of a word: the bits of 16 individuals in the layout of GenoWords::q/t/z
+__device__ __forceinline__ uint32_t spread16(uint32_t x)
+{
+    x = (x | (x << 8)) & 0x00FF00FFu;
+    x = (x | (x << 4)) & 0x0F0F0F0Fu;
+    x = (x | (x << 2)) & 0x33333333u;
+    return (x | (x << 1)) & 0x55555555u;
+}
 __device__ __forceinline__ v4i even_a4(uint32_t z)
 {
     return v4i{(int)(z & 0x11111111u), 0, (int)((z >> 2) & 0x11111111u), 0};   // 0.5, -, 0.5, -

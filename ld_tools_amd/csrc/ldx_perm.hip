@@ -71,19 +71,7 @@ __device__ __forceinline__ bool perm_cell(int test, uint32_t n_called, uint32_t 
 }
 
 // ---- labels ---------------------------------------------------------------------------------------------------------------------
-// key(p, k) = synth.key(seed, i = p, h = k): the finaliser of ldx_synth.hip and ld_tools_amd/synth.py
-__device__ __forceinline__ uint64_t mix64(uint64_t x)
-{
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-__device__ __forceinline__ uint64_t key64(uint64_t seed, uint64_t i, uint64_t h)
-{
-    return mix64(seed ^ (i * 0x9E3779B97F4A7C15ull) ^ (h * 0xBF58476D1CE4E5B9ull));
-}
-
+// key(p, k) = key64(seed, i = p, h = k) of ldx_common.h: the synthetic panels' key (ldx_synth.hip, ld_tools_amd/synth.py)
 constexpr uint32_t kLabThreads = 256;
 constexpr uint32_t kLabPer = kMaxInd / kLabThreads;   // individuals per thread: 20
 static_assert(kLabPer * kLabThreads == kMaxInd && kLabPer <= 32u, "a thread's individuals fit a 32-bit mask");
@@ -93,14 +81,6 @@ static_assert(kMaxInd <= (1u << 16), "the index is two digits of the composite")
 __device__ __forceinline__ uint32_t digit_of(uint32_t d, uint64_t key, uint32_t k)
 {
     return d < 8u ? (uint32_t)(key >> (56u - 8u * d)) & 255u : (d == 8u ? (k >> 8) & 255u : k & 255u);
-}
-// the bits of 16 individuals on the even haplotype slots of a word
-__device__ __forceinline__ uint32_t spread16(uint32_t x)
-{
-    x = (x | (x << 8)) & 0x00FF00FFu;
-    x = (x | (x << 4)) & 0x0F0F0F0Fu;
-    x = (x | (x << 2)) & 0x33333333u;
-    return (x | (x << 1)) & 0x55555555u;
 }
 
 __global__ void __launch_bounds__(kLabThreads) labels_kernel(uint64_t seed, uint64_t first, uint32_t n_perm, uint32_t n, uint32_t n_case,

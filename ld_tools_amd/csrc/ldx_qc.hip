@@ -27,16 +27,6 @@ constexpr uint32_t kThreads = 256;
 constexpr uint32_t kPartStride = kSlab + 1u;   // words between two counters of the meeting buffer: g and g + 1 on adjacent banks
 constexpr uint32_t kMaxWords = LDX_MAX_HAPS / 32u;   // 32-bit words of a row: 320
 
-// 16 bits to the even slots of a word
-__device__ __forceinline__ uint32_t spread16(uint32_t x)
-{
-    x = (x | (x << 8)) & 0x00FF00FFu;
-    x = (x | (x << 4)) & 0x0F0F0F0Fu;
-    x = (x | (x << 2)) & 0x33333333u;
-    x = (x | (x << 1)) & 0x55555555u;
-    return x;
-}
-
 template <uint32_t NG>
 __global__ void __launch_bounds__(kThreads) group_counts_kernel(const uint4 *alt, const uint4 *ref, const uint8_t *keep,
                                                                 const uint32_t *member, uint32_t n_snps, uint32_t n_ind,

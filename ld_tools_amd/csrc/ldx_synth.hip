@@ -13,19 +13,6 @@
 
 namespace ldx {
 
-__host__ __device__ inline uint64_t mix64(uint64_t x)
-{
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-__host__ __device__ inline uint64_t key64(uint64_t seed, uint64_t i, uint64_t h)
-{
-    return mix64(seed ^ (i * 0x9E3779B97F4A7C15ull) ^ (h * 0xBF58476D1CE4E5B9ull));
-}
-
 // one thread per (LD block, haplotype): walks the block's SNPs in order
 __global__ void synth_codes_kernel(int8_t *__restrict__ codes, uint32_t n_snps, uint32_t n_hap, size_t ld,
                                    uint64_t seed, const uint64_t *__restrict__ thr, uint64_t rho_thr,

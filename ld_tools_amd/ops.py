@@ -4389,22 +4389,31 @@ def _logit_mu(eta):
     return np.where(pos, hi, lo), np.where(pos, lo, hi), hi * lo
 
 
+def _logit_evaluation(V, yes, theta, gradient: bool):
+    """The evaluation that both iterations below begin with, at ``theta``: (mu, r = y - mu, w, L, grad) with L the Cholesky factor
+    of the information (V w) V^T and grad = V r (None without ``gradient``); L is None where a sum is not finite or a pivot is
+    not > 0, which ends the fit."""
+    with np.errstate(all="ignore"):
+        mu, om, w = _logit_mu(theta @ V)
+        r = np.where(yes, om, -mu)
+        info = (V * w) @ V.T
+        grad = V @ r if gradient else None
+    if not (np.isfinite(info).all() and (grad is None or np.isfinite(grad).all())):
+        return mu, r, w, None, grad
+    try:
+        return mu, r, w, np.linalg.cholesky(info), grad
+    except np.linalg.LinAlgError:
+        return mu, r, w, None, grad
+
+
 def _logit_newton(V, y, theta, last_index: int):
     """Undamped Newton on the rows of ``V`` [m, N] from ``theta`` (include/ldx.h, "logistic association scan", Iteration):
     (theta, se of parameter ``last_index``, evaluations, ok)."""
     yes = y != 0
     done = False
     for it in range(1, _lib.LOGIT_MAX_ITER + 1):
-        with np.errstate(all="ignore"):
-            mu, om, w = _logit_mu(theta @ V)
-            r = np.where(yes, om, -mu)
-            info = (V * w) @ V.T
-            grad = V @ r
-        if not (np.isfinite(info).all() and np.isfinite(grad).all()):
-            return theta, np.nan, it, False
-        try:
-            L = np.linalg.cholesky(info)
-        except np.linalg.LinAlgError:
+        _mu, _r, _w, L, grad = _logit_evaluation(V, yes, theta, True)
+        if L is None:
             return theta, np.nan, it, False
         if done:
             return theta, 1.0 / L[last_index, last_index], it, True
@@ -4428,15 +4437,8 @@ def _firth_scoring(V, y, theta, last_index: int, decs: Optional[list] = None):
     # step, and the step length stays halved for the rest of the fit
     length, before, start, step = 1.0, np.inf, theta, None
     for it in range(1, _lib.FIRTH_MAX_ITER + 1):
-        with np.errstate(all="ignore"):
-            mu, om, w = _logit_mu(theta @ V)
-            r = np.where(yes, om, -mu)
-            info = (V * w) @ V.T
-        if not np.isfinite(info).all():
-            return theta, np.nan, it, False
-        try:
-            L = np.linalg.cholesky(info)
-        except np.linalg.LinAlgError:
+        mu, r, w, L, _grad = _logit_evaluation(V, yes, theta, False)
+        if L is None:
             return theta, np.nan, it, False
         if done:
             return theta, 1.0 / L[last_index, last_index], it, True
