@@ -1159,6 +1159,69 @@ int ldx_geno_matmul_dev(const void *store, const uint32_t *tables, uint32_t n_in
 int ldx_geno_rmatmul_dev(const void *alt, const void *ref, uint32_t n_snps, uint32_t n_hap, const uint8_t *keep,
                          const int32_t *u, size_t ld_u, uint32_t k, int64_t *z, int64_t *zc, size_t ld_z, void *stream);
 
+/* ---- weighted sample products: the genotype matrix against itself with a weight per SNP; the genetic relationship matrix ------
+ * This project's own definition, written after Yang et al. 2011 (GCTA --make-grm, PLINK 2 --make-rel); NOT validated against
+ * either program.
+ *
+ * Individuals, called genotypes, kept SNPs and the transposed store are those of "sample relatedness"; g_ia in {0, 1, 2} (0 when
+ * the call is missing) and c_ia in {0, 1} those of "genotype products".  With three int32 weights per SNP of the store, |.| <=
+ * LDX_WPROD_MAX_WEIGHT = 2^28, laid out int32 [n_snps][3] = {q2, q1, q0}, row i belonging to SNP snp_begin + i of the store:
+ *     S[a][b] = sum_i ( q2_i g_ia g_ib + q1_i (g_ia c_ib + c_ia g_ib) + q0_i c_ia c_ib )          int64 [n_ind][ld], the full square
+ * The sum is exact and symmetric and does not depend on SNP order, slicing or chunking: bit-reproducible.  A term is at most
+ * (4 + 2 + 2 + 1) 2^28 < 2^32 in size, so across the 2^27 SNPs of the largest store every partial sum stays below 9 x 2^55 < 2^59;
+ * sums of several stores stay exact while their SNPs together do not pass 2^31 (9 x 2^28 x 2^31 < 2^63).
+ *
+ * ldx_sample_wprod_dev: store and tables are what ldx_sample_planes_dev wrote for the same n_snps (tables is part of the contract
+ * for a shortcut on tiles without missing calls; the present kernel takes the general path everywhere and does not read it).
+ * accumulate = 0: the call first defines every word S[a][b < n_ind]; accumulate = 1: it adds to what is there (the stores of a long
+ * panel, chromosomes, .bed chunks).  workspace: ldx_sample_wprod_workspace_bytes(n_snps) bytes, 16-byte aligned, written by the
+ * call (the weights' digit table: 24 bytes per SNP); no initialisation.
+ * PRECONDITION: every weight lies in -2^28 .. 2^28.  The entry cannot check device memory before its launch; the Python layer
+ * does (ops.sample_wprod, one device reduction).  A weight outside the range gives wrong sums, never a fault.
+ * Work: (lower tile of 128 x 128 individuals) x (K slice) on v_mfma_i32_32x32x32_i8.  With u_ib = q2_i g_ib + q1_i c_ib and
+ * v_ib = q1_i g_ib + q0_i c_ib the sum is sum_i (g_ia u_ib + c_ia v_ib); u and v take three values per SNP among the called
+ * (g = 0, 1, 2), each |.| <= 3 x 2^28 < 2^30: four balanced base-256 digits in [-128, 127] (x + 0x80808080 has them, plus 128, in
+ * its bytes).  The row operand is g resp. c as int8, the column operand digit l of u resp. v, selected from a per-SNP table by
+ * byte masks made of the column individual's bit planes; 8 MFMAs per 32 x 32 x 32, 1024 per 128 x 128 x 256 block, into four int32
+ * accumulators per cell, recombined as sum_l 256^l acc_l in int64 at the end of the slice and added to S with 64-bit integer
+ * atomics; the mirror-image tile is written from the same integers.  No floating-point atomics anywhere.
+ * An accumulator takes at most |g d| + |c d'| <= 2 x 128 + 128 = 384 per SNP, so slice SNPs <= LDX_WPROD_MAX_SLICE_SNPS:
+ * 384 x 2^22 = 3 x 2^29 < 2^31.  n_slices = 0 lets the library choose (about four rounds of workgroups, no slice under
+ * LDX_WPROD_MIN_SLICE_SNPS); a value of the caller's is used as given (capped at the K-blocks of 256 SNPs) and refused with
+ * LDX_E_ARG when a slice would pass the bound.
+ * Argument rules, checked before any HIP call: a null pointer, n_ind or n_snps = 0, ld < n_ind, more than LDX_KING_MAX_STORE_SNPS
+ * SNPs, a workspace that is too small or not aligned, an n_slices past the slice bound = LDX_E_ARG; n_ind > LDX_MAX_HAPS / 2 =
+ * LDX_E_UNSUPPORTED.
+ *
+ * The genetic relationship matrix (ops.grm_weights, ops.ld_grm): per SNP, from the counts {n called, het, hom} of
+ * ldx_geno_snp_counts_dev, s = het + 2 hom.  A SNP is LIVE when it is kept, 0 < s < 2n, and -- with a bound maf_min --
+ * (double)min(s, 2n - s) / (double)(2n) >= maf_min.  For a live SNP, every operation in fp64 rounded once, in this order:
+ *     p = (double)s / (double)(2n)      w = 1.0 / ((2.0 p) (1.0 - p))
+ *     x2 = w      x1 = -((2.0 p) w)      x0 = ((4.0 p) p) w
+ * All 3 n_live values are quantised as ONE column by the genotype products' rule with 28 scale bits: e = the smallest integer
+ * with max |x| 2^-e <= 1 (0 when no SNP is live), q = rint(x 2^(28 - e)), round-half-even; a SNP that is not live gets (0, 0, 0).
+ * Then S 2^(e - 28) = sum over the live SNPs called in both of w^ (g_a - 2 p^)(g_b - 2 p^) with the quantised coefficients, and
+ * with N[a][b] the live SNPs called in both (ldx_sample_counts_dev over keep = live) the cell is GCTA's default,
+ *     grm[a][b] = (float)( ((double)S[a][b] 2^(e - 28)) / (double)N[a][b] );      -0.0f where N[a][b] == 0
+ * (the conversion of S rounds once, to nearest-even, the scaling is exact, the division rounds once: numpy reproduces the cell bit
+ * for bit, ops.grm_cell_host).  A missing call DROPS OUT of the pair's sum and of its N, as in GCTA: this is the one place where
+ * the library does NOT set a missing genotype to the SNP's mean (the association scans and sample_pca do).  S and N add over
+ * chromosomes and chunks of a fileset -- each with the weights of its own SNPs but ONE exponent e: ops.ld_grm quantises a
+ * chunk with the exponent it is given -- before the division.
+ * Against the GRM of the unquantised rational weights: a coefficient is off by at most 2^(e - 29), the three multiply at most
+ * 4, 4 and 1, so |S 2^(e - 28) - exact| <= 9 n_live 2^(e - 29), before the division by N.
+ * ldx_grm_cells_dev: grm float32 [n_ind][ld_out] from S int64 [n_ind][ld_s] and N uint32 [n_ind][ld_n]; |exp| <= LDX_GRM_MAX_EXP. */
+#define LDX_WPROD_SCALE_BITS 28
+#define LDX_WPROD_MAX_WEIGHT 268435456      /* 2^28 */
+#define LDX_WPROD_MIN_SLICE_SNPS 16384u     /* the automatic choice makes no shorter slice: its atomics stay small beside its MFMAs */
+#define LDX_WPROD_MAX_SLICE_SNPS 4194304u   /* 2^22: (2 x 128 + 128) x (slice SNPs) < 2^31 */
+#define LDX_GRM_MAX_EXP 900
+size_t ldx_sample_wprod_workspace_bytes(uint32_t n_snps);
+int ldx_sample_wprod_dev(const void *store, const uint32_t *tables, uint32_t n_ind, uint32_t n_snps, const int32_t *q, int64_t *S,
+                         size_t ld, int accumulate, uint32_t n_slices, void *workspace, size_t workspace_bytes, void *stream);
+int ldx_grm_cells_dev(const int64_t *S, size_t ld_s, const uint32_t *N, size_t ld_n, uint32_t n_ind, int exp, float *grm,
+                      size_t ld_out, void *stream);
+
 /* ---- association scan: per SNP the least-squares fit of quantitative phenotypes on the genotype, an intercept and covariates --
  * This project's own definition (what PLINK 2 --glm reports for a quantitative trait: BETA, SE, T_STAT, P), NOT validated
  * against PLINK 2.  It differs from PLINK wherever a call is missing: a missing genotype is set to the SNP's MEAN over its

@@ -25,6 +25,8 @@ from .ops import (GabrielBlocks, LDCiBand, dprime_ci_host, gabriel_candidates_ho
                   gabriel_pick_host, ld_ci_from_counts, ld_dprime_ci, ld_gabriel_blocks)
 from .ops import (RelatedPairs, SampleCounts, ibs_cell_host, ibs_matrix, king_cell_host, king_cutoff,  # noqa: F401
                   king_from_counts, king_kinship, sample_counts, sample_counts_host)
+from .ops import (GrmResult, grm_cell_host, grm_cutoff, grm_weights, ld_grm, ld_grm_from_sums, ld_grm_host,  # noqa: F401
+                  sample_wprod, sample_wprod_host)
 from .ops import (GenoOperator, GenoProduct, SamplePCA, Scores, geno_matmul, geno_matmul_host, geno_quantize,  # noqa: F401
                   geno_rmatmul, geno_rmatmul_host, polygenic_score, polygenic_score_host, sample_pca, sample_pca_host)
 from .ops import (GLM_FLAGS, GlmDesign, GlmResult, geno_counts_host, geno_snp_counts, glm_design, glm_linear_host,  # noqa: F401
@@ -53,6 +55,8 @@ __all__ = ["PackedPanel", "encode_codes", "select_index", "ld_triangle", "ld_are
            "LDCiBand", "ld_gabriel_blocks", "GabrielBlocks", "ld_ci_from_counts", "dprime_ci_host", "gabriel_candidates_host",
            "gabriel_pick_host", "gabriel_kept_host", "sample_counts", "SampleCounts", "RelatedPairs", "king_kinship", "ibs_matrix",
            "sample_counts_host", "king_cell_host", "ibs_cell_host", "king_from_counts", "king_cutoff", "GenoOperator", "GenoProduct",
+           "sample_wprod", "sample_wprod_host", "grm_weights", "grm_cell_host", "ld_grm", "ld_grm_host", "ld_grm_from_sums",
+           "grm_cutoff", "GrmResult",
            "geno_quantize", "geno_matmul", "geno_rmatmul", "geno_matmul_host", "geno_rmatmul_host", "polygenic_score",
            "polygenic_score_host", "Scores", "sample_pca", "sample_pca_host", "SamplePCA", "geno_snp_counts", "geno_counts_host",
            "glm_design", "GlmDesign", "ld_glm", "ld_glm_host", "glm_linear_host", "glm_tail_host", "GlmResult", "GLM_FLAGS", "LdxError",

@@ -38,6 +38,11 @@ KING_MAX_SLICE_SNPS = 1 << 23            # LDX_KING_MAX_SLICE_SNPS
 KING_MAX_STORE_SNPS = 1 << 27            # LDX_KING_MAX_STORE_SNPS
 GENO_MAX_COLS = 64                       # LDX_GENO_MAX_COLS
 GENO_MAX_SLICE_SNPS = 1 << 22            # LDX_GENO_MAX_SLICE_SNPS
+WPROD_SCALE_BITS = 28                    # LDX_WPROD_SCALE_BITS
+WPROD_MAX_WEIGHT = 1 << 28               # LDX_WPROD_MAX_WEIGHT
+WPROD_MIN_SLICE_SNPS = 16384             # LDX_WPROD_MIN_SLICE_SNPS
+WPROD_MAX_SLICE_SNPS = 1 << 22           # LDX_WPROD_MAX_SLICE_SNPS
+GRM_MAX_EXP = 900                        # LDX_GRM_MAX_EXP
 LOGIT_MAX_COV = 13                       # LDX_LOGIT_MAX_COV
 LOGIT_MAX_ITER = 30                      # LDX_LOGIT_MAX_ITER
 FIRTH_MAX_ITER = 200                     # LDX_FIRTH_MAX_ITER
@@ -222,6 +227,9 @@ SIGNATURES = {
     "ldx_sample_cells_dev": (_int, [_vp, _u32, _sz, _vp, _vp, _sz, _vp]),
     "ldx_geno_matmul_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _sz, _u32, _vp, _sz, _int, _u32, _vp]),
     "ldx_geno_rmatmul_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _sz, _u32, _vp, _vp, _sz, _vp]),
+    "ldx_sample_wprod_workspace_bytes": (_sz, [_u32]),
+    "ldx_sample_wprod_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _sz, _int, _u32, _vp, _sz, _vp]),
+    "ldx_grm_cells_dev": (_int, [_vp, _sz, _vp, _sz, _u32, _int, _vp, _sz, _vp]),
     "ldx_geno_snp_counts_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp]),
     "ldx_glm_linear_dev": (_int, [_vp, _vp, _sz, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ldx_glm_logistic_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _sz, _u32, _vp, _vp, _u32, _dbl, _vp, _vp, _vp, _vp, _vp,

@@ -22,7 +22,7 @@ LIB = PKG / "libldx.so"
 SOURCES = ["ldx_api.hip", "ldx_pack.hip", "ldx_pairs.hip", "ldx_mfma.hip", "ldx_area.hip", "ldx_synth.hip",
            "ldx_select.hip", "ldx_band.hip", "ldx_rect.hip", "ldx_em.hip", "ldx_pwc.hip", "ldx_pwband.hip",
            "ldx_emband.hip", "ldx_bed.hip", "ldx_gabriel.hip", "ldx_king.hip", "ldx_geno.hip", "ldx_glm.hip",
-           "ldx_logit.hip", "ldx_firth.hip", "ldx_qc.hip", "ldx_epi.hip", "ldx_perm.hip"]
+           "ldx_logit.hip", "ldx_firth.hip", "ldx_qc.hip", "ldx_epi.hip", "ldx_perm.hip", "ldx_grm.hip"]
 HEADERS = [CSRC / "ldx_common.h", CSRC / "ldx_fp4.h", CSRC / "ldx_tile.h", CSRC / "ldx_pwc_tile.h", CSRC / "ldx_em_tile.h",
            CSRC / "ldx_em_pw_tile.h", CSRC / "ldx_band_plan.h", CSRC / "ldx_sample_store.h", CSRC / "ldx_tail.h",
            CSRC / "ldx_logit_fit.h", PKG.parent / "include" / "ldx.h"]

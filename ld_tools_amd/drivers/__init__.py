@@ -23,6 +23,7 @@ from .em import (EmBand, EmMatrix, em_band, em_hits, em_matrix, em_window_hits, 
 from .epistasis import EpiTable, epistasis_table, write_epi_cc, write_epi_summary  # noqa: F401
 from .glm import GlmTable, glm_table, write_glm_linear  # noqa: F401
 from .king import KingTable, king_table, write_kin0, write_king_cutoff, write_king_matrix  # noqa: F401
+from .grm import GrmTable, grm_table, write_grm_bin, write_grm_cutoff, write_rel  # noqa: F401
 from .pca import PcaTable, ScoreTable, pca_table, score_table, write_eigenval, write_eigenvec, write_sscore  # noqa: F401
 from .prune import PruneTable, prune, write_prune  # noqa: F401
 from .qc import (QcVariants, write_assoc_fisher, write_hardy, write_het, write_model, write_smiss,  # noqa: F401
@@ -35,7 +36,7 @@ from .triangle import (TriangleMatrix, create_matrix, stream_triangle_table, tri
 # drivers/plink.py is also a command (python -m ld_tools_amd.drivers.plink), so its names are bound on first use rather than
 # imported here: runpy would otherwise find the module loaded before it runs it
 _PLINK_NAMES = ("Bfile", "load_bfile", "bfile_ld_table", "bfile_clump", "bfile_prune", "bfile_ld_scores", "bfile_band",
-                "bfile_em_band", "bfile_blocks", "bfile_king", "bfile_pca", "bfile_score", "bfile_glm", "read_score_file", "make_bed",
+                "bfile_em_band", "bfile_blocks", "bfile_king", "bfile_grm", "bfile_pca", "bfile_score", "bfile_glm", "read_score_file", "make_bed",
                 "bfile_hardy", "bfile_missing", "bfile_het", "bfile_model", "bfile_qc", "bfile_epistasis")
 
 

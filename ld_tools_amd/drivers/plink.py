@@ -11,6 +11,7 @@ dataclasses of the VCF drivers from it, so that their writers write them unchang
     bfile_blocks     -> GabrielTable for write_gabriel_blocks              PLINK --blocks (Gabriel et al.'s D' interval rule)
     bfile_king       -> KingTable for write_kin0 / write_king_cutoff       PLINK 2 --make-king-table / --king-cutoff
     bfile_pca        -> PcaTable for write_eigenvec / write_eigenval       PLINK 2 --pca approx
+    bfile_grm        -> GrmTable for write_grm_bin / write_rel             GCTA --make-grm / --grm-cutoff, PLINK 2 --make-rel
     bfile_score      -> ScoreTable for write_sscore                        PLINK --score (sums)
     bfile_glm        -> GlmTables for write_glm_linear                     PLINK 2 --glm (quantitative traits, mean imputation)
     bfile_logistic   -> LogisticTables for write_glm_logistic              PLINK 2 --glm (case/control traits, no Firth fallback)
@@ -26,7 +27,7 @@ A ``.bed`` holds unphased genotype calls: a het is written (ALT, REF) whatever t
 operators means nothing here.  Every driver defaults to an unphased form (EM or genotype dosage) and refuses
 ``dosage=False, em=False``.  ``make_bed`` writes a panel, or a subset of a loaded fileset, back as a fileset.
 
-    python -m ld_tools_amd.drivers.plink {ld,clump,prune,l2,blocks,king,pca,score,glm,logistic,hardy,missing,het,model,mperm,qc,make-bed}
+    python -m ld_tools_amd.drivers.plink {ld,clump,prune,l2,blocks,king,grm,pca,score,glm,logistic,hardy,missing,het,model,mperm,qc,make-bed}
         --bfile P --out O ...
 """
 from __future__ import annotations
@@ -355,6 +356,63 @@ def bfile_king(src, out: Optional[str] = None, keep=None, extract=None, prune_r2
             write_king_matrix(out, table, kin.cpu().numpy())
         if cutoff is not None:
             write_king_cutoff(out, table, cutoff, kin)
+    return table
+
+
+GRM_CHUNK_SNPS = 65536            # variants of a fileset that bfile_grm holds on the device at a time
+
+
+def bfile_grm(src, out: Optional[str] = None, keep=None, extract=None, chrom=None, maf_min: Optional[float] = None,
+              cutoff: Optional[float] = None, fmt: str = "gcta", chunk_snps: int = GRM_CHUNK_SNPS, alt: str = "a1"):
+    """drivers/grm.py's ``grm_table`` from a fileset: the genetic relationship matrix of its individuals over the live variants
+    (``maf_min``: the MAF bound among the called), IDs from the ``.fam``.  A fileset given by its prefix (or a
+    ``plink.BedFile``) is STREAMED, ``chunk_snps`` variants at a time, in two passes over the file: the first takes every
+    chunk's SNP counts and from them the ONE exponent of the coefficients, the second accumulates S and N over the chunks, each
+    with the weights of its own SNP counts -- the same integers, and so the same files, as one call on the whole panel.
+    ``keep`` / ``extract`` / ``chrom`` / ``alt``: load_bfile's selections (all chromosomes count when ``chrom`` is None).  A
+    loaded ``Bfile`` is taken as it is, in one piece.  ``out``: a prefix to write under -- ``fmt="gcta"``: ``.grm.bin``,
+    ``.grm.N.bin``, ``.grm.id``; ``fmt="rel"``: ``.rel``, ``.rel.id``; with ``cutoff`` also ``.grm.cutoff.in.id`` / ``.out.id``.
+    Returns the GrmTable."""
+    from .grm import GrmTable, grm_table, write_grm_bin, write_grm_cutoff, write_rel
+    from ..ops import geno_snp_counts, grm_coefficients, grm_exponent, ld_grm
+
+    if fmt not in ("gcta", "rel"):
+        raise LdxError(f"bfile_grm: fmt must be 'gcta' or 'rel', got {fmt!r}")
+    if isinstance(src, Bfile):
+        if keep is not None or extract is not None or chrom is not None:
+            raise LdxError("bfile_grm: a loaded fileset takes no keep / extract / chrom arguments")
+        table = grm_table(src.panel, list(zip(src.fid, src.iid)), maf_min=maf_min)
+    else:
+        chunk_snps = int(chunk_snps)
+        if chunk_snps < 1:
+            raise LdxError("bfile_grm: chunk_snps must be positive")
+        bed = src if isinstance(src, plink.BedFile) else plink.BedFile(src)
+        snps = np.arange(bed.n_snps) if extract is None else (
+            _by_name(extract, bed.ids, "variant ID") if _is_names(extract, False) else
+            select_index(extract, bed.n_snps, "SNP").astype(np.int64))
+        if chrom is not None:
+            snps = snps[np.asarray([bed.chrom[i] == str(chrom) for i in snps], dtype=bool)]
+        if snps.size == 0:
+            raise LdxError("bfile_grm: no variant selected")
+        inds = None
+        if keep is not None:
+            inds = _by_name(keep, list(zip(bed.fid, bed.iid)), "(FID, IID) pair") if _is_names(keep, True) else \
+                select_index(keep, bed.n_ind, "individual").astype(np.int64)
+        chunks = [snps[k:k + chunk_snps] for k in range(0, snps.size, chunk_snps)]
+        load = lambda part: PackedPanel.from_bed(bed, keep=inds, extract=part, alt=alt)  # noqa: E731
+        big = 0.0
+        for part in chunks:                                   # pass 1: the largest coefficient of the fileset
+            x, _ = grm_coefficients(geno_snp_counts(load(part)), None, maf_min)
+            big = max(big, float(np.abs(x).max()) if x.size else 0.0)
+        res = None
+        for part in chunks:                                   # pass 2: the sums
+            res = ld_grm(load(part), maf_min=maf_min, out=res, exp=grm_exponent(big))
+        f = bed.fam(inds)
+        table = GrmTable(list(f["fid"]), list(f["iid"]), res)
+    if out is not None:
+        (write_grm_bin if fmt == "gcta" else write_rel)(out, table)
+        if cutoff is not None:
+            write_grm_cutoff(out, table, cutoff)
     return table
 
 
@@ -890,6 +948,11 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--prune-r2", type=float, default=None, help="count over the variants LD pruning keeps at this r^2")
     p.add_argument("--prune-window-kb", type=float, default=250.0)
     p.add_argument("--missing", choices=("pairwise",), default=None, help="how the pruning treats missing calls")
+    p = common("grm", "genetic relationship matrix, streamed (.grm.bin / .grm.N.bin / .grm.id, or .rel / .rel.id; "
+                      "--maf: the MAF bound among the called)")
+    p.add_argument("--grm-cutoff", type=float, default=None, help="keep a maximal set with no pair above this relationship")
+    p.add_argument("--format", choices=("gcta", "rel"), default="gcta", help="GCTA's binary triangle or PLINK's text triangle")
+    p.add_argument("--chunk-snps", type=int, default=GRM_CHUNK_SNPS, help="variants held on the device at a time")
     p = common("pca", "principal components of the individuals (.eigenvec, .eigenval)")
     p.add_argument("--pca", type=int, default=10, dest="n_pcs", help="the number of components")
     p.add_argument("--king-cutoff", type=float, default=None, help="decompose a maximal unrelated set, project the others")
@@ -963,6 +1026,14 @@ def main(argv=None) -> int:
     a = parser().parse_args(argv)
     keep = None if a.keep is None else _read_names(a.keep, 2)
     extract = None if a.extract is None else _read_names(a.extract, 1)
+    if a.command == "grm":               # streamed from the file: nothing is loaded in one piece; --maf is the GRM's own bound
+        if a.geno is not None:
+            raise LdxError("grm: --geno is not supported (a missing call drops out of its pairs)")
+        table = bfile_grm(a.bfile, out=a.out, keep=keep, extract=extract, chrom=a.chr, maf_min=a.maf, cutoff=a.grm_cutoff,
+                          fmt=a.format, chunk_snps=a.chunk_snps, alt=a.alt)
+        print(table.result.n_ind, "individuals,", table.result.n_live, "live variants ->",
+              a.out + (".grm.bin" if a.format == "gcta" else ".rel"))
+        return 0
     own_filters = a.command == "qc"      # qc applies --maf / --geno itself, after --mind
     bf = load_bfile(a.bfile, chrom=a.chr, keep=keep, extract=extract, maf_min=None if own_filters else a.maf,
                     geno_max=None if own_filters else a.geno, alt=a.alt)

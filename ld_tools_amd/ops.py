@@ -20,6 +20,7 @@
     ld_decay / ld_blocks                    LD decay curves per distance bin; haplotype blocks by the four-gamete test
     ld_dprime_ci / ld_gabriel_blocks        D' confidence bounds on the EM band and Gabriel's haplotype blocks
     sample_counts / king_kinship / ibs_matrix   IBS counts and KING-robust kinship between the individuals
+    sample_wprod / ld_grm / grm_cutoff      weighted genotype x genotype sums on the int8 matrix cores; the genetic relationship matrix
     GenoOperator / geno_matmul / geno_rmatmul   genotype products on the matrix cores, exact integers
     sample_pca / polygenic_score            sample PCA and per-SNP weights applied to the individuals, on those products
     ld_glm(panel, Y, covar, ...)            linear association scan on the reverse genotype product
@@ -4056,6 +4057,217 @@ def sample_pca_host(codes, n_pcs: int = 10, keep=None, oversample: int = 10, n_i
                     loadings: bool = False) -> SamplePCA:
     """Host mirror of sample_pca on the allele codes [n_snps, n_hap]."""
     return _pca(_HostEngine(codes, keep), int(n_pcs), int(oversample), int(n_iter), seed, loadings)
+
+
+# --------------------------------------------------------------------------- weighted sample products, the GRM
+WPROD_SCALE_BITS = _lib.WPROD_SCALE_BITS       # a quantised GRM coefficient is rint(2^28 x 2^-e): |q| <= 2^28
+
+
+def _wprod_weights(what: str, q, rows: int, dev) -> torch.Tensor:
+    """The weights of sample_wprod as the entry takes them: a contiguous int32 [rows, 3] tensor on ``dev`` within -2^28 .. 2^28
+    (the C entry's precondition, checked here: on the host for a host array, by one device reduction for a device tensor)."""
+    t = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q))
+    if t.dtype != torch.int32 or t.ndim != 2 or tuple(t.shape) != (rows, 3):
+        raise _lib.LdxError(f"{what}: int32 weights [{rows}, 3] = (q2, q1, q0) needed; got {t.dtype} {tuple(t.shape)}")
+    if rows:
+        lo, hi = torch.aminmax(t)
+        if int(lo.item()) < -_lib.WPROD_MAX_WEIGHT or int(hi.item()) > _lib.WPROD_MAX_WEIGHT:
+            raise _lib.LdxError(f"{what}: the weights must lie in -2^28 .. 2^28")
+    return t.to(dev).contiguous()
+
+
+def sample_wprod(panel: PackedPanel, q, keep=None, out: Optional[torch.Tensor] = None, n_slices: Optional[int] = None,
+                 store_snps: int = SAMPLE_STORE_SNPS) -> torch.Tensor:
+    """S[a, b] = sum_i (q2_i g_ia g_ib + q1_i (g_ia c_ib + c_ia g_ib) + q0_i c_ia c_ib) between the individuals of ``panel`` over
+    the SNPs that pass ``keep``: int64 device tensor [n_ind, n_ind], exact (include/ldx.h, "weighted sample products").  ``q``:
+    int32 [n_snps, 3] = (q2, q1, q0) per SNP of the panel, each within -2^28 .. 2^28.  The panel is transposed ``store_snps`` SNPs
+    at a time as sample_counts does, and each store multiplied on the int8 matrix cores (ldx_sample_wprod_dev).  ``out``: an
+    earlier result of the same individuals to add to (chromosomes, chunks of a fileset).  ``n_slices``: the K slices per tile
+    (None: the library's choice).  The result does not depend on the order or the split of the SNPs."""
+    require_gpu()
+    store_snps, keep_d = _store_args("sample_wprod", panel, keep, store_snps)
+    n_ind, n_snps, dev = panel.n_ind, panel.n_snps, panel.device
+    w = _wprod_weights("sample_wprod", q, n_snps, dev)
+    if out is None:
+        S, accumulate = torch.empty((n_ind, n_ind), dtype=torch.int64, device=dev), 0
+    else:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != (n_ind, n_ind) or \
+                not out.is_contiguous() or out.device != dev:
+            raise _lib.LdxError(f"sample_wprod: out must be a contiguous int64 [{n_ind}, {n_ind}] tensor on {dev}")
+        S, accumulate = out, 1
+    width = min(store_snps, n_snps)
+    store = torch.empty(lib.ldx_sample_planes_bytes(n_ind, width), dtype=torch.uint8, device=dev)
+    tables = torch.empty(lib.ldx_sample_tables_bytes(n_ind) // 4, dtype=torch.int32, device=dev)
+    ws = torch.empty(lib.ldx_sample_wprod_workspace_bytes(width), dtype=torch.uint8, device=dev)
+    for begin in range(0, n_snps, store_snps):
+        count = min(store_snps, n_snps - begin)
+        _planes_launch(panel, keep_d, begin, count, store, tables)
+        check(lib.ldx_sample_wprod_dev(store.data_ptr(), tables.data_ptr(), n_ind, count, w.data_ptr() + 12 * begin, S.data_ptr(),
+                                       n_ind, accumulate, int(n_slices or 0), *_ws(ws), _stream_ptr()), "ldx_sample_wprod_dev")
+        accumulate = 1
+    S._keep = (store, tables, ws, w, keep_d)   # alive until the launches are done
+    return S
+
+
+def sample_wprod_host(codes, q, keep=None) -> np.ndarray:
+    """Host mirror of sample_wprod in numpy integers, term by term as the definition reads: int64 [n_ind, n_ind] from the allele
+    codes [n_snps, n_hap] (Python integers where 9 x 2^28 x n_snps could pass 2^63)."""
+    g, c = geno_planes_host(codes, keep)
+    q = q.cpu().numpy() if isinstance(q, torch.Tensor) else np.asarray(q)
+    if q.ndim != 2 or q.shape != (g.shape[0], 3) or q.dtype.kind not in "iu":
+        raise _lib.LdxError(f"sample_wprod_host: integer weights [{g.shape[0]}, 3] needed, got {q.dtype} {q.shape}")
+    kind = np.int64 if g.shape[0] < (1 << 63) // (9 << WPROD_SCALE_BITS) else object
+    g, c, q = g.astype(kind), c.astype(kind), q.astype(kind)
+    q2, q1, q0 = q[:, 0:1], q[:, 1:2], q[:, 2:3]
+    return g.T @ (q2 * g) + g.T @ (q1 * c) + c.T @ (q1 * g) + c.T @ (q0 * c)
+
+
+def grm_exponent(big: float) -> int:
+    """The smallest integer e with big 2^-e <= 1 (geno_quantize's rule); 0 for big = 0."""
+    big = float(big)
+    if not np.isfinite(big) or big < 0:
+        raise _lib.LdxError(f"grm_exponent: a finite non-negative value is needed, got {big}")
+    if big == 0.0:
+        return 0
+    mant, e = math.frexp(big)                   # big = mant 2^e, mant in [0.5, 1)
+    return e - 1 if mant == 0.5 else e
+
+
+def grm_coefficients(snp_counts, keep=None, maf_min: Optional[float] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """The unquantised half of grm_weights: (x float64 [n_live, 3] = (w, -2 p w, 4 p^2 w), live bool [n_snps]) from the SNP
+    counts {called n, het, hom} of geno_snp_counts, every operation rounded once in the order of include/ldx.h."""
+    c = snp_counts.cpu().numpy() if isinstance(snp_counts, torch.Tensor) else np.asarray(snp_counts)
+    if c.ndim != 2 or c.shape[1] < 3 or c.dtype.kind not in "iu":
+        raise _lib.LdxError(f"grm_weights: integer SNP counts [n_snps, 3 or 4] = (called, het, hom ALT) needed, got {c.dtype} {c.shape}")
+    if c.dtype == np.int32:
+        c = c.view(np.uint32)                   # geno_snp_counts' words
+    c = c.astype(np.int64)
+    n, s = c[:, 0], c[:, 1] + 2 * c[:, 2]
+    two_n = 2 * n
+    live = (s > 0) & (s < two_n)                # hence n > 0
+    k = _keep_mask(keep, c.shape[0])
+    if k is not None:
+        live &= k
+    if maf_min is not None:
+        maf = np.minimum(s, two_n - s).astype(np.float64) / np.where(two_n > 0, two_n, 1).astype(np.float64)
+        live &= maf >= float(maf_min)
+    p = s[live].astype(np.float64) / two_n[live].astype(np.float64)
+    tp = 2.0 * p
+    w = 1.0 / (tp * (1.0 - p))
+    return np.stack([w, -(tp * w), ((4.0 * p) * p) * w], axis=1).reshape(-1, 3), live
+
+
+def grm_weights(snp_counts, keep=None, maf_min: Optional[float] = None, exp: Optional[int] = None) -> Tuple[np.ndarray, int, np.ndarray]:
+    """The fixed-point GRM coefficients of every SNP (include/ldx.h, "weighted sample products"): (q int32 [n_snps, 3], e, live
+    uint8 [n_snps]).  A SNP is live when it is kept, 0 < s < 2 n (s = het + 2 hom) and its MAF is >= ``maf_min``; its
+    coefficients (w, -2 p w, 4 p^2 w), p = s / (2 n), w = 1 / (2 p (1 - p)), are quantised with ONE exponent for all 3 n_live
+    values -- e = the smallest integer with max |x| 2^-e <= 1, q = rint(x 2^(28 - e)) -- and the other SNPs get (0, 0, 0).
+    ``exp``: quantise with this exponent instead (the one of an earlier chunk or of the whole fileset; it must cover every
+    value)."""
+    x, live = grm_coefficients(snp_counts, keep, maf_min)
+    big = float(np.abs(x).max()) if x.size else 0.0
+    e = grm_exponent(big) if exp is None else int(exp)
+    if abs(e) > _lib.GRM_MAX_EXP or big > math.ldexp(1.0, e):
+        raise _lib.LdxError(f"grm_weights: the exponent {e} does not cover the largest coefficient {big}")
+    q = np.zeros((live.size, 3), dtype=np.int32)
+    q[live] = np.rint(x * math.ldexp(1.0, WPROD_SCALE_BITS - e)).astype(np.int32)
+    return q, e, live.astype(np.uint8)
+
+
+def grm_cell_host(S, N, exp: int) -> np.ndarray:
+    """Host mirror of the GRM cell: float32 ((double)S 2^(exp - 28)) / (double)N, -0.0f where N is 0."""
+    S, N = np.asarray(S).astype(np.int64), np.asarray(N).astype(np.int64)
+    val = ((S.astype(np.float64) * math.ldexp(1.0, int(exp) - WPROD_SCALE_BITS)) / np.where(N > 0, N, 1).astype(np.float64)).astype(np.float32)
+    return np.where(N > 0, val, np.float32(-0.0)).astype(np.float32)
+
+
+def ld_grm_from_sums(S, N, exp: int, device: Optional[torch.device] = None) -> torch.Tensor:
+    """The GRM cells of accumulated integers (ldx_grm_cells_dev): float32 device tensor [n_ind, n_ind] from S (int64) and N
+    (uint32 values), device tensors or host arrays, so that S and N can be summed over chromosomes before the division."""
+    require_gpu()
+    dev = device or (S.device if isinstance(S, torch.Tensor) and S.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    s = (S if isinstance(S, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(S).astype(np.int64)))).to(dev)
+    if isinstance(N, torch.Tensor):
+        n = (N.view(torch.int32) if N.dtype == torch.uint32 else N).to(dev)
+    else:
+        nn = np.asarray(N).astype(np.int64)
+        if nn.size and (int(nn.min()) < 0 or int(nn.max()) >= (1 << 32)):
+            raise _lib.LdxError("ld_grm_from_sums: N must hold uint32 values")
+        n = torch.from_numpy(np.ascontiguousarray(nn.astype(np.uint32).view(np.int32))).to(dev)
+    if n.dtype == torch.int64:
+        n = n.to(torch.int32)                   # the low 32 bits: uint32 values
+    if s.dtype != torch.int64 or n.dtype != torch.int32 or s.ndim != 2 or s.shape[0] != s.shape[1] or s.shape != n.shape:
+        raise _lib.LdxError(f"ld_grm_from_sums: square int64 S and uint32 N of one shape needed, got {tuple(s.shape)} and {tuple(n.shape)}")
+    if abs(int(exp)) > _lib.GRM_MAX_EXP:
+        raise _lib.LdxError(f"ld_grm_from_sums: exp {exp} outside -{_lib.GRM_MAX_EXP} .. {_lib.GRM_MAX_EXP}")
+    s, n = s.contiguous(), n.contiguous()
+    m = int(s.shape[0])
+    grm = torch.empty((m, m), dtype=torch.float32, device=dev)
+    if m:
+        check(lib.ldx_grm_cells_dev(s.data_ptr(), m, n.data_ptr(), m, m, int(exp), grm.data_ptr(), m, _stream_ptr()), "ldx_grm_cells_dev")
+    return grm
+
+
+@dataclass
+class GrmResult:
+    """The genetic relationship matrix as its integers (include/ldx.h, "weighted sample products"): ``S`` int64 [n_ind, n_ind],
+    the weighted sums in units of 2^(exp - 28); ``N`` uint32 [n_ind, n_ind], the live SNPs called in both; ``exp``, the shared
+    exponent of the coefficients; ``n_live``, the live SNPs so far.  From ld_grm they are device tensors (``counts`` is the
+    SampleCounts behind N), from ld_grm_host numpy arrays."""
+
+    S: object
+    N: object
+    exp: int
+    n_live: int
+    counts: Optional[SampleCounts] = None
+
+    @property
+    def n_ind(self) -> int:
+        return int(self.S.shape[0])
+
+    def grm(self):
+        """float32 [n_ind, n_ind]: ((double)S 2^(exp - 28)) / (double)N per cell, -0.0f where N is 0 -- GCTA's default: a missing
+        call drops out of the pair."""
+        if isinstance(self.S, np.ndarray):
+            return grm_cell_host(self.S, self.N, self.exp)
+        return ld_grm_from_sums(self.S, self.N, self.exp)
+
+
+def ld_grm(panel: PackedPanel, keep=None, maf_min: Optional[float] = None, out: Optional[GrmResult] = None,
+           exp: Optional[int] = None) -> GrmResult:
+    """The genetic relationship matrix of the individuals of ``panel`` (gcta --make-grm, plink2 --make-rel) over the SNPs that
+    pass ``keep`` and are live (polymorphic among the called, MAF >= ``maf_min``): the SNP counts (geno_snp_counts) give the
+    coefficients on the host (grm_weights), sample_wprod the sums S on the int8 matrix cores and sample_counts over the live SNPs
+    the jointly called counts N.  ``out``: an earlier result of the same individuals to add to -- chromosomes or chunks of a
+    fileset; its exponent is used, and must cover this panel's coefficients.  ``exp``: the exponent to quantise with (None: this
+    panel's own, or ``out``'s)."""
+    require_gpu()
+    _even_n_hap("ld_grm", panel)
+    if out is not None:
+        if not isinstance(out, GrmResult) or out.counts is None or out.n_ind != panel.n_ind:
+            raise _lib.LdxError(f"ld_grm: out must be an earlier ld_grm result of the same {panel.n_ind} individuals")
+        if exp is not None and int(exp) != out.exp:
+            raise _lib.LdxError(f"ld_grm: exp {exp} beside out's exponent {out.exp}")
+        exp = out.exp
+    keep_d = _keep_dev(keep, panel.n_snps, panel.device)
+    q, e, live = grm_weights(_snp_counts(panel, keep_d), None, maf_min, exp)
+    S = sample_wprod(panel, q, keep=live, out=None if out is None else out.S)
+    counts = sample_counts(panel, keep=live, out=None if out is None else out.counts)
+    return GrmResult(S, counts.n, e, int(live.sum()) + (0 if out is None else out.n_live), counts)
+
+
+def ld_grm_host(codes, keep=None, maf_min: Optional[float] = None, exp: Optional[int] = None) -> GrmResult:
+    """Host mirror of ld_grm on the allele codes [n_snps, n_hap], all numpy: the same integers, and ``grm()`` the same bits."""
+    q, e, live = grm_weights(geno_counts_host(codes, keep), None, maf_min, exp)
+    S = sample_wprod_host(codes, q, keep=live)
+    N = sample_counts_host(codes, keep=live)[0]
+    return GrmResult(S, N, e, int(live.sum()))
+
+
+def grm_cutoff(grm, cutoff: float) -> Tuple[np.ndarray, np.ndarray]:
+    """gcta --grm-cutoff: a maximal set of individuals no two of which have a relationship above ``cutoff`` -- king_cutoff's
+    greedy rule on this matrix.  Returns (keep bool [n_ind], removed_because_of int64 [n_ind])."""
+    return king_cutoff(grm, cutoff)
 
 
 # --------------------------------------------------------------------------- linear association scan
